@@ -30,10 +30,9 @@ import tempfile
 import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
-# The pipeline keeps a front stream and up to three coder streams busy at once: HIP maps streams onto GPU_MAX_HW_QUEUES
-# hardware queues (default 4), and two streams that share a queue run one after the other -- a front-stage kernel behind a
-# 0.65 s coder launch.  Must be set before the runtime comes up.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
+# The pipeline keeps a front stream and up to three coder streams busy at once: HIP maps streams onto the hardware queues
+# the runtime gives the process, and two streams that share a queue run one after the other -- a front-stage kernel behind a
+# 0.65 s coder launch.  The number of queues is the machine's setting: bench.py leaves it as it finds it.
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: 8.0 TB/s spec
@@ -66,6 +65,9 @@ def main():
     ap.add_argument("--ref-full-shard", action="store_true",
                     help="also run the reference's own compress() -T 1 on the whole bench shard on this box's host (~5 min for 50 M reads) and "
                          "compare its three archive files with the product's, byte for byte (parity.ref_full_shard)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed -- the archive streams of its shard -- as DIR/<name>.npy "
+                         "(see dump_outputs); that shard reads slot 0's text, whatever the number of shards in flight")
     args = ap.parse_args()
 
     import numpy as np
@@ -187,6 +189,13 @@ def main():
             print("bench: %.0f GB of HBM free: %d shards in flight, %d per coder launch" % (free_b / 1e9, D, G), file=sys.stderr)
     if G > 1:
         D = max(D, 2 * G)
+    warm = max(args.warmup, D) if args.warmup > 0 else 0  # every slot allocates its buffers outside the timed region
+    # --dump-outputs: the slot the last timed step takes (slots go round-robin: `warm` shards, one alone, then the timed ones)
+    dump_slot = None
+    if args.dump_outputs:
+        if sharded or F > 1 or world > 1:
+            sys.exit("bench: --dump-outputs needs the plain one-GPU path (no sharded run, one front thread)")
+        dump_slot = (warm + args.steps) % D
     # slot i reads texts[i]: different seeds, the same record shape (sizes are equal: names and lengths are)
     texts = [text]
     if own_text:
@@ -195,6 +204,8 @@ def main():
             assert texts[-1].numel() == nbytes
     else:
         texts = [text] * D
+    if dump_slot is not None:   # the dumped shard's input must not depend on how many slots the free HBM allowed
+        texts[dump_slot] = text
     # -B: the reference's default, 4 GiB of record bytes per spill chunk (main.cpp:68) -- 50 M reads of 100 bp are 3 chunks
     B = int(os.environ.get("SCALCE_BENCH_BUCKET_SET", str(4 << 30)))
     # the shards in flight share ONE set of front-stage buffers (rows, tokens, events, sort scratch: dead once a shard is
@@ -330,7 +341,6 @@ def main():
         pipe.drain()
 
     torch.cuda.synchronize()  # the synthetic shard was generated on the default stream
-    warm = max(args.warmup, D) if args.warmup > 0 else 0  # every slot allocates its buffers outside the timed region
     run(warm)
     barrier()
     t1 = time.perf_counter()
@@ -354,6 +364,9 @@ def main():
     k = {key: sum(x[key] for x in ks) for key in ks[0]}
     stats = batch.stats()
     out_bytes = sum(batch.output_ptr(w, 0)[1] for w in (host.OUT_READS, host.OUT_NAMES, host.OUT_QUAL))
+    if dump_slot is not None:
+        assert (pipe._next - 1) % DF == dump_slot, "the last timed step did not take the slot --dump-outputs expected"
+        dump_outputs(batches[dump_slot], args.dump_outputs)
 
     # ---- the run proves its own output (never inside the timed region) ----
     parity = {}
@@ -621,6 +634,31 @@ def main():
     if world > 1:
         dist.barrier()   # (rank 0's CPU leg and checks run while the others wait here)
         dist.destroy_process_group()
+
+
+def dump_outputs(batch, d, sample=1 << 21, chunk=1 << 20, seed=20261015):
+    """--dump-outputs: the archive streams of `batch`'s shard, what a caller of the hot path receives -- .scalcer (OUT_READS),
+    .scalcen (OUT_NAMES), .scalceq (OUT_TABLE + OUT_QUAL) -- as .npy files in d.  The streams are GBs, so each is written as
+      <s>_bytes.npy       [its length in bytes] (float64)
+      <s>_chunk_sums.npy  the sum of every `chunk` bytes, the last chunk possibly shorter (float64: exact up to 2^53)
+      <s>_sample.npy      its bytes at `sample` positions drawn with a fixed seed from its length, in ascending order (float32)
+    for s in reads, names, qual, and qual_table.npy holds the quality model's table whole (float64).  About 30 MB in all."""
+    import numpy as np
+    from scalce_amd import host
+    os.makedirs(d, exist_ok=True)
+    for name, which in (("reads", host.OUT_READS), ("names", host.OUT_NAMES), ("qual", host.OUT_QUAL)):
+        a = batch.output(which, 0)
+        n = len(a)
+        whole = n // chunk * chunk
+        sums = a[:whole].reshape(-1, chunk).sum(axis=1, dtype=np.uint64)
+        if whole < n:
+            sums = np.append(sums, a[whole:].sum(dtype=np.uint64))
+        pos = np.sort(np.random.default_rng(seed).integers(0, n, sample)) if n > sample else np.arange(n)
+        np.save(os.path.join(d, name + "_bytes.npy"), np.array([n], dtype=np.float64))
+        np.save(os.path.join(d, name + "_chunk_sums.npy"), sums.astype(np.float64))
+        np.save(os.path.join(d, name + "_sample.npy"), a[pos].astype(np.float32))
+        del a
+    np.save(os.path.join(d, "qual_table.npy"), batch.output(host.OUT_TABLE, 0, np.uint32).astype(np.float64))
 
 
 def end_to_end(text, nbytes):

@@ -6,7 +6,8 @@
 // NEXT shards run on one stream beside the coder launches of the previous ones on others.  What the measurements on MI355X
 // fixed:
 //   * one front stream and `coder_streams` coder streams: HIP maps streams onto a handful of hardware queues, and a read-back
-//     that lands in a queue behind a 0.5 s coder kernel waits for all of it (callers set GPU_MAX_HW_QUEUES=8);
+//     that lands in a queue behind a 0.5 s coder kernel waits for all of it (how many queues a process gets is the runtime's
+//     setting, not the library's);
 //   * a launch takes `group` shards (scalce_batch_entropy_begin_group); consecutive launches rotate over the coder streams
 //     and run side by side;
 //   * a shard is retired on an EVENT recorded behind its coder launch and collected over the FRONT stream;
