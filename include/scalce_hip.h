@@ -233,11 +233,10 @@ int scalce_batch_entropy_end(scalce_batch *b, void *stream);
  * enqueued on stream.  Each shard is completed by its own scalce_batch_entropy_end / scalce_batch_finish (on any
  * stream, after `stream` has reached the end of the launch). */
 int scalce_batch_entropy_begin_group(scalce_batch **batches, int n, void *prep_stream, void *stream);
+#define SCALCE_GROUP_MAX 16  /* shards per grouped launch (n), and so the largest `group` of scalce_pipeline_create */
 /* The same for the LAST launch of a run (last == 1: nothing will be queued behind it): picks the coder kernel by how soon
- * the launch is done instead of by how few CUs it holds beside the next shards' front stages.  last == 2: a launch of one
- * or two shards at the START of a run, with more shards on their way: the kernel that holds the fewest CUs whatever the
- * size of the launch.  last == 3: one of the last launches of a run, a front stage or two still to come: a kernel between
- * the two (eight blocks per chain wave for up to 1024 blocks).  Same bytes. */
+ * the launch is done instead of by how few CUs it holds beside the next shards' front stages.  last == 0 is
+ * scalce_batch_entropy_begin_group; any other value is SCALCE_ERR_ARG.  Same bytes. */
 int scalce_batch_entropy_begin_group_last(scalce_batch **batches, int n, void *prep_stream, void *stream, int last);
 /* Sharded runs: code a caller-assembled range of the run-wide reordered stream (it must start on a 10 MiB
  * block boundary) against the run-wide table; result in SCALCE_OUT_QUAL of `mate`. */
@@ -428,9 +427,9 @@ int scalce_shard_plan_blocks(int world, int rank, uint32_t nb1, const uint64_t *
  *                       scalce_pipeline_submit(p, slot, flush_now, &launched);
  *     scalce_pipeline_drain(p);          (the caller walks the slots for their outputs, or retires them one by one before)
  * flush_now: 0 = the launch goes out when `group` shards are pending; 1 = what is pending goes out now and nothing will run
- * beside it (the end of a run, or a wave that fills every slot -- `group` may be as large as nslots for a caller that plans
- * its launches): it is shaped for its own latency, on every CU; 2 = it goes out now, front stages of further shards follow
- * beside it.  A coder launch takes ~0.5 s whether it holds five 50 M-read shards or fifteen: a caller that knows the length
+ * beside it (the end of a run, or a wave that fills every slot -- `group` may be as large as nslots, up to SCALCE_GROUP_MAX,
+ * for a caller that plans its launches): it is shaped for its own latency, on every CU; 2 = it goes out now, front stages of
+ * further shards follow beside it.  A coder launch takes ~0.5 s whether it holds five 50 M-read shards or fifteen: a caller that knows the length
  * of its run puts the remainder first and then launches whole waves (bench.py --launch-plan waves). */
 typedef struct scalce_pipeline scalce_pipeline;
 int scalce_pipeline_create(scalce_batch **batches, int nslots, int group, int coder_streams, int external_coder, scalce_pipeline **out);

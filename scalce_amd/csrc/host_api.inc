@@ -12,10 +12,10 @@ extern "C" int scalce_batch_compress(scalce_batch *b, const uint8_t *t1, uint64_
   return SCALCE_OK;
 }
 
-// Every stage in front of the entropy coder (ingest .. emit) of a shard that is resident as text, on `stream`.
-// (Round 5 ran the quality statistics on a second stream beside the tie-break's windows -- a few hundred launches of ~13 us that
-// leave most of the chip idle: 73.97 against 74.04 ms per shard in the bench, as in round 3.  What the windows leave idle the coder
-// launches of the other shards in flight already use.  One stream.)
+// Every stage in front of the entropy coder (ingest .. emit) of a shard that is resident as text, on `stream` -- except the
+// quality statistics, which the tokenizer forks onto the workspace's side stream beside the tie-break's window sweeps
+// (quality_beside, host_tokenize.inc: ev_fork, then ev_side behind the statistics); `stream` waits for ev_side before it
+// returns, so everything behind this call sees the statistics.  With stage times taken, or -A, they stay on `stream`.
 extern "C" int scalce_batch_front(scalce_batch *b, const uint8_t *t1, uint64_t n1, const uint8_t *t2, uint64_t n2, void *stream) {
   if (!b) return SCALCE_ERR_ARG;
   int rc;

@@ -70,29 +70,89 @@ static int ac_prepare(AcJob &j, hipStream_t s, bool framed_output = true, bool f
   return SCALCE_OK;
 }
 
+// The shape of a coder launch -- which kernel runs, how many blocks each workgroup takes, how many lanes of
+// ac_encode_lanes_k hold a block -- is decided here and nowhere else:
+//
+//   launch                                    blocks per workgroup
+//   AC_SINGLE     (encode_stream)             SCALCE_AC_BLOCKS_PER_WG if set (4, 8, 64), else 1 = ac_encode_k, one job only
+//   AC_PAIRED     (both mates, one launch)    <= 1024 blocks: 4, else 8 (with the override set each mate is an AC_SINGLE launch)
+//   AC_RECODE     (entropy_recode_full)       <= 1024: 4, else 8; the override is ignored
+//   AC_WINDOW     (entropy_windowed)          8; the override is ignored
+//   AC_GROUP(_LAST) (grouped launch)          < 900: 4, else 64; AC_GROUP_LAST with 900 .. 2048 blocks: 8; the override replaces it
+//   any launch at 64 that needs the general step: 8 (one block per lane only follows the reference while no interval can
+//   invert, kernels_acl.hpp)
+//
+//   lanes per workgroup (64 only): SCALCE_AC_LANES_USED if set (ac_lanes_override); else AC_GROUP_LAST:
+//   clamp(ceil(blocks / CUs), 8, 64), the others 32.  ac_launch runs rows of up to 48 lanes as <true, 1, 48, 5>, wider
+//   ones as <true, 1, 64, 5>.
+//
+// One block per workgroup has the lowest latency of a block; four take 0.57 x the SIMD time per block at 1.2 x the
+// latency.  Paired reads: both mates' streams in ONE launch instead of two launches of the one-block kernel behind each
+// other -- the same chip, half the time.  Grouped launches: as few blocks per workgroup as keep the launch at one
+// workgroup per CU (256 CUs), so that every chain wave has a SIMD of its own -- one shard (477 blocks at 50 M x 100) at
+// four; from two shards on one block per LANE: the launch then takes ~0.56 s whatever its size, but on a sixth of the SIMD
+// time per block, and the front stages of the next shards keep the chip (DESIGN.md section 5).  The last launch of a run
+// (nothing is queued behind it) is judged by how soon it is done, not by how few CUs it holds: eight blocks per chain wave
+// (0.36-0.47 s for up to 2048 blocks) instead of one block per lane (0.56-0.65 s), and one block per lane beyond that on
+// every CU with as few blocks per workgroup as that allows (0.45 s at 24, 0.47 at 32, 0.50 at 40).
+enum AcLaunchKind { AC_SINGLE, AC_PAIRED, AC_RECODE, AC_WINDOW, AC_GROUP, AC_GROUP_LAST };
+struct AcShape {
+  int blocks_per_wg;  // 1 = ac_encode_k, 4 / 8 = ac_encode_rows_k, 64 = ac_encode_lanes_k (one block per lane)
+  u32 lanes;          // ac_encode_lanes_k: blocks per workgroup
+};
+
+// SCALCE_AC_BLOCKS_PER_WG (tests, tools/coder_alone.py): 4, 8 or 64; 0 = no override
+static int ac_blocks_override() {
+  const char *e = getenv("SCALCE_AC_BLOCKS_PER_WG");
+  const int v = e ? atoi(e) : 0;
+  return (v == 4 || v == 8 || v == 64) ? v : 0;
+}
+
 // Blocks per workgroup of ac_encode_lanes_k.  A lane per block would be 64; the default is fewer: all table rows of a
 // workgroup's blocks go through ONE CU's vector memory pipeline (1024 scattered 16-byte reads per 0.75 us round at 64), and
 // beside another shard's streaming front stages -- when an L2 miss takes three times as long -- that pipeline, not the coder,
 // set the pace of a launch: 908 ms beside the ingest stage and 1299 ms beside the order stage at 64 blocks per workgroup
 // against 575 / 694 ms at 32 and 560 / 559 ms at 16 (543 ms alone; tools/coder_beside.py).  Fewer blocks per workgroup
 // are more CUs held per launch, CUs the front stages of the next shards do not get: in round 3's mix 48 was the best
-// trade (ms per shard at 32 / 40 / 48 / 56 / 64 blocks: 107.0 / 106.6 / 102.4 / 108.0 / 115.5; DESIGN.md section 7); since
-// round 4 the default is 40 (below).
-static u32 ac_lanes_used() {
+// trade (ms per shard at 32 / 40 / 48 / 56 / 64 blocks: 107.0 / 106.6 / 102.4 / 108.0 / 115.5; DESIGN.md section 7).
+// Round 4 (twelve slots, block buffers of their own): 79.9 / 80.0 / 81.1 / 81.7 / 82.2 / 85.6 ms per shard at 32 / 36 / 40 /
+// 44 / 48 / 56, 40 the default.  Round 5 (fifteen slots, coded in place, six shards per launch on two streams;
+// tools/r5_sweep.sh): 79.3 / 79.6 / 74.0 / 74.6 / 75.2 / 77.9 / 81.8 at 24 / 28 / 32 / 36 / 40 / 48 / 56 -- a launch takes
+// 0.47 s at 32 against 0.50 at 40, and with slots to spare the pipeline follows the launch's latency: 32.
+// SCALCE_AC_LANES_USED overrides it (1 .. 64; anything else is 32); 0 = not set.
+static u32 ac_lanes_override() {
   const char *e = getenv("SCALCE_AC_LANES_USED");
-  // round 4 (twelve slots, block buffers of their own): 79.9 / 80.0 / 81.1 / 81.7 / 82.2 / 85.6 ms per shard at 32 / 36 / 40 / 44 / 48 / 56,
-  // 40 the default.  Round 5 (fifteen slots, coded in place, six shards per launch on two streams; tools/r5_sweep.sh): 79.3 / 79.6 /
-  // 74.0 / 74.6 / 75.2 / 77.9 / 81.8 at 24 / 28 / 32 / 36 / 40 / 48 / 56 -- a launch takes 0.47 s at 32 against 0.50 at 40, and with
-  // slots to spare the pipeline follows the launch's latency: 32.
-  const int v = e ? atoi(e) : 32;
+  if (!e) return 0;
+  const int v = atoi(e);
   return (u32)(v < 1 || v > 64 ? 32 : v);
 }
 
-// ONE launch over the blocks of all jobs.  blocks_per_wg: 1 = ac_encode_k (one job only), 4 / 8 = ac_encode_rows_k,
-// 64 = ac_encode_lanes_k (one block per lane).
+static AcShape ac_shape(AcLaunchKind kind, u32 blocks, bool general, int device) {
+  const int over = ac_blocks_override();
+  int bpw;
+  switch (kind) {
+    case AC_SINGLE: bpw = over ? over : 1; break;
+    case AC_PAIRED:
+    case AC_RECODE: bpw = blocks <= 1024 ? 4 : 8; break;
+    case AC_WINDOW: bpw = 8; break;
+    default:
+      bpw = blocks < 900 ? 4 : (kind == AC_GROUP_LAST && blocks <= 2048) ? 8 : 64;
+      if (over) bpw = over;
+  }
+  if (bpw == 64 && general) bpw = 8;
+  u32 lanes = ac_lanes_override();
+  if (!lanes && kind == AC_GROUP_LAST && bpw == 64) {
+    static int n_cus = 0;
+    if (!n_cus) { hipDeviceProp_t pr; n_cus = hipGetDeviceProperties(&pr, device) == hipSuccess && pr.multiProcessorCount > 0 ? pr.multiProcessorCount : 256; }
+    lanes = std::min<u32>(std::max<u32>(cdiv(blocks, (u32)n_cus), 8u), 64u);
+  }
+  return AcShape{bpw, lanes ? lanes : 32u};
+}
+
+// ONE launch over the blocks of all jobs, in the shape ac_shape gives `kind`.
 // `ps` = the stream the tables were prepared on: the block descriptors are uploaded there (never behind a coder that
 // is still running on `s`), and `s` is made to wait for it.
-static int ac_launch(AcJob *jobs, int njobs, int blocks_per_wg, hipStream_t s, hipStream_t ps, u32 lanes_per_wg = 0) {
+static int ac_launch(AcJob *jobs, int njobs, AcLaunchKind kind, hipStream_t s, hipStream_t ps) {
   scalce_batch *lead = jobs[0].b;
   scalce_ctx *c = lead->ctx;
   u32 total = 0;
@@ -104,6 +164,7 @@ static int ac_launch(AcJob *jobs, int njobs, int blocks_per_wg, hipStream_t s, h
     if (jobs[i].max_total > (1u << 29)) general = true;
   }
   if (!total) return SCALCE_OK;
+  const AcShape shape = ac_shape(kind, total, general, c->device);
   AcEncArgs a;
   memset(&a, 0, sizeof a);
   a.slow_threshold = 32;
@@ -132,27 +193,17 @@ static int ac_launch(AcJob *jobs, int njobs, int blocks_per_wg, hipStream_t s, h
     ke0 = lead->kev[lead->kev_used].first; ke1 = lead->kev[lead->kev_used].second;
     lead->kev_used++;
   }
-  if (blocks_per_wg == 1) {
+  if (shape.blocks_per_wg == 1) {
     if (njobs != 1) { set_err(c, "internal: ac_encode_k takes one job"); return SCALCE_ERR_ARG; }
     scalce_batch *b = jobs[0].b;
     const int m = jobs[0].m;
     a.sym = jobs[0].sym; a.nsym = jobs[0].nsym; a.tab = b->ac_tab[m].as<uint4>(); a.out = b->ac_base[m];
     a.out_stride = b->ac_stride[m]; a.out_cap = (u32)b->ac_stride[m]; a.out_size = b->ac_sizes[m].as<u32>(); a.err = b->d_err;
-    if (getenv("SCALCE_AC_PROF")) { HIP_TRY(c, hipMalloc(&a.prof, sizeof(u64) * 3 * total)); }
     { int rc = join(); if (rc) return rc; }
     if (ke0) hipEventRecord(ke0, s);
     if (general) LAUNCH(ac_encode_k<true>, total, 128, 0, s, a);
     else LAUNCH(ac_encode_k<false>, total, 128, 0, s, a);
     if (ke1) hipEventRecord(ke1, s);
-    if (a.prof) {  // profiling only: where do the chain wave's cycles go (shader clock)
-      std::vector<u64> h(3 * (size_t)total);
-      HIP_TRY(c, hipMemcpy(h.data(), a.prof, sizeof(u64) * h.size(), hipMemcpyDeviceToHost));
-      double sys = 0, tot = 0, rounds = 0;
-      for (u32 i = 0; i < total; i++) { sys += h[3 * i]; tot += h[3 * i + 1]; rounds += h[3 * i + 2]; }
-      fprintf(stderr, "ac prof: %u blocks, per plain round: %.1f cycles in the 64 steps, %.1f cycles in all (%.0f plain rounds per block)\n",
-              total, sys / rounds, tot / rounds, rounds / total);
-      hipFree(a.prof);
-    }
   } else {
     // block descriptors: the launch may hold blocks of several shards, each with its own table and output
     if (total > lead->ac_desc_cap) {
@@ -165,9 +216,7 @@ static int ac_launch(AcJob *jobs, int njobs, int blocks_per_wg, hipStream_t s, h
       HIP_TRY(c, hipHostMalloc(reinterpret_cast<void **>(&lead->ac_desc_host), sizeof(AcBlockDesc) * (size_t)cap, hipHostMallocDefault));
       lead->ac_desc_cap = cap;
     }
-    // one block per lane only follows the reference while no interval can invert (kernels_acl.hpp)
-    if (blocks_per_wg == 64 && general) blocks_per_wg = 8;
-    const bool lanes = blocks_per_wg == 64;  // gathers from the compact table
+    const bool lanes = shape.blocks_per_wg == 64;  // gathers from the compact table
     AcBlockDesc *d = lead->ac_desc_host;
     u32 nd = 0;
     for (int i = 0; i < njobs; i++) {
@@ -202,17 +251,14 @@ static int ac_launch(AcJob *jobs, int njobs, int blocks_per_wg, hipStream_t s, h
     a.out_cap = (u32)AC_STRIDE;
     { int rc = join(); if (rc) return rc; }
     if (ke0) hipEventRecord(ke0, s);
-    if (!lanes_per_wg || getenv("SCALCE_AC_LANES_USED")) lanes_per_wg = ac_lanes_used();  // (blocks per workgroup of the one-block-per-lane kernel)
-    const u32 nwg = cdiv(total, blocks_per_wg == 64 ? lanes_per_wg : (u32)blocks_per_wg);
-    if (getenv("SCALCE_AC_PROF")) { HIP_TRY(c, hipMalloc(&a.prof, sizeof(u64) * 5 * (nwg + 2))); HIP_TRY(c, hipMemset(a.prof, 0, sizeof(u64) * 5 * (nwg + 2))); }
-    if (blocks_per_wg == 64) {
-      a.lanes_used = lanes_per_wg;
+    if (lanes) {
+      a.lanes_used = shape.lanes;
       // (two sets of four waves per CU -- a chain or sink sharing its SIMD with a light wave of the other set -- cost a third fewer
       //  CU-seconds and 35 % more latency per launch: 98 against 75 ms per shard with fifteen slots, round 5; waves on shared CUs at
       //  raised priority: +5 %, round 3.  Both removed.)
       if (a.lanes_used <= 48) LAUNCH((ac_encode_lanes_k<true, 1, 48, 5>), cdiv(total, a.lanes_used), 256, 0, s, a);  // (rows of 48: LDS for a longer staging ring)
       else LAUNCH((ac_encode_lanes_k<true, 1, 64, 5>), cdiv(total, a.lanes_used), 256, 0, s, a);
-    } else if (blocks_per_wg == 8) {
+    } else if (shape.blocks_per_wg == 8) {
       if (general) LAUNCH((ac_encode_rows_k<true, 8>), cdiv(total, 8), 320, 0, s, a);
       else LAUNCH((ac_encode_rows_k<false, 8>), cdiv(total, 8), 320, 0, s, a);
     } else {
@@ -220,11 +266,6 @@ static int ac_launch(AcJob *jobs, int njobs, int blocks_per_wg, hipStream_t s, h
       else LAUNCH((ac_encode_rows_k<false, 16>), cdiv(total, 4), 192, 0, s, a);
     }
     if (ke1) hipEventRecord(ke1, s);
-    if (a.prof) {  // profiling only: read back when the lead shard is collected (the launch keeps running beside others)
-      lead->prof_ptr = a.prof;
-      lead->prof_n = nwg;
-      lead->prof_lanes = blocks_per_wg == 64;
-    }
   }
   for (int i = 0; i < njobs; i++) {
     lead->k_in_bytes += jobs[i].nsym;
@@ -235,7 +276,6 @@ static int ac_launch(AcJob *jobs, int njobs, int blocks_per_wg, hipStream_t s, h
 }
 
 // framing: sizes -> offsets -> [u32 size][bytes] per block, all enqueued; the total is read back by entropy_collect
-static bool frames_at_collect() { return true; }  // (behind the coder on its own stream: measured slower, DESIGN.md appendix)
 static int ac_frame(AcJob &j, hipStream_t s) {
   scalce_batch *b = j.b;
   const int m = j.m;
@@ -262,20 +302,13 @@ static int ac_frame(AcJob &j, hipStream_t s) {
   return SCALCE_OK;
 }
 
-static int ac_blocks_per_wg() {
-  // one block per workgroup (lowest latency of a block) or four (0.57 x the SIMD time per block, 1.2 x the latency)
-  const char *bpw = getenv("SCALCE_AC_BLOCKS_PER_WG");
-  const int v = bpw ? atoi(bpw) : 1;
-  return (v == 4 || v == 8 || v == 64) ? v : 1;
-}
-
 // Code one mate's symbol stream `d_sym` (nsym symbols, first symbol = start of a 10 MiB block of the run-wide
 // stream) against `table` (device, 512000 x u32, already scaled).
 static int encode_stream(scalce_batch *b, int m, const u8 *d_sym, u64 nsym, hipStream_t s) {
   AcJob j{b, m, d_sym, nsym, 0, false};
   int rc = ac_prepare(j, s);
   if (rc) return rc;
-  if ((rc = ac_launch(&j, 1, ac_blocks_per_wg(), s, s))) return rc;
+  if ((rc = ac_launch(&j, 1, AC_SINGLE, s, s))) return rc;
   return ac_frame(j, s);
 }
 
@@ -291,9 +324,7 @@ static int entropy_recode_full(scalce_batch *b, hipStream_t s) {
     jobs.push_back(j);
   }
   if (jobs.empty()) return SCALCE_OK;
-  u32 total = 0;
-  for (auto &j : jobs) total += j.nblk;
-  int rc = ac_launch(jobs.data(), (int)jobs.size(), total <= 1024 ? 4 : 8, s, s);
+  int rc = ac_launch(jobs.data(), (int)jobs.size(), AC_RECODE, s, s);
   if (rc) return rc;
   for (auto &j : jobs) { b->frame_deferred[j.m] = j.nblk; b->ent_pending[j.m] = 0; }
   return SCALCE_OK;
@@ -346,25 +377,6 @@ static int entropy_collect(scalce_batch *b, hipStream_t s) {
         if (rc) return rc;
       }
     }
-  }
-  if (b->prof_ptr) {  // profiling only: share of the chain waves' time spent waiting at the barrier
-    std::vector<u64> h(5 * (size_t)b->prof_n);
-    HIP_TRY(b->ctx, hipMemcpy(h.data(), b->prof_ptr, sizeof(u64) * h.size(), hipMemcpyDeviceToHost));
-    double wait = 0, tot = 0, hwait = 0, htot = 0;
-    for (u32 i = 0; i < b->prof_n; i++) { wait += h[5 * i]; tot += h[5 * i + 1]; hwait += h[5 * i + 3]; htot += h[5 * i + 4]; }
-    fprintf(stderr, "ac prof (rows): %u workgroups, chain waves waited at the barrier %.1f %% of their time (%.0f of %.0f Mcycles each), "
-            "the first helper wave %.1f %%\n",
-            b->prof_n, 100.0 * wait / tot, wait / b->prof_n / 1e6, tot / b->prof_n / 1e6, 100.0 * hwait / (htot > 0 ? htot : 1));
-    if (b->prof_lanes) {
-      fprintf(stderr, "ac prof (lanes): SIMD of chain / gather / sink / writer per workgroup:");
-      for (u32 i = 0; i < b->prof_n && i < 24; i++) fprintf(stderr, " %llu%llu%llu%llu", h[5 * i + 2] & 15, (h[5 * i + 2] >> 4) & 15, (h[5 * i + 2] >> 8) & 15, (h[5 * i + 2] >> 12) & 15);
-      fprintf(stderr, "\n");
-    }
-    if (b->prof_lanes)
-      fprintf(stderr, "ac prof (lanes): of the chain wave's %.0f Mcycles the gather wave waited at the barrier %.1f %%, the sink wave %.1f %%\n",
-              tot / b->prof_n / 1e6, 100.0 * hwait / tot, 100.0 * htot / tot);
-    hipFree(b->prof_ptr);
-    b->prof_ptr = nullptr;
   }
   for (int m = 0; m < b->nm; m++) {
     if (b->frame_deferred[m]) {
@@ -436,7 +448,7 @@ static int entropy_windowed(scalce_batch *b, const uint32_t *d_table_override, h
       nj++;
     }
     if (!nj) break;
-    int rc = ac_launch(jobs, nj, 8, s, s);
+    int rc = ac_launch(jobs, nj, AC_WINDOW, s, s);
     if (rc) return rc;
     for (int i = 0; i < nj; i++) {
       const int m = jobs[i].m;
@@ -472,20 +484,16 @@ extern "C" int scalce_batch_entropy_begin(scalce_batch *b, const uint32_t *d_tab
     for (int m = 0; m < b->nm; m++) blocks += cdiv(N * (u64)b->L[m], AC_BLOCK_SYMS);
     if (blocks > AC_WINDOW_BLOCKS || getenv("SCALCE_AC_WINDOW_BLOCKS")) return entropy_windowed(b, d_table_override, s);  // (the variable: a test hook)
   }
-  if (b->nm == 2 && !b->p.no_ac && ac_blocks_per_wg() == 1) {
-    // paired reads: both mates' streams in ONE launch (several blocks per chain wave) instead of two launches of the
-    // one-block kernel behind each other -- the same chip, half the time
+  if (b->nm == 2 && !b->p.no_ac && !ac_blocks_override()) {  // paired reads: both mates' streams in ONE launch (ac_shape)
     AcJob jobs[2];
-    u32 total = 0;
     for (int m = 0; m < 2; m++) {
       const u64 nsym = N * (u64)b->L[m];
       int rc = ac_table_for(b, m, d_table_override, nsym, s);
       if (rc) return rc;
       jobs[m] = AcJob{b, m, b->qs(m).as<u8>(), nsym, 0, false};
       if ((rc = ac_prepare(jobs[m], s))) return rc;
-      total += jobs[m].nblk;
     }
-    int rc = ac_launch(jobs, 2, total <= 4 * 256 ? 4 : 8, s, s);
+    int rc = ac_launch(jobs, 2, AC_PAIRED, s, s);
     if (rc) return rc;
     for (int m = 0; m < 2; m++)
       if ((rc = ac_frame(jobs[m], s))) return rc;
@@ -514,10 +522,13 @@ extern "C" int scalce_batch_entropy_begin(scalce_batch *b, const uint32_t *d_tab
 extern "C" int scalce_batch_entropy_begin_group(scalce_batch **bs, int n, void *prep_stream, void *stream) {
   return scalce_batch_entropy_begin_group_last(bs, n, prep_stream, stream, 0);
 }
-// last != 0: nothing will be queued behind this launch (the end of a run): what counts is how soon it is done, not how few
-// CUs it holds -- eight blocks per chain wave (0.36-0.47 s for up to 2048 blocks) instead of one block per lane (0.56-0.65 s)
+// last = 1: nothing will be queued behind this launch (the end of a run, or a wave of shards behind whose front stages
+// nothing is waiting); 0: more shards follow (ac_shape).  The framing ([u32 size][bytes] per block: a scan of the sizes +
+// one copy kernel, ~1.5 ms per 50 M-read shard on an idle chip) is left to entropy_collect, i.e. to the stream the caller
+// collects on: behind the coder on its own stream it was measured slower with one coder stream (it lengthens the launch
+// the pipeline waits for) and with three (95.6 against 93.0 ms per shard).
 extern "C" int scalce_batch_entropy_begin_group_last(scalce_batch **bs, int n, void *prep_stream, void *stream, int last) {
-  if (!bs || n <= 0 || n > 16) return SCALCE_ERR_ARG;
+  if (!bs || n <= 0 || n > SCALCE_GROUP_MAX || (last != 0 && last != 1)) return SCALCE_ERR_ARG;
   for (int i = 0; i < n; i++) if (!bs[i] || bs[i]->ctx != bs[0]->ctx) return SCALCE_ERR_ARG;
   hipStream_t ps = (hipStream_t)prep_stream, s = (hipStream_t)stream;
   scalce_ctx *c = bs[0]->ctx;
@@ -531,49 +542,15 @@ extern "C" int scalce_batch_entropy_begin_group_last(scalce_batch **bs, int n, v
       AcJob j{b, m, b->ent_external[m] ? b->ent_sym[m] : b->qs(m).as<u8>(), b->ent_external[m] ? b->ent_nsym[m] : own, 0, false};
       if (!b->ent_external[m]) { int rc = ac_table_for(b, m, nullptr, own, ps); if (rc) return rc; }
       b->ent_external[m] = false;
-      int rc = ac_prepare(j, ps, /*framed_output=*/!frames_at_collect(), /*full_stride=*/false, /*allow_in_place=*/true);
+      int rc = ac_prepare(j, ps, /*framed_output=*/false, /*full_stride=*/false, /*allow_in_place=*/true);
       if (rc) return rc;
       jobs.push_back(j);
     }
   }
   if (jobs.empty()) return SCALCE_OK;
-  // blocks per workgroup: as few as keep the launch at one workgroup per CU (256 CUs), so that every coder wave has
-  // a SIMD to itself -- four for up to two 50 M-read shards, eight beyond
-  u32 total = 0;
-  for (auto &j : jobs) total += j.nblk;
-  // one shard (477 blocks at 50 M x 100): four blocks per chain wave, the lowest latency that still leaves every chain wave a
-  // SIMD of its own; from two shards on one block per LANE -- the launch then takes ~0.56 s whatever its size, but on a
-  // sixth of the SIMD time per block, and the front stages of the next shards keep the chip (DESIGN.md section 5)
-  // last == 2: a small launch at the START of a run (more shards are on their way: the CUs belong to their front stages):
-  // one block per lane whatever the size
-  // last == 3: one of the last launches of a run, with a front stage or two still to come: eight blocks per chain wave (60 CUs
-  // per 50 M-read shard for ~0.4 s) -- sooner done than one block per lane, and not the whole chip
-  int bpw = (total < 900 && last != 2 && last != 3) ? 4 : 64;
-  if ((last == 1 && total >= 900 && total <= 2048) || (last == 3 && total <= 1024)) bpw = 8;
-  if (ac_blocks_per_wg() != 1) bpw = ac_blocks_per_wg();
-
-  // A launch that has the chip to itself (last == 1: the end of a run, or a wave of shards behind whose front stages nothing
-  // is waiting) takes every CU with as few blocks per workgroup as that allows: a launch's time grows with the blocks a
-  // chain wave carries (0.45 s at 24, 0.47 at 32, 0.50 at 40), the CUs it leaves idle are nobody's.
-  u32 lanes = 0;
-  if (last == 1 && bpw == 64) {
-    static int n_cus = 0;
-    if (!n_cus) { hipDeviceProp_t pr; n_cus = hipGetDeviceProperties(&pr, c->device) == hipSuccess && pr.multiProcessorCount > 0 ? pr.multiProcessorCount : 256; }
-    lanes = cdiv(total, (u32)n_cus);
-    lanes = lanes < 8 ? 8u : lanes > 64 ? 64u : lanes;
-  }
-  int rc = ac_launch(jobs.data(), (int)jobs.size(), bpw, s, ps, lanes);
+  int rc = ac_launch(jobs.data(), (int)jobs.size(), last ? AC_GROUP_LAST : AC_GROUP, s, ps);
   if (rc) return rc;
-  // The framing ([u32 size][bytes] per block: a scan of the sizes + one copy kernel, ~1.5 ms per 50 M-read shard on an
-  // idle chip) is left to entropy_collect, i.e. to the stream the caller collects on.  Behind the coder on its own stream
-  // (SCALCE_AC_FRAME_BEHIND_CODER=1) it was measured slower with one coder stream (it lengthens the launch the pipeline
-  // waits for) and with three (95.6 against 93.0 ms per shard).
-  const bool at_collect = frames_at_collect();
-  for (auto &j : jobs) {
-    if (at_collect) { j.b->frame_deferred[j.m] = j.nblk; continue; }
-    rc = ac_frame(j, s);
-    if (rc) return rc;
-  }
+  for (auto &j : jobs) j.b->frame_deferred[j.m] = j.nblk;
   return SCALCE_OK;
 }
 

@@ -430,9 +430,6 @@ struct scalce_batch {
   size_t kev_used = 0;
   u64 k_in_bytes = 0, k_out_bytes = 0;
   // entropy launched but its result size not read back yet (scalce_batch_entropy_begin / _end): blocks per mate
-  u64 *prof_ptr = nullptr;  // SCALCE_AC_PROF of the last rows-coder launch this shard led
-  u32 prof_n = 0;
-  bool prof_lanes = false;
   u32 ent_pending[2] = {0, 0};
   u32 frame_deferred[2] = {0, 0};  // blocks coded by a grouped launch and not framed yet (entropy_collect frames them)
   // Framing on demand (scalce_batch_set_frame_on_demand): the coded blocks stay where the coder wrote them; entropy_collect

@@ -103,7 +103,6 @@ struct AcEncArgs {
   DevErr *err;
   u32 slow_threshold;  // 32; tests lower it to drive every pending underflow through the serial path
   u32 *simd_load;      // [AC_SIMD_KEYS] coder waves per SIMD of the device, shared by every launch (may be null)
-  u64 *prof;           // profiling only (SCALCE_AC_PROF): per block {cycles in the 64 steps, cycles in the rest of the round, rounds}
   const AcBlockDesc *desc;  // ac_encode_rows_k: one entry per block of the launch
   u32 nblocks;
   u32 chain_prio;      // s_setprio of the chain waves (ac_encode_rows_k)
@@ -594,9 +593,6 @@ __global__ __launch_bounds__(128) void ac_encode_k(AcEncArgs a) {
   sink.wcap = a.out_cap / 4;
   // ---- chain-wave state ----
   u32 lo = 0, hi = 0xFFFFFFFFu;
-
-  u64 prof_sys = 0, prof_rounds = 0;
-  const u64 prof_t0 = a.prof ? __builtin_amdgcn_s_memtime() : 0;
   // ---- operand pipeline (helper wave) ----
   // {g(lo), g(hi)} of the 64 symbols of round rr, lane l serving symbol 64 rr + l.  The context of lane l is the
   // two symbols before it: sy = symbols of round rr (one per lane), sy_prev = those of round rr - 1 for lanes 0, 1.
@@ -698,10 +694,8 @@ __global__ __launch_bounds__(128) void ac_encode_k(AcEncArgs a) {
       bool done = false;
       if (!GENERAL && cur_ok && M0 != 0) {
         SysState st;
-        const u64 pt0 = a.prof ? __builtin_amdgcn_s_memtime() : 0;
         u32 tlo, tM;
         sys_round(st, lo, M0, ops, tlo, tM);
-        if (a.prof) { const u64 pt1 = __builtin_amdgcn_s_memtime(); prof_sys += pt1 - pt0; prof_rounds++; }
         // every lane hands the state it latched in its own step to the helper, which redoes the symbol from it
         const int q = lane & 3;
         const u32 inM = q == 0 ? st.kM[0] : q == 1 ? st.kM[1] : q == 2 ? st.kM[2] : st.kM[3];
@@ -739,11 +733,6 @@ __global__ __launch_bounds__(128) void ac_encode_k(AcEncArgs a) {
       cur_ok = nxt_ok;
       __syncthreads();
     }
-  }
-  if (a.prof && chain_wave && lane == 0) {
-    a.prof[blk * 3 + 0] = prof_sys;
-    a.prof[blk * 3 + 1] = __builtin_amdgcn_s_memtime() - prof_t0;
-    a.prof[blk * 3 + 2] = prof_rounds;
   }
   if (a.simd_load && lane == 0) atomicSub(&a.simd_load[skey], chain_wave ? 4u : 1u);
 }
@@ -839,7 +828,7 @@ __global__ __launch_bounds__(64 * (1 + 32 / R)) void ac_encode_rows_k(AcEncArgs 
 
   if (wv != 0) {
     // ================= helper waves: two blocks each =================
-    // beside other shards' front stages it is the helpers, not the chain, that fall behind (SCALCE_AC_PROF: the chain
+    // beside other shards' front stages it is the helpers, not the chain, that fall behind (shader-clock stamps, DESIGN_HISTORY.md: the chain
     // waves then wait at the barrier for 27 % of their time, 0.9 % alone)
     switch (a.helper_prio) {
       case 1: __builtin_amdgcn_s_setprio(1); break;
@@ -929,8 +918,6 @@ __global__ __launch_bounds__(64 * (1 + 32 / R)) void ac_encode_rows_k(AcEncArgs 
     // there.  (Every later slot is read a whole super-round before it is overwritten; this first hand-over was not, and
     // once the helpers stopped waiting for their loads they could win the race: a block coded wrongly now and then.)
     __syncthreads();
-    u64 hprof_wait = 0;
-    const u64 hprof_t0 = a.prof ? __builtin_amdgcn_s_memtime() : 0;
     auto super_round = [&](auto first, const u32 r, uint4 (&o_use)[2], u32 (&s_use)[2], uint4 (&o_load)[2], u32 (&s_load)[2]) {
 #pragma unroll
       for (int e = 0; e < 2; e++) {
@@ -961,22 +948,12 @@ __global__ __launch_bounds__(64 * (1 + 32 / R)) void ac_encode_rows_k(AcEncArgs 
         hist[e][1] = hist[e][2];
         hist[e][2] = o_use[e];
       }
-      if (a.prof && h == 0) {
-        const u64 w0 = __builtin_amdgcn_s_memtime();
-        barrier_lds_only();
-        hprof_wait += __builtin_amdgcn_s_memtime() - w0;
-      } else {
-        barrier_lds_only();
-      }
+      barrier_lds_only();
     };
     if (nsr) super_round(std::true_type{}, 0u, oA, sA, oB, sB);
     for (u32 r = 1; r < nsr; r += 2) {
       super_round(std::false_type{}, r, oB, sB, oA, sA);
       if (r + 1 < nsr) super_round(std::false_type{}, r + 1, oA, sA, oB, sB);
-    }
-    if (a.prof && h == 0 && lane == 0) {
-      a.prof[blockIdx.x * 5 + 3] = hprof_wait;
-      a.prof[blockIdx.x * 5 + 4] = __builtin_amdgcn_s_memtime() - hprof_t0;
     }
 #pragma unroll
     for (int e = 0; e < 2; e++) {
@@ -1018,8 +995,6 @@ __global__ __launch_bounds__(64 * (1 + 32 / R)) void ac_encode_rows_k(AcEncArgs 
     for (int q = 0; q < NQ; q++) cur[q] = opsb[0][row][q * R + col];
     __syncthreads();  // slot 0 is in registers: the helpers may overwrite it (see their side)
     u32 cur_ok = 0;
-    u64 prof_wait = 0;
-    const u64 prof_t0 = a.prof ? __builtin_amdgcn_s_memtime() : 0;
     for (u32 r = 0; r < nsr; r++) {
       uint4 ops[NQ], nxt[NQ];
 #pragma unroll
@@ -1087,18 +1062,7 @@ __global__ __launch_bounds__(64 * (1 + 32 / R)) void ac_encode_rows_k(AcEncArgs 
 #pragma unroll
       for (int q = 0; q < NQ; q++) cur[q] = nxt[q];
       cur_ok = nxt_ok;
-      if (a.prof) {
-        const u64 w0 = __builtin_amdgcn_s_memtime();
-        __syncthreads();
-        prof_wait += __builtin_amdgcn_s_memtime() - w0;
-      } else {
-        __syncthreads();
-      }
-    }
-    if (a.prof && lane == 0) {
-      a.prof[blockIdx.x * 5 + 0] = prof_wait;
-      a.prof[blockIdx.x * 5 + 1] = __builtin_amdgcn_s_memtime() - prof_t0;
-      a.prof[blockIdx.x * 5 + 2] = nsr;
+      __syncthreads();
     }
   }
 }

@@ -302,8 +302,6 @@ __global__ __launch_bounds__(256 * SETS) void ac_encode_lanes_k(AcEncArgs a) {
     else if (a.helper_prio == 3) __builtin_amdgcn_s_setprio(3);
     else __builtin_amdgcn_s_setprio(2);
   } else __builtin_amdgcn_s_setprio(3);
-  u64 *const prof = a.prof ? a.prof + (size_t)(blockIdx.x * SETS + set) * 5 : nullptr;
-  if (prof && lane == 0) atomicOr((unsigned int *)&prof[2], (simd_key() & 3u) << (4 * role));  // profiling: which SIMD each role runs on
   // lanes beyond LW (SETS == 2) hold no block and must not touch the arrays, whose rows are LW wide
   const bool inrow = LW == 64 || lane < LW;
 
@@ -349,7 +347,6 @@ __global__ __launch_bounds__(256 * SETS) void ac_encode_lanes_k(AcEncArgs a) {
 #pragma unroll
       for (int q = 0; q < 8; q++) c[q] = acl_load16(sym_addr(first + q));
     };
-    u64 gprof_wait = 0;
     if (inrow) {
       load_chunk(ca, 0);
       load_chunk(cb, 8);
@@ -362,13 +359,7 @@ __global__ __launch_bounds__(256 * SETS) void ac_encode_lanes_k(AcEncArgs a) {
       // iteration i: request round i + AHEAD; round i + 1 is in LDS when at most the AHEAD - 1 requests behind it are outstanding
       auto close = [&]() {
         acl_wait_vm<(AHEAD - 1) * 16>();
-        if (prof) {
-          const u64 w0 = __builtin_amdgcn_s_memtime();
-          asm volatile("s_barrier" ::: "memory");
-          gprof_wait += __builtin_amdgcn_s_memtime() - w0;
-        } else {
-          asm volatile("s_barrier" ::: "memory");
-        }
+        asm volatile("s_barrier" ::: "memory");
       };
       for (u32 i0 = 0; i0 < nr_wg; i0 += 16) {
 #pragma unroll
@@ -388,7 +379,6 @@ __global__ __launch_bounds__(256 * SETS) void ac_encode_lanes_k(AcEncArgs a) {
       asm volatile("s_barrier" ::: "memory");  // (the sink's last round)
       asm volatile("s_barrier" ::: "memory");  // (the writer's last words)
     }
-    if (prof && lane == 0) prof[3] = gprof_wait;
   } else if (role == 0) {
     // ================= chain: one coder state per lane =================
     u32 ones, zero;
@@ -396,8 +386,6 @@ __global__ __launch_bounds__(256 * SETS) void ac_encode_lanes_k(AcEncArgs a) {
     asm("v_mov_b32 %0, 0" : "=v"(zero));
     u32 lo = 0, M = 0;  // M = 0 stands for 2^32
     u32 Q = 16;         // stream position of the next B's top bit: the two raw symbols, then every bit dropped
-    u64 prof_wait = 0;
-    const u64 prof_t0 = prof ? __builtin_amdgcn_s_memtime() : 0;
     if (inrow) {
       __syncthreads();  // round 0's operands are in LDS
       for (u32 r = 0; r < nr_wg; r++) {
@@ -447,24 +435,13 @@ __global__ __launch_bounds__(256 * SETS) void ac_encode_lanes_k(AcEncArgs a) {
           }
         }
         if (r + 1 == nr) sh.final_lo[lane] = lo & 0x7FFFFFFFu;
-        if (prof) {
-          const u64 w0 = __builtin_amdgcn_s_memtime();
-          __syncthreads();
-          prof_wait += __builtin_amdgcn_s_memtime() - w0;
-        } else {
-          __syncthreads();
-        }
+        __syncthreads();
       }
       __syncthreads();  // (the sink's last round)
       __syncthreads();  // (the writer's last words)
     }
-    if (prof && lane == 0) {
-      prof[0] = prof_wait;
-      prof[1] = __builtin_amdgcn_s_memtime() - prof_t0;
-    }
   } else if (role == 2) {
     // ================= sink: one bit accumulator per lane, one round behind the chain =================
-    u64 sprof_wait = 0;
     if (inrow) {
       AclSink<LW> sk;
       {
@@ -507,13 +484,7 @@ __global__ __launch_bounds__(256 * SETS) void ac_encode_lanes_k(AcEncArgs a) {
       for (u32 i = 0; i < nr_wg; i++) {  // iteration i: round i - 1
         if (i > 0) take(i - 1);
         sh.pub[i & 1][lane] = sk.final_words();
-        if (prof) {
-          const u64 w0 = __builtin_amdgcn_s_memtime();
-          barrier_lds_only();
-          sprof_wait += __builtin_amdgcn_s_memtime() - w0;
-        } else {
-          barrier_lds_only();
-        }
+        barrier_lds_only();
       }
       take(nr_wg - 1);
       sh.pub[nr_wg & 1][lane] = sk.final_words();
@@ -525,7 +496,6 @@ __global__ __launch_bounds__(256 * SETS) void ac_encode_lanes_k(AcEncArgs a) {
         if (sk.over) dev_fail(dp->err, E_ACOVERFLOW, dp->index, bytes);
       }
     }
-    if (prof && lane == 0) prof[4] = sprof_wait;
   } else {
     // ================= writer: final words out of the staging ring =================
     constexpr u32 RING = AclRing<LW, SETS>::WORDS;

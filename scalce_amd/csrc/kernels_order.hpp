@@ -529,21 +529,6 @@ __global__ __launch_bounds__(256) void gather_rows_k(u64 nrec, const u32 *perm, 
   }
 }
 
-__global__ __launch_bounds__(256) void sum_bytes_k(const u8 *v, u64 n, unsigned long long *out /* zeroed */) {
-  u64 acc = 0;
-  for (u64 i = ((u64)blockIdx.x * blockDim.x + threadIdx.x) * 16; i < n; i += (u64)gridDim.x * blockDim.x * 16) {
-    if (i + 16 <= n && (((u64)(v + i)) & 15) == 0) {
-      const uint4 w = *reinterpret_cast<const uint4 *>(v + i);
-      const u32 x[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-      for (int k = 0; k < 4; k++) acc += (x[k] & 0xFF) + ((x[k] >> 8) & 0xFF) + ((x[k] >> 16) & 0xFF) + (x[k] >> 24);
-    } else {
-      for (u64 j = i; j < n && j < i + 16; j++) acc += v[j];
-    }
-  }
-  for (int o = 32; o; o >>= 1) acc += (u64)__shfl_xor((long long)acc, o);
-  if (lane_id() == 0 && acc) atomicAdd(out, (unsigned long long)acc);
-}
 // classic arrays of a piece -> fused rows (the rare pieces that went through the indexed ingest kernels): row r = q' | packed words [| cell]
 __global__ __launch_bounds__(256) void fuse_rows_k(u64 nrec, const u8 *q, u32 L, const u8 *cells /* or null */, const u8 *packed, u32 pstride, u32 pwords,
                                                   u8 *frow, u32 rs, u32 cell_off) {

@@ -587,30 +587,6 @@ struct DigitOfArray {  // digit functor for radix_pass: byte `shift/8` of key[pa
   __device__ u32 operator()(u32 v) const { return (key[v] >> shift) & 255u; }
 };
 
-// after the sort: where did each event land, and the initial chosen flags in sorted order
-__global__ __launch_bounds__(256) void events_place_k(u32 nev, const u32 *sorted, const u8 *ev_init, u32 *ev_place,
-                                                     u8 *chosen) {
-  const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= nev) return;
-  const u32 e = sorted[i];
-  ev_place[e] = i;
-  chosen[i] = ev_init[e];
-}
-
-// segment starts of the sorted event array: seg[b] = first position of bucket b (seg[nb] = nev)
-__global__ __launch_bounds__(256) void events_segments_k(u32 nev, const u32 *sorted, const u32 *ev_bucket, u32 nb,
-                                                        u32 *seg) {
-  const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i > nev) return;
-  const u32 cur = i < nev ? ev_bucket[sorted[i]] : nb;
-  const u32 prev = i ? ev_bucket[sorted[i - 1]] : 0xFFFFFFFFu;
-  if (i == 0) {
-    for (u32 b = 0; b <= cur && b <= nb; b++) seg[b] = 0;
-  } else if (cur != prev) {
-    for (u32 b = prev + 1; b <= cur && b <= nb; b++) seg[b] = i;
-  }
-}
-
 // The sweeps only ever need the events of TIE candidates: a fixed read is in its bucket in every sweep, so what the fixed
 // reads in front of a candidate contribute is a constant (fixed_before).  Of the 61 M events of a 50 M-read shard 20 M are
 // tie candidates: the flags and prefix sums the sweeps gather from shrink from 246 MB to 80 MB (inside the 256 MB of

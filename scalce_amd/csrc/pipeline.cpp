@@ -72,6 +72,10 @@ extern "C" int scalce_pipeline_create(scalce_batch **batches, int nslots, int gr
   if (group > 1 && nslots < group) return SCALCE_ERR_ARG;  // (a caller that lets launches fill up needs 2 * group slots: the front stages of one group run while the previous one is coded)
   scalce_pipeline *p = new scalce_pipeline;
   *out = p;
+  if (group > SCALCE_GROUP_MAX) {  // (one launch codes at most that many shards: scalce_batch_entropy_begin_group_last)
+    p->err = "group " + std::to_string(group) + " is above SCALCE_GROUP_MAX (" + std::to_string(SCALCE_GROUP_MAX) + " shards per coder launch)";
+    return SCALCE_ERR_ARG;
+  }
   p->b.assign(batches, batches + nslots);
   p->G = group;
   p->external = external_coder != 0;
@@ -135,7 +139,8 @@ extern "C" int scalce_pipeline_acquire(scalce_pipeline *p, int *slot, int *retir
 // The front stages of `slot` are enqueued on the front stream: launch the coder now or with the next shards.
 // flush_now 1: launch what is pending now, and nothing will run beside that launch (the end of a run, or a wave of shards
 // that fills every slot: the next front stages wait for these slots anyway) -- it is shaped for its own latency;
-// flush_now 2: launch what is pending now, front stages of further shards follow beside it.
+// flush_now 2: launch what is pending now, front stages of further shards follow beside it -- shaped as any launch that is
+// not the last (last = 0).
 extern "C" int scalce_pipeline_submit(scalce_pipeline *p, int slot, int flush_now, int *launched) {
   if (!p || slot < 0 || slot >= (int)p->b.size()) return SCALCE_ERR_ARG;
   if (launched) *launched = 0;

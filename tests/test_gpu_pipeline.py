@@ -157,3 +157,21 @@ def test_coding_in_place_writes_the_same_streams(bpw, overflow, patterns_blob, m
             assert len(g[w]) == len(want[i][w]) and (g[w] == want[i][w]).all(), f"shard {i} (pass {rep}): {name} differ"
     reruns = sum(b.reruns for b in batches)
     assert (reruns > 0) == overflow, f"{reruns} shards were run again from their text"
+
+
+@pytest.mark.parametrize("last", [2, 3, -1])
+def test_group_launch_refuses_other_last_modes(last, patterns_blob):
+    """scalce_batch_entropy_begin_group_last knows two launches: the last of a run (1) and any other (0)."""
+    ctx = host.Context(0, patterns_bin=patterns_blob)
+    b = host.Batch(ctx, 100, 1008, 1 << 20)
+    with pytest.raises(host.ScalceError, match=r"^\[1\]"):   # SCALCE_ERR_ARG
+        host.entropy_begin_group([b], last=last)
+
+
+def test_pipeline_refuses_a_group_above_the_launch_limit(patterns_blob):
+    """A coder launch codes at most 16 shards (SCALCE_GROUP_MAX): a pipeline whose group is larger is refused when it is
+    made, with the reason, not at its first launch."""
+    ctx = host.Context(0, patterns_bin=patterns_blob)
+    batches = [host.Batch(ctx, 100, 1008, 1 << 20) for _ in range(17)]
+    with pytest.raises(RuntimeError, match=r"group 17 is above SCALCE_GROUP_MAX \(16 .*\(rc 1\)"):
+        ShardPipeline(batches, group=17)
