@@ -75,6 +75,13 @@ typedef struct {
   uint64_t bucket_set_size;  /* -B in bytes (spill rule, compress.cpp:702-715); 0 = never spill */
   /* state carried in from earlier shards of the same run (multi-GPU / multi-file); NULL = none */
   uint32_t qprev[2][2];      /* last two quality symbols before this shard, 500 = none (qualities.cpp:179) */
+  /* Records without qualities (zero = FASTQ with qualities, as before).  fasta (-f): two-line records, a name line and
+   * one sequence line (compress.cpp:637,662); no_qualities (-Q): four-line FASTQ whose '+' and quality lines are read and
+   * dropped (compress.cpp:689,697).  Either one: no q' rows, no quality statistics, no table, no coder -- SCALCE_OUT_QUAL,
+   * _TABLE, _FREQ4, _QSTREAM and _QINPUT are empty, and the -B rule counts records without quality bytes.  One GPU only:
+   * scalce_sharded_compress and scalce_pipeline_create refuse such batches (SCALCE_ERR_ARG). */
+  int32_t fasta;
+  int32_t no_qualities;
 } scalce_params;
 
 void scalce_params_default(scalce_params *p);
@@ -328,13 +335,17 @@ int scalce_ac_decode(scalce_ctx *ctx, const uint32_t *table_host, const uint8_t 
  *                is serial; has_buckets = 1 for mate 1 (bucket headers, end metadata), 0 for mate 2 (bare records,
  *                no core -- the reference's stale `corlen` of decompress.cpp:250,332 is NOT reproduced);
  *   d_qual       nrecords * read_len quality symbols in archive order (scalce_ac_decode's output, or the raw
- *                bytes of a -A archive), device memory;
+ *                bytes of a -A archive), device memory; NULL: two-line records (scalce_fasta_text_bytes);
  *   names_host   .scalcen payload behind magic and use_names byte, or NULL for library mode (`library` used);
  *   mate_digit   0, or '1' / '2' for paired archives: a name ending in "/x" gets this digit (:296-298);
  *   d_out        device buffer of out_cap >= scalce_fastq_text_bytes(...) bytes;
  *   record_offsets_host  optional, nrecords + 1 entries: where each record starts in the text (-S splitting).
  * Returns when the text is complete. */
 uint64_t scalce_fastq_text_bytes(int read_len, uint64_t nrecords, uint64_t names_bytes, const char *library /* NULL: names */);
+/* The same for the two-line records of an archive without qualities (-Q / -f): "@name\n" + bases + "\n" per record
+ * (decompress.cpp:323-366 with _compress_qualities = 0).  scalce_fastq_records writes them when d_qual is NULL: no '+'
+ * line, no quality line, no N restore (a base stored as 0 comes back as 'A'). */
+uint64_t scalce_fasta_text_bytes(int read_len, uint64_t nrecords, uint64_t names_bytes, const char *library /* NULL: names */);
 int scalce_fastq_records(scalce_ctx *ctx, int read_len, int has_buckets, const uint8_t *reads_host, uint64_t reads_bytes,
                          uint64_t nrecords, const uint8_t *d_qual, int64_t phred_offset, const uint8_t *names_host,
                          uint64_t names_bytes, const char *library, int mate_digit, uint8_t *d_out, uint64_t out_cap,

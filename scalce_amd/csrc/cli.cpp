@@ -64,6 +64,7 @@ static double now() {
 struct Options {
   int lossy = 0, sample = 100000, threads = 0, split = 0;
   bool paired = false, use_names = true, no_ac = false, decompress = false;
+  bool fasta = false, no_qual = false;    // -f (implies no qualities, main.cpp:220-223), -Q (main.cpp:270-272)
   uint64_t bucket_set_size = 4ull << 30;  // main.cpp:68
   std::string out, library, patterns, temp = "__temp__", patterns_bin;
   int gpus = 1;                           // --gpus N: one process per GPU, ONE archive (plain-text input, -c no)
@@ -81,6 +82,9 @@ static const char *HELP_TEXT =
     "  -n, --skip-names STR        drop read names, regenerate them as STR.<index>\n"
     "  -c, --compression STR       container of the read/name streams: gz (default), pigz (= gz), no; bz is not built\n"
     "  -A, --no-arithmetic         store qualities raw instead of arithmetic coding\n"
+    "  -f, --fasta                 input is FASTA (a name line and one sequence line per record): no qualities are stored\n"
+    "  -Q, --no-qualities          drop the qualities of FASTQ input; decompression: write two-line records (@name, bases)\n"
+    "                              of an archive made with -Q or -f (bases stored as N come back as A).  One GPU only\n"
     "  -p, --lossy-percentage INT  lossy quality transform, 0..100 (default 0)\n"
     "  -s, --sample-size INT       records sampled for the quality model (default 100000)\n"
     "  -B, --bucket-set-size NUM[M|G]  bucket storage that triggers a spill chunk (default 4G); order follows the reference\n"
@@ -441,22 +445,23 @@ struct MateSource {
   }
   // read ahead until the text holds `records` records or the FIRST file ends: quality_mapping_init's sample is taken
   // from files[0] alone (get_quality_stats, compress.cpp:761; the loop of qualities.cpp:66-78 stops at its end)
-  void fill_peek(int records) {
+  void fill_peek(int records, int lines_per_record = 4) {
     hold_at_file_end = true;
-    fill_peek_held(records);
+    fill_peek_held(records, lines_per_record);
     hold_at_file_end = false;
   }
-  void fill_peek_held(int records) {
+  void fill_peek_held(int records, int lines_per_record = 4) {
+    const size_t want = (size_t)lines_per_record * (size_t)records;
     size_t lines = 0, scanned = 0;
     for (;;) {
       const uint8_t *p = peek.data();
-      while (scanned < peek.size() && lines < 4 * (size_t)records) {
+      while (scanned < peek.size() && lines < want) {
         const void *nl = memchr(p + scanned, '\n', peek.size() - scanned);
         if (!nl) { scanned = peek.size(); break; }
         scanned = (size_t)((const uint8_t *)nl - p) + 1;
         lines++;
       }
-      if (lines >= 4 * (size_t)records) return;
+      if (lines >= want) return;
       const size_t old = peek.size(), step = 16u << 20;
       peek.resize(old + step);
       int64_t got = 0;
@@ -511,6 +516,15 @@ static std::vector<uint8_t> load_core_table(const Options &o, const char *argv0,
   FAIL("No core table: give --patterns-bin FILE, -P LIST or set SCALCE_PATTERNS (the reference embeds patterns.bin at link time)\n");
 }
 
+// -f: nothing is sampled (qualities.cpp:65): the read length is that of line 2 of the first record
+static void first_sequence_length(const std::vector<uint8_t> &t, int &read_length) {
+  const void *nl = memchr(t.data(), '\n', t.size());
+  if (!nl) return;
+  const size_t s = (const uint8_t *)nl - t.data() + 1;
+  const void *nl2 = s < t.size() ? memchr(t.data() + s, '\n', t.size() - s) : nullptr;
+  if (nl2) read_length = (int)((const uint8_t *)nl2 - (t.data() + s));
+}
+
 // ---- compress -----------------------------------------------------------------------------------------
 static int do_compress(const Options &o, const std::vector<std::string> &files, scalce_ctx *ctx) {
   const double t0 = now();
@@ -520,6 +534,8 @@ static int do_compress(const Options &o, const std::vector<std::string> &files, 
   scalce_params p;
   scalce_params_default(&p);
   p.paired = o.paired; p.use_names = o.use_names; p.no_ac = o.no_ac; p.bucket_set_size = o.bucket_set_size;
+  p.fasta = o.fasta; p.no_qualities = o.no_qual;
+  const bool no_qual = o.fasta || o.no_qual;
   LOG("Preprocessing FASTQ files ...\n");
   MateSource src[2];
   for (int m = 0; m < nm; m++) {
@@ -533,8 +549,14 @@ static int do_compress(const Options &o, const std::vector<std::string> &files, 
     }
     // get_quality_stats looks at the first file only (compress.cpp:761)
     int rl = 0;
-    src[m].fill_peek(o.sample);
-    sample_stats(src[m].peek, o.sample, qhist, rl);
+    if (o.fasta) {  // the statistics stay zero: the offset stays 64 (qualities.cpp:91-101)
+      src[m].fill_peek(1, 2);
+      memset(qhist, 0, sizeof qhist);
+      first_sequence_length(src[m].peek, rl);
+    } else {  // (-Q samples as usual: the offset in the header is the one detected)
+      src[m].fill_peek(o.sample);
+      sample_stats(src[m].peek, o.sample, qhist, rl);
+    }
     scalce_qmap_init(&p.qmap[m], qhist, o.lossy);
     p.read_len[m] = rl;
     LOG("\tPaired end #%d, quality offset: %d\n\t               read length: %d\n", m + 1, p.qmap[m].offset, rl);
@@ -545,7 +567,7 @@ static int do_compress(const Options &o, const std::vector<std::string> &files, 
   if (src[0].all_plain && !src[0].gz) {
     uint64_t bytes = 0;
     for (auto &f : src[0].files) { struct stat st; if (stat(f.c_str(), &st) == 0) bytes += (uint64_t)st.st_size; }
-    hint = bytes / (2 * (uint64_t)p.read_len[0] + 8) + 64;
+    hint = bytes / ((o.fasta ? 1 : 2) * (uint64_t)p.read_len[0] + (o.fasta ? 4 : 8)) + 64;
     for (auto &f : src[0].files) { int fd = ::open(f.c_str(), O_RDONLY); uint8_t mg[2] = {0, 0}; if (fd >= 0) { if (::pread(fd, mg, 2, 0) == 2 && mg[0] == 0x1F && mg[1] == 0x8B) hint = 0; ::close(fd); } }
   }
   uint64_t piece = 256ull << 20;  // per chunk; three of them are pinned per mate
@@ -616,6 +638,11 @@ static int do_compress(const Options &o, const std::vector<std::string> &files, 
     snprintf(fn, sizeof fn, "%s_%d.scalceq", o.out.c_str(), m + 1); fQ.open(fn, o.no_ac ? gz : false);  // :249
     const int64_t phred = p.qmap[0].offset;  // mate 1's offset for both (compress.cpp:294,816-817)
     fQ.write(magic, 8); fQ.write(&phred, 8);
+    if (no_qual) {  // -Q / -f: the header and nothing else -- no table (:296), no coder blocks (ac_write of nothing)
+      fQ.close();
+      downs[m].reset();
+      return;
+    }
     if (!o.no_ac) {
       auto tb = fetch(ctx, b, SCALCE_OUT_TABLE, m);
       fQ.write(tb.data(), tb.size());
@@ -1136,6 +1163,28 @@ struct Reader {
   }
 };
 
+// records of a .scalcer payload (behind its 16-byte header): mate 1 walks the bucket headers -- [i32 core][u64 count], then
+// count records of SZ_READ(L - core length) + metadata bytes (decompress.cpp:262-270) --, mate 2 holds bare records
+static uint64_t read_stream_records(scalce_ctx *ctx, const uint8_t *p, uint64_t n, int L, bool buckets) {
+  if (!buckets) return n / (uint64_t)((L + 3) / 4);
+  const uint64_t meta = L > 255 ? 2 : 1;
+  uint64_t pos = 0, k = 0;
+  while (pos + 12 <= n) {
+    int32_t core;
+    uint64_t cnt;
+    memcpy(&core, p + pos, 4);
+    memcpy(&cnt, p + pos + 4, 8);
+    pos += 12;
+    const int cl = core == SCALCE_ROOT_CORE ? 0 : scalce_pattern_length(ctx, core);
+    if (cl < 0 || cl > L) FAIL("archive refers to core %d which the core table does not have\n", core);
+    const uint64_t rb = (uint64_t)((L - cl + 3) / 4) + meta;
+    if (cnt > (n - pos) / rb) FAIL("truncated read stream\n");
+    pos += cnt * rb;
+    k += cnt;
+  }
+  return k;
+}
+
 static int do_decompress(const Options &o, const std::string &path, scalce_ctx *ctx) {
   const double t0 = now();
   const int nm = o.paired ? 2 : 1;
@@ -1164,6 +1213,13 @@ static int do_decompress(const Options &o, const std::string &path, scalce_ctx *
     R[m].read(&len[m], 4);
     Q[m].read(&phred[m], 8);
   }
+  // -d -Q / -d -f: two-line records, whatever the .scalceq holds (decompress.cpp:159-168 does not read it).  Without either, an
+  // archive made with -Q / -f -- a .scalceq that ends behind its 16-byte header while the read stream holds records -- is an
+  // error: decoding qualities that are not there would misread it.
+  const bool no_qual = o.fasta || o.no_qual;
+  for (int m = 0; m < nm && !no_qual; m++)
+    if (Q[m].pos >= Q[m].v.size() && read_stream_records(ctx, R[m].v.data() + R[m].pos, R[m].v.size() - R[m].pos, len[m], m == 0))
+      FAIL("%s holds no qualities: the archive was made with -Q or -f; decompress it with -Q\n", scalce_name(base[m], 'q').c_str());
   uint8_t names = 0;
   std::string library = o.library;
   if (o.use_names) {  // decompress.cpp:219-237
@@ -1195,7 +1251,9 @@ static int do_decompress(const Options &o, const std::string &path, scalce_ctx *
     // qualities: arithmetic decoder on the device, or the raw q - offset bytes of a -A archive
     void *d_q = nullptr;
     uint64_t total = 0;
-    if (!no_ac) {  // table + total + blocks -> GPU decoder
+    if (no_qual) {  // nothing to decode: the records are counted in the read stream
+      total = read_stream_records(ctx, R[m].v.data() + R[m].pos, R[m].v.size() - R[m].pos, L, m == 0) * (uint64_t)L;
+    } else if (!no_ac) {  // table + total + blocks -> GPU decoder
       std::vector<uint32_t> table(512000);
       if (Q[m].read(table.data(), 512000 * 4) != 512000 * 4) FAIL("truncated quality table\n");
       Q[m].read(&total, 8);
@@ -1219,7 +1277,7 @@ static int do_decompress(const Options &o, const std::string &path, scalce_ctx *
     const uint8_t *npay = names ? Nn[m].v.data() + Nn[m].pos : nullptr;
     const uint64_t nbytes_names = names ? Nn[m].v.size() - Nn[m].pos : 0;
     if (names && nbytes_names < nrec) FAIL("truncated name stream\n");
-    const uint64_t cap = scalce_fastq_text_bytes(L, nrec, nbytes_names, names ? nullptr : library.c_str());
+    const uint64_t cap = (no_qual ? scalce_fasta_text_bytes : scalce_fastq_text_bytes)(L, nrec, nbytes_names, names ? nullptr : library.c_str());
     void *d_text = nullptr;
     HIPOK(hipMalloc(&d_text, cap + 64));
     const double tb = now();
@@ -1289,7 +1347,8 @@ int main(int argc, char **argv) {
       case 'v': return 0;
       case 'h': fputs(HELP_TEXT, stdout); return 0;
       case 'A': o.no_ac = true; break;
-      case 'f': case 'Q': FAIL("FASTA / no-quality mode is outside this build's scope (SURVEY.md section 2, #23)\n");
+      case 'f': o.fasta = true; break;
+      case 'Q': o.no_qual = true; break;
       case 'c':
         if (!strcmp(optarg, "gz") || !strcmp(optarg, "pigz")) o.container = 1;
         else if (!strcmp(optarg, "no")) o.container = 0;
@@ -1336,6 +1395,8 @@ int main(int argc, char **argv) {
       if (stat(f2.c_str(), &st) != 0) FAIL("File %s does not exist or it is not accessible.\n", f2.c_str());
     }
   }
+  if (o.gpus > 1 && !o.decompress && (o.fasta || o.no_qual))
+    FAIL("-f / -Q runs on one GPU: --gpus %d is not available without qualities\n", o.gpus);
   if (o.gpus > 1 && !o.decompress) {  // forks before anything touches a GPU
     // (a run that -B does not cut anywhere is one chunk: scalce_sharded_compress sends all its rows to rank 0)
     return multi_gpu_compress(o, files, argv[0]);

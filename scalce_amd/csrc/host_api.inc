@@ -23,7 +23,7 @@ extern "C" int scalce_batch_front(scalce_batch *b, const uint8_t *t1, uint64_t n
   if (b->nm == 2 && (rc = scalce_batch_ingest(b, 1, t2, n2, stream))) return rc;
   // the quality statistics run beside the tie-break's sweeps (quality_beside, host_tokenize.inc) -- or here, when the
   // tokenizer never gets there (no tie reads, another tie-break path) or stage times are being taken
-  b->quality_deferred = !b->timing && !b->p.no_ac;
+  b->quality_deferred = !b->timing && !b->p.no_ac && !b->nq;  // (-Q / -f: nothing to fork)
   if (!b->quality_deferred && (rc = scalce_batch_quality(b, stream))) return rc;
   rc = scalce_batch_tokenize(b, nullptr, stream);
   if (b->quality_deferred) {
@@ -61,7 +61,7 @@ extern "C" int scalce_batch_params(const scalce_batch *b, scalce_params *out) {
 // sharded run tells its neighbours (the trigrams that straddle a rank boundary) -- without asking for SCALCE_OUT_QINPUT as
 // one array, which fused rows would have to be copied together for
 extern "C" int scalce_batch_qinput_edges(scalce_batch *b, int mate, uint8_t edge[4], uint64_t *nsym, int32_t *read_len, void *stream) {
-  if (!b || mate < 0 || mate >= b->nm || !edge || !nsym) return SCALCE_ERR_ARG;
+  if (!b || mate < 0 || mate >= b->nm || !edge || !nsym || b->nq) return SCALCE_ERR_ARG;
   scalce_ctx *c = b->ctx;
   hipStream_t s = (hipStream_t)stream;
   HIP_TRY(c, hipSetDevice(c->device));
@@ -141,6 +141,12 @@ static int materialize_frames(scalce_batch *b, int m) {
 extern "C" int scalce_batch_output(const scalce_batch *b, int which, int mate, const void **d_ptr, uint64_t *nbytes) {
   if (!b || !d_ptr || !nbytes || mate < 0 || mate >= b->nm) return SCALCE_ERR_ARG;
   const u32 nb1 = (u32)b->ctx->A.n_buckets + 1;
+  if (b->nq && (which == SCALCE_OUT_QUAL || which == SCALCE_OUT_TABLE || which == SCALCE_OUT_FREQ4 || which == SCALCE_OUT_QSTREAM ||
+                which == SCALCE_OUT_QINPUT)) {  // -Q / -f: nothing quality-side exists
+    *d_ptr = nullptr;
+    *nbytes = 0;
+    return SCALCE_OK;
+  }
   if (which == SCALCE_OUT_QUAL && !b->p.no_ac && b->frame_virtual[mate]) {
     int rc = materialize_frames(const_cast<scalce_batch *>(b), mate);
     if (rc) return rc;

@@ -110,12 +110,20 @@ extern "C" uint64_t scalce_fastq_text_bytes(int read_len, uint64_t nrecords, uin
   for (int t = 2; t <= 20 && N > p; t++, p *= 10) digits += N - p;
   return N * (strlen(library) + 2 * L + 7) + digits;
 }
+extern "C" uint64_t scalce_fasta_text_bytes(int read_len, uint64_t nrecords, uint64_t names_bytes, const char *library) {
+  const u64 L = (u64)read_len, N = nrecords;
+  if (!library) return names_bytes - N + N * (L + 3);  // "@" name "\n" bases "\n"
+  u64 digits = N, p = 10;
+  for (int t = 2; t <= 20 && N > p; t++, p *= 10) digits += N - p;
+  return N * (strlen(library) + L + 4) + digits;
+}
 
 extern "C" int scalce_fastq_records(scalce_ctx *c, int read_len, int has_buckets, const uint8_t *reads_host, uint64_t reads_bytes,
                                     uint64_t nrecords, const uint8_t *d_qual, int64_t phred_offset, const uint8_t *names_host,
                                     uint64_t names_bytes, const char *library, int mate_digit, uint8_t *d_out, uint64_t out_cap,
                                     uint64_t *out_bytes, uint64_t *record_offsets_host, void *stream) {
-  if (!c || read_len <= 0 || !reads_host || (!names_host && !library) || !d_out || (nrecords && !d_qual)) return SCALCE_ERR_ARG;
+  if (!c || read_len <= 0 || !reads_host || (!names_host && !library) || !d_out) return SCALCE_ERR_ARG;
+  const bool qual = d_qual != nullptr;  // NULL: two-line records of an archive without qualities
   hipStream_t s = (hipStream_t)stream;
   HIP_TRY(c, hipSetDevice(c->device));
   const u32 L = (u32)read_len;
@@ -175,7 +183,7 @@ extern "C" int scalce_fastq_records(scalce_ctx *c, int read_len, int has_buckets
     name_off[nrecords] = pos;
     names_bytes = pos;
   }
-  const u64 total = scalce_fastq_text_bytes(read_len, nrecords, names_bytes, names_host ? nullptr : library);
+  const u64 total = (qual ? scalce_fastq_text_bytes : scalce_fasta_text_bytes)(read_len, nrecords, names_bytes, names_host ? nullptr : library);
   if (out_bytes) *out_bytes = total;
   if (total > out_cap) { set_err(c, "output buffer of %llu bytes, the text needs %llu", (unsigned long long)out_cap, (unsigned long long)total); return SCALCE_ERR_CAPACITY; }
   if (!nrecords) return SCALCE_OK;
@@ -205,7 +213,8 @@ extern "C" int scalce_fastq_records(scalce_ctx *c, int read_len, int has_buckets
   a.qual = d_qual; a.phred = (u32)phred_offset; a.names = d_names; a.name_off = d_noff;
   a.mate_digit = (u32)mate_digit; a.out = d_out; a.rec_off = d_roff;
   const u64 waves = (nrecords + FQ_RECORDS_PER_WAVE - 1) / FQ_RECORDS_PER_WAVE;
-  LAUNCH(fastq_records_k, cdiv(waves, 4), 256, 0, s, a);
+  if (qual) LAUNCH(fastq_records_k<true>, cdiv(waves, 4), 256, 0, s, a);
+  else LAUNCH(fastq_records_k<false>, cdiv(waves, 4), 256, 0, s, a);
   if (record_offsets_host)
     FQ_TRY(hipMemcpyAsync(record_offsets_host, d_roff, sizeof(u64) * (nrecords + 1), hipMemcpyDeviceToHost, s));
   FQ_TRY(hipStreamSynchronize(s));

@@ -478,6 +478,10 @@ extern "C" int scalce_batch_entropy_begin(scalce_batch *b, const uint32_t *d_tab
   hipStream_t s = (hipStream_t)stream;
   scalce_ctx *c = b->ctx;
   HIP_TRY(c, hipSetDevice(c->device));
+  if (b->nq) {  // -Q / -f: no quality stream, nothing to code (SCALCE_OUT_QUAL is empty)
+    for (int m = 0; m < b->nm; m++) b->out_qual_bytes[m] = 0;
+    return SCALCE_OK;
+  }
   const u64 N = b->N;
   if (!b->p.no_ac) {
     u64 blocks = 0;
@@ -538,6 +542,7 @@ extern "C" int scalce_batch_entropy_begin_group_last(scalce_batch **bs, int n, v
     scalce_batch *b = bs[i];
     for (int m = 0; m < b->nm; m++) {
       const u64 own = b->N * (u64)b->L[m];
+      if (b->nq) { b->out_qual_bytes[m] = 0; continue; }  // (-Q / -f: nothing to code)
       if (b->p.no_ac) { b->out_qual_bytes[m] = own; continue; }
       AcJob j{b, m, b->ent_external[m] ? b->ent_sym[m] : b->qs(m).as<u8>(), b->ent_external[m] ? b->ent_nsym[m] : own, 0, false};
       if (!b->ent_external[m]) { int rc = ac_table_for(b, m, nullptr, own, ps); if (rc) return rc; }
@@ -558,7 +563,7 @@ extern "C" int scalce_batch_entropy_begin_group_last(scalce_batch **bs, int n, v
 // scalce_batch_entropy_begin_group codes it.
 extern "C" int scalce_batch_entropy_stream_prepare(scalce_batch *b, int mate, const uint32_t *d_table, const uint8_t *d_symbols,
                                                    uint64_t nsym, void *stream) {
-  if (!b || mate < 0 || mate >= b->nm || !d_table || (nsym && !d_symbols) || b->p.no_ac) return SCALCE_ERR_ARG;
+  if (!b || mate < 0 || mate >= b->nm || !d_table || (nsym && !d_symbols) || b->p.no_ac || b->nq) return SCALCE_ERR_ARG;
   scalce_ctx *c = b->ctx;
   HIP_TRY(c, hipSetDevice(c->device));
   HIP_TRY(c, hipMemcpyAsync(b->table[mate].p, d_table, sizeof(u32) * 512000, hipMemcpyDeviceToDevice, (hipStream_t)stream));
@@ -576,6 +581,7 @@ extern "C" int scalce_batch_entropy_end(scalce_batch *b, void *stream) {
 
 extern "C" int scalce_batch_entropy(scalce_batch *b, const uint32_t *d_table_override, void *stream) {
   if (!b) return SCALCE_ERR_ARG;
+  if (b->nq) return scalce_batch_entropy_begin(b, d_table_override, stream);  // (-Q / -f: no launch, not even a timed stage)
   StageTimer tm(b, ST_ENTROPY, (hipStream_t)stream);
   int rc = scalce_batch_entropy_begin(b, d_table_override, stream);
   if (rc) return rc;
@@ -586,7 +592,7 @@ extern "C" int scalce_batch_entropy(scalce_batch *b, const uint32_t *d_table_ove
 // run-wide reordered stream that starts on a 10 MiB block boundary) against the run-wide table.
 extern "C" int scalce_batch_entropy_stream_begin(scalce_batch *b, int mate, const uint32_t *d_table, const uint8_t *d_symbols,
                                                  uint64_t nsym, void *stream) {
-  if (!b || mate < 0 || mate >= b->nm || !d_table || (nsym && !d_symbols) || b->p.no_ac) return SCALCE_ERR_ARG;
+  if (!b || mate < 0 || mate >= b->nm || !d_table || (nsym && !d_symbols) || b->p.no_ac || b->nq) return SCALCE_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
   scalce_ctx *c = b->ctx;
   HIP_TRY(c, hipSetDevice(c->device));

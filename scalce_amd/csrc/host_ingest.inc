@@ -28,10 +28,10 @@ static int ensure_line_index(scalce_batch *b, int mate, hipStream_t s) {
   const u64 nrec = b->NP, nbytes = b->text_bytes[mate];
   if (nrec > b->piece_rows_cap || !b->line_end[mate].p) {
     if (nrec > b->piece_rows_cap) b->piece_rows_cap = nrec;
-    ENSURE(b, b->line_end[mate], sizeof(u64) * 4 * (b->piece_rows_cap + 1));
+    ENSURE(b, b->line_end[mate], sizeof(u64) * b->lpr * (b->piece_rows_cap + 1));
   }
   const u32 ntiles = cdiv(nbytes, IDX_TILE);
-  if (ntiles) LAUNCH(index_write_k, ntiles, IDX_THREADS, 0, s, b->piece_text[mate], nbytes, b->tile[mate].as<u64>(), b->line_end[mate].as<u64>(), 4 * nrec);
+  if (ntiles) LAUNCH(index_write_k, ntiles, IDX_THREADS, 0, s, b->piece_text[mate], nbytes, b->tile[mate].as<u64>(), b->line_end[mate].as<u64>(), (u64)b->lpr * nrec);
   b->line_index_ok[mate] = true;
   return SCALCE_OK;
 }
@@ -39,7 +39,14 @@ static int ensure_line_index(scalce_batch *b, int mate, hipStream_t s) {
 // the first `nrec` records of the text -> rows [base, base + nrec): 2-bit bases, q', names
 // (A one-pass variant -- no count pass, the tiles' line bases by decoupled look-back between the workgroups -- was byte-exact
 // and slower: 9.2 ms against 1.7 + 6.2 at 50 M x 100 bp, rounds 3-4; removed in round 5.)
-static int piece_unpack(scalce_batch *b, int mate, const u8 *d_text, u64 nbytes, u64 nrec, hipStream_t s) {
+// LPR = lines per record, QOUT = q' rows written: the record variants of the kernels (unpack_record_at)
+template <int LPR, bool QOUT>
+static int piece_unpack_t(scalce_batch *b, int mate, const u8 *d_text, u64 nbytes, u64 nrec, hipStream_t s) {
+  constexpr auto k_tiles2 = &ingest_tiles2_k<LPR, QOUT>;
+  constexpr auto k_unpack_tiled = &unpack_tiled_k<LPR, QOUT>;
+  constexpr auto k_unpack = &unpack_k<LPR, QOUT>;
+  constexpr auto k_last_end = &last_record_end_k<LPR>;
+  constexpr auto k_long_names = &long_names_k<LPR>;
   scalce_ctx *c = b->ctx;
   b->piece_text[mate] = d_text;
   b->line_index_ok[mate] = false;
@@ -49,7 +56,7 @@ static int piece_unpack(scalce_batch *b, int mate, const u8 *d_text, u64 nbytes,
   a.text = d_text; a.nbytes = nbytes; a.line_end = nullptr; a.nrec = nrec;
   a.L = b->L[mate]; a.stride = b->stride[mate]; a.mate = mate; a.use_names = b->p.use_names; a.no_ac = b->p.no_ac;
   a.packed = b->packed[mate].as<u8>() + b->base * (u64)b->stride[mate];
-  a.q = b->q[mate].as<u8>() + b->base * (u64)b->qstride[mate];
+  a.q = QOUT ? b->q[mate].as<u8>() + b->base * (u64)b->qstride[mate] : nullptr;
   a.qstride = b->qstride[mate];
   a.cellstride = 16;
   a.packed2 = nullptr;
@@ -77,7 +84,7 @@ static int piece_unpack(scalce_batch *b, int mate, const u8 *d_text, u64 nbytes,
     ia.slow = slow;
     {
       const u32 ntiles2 = cdiv(nbytes, ING_TILE);
-      ENSURE(b, b->tile_mm[mate], sizeof(u16) * ((size_t)ntiles2 + 8));
+      if (QOUT) ENSURE(b, b->tile_mm[mate], sizeof(u16) * ((size_t)ntiles2 + 8));
       Ingest2Args ga;
       ga.i = ia;
       const u64 S = (u64)a.stride / 4, W = ((u64)a.L + 15) / 16;
@@ -85,10 +92,12 @@ static int piece_unpack(scalce_batch *b, int mate, const u8 *d_text, u64 nbytes,
       ga.magic_w = ((1ull << 32) + W - 1) / W;
       ga.step_ks = (u32)(ING_THREADS / S); ga.step_rs = (u32)(ING_THREADS % S);
       ga.step_kw = (u32)(ING_THREADS / W); ga.step_rw = (u32)(ING_THREADS % W);
-      ga.tile_minmax = b->tile_mm[mate].as<u16>();
-      LAUNCH(ingest_tiles2_k, ntiles2, ING_THREADS, 0, s, ga);
-      b->mm_valid[mate] = true;
-      b->ws->tile_mm_owner[mate] = b;
+      ga.tile_minmax = QOUT ? b->tile_mm[mate].as<u16>() : nullptr;
+      LAUNCH(k_tiles2, ntiles2, ING_THREADS, 0, s, ga);
+      if (QOUT) {
+        b->mm_valid[mate] = true;
+        b->ws->tile_mm_owner[mate] = b;
+      }
     }
     { int rc = read_u32(b, b->d_small + 16, flags, 2, s); if (rc) return rc; }
     if (flags[1]) { fused = false; b->mm_valid[mate] = false; }  // a record longer than the overlap: redo the piece the indexed way
@@ -105,12 +114,12 @@ static int piece_unpack(scalce_batch *b, int mate, const u8 *d_text, u64 nbytes,
       a.packed2 = nullptr;
     }
     if ((size_t)UNP_RPB * a.L <= (size_t)UNP_Q_CAP)
-      LAUNCH(unpack_tiled_k, cdiv(nrec, UNP_RPB), 2 * UNP_RPB, unp_text_cap(a.L) + 32 + unp_q_cap(a.L), s, a);
-    else LAUNCH(unpack_k, cdiv(nrec, 256), 256, 0, s, a);
+      LAUNCH(k_unpack_tiled, cdiv(nrec, UNP_RPB), 2 * UNP_RPB, unp_text_cap(a.L) + 32 + (QOUT ? unp_q_cap(a.L) : 0u), s, a);
+    else LAUNCH(k_unpack, cdiv(nrec, 256), 256, 0, s, a);
     if (fused_rows)
       LAUNCH(fuse_rows_k, cdiv(nrec, 256), 256, 0, s, nrec, b->fuse_q.as<u8>(), (u32)a.L, (const u8 *)nullptr, a.packed, (u32)a.stride, b->row_pwords,
              row_q, b->qstride[0], b->row_cell_off);
-    LAUNCH(last_record_end_k, 1, 1, 0, s, a.line_end, nrec, d_consumed);
+    LAUNCH(k_last_end, 1, 1, 0, s, a.line_end, nrec, d_consumed);
     { int rc = read_u32(b, b->d_small + 16, flags, 1, s); if (rc) return rc; }
   }
   { u64 v = 0; int rc = read_u64(b, d_consumed, &v, 1, s); if (rc) return rc; b->piece_consumed[mate] = v; }
@@ -129,11 +138,16 @@ static int piece_unpack(scalce_batch *b, int mate, const u8 *d_text, u64 nbytes,
       u64 total = 0;
       { int rc = read_u64(b, b->d_small64 + 6, &total, 1, s); if (rc) return rc; }
       { int rc = ensure_keep(b, b->names_in, b->names_in_used + total + 64, b->names_in_used, s); if (rc) return rc; }
-      LAUNCH(long_names_k, cdiv(nrec, 256), 256, 0, s, nrec, d_text, b->line_end[mate].as<u64>(), a.namelen, off, b->names_in_used, b->names_in.as<u8>());
+      LAUNCH(k_long_names, cdiv(nrec, 256), 256, 0, s, nrec, d_text, b->line_end[mate].as<u64>(), a.namelen, off, b->names_in_used, b->names_in.as<u8>());
       b->names_in_used += total;
     }
   }
   return SCALCE_OK;
+}
+static int piece_unpack(scalce_batch *b, int mate, const u8 *d_text, u64 nbytes, u64 nrec, hipStream_t s) {
+  if (b->lpr == 2) return piece_unpack_t<2, false>(b, mate, d_text, nbytes, nrec, s);  // -f
+  if (b->nq) return piece_unpack_t<4, false>(b, mate, d_text, nbytes, nrec, s);        // -Q
+  return piece_unpack_t<4, true>(b, mate, d_text, nbytes, nrec, s);
 }
 
 static void batch_restart(scalce_batch *b) {
@@ -166,11 +180,12 @@ extern "C" int scalce_batch_ingest(scalce_batch *b, int mate, const uint8_t *d_t
   u8 last = '\n';
   { int rc = piece_count(b, mate, d_text, nbytes, s, &nlines, &last); if (rc) return rc; }
   HIP_TRY(c, hipStreamSynchronize(s));
-  if ((nlines & 3) || last != '\n') {
-    set_err(c, "(ERROR) FASTQ text has %llu lines (not a multiple of 4) or no trailing newline", (unsigned long long)nlines);
+  if ((nlines % b->lpr) || last != '\n') {
+    set_err(c, "(ERROR) %s text has %llu lines (not a multiple of %d) or no trailing newline", b->lpr == 2 ? "FASTA" : "FASTQ",
+            (unsigned long long)nlines, b->lpr);
     return SCALCE_ERR_FORMAT;
   }
-  const u64 nrec = nlines / 4;
+  const u64 nrec = nlines / b->lpr;
   if (nrec > b->max_reads) { set_err(c, "%llu records exceed the batch capacity", (unsigned long long)nrec); return SCALCE_ERR_CAPACITY; }
   if (mate == 0) { b->N = b->NP = nrec; }
   else if (nrec != b->N) { set_err(c, "(ERROR) mates have different record counts"); return SCALCE_ERR_FORMAT; }
@@ -196,11 +211,13 @@ static int ingest_piece(scalce_batch *b, const uint8_t *const text[2], const u64
   for (int m = 0; m < b->nm; m++)
     if (nbytes[m]) { int rc = piece_count(b, m, text[m], nbytes[m], s, &nlines[m], &last[m]); if (rc) return rc; }
   HIP_TRY(c, hipStreamSynchronize(s));
-  for (int m = 0; m < b->nm; m++) nrec = nlines[m] / 4 < nrec ? nlines[m] / 4 : nrec;
+  const u64 lpr = (u64)b->lpr;
+  for (int m = 0; m < b->nm; m++) nrec = nlines[m] / lpr < nrec ? nlines[m] / lpr : nrec;
   if (final_piece) {
     for (int m = 0; m < b->nm; m++)
-      if ((nlines[m] & 3) || last[m] != '\n') {
-        set_err(c, "(ERROR) FASTQ text has %llu lines (not a multiple of 4) or no trailing newline", (unsigned long long)(4 * b->N + nlines[m]));
+      if ((nlines[m] % lpr) || last[m] != '\n') {
+        set_err(c, "(ERROR) %s text has %llu lines (not a multiple of %d) or no trailing newline", b->lpr == 2 ? "FASTA" : "FASTQ",
+                (unsigned long long)(lpr * b->N + nlines[m]), b->lpr);
         return SCALCE_ERR_FORMAT;
       }
     if (b->nm == 2 && nlines[0] != nlines[1]) { set_err(c, "(ERROR) mates have different record counts"); return SCALCE_ERR_FORMAT; }
@@ -359,6 +376,7 @@ extern "C" int scalce_batch_set_fused_rows(scalce_batch *b, int on) {
 // ---- stage 1: quality statistics -------------------------------------------------------------------
 extern "C" int scalce_batch_quality(scalce_batch *b, void *stream) {
   if (!b) return SCALCE_ERR_ARG;
+  if (b->nq) return SCALCE_OK;  // -Q / -f: no qualities, no statistics (compress.cpp:689,697) -- nothing is launched
   hipStream_t s = (hipStream_t)stream;
   scalce_ctx *c = b->ctx;
   HIP_TRY(c, hipSetDevice(c->device));

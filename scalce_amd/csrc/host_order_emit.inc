@@ -35,7 +35,8 @@ extern "C" int scalce_batch_order(scalce_batch *b, void *stream) {
     ENSURE(b, b->chunk, sizeof(u32) * (N + 2));
     const u32 max_chunks = 4096;
     ENSURE(b, b->chunk_start, sizeof(u64) * (max_chunks + 2));
-    RecSize rs{b->bucket.as<u32>(), c->d_bucket_level, b->namelen.as<u8>(), b->L[0], b->L[1], b->p.paired, b->p.use_names, 1};
+    // (-Q / -f: rd.sz holds no quality bytes, compress.cpp:689-702 -- the cuts fall elsewhere than with qualities)
+    RecSize rs{b->bucket.as<u32>(), c->d_bucket_level, b->namelen.as<u8>(), b->L[0], b->L[1], b->p.paired, b->p.use_names, !b->nq};
     u64 *S = b->S.as<u64>();
     exclusive_scan<u64>(rs, N, StoreTo<u64>{S}, b->scan_ws.as<u64>(), S + N, s);
     LAUNCH(chunk_bounds_k, 1, 1, 0, s, S, N, (u64)b->p.bucket_set_size, max_chunks, b->chunk_start.as<u64>(), b->d_small + 8);
@@ -225,7 +226,7 @@ extern "C" int scalce_batch_emit(scalce_batch *b, void *stream) {
     else if (b->p.use_names)
       LAUNCH(emit_names_k, cdiv(N, 256), 256, 0, s, N, b->perm, b->namecell.as<u8>(), b->name_in_off.as<u64>(),
              b->names_in.as<u8>(), b->name_off.as<u64>(), b->out_names.as<u8>());
-    for (int m = 0; m < b->nm; m++) {
+    for (int m = 0; m < b->nm && !b->nq; m++) {  // (-Q / -f: no quality stream)
       const u32 w = (u32)b->L[m];
       if (m == 0 && b->fused) continue;  // (emit_reads_k<true> has done it)
       ENSURE(b, b->qs(m), (size_t)w * N + 64 + AC_INPLACE_PAD);

@@ -28,6 +28,8 @@ static void set_err(scalce_ctx *c, const char *fmt, ...) {
   va_end(ap);
   c->err = buf;
 }
+// (for the other translation units of the library: sharded.cpp)
+void scalce_set_last_error(scalce_ctx *c, const char *msg) { if (c) c->err = msg; }
 
 #define HIP_TRY(ctx, expr)                                                               \
   do {                                                                                   \
@@ -353,6 +355,10 @@ struct scalce_batch {
   u64 max_reads = 0, max_text = 0;
   int nm = 1;
   int L[2] = {0, 0}, stride[2] = {0, 0}, szr[2] = {0, 0}, sz_meta = 1;
+  // Records without qualities (params fasta / no_qualities): lpr = text lines per record (2 under fasta, else 4); nq = no q'
+  // anywhere -- no q' rows, no quality statistics, no table, no coder, and the -B rule counts no quality bytes.
+  int lpr = 4;
+  bool nq = false;
   // Rows.  A batch takes its input in one piece (scalce_batch_ingest) or in several (scalce_batch_append): rows
   // [base, base + NP) are the piece being ingested / tokenized, N = base + NP is everything the batch holds.  Packed
   // bases, q', names and tokens are run-wide arrays indexed by row; the text of a piece is dead once it is ingested.
@@ -551,7 +557,7 @@ static int reserve_rows(scalce_batch *b, u64 rows, u64 used, hipStream_t s) {
   int rc;
   for (int m = 0; m < b->nm; m++) {
     if ((rc = ensure_keep(b, b->packed[m], (size_t)b->stride[m] * rows + 64, (size_t)b->stride[m] * used, s))) return rc;
-    if ((rc = ensure_keep(b, b->q[m], (size_t)b->qstride[m] * rows + 64, (size_t)b->qstride[m] * used, s))) return rc;
+    if (!b->nq && (rc = ensure_keep(b, b->q[m], (size_t)b->qstride[m] * rows + 64, (size_t)b->qstride[m] * used, s))) return rc;
   }
   if ((rc = ensure_keep(b, b->namelen, rows + 64, used, s))) return rc;
   if (b->p.use_names && (rc = ensure_keep(b, b->namecell, 16 * (rows + 8), 16 * used, s))) return rc;
@@ -611,9 +617,11 @@ static int batch_create(scalce_ctx *c, const scalce_params *p, uint64_t max_read
     b->stride[m] = ((b->szr[m] + 1 + 15) / 16) * 16;  // one spare zero byte for 16-bit digit windows
   }
   b->sz_meta = b->L[0] > 255 ? 2 : 1;  // reads.cpp:106-108
-  b->qstride[0] = (u32)b->L[0];
-  b->qstride[1] = (u32)b->L[1];
-  if (b->nm == 1 && (b->L[0] & 3) == 0 && b->L[0] >= 16 && b->L[0] <= 160) {
+  b->lpr = p->fasta ? 2 : 4;
+  b->nq = p->fasta || p->no_qualities;
+  b->qstride[0] = b->nq ? 0u : (u32)b->L[0];
+  b->qstride[1] = b->nq ? 0u : (u32)b->L[1];
+  if (b->nm == 1 && !b->nq && (b->L[0] & 3) == 0 && b->L[0] >= 16 && b->L[0] <= 160) {
     b->fused = true;
     b->row_cell_off = (u32)b->L[0];   // where the packed words begin
     b->row_pwords = (u32)(b->L[0] + 15) / 16;
@@ -633,7 +641,7 @@ static int batch_create(scalce_ctx *c, const scalce_params *p, uint64_t max_read
   }
   HIP_TRY(c, hipEventCreate(&b->ev0));
   HIP_TRY(c, hipEventCreate(&b->ev1));
-  for (int m = 0; m < b->nm; m++) {
+  for (int m = 0; m < b->nm && !b->nq; m++) {  // (nothing of the quality model without qualities)
     u8 lut[128];
     bool identity = p->qmap[m].offset >= 0 && p->qmap[m].offset < 128;
     for (int i = 0; i < 128; i++) {
@@ -646,8 +654,9 @@ static int batch_create(scalce_ctx *c, const scalce_params *p, uint64_t max_read
     ENSURE(b, b->freq4[m], sizeof(u64) * 512000);
     ENSURE(b, b->table[m], sizeof(u32) * 512000);
   }
-  // a record is at least "@x", L bases, "+", L qualities and four newlines: what one piece of max_text bytes can bring
-  const u64 per_piece = max_text / (2 * (u64)b->L[0] + 7) + 2;
+  // a record is at least "@x", L bases, "+", L qualities and four newlines (">x", L bases and two newlines under -f): what
+  // one piece of max_text bytes can bring
+  const u64 per_piece = max_text / (b->lpr == 2 ? (u64)b->L[0] + 4 : 2 * (u64)b->L[0] + 7) + 2;
   b->piece_rows_cap = per_piece < max_reads ? per_piece : max_reads;
   // (the line index of a piece, 32 bytes per record, is only built when something asks for it: ensure_line_index)
   { int rc = reserve_rows(b, max_reads, 0, nullptr); if (rc) return rc; }

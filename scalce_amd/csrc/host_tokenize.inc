@@ -497,7 +497,7 @@ extern "C" int scalce_batch_chunk_plan(scalce_batch *b, uint64_t carry_in, uint6
   ENSURE(b, b->chunk_start, sizeof(u64) * (cap + 8));
   u64 *S = b->S.as<u64>();
   if (b->S_rows != N) {
-    RecSize rs{b->tok_bucket.as<u32>(), c->d_bucket_level, b->namelen.as<u8>(), b->L[0], b->L[1], b->p.paired, b->p.use_names, 1};
+    RecSize rs{b->tok_bucket.as<u32>(), c->d_bucket_level, b->namelen.as<u8>(), b->L[0], b->L[1], b->p.paired, b->p.use_names, !b->nq};
     exclusive_scan<u64>(rs, N, StoreTo<u64>{S}, b->scan_ws.as<u64>(), S + N, s);
     b->S_rows = N;
   }
@@ -526,7 +526,7 @@ extern "C" int scalce_batch_text_offset(scalce_batch *b, int mate, uint64_t row,
   // on the caller's stream, behind the ingest that produced the tile counts, and in a word of its own (slot 7 belongs to
   // scalce_batch_chunk_plan's carry)
   u64 *d_out = b->d_small64 + 10;
-  LAUNCH(line_offset_k, 1, 64, 0, s, b->piece_text[mate], nbytes, b->tile[mate].as<u64>(), ntiles, (u64)(4 * row), d_out);
+  LAUNCH(line_offset_k, 1, 64, 0, s, b->piece_text[mate], nbytes, b->tile[mate].as<u64>(), ntiles, (u64)b->lpr * row, d_out);
   u64 v = 0;
   { int rc = read_u64(b, d_out, &v, 1, s); if (rc) return rc; }
   *offset = v;

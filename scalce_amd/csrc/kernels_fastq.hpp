@@ -1,6 +1,8 @@
 // Decode side, records back to FASTQ text: the per-record body of decompress.cpp:240-366 -- bucket of the
 // record, un-rotation of the 2-bit bases around the core (:331-345), N restore from quality 0 (:350-351), name line,
 // '+' line, qualities + phred offset.  One wavefront per run of records, one lane per output byte.
+// QUAL = false: an archive without qualities (-Q / -f): two-line records "@name\n" + bases + "\n" (decompress.cpp:323,347,358
+// with _compress_qualities = 0) -- no '+' line, no quality line, no N restore.
 #pragma once
 #include "prims.hpp"
 
@@ -20,7 +22,7 @@ struct FqArgs {
   u32 nbuckets;
   u64 nrecords;
   u32 L, sz_meta;           // sz_meta = 0: no end metadata (mate 2)
-  const u8 *qual;           // nrecords x L decoded quality symbols
+  const u8 *qual;           // nrecords x L decoded quality symbols (unused when QUAL = false)
   u32 phred;
   const u8 *names;          // [u8 n][n bytes]... or nullptr: library mode
   const u64 *name_off;      // start of each record's length byte, nrecords + 1 entries
@@ -45,7 +47,9 @@ __device__ __forceinline__ u32 fq_digits(u64 K) {
 
 constexpr int FQ_RECORDS_PER_WAVE = 32;
 
+template <bool QUAL>
 __global__ __launch_bounds__(256) void fastq_records_k(FqArgs a) {
+  constexpr u32 FIXED = QUAL ? 6 : 3;  // bytes of a record beside its name and its L bases (and L qualities): '@', newlines, '+'
   const int lane = lane_id();
   const u64 w = (u64)blockIdx.x * (blockDim.x / 64) + wave_id();
   const u64 k0 = w * FQ_RECORDS_PER_WAVE;
@@ -75,15 +79,15 @@ __global__ __launch_bounds__(256) void fastq_records_k(FqArgs a) {
       const u64 no = a.name_off[K];
       n = a.names[no];
       nm = a.names + no + 1;
-      at = (no - K) + K * (2ull * L + 6);
+      at = (no - K) + K * ((QUAL ? 2ull : 1ull) * L + FIXED);
     } else {
       n = a.lib_len + 1 + fq_digits(K);
-      at = K * (a.lib_len + 2ull * L + 7) + fq_digits_below(K);
+      at = K * (a.lib_len + (QUAL ? 2ull : 1ull) * L + FIXED + 1) + fq_digits_below(K);
     }
     if (a.rec_off && lane == 0) a.rec_off[K] = at;
-    const u8 *q = a.qual + K * (u64)L;
+    const u8 *q = QUAL ? a.qual + K * (u64)L : nullptr;
     u8 *o = a.out + at;
-    const u32 len = n + 2 * L + 6;
+    const u32 len = n + (QUAL ? 2 : 1) * L + FIXED;
     const bool patch = a.names && a.mate_digit && n > 1 && nm[n - 2] == '/';
     for (u32 t = lane; t < len; t += 64) {
       u8 c;
@@ -101,7 +105,7 @@ __global__ __launch_bounds__(256) void fastq_records_k(FqArgs a) {
       } else if (t == n + 1) c = '\n';
       else if (t < n + 2 + L) {
         const u32 i = t - (n + 2);
-        if (q[i] == 0) c = 'N';  // decompress.cpp:350-351
+        if (QUAL && q[i] == 0) c = 'N';  // decompress.cpp:350-351
         else {
           // stored order: the part behind the core, then the part in front of it (reads.cpp:432-461)
           u32 p;
@@ -112,7 +116,7 @@ __global__ __launch_bounds__(256) void fastq_records_k(FqArgs a) {
           else p = i - end;
           c = in_core ? (u8)bk.core[p] : (u8)"ACGT"[(rec[p >> 2] >> ((~p & 3) << 1)) & 3];
         }
-      } else if (t == n + 2 + L) c = '\n';
+      } else if (t == n + 2 + L || !QUAL) c = '\n';
       else if (t == n + 3 + L) c = '+';
       else if (t == n + 4 + L) c = '\n';
       else if (t < n + 5 + 2 * L) c = (u8)(q[t - (n + 5 + L)] + a.phred);

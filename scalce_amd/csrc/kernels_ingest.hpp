@@ -92,7 +92,7 @@ __global__ __launch_bounds__(IDX_THREADS) void index_write_k(const u8 *text, u64
 struct UnpackArgs {
   const u8 *text;
   u64 nbytes;
-  const u64 *line_end;  // 4 per record
+  const u64 *line_end;  // LPR per record (4: FASTQ; 2: FASTA, -f)
   u64 nrec;
   int L, stride, mate, use_names, no_ac;
   u8 *packed;     // nrec * stride, zero padded rows, base 4j..4j+3 in byte j, first base in bits 7-6
@@ -139,7 +139,10 @@ __device__ __forceinline__ u32 load_u32_unaligned(const u8 *t, u64 at, u64 n) {
   return (lo >> sh) | (hi << (32 - sh));
 }
 
-template <int PART, typename WordAt, typename ByteAt>
+// The record variants are template parameters of every ingest kernel: LPR = text lines per record (4: FASTQ; 2: FASTA, a name
+// line and one sequence line, compress.cpp:637,662) and QOUT = whether q' rows are written (false under -Q / -f: the quality
+// line of a FASTQ record is still checked for its length, nothing is made of it).
+template <int PART, int LPR, bool QOUT, typename WordAt, typename ByteAt>
 __device__ __forceinline__ void unpack_record_at(const UnpackArgs &a, u64 r, u64 ns, u64 p0, u64 p1, u64 p2, u64 p3, const u8 *lut,
                                                  WordAt word, ByteAt byte_at, u8 *qrow, bool qrow_aligned);
 // One record: bases -> 2-bit row (global), qualities -> q' (through `qrow`, LDS or global), name length.
@@ -147,17 +150,20 @@ __device__ __forceinline__ void unpack_record_at(const UnpackArgs &a, u64 r, u64
 // PART: 3 = the whole record; 1 = bases + name only, 2 = qualities only (unpack_tiled_k gives a record to two threads of
 // different waves: the work of a thread is a long chain of dependent instructions, and with the 40 KB tile per 128
 // records only two waves per SIMD were resident to hide it).
-template <int PART = 3, typename WordAt, typename ByteAt>
+template <int PART, int LPR, bool QOUT, typename WordAt, typename ByteAt>
 __device__ __forceinline__ void unpack_record(const UnpackArgs &a, u64 r, const u8 *lut, WordAt word, ByteAt byte_at, u8 *qrow,
                                               bool qrow_aligned) {
-  unpack_record_at<PART>(a, r, r ? a.line_end[4 * r - 1] + 1 : 0, a.line_end[4 * r], a.line_end[4 * r + 1], a.line_end[4 * r + 2],
-                         a.line_end[4 * r + 3], lut, word, byte_at, qrow, qrow_aligned);
+  const u64 *e = a.line_end + (u64)LPR * r;
+  unpack_record_at<PART, LPR, QOUT>(a, r, r ? e[-1] + 1 : 0, e[0], e[1], e[LPR - 2], e[LPR - 1], lut, word, byte_at, qrow, qrow_aligned);
 }
-// ns = where the record's name line starts, p0 .. p3 = the newlines that end its four lines (text offsets)
-template <int PART, typename WordAt, typename ByteAt>
+// ns = where the record's name line starts, p0 .. p3 = the newlines that end its four lines (text offsets; two-line records:
+// p2 = p3 = p1, nothing is read behind the sequence line)
+template <int PART, int LPR, bool QOUT, typename WordAt, typename ByteAt>
 __device__ __forceinline__ void unpack_record_at(const UnpackArgs &a, u64 r, u64 ns, u64 p0, u64 p1, u64 p2, u64 p3, const u8 *lut,
                                                  WordAt word, ByteAt byte_at, u8 *qrow, bool qrow_aligned) {
-  if (p1 - p0 - 1 != (u64)a.L || p3 - p2 - 1 != (u64)a.L) {
+  static_assert(LPR == 4 || (LPR == 2 && !QOUT), "two-line records have no qualities");
+  if (!QOUT && !(PART & 1)) return;  // (the quality half of a record has nothing to do)
+  if (p1 - p0 - 1 != (u64)a.L || (LPR == 4 && p3 - p2 - 1 != (u64)a.L)) {
     if (PART & 1) {
       dev_fail(a.err, E_READLEN, r, (u32)(p1 - p0 - 1));
       if (a.mate == 0) {  // the run ends with an error; until the host sees it, later stages must find a well-formed row
@@ -181,7 +187,7 @@ __device__ __forceinline__ void unpack_record_at(const UnpackArgs &a, u64 r, u64
   bool bad = false;
   for (int i = 0; i < L; i += 4) {
     u32 vb = fetch(sb + i);
-    u32 vq = fetch(sq + i);
+    u32 vq = QOUT ? fetch(sq + i) : 0u;
     const int rem = L - i;
     if (rem < 4) {  // last partial group: bytes beyond the line are not part of the read
       const u32 keep = (1u << (8 * rem)) - 1;
@@ -197,7 +203,7 @@ __device__ __forceinline__ void unpack_record_at(const UnpackArgs &a, u64 r, u64
         nacc = 0;
       }
     }
-    if (!(PART & 2)) continue;
+    if (!QOUT || !(PART & 2)) continue;
     // q' (qualities.cpp:183): exactly 'N' forces the offset, i.e. symbol 0
     const u32 isN = (zero_bytes(vb ^ 0x4E4E4E4Eu) >> 7) * 0xFFu;
     u32 qq;
@@ -255,6 +261,7 @@ struct LongNameLen {
   const u8 *namelen;
   __device__ u64 operator()(u64 r) const { return namelen[r] > 15 ? (u64)namelen[r] : 0ull; }
 };
+template <int LPR>
 __global__ __launch_bounds__(256) void long_names_k(u64 nrec, const u8 *text, const u64 *line_end, const u8 *namelen, u64 *off,
                                                    u64 store_base, u8 *store) {
   const u64 r = (u64)blockIdx.x * blockDim.x + threadIdx.x;
@@ -263,7 +270,7 @@ __global__ __launch_bounds__(256) void long_names_k(u64 nrec, const u8 *text, co
   off[r] = at;
   const u32 n = namelen[r];
   if (n <= 15) return;
-  const u64 src = (r ? line_end[4 * r - 1] + 1 : 0) + 1;  // behind the '@'
+  const u64 src = (r ? line_end[(u64)LPR * r - 1] + 1 : 0) + 1;  // behind the '@' (or '>')
   for (u32 i = 0; i < n; i++) store[at + i] = text[src + i];
 }
 
@@ -294,19 +301,21 @@ __global__ __launch_bounds__(64) void line_offset_k(const u8 *text, u64 nbytes, 
   if (threadIdx.x == 0) *out = nbytes;  // fewer lines than asked for
 }
 
+template <int LPR>
 __global__ void last_record_end_k(const u64 *line_end, u64 nrec, u64 *out) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) *out = nrec ? line_end[4 * nrec - 1] + 1 : 0;
+  if (threadIdx.x == 0 && blockIdx.x == 0) *out = nrec ? line_end[(u64)LPR * nrec - 1] + 1 : 0;
 }
 
 // direct form: every thread reads its record straight from global memory (fallback for long reads / huge names)
+template <int LPR, bool QOUT>
 __global__ __launch_bounds__(256) void unpack_k(UnpackArgs a) {
   __shared__ u8 lut[128];
-  if (threadIdx.x < 128) lut[threadIdx.x] = a.qlut[threadIdx.x];
+  if (QOUT && threadIdx.x < 128) lut[threadIdx.x] = a.qlut[threadIdx.x];
   __syncthreads();
   const u64 r = (u64)blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= a.nrec) return;
-  u8 *qrow = a.q + r * (u64)a.L;
-  unpack_record(a, r, lut, [&](u64 at) { return load_word(a.text, at & ~3ull, a.nbytes); },
+  u8 *qrow = QOUT ? a.q + r * (u64)a.L : nullptr;
+  unpack_record<3, LPR, QOUT>(a, r, lut, [&](u64 at) { return load_word(a.text, at & ~3ull, a.nbytes); },
                 [&](u64 at) { return a.text[at]; }, qrow, ((u64)qrow & 3) == 0);
 }
 
@@ -318,6 +327,7 @@ constexpr int UNP_RPB = 128;
 constexpr int UNP_Q_CAP = 20 * 1024;  // UNP_RPB * L must fit: L <= 160
 __host__ __device__ inline u32 unp_text_cap(int L) { return (u32)(((UNP_RPB * (2 * L + 20) + 64) + 15) & ~15); }
 __host__ __device__ inline u32 unp_q_cap(int L) { return (u32)((UNP_RPB * L + 15) & ~15); }
+template <int LPR, bool QOUT>
 __global__ __launch_bounds__(2 * UNP_RPB) void unpack_tiled_k(UnpackArgs a) {
   extern __shared__ __attribute__((aligned(16))) u8 unp_lds[];
   const u32 UNP_TEXT_CAP = unp_text_cap(a.L);
@@ -325,11 +335,11 @@ __global__ __launch_bounds__(2 * UNP_RPB) void unpack_tiled_k(UnpackArgs a) {
   u8 *qt = unp_lds + UNP_TEXT_CAP + 32;
   __shared__ u8 lut[128];
   const int tid = threadIdx.x;
-  if (tid < 128) lut[tid] = a.qlut[tid];
+  if (QOUT && tid < 128) lut[tid] = a.qlut[tid];
   const u64 r0 = (u64)blockIdx.x * UNP_RPB;
   const u64 r1 = r0 + UNP_RPB < a.nrec ? r0 + UNP_RPB : a.nrec;
-  const u64 span0 = r0 ? a.line_end[4 * r0 - 1] + 1 : 0;
-  const u64 span1 = a.line_end[4 * (r1 - 1) + 3] + 1;
+  const u64 span0 = r0 ? a.line_end[(u64)LPR * r0 - 1] + 1 : 0;
+  const u64 span1 = a.line_end[(u64)LPR * r1 - 1] + 1;
   const u64 a0 = span0 & ~15ull;
   const u64 tbytes = span1 - a0;
   const bool in_lds = tbytes <= (u64)UNP_TEXT_CAP;  // uniform for the workgroup
@@ -359,13 +369,14 @@ __global__ __launch_bounds__(2 * UNP_RPB) void unpack_tiled_k(UnpackArgs a) {
     auto w_glb = [&](u64 at) { return load_word(a.text, at & ~3ull, a.nbytes); };
     auto b_glb = [&](u64 at) { return a.text[at]; };
     if (in_lds) {
-      if (second) unpack_record<2>(a, r, lut, w_lds, b_lds, qrow, al);
-      else unpack_record<1>(a, r, lut, w_lds, b_lds, qrow, al);
+      if (second) unpack_record<2, LPR, QOUT>(a, r, lut, w_lds, b_lds, qrow, al);
+      else unpack_record<1, LPR, QOUT>(a, r, lut, w_lds, b_lds, qrow, al);
     } else {
-      if (second) unpack_record<2>(a, r, lut, w_glb, b_glb, qrow, al);
-      else unpack_record<1>(a, r, lut, w_glb, b_glb, qrow, al);
+      if (second) unpack_record<2, LPR, QOUT>(a, r, lut, w_glb, b_glb, qrow, al);
+      else unpack_record<1, LPR, QOUT>(a, r, lut, w_glb, b_glb, qrow, al);
     }
   }
+  if (!QOUT) return;  // (no q' rows to write out)
   __syncthreads();
   // q' rows of this workgroup are one contiguous range of the output
   const u64 qbytes = (r1 - r0) * (u64)a.L;
@@ -412,7 +423,8 @@ struct Ingest2Args {
   u32 step_ks, step_rs, step_kw, step_rw;  // 256 / S, 256 % S, 256 / W, 256 % W
   u16 *tile_minmax;       // per tile: min | max << 8 of its q' symbols (255 | 0 << 8: none), or null
 };
-constexpr u32 ING2_RECMAX = ING_NLMAX / 4 + 4;
+// records that END in tile + overlap: at most one per LPR newlines (two-line records: twice as many as FASTQ's)
+template <int LPR> constexpr u32 ing2_recmax() { return ING_NLMAX / LPR + 4; }
 typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
 typedef u32 u32x4a __attribute__((ext_vector_type(4), aligned(4)));  // sixteen bytes at a 4-byte boundary
 __device__ __forceinline__ u32 pk_min_u16(u32 a, u32 b) {
@@ -425,11 +437,15 @@ __device__ __forceinline__ u32 lds_fetch_u32(const u8 *text, u32 at) {  // unali
   const u32 *p = reinterpret_cast<const u32 *>(text + (at & ~3u));
   return __builtin_amdgcn_alignbyte(p[1], p[0], at & 3u);
 }
+// LPR, QOUT: see unpack_record_at.  LDS: 17.4 KB of text, 4 KB of newlines, the record starts (2 KB for FASTQ; 2 KB for
+// two-line records, which need no quality starts): about 24 KB either way.
+template <int LPR, bool QOUT>
 __global__ __launch_bounds__(ING_THREADS) void ingest_tiles2_k(Ingest2Args g) {
   const IngestArgs &a = g.i;
+  constexpr u32 RECMAX = ing2_recmax<LPR>();
   __shared__ __attribute__((aligned(16))) u8 text[ING_TILE + ING_OVER + 32];
   __shared__ u16 nl[ING_NLMAX];
-  __shared__ u16 rec_sb[ING2_RECMAX], rec_sq[ING2_RECMAX];
+  __shared__ u16 rec_sb[RECMAX], rec_sq[QOUT ? RECMAX : 1];
   __shared__ u8 lut[128];
   __shared__ u32 sm[ING_THREADS / 64];
   __shared__ u32 s_count[2];
@@ -439,7 +455,7 @@ __global__ __launch_bounds__(ING_THREADS) void ingest_tiles2_k(Ingest2Args g) {
   const u64 t0 = (u64)ti * ING_TILE;                               // text offset of the tile
   const u64 avail = a.u.nbytes - t0;
   const u32 len = (u32)(avail < ING_TILE + ING_OVER ? avail : ING_TILE + ING_OVER);
-  if (tid < 128) lut[tid] = a.u.qlut[tid];
+  if (QOUT && tid < 128) lut[tid] = a.u.qlut[tid];
   if (tid == 0) s_count[1] = 0;
   for (u32 i = (u32)tid * 16; i < len + 8; i += ING_THREADS * 16) {
     uint4 v;
@@ -499,13 +515,13 @@ __global__ __launch_bounds__(ING_THREADS) void ingest_tiles2_k(Ingest2Args g) {
   const u64 G0 = a.tile_base[(u64)ti * (ING_TILE / IDX_TILE)];
   const bool starts_line = t0 == 0 || a.u.text[t0 - 1] == '\n';
   const u32 jmin = starts_line ? 0u : 1u;
-  const u32 j0 = jmin + (u32)((4 - ((G0 + jmin) & 3)) & 3);         // first name line that starts here
-  const u64 rid0 = (G0 + j0) >> 2;
-  const u32 nloc = j0 < count ? (count - j0 + 3) / 4 : 0u;         // name lines that END in tile + overlap
+  const u32 j0 = jmin + (u32)((LPR - ((G0 + jmin) % LPR)) % LPR);  // first name line that starts here
+  const u64 rid0 = (G0 + j0) / LPR;
+  const u32 nloc = j0 < count ? (count - j0 + LPR - 1) / LPR : 0u;  // name lines that END in tile + overlap (<= RECMAX)
   const int L = a.u.L;
   // one thread per record: is it this tile's (it STARTS here and is whole), are its lines as long as they must be, its name
   for (u32 k = (u32)tid; k < nloc; k += ING_THREADS) {
-    const u32 j = j0 + 4 * k;
+    const u32 j = j0 + LPR * k;
     const u64 rid = rid0 + k;
     bool take = rid < a.u.nrec;
     u32 ns = 0;
@@ -514,18 +530,18 @@ __global__ __launch_bounds__(ING_THREADS) void ingest_tiles2_k(Ingest2Args g) {
       if (j && j - 1 >= count) take = false;
       else if (ns >= ING_TILE) take = false;                        // starts in the next tile: that workgroup's record
     }
-    if (take && j + 3 >= count) {                                   // its four lines must end inside tile + overlap
+    if (take && j + LPR - 1 >= count) {                             // all its lines must end inside tile + overlap
       take = false;
       atomicExch(a.slow, 1u);
     }
     if (!take) continue;
     atomicAdd(&s_count[1], 1u);                                     // (the records taken are the first ones: a prefix of k)
-    const u32 p0 = nl[j], p1 = nl[j + 1], p2 = nl[j + 2], p3 = nl[j + 3];
+    const u32 p0 = nl[j], p1 = nl[j + 1], p2 = nl[j + LPR - 2], p3 = nl[j + LPR - 1];  // (two-line records: p2 = p3 = p1)
     if (rid + 1 == a.u.nrec) *a.consumed = t0 + p3 + 1;
-    if (p1 - p0 - 1 != (u32)L || p3 - p2 - 1 != (u32)L) {
+    if (p1 - p0 - 1 != (u32)L || (LPR == 4 && p3 - p2 - 1 != (u32)L)) {
       dev_fail(a.u.err, E_READLEN, rid, p1 - p0 - 1);
       rec_sb[k] = 0xFFFFu;                                          // nothing of it is unpacked
-      rec_sq[k] = 0xFFFFu;
+      if (QOUT) rec_sq[k] = 0xFFFFu;
       if (a.u.mate == 0) {  // the run ends with an error; until the host sees it, later stages must find a well-formed row
         a.u.namelen[rid] = 0;
         if (a.u.namecell) { u32x4a z; z.x = z.y = z.z = z.w = 0; *reinterpret_cast<u32x4a *>(a.u.namecell + (u64)a.u.cellstride * rid) = z; }
@@ -533,7 +549,7 @@ __global__ __launch_bounds__(ING_THREADS) void ingest_tiles2_k(Ingest2Args g) {
       continue;
     }
     rec_sb[k] = (u16)(p0 + 1);
-    rec_sq[k] = (u16)(p2 + 1);
+    if (QOUT) rec_sq[k] = (u16)(p2 + 1);
     if (a.u.mate == 0) {
       // output_name, names.cpp:55-57: characters after '@' up to the first space or the newline
       u32 nlen = 0;
@@ -604,6 +620,7 @@ __global__ __launch_bounds__(ING_THREADS) void ingest_tiles2_k(Ingest2Args g) {
       if (w >= S) { w -= S; k++; }
     }
   }
+  if (!QOUT) return;  // (-Q / -f: no q' rows, no symbol range; the whole workgroup leaves here)
   // qualities: one unit = sixteen symbols (the last unit of a read: what is left, computed like a whole one and cut when it
   // is stored); q' (qualities.cpp:183): exactly 'N' forces the offset, i.e. symbol 0
   // smallest / largest symbol: packed 16-bit min / max order their halves by the HIGH byte, so a word as it is gives the

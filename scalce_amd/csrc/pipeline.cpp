@@ -76,6 +76,14 @@ extern "C" int scalce_pipeline_create(scalce_batch **batches, int nslots, int gr
     p->err = "group " + std::to_string(group) + " is above SCALCE_GROUP_MAX (" + std::to_string(SCALCE_GROUP_MAX) + " shards per coder launch)";
     return SCALCE_ERR_ARG;
   }
+  for (int i = 0; i < nslots; i++) {
+    scalce_params bp;
+    if (!batches[i] || scalce_batch_params(batches[i], &bp) != SCALCE_OK) { p->err = "a slot without a batch"; return SCALCE_ERR_ARG; }
+    if (bp.fasta || bp.no_qualities) {  // (nothing to code: the pipeline exists for the coder launches)
+      p->err = "records without qualities (-f / -Q) have no coder stage: the pipeline does not take them";
+      return SCALCE_ERR_ARG;
+    }
+  }
   p->b.assign(batches, batches + nslots);
   p->G = group;
   p->external = external_coder != 0;

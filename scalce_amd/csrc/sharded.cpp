@@ -28,6 +28,8 @@
 
 #include "../../include/scalce_hip.h"
 
+void scalce_set_last_error(scalce_ctx *c, const char *msg);  // (host_state.inc: the message scalce_last_error returns)
+
 namespace {
 
 typedef uint64_t u64;
@@ -211,6 +213,14 @@ extern "C" int scalce_sharded_compress(scalce_comm *comm, scalce_ctx *ctx, scalc
                                        const uint8_t *d_text2, uint64_t n2, int flags, void *stream, void *coder_stream,
                                        scalce_shard_result *res) {
   if (!comm || !ctx || !b || !res) return SCALCE_ERR_ARG;
+  {
+    scalce_params bp;
+    if (scalce_batch_params(b, &bp) != SCALCE_OK) return SCALCE_ERR_ARG;
+    if (bp.fasta || bp.no_qualities) {
+      scalce_set_last_error(ctx, "records without qualities (-f / -Q) are compressed on one GPU: sharded runs do not take them");
+      return SCALCE_ERR_ARG;
+    }
+  }
   hipStream_t s = (hipStream_t)stream;
   const int W = scalce_comm_world(comm), rank = scalce_comm_rank(comm);
   if (W > 64) return SCALCE_ERR_ARG;

@@ -160,7 +160,8 @@ extern "C" int scalce_stream_compress(scalce_ctx *ctx, const scalce_params *p, s
     }
   }
   {
-    const uint64_t rows0 = reads_hint ? reads_hint + 16 : piece / (2 * (uint64_t)p->read_len[0] + 7) + 16;
+    const uint64_t rec_min = p->fasta ? (uint64_t)p->read_len[0] + 4 : 2 * (uint64_t)p->read_len[0] + 7;  // (">x", bases, two newlines)
+    const uint64_t rows0 = reads_hint ? reads_hint + 16 : piece / rec_min + 16;
     rc = scalce_batch_create(ctx, p, rows0, cap + 256, &b);
     if (rc) { err = scalce_last_error(ctx); goto fail_rc; }
     scalce_batch_set_lean(b, (flags & SCALCE_STREAM_LEAN) ? 1 : 0);

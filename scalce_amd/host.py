@@ -33,7 +33,8 @@ class QMap(C.Structure):
 
 class Params(C.Structure):
     _fields_ = [("read_len", C.c_int32 * 2), ("paired", C.c_int32), ("use_names", C.c_int32), ("no_ac", C.c_int32),
-                ("qmap", QMap * 2), ("bucket_set_size", C.c_uint64), ("qprev", (C.c_uint32 * 2) * 2)]
+                ("qmap", QMap * 2), ("bucket_set_size", C.c_uint64), ("qprev", (C.c_uint32 * 2) * 2),
+                ("fasta", C.c_int32), ("no_qualities", C.c_int32)]
 
 
 class ShardResult(C.Structure):
@@ -149,6 +150,8 @@ def lib():
     L.scalce_ac_decode.argtypes = [vp, vp, vp, u64, u64, vp, vp]
     L.scalce_fastq_text_bytes.restype = u64
     L.scalce_fastq_text_bytes.argtypes = [i32, u64, u64, C.c_char_p]
+    L.scalce_fasta_text_bytes.restype = u64
+    L.scalce_fasta_text_bytes.argtypes = [i32, u64, u64, C.c_char_p]
     L.scalce_fastq_records.argtypes = [vp, i32, i32, vp, u64, u64, vp, C.c_int64, vp, u64, C.c_char_p, i32, vp, u64,
                                        C.POINTER(u64), vp, vp]
     _LIB = L
@@ -229,12 +232,14 @@ class Context:
 
     def fastq_records(self, read_len, reads_payload, nrecords, d_qual, phred, names_payload=None, library=None, has_buckets=True,
                       mate_digit=0, stream=0):
-        """Records back to FASTQ text on the device (scalce_fastq_records); returns the text as bytes."""
+        """Records back to FASTQ text on the device (scalce_fastq_records); returns the text as bytes.  d_qual = None: the
+        two-line records of an archive without qualities."""
         import torch
         reads = np.frombuffer(reads_payload, dtype=np.uint8)
         names = None if names_payload is None else np.frombuffer(names_payload, dtype=np.uint8)
         lib = None if library is None else library.encode()
-        cap = self.L.scalce_fastq_text_bytes(read_len, nrecords, 0 if names is None else len(names), None if names is not None else lib)
+        text_bytes = self.L.scalce_fastq_text_bytes if d_qual is not None else self.L.scalce_fasta_text_bytes
+        cap = text_bytes(read_len, nrecords, 0 if names is None else len(names), None if names is not None else lib)
         out = torch.empty(cap + 64, dtype=torch.uint8, device=f"cuda:{self.device}")
         nb = C.c_uint64(0)
         self._check(self.L.scalce_fastq_records(self.h, read_len, int(has_buckets), reads.ctypes.data, len(reads), nrecords, d_qual,
@@ -404,7 +409,7 @@ class Batch:
     """One FASTQ shard in HBM (scalce_batch)."""
 
     def __init__(self, ctx, read_len, max_reads, max_text, paired=False, use_names=True, no_ac=False, qmap=None,
-                 bucket_set_size=0, read_len2=0, qprev=None, workspace=None):
+                 bucket_set_size=0, read_len2=0, qprev=None, workspace=None, fasta=False, no_qualities=False):
         self.ctx = ctx
         self.L = ctx.L
         p = Params()
@@ -413,6 +418,7 @@ class Batch:
         p.read_len[1] = int(read_len2 or read_len) if paired else 0
         p.paired, p.use_names, p.no_ac = int(paired), int(use_names), int(no_ac)
         p.bucket_set_size = int(bucket_set_size)
+        p.fasta, p.no_qualities = int(fasta), int(no_qualities)  # two-line records (-f) / qualities dropped (-Q)
         if qmap is not None:  # [(offset, values)] per mate
             for m, (off, vals) in enumerate(qmap):
                 p.qmap[m].offset = int(off)
