@@ -48,6 +48,18 @@ int scalce_patterns_load_text(scalce_ctx *ctx, const char *text, size_t nbytes);
 int scalce_patterns_count(const scalce_ctx *ctx);   /* cores in file order (the index .scalcer stores) */
 int scalce_patterns_states(const scalce_ctx *ctx);  /* automaton states, root included */
 int scalce_patterns_buckets(const scalce_ctx *ctx); /* distinct cores = buckets, root excluded */
+/* The tokenizer walk the loaded table selects (decided from the table alone when it is loaded):
+ *   SCALCE_WALK_KMER     k-mer tables of the states of depth <= 8 (tokenize_kmer_pipe_k), no core under 8 bases
+ *   SCALCE_WALK_KMER_T7  the same, some core has fewer than 8 bases
+ *   SCALCE_WALK_ANCHOR   anchors of K = min(shortest core, 12) bases (tokenize_anchor_k); *anchor_k = K
+ *   SCALCE_WALK_STATES   the automaton alone (tokenize_k)
+ * SCALCE_WALK_NONE without a table.  *anchor_k (may be null) is 0 unless the walk is SCALCE_WALK_ANCHOR. */
+#define SCALCE_WALK_NONE 0
+#define SCALCE_WALK_KMER 1
+#define SCALCE_WALK_KMER_T7 2
+#define SCALCE_WALK_ANCHOR 3
+#define SCALCE_WALK_STATES 4
+int scalce_patterns_walk(const scalce_ctx *ctx, int *anchor_k);
 /* core string / length by file-order index (decompress.cpp:269,341 use patterns[core]) */
 int scalce_pattern_length(const scalce_ctx *ctx, int pattern);
 const char *scalce_pattern_string(const scalce_ctx *ctx, int pattern);

@@ -258,6 +258,21 @@ extern "C" int scalce_patterns_load_text(scalce_ctx *c, const char *text, size_t
 extern "C" int scalce_patterns_count(const scalce_ctx *c) { return c ? (int)c->A.patterns.size() : 0; }
 extern "C" int scalce_patterns_states(const scalce_ctx *c) { return c ? c->A.n_states : 0; }
 extern "C" int scalce_patterns_buckets(const scalce_ctx *c) { return c ? c->A.n_buckets : 0; }
+// the walk both tokenizer passes take (first_walk, the tie candidates): decided by the loaded table alone.  (STATES is not
+// reached from a loaded table: ids are BFS ranks with children in A,C,G,T order, so the k-mer tables' checks always hold.)
+static int token_walk(const scalce_ctx *c) {
+  if (!c->have_patterns) return SCALCE_WALK_NONE;
+  if (c->anchor_K) return SCALCE_WALK_ANCHOR;
+  if (c->d_kmer) return c->kmer_t7_out ? SCALCE_WALK_KMER_T7 : SCALCE_WALK_KMER;
+  return SCALCE_WALK_STATES;
+}
+extern "C" int scalce_patterns_walk(const scalce_ctx *c, int *anchor_k) {
+  if (anchor_k) *anchor_k = 0;
+  if (!c) return SCALCE_WALK_NONE;
+  const int w = token_walk(c);
+  if (anchor_k && w == SCALCE_WALK_ANCHOR) *anchor_k = (int)c->anchor_K;
+  return w;
+}
 extern "C" int scalce_pattern_length(const scalce_ctx *c, int p) {
   return (c && p >= 0 && p < (int)c->A.patterns.size()) ? (int)c->A.patterns[p].size() : -1;
 }

@@ -11,15 +11,14 @@ static int first_walk(scalce_batch *b, u64 row0, u64 n, u64 tok_row0, hipStream_
   a.root_bucket = (u32)c->A.n_buckets; a.tok_bucket = b->tok_bucket.as<u32>() + (row0 - tok_row0); a.tok_pos = b->tok_pos.as<u32>() + (row0 - tok_row0);
   const size_t sh = (size_t)a.lds_states * 20;
   a.kmer = c->d_kmer; a.id8_first = c->id8_first;
-  if (c->anchor_K) {
+  const int walk = token_walk(c);
+  if (walk == SCALCE_WALK_ANCHOR) {
     AnchorArgs g;
     anchor_args(c, b, packed0, n, g);
     g.tok_bucket = a.tok_bucket; g.tok_pos = a.tok_pos;
     LAUNCH(tokenize_anchor_k<false>, cdiv(n, 256), 256, 0, s, g);
-  } else if (c->d_kmer) {
-    if (c->kmer_t7_out) LAUNCH(tokenize_kmer_pipe_k<true>, cdiv(n, TOKP_THREADS), TOKP_THREADS, 0, s, a);
-    else LAUNCH(tokenize_kmer_pipe_k<false>, cdiv(n, TOKP_THREADS), TOKP_THREADS, 0, s, a);
-  }
+  } else if (walk == SCALCE_WALK_KMER_T7) LAUNCH(tokenize_kmer_pipe_k<true>, cdiv(n, TOKP_THREADS), TOKP_THREADS, 0, s, a);
+  else if (walk == SCALCE_WALK_KMER) LAUNCH(tokenize_kmer_pipe_k<false>, cdiv(n, TOKP_THREADS), TOKP_THREADS, 0, s, a);
   else if (a.lds_states) LAUNCH(tokenize_k<true>, cdiv(n, TOK_THREADS), TOK_THREADS, sh, s, a);
   else LAUNCH(tokenize_k<false>, cdiv(n, TOK_THREADS), TOK_THREADS, 0, s, a);
   return SCALCE_OK;
@@ -100,16 +99,15 @@ extern "C" int scalce_batch_tokenize_begin(scalce_batch *b, void *stream) {
     a.tie_ncand = b->tie_ncand.as<u32>();
     a.lds_states = (u32)c->tok_lds_states;
     a.kmer = c->d_kmer; a.id8_first = c->id8_first;
-    if (c->anchor_K) {
+    const int walk = token_walk(c);
+    if (walk == SCALCE_WALK_ANCHOR) {
       AnchorArgs g;
       anchor_args(c, b, packed0, N, g);
       g.ntie = ntie; g.tie_read = a.tie_read; g.tie_off = a.tie_off; g.bucket_level = a.bucket_level;
       g.cand_bucket = a.cand_bucket; g.cand_pos = a.cand_pos; g.tie_ncand = a.tie_ncand;
       LAUNCH(tokenize_anchor_k<true>, cdiv(ntie, 256), 256, 0, s, g);
-    } else if (c->d_kmer) {
-      if (c->kmer_t7_out) LAUNCH(tie_candidates_pipe_k<true>, cdiv(ntie, TOKP_THREADS), TOKP_THREADS, 0, s, a);
-      else LAUNCH(tie_candidates_pipe_k<false>, cdiv(ntie, TOKP_THREADS), TOKP_THREADS, 0, s, a);
-    }
+    } else if (walk == SCALCE_WALK_KMER_T7) LAUNCH(tie_candidates_pipe_k<true>, cdiv(ntie, TOKP_THREADS), TOKP_THREADS, 0, s, a);
+    else if (walk == SCALCE_WALK_KMER) LAUNCH(tie_candidates_pipe_k<false>, cdiv(ntie, TOKP_THREADS), TOKP_THREADS, 0, s, a);
     else if (a.lds_states) LAUNCH(tie_candidates_k<true>, cdiv(ntie, TOK_THREADS), TOK_THREADS, (size_t)a.lds_states * 20, s, a);
     else LAUNCH(tie_candidates_k<false>, cdiv(ntie, TOK_THREADS), TOK_THREADS, 0, s, a);
     HIP_TRY(c, hipMemsetAsync(b->choice.p, 0, sizeof(u32) * ntie, s));

@@ -46,6 +46,8 @@ class ShardResult(C.Structure):
 
 
 SHARD_PREPARE_ONLY, SHARD_CODER_ASYNC = 1, 2
+# scalce_patterns_walk, by SCALCE_WALK_* value
+WALKS = ("none", "kmer", "kmer_t7", "anchor", "states")
 
 
 def lib():
@@ -74,6 +76,7 @@ def lib():
     L.scalce_patterns_load_text.argtypes = [vp, C.c_char_p, C.c_size_t]
     for f in ("scalce_patterns_count", "scalce_patterns_states", "scalce_patterns_buckets"):
         getattr(L, f).argtypes = [vp]
+    L.scalce_patterns_walk.argtypes = [vp, C.POINTER(C.c_int)]
     L.scalce_pattern_length.argtypes = [vp, i32]
     L.scalce_pattern_string.argtypes = [vp, i32]
     L.scalce_pattern_string.restype = C.c_char_p
@@ -196,6 +199,13 @@ class Context:
     @property
     def n_buckets(self):
         return self.L.scalce_patterns_buckets(self.h)
+
+    @property
+    def walk(self):
+        """The tokenizer walk the loaded table selects: (name, K) with name one of WALKS; K > 0 only for "anchor"."""
+        k = C.c_int(0)
+        w = self.L.scalce_patterns_walk(self.h, C.byref(k))
+        return WALKS[w], k.value
 
     def pattern(self, p):
         return self.L.scalce_pattern_string(self.h, p)
