@@ -9,14 +9,19 @@ scalce_sharded_compress, the C++ host of scalce_amd/csrc/sharded.cpp over RCCL (
 tie-break, quality model and 10 MiB block cutting, byte-identical with the one-GPU archive of the same input.
 torch.distributed is only used to hand RCCL's unique id to the ranks and for the timing barrier.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with these extra objects:
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times the steps, writes
+--dump-outputs and prints the line; beside the headline it carries only what the timed run itself yields:
   roofline       -- SURVEY 8(d): algorithmic bytes of a step (308 B per read) / ms_per_step against the 8 TB/s HBM peak;
                     beside it the dominant kernel's own views (HBM bytes and issue slots per launch, HIP events)
+--full adds the legs that take runs of their own (over a minute more on one GPU):
+  value_single_job -- one shard alone, nothing in flight beside it (that shard runs in every run: the timed steps follow it)
   cpu_baseline   -- the reference's own compress() (oracle/_ref/ref_full: every reference source but main.cpp, built in
                     the dev container, the binary travels) at -T 1 and at its default thread count, on a bounded sample
   parity_checked -- the run proves its own output: the LAST timed shard is decoded on the device back to FASTQ text whose
                     record multiset equals the input's, and the sample of the CPU leg gives byte-identical archives
-                    through the `scalce` binary and through the reference
+                    through the `scalce` binary and through the reference (false in a plain run: nothing is checked)
+  decode, e2e, table_scale -- the inverse path on the last shard, the `scalce` binary file to archive, the tokenizer on a
+                    core table of a million cores
 One GPU on its own plans its coder launches for the length of the run (--launch-plan waves, config.launch_plan): a launch
 takes ~0.5 s whether it holds five shards or fifteen, so the remainder of the run goes first and every later launch fills
 all slots and all CUs; --launch-plan eager is the pipeline of a stream of unknown length (a launch per six shards).
@@ -51,11 +56,14 @@ def main():
                          "1 = one launch per shard with the one-block-per-workgroup kernel")
     ap.add_argument("--reads", type=int, default=50_000_000, help="reads per GPU")
     ap.add_argument("--length", type=int, default=100)
-    ap.add_argument("--cpu-sample", type=int, default=1_500_000, help="records of the CPU baseline sample (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline: the self-checks, the CPU baseline, the single-job figure, decode, e2e "
+                         "and table_scale (the --no-* switches and --cpu-sample below drop some of them again)")
+    ap.add_argument("--cpu-sample", type=int, default=1_500_000, help="--full: records of the CPU baseline sample (0 = skip)")
     ap.add_argument("--stage-times", action="store_true", help="also print per-stage HIP-event times to stderr")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the file -> archive leg (the `scalce` binary on the same shard written to a file)")
-    ap.add_argument("--no-verify", action="store_true", help="skip the self-check of the last timed shard (device decode + record digest)")
-    ap.add_argument("--no-table-scale", action="store_true", help="skip the tokenizer leg on a core table of a million cores")
+    ap.add_argument("--no-e2e", action="store_true", help="--full: skip the file -> archive leg (the `scalce` binary on the same shard written to a file)")
+    ap.add_argument("--no-verify", action="store_true", help="--full: skip the self-check of the last timed shard (device decode + record digest)")
+    ap.add_argument("--no-table-scale", action="store_true", help="--full: skip the tokenizer leg on a core table of a million cores")
     ap.add_argument("--launch-plan", choices=("waves", "eager"), default="waves",
                     help="one GPU on its own: `waves` = coder launches that fill every slot, the remainder of the run first (a launch takes "
                          "~0.5 s whatever it holds); `eager` = a launch as soon as `--group` shards are ready, side by side (what a stream of "
@@ -344,7 +352,10 @@ def main():
     run(warm)
     barrier()
     t1 = time.perf_counter()
-    run(1)  # one shard alone, nothing in flight beside it: the latency of a single job
+    # one shard alone, nothing in flight beside it: the latency of a single job (value_single_job, --full).  A plain run takes
+    # it too: the timed steps follow it -- it decides the slot, and so the text, of every timed step, and with --warmup 0 it
+    # is where the first launches start up
+    run(1)
     barrier()
     single_ms = (time.perf_counter() - t1) * 1e3
     for b in batches:
@@ -371,7 +382,7 @@ def main():
     # ---- the run proves its own output (never inside the timed region) ----
     parity = {}
     decode = None
-    if sharded and not args.no_verify:
+    if sharded and args.full and not args.no_verify:
         from scalce_amd import verify
         last_slot = (pipe._next - 1) % DF
         # (1) one rank (SCALCE_BENCH_FORCE_SHARDED=1: every collective a real RCCL call of one rank) builds the whole archive in one
@@ -435,7 +446,7 @@ def main():
                                                  "device, the symbols return to the ranks that emitted the records, every rank rebuilds its records' FASTQ "
                                                  "text; (count, two 64-bit sums of per-record hashes) summed over the ranks equal to the input texts'",
                                          "seconds": round(time.perf_counter() - tv0, 2)}
-    if rank == 0 and not sharded and not args.no_verify:
+    if rank == 0 and not sharded and args.full and not args.no_verify:
         from scalce_amd import verify
         # the checks need room (5 GB of symbols, 10.8 GB of text, the digest's temporaries): everything but slot 0 and the slot
         # of the last timed shard goes first
@@ -503,13 +514,13 @@ def main():
             parity["ref_full_shard"] = {"ok": False, "error": repr(ex)[:300]}
 
     cpu = None
-    if rank == 0 and args.cpu_sample > 0:   # (rank 0's host cores, rank 0's own shard: any number of ranks)
+    if rank == 0 and args.full and args.cpu_sample > 0:   # (rank 0's host cores, rank 0's own shard: any number of ranks)
         try:
             cpu, parity["sample"] = cpu_baseline(text, n, L, args.cpu_sample)
         except Exception as ex:  # noqa: BLE001
             cpu = {"error": repr(ex)[:300]}
     e2e = None
-    if rank == 0 and world == 1 and not args.no_e2e:
+    if rank == 0 and world == 1 and args.full and not args.no_e2e:
         for b in batches:   # the CLI is a process of its own and needs the card's memory
             b.close()
         del batches[:], pipe, pipes[:]
@@ -521,7 +532,7 @@ def main():
             e2e = {"error": repr(ex)[:300]}
 
     table_scale = None
-    if rank == 0 and world == 1 and not args.no_table_scale and not args.no_e2e:
+    if rank == 0 and world == 1 and args.full and not args.no_table_scale and not args.no_e2e:
         try:
             table_scale = table_scale_leg(dev)
         except Exception as ex:  # noqa: BLE001
@@ -572,6 +583,7 @@ def main():
             issue = {"achieved": round(ips / 1e9, 2), "peak": round(1024 * 2.4, 1), "unit": "Ginstr/s", "frac": round(ips / (1024 * 2.4e9), 4),
                      "instr_per_symbol": round(instr_per_symbol, 3), "issue_source": issue_src}
         parity_checked = bool(parity) and all(v.get("ok") for v in parity.values())
+        single = single_ms if args.full else None   # (the shard alone runs in every run, its figure is --full's)
         line = {
             "metric": "input FASTQ MB/s compressed, 100 bp reads, bit-exact decompress",
             "value": round(value, 2),
@@ -580,7 +592,7 @@ def main():
             "steps": args.steps,
             "warmup": warm,
             "ms_per_step": round(ms_per_step, 3),
-            "value_single_job": round(nbytes / single_ms / 1e3, 2) if single_ms else None,
+            "value_single_job": round(nbytes / single / 1e3, 2) if single else None,
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,
@@ -603,7 +615,7 @@ def main():
                        "inputs": ("one text tensor per shard in flight: %d distinct synthetic shards of the same shape (seeds %d + 7919 k), "
                                   "each resident in HBM before the timed region; step j reads the text of slot j mod %d" % (D, SEED0, D)) if own_text
                                  else "ONE text tensor read by every shard in flight (--shared-input)",
-                       "hbm_used_gb": hbm_used_gb, "ms_single_shard_alone": round(single_ms, 3) if single_ms else None},
+                       "hbm_used_gb": hbm_used_gb, "ms_single_shard_alone": round(single, 3) if single else None},
             # achieved = algorithmic bytes of a step (the FASTQ record read once + the three archive streams
             # written once: 308 B per read) / ms_per_step, against the HBM peak.  `kernel` = the dominant kernel on its own:
             # algorithmic bytes of a launch (symbols in + coded bytes out) / its HIP-event time, its counter traffic, and the
@@ -626,9 +638,10 @@ def main():
             "e2e": e2e,
             "table_scale": table_scale,
             "note": "value = %d shards (independent jobs of the configs[1] size) through the device-resident hot path, %d in flight, each "
-                    "with an input text of its own, fill and drain of the pipeline inside the timed region%s; value_single_job = one such job "
-                    "alone, input already in HBM; decode = the inverse path on the last shard; e2e = the scalce binary, file in, archive out"
-                    % (args.steps, D, (" (coder launches planned for a run of this length: %s shards)" % " + ".join(str(x) for x in launch_plan(args.steps))) if waves else ""),
+                    "with an input text of its own, fill and drain of the pipeline inside the timed region%s%s"
+                    % (args.steps, D, (" (coder launches planned for a run of this length: %s shards)" % " + ".join(str(x) for x in launch_plan(args.steps))) if waves else "",
+                       "; value_single_job = one such job alone, input already in HBM; decode = the inverse path on the last shard; e2e = the "
+                       "scalce binary, file in, archive out" if args.full else "; the legs beside it (checks, baselines, decode, e2e) run with --full"),
         }
         print(json.dumps(line))
     if world > 1:

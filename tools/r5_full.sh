@@ -4,7 +4,7 @@ cd "$(dirname "$0")/.."
 O=gpurun_out/r5_full; mkdir -p $O
 timeout -k 10 1000 python -m pytest tests -x -q -m gpu > $O/tests.txt 2>&1; echo "tests rc $?" >> $O/tests.txt
 tail -4 $O/tests.txt
-timeout -k 10 600 python bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err; echo "bench rc $?"
+timeout -k 10 600 python bench.py --full --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err; echo "bench rc $?"
 python - <<'P'
 import json
 j=json.loads(open('gpurun_out/r5_full/bench.json').read().strip().splitlines()[-1])
