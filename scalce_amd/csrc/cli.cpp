@@ -100,67 +100,65 @@ static const char *HELP_TEXT =
     "core table: --patterns-bin FILE or $SCALCE_PATTERNS or patterns.bin next to the executable\n";
 
 // ---- small I/O helpers ------------------------------------------------------------------------------
-static int g_threads_gz();
-static std::vector<uint8_t> read_maybe_gz(const std::string &path) {  // IO_GZIP reader (compress.cpp:756); plain files pass through
-  {
-    const int fd = ::open(path.c_str(), O_RDONLY);
-    if (fd < 0) FAIL("Cannot read file %s\n", path.c_str());
-    uint8_t mg[2] = {0, 0};
-    const bool gz = ::pread(fd, mg, 2, 0) == 2 && mg[0] == 0x1F && mg[1] == 0x8B;
-    std::vector<uint8_t> out;
-    if (!gz) {
-      struct stat st;
-      if (fstat(fd, &st) != 0) FAIL("Cannot read file %s\n", path.c_str());
-      out.resize((size_t)st.st_size);
-      size_t done = 0;
-      while (done < out.size()) { const ssize_t k = ::pread(fd, out.data() + done, out.size() - done, (off_t)done); if (k <= 0) FAIL("Read error on %s\n", path.c_str()); done += (size_t)k; }
-      ::close(fd);
-      return out;
-    }
-    ::close(fd);
-  }
-  scalce_host::ParGz z;  // members inflated by several threads (our own -c gz containers are 4 MiB members)
-  if (!z.open(path, g_threads_gz())) FAIL("Cannot read file %s\n", path.c_str());
-  std::vector<uint8_t> out;
-  std::vector<uint8_t> chunk(64u << 20);
-  for (;;) {
-    const int64_t k = z.read(chunk.data(), chunk.size());
-    if (k < 0) FAIL("Read error on %s\n", path.c_str());
-    if (k == 0) break;
-    out.insert(out.end(), chunk.begin(), chunk.begin() + k);
-  }
-  return out;
+// Host threads: -T, else the cores shared by `procs` processes (a process alone leaves one to its main thread), at most
+// 64.  Plain files are read by up to 8 of them, gzip members inflated by up to 32, the gz containers deflated by all.
+static int g_threads = 1;
+static void set_threads(const Options &o, int procs) {
+  const int hw = (int)std::thread::hardware_concurrency();
+  g_threads = o.threads > 0 ? o.threads : std::max(1, std::min(64, procs > 1 ? hw / procs : hw - 1));
 }
-static int g_threads_io();
-// plain files with several threads (pread), gzip through zlib
-static std::vector<uint8_t> read_file_fast(const std::string &path) {
-  int fd = ::open(path.c_str(), O_RDONLY);
-  if (fd < 0) FAIL("Cannot read file %s\n", path.c_str());
+static int g_threads_io() { return std::max(1, std::min(g_threads, 8)); }
+static int g_threads_gz() { return std::max(1, std::min(g_threads, 32)); }
+
+static bool is_gzip(const std::string &path) {  // the gzip magic (the reference's readers sniff it too, decompress.cpp:99-113)
+  const int fd = ::open(path.c_str(), O_RDONLY);
   uint8_t mg[2] = {0, 0};
-  struct stat st;
-  if (::pread(fd, mg, 2, 0) == 2 && mg[0] == 0x1F && mg[1] == 0x8B) { ::close(fd); return read_maybe_gz(path); }
-  if (fstat(fd, &st) != 0) FAIL("Cannot read file %s\n", path.c_str());
-  std::vector<uint8_t> out((size_t)st.st_size);
-  const uint64_t n = out.size(), SL = 64u << 20;
+  const bool gz = fd >= 0 && ::pread(fd, mg, 2, 0) == 2 && mg[0] == 0x1F && mg[1] == 0x8B;
+  if (fd >= 0) ::close(fd);
+  return gz;
+}
+// fn(a, b) on the slices [a, b) of [0, n), `slice` bytes each, taken in turn by up to `threads` threads (the caller's included)
+template <class Fn> static void for_slices(uint64_t n, uint64_t slice, int threads, Fn fn) {
   std::atomic<uint64_t> next{0};
-  std::atomic<bool> bad{false};
-  auto work = [&]() {
-    for (uint64_t a; (a = next.fetch_add(SL)) < n;) {
-      uint64_t done = a;
-      const uint64_t b = std::min(n, a + SL);
-      while (done < b) {
-        const ssize_t k = ::pread(fd, out.data() + done, (size_t)(b - done), (off_t)done);
-        if (k <= 0) { bad = true; return; }
-        done += (uint64_t)k;
-      }
-    }
-  };
+  auto work = [&]() { for (uint64_t a; (a = next.fetch_add(slice)) < n;) fn(a, std::min(n, a + slice)); };
+  const int nt = (int)std::min<uint64_t>((uint64_t)std::max(1, threads), (n + slice - 1) / slice);
   std::vector<std::thread> pool;
-  for (int t = 1; t < g_threads_io(); t++) pool.emplace_back(work);
+  for (int t = 1; t < nt; t++) pool.emplace_back(work);
   work();
   for (auto &t : pool) t.join();
+}
+// n bytes of fd from offset off, read in slices by several threads (one thread copying out of the page cache delivers about
+// 5 GB/s, a tenth of what an upload behind it can take)
+static bool pread_parallel(int fd, uint8_t *dst, uint64_t n, uint64_t off, uint64_t slice, int threads) {
+  std::atomic<bool> bad{false};
+  for_slices(n, slice, threads, [&](uint64_t a, uint64_t b) {
+    for (uint64_t done = a; done < b && !bad;) {
+      const ssize_t k = ::pread(fd, dst + done, (size_t)(b - done), (off_t)(off + done));
+      if (k <= 0) bad = true; else done += (uint64_t)k;
+    }
+  });
+  return !bad;
+}
+// A whole file: plain by parallel pread, gzip (the IO_GZIP reader, compress.cpp:756) with its members inflated by several
+// threads (our own -c gz containers are 4 MiB members)
+static std::vector<uint8_t> read_whole(const std::string &path) {
+  std::vector<uint8_t> out;
+  if (is_gzip(path)) {
+    scalce_host::ParGz z;
+    if (!z.open(path, g_threads_gz())) FAIL("Cannot read file %s\n", path.c_str());
+    std::vector<uint8_t> chunk(64u << 20);
+    for (int64_t k; (k = z.read(chunk.data(), chunk.size())) != 0;) {
+      if (k < 0) FAIL("Read error on %s\n", path.c_str());
+      out.insert(out.end(), chunk.begin(), chunk.begin() + k);
+    }
+    return out;
+  }
+  const int fd = ::open(path.c_str(), O_RDONLY);
+  struct stat st;
+  if (fd < 0 || fstat(fd, &st) != 0) FAIL("Cannot read file %s\n", path.c_str());
+  out.resize((size_t)st.st_size);
+  if (!pread_parallel(fd, out.data(), out.size(), 0, 64u << 20, g_threads_io())) FAIL("Read error on %s\n", path.c_str());
   ::close(fd);
-  if (bad) FAIL("Read error on %s\n", path.c_str());
   return out;
 }
 static bool second_file(const std::string &p, std::string &out) {  // get_second_file, const.cpp:51-64
@@ -169,14 +167,42 @@ static bool second_file(const std::string &p, std::string &out) {  // get_second
     if (out[i] == '1') { out[i] = '2'; return true; }
   return false;
 }
+static std::string mate_file(const std::string &f, int m) {  // input f's file of mate m
+  std::string out = f;
+  if (m && !second_file(f, out)) FAIL("Cannot get file name for paired end for file %s. File should contain character 1.\n", f.c_str());
+  return out;
+}
+
+// ---- the archive: the file headers of combine_and_compress_with_split (compress.cpp:263-343) ---------------------------
+//   PREFIX_<m>.scalcer  magic, int32 no_ac (-A), int32 read length; the read stream (mate 1: buckets, each opened by
+//                       [int32 core][int64 records]; mate 2: bare records in mate 1's order)
+//   PREFIX_<m>.scalcen  magic, u8 names; the name stream, or without names (-n) int64 0 and the library name
+//   PREFIX_<m>.scalceq  magic, int64 Phred offset (mate 1's for both mates, compress.cpp:294,816-817); arithmetic coded:
+//                       the scaled table (QTABLE_WORDS x u32), the int64 symbol count and the coded blocks; -A: the q' rows
+static const uint8_t MAGIC[8] = {'s', 'c', 'a', 'l', 'c', 'e', '2', '2'};
+static constexpr size_t QTABLE_WORDS = 512000;
+static std::string archive_path(const std::string &out, int m, char ext) { return out + "_" + std::to_string(m + 1) + ".scalce" + ext; }
+// -c gz holds every file in a gzip container but an arithmetic-coded .scalceq (compress.cpp:249)
+static bool gz_container(const Options &o, char ext) { return o.container == 1 && (ext != 'q' || o.no_ac); }
+static std::vector<uint8_t> with_magic(const void *fields, size_t n) {
+  std::vector<uint8_t> h(MAGIC, MAGIC + 8);
+  h.insert(h.end(), static_cast<const uint8_t *>(fields), static_cast<const uint8_t *>(fields) + n);
+  return h;
+}
+static std::vector<uint8_t> reads_header(const Options &o, int len) { const int32_t f[2] = {o.no_ac, len}; return with_magic(f, 8); }
+static std::vector<uint8_t> names_header(const Options &o) {  // without names: the whole file
+  const uint8_t un = o.use_names ? 1 : 0;
+  std::vector<uint8_t> h = with_magic(&un, 1);
+  if (!o.use_names) { h.resize(h.size() + 8, 0); h.insert(h.end(), o.library.begin(), o.library.end()); }
+  return h;
+}
+static std::vector<uint8_t> qual_header(int64_t phred) { return with_magic(&phred, 8); }
+
 // Output file.  Plain: stdio.  gzip container (-c gz / pigz): the reference hands the stream to a pigz child or to
 // zlib's gzwrite (buffio.cpp:148-188, 190-260); here the bytes are collected and deflated at close() by g_threads
 // host threads, 4 MiB per independent gzip member -- concatenated members are one valid gzip file, which the
 // reference's reader (gzread, decompress.cpp:99-113) and ours accept alike (once the hot path is on
 // the GPU, single-threaded deflate of .scalcer/.scalcen is what the wall clock of a run is made of).
-static int g_threads = 1;
-static int g_threads_io() { return std::max(1, std::min(g_threads, 8)); }
-static int g_threads_gz() { return std::max(1, std::min(g_threads, 32)); }
 struct OutFile {
   bool gz = false;
   FILE *f = nullptr;
@@ -203,6 +229,7 @@ struct OutFile {
     // enough for every thread: deflate what is there, member by member (the stream never has to sit in memory whole)
     if (pending.size() >= MEMBER * (size_t)std::max(1, g_threads) * 2) flush_members(false);
   }
+  void write(const std::vector<uint8_t> &v) { write(v.data(), v.size()); }
   // The reference writes its containers at zlib's default level (buffio.cpp: gzopen(path, "wb")), and so does this writer for
   // what deflate shrinks (names: to a third).  The read stream is 2-bit packed bases, as good as incompressible (the
   // reference's own gz gains 2.5 % on it) and the slowest thing zlib can be fed: ~20 MB/s per core at level 6 -- 3.6 of the
@@ -241,20 +268,9 @@ struct OutFile {
     const size_t whole = pending.size() / MEMBER, nchunks = all ? (pending.empty() ? 0 : (pending.size() + MEMBER - 1) / MEMBER) : whole;
     if (!nchunks) return;
     std::vector<std::vector<uint8_t>> members(nchunks);
-    std::atomic<size_t> next{0};
-    auto work = [&]() {
-      for (size_t i; (i = next.fetch_add(1)) < nchunks;) {
-        const size_t a = i * MEMBER, b = std::min(pending.size(), a + MEMBER);
-        deflate_member(pending.data() + a, b - a, members[i]);
-      }
-    };
-    const int nt = (int)std::min<size_t>((size_t)std::max(1, g_threads), nchunks);
-    std::vector<std::thread> pool;
-    for (int t = 1; t < nt; t++) pool.emplace_back(work);
-    work();
-    for (auto &t : pool) t.join();
-    for (auto &m : members) raw(m.data(), m.size());
     const size_t done = std::min(pending.size(), nchunks * MEMBER);
+    for_slices(done, MEMBER, g_threads, [&](uint64_t a, uint64_t b) { deflate_member(pending.data() + a, b - a, members[a / MEMBER]); });
+    for (auto &m : members) raw(m.data(), m.size());
     pending.erase(pending.begin(), pending.begin() + done);
   }
   void close() {
@@ -309,24 +325,19 @@ struct Downloader {
   void qual_to_file(scalce_ctx *ctx, scalce_batch *b, int mate, OutFile &f) {
     uint64_t total = 0;
     SCOK(ctx, scalce_batch_qual_bytes(b, mate, &total));
-    const uint64_t nslices = (total + SLICE - 1) / SLICE;
-    auto start = [&](uint64_t i) {
-      const uint64_t off = i * SLICE, k = std::min<uint64_t>(SLICE, total - off);
-      SCOK(ctx, scalce_batch_qual_window(b, mate, off, k, pin[i & 1], s));
-      HIPOK(hipEventRecord(ev[i & 1], s));
-    };
-    if (nslices) start(0);
-    for (uint64_t i = 0; i < nslices; i++) {
-      HIPOK(hipEventSynchronize(ev[i & 1]));
-      if (i + 1 < nslices) start(i + 1);
-      f.write(pin[i & 1], (size_t)std::min<uint64_t>(SLICE, total - i * SLICE));
-    }
+    slices_to_file(total, f, [&](uint8_t *dst, uint64_t off, uint64_t k) { SCOK(ctx, scalce_batch_qual_window(b, mate, off, k, dst, s)); });
   }
   void range_to_file(const uint8_t *src, uint64_t n, OutFile &f) {
+    slices_to_file(n, f, [&](uint8_t *dst, uint64_t off, uint64_t k) {
+      HIPOK(hipMemcpyAsync(dst, src + off, k, hipMemcpyDeviceToHost, s));
+    });
+  }
+  // n bytes in slices: fill(dst, off, k) enqueues bytes off .. off + k of the stream into pinned slice dst on s
+  template <class Fill> void slices_to_file(uint64_t n, OutFile &f, Fill fill) {
     const uint64_t nslices = (n + SLICE - 1) / SLICE;
     auto start = [&](uint64_t i) {
-      const uint64_t off = i * SLICE, k = std::min<uint64_t>(SLICE, n - off);
-      HIPOK(hipMemcpyAsync(pin[i & 1], src + off, k, hipMemcpyDeviceToHost, s));
+      const uint64_t off = i * SLICE;
+      fill(pin[i & 1], off, std::min<uint64_t>(SLICE, n - off));
       HIPOK(hipEventRecord(ev[i & 1], s));
     };
     if (nslices) start(0);
@@ -340,39 +351,29 @@ struct Downloader {
 
 // One mate's input: the files of the command line one after the other (compress.cpp:756-797 runs them through the same
 // trie; the record stream is their concatenation), each plain or gzip (the reference opens everything through zlib,
-// :767-779).  Plain files are read with read(2) straight into the pinned chunk the streaming host hands in.
+// :767-779).  Plain files are read by parallel pread straight into the pinned chunk the streaming host hands in.
 struct MateSource {
   std::vector<std::string> files;
   size_t cur = 0;
   int fd = -1;
   scalce_host::ParGz pgz;     // gzip input: members inflated on several threads (pargz.hpp)
   bool gz = false;
-  int gz_threads = 0;         // 0: g_threads (two mates read at once: the paired reader halves it)
-  uint64_t gz_parallel_windows = 0, gz_serial_bytes = 0;
   std::vector<uint8_t> peek;  // bytes read ahead for the quality sample, served first
   size_t peek_pos = 0;
-  bool all_plain = true;
   bool open_next() {
-    while (cur < files.size()) {
-      const std::string &path = files[cur++];
-      fd = ::open(path.c_str(), O_RDONLY);
-      if (fd < 0) FAIL("Cannot read file %s\n", path.c_str());
-      uint8_t mg[2] = {0, 0};
-      const ssize_t k = ::pread(fd, mg, 2, 0);
-      if (k == 2 && mg[0] == 0x1F && mg[1] == 0x8B) {
-        all_plain = false;
-        ::close(fd);
-        fd = -1;
-        if (!pgz.open(path, gz_threads > 0 ? gz_threads : std::max(1, g_threads))) FAIL("Cannot read file %s\n", path.c_str());
-        gz = true;
-      } else {
-#ifdef POSIX_FADV_SEQUENTIAL
-        posix_fadvise(fd, 0, 0, POSIX_FADV_SEQUENTIAL);
-#endif
-      }
+    if (cur >= files.size()) return false;
+    const std::string &path = files[cur++];
+    if (is_gzip(path)) {
+      if (!pgz.open(path, std::max(1, g_threads))) FAIL("Cannot read file %s\n", path.c_str());
+      gz = true;
       return true;
     }
-    return false;
+    fd = ::open(path.c_str(), O_RDONLY);
+    if (fd < 0) FAIL("Cannot read file %s\n", path.c_str());
+#ifdef POSIX_FADV_SEQUENTIAL
+    posix_fadvise(fd, 0, 0, POSIX_FADV_SEQUENTIAL);
+#endif
+    return true;
   }
   uint64_t fpos = 0;  // plain files: where the next read starts
   bool hold_at_file_end = false;  // fill_peek: the sample never runs into the next file
@@ -389,47 +390,19 @@ struct MateSource {
         if (!open_next()) return 0;
         fpos = 0;
       }
-      int64_t k;
-      if (gz) k = pgz.read(dst, cap);
-      else k = read_plain(static_cast<uint8_t *>(dst), cap);
+      const int64_t k = gz ? pgz.read(dst, cap) : read_plain(static_cast<uint8_t *>(dst), cap);
       if (k < 0) return -1;
       if (k > 0) { last_byte = static_cast<uint8_t *>(dst)[k - 1]; return k; }
-      if (gz) { gz_parallel_windows += pgz.parallel_windows; gz_serial_bytes += pgz.serial_bytes; pgz.close(); gz = false; } else { ::close(fd); fd = -1; }
+      if (gz) { pgz.close(); gz = false; } else { ::close(fd); fd = -1; }
       if (last_byte != '\n') pending_newline = true;
     }
   }
-  // A big request on a plain file is cut into slices read by several threads at once (pread): one thread copying out
-  // of the page cache delivers about 5 GB/s, a tenth of what the upload behind it can take.
+  // a big request on a plain file is read by several threads at once
   int64_t read_plain(uint8_t *dst, uint64_t cap) {
-    const uint64_t SLICE = 16u << 20;
-    const int nt = (int)std::min<uint64_t>((uint64_t)std::max(1, std::min(g_threads, 8)), (cap + SLICE - 1) / SLICE);
-    if (nt <= 1) {
-      const int64_t k = ::pread(fd, dst, (size_t)std::min<uint64_t>(cap, 1u << 30), (off_t)fpos);
-      if (k > 0) fpos += (uint64_t)k;
-      return k;
-    }
     struct stat st;
     if (fstat(fd, &st) != 0) return -1;
-    const uint64_t left = (uint64_t)st.st_size > fpos ? (uint64_t)st.st_size - fpos : 0;
-    const uint64_t want = std::min(cap, left);
-    if (!want) return 0;
-    const uint64_t per = ((want + nt - 1) / nt + 4095) & ~4095ull;
-    std::atomic<bool> bad{false};
-    std::vector<std::thread> pool;
-    for (int t = 0; t < nt; t++) {
-      const uint64_t a = (uint64_t)t * per, b = std::min(want, a + per);
-      if (a >= b) break;
-      pool.emplace_back([&, a, b]() {
-        uint64_t done = a;
-        while (done < b) {
-          const ssize_t k = ::pread(fd, dst + done, (size_t)(b - done), (off_t)(fpos + done));
-          if (k <= 0) { bad = true; return; }
-          done += (uint64_t)k;
-        }
-      });
-    }
-    for (auto &t : pool) t.join();
-    if (bad) return -1;
+    const uint64_t want = std::min(cap, (uint64_t)st.st_size > fpos ? (uint64_t)st.st_size - fpos : 0);
+    if (!pread_parallel(fd, dst, want, fpos, 16u << 20, g_threads_io())) return -1;
     fpos += want;
     return (int64_t)want;
   }
@@ -445,15 +418,11 @@ struct MateSource {
   }
   // read ahead until the text holds `records` records or the FIRST file ends: quality_mapping_init's sample is taken
   // from files[0] alone (get_quality_stats, compress.cpp:761; the loop of qualities.cpp:66-78 stops at its end)
-  void fill_peek(int records, int lines_per_record = 4) {
+  void fill_peek(int records, int lines_per_record) {
     hold_at_file_end = true;
-    fill_peek_held(records, lines_per_record);
-    hold_at_file_end = false;
-  }
-  void fill_peek_held(int records, int lines_per_record = 4) {
     const size_t want = (size_t)lines_per_record * (size_t)records;
     size_t lines = 0, scanned = 0;
-    for (;;) {
+    for (int64_t got = 1; got;) {
       const uint8_t *p = peek.data();
       while (scanned < peek.size() && lines < want) {
         const void *nl = memchr(p + scanned, '\n', peek.size() - scanned);
@@ -461,122 +430,124 @@ struct MateSource {
         scanned = (size_t)((const uint8_t *)nl - p) + 1;
         lines++;
       }
-      if (lines >= want) return;
+      if (lines >= want) break;
       const size_t old = peek.size(), step = 16u << 20;
       peek.resize(old + step);
-      int64_t got = 0;
-      while ((size_t)got < step) {
+      for (got = 0; (size_t)got < step;) {
         const int64_t k = read_raw(peek.data() + old + got, step - (size_t)got);
         if (k < 0) FAIL("Read error\n");
         if (k == 0) break;
         got += k;
       }
       peek.resize(old + (size_t)got);
-      if (!got) return;
     }
+    hold_at_file_end = false;
   }
   static int64_t read_cb(void *user, void *dst, uint64_t cap) { return static_cast<MateSource *>(user)->read(dst, cap); }
 };
 
 // sampling loop of quality_mapping_init (qualities.cpp:64-97) on the text read ahead
-static void sample_stats(const std::vector<uint8_t> &t, int sample, int32_t stat[128], int &read_length) {
-  memset(stat, 0, 128 * sizeof(int32_t));
-  size_t pos = 0;
-  for (int i = 0; i < sample; i++) {
-    size_t e = pos;
-    bool ok = true;
-    for (int k = 0; k < 3 && ok; k++) {
-      const void *nl = e < t.size() ? memchr(t.data() + e, '\n', t.size() - e) : nullptr;
-      if (!nl) ok = false; else e = (const uint8_t *)nl - t.data() + 1;
+static void sample_stats(const uint8_t *t, size_t n, int sample, int32_t stat[128], int &read_length) {
+  size_t line[5] = {0};  // where a record's four lines start, and the next record
+  for (int i = 0; i < sample; i++, line[0] = line[4]) {
+    for (int k = 1; k < 5; k++) {
+      const void *nl = line[k - 1] < n ? memchr(t + line[k - 1], '\n', n - line[k - 1]) : nullptr;
+      if (!nl) return;
+      line[k] = (size_t)((const uint8_t *)nl - t) + 1;
     }
-    if (!ok) break;
-    const void *nl = e < t.size() ? memchr(t.data() + e, '\n', t.size() - e) : nullptr;
-    if (!nl) break;
-    size_t qe = (const uint8_t *)nl - t.data();
-    for (size_t j = e; j < qe; j++) stat[t[j] & 127]++;
-    read_length = (int)(qe - e);
-    pos = qe + 1;
+    for (size_t j = line[3]; j + 1 < line[4]; j++) stat[t[j] & 127]++;
+    read_length = (int)(line[4] - 1 - line[3]);
   }
 }
 
-static std::vector<uint8_t> load_core_table(const Options &o, const char *argv0, bool &is_text) {
-  is_text = false;
-  if (!o.patterns.empty()) { is_text = true; return read_maybe_gz(o.patterns); }
-  std::vector<std::string> cand;
-  if (!o.patterns_bin.empty()) cand.push_back(o.patterns_bin);
-  if (const char *e = getenv("SCALCE_PATTERNS")) cand.push_back(e);
-  std::string self = argv0;
-  size_t sl = self.rfind('/');
-  cand.push_back((sl == std::string::npos ? std::string(".") : self.substr(0, sl)) + "/patterns.bin");
-  cand.push_back("patterns.bin");
-  for (auto &c : cand) {
-    struct stat st;
-    if (stat(c.c_str(), &st) == 0) return read_maybe_gz(c);
-  }
-  FAIL("No core table: give --patterns-bin FILE, -P LIST or set SCALCE_PATTERNS (the reference embeds patterns.bin at link time)\n");
+// ---- run setup --------------------------------------------------------------------------------------------
+static scalce_params params_from(const Options &o) {
+  scalce_params p;
+  scalce_params_default(&p);
+  p.paired = o.paired; p.use_names = o.use_names; p.no_ac = o.no_ac; p.bucket_set_size = o.bucket_set_size;
+  p.fasta = o.fasta; p.no_qualities = o.no_qual;
+  return p;
 }
-
-// -f: nothing is sampled (qualities.cpp:65): the read length is that of line 2 of the first record
-static void first_sequence_length(const std::vector<uint8_t> &t, int &read_length) {
-  const void *nl = memchr(t.data(), '\n', t.size());
-  if (!nl) return;
-  const size_t s = (const uint8_t *)nl - t.data() + 1;
-  const void *nl2 = s < t.size() ? memchr(t.data() + s, '\n', t.size() - s) : nullptr;
-  if (nl2) read_length = (int)((const uint8_t *)nl2 - (t.data() + s));
+// Mate m's quality map and read length from the first records of the first input file (get_quality_stats,
+// compress.cpp:761).  fill_peek holds at the end of that file; under --gpus, where several files were written out as one,
+// the sample ends where the first file did (first_file_bytes).  -f: the statistics stay zero, so the offset stays 64
+// (qualities.cpp:91-101); -Q samples as usual: the offset in the header is the one detected.
+static void quality_model(const Options &o, MateSource &src, int m, scalce_params &p, bool log) {
+  src.fill_peek(o.fasta ? 1 : o.sample, o.fasta ? 2 : 4);
+  const size_t n = o.first_file_bytes[m] ? std::min<size_t>(src.peek.size(), o.first_file_bytes[m]) : src.peek.size();
+  int32_t qhist[128] = {0};
+  int rl = 0;
+  if (o.fasta) {  // nothing is sampled (qualities.cpp:65): the read length is that of line 2 of the first record
+    const uint8_t *t = src.peek.data(), *nl = (const uint8_t *)memchr(t, '\n', n);
+    const uint8_t *nl2 = nl ? (const uint8_t *)memchr(nl + 1, '\n', n - (size_t)(nl + 1 - t)) : nullptr;
+    if (nl2) rl = (int)(nl2 - nl - 1);
+  } else {
+    sample_stats(src.peek.data(), n, o.sample, qhist, rl);
+  }
+  scalce_qmap_init(&p.qmap[m], qhist, o.lossy);
+  p.read_len[m] = rl;
+  if (log) LOG("\tPaired end #%d, quality offset: %d\n\t               read length: %d\n", m + 1, p.qmap[m].offset, rl);
+}
+// The device context with the core table loaded: -P LIST, --patterns-bin FILE, $SCALCE_PATTERNS or patterns.bin next to
+// the executable.  The table's bytes come back in `table`.  --gpus forks before anything touches HIP: this runs in main()
+// on one GPU and inside each rank, never in the parent of a --gpus run.
+static scalce_ctx *open_device(const Options &o, const char *argv0, int device, std::vector<uint8_t> &table, bool &is_text) {
+  scalce_ctx *ctx = nullptr;
+  if (scalce_ctx_create(device, &ctx)) FAIL("%s\n", scalce_last_error(ctx));
+  is_text = !o.patterns.empty();
+  if (is_text) table = read_whole(o.patterns);
+  else {
+    std::vector<std::string> cand;
+    if (!o.patterns_bin.empty()) cand.push_back(o.patterns_bin);
+    if (const char *e = getenv("SCALCE_PATTERNS")) cand.push_back(e);
+    const size_t sl = std::string(argv0).rfind('/');
+    cand.push_back((sl == std::string::npos ? std::string(".") : std::string(argv0, sl)) + "/patterns.bin");
+    cand.push_back("patterns.bin");
+    auto found = std::find_if(cand.begin(), cand.end(), [](const std::string &c) { struct stat st; return stat(c.c_str(), &st) == 0; });
+    if (found == cand.end())
+      FAIL("No core table: give --patterns-bin FILE, -P LIST or set SCALCE_PATTERNS (the reference embeds patterns.bin at link time)\n");
+    table = read_whole(*found);
+  }
+  if (is_text) SCOK(ctx, scalce_patterns_load_text(ctx, (const char *)table.data(), table.size()));
+  else SCOK(ctx, scalce_patterns_load_bin(ctx, table.data(), table.size()));
+  return ctx;
+}
+// the statistics lines both compress paths print
+static void log_statistics(const Options &o, const scalce_params &p, uint64_t N, uint64_t unbucketed) {
+  LOG("Statistics:\n\tTotal number of reads: %llu\n\tRead length: first end %d\n", (unsigned long long)N, p.read_len[0]);
+  if (o.paired) LOG("\t             second end %d\n", p.read_len[1]);
+  LOG("\tUnbucketed reads count: %llu, bucketed percentage %.2lf\n", (unsigned long long)unbucketed,
+      N ? 100.0 * (double)(N - unbucketed) / (double)N : 0.0);
+  LOG("\tLossy percentage: %d\n", o.lossy);
 }
 
 // ---- compress -----------------------------------------------------------------------------------------
 static int do_compress(const Options &o, const std::vector<std::string> &files, scalce_ctx *ctx) {
   const double t0 = now();
   const int nm = o.paired ? 2 : 1;
-  uint64_t original = 0;
-  int32_t qhist[128];
-  scalce_params p;
-  scalce_params_default(&p);
-  p.paired = o.paired; p.use_names = o.use_names; p.no_ac = o.no_ac; p.bucket_set_size = o.bucket_set_size;
-  p.fasta = o.fasta; p.no_qualities = o.no_qual;
+  uint64_t original = 0, bytes1 = 0;  // input bytes: every mate's, mate 1's
+  bool plain1 = true;                 // no gzip among mate 1's files
+  scalce_params p = params_from(o);
   const bool no_qual = o.fasta || o.no_qual;
   LOG("Preprocessing FASTQ files ...\n");
   MateSource src[2];
   for (int m = 0; m < nm; m++) {
-    for (size_t F = 0; F < files.size(); F++) {
-      std::string path = files[F];
-      if (m && !second_file(files[F], path))
-        FAIL("Cannot get file name for paired end for file %s. File should contain character 1.\n", files[F].c_str());
+    for (const std::string &f : files) {
+      const std::string path = mate_file(f, m);
       struct stat st;
-      if (stat(path.c_str(), &st) == 0) original += (uint64_t)st.st_size;
+      const uint64_t size = stat(path.c_str(), &st) == 0 ? (uint64_t)st.st_size : 0;
+      original += size;
+      if (m == 0) { bytes1 += size; plain1 = plain1 && !is_gzip(path); }
       src[m].files.push_back(path);
     }
-    // get_quality_stats looks at the first file only (compress.cpp:761)
-    int rl = 0;
-    if (o.fasta) {  // the statistics stay zero: the offset stays 64 (qualities.cpp:91-101)
-      src[m].fill_peek(1, 2);
-      memset(qhist, 0, sizeof qhist);
-      first_sequence_length(src[m].peek, rl);
-    } else {  // (-Q samples as usual: the offset in the header is the one detected)
-      src[m].fill_peek(o.sample);
-      sample_stats(src[m].peek, o.sample, qhist, rl);
-    }
-    scalce_qmap_init(&p.qmap[m], qhist, o.lossy);
-    p.read_len[m] = rl;
-    LOG("\tPaired end #%d, quality offset: %d\n\t               read length: %d\n", m + 1, p.qmap[m].offset, rl);
+    quality_model(o, src[m], m, p, true);
   }
   if (p.read_len[0] <= 0) FAIL("Cannot determine the read length of %s\n", files[0].c_str());
   // rows to expect: exact enough for plain text (a record is 2 L + 6 bytes plus its name), unknown behind gzip
-  uint64_t hint = 0;
-  if (src[0].all_plain && !src[0].gz) {
-    uint64_t bytes = 0;
-    for (auto &f : src[0].files) { struct stat st; if (stat(f.c_str(), &st) == 0) bytes += (uint64_t)st.st_size; }
-    hint = bytes / ((o.fasta ? 1 : 2) * (uint64_t)p.read_len[0] + (o.fasta ? 4 : 8)) + 64;
-    for (auto &f : src[0].files) { int fd = ::open(f.c_str(), O_RDONLY); uint8_t mg[2] = {0, 0}; if (fd >= 0) { if (::pread(fd, mg, 2, 0) == 2 && mg[0] == 0x1F && mg[1] == 0x8B) hint = 0; ::close(fd); } }
-  }
+  const uint64_t hint = plain1 ? bytes1 / ((o.fasta ? 1 : 2) * (uint64_t)p.read_len[0] + (o.fasta ? 4 : 8)) + 64 : 0;
   uint64_t piece = 256ull << 20;  // per chunk; three of them are pinned per mate
   if (const char *e = getenv("SCALCE_PIECE_BYTES")) piece = strtoull(e, nullptr, 10);
-  {  // small inputs: no point in pinning gigabytes
-    uint64_t bytes = 0;
-    for (auto &f : src[0].files) { struct stat st; if (stat(f.c_str(), &st) == 0) bytes += (uint64_t)st.st_size; }
-    if (hint && bytes + (1u << 20) < piece) piece = bytes + (1u << 20);
-  }
+  if (hint && bytes1 + (1u << 20) < piece) piece = bytes1 + (1u << 20);  // small inputs: no point in pinning gigabytes
   scalce_batch *b = nullptr;
   scalce_stream_stats ss;
   char emsg[512] = "";
@@ -598,11 +569,6 @@ static int do_compress(const Options &o, const std::vector<std::string> &files, 
   SCOK(ctx, scalce_batch_set_frame_on_demand(b, 1));  // the coded blocks are framed on their way into the pinned slices
   SCOK(ctx, scalce_batch_entropy_begin(b, nullptr, s_ent));
 
-  // final writer: headers of combine_and_compress_with_split (compress.cpp:263-343)
-  const uint8_t magic[8] = {'s', 'c', 'a', 'l', 'c', 'e', '2', '2'};
-  const bool gz = o.container == 1;
-  uint64_t new_size = 0;
-  char fn[4096];
   // the files of a mate are written by a thread of its own (paired runs: two mates, two sets of files, two threads)
   auto per_mate = [&](auto &&body) {
     if (nm == 1) { body(0); return; }
@@ -613,52 +579,40 @@ static int do_compress(const Options &o, const std::vector<std::string> &files, 
   std::unique_ptr<Downloader> downs[2];  // (a mate's pinned slices serve both of its passes)
   per_mate([&](int m) {
     downs[m].reset(new Downloader);
-    Downloader &down = *downs[m];
-    char fn[4096];
     OutFile fR, fN;
-    snprintf(fn, sizeof fn, "%s_%d.scalcer", o.out.c_str(), m + 1); fR.open(fn, gz);
-    const int32_t noac = o.no_ac, len32 = p.read_len[m];
-    fR.write(magic, 8); fR.write(&noac, 4); fR.write(&len32, 4);
-    down.to_file(ctx, b, SCALCE_OUT_READS, m, fR);
+    fR.open(archive_path(o.out, m, 'r'), gz_container(o, 'r'));
+    fR.write(reads_header(o, p.read_len[m]));
+    downs[m]->to_file(ctx, b, SCALCE_OUT_READS, m, fR);
     fR.close();
-    snprintf(fn, sizeof fn, "%s_%d.scalcen", o.out.c_str(), m + 1); fN.open(fn, gz);
-    const uint8_t un = o.use_names ? 1 : 0;
-    fN.write(magic, 8); fN.write(&un, 1);
-    if (o.use_names) down.to_file(ctx, b, SCALCE_OUT_NAMES, 0, fN);  // mate 2 repeats mate 1's names (:450-454)
-    else { const int64_t z = 0; fN.write(&z, 8); fN.write(o.library.data(), o.library.size()); }
+    fN.open(archive_path(o.out, m, 'n'), gz_container(o, 'n'));
+    fN.write(names_header(o));
+    if (o.use_names) downs[m]->to_file(ctx, b, SCALCE_OUT_NAMES, 0, fN);  // mate 2 repeats mate 1's names (:450-454)
     fN.close();
   });
   const double t2b = now();
   SCOK(ctx, scalce_batch_finish(b, s_ent));  // the coder is through: sizes of the coded streams, device error word
   const double t2c = now();
   per_mate([&](int m) {
-    Downloader &down = *downs[m];
-    char fn[4096];
     OutFile fQ;
-    snprintf(fn, sizeof fn, "%s_%d.scalceq", o.out.c_str(), m + 1); fQ.open(fn, o.no_ac ? gz : false);  // :249
-    const int64_t phred = p.qmap[0].offset;  // mate 1's offset for both (compress.cpp:294,816-817)
-    fQ.write(magic, 8); fQ.write(&phred, 8);
-    if (no_qual) {  // -Q / -f: the header and nothing else -- no table (:296), no coder blocks (ac_write of nothing)
-      fQ.close();
-      downs[m].reset();
-      return;
+    fQ.open(archive_path(o.out, m, 'q'), gz_container(o, 'q'));
+    fQ.write(qual_header(p.qmap[0].offset));
+    if (!no_qual) {  // (-Q / -f: the header and nothing else -- no table (:296), no coder blocks (ac_write of nothing))
+      if (!o.no_ac) {
+        fQ.write(fetch(ctx, b, SCALCE_OUT_TABLE, m));
+        const uint64_t total = N * (uint64_t)p.read_len[m];
+        fQ.write(&total, 8);
+      }
+      downs[m]->qual_to_file(ctx, b, m, fQ);
     }
-    if (!o.no_ac) {
-      auto tb = fetch(ctx, b, SCALCE_OUT_TABLE, m);
-      fQ.write(tb.data(), tb.size());
-      const uint64_t total = N * (uint64_t)p.read_len[m];
-      fQ.write(&total, 8);
-    }
-    down.qual_to_file(ctx, b, m, fQ);
     fQ.close();
     downs[m].reset();
   });
   const double t2d = now();
+  uint64_t new_size = 0;
   for (int m = 0; m < nm; m++)
-    for (const char *ext : {"r", "q", "n"}) {
-      snprintf(fn, sizeof fn, "%s_%d.scalce%s", o.out.c_str(), m + 1, ext);
+    for (char ext : {'r', 'q', 'n'}) {
       struct stat st;
-      if (stat(fn, &st) == 0) new_size += (uint64_t)st.st_size;
+      if (stat(archive_path(o.out, m, ext).c_str(), &st) == 0) new_size += (uint64_t)st.st_size;
     }
   hipStreamDestroy(s_ent);
   const void *dc = nullptr;
@@ -668,11 +622,7 @@ static int do_compress(const Options &o, const std::vector<std::string> &files, 
   if (nc >= 8) SCOK(ctx, scalce_memcpy_d2h(ctx, &unbucketed, (const uint8_t *)dc + nc - 8, 8));
   scalce_batch_destroy(b);
   const double t3 = now();
-  LOG("Statistics:\n\tTotal number of reads: %llu\n\tRead length: first end %d\n", (unsigned long long)N, p.read_len[0]);
-  if (o.paired) LOG("\t             second end %d\n", p.read_len[1]);
-  LOG("\tUnbucketed reads count: %llu, bucketed percentage %.2lf\n", (unsigned long long)unbucketed,
-      N ? 100.0 * (double)(N - unbucketed) / (double)N : 0.0);
-  LOG("\tLossy percentage: %d\n", o.lossy);
+  log_statistics(o, p, N, unbucketed);
   LOG("\tSpill chunks: %u, pieces streamed: %llu\n", st4[3], (unsigned long long)ss.rounds);
   LOG("\tTime elapsed: %.2f s (sample %.2f; stream %.2f = waiting for the reader %.2f + for uploads %.2f + ingest/count/tokenize %.2f; "
       "order %.2f, emit %.2f; reads+names down and written beside the coder %.2f, waiting for the coder %.2f, qualities down and written %.2f, device buffers released %.2f)\n",
@@ -734,18 +684,44 @@ static void pwrite_all(int fd, const void *src, size_t n, uint64_t off) {
     p += k; n -= (size_t)k; off += (uint64_t)k;
   }
 }
+// Bucket k of a stream holds the units of every rank in rank order: amount[r * nb + k] of rank r.  Per bucket: this rank's
+// amount, the amount of the ranks before it, and the run's.
+struct Shares {
+  std::vector<uint64_t> mine, before, all;
+  Shares(const uint64_t *amount, uint32_t nb, int world, int rank) : mine(nb, 0), before(nb, 0), all(nb, 0) {
+    for (int r = 0; r < world; r++)
+      for (uint32_t k = 0; k < nb; k++) {
+        const uint64_t a = amount[(size_t)r * nb + k];
+        if (r < rank) before[k] += a;
+        if (r == rank) mine[k] = a;
+        all[k] += a;
+      }
+  }
+};
+// This rank's share of a stream that starts at byte `base` of the file, pwritten bucket by bucket at its run-wide place;
+// a unit of bucket k is unit(k) bytes.  With `cores` (mate-1 reads) a bucket with units in the run opens with the 12-byte
+// header [int32 core][int64 units]: rank 0 (`lead`) writes it, and the rank's own bytes carry one per bucket it has units in.
+template <class Unit>
+static void place_share(int fd, uint64_t base, const uint8_t *mine, const Shares &sh, Unit unit, const int32_t *cores = nullptr,
+                        bool lead = false) {
+  const uint64_t h = cores ? 12 : 0;
+  for (size_t k = 0; k < sh.all.size(); k++) {
+    if (cores && !sh.all[k]) continue;
+    if (cores && lead) { uint8_t hd[12]; memcpy(hd, &cores[k], 4); memcpy(hd + 4, &sh.all[k], 8); pwrite_all(fd, hd, 12, base); }
+    const uint64_t u = unit(k);
+    if (sh.mine[k]) { pwrite_all(fd, mine + h, sh.mine[k] * u, base + h + sh.before[k] * u); mine += h + sh.mine[k] * u; }
+    base += h + sh.all[k] * u;
+  }
+}
 
 static int rank_main(const Options &o, const std::vector<std::string> &files, const char *argv0, int rank, int world, const std::string &tag) {
   const bool shm = getenv("SCALCE_COMM") && !strcmp(getenv("SCALCE_COMM"), "shm");
   const int device = shm ? 0 : rank;
   const int nm = o.paired ? 2 : 1;
   const double t0 = now();
-  scalce_ctx *ctx = nullptr;
-  if (scalce_ctx_create(device, &ctx)) FAIL("%s\n", scalce_last_error(ctx));
+  std::vector<uint8_t> table;
   bool is_text = false;
-  std::vector<uint8_t> table = load_core_table(o, argv0, is_text);
-  if (is_text) SCOK(ctx, scalce_patterns_load_text(ctx, (const char *)table.data(), table.size()));
-  else SCOK(ctx, scalce_patterns_load_bin(ctx, table.data(), table.size()));
+  scalce_ctx *ctx = open_device(o, argv0, device, table, is_text);
   // communicator
   scalce_comm *comm = nullptr;
   if (shm) {
@@ -770,29 +746,19 @@ static int rank_main(const Options &o, const std::vector<std::string> &files, co
     if (rank == 0) unlink(idfile.c_str());
   }
   // quality model: the first records of the FILE, the same on every rank (get_quality_stats, compress.cpp:761)
-  scalce_params p;
-  scalce_params_default(&p);
-  p.paired = o.paired; p.use_names = o.use_names; p.no_ac = o.no_ac; p.bucket_set_size = o.bucket_set_size;
-  std::string path[2] = {files[0], files[0]};
-  if (o.paired && !second_file(files[0], path[1])) FAIL("Cannot get file name for paired end for file %s. File should contain character 1.\n", files[0].c_str());
+  scalce_params p = params_from(o);
+  const std::string path[2] = {files[0], mate_file(files[0], o.paired ? 1 : 0)};
   int fd[2] = {-1, -1};
   uint64_t fsize[2] = {0, 0};
   for (int m = 0; m < nm; m++) {
+    if (is_gzip(path[m])) FAIL("--gpus needs plain (not gzip) input: the file is split by byte ranges\n");
     MateSource src;
     src.files.push_back(path[m]);
-    src.fill_peek(o.sample);
-    if (!src.all_plain) FAIL("--gpus needs plain (not gzip) input: the file is split by byte ranges\n");
-    if (o.first_file_bytes[m] && src.peek.size() > o.first_file_bytes[m]) src.peek.resize((size_t)o.first_file_bytes[m]);
-    int32_t qhist[128];
-    int rl = 0;
-    sample_stats(src.peek, o.sample, qhist, rl);
-    scalce_qmap_init(&p.qmap[m], qhist, o.lossy);
-    p.read_len[m] = rl;
+    quality_model(o, src, m, p, rank == 0);
     fd[m] = ::open(path[m].c_str(), O_RDONLY);
     struct stat st;
     if (fd[m] < 0 || fstat(fd[m], &st) != 0) FAIL("Cannot read file %s\n", path[m].c_str());
     fsize[m] = (uint64_t)st.st_size;
-    if (rank == 0) LOG("\tPaired end #%d, quality offset: %d\n\t               read length: %d\n", m + 1, p.qmap[m].offset, rl);
   }
   if (p.read_len[0] <= 0) FAIL("Cannot determine the read length of %s\n", files[0].c_str());
   // ---- this rank's records: line-aligned byte ranges, line counts of everybody, then cuts at multiples of four lines
@@ -841,20 +807,15 @@ static int rank_main(const Options &o, const std::vector<std::string> &files, co
     for (int m = 0; m < nm; m++) {
       const uint64_t n = hi[m] - lo[m];
       HIPOK(hipMalloc(reinterpret_cast<void **>(&d_text[m]), n + 256));
-      MateSource src;  // (parallel pread into the pinned chunk)
-      src.fd = fd[m];
-      src.fpos = lo[m];
       uint64_t done = 0;
       for (int i = 0; done < n; i ^= 1) {
         HIPOK(hipEventSynchronize(ev[i]));
         const uint64_t k = std::min<uint64_t>(CH, n - done);
-        uint64_t got = 0;
-        while (got < k) { const int64_t r = src.read_plain(pin[i] + got, k - got); if (r <= 0) FAIL("Read error\n"); got += (uint64_t)r; }
+        if (!pread_parallel(fd[m], pin[i], k, lo[m] + done, 16u << 20, g_threads_io())) FAIL("Read error\n");
         HIPOK(hipMemcpyAsync(d_text[m] + done, pin[i], k, hipMemcpyHostToDevice, s));
         HIPOK(hipEventRecord(ev[i], s));
         done += k;
       }
-      src.fd = -1;
     }
     HIPOK(hipStreamSynchronize(s));
     for (int i = 0; i < 2; i++) { hipHostFree(pin[i]); hipEventDestroy(ev[i]); }
@@ -866,10 +827,9 @@ static int rank_main(const Options &o, const std::vector<std::string> &files, co
   SCOK(ctx, scalce_batch_create(ctx, &p, rows + rows / 3, std::max(hi[0] - lo[0], nm == 2 ? hi[1] - lo[1] : 0) + 256, &b));
   scalce_shard_result res;
   memset(&res, 0, sizeof res);
-  {
-    const int rc = scalce_sharded_compress(comm, ctx, b, d_text[0], hi[0] - lo[0], nm == 2 ? d_text[1] : nullptr, nm == 2 ? hi[1] - lo[1] : 0, 0, s, nullptr, &res);
-    if (rc) exit(1);
-  }
+  if (scalce_sharded_compress(comm, ctx, b, d_text[0], hi[0] - lo[0], nm == 2 ? d_text[1] : nullptr, nm == 2 ? hi[1] - lo[1] : 0, 0, s,
+                              nullptr, &res))
+    exit(1);
   for (int m = 0; m < nm; m++) hipFree(d_text[m]);
   const double t2 = now();
   // ---- every rank writes its pieces of the archive
@@ -877,115 +837,68 @@ static int rank_main(const Options &o, const std::vector<std::string> &files, co
   std::vector<int32_t> bucket_pattern(nb1);
   int32_t nst = 0, nbk = 0;
   scalce_patterns_describe_host(table.data(), table.size(), is_text ? 1 : 0, bucket_pattern.data(), nb1, &nst, &nbk);
-  std::vector<uint64_t> recsz(nb1), Cg(nb1, 0);
+  const Shares reads(res.counts, nb1, world, rank), names(res.name_bytes, nb1, world, rank);
+  std::vector<uint64_t> recsz(nb1);
   const int L0 = p.read_len[0], sz_meta = L0 > 255 ? 2 : 1;
   for (uint32_t k = 0; k < nb1; k++) {
     const int lv = bucket_pattern[k] == SCALCE_ROOT_CORE ? 0 : scalce_pattern_length(ctx, bucket_pattern[k]);
     recsz[k] = (uint64_t)((L0 - lv + 3) / 4 + sz_meta);
-    for (int r = 0; r < world; r++) Cg[k] += res.counts[(size_t)r * nb1 + k];
   }
-  const uint8_t magic[8] = {'s', 'c', 'a', 'l', 'c', 'e', '2', '2'};
   const uint64_t N = res.reads_total;
-  char fn[4096];
-  auto open_out = [&](const char *ext, int m) {
-    snprintf(fn, sizeof fn, "%s_%d.scalce%s", o.out.c_str(), m + 1, ext);
-    if (rank == 0) { const int f = ::open(fn, O_CREAT | O_TRUNC | O_WRONLY, 0644); if (f < 0) FAIL("Cannot create %s\n", fn); ::close(f); }
+  const bool lead = rank == 0;  // rank 0 writes the file headers
+  auto open_out = [&](int m, char ext, const std::vector<uint8_t> &header) {
+    const std::string fn = archive_path(o.out, m, ext);
+    if (lead) {
+      const int f = ::open(fn.c_str(), O_CREAT | O_TRUNC | O_WRONLY, 0644);
+      if (f < 0) FAIL("Cannot create %s\n", fn.c_str());
+      ::close(f);
+    }
     scalce_comm_barrier(comm, s);
-    const int f = ::open(fn, O_WRONLY);
-    if (f < 0) FAIL("Cannot open %s\n", fn);
+    const int f = ::open(fn.c_str(), O_WRONLY);
+    if (f < 0) FAIL("Cannot open %s\n", fn.c_str());
+    if (lead) pwrite_all(f, header.data(), header.size(), 0);
     return f;
   };
-  auto host_copy = [&](int which, int m) { return fetch(ctx, b, which, m); };
   for (int m = 0; m < nm; m++) {
-    {  // .scalcer
-      const int f = open_out("r", m);
-      if (rank == 0) { const int32_t noac = o.no_ac, len32 = p.read_len[m]; uint8_t h[16]; memcpy(h, magic, 8); memcpy(h + 8, &noac, 4); memcpy(h + 12, &len32, 4); pwrite_all(f, h, 16, 0); }
-      std::vector<uint8_t> mine = host_copy(SCALCE_OUT_READS, m);
-      if (m == 0) {
-        uint64_t base = 16, local = 0;
-        for (uint32_t k = 0; k < nb1; k++) {
-          if (!Cg[k]) continue;
-          if (rank == 0) { uint8_t h[12]; const int32_t core = bucket_pattern[k]; memcpy(h, &core, 4); memcpy(h + 4, &Cg[k], 8); pwrite_all(f, h, 12, base); }
-          uint64_t before = 0;
-          for (int r = 0; r < rank; r++) before += res.counts[(size_t)r * nb1 + k];
-          const uint64_t c = res.counts[(size_t)rank * nb1 + k];
-          if (c) { pwrite_all(f, mine.data() + local + 12, c * recsz[k], base + 12 + before * recsz[k]); local += 12 + c * recsz[k]; }
-          base += 12 + Cg[k] * recsz[k];
-        }
-      } else {  // mate 2: bare rows in mate 1's order
-        const uint64_t w = (uint64_t)(p.read_len[1] + 3) / 4;
-        uint64_t first = 0, local = 0;
-        for (uint32_t k = 0; k < nb1; k++) {
-          uint64_t before = 0;
-          for (int r = 0; r < rank; r++) before += res.counts[(size_t)r * nb1 + k];
-          const uint64_t c = res.counts[(size_t)rank * nb1 + k];
-          if (c) { pwrite_all(f, mine.data() + local * w, c * w, 16 + (first + before) * w); local += c; }
-          first += Cg[k];
-        }
-      }
+    const uint64_t L = (uint64_t)p.read_len[m], w = (L + 3) / 4;
+    {  // .scalcer: mate 1 in buckets, mate 2 bare rows in mate 1's order
+      const std::vector<uint8_t> h = reads_header(o, p.read_len[m]), mine = fetch(ctx, b, SCALCE_OUT_READS, m);
+      const int f = open_out(m, 'r', h);
+      if (m == 0) place_share(f, h.size(), mine.data(), reads, [&](size_t k) { return recsz[k]; }, bucket_pattern.data(), lead);
+      else place_share(f, h.size(), mine.data(), reads, [w](size_t) { return w; });
       ::close(f);
     }
     {  // .scalcen (mate 2 repeats mate 1's names, compress.cpp:450-454)
-      const int f = open_out("n", m);
-      const uint8_t un = o.use_names ? 1 : 0;
-      if (rank == 0) { uint8_t h[9]; memcpy(h, magic, 8); h[8] = un; pwrite_all(f, h, 9, 0); }
-      if (o.use_names) {
-        std::vector<uint8_t> mine = host_copy(SCALCE_OUT_NAMES, 0);
-        uint64_t base = 9, local = 0;
-        for (uint32_t k = 0; k < nb1; k++) {
-          uint64_t before = 0, all = 0;
-          for (int r = 0; r < world; r++) { if (r < rank) before += res.name_bytes[(size_t)r * nb1 + k]; all += res.name_bytes[(size_t)r * nb1 + k]; }
-          const uint64_t c = res.name_bytes[(size_t)rank * nb1 + k];
-          if (c) { pwrite_all(f, mine.data() + local, c, base + before); local += c; }
-          base += all;
-        }
-      } else if (rank == 0) {
-        const int64_t z = 0;
-        pwrite_all(f, &z, 8, 9);
-        pwrite_all(f, o.library.data(), o.library.size(), 17);
-      }
+      const std::vector<uint8_t> h = names_header(o);
+      const int f = open_out(m, 'n', h);
+      if (o.use_names) place_share(f, h.size(), fetch(ctx, b, SCALCE_OUT_NAMES, 0).data(), names, [](size_t) { return (uint64_t)1; });
       ::close(f);
     }
     {  // .scalceq
-      const int f = open_out("q", m);
-      uint64_t base = 16;
-      if (rank == 0) { const int64_t phred = p.qmap[0].offset; uint8_t h[16]; memcpy(h, magic, 8); memcpy(h + 8, &phred, 8); pwrite_all(f, h, 16, 0); }
-      if (!o.no_ac) {
-        if (rank == 0) {
-          std::vector<uint8_t> tb = host_copy(SCALCE_OUT_TABLE, m);
-          pwrite_all(f, tb.data(), tb.size(), 16);
-          const uint64_t total = N * (uint64_t)p.read_len[m];
-          pwrite_all(f, &total, 8, 16 + tb.size());
+      const std::vector<uint8_t> h = qual_header(p.qmap[0].offset);
+      const int f = open_out(m, 'q', h);
+      if (!o.no_ac) {  // the table and the symbol count, then the coded blocks of every rank in rank order
+        if (lead) {
+          const std::vector<uint8_t> tb = fetch(ctx, b, SCALCE_OUT_TABLE, m);
+          pwrite_all(f, tb.data(), tb.size(), h.size());
+          const uint64_t total = N * L;
+          pwrite_all(f, &total, 8, h.size() + tb.size());
         }
-        base = 16 + 2048000 + 8;
         uint64_t before = 0;
         for (int r = 0; r < rank; r++) before += res.coded_bytes[m][r];
-        std::vector<uint8_t> mine = host_copy(SCALCE_OUT_QUAL, m);
-        pwrite_all(f, mine.data(), mine.size(), base + before);
+        const std::vector<uint8_t> mine = fetch(ctx, b, SCALCE_OUT_QUAL, m);
+        pwrite_all(f, mine.data(), mine.size(), h.size() + QTABLE_WORDS * 4 + 8 + before);
       } else {  // -A: the raw q' rows, bucket by bucket in rank order (compress.cpp:389-390)
-        std::vector<uint8_t> mine = host_copy(SCALCE_OUT_QSTREAM, m);
-        const uint64_t w = (uint64_t)p.read_len[m];
-        uint64_t first = 0, local = 0;
-        for (uint32_t k = 0; k < nb1; k++) {
-          uint64_t before = 0;
-          for (int r = 0; r < rank; r++) before += res.counts[(size_t)r * nb1 + k];
-          const uint64_t c = res.counts[(size_t)rank * nb1 + k];
-          if (c) { pwrite_all(f, mine.data() + local * w, c * w, 16 + (first + before) * w); local += c; }
-          first += Cg[k];
-        }
+        place_share(f, h.size(), fetch(ctx, b, SCALCE_OUT_QSTREAM, m).data(), reads, [L](size_t) { return L; });
       }
       ::close(f);
     }
   }
   scalce_comm_barrier(comm, s);
   const double t3 = now();
-  if (rank == 0) {
+  if (lead) {
     LOG("\tDone with file %s, %llu reads found\n", files[0].c_str(), (unsigned long long)N);
-    LOG("Statistics:\n\tTotal number of reads: %llu\n\tRead length: first end %d\n", (unsigned long long)N, p.read_len[0]);
-    if (o.paired) LOG("\t             second end %d\n", p.read_len[1]);
-    uint64_t unb = Cg[nb1 - 1];
-    LOG("\tUnbucketed reads count: %llu, bucketed percentage %.2lf\n", (unsigned long long)unb, N ? 100.0 * (double)(N - unb) / (double)N : 0.0);
-    LOG("\tLossy percentage: %d\n", o.lossy);
+    log_statistics(o, p, N, reads.all[nb1 - 1]);
     LOG("\tGPUs: %d, spill chunks: %u, tie-break rounds: %u\n", world, res.chunks_total, res.rounds);
     LOG("\tTime elapsed: %.2f s (split + read + upload %.2f, sharded hot path %.2f, download + write %.2f)\n", t3 - t0, t1 - t0, t2 - t1, t3 - t2);
   }
@@ -1004,11 +917,7 @@ static bool plain_single_input(const Options &o, const std::vector<std::string> 
   for (int m = 0; m < (o.paired ? 2 : 1); m++) {
     std::string path = files[0];
     if (m && !second_file(files[0], path)) return true;  // (the rank reports it)
-    const int fd = ::open(path.c_str(), O_RDONLY);
-    uint8_t mg[2] = {0, 0};
-    const bool gz = fd >= 0 && ::pread(fd, mg, 2, 0) == 2 && mg[0] == 0x1F && mg[1] == 0x8B;
-    if (fd >= 0) ::close(fd);
-    if (gz) return false;
+    if (is_gzip(path)) return false;
   }
   return true;
 }
@@ -1016,13 +925,12 @@ static bool plain_single_input(const Options &o, const std::vector<std::string> 
 // leave through _exit and never get here)
 static std::vector<std::string> g_unlink_at_exit;
 static void unlink_at_exit() { for (auto &f : g_unlink_at_exit) unlink(f.c_str()); }
-static std::string materialize_inputs(Options &o, const std::vector<std::string> &files, const char *tag, std::vector<std::string> &made) {
+static std::string materialize_inputs(Options &o, const std::vector<std::string> &files, const std::string &tag) {
   struct stat st;
   std::string dir = o.temp;
   // (no silent fall-back to /tmp: at full size this is 100+ GB, and the user said where temporary files go)
   if (stat(dir.c_str(), &st) != 0 && mkdir(dir.c_str(), 0777) != 0) FAIL("Cannot create temporary directory %s (-t)\n", dir.c_str());
-  static bool registered = false;
-  if (!registered) { atexit(unlink_at_exit); registered = true; }
+  atexit(unlink_at_exit);
   // the mate digit is the LAST '1' of the path (get_second_file, const.cpp:51-64): it closes the name
   std::string base = dir + "/scalce_gpus_" + tag + "_m";
   for (char &c : base) if (&c >= &base[dir.size()] && c == '1') c = 'x';
@@ -1030,15 +938,13 @@ static std::string materialize_inputs(Options &o, const std::vector<std::string>
   for (int m = 0; m < (o.paired ? 2 : 1); m++) {
     MateSource src;
     for (auto &f : files) {
-      std::string path = f;
-      if (m && !second_file(f, path)) FAIL("Cannot get file name for paired end for file %s. File should contain character 1.\n", f.c_str());
+      const std::string path = mate_file(f, m);
       if (stat(path.c_str(), &st) != 0) FAIL("File %s does not exist or it is not accessible.\n", path.c_str());
       src.files.push_back(path);
     }
     const std::string out = base + (m ? "2" : "1");
     FILE *f = fopen(out.c_str(), "wb");
     if (!f) FAIL("Cannot create %s\n", out.c_str());
-    made.push_back(out);
     g_unlink_at_exit.push_back(out);
     uint64_t total = 0;
     for (;;) {
@@ -1077,29 +983,17 @@ static void gzip_in_place(const std::string &path) {
 static int multi_gpu_compress(const Options &o_in, const std::vector<std::string> &files_in, const char *argv0) {
   if (o_in.gpus > 64) FAIL("--gpus: at most 64\n");
   LOG("Preprocessing FASTQ files ...\n");
-  char tag[64];
-  snprintf(tag, sizeof tag, "%d_%ld", (int)getpid(), (long)time(nullptr));
-  {
-    const int hw = (int)std::thread::hardware_concurrency();
-    g_threads = o_in.threads > 0 ? o_in.threads : std::max(1, std::min(64, hw - 1));
-  }
+  const std::string tag = std::to_string(getpid()) + "_" + std::to_string((long)time(nullptr));
+  set_threads(o_in, 1);
   Options o = o_in;
   o.container = 0;  // the ranks write plain; -c gz is applied to the finished files below
-  std::vector<std::string> files = files_in, made;
+  std::vector<std::string> files = files_in;
   if (!plain_single_input(o, files)) {
     const double t0 = now();
-    files.assign(1, materialize_inputs(o, files_in, tag, made));
-    LOG("\t%zu input file(s) per mate written out as one plain file under %s (%.2f s)\n", files_in.size(),
-        made[0].substr(0, made[0].rfind('/')).c_str(), now() - t0);
+    files.assign(1, materialize_inputs(o, files_in, tag));
+    LOG("\t%zu input file(s) per mate written out as one plain file under %s (%.2f s)\n", files_in.size(), o.temp.c_str(), now() - t0);
   }
-  struct Cleanup {
-    std::vector<std::string> &v;
-    ~Cleanup() { for (auto &f : v) unlink(f.c_str()); }
-  } cleanup{made};
-  {
-    const int hw = (int)std::thread::hardware_concurrency();
-    g_threads = o.threads > 0 ? o.threads : std::max(1, std::min(64, hw / std::max(1, o.gpus)));
-  }
+  set_threads(o, o.gpus);  // (the ranks share the host)
   std::vector<pid_t> kids;
   for (int r = 0; r < o.gpus; r++) {
     const pid_t pid = fork();
@@ -1127,19 +1021,16 @@ static int multi_gpu_compress(const Options &o_in, const std::vector<std::string
   }
   if (bad) {  // what the ranks had written so far is not an archive: nothing stays behind under the output name
     for (int m = 0; m < (o.paired ? 2 : 1); m++)
-      for (const char *ext : {"r", "n", "q"}) unlink((o.out + "_" + std::to_string(m + 1) + ".scalce" + ext).c_str());
+      for (char ext : {'r', 'n', 'q'}) unlink(archive_path(o.out, m, ext).c_str());
     fprintf(stderr, "(ERROR) a rank failed\n");
     return 1;
   }
-  if (o_in.container != 0) {  // compress.cpp:249: the arithmetic-coded stream is never containerised
-    const int hw = (int)std::thread::hardware_concurrency();
-    g_threads = o_in.threads > 0 ? o_in.threads : std::max(1, std::min(64, hw - 1));
+  if (o_in.container != 0) {
+    set_threads(o_in, 1);
     const double t0 = now();
     for (int m = 0; m < (o.paired ? 2 : 1); m++)
-      for (const char *ext : {"r", "n", "q"}) {
-        if (ext[0] == 'q' && !o.no_ac) continue;
-        gzip_in_place(o.out + "_" + std::to_string(m + 1) + ".scalce" + ext);
-      }
+      for (char ext : {'r', 'n', 'q'})
+        if (gz_container(o_in, ext)) gzip_in_place(archive_path(o.out, m, ext));
     LOG("\tgzip containers written by %d host threads: %.2f s\n", g_threads, now() - t0);
   }
   LOG("Done!\n");
@@ -1197,15 +1088,15 @@ static int do_decompress(const Options &o, const std::string &path, scalce_ctx *
      // 10 of the run's 35 s
     std::vector<std::thread> rd;
     for (int m = 0; m < nm; m++) {
-      rd.emplace_back([&, m]() { R[m].v = read_file_fast(scalce_name(base[m], 'r')); });  // container sniffing (decompress.cpp:99-113): gzip magic or plain
-      rd.emplace_back([&, m]() { Nn[m].v = read_file_fast(scalce_name(base[m], 'n')); });
-      rd.emplace_back([&, m]() { Q[m].v = read_file_fast(scalce_name(base[m], 'q')); });
+      rd.emplace_back([&, m]() { R[m].v = read_whole(scalce_name(base[m], 'r')); });  // container sniffing (decompress.cpp:99-113)
+      rd.emplace_back([&, m]() { Nn[m].v = read_whole(scalce_name(base[m], 'n')); });
+      rd.emplace_back([&, m]() { Q[m].v = read_whole(scalce_name(base[m], 'q')); });
     }
     for (auto &t : rd) t.join();
   }
   for (int m = 0; m < nm; m++) {
     uint8_t mg[8];
-    if (R[m].read(mg, 8) != 8 || memcmp(mg, "scalce2", 7)) FAIL("%s is not a scalce archive\n", base[m].c_str());
+    if (R[m].read(mg, 8) != 8 || memcmp(mg, MAGIC, 7)) FAIL("%s is not a scalce archive\n", base[m].c_str());
     no_ac = 0;
     if (mg[6] == '2' && mg[7] >= '2') R[m].read(&no_ac, 4);
     Q[m].read(mg, 8);
@@ -1254,8 +1145,8 @@ static int do_decompress(const Options &o, const std::string &path, scalce_ctx *
     if (no_qual) {  // nothing to decode: the records are counted in the read stream
       total = read_stream_records(ctx, R[m].v.data() + R[m].pos, R[m].v.size() - R[m].pos, L, m == 0) * (uint64_t)L;
     } else if (!no_ac) {  // table + total + blocks -> GPU decoder
-      std::vector<uint32_t> table(512000);
-      if (Q[m].read(table.data(), 512000 * 4) != 512000 * 4) FAIL("truncated quality table\n");
+      std::vector<uint32_t> table(QTABLE_WORDS);
+      if (Q[m].read(table.data(), QTABLE_WORDS * 4) != QTABLE_WORDS * 4) FAIL("truncated quality table\n");
       Q[m].read(&total, 8);
       const size_t nb = Q[m].v.size() - Q[m].pos;
       void *d_in = nullptr;
@@ -1299,17 +1190,14 @@ static int do_decompress(const Options &o, const std::string &path, scalce_ctx *
       Downloader down;
       char fn[4096];
       int part = 1;
-      auto part_name = [&](int F) {
-        if (o.out == "-") snprintf(fn, sizeof fn, "-");
-        else if (o.split) snprintf(fn, sizeof fn, "%s.%d_%d.fastq", o.out.c_str(), part, F + 1);
-        else snprintf(fn, sizeof fn, "%s_%d.fastq", o.out.c_str(), F + 1);
-      };
       const uint64_t per = o.split ? (uint64_t)o.split : (nrec ? nrec : 1);
       for (uint64_t k0 = 0; k0 < nrec || k0 == 0; k0 += per, part++) {  // decompress.cpp:276-287: a new file every -S reads
         const uint64_t k1 = std::min<uint64_t>(nrec, k0 + per);
         const uint64_t b0 = o.split ? roff[(size_t)k0] : 0, b1 = o.split ? roff[(size_t)k1] : text_bytes;
+        if (o.out == "-") snprintf(fn, sizeof fn, "-");
+        else if (o.split) snprintf(fn, sizeof fn, "%s.%d_%d.fastq", o.out.c_str(), part, m + 1);
+        else snprintf(fn, sizeof fn, "%s_%d.fastq", o.out.c_str(), m + 1);
         OutFile fo;
-        part_name(m);
         fo.open(fn, false);
         down.range_to_file(static_cast<const uint8_t *>(d_text) + b0, b1 - b0, fo);
         fo.close();
@@ -1386,31 +1274,22 @@ int main(int argc, char **argv) {
   if (o.lossy < 0 || o.lossy > 100) FAIL("Percentage must be in range [0,100].\n");
   if (o.out == "-" && (o.split || o.paired)) FAIL("stdout can be only used with single-end file decompression. It cannot be used with --split-reads option!\n");
   if (files.empty()) FAIL("No input file specified.\n");
-  for (auto &f : files) {
-    struct stat st;
-    if (stat(f.c_str(), &st) != 0) FAIL("File %s does not exist or it is not accessible.\n", f.c_str());
-    if (o.paired) {
-      std::string f2;
-      if (!second_file(f, f2)) FAIL("Cannot get file name for paired end for file %s. File should contain character 1.\n", f.c_str());
-      if (stat(f2.c_str(), &st) != 0) FAIL("File %s does not exist or it is not accessible.\n", f2.c_str());
+  for (auto &f : files)
+    for (int m = 0; m < (o.paired ? 2 : 1); m++) {
+      const std::string path = mate_file(f, m);
+      struct stat st;
+      if (stat(path.c_str(), &st) != 0) FAIL("File %s does not exist or it is not accessible.\n", path.c_str());
     }
-  }
   if (o.gpus > 1 && !o.decompress && (o.fasta || o.no_qual))
     FAIL("-f / -Q runs on one GPU: --gpus %d is not available without qualities\n", o.gpus);
   if (o.gpus > 1 && !o.decompress) {  // forks before anything touches a GPU
     // (a run that -B does not cut anywhere is one chunk: scalce_sharded_compress sends all its rows to rank 0)
     return multi_gpu_compress(o, files, argv[0]);
   }
-  scalce_ctx *ctx = nullptr;
-  if (scalce_ctx_create(0, &ctx)) FAIL("%s\n", scalce_last_error(ctx));
+  std::vector<uint8_t> table;
   bool is_text = false;
-  std::vector<uint8_t> table = load_core_table(o, argv[0], is_text);
-  if (is_text) SCOK(ctx, scalce_patterns_load_text(ctx, (const char *)table.data(), table.size()));
-  else SCOK(ctx, scalce_patterns_load_bin(ctx, table.data(), table.size()));
-  {
-    const int hw = (int)std::thread::hardware_concurrency();
-    g_threads = o.threads > 0 ? o.threads : std::max(1, std::min(64, hw - 1));
-  }
+  scalce_ctx *ctx = open_device(o, argv[0], 0, table, is_text);
+  set_threads(o, 1);
   const double t_ready = now();
   const int rc = o.decompress ? do_decompress(o, files[0], ctx) : do_compress(o, files, ctx);
   scalce_ctx_destroy(ctx);
