@@ -94,6 +94,12 @@ typedef struct {
    * scalce_sharded_compress and scalce_pipeline_create refuse such batches (SCALCE_ERR_ARG). */
   int32_t fasta;
   int32_t no_qualities;
+  /* Interleaved paired-end input (-i; zero = as before).  Set together with `paired`: ONE text holds both mates, record
+   * 2k + m of it is mate m of pair k.  scalce_batch_ingest takes it as mate 0 (mate 1 is an error), scalce_batch_append
+   * as d_text1 (d_text2 NULL / 0) and takes whole pairs; scalce_stream_compress reads it through rd1 alone (rd2 NULL).
+   * Everything behind the ingest is -r's on the same pairs: the archive is byte for byte the one of the two split texts.
+   * One GPU only: scalce_sharded_compress refuses such batches (SCALCE_ERR_ARG). */
+  int32_t interleaved;
 } scalce_params;
 
 void scalce_params_default(scalce_params *p);
@@ -362,6 +368,15 @@ int scalce_fastq_records(scalce_ctx *ctx, int read_len, int has_buckets, const u
                          uint64_t nrecords, const uint8_t *d_qual, int64_t phred_offset, const uint8_t *names_host,
                          uint64_t names_bytes, const char *library, int mate_digit, uint8_t *d_out, uint64_t out_cap,
                          uint64_t *out_bytes, uint64_t *record_offsets_host, void *stream);
+/* Both mates of a paired archive into ONE interleaved text (-d -i): mate 1 of pair k, then mate 2 of pair k.  Arguments are
+ * scalce_fastq_records' per mate ([0]: mate 1, whose read stream has the bucket headers; [1]: mate 2); each record's bytes
+ * are the ones scalce_fastq_records writes for it with mate_digit '1' / '2'.  Both mates hold `npairs` records.
+ * out_bytes = the sum of both mates' text sizes; pair_offsets_host (optional, npairs + 1 entries): where each pair starts. */
+int scalce_fastq_records_interleaved(scalce_ctx *ctx, const int read_len[2], const uint8_t *const reads_host[2],
+                                     const uint64_t reads_bytes[2], uint64_t npairs, const uint8_t *const d_qual[2],
+                                     const int64_t phred_offset[2], const uint8_t *const names_host[2],
+                                     const uint64_t names_bytes[2], const char *library, uint8_t *d_out, uint64_t out_cap,
+                                     uint64_t *out_bytes, uint64_t *pair_offsets_host, void *stream);
 
 /* ---- runs sharded over several GPUs: one process per GPU, ONE archive -----------------------------------------
  * The reference has no distributed mode; what it carries across reads is what ranks exchange (see comm.cpp).  The

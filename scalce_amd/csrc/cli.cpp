@@ -65,6 +65,8 @@ struct Options {
   int lossy = 0, sample = 100000, threads = 0, split = 0;
   bool paired = false, use_names = true, no_ac = false, decompress = false;
   bool fasta = false, no_qual = false;    // -f (implies no qualities, main.cpp:220-223), -Q (main.cpp:270-272)
+  bool interleave = false;                // -i: pairs in ONE file, mate 1 then mate 2 (main.cpp:196,225, commented out there)
+  bool pairs() const { return paired || interleave; }  // two mates, whichever way they come in
   uint64_t bucket_set_size = 4ull << 30;  // main.cpp:68
   std::string out, library, patterns, temp = "__temp__", patterns_bin;
   int gpus = 1;                           // --gpus N: one process per GPU, ONE archive (plain-text input, -c no)
@@ -79,6 +81,10 @@ static const char *HELP_TEXT =
     "       scalce FILE_1.scalcen -d -o OUTPUT                   decompress\n"
     "  -o, --output STR            output prefix (required)\n"
     "  -r, --paired-end            FILE_1 is paired with the file whose last '1' is a '2'\n"
+    "  -i, --interleave            paired-end reads interleaved in one file (mate 1, then mate 2 of every pair; each input\n"
+    "                              file holds whole pairs).  The archive is the one -r makes of the two mates split into _1 / _2\n"
+    "                              files: names are mate 1's as -r stores them (a trailing /1 is NOT stripped).  Decompression:\n"
+    "                              one interleaved FASTQ (OUTPUT_1.fastq, or -o - for stdout; -S counts pairs).  One GPU only\n"
     "  -n, --skip-names STR        drop read names, regenerate them as STR.<index>\n"
     "  -c, --compression STR       container of the read/name streams: gz (default), pigz (= gz), no; bz is not built\n"
     "  -A, --no-arithmetic         store qualities raw instead of arithmetic coding\n"
@@ -382,6 +388,10 @@ struct MateSource {
   // does not end in a newline is given one.
   uint8_t last_byte = '\n';
   bool pending_newline = false;
+  // -i: every file must hold whole pairs (concatenated, a file with an odd record count would pair the next file's records
+  // the wrong way round).  pair_lines = lines of a pair; the newlines of the current file are counted on their way through.
+  uint64_t pair_lines = 0, file_lines = 0;
+  std::string error;  // why read_raw returned -1, when it was the input's shape
   int64_t read_raw(void *dst, uint64_t cap) {
     for (;;) {
       if (pending_newline && cap) { pending_newline = false; last_byte = '\n'; *static_cast<uint8_t *>(dst) = '\n'; return 1; }
@@ -389,12 +399,27 @@ struct MateSource {
         if (hold_at_file_end && cur >= 1) return 0;
         if (!open_next()) return 0;
         fpos = 0;
+        file_lines = 0;
       }
       const int64_t k = gz ? pgz.read(dst, cap) : read_plain(static_cast<uint8_t *>(dst), cap);
       if (k < 0) return -1;
-      if (k > 0) { last_byte = static_cast<uint8_t *>(dst)[k - 1]; return k; }
+      if (k > 0) {
+        const uint8_t *p = static_cast<const uint8_t *>(dst), *e = p + k;
+        if (pair_lines)
+          while ((p = static_cast<const uint8_t *>(memchr(p, '\n', (size_t)(e - p))))) { file_lines++; p++; }
+        last_byte = static_cast<uint8_t *>(dst)[k - 1];
+        return k;
+      }
       if (gz) { pgz.close(); gz = false; } else { ::close(fd); fd = -1; }
       if (last_byte != '\n') pending_newline = true;
+      const uint64_t lines = file_lines + (pending_newline ? 1 : 0), lpr = pair_lines / 2;
+      if (pair_lines && lines % pair_lines && lines % lpr == 0) {
+        char msg[4352];
+        snprintf(msg, sizeof msg, "(ERROR) %s holds an odd number of records (%llu): -i needs mate 1 and mate 2 of every pair\n",
+                 files[cur - 1].c_str(), (unsigned long long)(lines / lpr));
+        error = msg;
+        return -1;
+      }
     }
   }
   // a big request on a plain file is read by several threads at once
@@ -435,7 +460,7 @@ struct MateSource {
       peek.resize(old + step);
       for (got = 0; (size_t)got < step;) {
         const int64_t k = read_raw(peek.data() + old + got, step - (size_t)got);
-        if (k < 0) FAIL("Read error\n");
+        if (k < 0) FAIL("%s", error.empty() ? "Read error\n" : error.c_str());
         if (k == 0) break;
         got += k;
       }
@@ -446,15 +471,18 @@ struct MateSource {
   static int64_t read_cb(void *user, void *dst, uint64_t cap) { return static_cast<MateSource *>(user)->read(dst, cap); }
 };
 
-// sampling loop of quality_mapping_init (qualities.cpp:64-97) on the text read ahead
-static void sample_stats(const uint8_t *t, size_t n, int sample, int32_t stat[128], int &read_length) {
+// sampling loop of quality_mapping_init (qualities.cpp:64-97) on the text read ahead: the first `sample` records r with
+// r % stride == first (-i: stride 2, `first` = the mate -- the _interleave == 10 / 20 skips of qualities.cpp:67-90)
+static void sample_stats(const uint8_t *t, size_t n, int sample, int32_t stat[128], int &read_length, int stride = 1, int first = 0) {
   size_t line[5] = {0};  // where a record's four lines start, and the next record
-  for (int i = 0; i < sample; i++, line[0] = line[4]) {
+  for (long r = 0, taken = 0; taken < sample; r++, line[0] = line[4]) {
     for (int k = 1; k < 5; k++) {
       const void *nl = line[k - 1] < n ? memchr(t + line[k - 1], '\n', n - line[k - 1]) : nullptr;
       if (!nl) return;
       line[k] = (size_t)((const uint8_t *)nl - t) + 1;
     }
+    if (r % stride != first) continue;
+    taken++;
     for (size_t j = line[3]; j + 1 < line[4]; j++) stat[t[j] & 127]++;
     read_length = (int)(line[4] - 1 - line[3]);
   }
@@ -464,25 +492,29 @@ static void sample_stats(const uint8_t *t, size_t n, int sample, int32_t stat[12
 static scalce_params params_from(const Options &o) {
   scalce_params p;
   scalce_params_default(&p);
-  p.paired = o.paired; p.use_names = o.use_names; p.no_ac = o.no_ac; p.bucket_set_size = o.bucket_set_size;
-  p.fasta = o.fasta; p.no_qualities = o.no_qual;
+  p.paired = o.pairs(); p.use_names = o.use_names; p.no_ac = o.no_ac; p.bucket_set_size = o.bucket_set_size;
+  p.fasta = o.fasta; p.no_qualities = o.no_qual; p.interleaved = o.interleave;
   return p;
 }
 // Mate m's quality map and read length from the first records of the first input file (get_quality_stats,
 // compress.cpp:761).  fill_peek holds at the end of that file; under --gpus, where several files were written out as one,
 // the sample ends where the first file did (first_file_bytes).  -f: the statistics stay zero, so the offset stays 64
 // (qualities.cpp:91-101); -Q samples as usual: the offset in the header is the one detected.
+// -i: both mates from the one source, every other record of it (mate m's first record is record m).
 static void quality_model(const Options &o, MateSource &src, int m, scalce_params &p, bool log) {
-  src.fill_peek(o.fasta ? 1 : o.sample, o.fasta ? 2 : 4);
+  const int stride = o.interleave ? 2 : 1, first = o.interleave ? m : 0;
+  src.fill_peek(stride * (o.fasta ? 1 : o.sample), o.fasta ? 2 : 4);
   const size_t n = o.first_file_bytes[m] ? std::min<size_t>(src.peek.size(), o.first_file_bytes[m]) : src.peek.size();
   int32_t qhist[128] = {0};
   int rl = 0;
-  if (o.fasta) {  // nothing is sampled (qualities.cpp:65): the read length is that of line 2 of the first record
-    const uint8_t *t = src.peek.data(), *nl = (const uint8_t *)memchr(t, '\n', n);
-    const uint8_t *nl2 = nl ? (const uint8_t *)memchr(nl + 1, '\n', n - (size_t)(nl + 1 - t)) : nullptr;
+  if (o.fasta) {  // nothing is sampled (qualities.cpp:65): the read length is that of line 2 of the (mate's) first record
+    const uint8_t *t = src.peek.data(), *e = t + n, *nl = nullptr;
+    for (int k = 0; k < 2 * first + 1 && t < e; k++, t = nl + 1)  // behind the name line of record `first`
+      if (!(nl = (const uint8_t *)memchr(t, '\n', (size_t)(e - t)))) break;
+    const uint8_t *nl2 = nl && nl + 1 < e ? (const uint8_t *)memchr(nl + 1, '\n', (size_t)(e - (nl + 1))) : nullptr;
     if (nl2) rl = (int)(nl2 - nl - 1);
   } else {
-    sample_stats(src.peek.data(), n, o.sample, qhist, rl);
+    sample_stats(src.peek.data(), n, o.sample, qhist, rl, stride, first);
   }
   scalce_qmap_init(&p.qmap[m], qhist, o.lossy);
   p.read_len[m] = rl;
@@ -515,7 +547,7 @@ static scalce_ctx *open_device(const Options &o, const char *argv0, int device, 
 // the statistics lines both compress paths print
 static void log_statistics(const Options &o, const scalce_params &p, uint64_t N, uint64_t unbucketed) {
   LOG("Statistics:\n\tTotal number of reads: %llu\n\tRead length: first end %d\n", (unsigned long long)N, p.read_len[0]);
-  if (o.paired) LOG("\t             second end %d\n", p.read_len[1]);
+  if (o.pairs()) LOG("\t             second end %d\n", p.read_len[1]);
   LOG("\tUnbucketed reads count: %llu, bucketed percentage %.2lf\n", (unsigned long long)unbucketed,
       N ? 100.0 * (double)(N - unbucketed) / (double)N : 0.0);
   LOG("\tLossy percentage: %d\n", o.lossy);
@@ -524,14 +556,16 @@ static void log_statistics(const Options &o, const scalce_params &p, uint64_t N,
 // ---- compress -----------------------------------------------------------------------------------------
 static int do_compress(const Options &o, const std::vector<std::string> &files, scalce_ctx *ctx) {
   const double t0 = now();
-  const int nm = o.paired ? 2 : 1;
+  const int nm = o.pairs() ? 2 : 1;
+  const int nsrc = o.interleave ? 1 : nm;  // input streams: -i reads both mates from one
   uint64_t original = 0, bytes1 = 0;  // input bytes: every mate's, mate 1's
   bool plain1 = true;                 // no gzip among mate 1's files
   scalce_params p = params_from(o);
   const bool no_qual = o.fasta || o.no_qual;
   LOG("Preprocessing FASTQ files ...\n");
   MateSource src[2];
-  for (int m = 0; m < nm; m++) {
+  if (o.interleave) src[0].pair_lines = 2 * (o.fasta ? 2 : 4);
+  for (int m = 0; m < nsrc; m++) {
     for (const std::string &f : files) {
       const std::string path = mate_file(f, m);
       struct stat st;
@@ -542,9 +576,10 @@ static int do_compress(const Options &o, const std::vector<std::string> &files, 
     }
     quality_model(o, src[m], m, p, true);
   }
+  if (o.interleave) quality_model(o, src[0], 1, p, true);
   if (p.read_len[0] <= 0) FAIL("Cannot determine the read length of %s\n", files[0].c_str());
   // rows to expect: exact enough for plain text (a record is 2 L + 6 bytes plus its name), unknown behind gzip
-  const uint64_t hint = plain1 ? bytes1 / ((o.fasta ? 1 : 2) * (uint64_t)p.read_len[0] + (o.fasta ? 4 : 8)) + 64 : 0;
+  const uint64_t hint = plain1 ? bytes1 / ((o.fasta ? 1 : 2) * (uint64_t)p.read_len[0] + (o.fasta ? 4 : 8)) / (o.interleave ? 2 : 1) + 64 : 0;
   uint64_t piece = 256ull << 20;  // per chunk; three of them are pinned per mate
   if (const char *e = getenv("SCALCE_PIECE_BYTES")) piece = strtoull(e, nullptr, 10);
   if (hint && bytes1 + (1u << 20) < piece) piece = bytes1 + (1u << 20);  // small inputs: no point in pinning gigabytes
@@ -552,9 +587,10 @@ static int do_compress(const Options &o, const std::vector<std::string> &files, 
   scalce_stream_stats ss;
   char emsg[512] = "";
   const double t1 = now();
-  if (scalce_stream_compress(ctx, &p, MateSource::read_cb, &src[0], nm == 2 ? MateSource::read_cb : nullptr, nm == 2 ? &src[1] : nullptr, piece,
+  if (scalce_stream_compress(ctx, &p, MateSource::read_cb, &src[0], nsrc == 2 ? MateSource::read_cb : nullptr, nsrc == 2 ? &src[1] : nullptr, piece,
                              hint, SCALCE_STREAM_LEAN | SCALCE_STREAM_DEFER_ENTROPY, &b, &ss, emsg, sizeof emsg)) {
-    fprintf(stderr, "%s\n", emsg[0] ? emsg : scalce_last_error(ctx));
+    if (!src[0].error.empty()) fputs(src[0].error.c_str(), stderr);  // (-i: a file of odd record count; the stream only saw a read error)
+    else fprintf(stderr, "%s\n", emsg[0] ? emsg : scalce_last_error(ctx));
     exit(1);
   }
   const double t2 = now();
@@ -1078,9 +1114,9 @@ static uint64_t read_stream_records(scalce_ctx *ctx, const uint8_t *p, uint64_t 
 
 static int do_decompress(const Options &o, const std::string &path, scalce_ctx *ctx) {
   const double t0 = now();
-  const int nm = o.paired ? 2 : 1;
+  const int nm = o.pairs() ? 2 : 1;
   std::string base[2] = {path, path};
-  if (o.paired && !second_file(path, base[1])) FAIL("Cannot get file name for paired end for file %s.\n", path.c_str());
+  if (o.pairs() && !second_file(path, base[1])) FAIL("Cannot get file name for paired end for file %s.\n", path.c_str());
   Reader R[2], Q[2], Nn[2];
   int32_t len[2] = {0, 0}, no_ac = 0;
   int64_t phred[2] = {0, 0};
@@ -1136,6 +1172,38 @@ static int do_decompress(const Options &o, const std::string &path, scalce_ctx *
   const double t_files = now() - t0;
   double t_decode = 0, t_records = 0;
   std::atomic<double> t_write{0};
+  // the text of `nrec` records (pairs under -i) comes down in slices through pinned buffers while the previous slices are
+  // being written; roff: where every record (pair) starts, for -S
+  auto writer = [&o, &t_write](int m, uint64_t nrec, uint64_t text_bytes, void *d_text, std::vector<uint64_t> roff) {
+    return [&o, &t_write, m, nrec, text_bytes, d_text, roff = std::move(roff)]() {
+      const double tw = now();
+      HIPOK(hipSetDevice(0));
+      Downloader down;
+      char fn[4096];
+      int part = 1;
+      const uint64_t per = o.split ? (uint64_t)o.split : (nrec ? nrec : 1);
+      for (uint64_t k0 = 0; k0 < nrec || k0 == 0; k0 += per, part++) {  // decompress.cpp:276-287: a new file every -S reads
+        const uint64_t k1 = std::min<uint64_t>(nrec, k0 + per);
+        const uint64_t b0 = o.split ? roff[(size_t)k0] : 0, b1 = o.split ? roff[(size_t)k1] : text_bytes;
+        if (o.out == "-") snprintf(fn, sizeof fn, "-");
+        else if (o.split) snprintf(fn, sizeof fn, "%s.%d_%d.fastq", o.out.c_str(), part, m + 1);
+        else snprintf(fn, sizeof fn, "%s_%d.fastq", o.out.c_str(), m + 1);
+        OutFile fo;
+        fo.open(fn, false);
+        down.range_to_file(static_cast<const uint8_t *>(d_text) + b0, b1 - b0, fo);
+        fo.close();
+        LOG("Created %s with %lld %s\n", fn, (long long)(k1 - k0), o.interleave ? "pairs" : "reads");
+        if (!nrec) break;
+      }
+      hipFree(d_text);
+      const double dt = now() - tw;
+      for (double cur = t_write.load(); !t_write.compare_exchange_weak(cur, cur + dt);) {}
+    };
+  };
+  // -i: what the loop leaves of each mate for the one interleaved text behind it
+  void *il_q[2] = {nullptr, nullptr};
+  uint64_t il_nrec[2] = {0, 0}, il_nnames[2] = {0, 0};
+  const uint8_t *il_npay[2] = {nullptr, nullptr};
   for (int m = 0; m < nm; m++) {
     const int L = len[m];
     const double ta = now();
@@ -1168,6 +1236,11 @@ static int do_decompress(const Options &o, const std::string &path, scalce_ctx *
     const uint8_t *npay = names ? Nn[m].v.data() + Nn[m].pos : nullptr;
     const uint64_t nbytes_names = names ? Nn[m].v.size() - Nn[m].pos : 0;
     if (names && nbytes_names < nrec) FAIL("truncated name stream\n");
+    if (o.interleave) {  // both mates go into one text behind this loop
+      il_q[m] = d_q; il_nrec[m] = nrec; il_npay[m] = npay; il_nnames[m] = nbytes_names;
+      t_decode += now() - ta;
+      continue;
+    }
     const uint64_t cap = (no_qual ? scalce_fasta_text_bytes : scalce_fastq_text_bytes)(L, nrec, nbytes_names, names ? nullptr : library.c_str());
     void *d_text = nullptr;
     HIPOK(hipMalloc(&d_text, cap + 64));
@@ -1177,44 +1250,43 @@ static int do_decompress(const Options &o, const std::string &path, scalce_ctx *
     std::vector<uint64_t> roff;
     if (o.split) roff.resize((size_t)nrec + 1);
     SCOK(ctx, scalce_fastq_records(ctx, L, m == 0, R[m].v.data() + R[m].pos, R[m].v.size() - R[m].pos, nrec, (const uint8_t *)d_q,
-                                   phred[m], npay, nbytes_names, library.c_str(), o.paired ? '1' + m : 0, (uint8_t *)d_text, cap,
+                                   phred[m], npay, nbytes_names, library.c_str(), o.pairs() ? '1' + m : 0, (uint8_t *)d_text, cap,
                                    &text_bytes, o.split ? roff.data() : nullptr, nullptr));
     hipFree(d_q);
     release(R[m].v);
     release(Nn[m].v);
     t_records += now() - tb;
-    // the text comes down in slices through pinned buffers while the previous slices are being written
-    auto write_out = [&o, &t_write, m, nrec, text_bytes, d_text, roff = std::move(roff)]() {
-      const double tw = now();
-      HIPOK(hipSetDevice(0));
-      Downloader down;
-      char fn[4096];
-      int part = 1;
-      const uint64_t per = o.split ? (uint64_t)o.split : (nrec ? nrec : 1);
-      for (uint64_t k0 = 0; k0 < nrec || k0 == 0; k0 += per, part++) {  // decompress.cpp:276-287: a new file every -S reads
-        const uint64_t k1 = std::min<uint64_t>(nrec, k0 + per);
-        const uint64_t b0 = o.split ? roff[(size_t)k0] : 0, b1 = o.split ? roff[(size_t)k1] : text_bytes;
-        if (o.out == "-") snprintf(fn, sizeof fn, "-");
-        else if (o.split) snprintf(fn, sizeof fn, "%s.%d_%d.fastq", o.out.c_str(), part, m + 1);
-        else snprintf(fn, sizeof fn, "%s_%d.fastq", o.out.c_str(), m + 1);
-        OutFile fo;
-        fo.open(fn, false);
-        down.range_to_file(static_cast<const uint8_t *>(d_text) + b0, b1 - b0, fo);
-        fo.close();
-        LOG("Created %s with %lld reads\n", fn, (long long)(k1 - k0));
-        if (!nrec) break;
-      }
-      hipFree(d_text);
-      const double dt = now() - tw;
-      for (double cur = t_write.load(); !t_write.compare_exchange_weak(cur, cur + dt);) {}
-    };
+    auto write_out = writer(m, nrec, text_bytes, d_text, std::move(roff));
     if (nm == 2 && o.out != "-") writers.emplace_back(std::move(write_out));  // (stdout takes one mate: decompress.cpp refuses -r with "-")
     else write_out();
+  }
+  if (o.interleave) {  // records of both mates -> ONE text, mate 1 then mate 2 of every pair (scalce_fastq_records_interleaved)
+    if (il_nrec[0] != il_nrec[1])
+      FAIL("(ERROR) the mates of %s hold %llu and %llu records\n", path.c_str(), (unsigned long long)il_nrec[0], (unsigned long long)il_nrec[1]);
+    const double tb = now();
+    const uint64_t npairs = il_nrec[0];
+    uint64_t cap = 0;
+    for (int m = 0; m < 2; m++)
+      cap += (no_qual ? scalce_fasta_text_bytes : scalce_fastq_text_bytes)(len[m], npairs, il_nnames[m], names ? nullptr : library.c_str());
+    void *d_text = nullptr;
+    HIPOK(hipMalloc(&d_text, cap + 64));
+    uint64_t text_bytes = 0;
+    std::vector<uint64_t> poff;
+    if (o.split) poff.resize((size_t)npairs + 1);
+    const int rl[2] = {len[0], len[1]};
+    const uint8_t *rh[2] = {R[0].v.data() + R[0].pos, R[1].v.data() + R[1].pos};
+    const uint64_t rb[2] = {R[0].v.size() - R[0].pos, R[1].v.size() - R[1].pos};
+    const uint8_t *dq[2] = {(const uint8_t *)il_q[0], (const uint8_t *)il_q[1]};
+    SCOK(ctx, scalce_fastq_records_interleaved(ctx, rl, rh, rb, npairs, dq, phred, il_npay, il_nnames, library.c_str(), (uint8_t *)d_text, cap,
+                                               &text_bytes, o.split ? poff.data() : nullptr, nullptr));
+    for (int m = 0; m < 2; m++) { hipFree(il_q[m]); release(R[m].v); release(Nn[m].v); }
+    t_records += now() - tb;
+    writer(0, npairs, text_bytes, d_text, std::move(poff))();
   }
   for (auto &t : writers) t.join();
   for (auto &t : droppers) t.join();
   LOG("\tTime elapsed: %.2f s (archive files read %.2f; qualities up and decoded %.2f; records to text %.2f; text down and written %.2f%s)\n",
-      now() - t0, t_files, t_decode, t_records, t_write.load(), nm == 2 ? ", a thread per mate beside the next mate's decode" : "");
+      now() - t0, t_files, t_decode, t_records, t_write.load(), nm == 2 && !o.interleave ? ", a thread per mate beside the next mate's decode" : "");
   return 0;
 }
 
@@ -1228,9 +1300,9 @@ int main(int argc, char **argv) {
                                      {"bucket-set-size", 1, 0, 'B'}, {"paired-end", 0, 0, 'r'}, {"skip-names", 1, 0, 'n'},
                                      {"split-reads", 1, 0, 'S'}, {"fasta", 0, 0, 'f'}, {"threads", 1, 0, 'T'},
                                      {"version", 0, 0, 'v'}, {"no-arithmetic", 0, 0, 'A'}, {"patterns-bin", 1, 0, 1000},
-                                     {"gpus", 1, 0, 1001}, {0, 0, 0, 0}};
+                                     {"gpus", 1, 0, 1001}, {"interleave", 0, 0, 'i'}, {0, 0, 0, 0}};
   int opt;
-  while ((opt = getopt_long(argc, argv, "vhp:T:dc:o:fs:t:B:rQAn:P:S:", long_opt, 0)) != -1) {
+  while ((opt = getopt_long(argc, argv, "vhp:T:dc:o:fs:t:B:rQAn:P:S:i", long_opt, 0)) != -1) {
     switch (opt) {
       case 'v': return 0;
       case 'h': fputs(HELP_TEXT, stdout); return 0;
@@ -1255,6 +1327,7 @@ int main(int argc, char **argv) {
       case 'T': o.threads = atoi(optarg); break;
       case 'S': o.split = atoi(optarg); break;
       case 'r': o.paired = true; break;
+      case 'i': o.interleave = true; break;
       case 's': o.sample = atoi(optarg); break;
       case 'd': o.decompress = true; break;
       case 'P': o.patterns = optarg; break;
@@ -1268,6 +1341,7 @@ int main(int argc, char **argv) {
   }
   std::vector<std::string> files(argv + optind, argv + argc);
   // check_arguments, main.cpp:120-164
+  if (o.interleave && o.paired) FAIL("Interleaved option (-i) cannot be used with paired-end option (-r).\n");
   if (o.out.empty()) FAIL("No output file specified.\n");
   if (!o.use_names && o.library.empty()) FAIL("No library name specified.\n");
   if (o.decompress && files.size() > 1) FAIL("Too many files specified (decompression only supports one file).\n");
@@ -1282,6 +1356,8 @@ int main(int argc, char **argv) {
     }
   if (o.gpus > 1 && !o.decompress && (o.fasta || o.no_qual))
     FAIL("-f / -Q runs on one GPU: --gpus %d is not available without qualities\n", o.gpus);
+  if (o.gpus > 1 && !o.decompress && o.interleave)
+    FAIL("-i runs on one GPU: --gpus %d is not available for interleaved input\n", o.gpus);
   if (o.gpus > 1 && !o.decompress) {  // forks before anything touches a GPU
     // (a run that -B does not cut anywhere is one chunk: scalce_sharded_compress sends all its rows to rank 0)
     return multi_gpu_compress(o, files, argv[0]);

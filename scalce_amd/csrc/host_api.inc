@@ -3,7 +3,7 @@ extern "C" int scalce_batch_compress(scalce_batch *b, const uint8_t *t1, uint64_
   if (!b) return SCALCE_ERR_ARG;
   int rc;
   if ((rc = scalce_batch_ingest(b, 0, t1, n1, stream))) return rc;
-  if (b->nm == 2 && (rc = scalce_batch_ingest(b, 1, t2, n2, stream))) return rc;
+  if (b->ntext == 2 && (rc = scalce_batch_ingest(b, 1, t2, n2, stream))) return rc;  // (-i: mate 0's text holds both)
   if ((rc = scalce_batch_quality(b, stream))) return rc;
   if ((rc = scalce_batch_tokenize(b, nullptr, stream))) return rc;
   if ((rc = scalce_batch_order(b, stream))) return rc;
@@ -20,7 +20,7 @@ extern "C" int scalce_batch_front(scalce_batch *b, const uint8_t *t1, uint64_t n
   if (!b) return SCALCE_ERR_ARG;
   int rc;
   if ((rc = scalce_batch_ingest(b, 0, t1, n1, stream))) return rc;
-  if (b->nm == 2 && (rc = scalce_batch_ingest(b, 1, t2, n2, stream))) return rc;
+  if (b->ntext == 2 && (rc = scalce_batch_ingest(b, 1, t2, n2, stream))) return rc;  // (-i: mate 0's text holds both)
   // the quality statistics run beside the tie-break's sweeps (quality_beside, host_tokenize.inc) -- or here, when the
   // tokenizer never gets there (no tie reads, another tie-break path) or stage times are being taken
   b->quality_deferred = !b->timing && !b->p.no_ac && !b->nq;  // (-Q / -f: nothing to fork)

@@ -118,10 +118,30 @@ extern "C" uint64_t scalce_fasta_text_bytes(int read_len, uint64_t nrecords, uin
   return N * (strlen(library) + L + 4) + digits;
 }
 
-extern "C" int scalce_fastq_records(scalce_ctx *c, int read_len, int has_buckets, const uint8_t *reads_host, uint64_t reads_bytes,
-                                    uint64_t nrecords, const uint8_t *d_qual, int64_t phred_offset, const uint8_t *names_host,
-                                    uint64_t names_bytes, const char *library, int mate_digit, uint8_t *d_out, uint64_t out_cap,
-                                    uint64_t *out_bytes, uint64_t *record_offsets_host, void *stream) {
+// where every name starts (each length byte says where the next one is: serial); false: the stream is short
+static bool name_offsets(const uint8_t *names_host, uint64_t names_bytes, uint64_t nrecords, std::vector<u64> &name_off) {
+  name_off.resize(nrecords + 1);
+  u64 pos = 0;
+  for (u64 k = 0; k < nrecords; k++) {
+    if (pos >= names_bytes) return false;
+    name_off[k] = pos;
+    pos += 1 + (u64)names_host[pos];
+  }
+  if (pos > names_bytes) return false;
+  name_off[nrecords] = pos;
+  return true;
+}
+// -d -i: this mate's records go into the text both mates share (FqArgs::il)
+struct FqPairHost {
+  u32 il;                        // 1: mate 1, 2: mate 2
+  int pair_L;                    // the other mate's read length
+  const std::vector<u64> *pair_noff;  // the other mate's name offsets (names mode)
+  u64 total;                     // bytes of the whole interleaved text
+};
+static int fastq_records_impl(scalce_ctx *c, int read_len, int has_buckets, const uint8_t *reads_host, uint64_t reads_bytes,
+                              uint64_t nrecords, const uint8_t *d_qual, int64_t phred_offset, const uint8_t *names_host,
+                              uint64_t names_bytes, const char *library, int mate_digit, uint8_t *d_out, uint64_t out_cap,
+                              uint64_t *out_bytes, uint64_t *record_offsets_host, void *stream, const FqPairHost *pair) {
   if (!c || read_len <= 0 || !reads_host || (!names_host && !library) || !d_out) return SCALCE_ERR_ARG;
   const bool qual = d_qual != nullptr;  // NULL: two-line records of an archive without qualities
   hipStream_t s = (hipStream_t)stream;
@@ -172,18 +192,11 @@ extern "C" int scalce_fastq_records(scalce_ctx *c, int read_len, int has_buckets
   // 2. where every name starts (each length byte says where the next one is: serial as well)
   std::vector<u64> name_off;
   if (names_host) {
-    name_off.resize(nrecords + 1);
-    u64 pos = 0;
-    for (u64 k = 0; k < nrecords; k++) {
-      if (pos >= names_bytes) { set_err(c, "(ERROR) truncated name stream"); return SCALCE_ERR_FORMAT; }
-      name_off[k] = pos;
-      pos += 1 + (u64)names_host[pos];
-    }
-    if (pos > names_bytes) { set_err(c, "(ERROR) truncated name stream"); return SCALCE_ERR_FORMAT; }
-    name_off[nrecords] = pos;
-    names_bytes = pos;
+    if (!name_offsets(names_host, names_bytes, nrecords, name_off)) { set_err(c, "(ERROR) truncated name stream"); return SCALCE_ERR_FORMAT; }
+    names_bytes = name_off[nrecords];
   }
-  const u64 total = (qual ? scalce_fastq_text_bytes : scalce_fasta_text_bytes)(read_len, nrecords, names_bytes, names_host ? nullptr : library);
+  const u64 total = pair ? pair->total
+                         : (qual ? scalce_fastq_text_bytes : scalce_fasta_text_bytes)(read_len, nrecords, names_bytes, names_host ? nullptr : library);
   if (out_bytes) *out_bytes = total;
   if (total > out_cap) { set_err(c, "output buffer of %llu bytes, the text needs %llu", (unsigned long long)out_cap, (unsigned long long)total); return SCALCE_ERR_CAPACITY; }
   if (!nrecords) return SCALCE_OK;
@@ -191,8 +204,8 @@ extern "C" int scalce_fastq_records(scalce_ctx *c, int read_len, int has_buckets
   memset(&a, 0, sizeof a);
   u8 *d_reads = nullptr, *d_names = nullptr;
   FqBucket *d_dir = nullptr;
-  u64 *d_noff = nullptr, *d_roff = nullptr;
-  auto release = [&]() { hipFree(d_reads); hipFree(d_names); hipFree(d_dir); hipFree(d_noff); hipFree(d_roff); };
+  u64 *d_noff = nullptr, *d_roff = nullptr, *d_pnoff = nullptr;
+  auto release = [&]() { hipFree(d_reads); hipFree(d_names); hipFree(d_dir); hipFree(d_noff); hipFree(d_roff); hipFree(d_pnoff); };
 #define FQ_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { release(); set_err(c, "%s failed: %s", #expr, hipGetErrorString(e_)); return SCALCE_ERR_HIP; } } while (0)
   FQ_TRY(hipMalloc(&d_reads, reads_bytes + 64));
   FQ_TRY(hipMalloc(&d_dir, sizeof(FqBucket) * dir.size()));
@@ -203,6 +216,10 @@ extern "C" int scalce_fastq_records(scalce_ctx *c, int read_len, int has_buckets
     FQ_TRY(hipMalloc(&d_noff, sizeof(u64) * (nrecords + 1)));
     FQ_TRY(hipMemcpyAsync(d_names, names_host, names_bytes, hipMemcpyHostToDevice, s));
     FQ_TRY(hipMemcpyAsync(d_noff, name_off.data(), sizeof(u64) * (nrecords + 1), hipMemcpyHostToDevice, s));
+    if (pair) {
+      FQ_TRY(hipMalloc(&d_pnoff, sizeof(u64) * (nrecords + 1)));
+      FQ_TRY(hipMemcpyAsync(d_pnoff, pair->pair_noff->data(), sizeof(u64) * (nrecords + 1), hipMemcpyHostToDevice, s));
+    }
   } else {
     a.lib_len = (u32)std::min<size_t>(strlen(library), sizeof a.lib - 1);
     if (strlen(library) >= sizeof a.lib) { release(); set_err(c, "library name longer than %zu characters", sizeof a.lib - 1); return SCALCE_ERR_ARG; }
@@ -212,6 +229,7 @@ extern "C" int scalce_fastq_records(scalce_ctx *c, int read_len, int has_buckets
   a.reads = d_reads; a.dir = d_dir; a.nbuckets = (u32)dir.size(); a.nrecords = nrecords; a.L = L; a.sz_meta = sz_meta;
   a.qual = d_qual; a.phred = (u32)phred_offset; a.names = d_names; a.name_off = d_noff;
   a.mate_digit = (u32)mate_digit; a.out = d_out; a.rec_off = d_roff;
+  if (pair) { a.il = pair->il; a.pair_L = (u32)pair->pair_L; a.pair_name_off = d_pnoff; }
   const u64 waves = (nrecords + FQ_RECORDS_PER_WAVE - 1) / FQ_RECORDS_PER_WAVE;
   if (qual) LAUNCH(fastq_records_k<true>, cdiv(waves, 4), 256, 0, s, a);
   else LAUNCH(fastq_records_k<false>, cdiv(waves, 4), 256, 0, s, a);
@@ -221,5 +239,44 @@ extern "C" int scalce_fastq_records(scalce_ctx *c, int read_len, int has_buckets
   FQ_TRY(hipGetLastError());
 #undef FQ_TRY
   release();
+  return SCALCE_OK;
+}
+
+extern "C" int scalce_fastq_records(scalce_ctx *c, int read_len, int has_buckets, const uint8_t *reads_host, uint64_t reads_bytes,
+                                    uint64_t nrecords, const uint8_t *d_qual, int64_t phred_offset, const uint8_t *names_host,
+                                    uint64_t names_bytes, const char *library, int mate_digit, uint8_t *d_out, uint64_t out_cap,
+                                    uint64_t *out_bytes, uint64_t *record_offsets_host, void *stream) {
+  return fastq_records_impl(c, read_len, has_buckets, reads_host, reads_bytes, nrecords, d_qual, phred_offset, names_host, names_bytes,
+                            library, mate_digit, d_out, out_cap, out_bytes, record_offsets_host, stream, nullptr);
+}
+
+// -d -i: both mates into one text, each by the kernel that writes its own text, at the places the pairs give
+extern "C" int scalce_fastq_records_interleaved(scalce_ctx *c, const int read_len[2], const uint8_t *const reads_host[2],
+                                                const uint64_t reads_bytes[2], uint64_t npairs, const uint8_t *const d_qual[2],
+                                                const int64_t phred_offset[2], const uint8_t *const names_host[2],
+                                                const uint64_t names_bytes[2], const char *library, uint8_t *d_out, uint64_t out_cap,
+                                                uint64_t *out_bytes, uint64_t *pair_offsets_host, void *stream) {
+  if (!c || !read_len || !reads_host || !reads_bytes || !d_qual || !phred_offset || !names_host || !names_bytes || !d_out) return SCALCE_ERR_ARG;
+  const bool names = names_host[0] != nullptr;
+  if ((names_host[1] != nullptr) != names || (!names && !library) || (d_qual[0] != nullptr) != (d_qual[1] != nullptr)) return SCALCE_ERR_ARG;
+  const bool qual = d_qual[0] != nullptr;
+  std::vector<u64> noff[2];
+  u64 total = 0;
+  for (int m = 0; m < 2; m++) {
+    u64 nb = names_bytes[m];
+    if (names) {
+      if (!name_offsets(names_host[m], names_bytes[m], npairs, noff[m])) { set_err(c, "(ERROR) truncated name stream"); return SCALCE_ERR_FORMAT; }
+      nb = noff[m][npairs];
+    }
+    total += (qual ? scalce_fastq_text_bytes : scalce_fasta_text_bytes)(read_len[m], npairs, nb, names ? nullptr : library);
+  }
+  if (out_bytes) *out_bytes = total;
+  if (total > out_cap) { set_err(c, "output buffer of %llu bytes, the text needs %llu", (unsigned long long)out_cap, (unsigned long long)total); return SCALCE_ERR_CAPACITY; }
+  for (int m = 0; m < 2; m++) {
+    const FqPairHost pr{(u32)(m + 1), read_len[1 - m], &noff[1 - m], total};
+    int rc = fastq_records_impl(c, read_len[m], m == 0, reads_host[m], reads_bytes[m], npairs, d_qual[m], phred_offset[m], names_host[m],
+                                names_bytes[m], library, '1' + m, d_out, out_cap, nullptr, m == 0 ? pair_offsets_host : nullptr, stream, &pr);
+    if (rc) return rc;
+  }
   return SCALCE_OK;
 }

@@ -343,8 +343,8 @@ static int entropy_rerun_from_text(scalce_batch *b, hipStream_t s) {
   }
   static const bool dbg = getenv("SCALCE_TRACE") != nullptr;
   if (dbg) fprintf(stderr, "scalce: batch %p: a block coded in place caught up with its input: the shard is run again from its text\n", (void *)b);
-  const u8 *t1 = b->piece_text[0], *t2 = b->nm == 2 ? b->piece_text[1] : nullptr;
-  const u64 n1 = b->text_bytes[0], n2 = b->nm == 2 ? b->text_bytes[1] : 0;
+  const u8 *t1 = b->piece_text[0], *t2 = b->ntext == 2 ? b->piece_text[1] : nullptr;
+  const u64 n1 = b->text_bytes[0], n2 = b->ntext == 2 ? b->text_bytes[1] : 0;
   for (int m = 0; m < 2; m++) { b->frame_deferred[m] = 0; b->ent_pending[m] = 0; b->in_place_now[m] = false; }
   b->in_place_suspended = true;
   b->reruns++;

@@ -22,16 +22,16 @@ static int piece_count(scalce_batch *b, int mate, const u8 *d_text, u64 nbytes, 
 }
 
 // the line index of the piece (index_write_k), built when something needs it: the indexed unpack kernels, names longer
-// than a cell, scalce_batch_text_offset
+// than a cell, scalce_batch_text_offset (interleaved: mate 0's, which is both mates')
 static int ensure_line_index(scalce_batch *b, int mate, hipStream_t s) {
   if (b->line_index_ok[mate]) return SCALCE_OK;
   const u64 nrec = b->NP, nbytes = b->text_bytes[mate];
   if (nrec > b->piece_rows_cap || !b->line_end[mate].p) {
     if (nrec > b->piece_rows_cap) b->piece_rows_cap = nrec;
-    ENSURE(b, b->line_end[mate], sizeof(u64) * b->lpr * (b->piece_rows_cap + 1));
+    ENSURE(b, b->line_end[mate], sizeof(u64) * b->unit_lines() * (b->piece_rows_cap + 1));
   }
   const u32 ntiles = cdiv(nbytes, IDX_TILE);
-  if (ntiles) LAUNCH(index_write_k, ntiles, IDX_THREADS, 0, s, b->piece_text[mate], nbytes, b->tile[mate].as<u64>(), b->line_end[mate].as<u64>(), (u64)b->lpr * nrec);
+  if (ntiles) LAUNCH(index_write_k, ntiles, IDX_THREADS, 0, s, b->piece_text[mate], nbytes, b->tile[mate].as<u64>(), b->line_end[mate].as<u64>(), b->unit_lines() * nrec);
   b->line_index_ok[mate] = true;
   return SCALCE_OK;
 }
@@ -39,34 +39,44 @@ static int ensure_line_index(scalce_batch *b, int mate, hipStream_t s) {
 // the first `nrec` records of the text -> rows [base, base + nrec): 2-bit bases, q', names
 // (A one-pass variant -- no count pass, the tiles' line bases by decoupled look-back between the workgroups -- was byte-exact
 // and slower: 9.2 ms against 1.7 + 6.2 at 50 M x 100 bp, rounds 3-4; removed in round 5.)
-// LPR = lines per record, QOUT = q' rows written: the record variants of the kernels (unpack_record_at)
-template <int LPR, bool QOUT>
+// LPR = lines per record, QOUT = q' rows written, IL = interleaved pairs: the record variants of the kernels (unpack_record_at).
+// IL: called for mate 0 with the one text, which it ingests for both mates -- nrec pairs, one count, one line index.
+template <int LPR, bool QOUT, bool IL>
 static int piece_unpack_t(scalce_batch *b, int mate, const u8 *d_text, u64 nbytes, u64 nrec, hipStream_t s) {
-  constexpr auto k_tiles2 = &ingest_tiles2_k<LPR, QOUT>;
-  constexpr auto k_unpack_tiled = &unpack_tiled_k<LPR, QOUT>;
-  constexpr auto k_unpack = &unpack_k<LPR, QOUT>;
-  constexpr auto k_last_end = &last_record_end_k<LPR>;
-  constexpr auto k_long_names = &long_names_k<LPR>;
+  constexpr auto k_tiles2 = &ingest_tiles2_k<LPR, QOUT, IL>;
+  constexpr auto k_unpack_tiled = &unpack_tiled_k<LPR, QOUT, IL>;
+  constexpr auto k_unpack = &unpack_k<LPR, QOUT, IL>;
+  constexpr auto k_last_end = &last_record_end_k<LPR, IL>;
+  constexpr auto k_long_names = &long_names_k<LPR, IL>;
+  constexpr int NMATE = IL ? 2 : 1;
   scalce_ctx *c = b->ctx;
-  b->piece_text[mate] = d_text;
-  b->line_index_ok[mate] = false;
-  b->piece_consumed[mate] = 0;
+  for (int m = mate; m < mate + NMATE; m++) {
+    b->piece_text[m] = d_text;
+    b->text_bytes[m] = nbytes;
+    b->line_index_ok[m] = false;
+    b->piece_consumed[m] = 0;
+  }
   if (!nrec) return SCALCE_OK;
-  UnpackArgs a;
-  a.text = d_text; a.nbytes = nbytes; a.line_end = nullptr; a.nrec = nrec;
-  a.L = b->L[mate]; a.stride = b->stride[mate]; a.mate = mate; a.use_names = b->p.use_names; a.no_ac = b->p.no_ac;
-  a.packed = b->packed[mate].as<u8>() + b->base * (u64)b->stride[mate];
-  a.q = QOUT ? b->q[mate].as<u8>() + b->base * (u64)b->qstride[mate] : nullptr;
-  a.qstride = b->qstride[mate];
-  a.cellstride = 16;
-  a.packed2 = nullptr;
-  a.namelen = b->namelen.as<u8>() + b->base;
-  a.namecell = (mate == 0 && b->p.use_names) ? b->namecell.as<u8>() + 16 * b->base : nullptr;
-  const bool fused_rows = b->fused && mate == 0;
+  // the arguments of the launches that write mate m's rows
+  auto args_of = [&](int m) {
+    UnpackArgs a;
+    a.text = d_text; a.nbytes = nbytes; a.line_end = nullptr; a.nrec = nrec;
+    a.L = b->L[m]; a.stride = b->stride[m]; a.mate = m; a.use_names = b->p.use_names; a.no_ac = b->p.no_ac;
+    a.packed = b->packed[m].as<u8>() + b->base * (u64)b->stride[m];
+    a.q = QOUT ? b->q[m].as<u8>() + b->base * (u64)b->qstride[m] : nullptr;
+    a.qstride = b->qstride[m];
+    a.cellstride = 16;
+    a.packed2 = nullptr;
+    a.namelen = b->namelen.as<u8>() + b->base;
+    a.namecell = (m == 0 && b->p.use_names) ? b->namecell.as<u8>() + 16 * b->base : nullptr;
+    a.qlut = b->d_qlut[m]; a.err = b->d_err;
+    a.q_affine = b->q_affine[m];
+    a.max_namelen = b->d_small + 16;
+    return a;
+  };
+  UnpackArgs a = args_of(mate);
+  const bool fused_rows = b->fused && mate == 0;  // (never under IL: fused rows are single-end)
   if (fused_rows) a.packed2 = a.q + b->row_cell_off;  // a copy of the packed words lies behind the row's q'
-  a.qlut = b->d_qlut[mate]; a.err = b->d_err;
-  a.q_affine = b->q_affine[mate];
-  a.max_namelen = b->d_small + 16;
   u32 *slow = b->d_small + 17;
   u64 *d_consumed = b->d_small64 + 2 + mate;  // (slots 1..3 are the emit stage's, long after this)
   if (mate == 0) HIP_TRY(c, hipMemsetAsync(b->d_small + 16, 0, 2 * sizeof(u32), s));
@@ -75,32 +85,41 @@ static int piece_unpack_t(scalce_batch *b, int mate, const u8 *d_text, u64 nbyte
   // record turns out not to fit the tile overlap
   bool fused = a.L >= 16 && a.L <= 160 && !getenv("SCALCE_INGEST_INDEXED");
   u32 flags[2] = {0, 0};
-  b->mm_valid[mate] = false;
+  for (int m = mate; m < mate + NMATE; m++) b->mm_valid[m] = false;
+  if (IL) fused = fused && b->L[1] >= 16 && b->L[1] <= 160;
   if (fused) {
-    IngestArgs ia;
-    ia.u = a;
-    ia.tile_base = b->tile[mate].as<u64>();
-    ia.consumed = d_consumed;
-    ia.slow = slow;
-    {
-      const u32 ntiles2 = cdiv(nbytes, ING_TILE);
-      if (QOUT) ENSURE(b, b->tile_mm[mate], sizeof(u16) * ((size_t)ntiles2 + 8));
-      Ingest2Args ga;
-      ga.i = ia;
-      const u64 S = (u64)a.stride / 4, W = ((u64)a.L + 15) / 16;
-      ga.magic_s = ((1ull << 32) + S - 1) / S;
-      ga.magic_w = ((1ull << 32) + W - 1) / W;
-      ga.step_ks = (u32)(ING_THREADS / S); ga.step_rs = (u32)(ING_THREADS % S);
-      ga.step_kw = (u32)(ING_THREADS / W); ga.step_rw = (u32)(ING_THREADS % W);
-      ga.tile_minmax = QOUT ? b->tile_mm[mate].as<u16>() : nullptr;
-      LAUNCH(k_tiles2, ntiles2, ING_THREADS, 0, s, ga);
-      if (QOUT) {
-        b->mm_valid[mate] = true;
-        b->ws->tile_mm_owner[mate] = b;
-      }
+    const u32 ntiles2 = cdiv(nbytes, ING_TILE);
+    // one launch: mate `mate`'s arguments, and under IL mate 2's beside them (the kernel ignores the second set otherwise)
+    Ingest2Args ga[2];
+    for (int i = 0; i < NMATE; i++) {
+      const int m = mate + i;
+      IngestArgs ia;
+      ia.u = i ? args_of(m) : a;
+      ia.tile_base = b->tile[mate].as<u64>();
+      ia.consumed = d_consumed;
+      ia.slow = slow;
+      if (QOUT) ENSURE(b, b->tile_mm[m], sizeof(u16) * ((size_t)ntiles2 + 8));
+      Ingest2Args &g = ga[i];
+      g.i = ia;
+      const u64 S = (u64)ia.u.stride / 4, W = ((u64)ia.u.L + 15) / 16;
+      g.magic_s = ((1ull << 32) + S - 1) / S;
+      g.magic_w = ((1ull << 32) + W - 1) / W;
+      g.step_ks = (u32)(ING_THREADS / S); g.step_rs = (u32)(ING_THREADS % S);
+      g.step_kw = (u32)(ING_THREADS / W); g.step_rw = (u32)(ING_THREADS % W);
+      g.tile_minmax = QOUT ? b->tile_mm[m].as<u16>() : nullptr;
     }
+    if (!IL) ga[1] = ga[0];
+    LAUNCH(k_tiles2, ntiles2, ING_THREADS, 0, s, ga[0], ga[1]);
+    if (QOUT)
+      for (int m = mate; m < mate + NMATE; m++) {
+        b->mm_valid[m] = true;
+        b->ws->tile_mm_owner[m] = b;
+      }
     { int rc = read_u32(b, b->d_small + 16, flags, 2, s); if (rc) return rc; }
-    if (flags[1]) { fused = false; b->mm_valid[mate] = false; }  // a record longer than the overlap: redo the piece the indexed way
+    if (flags[1]) {  // a record longer than the overlap: redo the piece the indexed way
+      fused = false;
+      for (int m = mate; m < mate + NMATE; m++) b->mm_valid[m] = false;
+    }
   }
   if (!fused) {
     { int rc = ensure_line_index(b, mate, s); if (rc) return rc; }
@@ -113,9 +132,13 @@ static int piece_unpack_t(scalce_batch *b, int mate, const u8 *d_text, u64 nbyte
       a.qstride = (u32)a.L;
       a.packed2 = nullptr;
     }
-    if ((size_t)UNP_RPB * a.L <= (size_t)UNP_Q_CAP)
-      LAUNCH(k_unpack_tiled, cdiv(nrec, UNP_RPB), 2 * UNP_RPB, unp_text_cap(a.L) + 32 + (QOUT ? unp_q_cap(a.L) : 0u), s, a);
-    else LAUNCH(k_unpack, cdiv(nrec, 256), 256, 0, s, a);
+    for (int m = mate; m < mate + NMATE; m++) {  // (IL: mate 2 from the same text and line index)
+      UnpackArgs am = a;
+      if (m != mate) { am = args_of(m); am.line_end = a.line_end; }
+      if ((size_t)UNP_RPB * am.L <= (size_t)UNP_Q_CAP)
+        LAUNCH(k_unpack_tiled, cdiv(nrec, UNP_RPB), 2 * UNP_RPB, unp_text_cap(am.L) + 32 + (QOUT ? unp_q_cap(am.L) : 0u), s, am);
+      else LAUNCH(k_unpack, cdiv(nrec, 256), 256, 0, s, am);
+    }
     if (fused_rows)
       LAUNCH(fuse_rows_k, cdiv(nrec, 256), 256, 0, s, nrec, b->fuse_q.as<u8>(), (u32)a.L, (const u8 *)nullptr, a.packed, (u32)a.stride, b->row_pwords,
              row_q, b->qstride[0], b->row_cell_off);
@@ -144,10 +167,26 @@ static int piece_unpack_t(scalce_batch *b, int mate, const u8 *d_text, u64 nbyte
   }
   return SCALCE_OK;
 }
+template <bool IL>
+static int piece_unpack_il(scalce_batch *b, int mate, const u8 *d_text, u64 nbytes, u64 nrec, hipStream_t s) {
+  if (b->lpr == 2) return piece_unpack_t<2, false, IL>(b, mate, d_text, nbytes, nrec, s);  // -f
+  if (b->nq) return piece_unpack_t<4, false, IL>(b, mate, d_text, nbytes, nrec, s);        // -Q
+  return piece_unpack_t<4, true, IL>(b, mate, d_text, nbytes, nrec, s);
+}
+// interleaved: both mates' rows from the one text (mate 0's call); nrec counts pairs
 static int piece_unpack(scalce_batch *b, int mate, const u8 *d_text, u64 nbytes, u64 nrec, hipStream_t s) {
-  if (b->lpr == 2) return piece_unpack_t<2, false>(b, mate, d_text, nbytes, nrec, s);  // -f
-  if (b->nq) return piece_unpack_t<4, false>(b, mate, d_text, nbytes, nrec, s);        // -Q
-  return piece_unpack_t<4, true>(b, mate, d_text, nbytes, nrec, s);
+  return b->il ? piece_unpack_il<true>(b, mate, d_text, nbytes, nrec, s) : piece_unpack_il<false>(b, mate, d_text, nbytes, nrec, s);
+}
+// "(ERROR) ..." for a text whose line count does not make whole records (pairs, under -i)
+static int text_shape_error(scalce_batch *b, u64 nlines, u8 last) {
+  const u64 lpr = (u64)b->lpr;
+  if (b->il && nlines % lpr == 0 && last == '\n')
+    set_err(b->ctx, "(ERROR) interleaved text holds an odd number of records (%llu): every mate-1 record must be followed by its mate 2",
+            (unsigned long long)(nlines / lpr));
+  else
+    set_err(b->ctx, "(ERROR) %s text has %llu lines (not a multiple of %d) or no trailing newline", b->lpr == 2 ? "FASTA" : "FASTQ",
+            (unsigned long long)nlines, b->lpr);
+  return SCALCE_ERR_FORMAT;
 }
 
 static void batch_restart(scalce_batch *b) {
@@ -172,6 +211,7 @@ extern "C" int scalce_batch_reset(scalce_batch *b) {
 extern "C" int scalce_batch_ingest(scalce_batch *b, int mate, const uint8_t *d_text, uint64_t nbytes, void *stream) {
   if (!b || mate < 0 || mate >= b->nm || !d_text) return SCALCE_ERR_ARG;
   scalce_ctx *c = b->ctx;
+  if (mate >= b->ntext) { set_err(c, "interleaved batch: both mates come in one text, ingested as mate 0"); return SCALCE_ERR_ARG; }
   hipStream_t s = (hipStream_t)stream;
   HIP_TRY(c, hipSetDevice(c->device));
   StageTimer tm(b, ST_INGEST, s);
@@ -180,17 +220,14 @@ extern "C" int scalce_batch_ingest(scalce_batch *b, int mate, const uint8_t *d_t
   u8 last = '\n';
   { int rc = piece_count(b, mate, d_text, nbytes, s, &nlines, &last); if (rc) return rc; }
   HIP_TRY(c, hipStreamSynchronize(s));
-  if ((nlines % b->lpr) || last != '\n') {
-    set_err(c, "(ERROR) %s text has %llu lines (not a multiple of %d) or no trailing newline", b->lpr == 2 ? "FASTA" : "FASTQ",
-            (unsigned long long)nlines, b->lpr);
-    return SCALCE_ERR_FORMAT;
-  }
-  const u64 nrec = nlines / b->lpr;
+  if ((nlines % b->unit_lines()) || last != '\n') return text_shape_error(b, nlines, last);
+  const u64 nrec = nlines / b->unit_lines();  // (records; pairs under -i)
   if (nrec > b->max_reads) { set_err(c, "%llu records exceed the batch capacity", (unsigned long long)nrec); return SCALCE_ERR_CAPACITY; }
   if (mate == 0) { b->N = b->NP = nrec; }
   else if (nrec != b->N) { set_err(c, "(ERROR) mates have different record counts"); return SCALCE_ERR_FORMAT; }
   { int rc = piece_unpack(b, mate, d_text, nbytes, nrec, s); if (rc) return rc; }
   b->ingested[mate] = true;
+  if (b->il) b->ingested[1] = true;
   return SCALCE_OK;
 }
 
@@ -208,30 +245,27 @@ static int ingest_piece(scalce_batch *b, const uint8_t *const text[2], const u64
   u64 nlines[2] = {0, 0}, nrec = ~0ull;
   u8 last[2] = {'\n', '\n'};
   StageTimer tm(b, ST_INGEST, s);
-  for (int m = 0; m < b->nm; m++)
+  for (int m = 0; m < b->ntext; m++)
     if (nbytes[m]) { int rc = piece_count(b, m, text[m], nbytes[m], s, &nlines[m], &last[m]); if (rc) return rc; }
   HIP_TRY(c, hipStreamSynchronize(s));
-  const u64 lpr = (u64)b->lpr;
-  for (int m = 0; m < b->nm; m++) nrec = nlines[m] / lpr < nrec ? nlines[m] / lpr : nrec;
+  const u64 lpr = b->unit_lines();  // (a pair's lines under -i: pieces end on a pair boundary)
+  for (int m = 0; m < b->ntext; m++) nrec = nlines[m] / lpr < nrec ? nlines[m] / lpr : nrec;
   if (final_piece) {
-    for (int m = 0; m < b->nm; m++)
-      if ((nlines[m] % lpr) || last[m] != '\n') {
-        set_err(c, "(ERROR) %s text has %llu lines (not a multiple of %d) or no trailing newline", b->lpr == 2 ? "FASTA" : "FASTQ",
-                (unsigned long long)(lpr * b->N + nlines[m]), b->lpr);
-        return SCALCE_ERR_FORMAT;
-      }
-    if (b->nm == 2 && nlines[0] != nlines[1]) { set_err(c, "(ERROR) mates have different record counts"); return SCALCE_ERR_FORMAT; }
+    for (int m = 0; m < b->ntext; m++)
+      if ((nlines[m] % lpr) || last[m] != '\n') return text_shape_error(b, lpr * b->N + nlines[m], last[m]);
+    if (b->ntext == 2 && nlines[0] != nlines[1]) { set_err(c, "(ERROR) mates have different record counts"); return SCALCE_ERR_FORMAT; }
   }
   b->base = b->N;
   b->NP = nrec;
   if (b->base + nrec >= (1ull << 32) - 64) { set_err(c, "a batch holds fewer than 2^32 reads"); return SCALCE_ERR_CAPACITY; }
   { int rc = reserve_rows(b, b->base + nrec, b->base, s); if (rc) return rc; }
-  for (int m = 0; m < b->nm; m++) {
+  for (int m = 0; m < b->ntext; m++) {
     int rc = piece_unpack(b, m, text[m], nbytes[m], nrec, s);
     if (rc) return rc;
     b->ingested[m] = true;
     consumed[m] = nrec ? b->piece_consumed[m] : 0;  // behind the newline that ends the last record taken
   }
+  if (b->il) b->ingested[1] = true;
   HIP_TRY(c, hipStreamSynchronize(s));
   b->N = b->base + nrec;
   return SCALCE_OK;
@@ -247,7 +281,7 @@ extern "C" int scalce_batch_append(scalce_batch *b, const uint8_t *d_text1, uint
   if (b->tok_open) { set_err(c, "a tokenization is still open"); return SCALCE_ERR_ARG; }
   if (!b->appending) { batch_restart(b); b->appending = true; }
   const uint8_t *text[2] = {d_text1, d_text2};
-  const u64 nbytes[2] = {n1, b->nm == 2 ? n2 : 0};
+  const u64 nbytes[2] = {n1, b->ntext == 2 ? n2 : 0};
   int rc = ingest_piece(b, text, nbytes, final_piece != 0, consumed, s);
   if (rc) return rc;
   if (!(flags & SCALCE_APPEND_NO_QUALITY) && (rc = scalce_batch_quality(b, stream))) return rc;
@@ -264,7 +298,7 @@ extern "C" int scalce_batch_append(scalce_batch *b, const uint8_t *d_text1, uint
 // only the back end moves.  Quality statistics are NOT touched: every record was counted by the rank that ingested it first.
 extern "C" int scalce_batch_rewindow(scalce_batch *b, uint64_t keep_first, uint64_t keep_rows, const uint8_t *const front[2],
                                      const uint64_t front_bytes[2], const uint8_t *const back[2], const uint64_t back_bytes[2], void *stream) {
-  if (!b || !front || !back || !front_bytes || !back_bytes || keep_first + keep_rows > b->N) return SCALCE_ERR_ARG;
+  if (!b || !front || !back || !front_bytes || !back_bytes || keep_first + keep_rows > b->N || b->il) return SCALCE_ERR_ARG;
   scalce_ctx *c = b->ctx;
   hipStream_t s = (hipStream_t)stream;
   HIP_TRY(c, hipSetDevice(c->device));

@@ -374,6 +374,11 @@ struct scalce_batch {
   // anywhere -- no q' rows, no quality statistics, no table, no coder, and the -B rule counts no quality bytes.
   int lpr = 4;
   bool nq = false;
+  // Interleaved pairs (params interleaved, -i): nm = 2, but ONE text per piece -- record 2k + m of it is mate m of row k.  The
+  // piece's newline counts and line index are mate 0's (tile[0], line_end[0]) and serve both mates; ntext = texts per piece.
+  bool il = false;
+  int ntext = 1;
+  u64 unit_lines() const { return (u64)lpr * (il ? 2 : 1); }  // text lines per row: a record, or a pair
   // Rows.  A batch takes its input in one piece (scalce_batch_ingest) or in several (scalce_batch_append): rows
   // [base, base + NP) are the piece being ingested / tokenized, N = base + NP is everything the batch holds.  Packed
   // bases, q', names and tokens are run-wide arrays indexed by row; the text of a piece is dead once it is ingested.
@@ -612,6 +617,7 @@ static int batch_create(scalce_ctx *c, const scalce_params *p, uint64_t max_read
                         scalce_batch **out) {
   if (!c || !p || !out) return SCALCE_ERR_ARG;
   if (!c->have_patterns) { set_err(c, "load a core table first"); return SCALCE_ERR_ARG; }
+  if (p->interleaved && !p->paired) { set_err(c, "interleaved input (-i) is paired: set paired as well"); return SCALCE_ERR_ARG; }
   if (p->read_len[0] <= 0 || p->read_len[0] > 2498 || (p->paired && (p->read_len[1] <= 0 || p->read_len[1] > 2498))) {
     set_err(c, "read_len must be set (1..2498: the reference reads lines into MAXLINE = 2500 bytes, const.h:87)");
     return SCALCE_ERR_ARG;
@@ -626,6 +632,8 @@ static int batch_create(scalce_ctx *c, const scalce_params *p, uint64_t max_read
   b->max_reads = max_reads;
   b->max_text = max_text;
   b->nm = p->paired ? 2 : 1;
+  b->il = p->interleaved != 0;
+  b->ntext = b->il ? 1 : b->nm;
   for (int m = 0; m < b->nm; m++) {
     b->L[m] = p->read_len[m];
     b->szr[m] = sz_read(b->L[m]);

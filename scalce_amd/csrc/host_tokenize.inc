@@ -518,13 +518,15 @@ extern "C" int scalce_batch_text_offset(scalce_batch *b, int mate, uint64_t row,
   if (!row) return SCALCE_OK;
   HIP_TRY(b->ctx, hipSetDevice(b->ctx->device));
   // from the per-tile newline counts of the piece (its text must still be where it was): no line index is built for this
-  const u64 nbytes = b->text_bytes[mate];
+  const int tm = b->il ? 0 : mate;  // (-i: one text, mate m of row r is its record 2r + m)
+  const u64 nbytes = b->text_bytes[tm];
   const u32 ntiles = cdiv(nbytes, IDX_TILE);
-  if (!ntiles || !b->piece_text[mate]) { set_err(b->ctx, "no piece ingested"); return SCALCE_ERR_ARG; }
+  if (!ntiles || !b->piece_text[tm]) { set_err(b->ctx, "no piece ingested"); return SCALCE_ERR_ARG; }
   // on the caller's stream, behind the ingest that produced the tile counts, and in a word of its own (slot 7 belongs to
   // scalce_batch_chunk_plan's carry)
   u64 *d_out = b->d_small64 + 10;
-  LAUNCH(line_offset_k, 1, 64, 0, s, b->piece_text[mate], nbytes, b->tile[mate].as<u64>(), ntiles, (u64)b->lpr * row, d_out);
+  const u64 line = b->il ? (u64)b->lpr * (2 * row + (u64)mate) : (u64)b->lpr * row;
+  LAUNCH(line_offset_k, 1, 64, 0, s, b->piece_text[tm], nbytes, b->tile[tm].as<u64>(), ntiles, line, d_out);
   u64 v = 0;
   { int rc = read_u64(b, d_out, &v, 1, s); if (rc) return rc; }
   *offset = v;

@@ -31,6 +31,13 @@ struct FqArgs {
   u32 mate_digit;           // paired: a trailing "/x" gets this character; 0: names as stored
   u8 *out;
   u64 *rec_off;             // optional: start of every record in the text, nrecords + 1 entries
+  // Interleaved text (-d -i): il = 1 for mate 1, 2 for mate 2 (0: a text of this mate alone).  Both mates' records go into
+  // ONE text, mate 1 then mate 2 of each pair: record K of a mate lies at its place in its own text plus the size of the other
+  // mate's first K records (mate 1) or first K + 1 (mate 2) -- the prefix over pairs of both record sizes, from the other
+  // mate's read length and name offsets.  rec_off then holds pair starts (mate 1) and the text's end.
+  u32 il;
+  u32 pair_L;
+  const u64 *pair_name_off; // the other mate's name_off (names mode)
 };
 
 // digits of 0 .. K-1 summed: K for the first digit, K - 10^(t-1) more for every t-digit number and beyond
@@ -46,6 +53,15 @@ __device__ __forceinline__ u32 fq_digits(u64 K) {
 }
 
 constexpr int FQ_RECORDS_PER_WAVE = 32;
+
+// where record K of a mate of read length L begins in that mate's own text: the name bytes of the records before it (name
+// offsets count a length byte per name) or the library names' digits, and the fixed part of every record
+template <bool QUAL>
+__device__ __forceinline__ u64 fq_record_at(u64 K, u32 L, const u64 *name_off, u32 lib_len) {
+  constexpr u32 FIXED = QUAL ? 6 : 3;
+  if (name_off) return (name_off[K] - K) + K * ((QUAL ? 2ull : 1ull) * L + FIXED);
+  return K * (lib_len + (QUAL ? 2ull : 1ull) * L + FIXED + 1) + fq_digits_below(K);
+}
 
 template <bool QUAL>
 __global__ __launch_bounds__(256) void fastq_records_k(FqArgs a) {
@@ -79,11 +95,11 @@ __global__ __launch_bounds__(256) void fastq_records_k(FqArgs a) {
       const u64 no = a.name_off[K];
       n = a.names[no];
       nm = a.names + no + 1;
-      at = (no - K) + K * ((QUAL ? 2ull : 1ull) * L + FIXED);
     } else {
       n = a.lib_len + 1 + fq_digits(K);
-      at = K * (a.lib_len + (QUAL ? 2ull : 1ull) * L + FIXED + 1) + fq_digits_below(K);
     }
+    at = fq_record_at<QUAL>(K, L, a.names ? a.name_off : nullptr, a.lib_len);
+    if (a.il) at += fq_record_at<QUAL>(a.il == 1 ? K : K + 1, a.pair_L, a.names ? a.pair_name_off : nullptr, a.lib_len);
     if (a.rec_off && lane == 0) a.rec_off[K] = at;
     const u8 *q = QUAL ? a.qual + K * (u64)L : nullptr;
     u8 *o = a.out + at;
@@ -123,7 +139,10 @@ __global__ __launch_bounds__(256) void fastq_records_k(FqArgs a) {
       else c = '\n';
       o[t] = c;
     }
-    if (a.rec_off && lane == 0 && K + 1 == a.nrecords) a.rec_off[K + 1] = at + len;
+    if (a.rec_off && lane == 0 && K + 1 == a.nrecords)
+      a.rec_off[K + 1] = a.il ? fq_record_at<QUAL>(K + 1, L, a.names ? a.name_off : nullptr, a.lib_len) +
+                                    fq_record_at<QUAL>(K + 1, a.pair_L, a.names ? a.pair_name_off : nullptr, a.lib_len)
+                              : at + len;
   }
 }
 

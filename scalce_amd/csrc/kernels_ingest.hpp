@@ -140,8 +140,10 @@ __device__ __forceinline__ u32 load_u32_unaligned(const u8 *t, u64 at, u64 n) {
 }
 
 // The record variants are template parameters of every ingest kernel: LPR = text lines per record (4: FASTQ; 2: FASTA, a name
-// line and one sequence line, compress.cpp:637,662) and QOUT = whether q' rows are written (false under -Q / -f: the quality
-// line of a FASTQ record is still checked for its length, nothing is made of it).
+// line and one sequence line, compress.cpp:637,662), QOUT = whether q' rows are written (false under -Q / -f: the quality
+// line of a FASTQ record is still checked for its length, nothing is made of it) and IL = interleaved pairs (-i: ONE text,
+// record 2r + m of it is mate m of pair r -- row r of mate m; UnpackArgs::mate says which mate a launch writes, nrec counts
+// pairs).  Under IL a unit of the text is a pair, RL = 2 LPR lines.
 template <int PART, int LPR, bool QOUT, typename WordAt, typename ByteAt>
 __device__ __forceinline__ void unpack_record_at(const UnpackArgs &a, u64 r, u64 ns, u64 p0, u64 p1, u64 p2, u64 p3, const u8 *lut,
                                                  WordAt word, ByteAt byte_at, u8 *qrow, bool qrow_aligned);
@@ -150,12 +152,14 @@ __device__ __forceinline__ void unpack_record_at(const UnpackArgs &a, u64 r, u64
 // PART: 3 = the whole record; 1 = bases + name only, 2 = qualities only (unpack_tiled_k gives a record to two threads of
 // different waves: the work of a thread is a long chain of dependent instructions, and with the 40 KB tile per 128
 // records only two waves per SIMD were resident to hide it).
-template <int PART, int LPR, bool QOUT, typename WordAt, typename ByteAt>
+template <int PART, int LPR, bool QOUT, bool IL, typename WordAt, typename ByteAt>
 __device__ __forceinline__ void unpack_record(const UnpackArgs &a, u64 r, const u8 *lut, WordAt word, ByteAt byte_at, u8 *qrow,
                                               bool qrow_aligned) {
-  const u64 *e = a.line_end + (u64)LPR * r;
-  unpack_record_at<PART, LPR, QOUT>(a, r, r ? e[-1] + 1 : 0, e[0], e[1], e[LPR - 2], e[LPR - 1], lut, word, byte_at, qrow, qrow_aligned);
+  const u64 t = IL ? 2 * r + (u64)a.mate : r;  // the record's place in the text
+  const u64 *e = a.line_end + (u64)LPR * t;
+  unpack_record_at<PART, LPR, QOUT>(a, r, t ? e[-1] + 1 : 0, e[0], e[1], e[LPR - 2], e[LPR - 1], lut, word, byte_at, qrow, qrow_aligned);
 }
+template <int LPR, bool IL> constexpr u32 text_unit_lines() { return IL ? 2 * LPR : LPR; }  // RL: a record, or a pair
 // ns = where the record's name line starts, p0 .. p3 = the newlines that end its four lines (text offsets; two-line records:
 // p2 = p3 = p1, nothing is read behind the sequence line)
 template <int PART, int LPR, bool QOUT, typename WordAt, typename ByteAt>
@@ -261,7 +265,7 @@ struct LongNameLen {
   const u8 *namelen;
   __device__ u64 operator()(u64 r) const { return namelen[r] > 15 ? (u64)namelen[r] : 0ull; }
 };
-template <int LPR>
+template <int LPR, bool IL>
 __global__ __launch_bounds__(256) void long_names_k(u64 nrec, const u8 *text, const u64 *line_end, const u8 *namelen, u64 *off,
                                                    u64 store_base, u8 *store) {
   const u64 r = (u64)blockIdx.x * blockDim.x + threadIdx.x;
@@ -270,7 +274,8 @@ __global__ __launch_bounds__(256) void long_names_k(u64 nrec, const u8 *text, co
   off[r] = at;
   const u32 n = namelen[r];
   if (n <= 15) return;
-  const u64 src = (r ? line_end[(u64)LPR * r - 1] + 1 : 0) + 1;  // behind the '@' (or '>')
+  constexpr u64 RL = text_unit_lines<LPR, IL>();  // (mate 1's names: the record that opens the unit)
+  const u64 src = (r ? line_end[RL * r - 1] + 1 : 0) + 1;  // behind the '@' (or '>')
   for (u32 i = 0; i < n; i++) store[at + i] = text[src + i];
 }
 
@@ -301,13 +306,14 @@ __global__ __launch_bounds__(64) void line_offset_k(const u8 *text, u64 nbytes, 
   if (threadIdx.x == 0) *out = nbytes;  // fewer lines than asked for
 }
 
-template <int LPR>
+template <int LPR, bool IL>
 __global__ void last_record_end_k(const u64 *line_end, u64 nrec, u64 *out) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) *out = nrec ? line_end[(u64)LPR * nrec - 1] + 1 : 0;
+  constexpr u64 RL = text_unit_lines<LPR, IL>();
+  if (threadIdx.x == 0 && blockIdx.x == 0) *out = nrec ? line_end[RL * nrec - 1] + 1 : 0;
 }
 
 // direct form: every thread reads its record straight from global memory (fallback for long reads / huge names)
-template <int LPR, bool QOUT>
+template <int LPR, bool QOUT, bool IL>
 __global__ __launch_bounds__(256) void unpack_k(UnpackArgs a) {
   __shared__ u8 lut[128];
   if (QOUT && threadIdx.x < 128) lut[threadIdx.x] = a.qlut[threadIdx.x];
@@ -315,7 +321,7 @@ __global__ __launch_bounds__(256) void unpack_k(UnpackArgs a) {
   const u64 r = (u64)blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= a.nrec) return;
   u8 *qrow = QOUT ? a.q + r * (u64)a.L : nullptr;
-  unpack_record<3, LPR, QOUT>(a, r, lut, [&](u64 at) { return load_word(a.text, at & ~3ull, a.nbytes); },
+  unpack_record<3, LPR, QOUT, IL>(a, r, lut, [&](u64 at) { return load_word(a.text, at & ~3ull, a.nbytes); },
                 [&](u64 at) { return a.text[at]; }, qrow, ((u64)qrow & 3) == 0);
 }
 
@@ -327,7 +333,8 @@ constexpr int UNP_RPB = 128;
 constexpr int UNP_Q_CAP = 20 * 1024;  // UNP_RPB * L must fit: L <= 160
 __host__ __device__ inline u32 unp_text_cap(int L) { return (u32)(((UNP_RPB * (2 * L + 20) + 64) + 15) & ~15); }
 __host__ __device__ inline u32 unp_q_cap(int L) { return (u32)((UNP_RPB * L + 15) & ~15); }
-template <int LPR, bool QOUT>
+// (IL: the tile spans the text of UNP_RPB pairs, both mates' records; when that does not fit, the records are read from global)
+template <int LPR, bool QOUT, bool IL>
 __global__ __launch_bounds__(2 * UNP_RPB) void unpack_tiled_k(UnpackArgs a) {
   extern __shared__ __attribute__((aligned(16))) u8 unp_lds[];
   const u32 UNP_TEXT_CAP = unp_text_cap(a.L);
@@ -338,8 +345,9 @@ __global__ __launch_bounds__(2 * UNP_RPB) void unpack_tiled_k(UnpackArgs a) {
   if (QOUT && tid < 128) lut[tid] = a.qlut[tid];
   const u64 r0 = (u64)blockIdx.x * UNP_RPB;
   const u64 r1 = r0 + UNP_RPB < a.nrec ? r0 + UNP_RPB : a.nrec;
-  const u64 span0 = r0 ? a.line_end[(u64)LPR * r0 - 1] + 1 : 0;
-  const u64 span1 = a.line_end[(u64)LPR * r1 - 1] + 1;
+  constexpr u64 RL = text_unit_lines<LPR, IL>();
+  const u64 span0 = r0 ? a.line_end[RL * r0 - 1] + 1 : 0;
+  const u64 span1 = a.line_end[RL * r1 - 1] + 1;
   const u64 a0 = span0 & ~15ull;
   const u64 tbytes = span1 - a0;
   const bool in_lds = tbytes <= (u64)UNP_TEXT_CAP;  // uniform for the workgroup
@@ -369,11 +377,11 @@ __global__ __launch_bounds__(2 * UNP_RPB) void unpack_tiled_k(UnpackArgs a) {
     auto w_glb = [&](u64 at) { return load_word(a.text, at & ~3ull, a.nbytes); };
     auto b_glb = [&](u64 at) { return a.text[at]; };
     if (in_lds) {
-      if (second) unpack_record<2, LPR, QOUT>(a, r, lut, w_lds, b_lds, qrow, al);
-      else unpack_record<1, LPR, QOUT>(a, r, lut, w_lds, b_lds, qrow, al);
+      if (second) unpack_record<2, LPR, QOUT, IL>(a, r, lut, w_lds, b_lds, qrow, al);
+      else unpack_record<1, LPR, QOUT, IL>(a, r, lut, w_lds, b_lds, qrow, al);
     } else {
-      if (second) unpack_record<2, LPR, QOUT>(a, r, lut, w_glb, b_glb, qrow, al);
-      else unpack_record<1, LPR, QOUT>(a, r, lut, w_glb, b_glb, qrow, al);
+      if (second) unpack_record<2, LPR, QOUT, IL>(a, r, lut, w_glb, b_glb, qrow, al);
+      else unpack_record<1, LPR, QOUT, IL>(a, r, lut, w_glb, b_glb, qrow, al);
     }
   }
   if (!QOUT) return;  // (no q' rows to write out)
@@ -437,16 +445,24 @@ __device__ __forceinline__ u32 lds_fetch_u32(const u8 *text, u32 at) {  // unali
   const u32 *p = reinterpret_cast<const u32 *>(text + (at & ~3u));
   return __builtin_amdgcn_alignbyte(p[1], p[0], at & 3u);
 }
-// LPR, QOUT: see unpack_record_at.  LDS: 17.4 KB of text, 4 KB of newlines, the record starts (2 KB for FASTQ; 2 KB for
+// LPR, QOUT, IL: see unpack_record_at.  LDS: 17.4 KB of text, 4 KB of newlines, the record starts (2 KB for FASTQ; 2 KB for
 // two-line records, which need no quality starts): about 24 KB either way.
-template <int LPR, bool QOUT>
-__global__ __launch_bounds__(ING_THREADS) void ingest_tiles2_k(Ingest2Args g) {
+// IL (-i): g is mate 1's, g2 mate 2's (unused otherwise).  The workgroup takes the PAIRS that start in its tile and end inside
+// tile + overlap -- mate m's name lines are those with line index = LPR m (mod 2 LPR) -- and unpacks both mates of each from
+// the one tile of text: mate 1's starts in the lower half of rec_sb / rec_sq, mate 2's in the upper (a pair has twice a
+// record's lines, so a tile holds at most half as many: the same arrays, the same LDS).
+template <int LPR, bool QOUT, bool IL>
+__global__ __launch_bounds__(ING_THREADS) void ingest_tiles2_k(Ingest2Args g, Ingest2Args g2) {
   const IngestArgs &a = g.i;
   constexpr u32 RECMAX = ing2_recmax<LPR>();
+  constexpr u32 RL = text_unit_lines<LPR, IL>();  // lines of a unit taken: a record, or a pair
+  constexpr u32 MSLOT = IL ? RECMAX / 2 : 0;      // where mate 2's starts begin
+  constexpr u32 NMATE = IL ? 2 : 1;
+  static_assert(!IL || (ING_NLMAX + RL - 1) / RL <= MSLOT, "a tile's pairs fit half the record arrays");
   __shared__ __attribute__((aligned(16))) u8 text[ING_TILE + ING_OVER + 32];
   __shared__ u16 nl[ING_NLMAX];
   __shared__ u16 rec_sb[RECMAX], rec_sq[QOUT ? RECMAX : 1];
-  __shared__ u8 lut[128];
+  __shared__ u8 lut[128 * NMATE];  // (each mate has its quality map)
   __shared__ u32 sm[ING_THREADS / 64];
   __shared__ u32 s_count[2];
   __shared__ u32 s_mm[2 * (ING_THREADS / 64)];
@@ -455,7 +471,7 @@ __global__ __launch_bounds__(ING_THREADS) void ingest_tiles2_k(Ingest2Args g) {
   const u64 t0 = (u64)ti * ING_TILE;                               // text offset of the tile
   const u64 avail = a.u.nbytes - t0;
   const u32 len = (u32)(avail < ING_TILE + ING_OVER ? avail : ING_TILE + ING_OVER);
-  if (QOUT && tid < 128) lut[tid] = a.u.qlut[tid];
+  if (QOUT && tid < 128 * (int)NMATE) lut[tid] = tid < 128 ? a.u.qlut[tid] : g2.i.u.qlut[tid - 128];
   if (tid == 0) s_count[1] = 0;
   for (u32 i = (u32)tid * 16; i < len + 8; i += ING_THREADS * 16) {
     uint4 v;
@@ -515,13 +531,12 @@ __global__ __launch_bounds__(ING_THREADS) void ingest_tiles2_k(Ingest2Args g) {
   const u64 G0 = a.tile_base[(u64)ti * (ING_TILE / IDX_TILE)];
   const bool starts_line = t0 == 0 || a.u.text[t0 - 1] == '\n';
   const u32 jmin = starts_line ? 0u : 1u;
-  const u32 j0 = jmin + (u32)((LPR - ((G0 + jmin) % LPR)) % LPR);  // first name line that starts here
-  const u64 rid0 = (G0 + j0) / LPR;
-  const u32 nloc = j0 < count ? (count - j0 + LPR - 1) / LPR : 0u;  // name lines that END in tile + overlap (<= RECMAX)
-  const int L = a.u.L;
-  // one thread per record: is it this tile's (it STARTS here and is whole), are its lines as long as they must be, its name
+  const u32 j0 = jmin + (u32)((RL - ((G0 + jmin) % RL)) % RL);  // first name line (of a pair's mate 1) that starts here
+  const u64 rid0 = (G0 + j0) / RL;
+  const u32 nloc = j0 < count ? (count - j0 + RL - 1) / RL : 0u;  // name lines that END in tile + overlap (<= RECMAX)
+  // one thread per record (pair): is it this tile's (it STARTS here and is whole), are its lines as long as they must be, its name
   for (u32 k = (u32)tid; k < nloc; k += ING_THREADS) {
-    const u32 j = j0 + LPR * k;
+    const u32 j = j0 + RL * k;
     const u64 rid = rid0 + k;
     bool take = rid < a.u.nrec;
     u32 ns = 0;
@@ -530,183 +545,200 @@ __global__ __launch_bounds__(ING_THREADS) void ingest_tiles2_k(Ingest2Args g) {
       if (j && j - 1 >= count) take = false;
       else if (ns >= ING_TILE) take = false;                        // starts in the next tile: that workgroup's record
     }
-    if (take && j + LPR - 1 >= count) {                             // all its lines must end inside tile + overlap
+    if (take && j + RL - 1 >= count) {                              // all its lines must end inside tile + overlap
       take = false;
       atomicExch(a.slow, 1u);
     }
     if (!take) continue;
     atomicAdd(&s_count[1], 1u);                                     // (the records taken are the first ones: a prefix of k)
-    const u32 p0 = nl[j], p1 = nl[j + 1], p2 = nl[j + LPR - 2], p3 = nl[j + LPR - 1];  // (two-line records: p2 = p3 = p1)
-    if (rid + 1 == a.u.nrec) *a.consumed = t0 + p3 + 1;
-    if (p1 - p0 - 1 != (u32)L || (LPR == 4 && p3 - p2 - 1 != (u32)L)) {
-      dev_fail(a.u.err, E_READLEN, rid, p1 - p0 - 1);
-      rec_sb[k] = 0xFFFFu;                                          // nothing of it is unpacked
-      if (QOUT) rec_sq[k] = 0xFFFFu;
-      if (a.u.mate == 0) {  // the run ends with an error; until the host sees it, later stages must find a well-formed row
-        a.u.namelen[rid] = 0;
-        if (a.u.namecell) { u32x4a z; z.x = z.y = z.z = z.w = 0; *reinterpret_cast<u32x4a *>(a.u.namecell + (u64)a.u.cellstride * rid) = z; }
-      }
-      continue;
-    }
-    rec_sb[k] = (u16)(p0 + 1);
-    if (QOUT) rec_sq[k] = (u16)(p2 + 1);
-    if (a.u.mate == 0) {
-      // output_name, names.cpp:55-57: characters after '@' up to the first space or the newline
-      u32 nlen = 0;
-      if (a.u.use_names) {
-        // the first space of the name line, four characters at a time (the newline at p0 ends the search)
-        u32 i = ns + 1;
-        for (; i < p0; i += 4) {
-          const u32 z = zero_bytes(lds_fetch_u32(text, i) ^ 0x20202020u);
-          if (z) { i += (u32)(__ffs((int)z) - 1) >> 3; break; }
-        }
-        if (i > p0) i = p0;
-        const u32 l = i - (ns + 1);
-        if (l > 255 || p0 <= ns) dev_fail(a.u.err, E_NAMELEN, rid);
-        nlen = l > 255 ? 0u : l;
-        if (a.u.namecell) {
-          // cell = [length][15 characters]: the 16 bytes from '@' on with the length in place of the '@', zero behind the name
-          u32 w[4];
+    if (rid + 1 == a.u.nrec) *a.consumed = t0 + nl[j + RL - 1] + 1;
 #pragma unroll
-          for (int x = 0; x < 4; x++) {
-            const int keepb = (int)nlen + 1 - 4 * x;                // bytes of this word that belong to the cell
-            const u32 v = lds_fetch_u32(text, ns + 4 * (u32)x);
-            w[x] = keepb >= 4 ? v : keepb <= 0 ? 0u : (v & ((1u << (8 * keepb)) - 1));
-          }
-          w[0] = (w[0] & 0xFFFFFF00u) | nlen;
-          u32x4a cv; cv.x = w[0]; cv.y = w[1]; cv.z = w[2]; cv.w = w[3];
-          *reinterpret_cast<u32x4a *>(a.u.namecell + (u64)a.u.cellstride * rid) = cv;  // (4-byte aligned inside a fused row)
+    for (u32 m = 0; m < NMATE; m++) {
+      const UnpackArgs &u = m ? g2.i.u : a.u;
+      const u32 jm = j + LPR * m, slot = MSLOT * m + k;
+      const u32 nsm = m ? (u32)nl[jm - 1] + 1 : ns;
+      const int L = u.L;
+      const u32 p0 = nl[jm], p1 = nl[jm + 1], p2 = nl[jm + LPR - 2], p3 = nl[jm + LPR - 1];  // (two-line records: p2 = p3 = p1)
+      if (p1 - p0 - 1 != (u32)L || (LPR == 4 && p3 - p2 - 1 != (u32)L)) {
+        dev_fail(u.err, E_READLEN, rid, p1 - p0 - 1);
+        rec_sb[slot] = 0xFFFFu;                                       // nothing of it is unpacked
+        if (QOUT) rec_sq[slot] = 0xFFFFu;
+        if (u.mate == 0) {  // the run ends with an error; until the host sees it, later stages must find a well-formed row
+          u.namelen[rid] = 0;
+          if (u.namecell) { u32x4a z; z.x = z.y = z.z = z.w = 0; *reinterpret_cast<u32x4a *>(u.namecell + (u64)u.cellstride * rid) = z; }
         }
-        if (nlen > 15 && a.u.max_namelen) atomicMax(a.u.max_namelen, nlen);
+        continue;
       }
-      a.u.namelen[rid] = (u8)nlen;
+      rec_sb[slot] = (u16)(p0 + 1);
+      if (QOUT) rec_sq[slot] = (u16)(p2 + 1);
+      if (u.mate == 0) {
+        const u32 ns = nsm;
+        // output_name, names.cpp:55-57: characters after '@' up to the first space or the newline
+        u32 nlen = 0;
+        if (u.use_names) {
+          // the first space of the name line, four characters at a time (the newline at p0 ends the search)
+          u32 i = ns + 1;
+          for (; i < p0; i += 4) {
+            const u32 z = zero_bytes(lds_fetch_u32(text, i) ^ 0x20202020u);
+            if (z) { i += (u32)(__ffs((int)z) - 1) >> 3; break; }
+          }
+          if (i > p0) i = p0;
+          const u32 l = i - (ns + 1);
+          if (l > 255 || p0 <= ns) dev_fail(u.err, E_NAMELEN, rid);
+          nlen = l > 255 ? 0u : l;
+          if (u.namecell) {
+            // cell = [length][15 characters]: the 16 bytes from '@' on with the length in place of the '@', zero behind the name
+            u32 w[4];
+#pragma unroll
+            for (int x = 0; x < 4; x++) {
+              const int keepb = (int)nlen + 1 - 4 * x;                // bytes of this word that belong to the cell
+              const u32 v = lds_fetch_u32(text, ns + 4 * (u32)x);
+              w[x] = keepb >= 4 ? v : keepb <= 0 ? 0u : (v & ((1u << (8 * keepb)) - 1));
+            }
+            w[0] = (w[0] & 0xFFFFFF00u) | nlen;
+            u32x4a cv; cv.x = w[0]; cv.y = w[1]; cv.z = w[2]; cv.w = w[3];
+            *reinterpret_cast<u32x4a *>(u.namecell + (u64)u.cellstride * rid) = cv;  // (4-byte aligned inside a fused row)
+          }
+          if (nlen > 15 && u.max_namelen) atomicMax(u.max_namelen, nlen);
+        }
+        u.namelen[rid] = (u8)nlen;
+      }
     }
   }
   __syncthreads();
   const u32 ntake = s_count[1];
-  // Units are dealt to the threads in order, 256 apart: (record, word) of a thread's next unit follow from the last one by
-  // additions (step_k, step_r = 256 / n, 256 % n from the host), and both outputs are back to back in memory -- unit u of
-  // the tile is word u behind the tile's first row.
-  // bases: one unit = one word of a packed row = 16 bases (zero behind the read).  The last unit of a read is packed like
-  // the others -- the bytes behind the line (its newline, the '+' line, the first qualities: all inside the record, which ends
-  // inside tile + overlap) go through pack4 with it -- and the codes behind the read are masked off afterwards (a path of
-  // its own for that unit ran in every wave beside the common one: a wave's 64 units hold eight or nine last ones).
-  const u32 wfull = (u32)L / 16, W = ((u32)L + 15) / 16, ntail = (u32)L - 16 * wfull;  // ntail: bases / symbols of a last unit
-  {
-    const u32 S = (u32)a.u.stride / 4, units = ntake * S;
-    u32 tailmask = 0;  // first base of a byte in its bits 7-6 (pack4): byte m keeps its top 2 * (ntail - 4 m) bits
-    for (u32 m = 0; m < 4; m++) {
-      const int rem = (int)ntail - 4 * (int)m;
-      if (rem > 0) tailmask |= (rem >= 4 ? 0xFFu : (0xFF00u >> (2 * rem)) & 0xFFu) << (8 * m);
-    }
-    u32 k = (u32)(((u64)(u32)tid * g.magic_s) >> 32), w = (u32)tid - k * S;
-    u32 *dst = reinterpret_cast<u32 *>(a.u.packed + rid0 * (u64)a.u.stride);
-    for (u32 u = (u32)tid; u < units; u += ING_THREADS) {
-      const u32 sb = rec_sb[k];
-      if (sb != 0xFFFFu) {
-        u32 acc = 0;
-        if (w < W) {  // sixteen bases: five aligned words of the tile, four bytes of the row
-          const u32 at = sb + 16 * w, sh = at & 3u;
-          const u32 *p = reinterpret_cast<const u32 *>(text + (at & ~3u));
-          const u32 d0 = p[0], d1 = p[1], d2 = p[2], d3 = p[3], d4 = p[4];
-          acc = pack4(__builtin_amdgcn_alignbyte(d1, d0, sh)) | (pack4(__builtin_amdgcn_alignbyte(d2, d1, sh)) << 8) |
-                (pack4(__builtin_amdgcn_alignbyte(d3, d2, sh)) << 16) | (pack4(__builtin_amdgcn_alignbyte(d4, d3, sh)) << 24);
-          if (w >= wfull) acc &= tailmask;
-        }
-        dst[u] = acc;
-        if (a.u.packed2 && w < W) reinterpret_cast<u32 *>(a.u.packed2 + (rid0 + k) * (u64)a.u.qstride)[w] = acc;
-      }
-      k += g.step_ks; w += g.step_rs;
-      if (w >= S) { w -= S; k++; }
-    }
-  }
-  if (!QOUT) return;  // (-Q / -f: no q' rows, no symbol range; the whole workgroup leaves here)
-  // qualities: one unit = sixteen symbols (the last unit of a read: what is left, computed like a whole one and cut when it
-  // is stored); q' (qualities.cpp:183): exactly 'N' forces the offset, i.e. symbol 0
-  // smallest / largest symbol: packed 16-bit min / max order their halves by the HIGH byte, so a word as it is gives the
-  // range of its odd bytes and the word shifted up by one byte that of its even bytes -- no masks
-  u32 lo_e = 0xFFFFFFFFu, lo_o = 0xFFFFFFFFu, hi_e = 0, hi_o = 0;
-  {
-    const u32 units = ntake * W;
-    const bool al = (L & 3) == 0;
-    const u32 aff = (u32)(a.u.q_affine >= 0 ? a.u.q_affine : 0) * 0x01010101u;
-    u32 k = (u32)(((u64)(u32)tid * g.magic_w) >> 32), w = (u32)tid - k * W;
-    const u32 QS = a.u.qstride;
-    u8 *qtile = a.u.q + rid0 * (u64)QS;
-    u32 qoff = k * QS + 16 * w;                                     // (a tile's q' rows: far below 2^32 bytes)
-    const u32 qstep = g.step_kw * QS + 16 * g.step_rw, qwrap = QS - 16 * W;
-    auto quality = [&](u32 vq) -> u32 {
-      if (a.u.q_affine >= 0)  // four subtractions in one word (see unpack_record_at)
-        return (((vq & 0x7F7F7F7Fu) | 0x80808080u) - aff) ^ 0x80808080u;
-      return (u32)lut[vq & 127] | ((u32)lut[(vq >> 8) & 127] << 8) | ((u32)lut[(vq >> 16) & 127] << 16) | ((u32)lut[(vq >> 24) & 127] << 24);
-    };
-    auto not_n = [&](u32 vb) -> u32 {  // 0xFF in every byte that is not 'N'
-      const u32 zN = zero_bytes(vb ^ 0x4E4E4E4Eu);
-      return ~(zN | (zN - (zN >> 7)));
-    };
-    auto range = [&](u32 ql, u32 qh) {  // ql: bytes that are not symbols hold 0xFF; qh: they hold 0
-      lo_o = pk_min_u16(lo_o, ql); lo_e = pk_min_u16(lo_e, ql << 8);
-      hi_o = pk_max_u16(hi_o, qh); hi_e = pk_max_u16(hi_e, qh << 8);
-    };
-    for (u32 u = (u32)tid; u < units; u += ING_THREADS) {
-      const u32 sb = rec_sb[k];
-      if (sb != 0xFFFFu) {
-        const u32 sq = rec_sq[k];
-        const u32 ab = sb + 16 * w, aq = sq + 16 * w, shb = ab & 3u, shq = aq & 3u;
-        const u32 *pb = reinterpret_cast<const u32 *>(text + (ab & ~3u)), *pq = reinterpret_cast<const u32 *>(text + (aq & ~3u));
-        const u32 b0 = pb[0], b1 = pb[1], b2 = pb[2], b3 = pb[3], b4 = pb[4];
-        const u32 q0 = pq[0], q1 = pq[1], q2 = pq[2], q3 = pq[3], q4 = pq[4];
-        const u32 r0 = quality(__builtin_amdgcn_alignbyte(q1, q0, shq)) & not_n(__builtin_amdgcn_alignbyte(b1, b0, shb));
-        const u32 r1 = quality(__builtin_amdgcn_alignbyte(q2, q1, shq)) & not_n(__builtin_amdgcn_alignbyte(b2, b1, shb));
-        const u32 r2 = quality(__builtin_amdgcn_alignbyte(q3, q2, shq)) & not_n(__builtin_amdgcn_alignbyte(b3, b2, shb));
-        const u32 r3 = quality(__builtin_amdgcn_alignbyte(q4, q3, shq)) & not_n(__builtin_amdgcn_alignbyte(b4, b3, shb));
-        u8 *qdst = qtile + qoff;
-        if (w < wfull) {
-          if (al) {
-            u32x4a v;
-            v.x = r0; v.y = r1; v.z = r2; v.w = r3;
-            *reinterpret_cast<u32x4a *>(qdst) = v;
-          } else {
-            const u32 rr[4] = {r0, r1, r2, r3};
-            for (int x = 0; x < 16; x++) qdst[x] = (u8)(rr[x >> 2] >> (8 * (x & 3)));
-          }
-          range(r0, r0); range(r1, r1); range(r2, r2); range(r3, r3);
-        } else {  // the last unit of a read: ntail symbols (the same for every read: the trip count is the wave's)
-          const u32 rr[4] = {r0, r1, r2, r3};
 #pragma unroll
-          for (int x = 0; x < 4; x++) {
-            const int rem = (int)ntail - 4 * x;
-            if (rem > 0) {
-              const u32 keep = rem < 4 ? (1u << (8 * rem)) - 1 : 0xFFFFFFFFu, qq = rr[x] & keep;
-              if (al) *reinterpret_cast<u32 *>(qdst + 4 * x) = qq;
-              else for (int y = 0; y < (rem < 4 ? rem : 4); y++) qdst[4 * x + y] = (u8)(qq >> (8 * y));
-              range(qq | ~keep, qq);
+  for (u32 m = 0; m < NMATE; m++) {
+    const Ingest2Args &gm = m ? g2 : g;
+    const UnpackArgs &um = gm.i.u;
+    const u16 *sbm = rec_sb + MSLOT * m, *sqm = rec_sq + (QOUT ? MSLOT * m : 0u);
+    const u8 *lutm = lut + 128 * m;
+    const int L = um.L;
+    // Units are dealt to the threads in order, 256 apart: (record, word) of a thread's next unit follow from the last one by
+    // additions (step_k, step_r = 256 / n, 256 % n from the host), and both outputs are back to back in memory -- unit u of
+    // the tile is word u behind the tile's first row.
+    // bases: one unit = one word of a packed row = 16 bases (zero behind the read).  The last unit of a read is packed like
+    // the others -- the bytes behind the line (its newline, the '+' line, the first qualities: all inside the record, which ends
+    // inside tile + overlap) go through pack4 with it -- and the codes behind the read are masked off afterwards (a path of
+    // its own for that unit ran in every wave beside the common one: a wave's 64 units hold eight or nine last ones).
+    const u32 wfull = (u32)L / 16, W = ((u32)L + 15) / 16, ntail = (u32)L - 16 * wfull;  // ntail: bases / symbols of a last unit
+    {
+      const u32 S = (u32)um.stride / 4, units = ntake * S;
+      u32 tailmask = 0;  // first base of a byte in its bits 7-6 (pack4): byte m keeps its top 2 * (ntail - 4 m) bits
+      for (u32 m = 0; m < 4; m++) {
+        const int rem = (int)ntail - 4 * (int)m;
+        if (rem > 0) tailmask |= (rem >= 4 ? 0xFFu : (0xFF00u >> (2 * rem)) & 0xFFu) << (8 * m);
+      }
+      u32 k = (u32)(((u64)(u32)tid * gm.magic_s) >> 32), w = (u32)tid - k * S;
+      u32 *dst = reinterpret_cast<u32 *>(um.packed + rid0 * (u64)um.stride);
+      for (u32 u = (u32)tid; u < units; u += ING_THREADS) {
+        const u32 sb = sbm[k];
+        if (sb != 0xFFFFu) {
+          u32 acc = 0;
+          if (w < W) {  // sixteen bases: five aligned words of the tile, four bytes of the row
+            const u32 at = sb + 16 * w, sh = at & 3u;
+            const u32 *p = reinterpret_cast<const u32 *>(text + (at & ~3u));
+            const u32 d0 = p[0], d1 = p[1], d2 = p[2], d3 = p[3], d4 = p[4];
+            acc = pack4(__builtin_amdgcn_alignbyte(d1, d0, sh)) | (pack4(__builtin_amdgcn_alignbyte(d2, d1, sh)) << 8) |
+                  (pack4(__builtin_amdgcn_alignbyte(d3, d2, sh)) << 16) | (pack4(__builtin_amdgcn_alignbyte(d4, d3, sh)) << 24);
+            if (w >= wfull) acc &= tailmask;
+          }
+          dst[u] = acc;
+          if (um.packed2 && w < W) reinterpret_cast<u32 *>(um.packed2 + (rid0 + k) * (u64)um.qstride)[w] = acc;
+        }
+        k += gm.step_ks; w += gm.step_rs;
+        if (w >= S) { w -= S; k++; }
+      }
+    }
+    if (!QOUT) continue;  // (-Q / -f: no q' rows, no symbol range; the whole workgroup goes on to the next mate, or leaves)
+    // qualities: one unit = sixteen symbols (the last unit of a read: what is left, computed like a whole one and cut when it
+    // is stored); q' (qualities.cpp:183): exactly 'N' forces the offset, i.e. symbol 0
+    // smallest / largest symbol: packed 16-bit min / max order their halves by the HIGH byte, so a word as it is gives the
+    // range of its odd bytes and the word shifted up by one byte that of its even bytes -- no masks
+    u32 lo_e = 0xFFFFFFFFu, lo_o = 0xFFFFFFFFu, hi_e = 0, hi_o = 0;
+    {
+      const u32 units = ntake * W;
+      const bool al = (L & 3) == 0;
+      const u32 aff = (u32)(um.q_affine >= 0 ? um.q_affine : 0) * 0x01010101u;
+      u32 k = (u32)(((u64)(u32)tid * gm.magic_w) >> 32), w = (u32)tid - k * W;
+      const u32 QS = um.qstride;
+      u8 *qtile = um.q + rid0 * (u64)QS;
+      u32 qoff = k * QS + 16 * w;                                     // (a tile's q' rows: far below 2^32 bytes)
+      const u32 qstep = gm.step_kw * QS + 16 * gm.step_rw, qwrap = QS - 16 * W;
+      auto quality = [&](u32 vq) -> u32 {
+        if (um.q_affine >= 0)  // four subtractions in one word (see unpack_record_at)
+          return (((vq & 0x7F7F7F7Fu) | 0x80808080u) - aff) ^ 0x80808080u;
+        return (u32)lutm[vq & 127] | ((u32)lutm[(vq >> 8) & 127] << 8) | ((u32)lutm[(vq >> 16) & 127] << 16) | ((u32)lutm[(vq >> 24) & 127] << 24);
+      };
+      auto not_n = [&](u32 vb) -> u32 {  // 0xFF in every byte that is not 'N'
+        const u32 zN = zero_bytes(vb ^ 0x4E4E4E4Eu);
+        return ~(zN | (zN - (zN >> 7)));
+      };
+      auto range = [&](u32 ql, u32 qh) {  // ql: bytes that are not symbols hold 0xFF; qh: they hold 0
+        lo_o = pk_min_u16(lo_o, ql); lo_e = pk_min_u16(lo_e, ql << 8);
+        hi_o = pk_max_u16(hi_o, qh); hi_e = pk_max_u16(hi_e, qh << 8);
+      };
+      for (u32 u = (u32)tid; u < units; u += ING_THREADS) {
+        const u32 sb = sbm[k];
+        if (sb != 0xFFFFu) {
+          const u32 sq = sqm[k];
+          const u32 ab = sb + 16 * w, aq = sq + 16 * w, shb = ab & 3u, shq = aq & 3u;
+          const u32 *pb = reinterpret_cast<const u32 *>(text + (ab & ~3u)), *pq = reinterpret_cast<const u32 *>(text + (aq & ~3u));
+          const u32 b0 = pb[0], b1 = pb[1], b2 = pb[2], b3 = pb[3], b4 = pb[4];
+          const u32 q0 = pq[0], q1 = pq[1], q2 = pq[2], q3 = pq[3], q4 = pq[4];
+          const u32 r0 = quality(__builtin_amdgcn_alignbyte(q1, q0, shq)) & not_n(__builtin_amdgcn_alignbyte(b1, b0, shb));
+          const u32 r1 = quality(__builtin_amdgcn_alignbyte(q2, q1, shq)) & not_n(__builtin_amdgcn_alignbyte(b2, b1, shb));
+          const u32 r2 = quality(__builtin_amdgcn_alignbyte(q3, q2, shq)) & not_n(__builtin_amdgcn_alignbyte(b3, b2, shb));
+          const u32 r3 = quality(__builtin_amdgcn_alignbyte(q4, q3, shq)) & not_n(__builtin_amdgcn_alignbyte(b4, b3, shb));
+          u8 *qdst = qtile + qoff;
+          if (w < wfull) {
+            if (al) {
+              u32x4a v;
+              v.x = r0; v.y = r1; v.z = r2; v.w = r3;
+              *reinterpret_cast<u32x4a *>(qdst) = v;
+            } else {
+              const u32 rr[4] = {r0, r1, r2, r3};
+              for (int x = 0; x < 16; x++) qdst[x] = (u8)(rr[x >> 2] >> (8 * (x & 3)));
+            }
+            range(r0, r0); range(r1, r1); range(r2, r2); range(r3, r3);
+          } else {  // the last unit of a read: ntail symbols (the same for every read: the trip count is the wave's)
+            const u32 rr[4] = {r0, r1, r2, r3};
+#pragma unroll
+            for (int x = 0; x < 4; x++) {
+              const int rem = (int)ntail - 4 * x;
+              if (rem > 0) {
+                const u32 keep = rem < 4 ? (1u << (8 * rem)) - 1 : 0xFFFFFFFFu, qq = rr[x] & keep;
+                if (al) *reinterpret_cast<u32 *>(qdst + 4 * x) = qq;
+                else for (int y = 0; y < (rem < 4 ? rem : 4); y++) qdst[4 * x + y] = (u8)(qq >> (8 * y));
+                range(qq | ~keep, qq);
+              }
             }
           }
         }
+        k += gm.step_kw; w += gm.step_rw; qoff += qstep;
+        if (w >= W) { w -= W; k++; qoff += qwrap; }
       }
-      k += g.step_kw; w += g.step_rw; qoff += qstep;
-      if (w >= W) { w -= W; k++; qoff += qwrap; }
     }
-  }
-  u32 lo = min(min((lo_o >> 8) & 0xFFu, lo_o >> 24), min((lo_e >> 8) & 0xFFu, lo_e >> 24));
-  u32 hi = max(max((hi_o >> 8) & 0xFFu, hi_o >> 24), max((hi_e >> 8) & 0xFFu, hi_e >> 24));
-  for (int o = 32; o; o >>= 1) {
-    lo = min(lo, (u32)__shfl_xor((int)lo, o));
-    hi = max(hi, (u32)__shfl_xor((int)hi, o));
-  }
-  if (lane_id() == 0) { s_mm[2 * wave_id()] = lo; s_mm[2 * wave_id() + 1] = hi; }
-  __syncthreads();  // (also: the q' rows of the tile are written)
-  for (int w = 0; w < ING_THREADS / 64; w++) { lo = min(lo, s_mm[2 * w]); hi = max(hi, s_mm[2 * w + 1]); }
-  if (tid == 0 && g.tile_minmax) g.tile_minmax[ti] = (u16)(lo | (hi << 8));
-  if (hi >= 80 && !a.u.no_ac) {  // a symbol the coder's tables have no row for (arithmetic.h:47): which record was it?
-    for (u32 k = (u32)tid; k < ntake; k += ING_THREADS) {
-      if (rec_sb[k] == 0xFFFFu) continue;
-      const u8 *qsrc = a.u.q + (rid0 + k) * (u64)a.u.qstride;
-      bool bad = false;
-      for (int x = 0; x < L; x++) bad |= qsrc[x] >= 80;
-      if (bad) { dev_fail(a.u.err, E_SYMBOL, rid0 + k); break; }
+    u32 lo = min(min((lo_o >> 8) & 0xFFu, lo_o >> 24), min((lo_e >> 8) & 0xFFu, lo_e >> 24));
+    u32 hi = max(max((hi_o >> 8) & 0xFFu, hi_o >> 24), max((hi_e >> 8) & 0xFFu, hi_e >> 24));
+    for (int o = 32; o; o >>= 1) {
+      lo = min(lo, (u32)__shfl_xor((int)lo, o));
+      hi = max(hi, (u32)__shfl_xor((int)hi, o));
     }
+    if (lane_id() == 0) { s_mm[2 * wave_id()] = lo; s_mm[2 * wave_id() + 1] = hi; }
+    __syncthreads();  // (also: the q' rows of the tile are written)
+    for (int w = 0; w < ING_THREADS / 64; w++) { lo = min(lo, s_mm[2 * w]); hi = max(hi, s_mm[2 * w + 1]); }
+    if (tid == 0 && gm.tile_minmax) gm.tile_minmax[ti] = (u16)(lo | (hi << 8));
+    if (hi >= 80 && !um.no_ac) {  // a symbol the coder's tables have no row for (arithmetic.h:47): which record was it?
+      for (u32 k = (u32)tid; k < ntake; k += ING_THREADS) {
+        if (sbm[k] == 0xFFFFu) continue;
+        const u8 *qsrc = um.q + (rid0 + k) * (u64)um.qstride;
+        bool bad = false;
+        for (int x = 0; x < L; x++) bad |= qsrc[x] >= 80;
+        if (bad) { dev_fail(um.err, E_SYMBOL, rid0 + k); break; }
+      }
+    }
+    if (IL) __syncthreads();  // (s_mm is the next mate's)
   }
 }
 // smallest / largest q' symbol of the piece from the tiles' (what sym_range_k leaves in minmax; preset to 255.., 0)

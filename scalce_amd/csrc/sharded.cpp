@@ -220,6 +220,10 @@ extern "C" int scalce_sharded_compress(scalce_comm *comm, scalce_ctx *ctx, scalc
       scalce_set_last_error(ctx, "records without qualities (-f / -Q) are compressed on one GPU: sharded runs do not take them");
       return SCALCE_ERR_ARG;
     }
+    if (bp.interleaved) {
+      scalce_set_last_error(ctx, "interleaved input (-i) is compressed on one GPU: sharded runs do not take it");
+      return SCALCE_ERR_ARG;
+    }
   }
   hipStream_t s = (hipStream_t)stream;
   const int W = scalce_comm_world(comm), rank = scalce_comm_rank(comm);

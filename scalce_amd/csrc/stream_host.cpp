@@ -124,8 +124,10 @@ struct Mate {
 extern "C" int scalce_stream_compress(scalce_ctx *ctx, const scalce_params *p, scalce_read_fn rd1, void *user1, scalce_read_fn rd2,
                                       void *user2, uint64_t piece_bytes, uint64_t reads_hint, int flags, scalce_batch **out,
                                       scalce_stream_stats *st, char *errbuf, size_t errcap) {
-  if (!ctx || !p || !rd1 || !out || (p->paired && !rd2)) return SCALCE_ERR_ARG;
-  const int nm = p->paired ? 2 : 1;
+  if (!ctx || !p || !rd1 || !out || (p->paired && !p->interleaved && !rd2) || (p->interleaved && rd2)) return SCALCE_ERR_ARG;
+  // streams read: one per mate, or ONE under -i (both mates in one text; scalce_batch_append takes whole pairs of it, so a
+  // piece's tail that goes on into the next piece always begins at a pair)
+  const int nm = p->paired && !p->interleaved ? 2 : 1;
   const uint64_t piece = ((piece_bytes ? piece_bytes : (1ull << 30)) + 4095) & ~4095ull;
   const int NPIN = 3;
   const uint64_t cap = 2 * piece;  // of a piece: the tail of the previous one plus one chunk

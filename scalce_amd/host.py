@@ -34,7 +34,7 @@ class QMap(C.Structure):
 class Params(C.Structure):
     _fields_ = [("read_len", C.c_int32 * 2), ("paired", C.c_int32), ("use_names", C.c_int32), ("no_ac", C.c_int32),
                 ("qmap", QMap * 2), ("bucket_set_size", C.c_uint64), ("qprev", (C.c_uint32 * 2) * 2),
-                ("fasta", C.c_int32), ("no_qualities", C.c_int32)]
+                ("fasta", C.c_int32), ("no_qualities", C.c_int32), ("interleaved", C.c_int32)]
 
 
 class ShardResult(C.Structure):
@@ -419,7 +419,7 @@ class Batch:
     """One FASTQ shard in HBM (scalce_batch)."""
 
     def __init__(self, ctx, read_len, max_reads, max_text, paired=False, use_names=True, no_ac=False, qmap=None,
-                 bucket_set_size=0, read_len2=0, qprev=None, workspace=None, fasta=False, no_qualities=False):
+                 bucket_set_size=0, read_len2=0, qprev=None, workspace=None, fasta=False, no_qualities=False, interleaved=False):
         self.ctx = ctx
         self.L = ctx.L
         p = Params()
@@ -429,6 +429,7 @@ class Batch:
         p.paired, p.use_names, p.no_ac = int(paired), int(use_names), int(no_ac)
         p.bucket_set_size = int(bucket_set_size)
         p.fasta, p.no_qualities = int(fasta), int(no_qualities)  # two-line records (-f) / qualities dropped (-Q)
+        p.interleaved = int(interleaved)  # -i: one text, mate 1 and mate 2 of a pair one after the other (needs paired)
         if qmap is not None:  # [(offset, values)] per mate
             for m, (off, vals) in enumerate(qmap):
                 p.qmap[m].offset = int(off)
