@@ -52,13 +52,12 @@ int scalce_patterns_buckets(const scalce_ctx *ctx); /* distinct cores = buckets,
  *   SCALCE_WALK_KMER     k-mer tables of the states of depth <= 8 (tokenize_kmer_pipe_k), no core under 8 bases
  *   SCALCE_WALK_KMER_T7  the same, some core has fewer than 8 bases
  *   SCALCE_WALK_ANCHOR   anchors of K = min(shortest core, 12) bases (tokenize_anchor_k); *anchor_k = K
- *   SCALCE_WALK_STATES   the automaton alone (tokenize_k)
- * SCALCE_WALK_NONE without a table.  *anchor_k (may be null) is 0 unless the walk is SCALCE_WALK_ANCHOR. */
+ * SCALCE_WALK_NONE without a table.  *anchor_k (may be null) is 0 unless the walk is SCALCE_WALK_ANCHOR.
+ * (4 was the walk of the automaton alone, state by state: no table the loaders accept selected it.) */
 #define SCALCE_WALK_NONE 0
 #define SCALCE_WALK_KMER 1
 #define SCALCE_WALK_KMER_T7 2
 #define SCALCE_WALK_ANCHOR 3
-#define SCALCE_WALK_STATES 4
 int scalce_patterns_walk(const scalce_ctx *ctx, int *anchor_k);
 /* core string / length by file-order index (decompress.cpp:269,341 use patterns[core]) */
 int scalce_pattern_length(const scalce_ctx *ctx, int pattern);
@@ -68,6 +67,10 @@ const char *scalce_pattern_string(const scalce_ctx *ctx, int pattern);
  * index of the core whose bucket is emitted k-th (aho_output order, reads.cpp:466-499), root (0x3FFFFFFF) last. */
 int scalce_patterns_describe_host(const void *blob, size_t nbytes, int is_text, int32_t *bucket_pattern_out,
                                   size_t cap, int32_t *n_states, int32_t *n_buckets);
+
+/* scalce_patterns_walk without a device: the walk the table would select once loaded, and its anchor K.  SCALCE_WALK_NONE
+ * for a table the loaders refuse. */
+int scalce_patterns_walk_host(const void *blob, size_t nbytes, int is_text, int *anchor_k);
 
 /* ---- quality model: quality_mapping_init (qualities.cpp:58-175), host only --------------- */
 typedef struct {

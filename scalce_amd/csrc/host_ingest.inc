@@ -236,8 +236,9 @@ extern "C" int scalce_batch_ingest(scalce_batch *b, int mate, const uint8_t *d_t
 // consumed[m] says how many bytes of each piece that was, the caller hands the rest in again in front of the next
 // piece.  Ingest, quality counters and the tie-break of the new rows (against all rows before them) run here; order,
 // emit and entropy run once, over everything, when the caller has no more input.
-static int first_walk(scalce_batch *b, u64 row0, u64 n, u64 tok_row0, hipStream_t s);
 static int entropy_rerun_from_text(scalce_batch *b, hipStream_t s);
+enum WalkPass { WALK_FIRST, WALK_CANDIDATES };
+static void launch_walk(scalce_batch *b, WalkPass pass, u64 row0, u64 n, u64 tok_row0, hipStream_t s);  // (host_tokenize.inc)
 // the ingest half of scalce_batch_append: as many complete records as both mates' pieces hold -> rows [N, N + nrec)
 static int ingest_piece(scalce_batch *b, const uint8_t *const text[2], const u64 nbytes[2], bool final_piece, uint64_t consumed[2], hipStream_t s) {
   scalce_ctx *c = b->ctx;
@@ -365,9 +366,8 @@ extern "C" int scalce_batch_rewindow(scalce_batch *b, uint64_t keep_first, uint6
   }
   // the first walk of the rows that came in (the kept rows keep theirs)
   if (walked && b->tok_bucket.cap >= sizeof(u32) * (b->N + 1) && b->tok_pos.cap >= sizeof(u32) * (b->N + 1)) {
-    int rc = first_walk(b, 0, nfront, 0, s);
-    if (!rc) rc = first_walk(b, nkept_end, b->N - nkept_end, 0, s);
-    if (rc) return rc;
+    launch_walk(b, WALK_FIRST, 0, nfront, 0, s);
+    launch_walk(b, WALK_FIRST, nkept_end, b->N - nkept_end, 0, s);
     b->walk_rows = b->N;
     w->walk_owner = b;
   } else {
@@ -460,14 +460,4 @@ extern "C" int scalce_batch_quality(scalce_batch *b, void *stream) {
     }
   }
   return SCALCE_OK;
-}
-
-// the tokenizer walks of a core table too large for the k-mer tables in LDS: occurrences from their starts (tokenize_anchor_k)
-static void anchor_args(const scalce_ctx *c, const scalce_batch *b, const u8 *packed, u64 nrec, AnchorArgs &a) {
-  memset(&a, 0, sizeof a);
-  a.next = reinterpret_cast<const u32 *>(c->d_next); a.outinfo = c->d_outinfo;
-  a.bits = c->d_anchor_bits; a.rank = c->d_anchor_rank; a.child = c->d_child_bits; a.K = c->anchor_K; a.idK = c->anchor_idK;
-  a.single = c->d_anchor_single;
-  a.packed = packed; a.nrec = nrec; a.L = b->L[0]; a.stride = b->stride[0]; a.root_bucket = (u32)c->A.n_buckets;
-  a.tok_bucket = b->tok_bucket.as<u32>(); a.tok_pos = b->tok_pos.as<u32>();
 }

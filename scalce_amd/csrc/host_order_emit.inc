@@ -256,7 +256,7 @@ extern "C" int scalce_batch_emit(scalce_batch *b, void *stream) {
     DBuf *dead[] = {&b->packed[0], &b->packed[1], &b->namecell, &b->names_in, &b->name_in_off, &b->name_off, &b->outlen, &b->cell_sorted,
                     &b->line_end[0], &b->line_end[1], &b->tile[0], &b->tile[1], &b->tok_bucket, &b->tok_pos, &b->tie_index,
                     &b->tie_read, &b->tie_off, &b->tie_ncand, &b->cand_bucket, &b->cand_pos, &b->choice, &b->ev_off,
-                    &b->ev_bucket, &b->ev_init, &b->ev_sorted, &b->ev_tmp, &b->ev_place, &b->chosen, &b->G, &b->cand_place,
+                    &b->ev_sorted, &b->ev_tmp, &b->ev_place, &b->chosen, &b->G, &b->cand_place,
                     &b->bucket, &b->endv, &b->tokens, &b->chunk, &b->perm_a, &b->perm_b, &b->key_a, &b->key_b, &b->hist, &b->S,
                     &b->run_head, &b->run_hcount, &b->run_rank, &b->runid, &b->run_items_a, &b->run_items_b, &b->run_pos};
     for (DBuf *d : dead)

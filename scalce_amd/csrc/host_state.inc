@@ -8,12 +8,12 @@ struct scalce_ctx {
   u32 *d_outinfo = nullptr;
   int32_t *d_bucket_pattern = nullptr;
   u32 *d_bucket_level = nullptr;
-  u32 *d_kmer = nullptr;      // k-mer tables of tokenize_kmer_k, or null when the core table does not qualify
-  bool kmer_t7_out = false;   // some state of depth <= 7 has an output
+  // what the table's walk reads (WalkTables, automaton.hpp): chosen and built when the table is loaded
+  int walk = SCALCE_WALK_NONE;
+  u32 *d_kmer = nullptr;      // the k-mer block of the k-mer walks (null under the anchor walk, which does not read it)
   u32 id8_first = 0;
-  int tok_lds_states = 0;
   u32 *d_simd_load = nullptr;  // per (XCC, SE, SH, CU, SIMD): coder waves resident there (ac_encode_k's role choice)
-  // anchor tables of tokenize_anchor_k (core tables too large for the k-mer tables in LDS), or null
+  // anchor tables of tokenize_anchor_k, or null
   u64 *d_anchor_bits = nullptr;
   u32 *d_anchor_rank = nullptr, *d_child_bits = nullptr;
   uint4 *d_anchor_single = nullptr;  // per depth-K node: the ONE core below it (length, bucket, packed suffix), or 0 = walk
@@ -86,161 +86,38 @@ extern "C" void scalce_ctx_destroy(scalce_ctx *c) {
 }
 extern "C" const char *scalce_last_error(const scalce_ctx *c) { return c ? c->err.c_str() : "null context"; }
 
+template <typename T>
+static int upload(scalce_ctx *c, T **d, const void *src, size_t bytes) {
+  HIP_TRY(c, hipMalloc(d, bytes));
+  HIP_TRY(c, hipMemcpy(*d, src, bytes, hipMemcpyHostToDevice));
+  return SCALCE_OK;
+}
+#define UPLOAD(c, dptr, vec) do { int rc_ = upload(c, &(dptr), (vec).data(), sizeof((vec)[0]) * (vec).size()); if (rc_) return rc_; } while (0)
+// the loaded table on the device: the DFA, the bucket tables and what its walk reads (build_walk_tables)
 static int upload_tables(scalce_ctx *c) {
   free_tables(c);
-  HIP_TRY(c, hipSetDevice(c->device));
+  c->have_patterns = false;
+  c->walk = SCALCE_WALK_NONE;
   const Automaton &A = c->A;
-  HIP_TRY(c, hipMalloc(&c->d_next, sizeof(uint4) * (size_t)A.n_states));
-  HIP_TRY(c, hipMalloc(&c->d_outinfo, sizeof(u32) * (size_t)A.n_states));
-  HIP_TRY(c, hipMalloc(&c->d_bucket_pattern, sizeof(int32_t) * A.bucket_pattern.size()));
-  HIP_TRY(c, hipMalloc(&c->d_bucket_level, sizeof(u32) * A.bucket_level.size()));
-  {  // transitions carry, in bit 31, whether the state they lead to ends a core (itself or through a suffix): the
-     // tokenizer then looks the output up only where there is one (~1 % of the positions of a read)
-    std::vector<u32> nx(A.next.begin(), A.next.end());
-    for (auto &t : nx)
-      if (A.outinfo[t] != kNoOutD) t |= 0x80000000u;
-    HIP_TRY(c, hipMemcpy(c->d_next, nx.data(), sizeof(u32) * nx.size(), hipMemcpyHostToDevice));
+  WalkTables T;
+  if (!build_walk_tables(A, T, c->err)) return SCALCE_ERR_FORMAT;
+  HIP_TRY(c, hipSetDevice(c->device));
+  UPLOAD(c, c->d_next, T.next);
+  UPLOAD(c, c->d_outinfo, A.outinfo);
+  UPLOAD(c, c->d_bucket_pattern, A.bucket_pattern);
+  UPLOAD(c, c->d_bucket_level, A.bucket_level);
+  c->id8_first = T.id8_first;
+  if (T.walk == SCALCE_WALK_ANCHOR) {
+    UPLOAD(c, c->d_anchor_single, T.anchor_single);
+    UPLOAD(c, c->d_anchor_bits, T.anchor_bits);
+    UPLOAD(c, c->d_anchor_rank, T.anchor_rank);
+    UPLOAD(c, c->d_child_bits, T.child_bits);
+    c->anchor_K = T.K;
+    c->anchor_idK = T.idK;
+  } else {
+    UPLOAD(c, c->d_kmer, T.kmer);
   }
-  HIP_TRY(c, hipMemcpy(c->d_outinfo, A.outinfo.data(), sizeof(u32) * A.outinfo.size(), hipMemcpyHostToDevice));
-  HIP_TRY(c, hipMemcpy(c->d_bucket_pattern, A.bucket_pattern.data(), sizeof(int32_t) * A.bucket_pattern.size(),
-                       hipMemcpyHostToDevice));
-  HIP_TRY(c, hipMemcpy(c->d_bucket_level, A.bucket_level.data(), sizeof(u32) * A.bucket_level.size(),
-                       hipMemcpyHostToDevice));
-  {
-    // k-mer tables for tokenize_kmer_k.  Depth of every state = its distance from the root (a transition raises the
-    // depth by at most one and the trie path does); the string of a state of depth 8 follows its first discovery.
-    const u32 ns = (u32)A.n_states;
-    std::vector<int> depth(ns, -1);
-    std::vector<u32> code(ns, 0), order;
-    order.reserve(ns);
-    depth[0] = 0;
-    order.push_back(0);
-    for (size_t h = 0; h < order.size(); h++) {
-      const u32 st = order[h];
-      for (u32 ch = 0; ch < 4; ch++) {
-        const u32 t = A.next[(size_t)st * 4 + ch];
-        if (depth[t] < 0) { depth[t] = depth[st] + 1; code[t] = (code[st] << 2) | ch; order.push_back(t); }
-      }
-    }
-    bool ok = order.size() == ns;
-    u32 id8 = ns, n8 = 0;
-    for (u32 st = 0; st < ns && ok; st++) {  // ids are BFS ranks: depth must not decrease with the id
-      if (st && depth[st] < depth[st - 1]) ok = false;
-      if (depth[st] >= 8 && id8 == ns) id8 = st;
-      if (depth[st] == 8) n8++;
-    }
-    if (ok && id8 > 32768) ok = false;  // t7 keeps a state in 15 bits
-    std::vector<u32> tab(KMER_WORDS, 0);
-    bool t7_out = false;  // a state of depth <= 7 with an output (a core of fewer than 8 bases in the table)
-    if (ok) {
-      u16 *t7 = reinterpret_cast<u16 *>(tab.data());
-      u32 *bits8 = tab.data() + KMER_T7_WORDS, *out8 = bits8 + KMER_BITS_WORDS;
-      u16 *rank8 = reinterpret_cast<u16 *>(out8 + KMER_BITS_WORDS);
-      for (u32 x = 0; x < 16384 && ok; x++) {
-        u32 st = 0;
-        for (int j = 0; j < 7; j++) st = A.next[(size_t)st * 4 + ((x >> (12 - 2 * j)) & 3)];
-        if (st >= 32768 || st >= id8) ok = false;
-        t7[x] = (u16)(st | (A.outinfo[st] != kNoOutD ? 0x8000u : 0u));
-        if (A.outinfo[st] != kNoOutD) t7_out = true;
-      }
-      u32 prev_code = 0;
-      for (u32 i = 0; i < n8 && ok; i++) {  // the depth-8 states: ids id8 .. id8 + n8 - 1 in the order of their 8-mers
-        const u32 st = id8 + i;
-        if (st >= ns || depth[st] != 8 || (i && code[st] <= prev_code)) { ok = false; break; }
-        prev_code = code[st];
-        bits8[code[st] >> 5] |= 1u << (code[st] & 31);
-        if (A.outinfo[st] != kNoOutD) out8[code[st] >> 5] |= 1u << (code[st] & 31);
-      }
-      u32 run = 0;
-      for (u32 wi = 0; wi < KMER_BITS_WORDS && ok; wi++) {
-        if (run > 0xFFFF) ok = false;
-        rank8[wi] = (u16)run;
-        run += (u32)__builtin_popcount(bits8[wi]);
-      }
-    }
-    if (ok) {
-      HIP_TRY(c, hipMalloc(&c->d_kmer, sizeof(u32) * KMER_WORDS));
-      HIP_TRY(c, hipMemcpy(c->d_kmer, tab.data(), sizeof(u32) * KMER_WORDS, hipMemcpyHostToDevice));
-      c->id8_first = id8;
-      c->kmer_t7_out = t7_out;
-    }
-    // Anchor tables (tokenize_anchor_k): a table whose shallow part does not fit the k-mer tables above -- thousands of
-    // 8-mers are fine, a million cores of 12-32 bases are not -- is searched from the occurrences' starts instead of by
-    // walking the automaton.  K = min(shortest core, 12).
-    // (the k-mer tables only shortcut transitions out of states of depth <= 7: with 400 000 states and more most of the walk
-    //  is deeper than that, whether the tables could be built or not)
-    const bool want = ns > 400000u;
-    if (want && order.size() == ns && A.min_level >= 6 && A.n_buckets > 0) {
-      const u32 K = (u32)std::min(A.min_level, 12);
-      const size_t nbits = (size_t)1 << (2 * K), nwords = (nbits + 63) / 64;
-      std::vector<u64> bits(nwords, 0);
-      u32 idK = ns;
-      bool lex = true;
-      u32 prev = 0;
-      for (u32 st = 0; st < ns; st++) {
-        if (depth[st] != (int)K) continue;
-        if (idK == ns) idK = st;
-        else if (code[st] <= prev) lex = false;      // (nodes of one depth are numbered in lexicographic order: BFS over ordered children)
-        prev = code[st];
-        bits[code[st] >> 6] |= 1ull << (code[st] & 63u);
-      }
-      // ids of depth K must be one contiguous, sorted range
-      u32 nK = 0;
-      for (u32 st = 0; st < ns; st++) nK += depth[st] == (int)K;
-      for (u32 st = idK; st < idK + nK && lex; st++) if (depth[st] != (int)K) lex = false;
-      if (lex && idK < ns) {
-        std::vector<u32> rank(nwords);
-        u32 run = 0;
-        for (size_t w = 0; w < nwords; w++) { rank[w] = run; run += (u32)__builtin_popcountll(bits[w]); }
-        std::vector<u32> child(((size_t)ns * 4 + 31) / 32, 0);
-        for (u32 st = 0; st < ns; st++)
-          for (u32 ch = 0; ch < 4; ch++) {
-            const u32 t = A.next[(size_t)st * 4 + ch];
-            if (depth[t] == depth[st] + 1) child[((size_t)st * 4 + ch) >> 5] |= 1u << (((size_t)st * 4 + ch) & 31);
-          }
-        // One probe for most anchors (round 5).  Below 97 % of the depth-K nodes of a million-core table hangs exactly ONE core,
-        // on a path without branches: for those the walk down the trie (three dependent loads per base, up to 20 bases) is one
-        // 16-byte record -- length, bucket, the bases behind the K-mer packed like the K-mer itself -- and one comparison with
-        // the read's own bits.  Any other node (branches, a core that is a prefix of another) keeps record 0 and is walked.
-        std::vector<uint4> single(nK, make_uint4(0, 0, 0, 0));
-        for (u32 j = 0; j < nK; j++) {
-          u32 st = idK + j, d = K, cores = 0, bucket = 0, len = 0;
-          u64 suf = 0;
-          bool simple = true;
-          for (;;) {
-            const u32 info = A.outinfo[st];
-            if (info != kNoOutD && (info >> kLevelShiftD) == d) { cores++; bucket = info & kBucketMaskD; len = d; }
-            u32 nch = 0, chv = 0, nxt = 0;
-            for (u32 ch = 0; ch < 4; ch++) {
-              const u32 t = A.next[(size_t)st * 4 + ch];
-              if (depth[t] == depth[st] + 1) { nch++; chv = ch; nxt = t; }
-            }
-            if (nch == 0) break;
-            if (nch > 1 || cores) { simple = false; break; }   // a branch, or a core with more cores below it
-            suf = (suf << 2) | chv;
-            st = nxt;
-            d++;
-            if (d > 44) { simple = false; break; }
-          }
-          if (simple && cores == 1 && len == d && len - K <= 32 && len < 64 && bucket < (1u << 26))
-            single[j] = make_uint4(len | (bucket << 6), (u32)suf, (u32)(suf >> 32), 0);
-        }
-        HIP_TRY(c, hipMalloc(&c->d_anchor_single, sizeof(uint4) * (size_t)nK));
-        HIP_TRY(c, hipMemcpy(c->d_anchor_single, single.data(), sizeof(uint4) * (size_t)nK, hipMemcpyHostToDevice));
-        HIP_TRY(c, hipMalloc(&c->d_anchor_bits, sizeof(u64) * nwords));
-        HIP_TRY(c, hipMalloc(&c->d_anchor_rank, sizeof(u32) * nwords));
-        HIP_TRY(c, hipMalloc(&c->d_child_bits, sizeof(u32) * child.size()));
-        HIP_TRY(c, hipMemcpy(c->d_anchor_bits, bits.data(), sizeof(u64) * nwords, hipMemcpyHostToDevice));
-        HIP_TRY(c, hipMemcpy(c->d_anchor_rank, rank.data(), sizeof(u32) * nwords, hipMemcpyHostToDevice));
-        HIP_TRY(c, hipMemcpy(c->d_child_bits, child.data(), sizeof(u32) * child.size(), hipMemcpyHostToDevice));
-        c->anchor_K = K;
-        c->anchor_idK = idK;
-      }
-    }
-  }
-  // stage as many leading (shallow) states as fit in 60 KiB of LDS: 2 workgroups per CU stay resident
-  int cap = (60 * 1024) / 20;
-  c->tok_lds_states = A.n_states < cap ? A.n_states : cap;
+  c->walk = T.walk;
   c->have_patterns = true;
   return SCALCE_OK;
 }
@@ -258,20 +135,9 @@ extern "C" int scalce_patterns_load_text(scalce_ctx *c, const char *text, size_t
 extern "C" int scalce_patterns_count(const scalce_ctx *c) { return c ? (int)c->A.patterns.size() : 0; }
 extern "C" int scalce_patterns_states(const scalce_ctx *c) { return c ? c->A.n_states : 0; }
 extern "C" int scalce_patterns_buckets(const scalce_ctx *c) { return c ? c->A.n_buckets : 0; }
-// the walk both tokenizer passes take (first_walk, the tie candidates): decided by the loaded table alone.  (STATES is not
-// reached from a loaded table: ids are BFS ranks with children in A,C,G,T order, so the k-mer tables' checks always hold.)
-static int token_walk(const scalce_ctx *c) {
-  if (!c->have_patterns) return SCALCE_WALK_NONE;
-  if (c->anchor_K) return SCALCE_WALK_ANCHOR;
-  if (c->d_kmer) return c->kmer_t7_out ? SCALCE_WALK_KMER_T7 : SCALCE_WALK_KMER;
-  return SCALCE_WALK_STATES;
-}
 extern "C" int scalce_patterns_walk(const scalce_ctx *c, int *anchor_k) {
-  if (anchor_k) *anchor_k = 0;
-  if (!c) return SCALCE_WALK_NONE;
-  const int w = token_walk(c);
-  if (anchor_k && w == SCALCE_WALK_ANCHOR) *anchor_k = (int)c->anchor_K;
-  return w;
+  if (anchor_k) *anchor_k = c ? (int)c->anchor_K : 0;
+  return c ? c->walk : SCALCE_WALK_NONE;
 }
 extern "C" int scalce_pattern_length(const scalce_ctx *c, int p) {
   return (c && p >= 0 && p < (int)c->A.patterns.size()) ? (int)c->A.patterns[p].size() : -1;
@@ -291,6 +157,19 @@ extern "C" int scalce_patterns_describe_host(const void *blob, size_t n, int is_
   if (bucket_pattern_out)
     for (size_t i = 0; i < cap && i < A.bucket_pattern.size(); i++) bucket_pattern_out[i] = A.bucket_pattern[i];
   return SCALCE_OK;
+}
+
+extern "C" int scalce_patterns_walk_host(const void *blob, size_t n, int is_text, int *anchor_k) {
+  // the same without a device: what scalce_patterns_walk answers once the table is loaded
+  Automaton A;
+  WalkTables T;
+  std::string err;
+  if (anchor_k) *anchor_k = 0;
+  if (!blob) return SCALCE_WALK_NONE;
+  const bool ok = is_text ? A.load_text(static_cast<const char *>(blob), n) : A.load_bin(blob, n);
+  if (!ok || !build_walk_tables(A, T, err)) return SCALCE_WALK_NONE;
+  if (anchor_k) *anchor_k = (int)T.K;
+  return T.walk;
 }
 
 extern "C" void scalce_params_default(scalce_params *p) {
@@ -323,7 +202,7 @@ struct scalce_workspace {
   u64 piece_rows_cap = 0;    // records one piece may bring (size of the line index)
   DBuf line_end[2], tile[2], packed[2], q[2], namelen, namecell, outlen, names_in, name_in_off, prior_buf;
   DBuf tok_bucket, tok_pos, tie_index, tie_read, tie_off, tie_ncand, cand_bucket, cand_pos, choice;
-  DBuf ev_off, ev_bucket, ev_init, ev_sorted, ev_tmp, ev_place, chosen, G, seg, dirty, cand_place, Gseg, cand_fixed;
+  DBuf ev_off, ev_sorted, ev_tmp, ev_place, chosen, G, seg, dirty, cand_place, Gseg, cand_fixed;
   DBuf bucket, endv, tokens, counts, bucket_first, bucket_off, chunk, chunk_start;
   DBuf perm_a, perm_b, key_a, key_b, hist, scan_ws, S, run_head, run_hcount, run_rank, runid, run_items_a, run_items_b, run_pos;
   DBuf name_off;
@@ -338,7 +217,7 @@ struct scalce_workspace {
   void free_all() {
     DBuf *all[] = {&line_end[0], &line_end[1], &tile[0], &tile[1], &packed[0], &packed[1], &q[0], &q[1], &namelen, &namecell, &outlen,
                    &names_in, &name_in_off, &prior_buf, &tok_bucket, &tok_pos, &tie_index, &tie_read, &tie_off, &tie_ncand, &cand_bucket,
-                   &cand_pos, &choice, &ev_off, &ev_bucket, &ev_init, &ev_sorted, &ev_tmp, &ev_place, &chosen, &G, &seg, &dirty,
+                   &cand_pos, &choice, &ev_off, &ev_sorted, &ev_tmp, &ev_place, &chosen, &G, &seg, &dirty,
                    &cand_place, &Gseg, &cand_fixed, &bucket, &endv, &tokens, &counts, &bucket_first, &bucket_off, &chunk, &chunk_start, &perm_a,
                    &perm_b, &key_a, &key_b, &hist, &scan_ws, &S, &run_head, &run_hcount, &run_rank, &runid, &run_items_a, &run_items_b,
                    &run_pos, &name_off, &tw_cells, &tw_cand, &tw_bits, &tw_base, &tile_mm[0], &tile_mm[1], &cell_sorted, &qs_shared[0], &qs_shared[1],
@@ -358,7 +237,7 @@ struct scalce_batch {
         packed(w->packed), q(w->q), namelen(w->namelen), namecell(w->namecell), outlen(w->outlen), names_in(w->names_in),
         name_in_off(w->name_in_off), prior_buf(w->prior_buf), tok_bucket(w->tok_bucket), tok_pos(w->tok_pos), tie_index(w->tie_index),
         tie_read(w->tie_read), tie_off(w->tie_off), tie_ncand(w->tie_ncand), cand_bucket(w->cand_bucket), cand_pos(w->cand_pos),
-        choice(w->choice), ev_off(w->ev_off), ev_bucket(w->ev_bucket), ev_init(w->ev_init), ev_sorted(w->ev_sorted), ev_tmp(w->ev_tmp),
+        choice(w->choice), ev_off(w->ev_off), ev_sorted(w->ev_sorted), ev_tmp(w->ev_tmp),
         ev_place(w->ev_place), chosen(w->chosen), G(w->G), seg(w->seg), dirty(w->dirty), cand_place(w->cand_place), Gseg(w->Gseg), cand_fixed(w->cand_fixed),
         bucket(w->bucket), endv(w->endv), tokens(w->tokens), counts(w->counts), bucket_first(w->bucket_first), bucket_off(w->bucket_off),
         chunk(w->chunk), chunk_start(w->chunk_start), perm_a(w->perm_a), perm_b(w->perm_b), key_a(w->key_a), key_b(w->key_b), hist(w->hist),
@@ -410,7 +289,7 @@ struct scalce_batch {
   DBuf (&line_end)[2], (&tile)[2], (&packed)[2], (&q)[2], &namelen, &namecell, &outlen;
   DBuf &names_in, &name_in_off, &prior_buf;  // names longer than a cell, input order
   DBuf &tok_bucket, &tok_pos, &tie_index, &tie_read, &tie_off, &tie_ncand, &cand_bucket, &cand_pos, &choice;
-  DBuf &ev_off, &ev_bucket, &ev_init, &ev_sorted, &ev_tmp, &ev_place, &chosen, &G, &seg, &dirty, &cand_place, &Gseg, &cand_fixed;
+  DBuf &ev_off, &ev_sorted, &ev_tmp, &ev_place, &chosen, &G, &seg, &dirty, &cand_place, &Gseg, &cand_fixed;
   DBuf &bucket, &endv, &tokens, &counts, &bucket_first, &bucket_off, &chunk, &chunk_start;
   // what the coder and the caller read behind the emit stage: the batch's own
   DBuf freq4[2], table[2], qs_own[2], counts_total, bucket_name_bytes, ac_scan;

@@ -1,27 +1,52 @@
 // host_tokenize.inc -- part of scalce_hip.hip (one translation unit; included there, in this order): stage 2: both walks, events, the exact tie-break (windows, global sweeps, sequential bound), spill-chunk plan
-// pass A of the tokenizer over rows [row0, row0 + n): longest core, its last base, hits at that length, tie flag -> tok_bucket /
-// tok_pos at index (row - tok_row0), tok_row0 = the row index 0 of those arrays stands for
-static int first_walk(scalce_batch *b, u64 row0, u64 n, u64 tok_row0, hipStream_t s) {
-  scalce_ctx *c = b->ctx;
-  if (!n) return SCALCE_OK;
-  const u8 *packed0 = b->packed[0].as<u8>() + row0 * (u64)b->stride[0];
-  TokArgs a;
-  a.next = c->d_next; a.outinfo = c->d_outinfo; a.n_states = (u32)c->A.n_states; a.lds_states = (u32)c->tok_lds_states;
-  a.packed = packed0; a.nrec = n; a.L = b->L[0]; a.stride = b->stride[0];
-  a.root_bucket = (u32)c->A.n_buckets; a.tok_bucket = b->tok_bucket.as<u32>() + (row0 - tok_row0); a.tok_pos = b->tok_pos.as<u32>() + (row0 - tok_row0);
-  const size_t sh = (size_t)a.lds_states * 20;
-  a.kmer = c->d_kmer; a.id8_first = c->id8_first;
-  const int walk = token_walk(c);
-  if (walk == SCALCE_WALK_ANCHOR) {
+// the anchor walk's view of the table and of `nrec` rows from `packed` on (tokenize_anchor_k; the candidate pass adds its own)
+static void anchor_args(const scalce_ctx *c, const scalce_batch *b, const u8 *packed, u64 nrec, AnchorArgs &a) {
+  memset(&a, 0, sizeof a);
+  a.next = reinterpret_cast<const u32 *>(c->d_next); a.outinfo = c->d_outinfo;
+  a.bits = c->d_anchor_bits; a.rank = c->d_anchor_rank; a.child = c->d_child_bits; a.K = c->anchor_K; a.idK = c->anchor_idK;
+  a.single = c->d_anchor_single;
+  a.packed = packed; a.nrec = nrec; a.L = b->L[0]; a.stride = b->stride[0]; a.root_bucket = (u32)c->A.n_buckets;
+}
+// The one place a tokenizer walk is launched: the walk the loaded table selected (scalce_ctx::walk) over rows
+// [row0, row0 + n), whose tokens live in tok_bucket / tok_pos at index (row - tok_row0).
+//   WALK_FIRST       every row: longest core, its last base, hits at that length, tie flag -> tok_bucket / tok_pos
+//   WALK_CANDIDATES  the b->ntie tie reads among them (tie_read counts from row0): the distinct cores of the longest length
+//                    in order of first appearance -> cand_bucket / cand_pos / tie_ncand
+static void launch_walk(scalce_batch *b, WalkPass pass, u64 row0, u64 n, u64 tok_row0, hipStream_t s) {
+  const scalce_ctx *c = b->ctx;
+  const bool cands = pass == WALK_CANDIDATES, t7 = c->walk == SCALCE_WALK_KMER_T7;
+  const u32 ntie = cands ? b->ntie : 0;
+  if (!(cands ? (u64)ntie : n)) return;
+  const u8 *packed = b->packed[0].as<u8>() + row0 * (u64)b->stride[0];
+  u32 *tok_bucket = b->tok_bucket.as<u32>() + (row0 - tok_row0), *tok_pos = b->tok_pos.as<u32>() + (row0 - tok_row0);
+  if (c->walk == SCALCE_WALK_ANCHOR) {
     AnchorArgs g;
-    anchor_args(c, b, packed0, n, g);
-    g.tok_bucket = a.tok_bucket; g.tok_pos = a.tok_pos;
-    LAUNCH(tokenize_anchor_k<false>, cdiv(n, 256), 256, 0, s, g);
-  } else if (walk == SCALCE_WALK_KMER_T7) LAUNCH(tokenize_kmer_pipe_k<true>, cdiv(n, TOKP_THREADS), TOKP_THREADS, 0, s, a);
-  else if (walk == SCALCE_WALK_KMER) LAUNCH(tokenize_kmer_pipe_k<false>, cdiv(n, TOKP_THREADS), TOKP_THREADS, 0, s, a);
-  else if (a.lds_states) LAUNCH(tokenize_k<true>, cdiv(n, TOK_THREADS), TOK_THREADS, sh, s, a);
-  else LAUNCH(tokenize_k<false>, cdiv(n, TOK_THREADS), TOK_THREADS, 0, s, a);
-  return SCALCE_OK;
+    anchor_args(c, b, packed, n, g);
+    g.tok_bucket = tok_bucket; g.tok_pos = tok_pos;
+    if (cands) {
+      g.ntie = ntie; g.tie_read = b->tie_read.as<u32>(); g.tie_off = b->tie_off.as<u32>(); g.bucket_level = c->d_bucket_level;
+      g.cand_bucket = b->cand_bucket.as<u32>(); g.cand_pos = b->cand_pos.as<u32>(); g.tie_ncand = b->tie_ncand.as<u32>();
+      LAUNCH(tokenize_anchor_k<true>, cdiv(ntie, 256), 256, 0, s, g);
+    } else {
+      LAUNCH(tokenize_anchor_k<false>, cdiv(n, 256), 256, 0, s, g);
+    }
+  } else if (cands) {
+    TieArgs a;
+    a.next = c->d_next; a.outinfo = c->d_outinfo; a.packed = packed; a.L = b->L[0]; a.stride = b->stride[0];
+    a.ntie = ntie; a.tie_read = b->tie_read.as<u32>(); a.tie_off = b->tie_off.as<u32>(); a.bucket_level = c->d_bucket_level;
+    a.tok_bucket = tok_bucket; a.cand_bucket = b->cand_bucket.as<u32>(); a.cand_pos = b->cand_pos.as<u32>();
+    a.tie_ncand = b->tie_ncand.as<u32>();
+    a.kmer = c->d_kmer; a.id8_first = c->id8_first;
+    if (t7) LAUNCH(tie_candidates_pipe_k<true>, cdiv(ntie, TOKP_THREADS), TOKP_THREADS, 0, s, a);
+    else LAUNCH(tie_candidates_pipe_k<false>, cdiv(ntie, TOKP_THREADS), TOKP_THREADS, 0, s, a);
+  } else {
+    TokArgs a;
+    a.next = c->d_next; a.outinfo = c->d_outinfo; a.packed = packed; a.nrec = n; a.L = b->L[0]; a.stride = b->stride[0];
+    a.root_bucket = (u32)c->A.n_buckets; a.tok_bucket = tok_bucket; a.tok_pos = tok_pos;
+    a.kmer = c->d_kmer; a.id8_first = c->id8_first;
+    if (t7) LAUNCH(tokenize_kmer_pipe_k<true>, cdiv(n, TOKP_THREADS), TOKP_THREADS, 0, s, a);
+    else LAUNCH(tokenize_kmer_pipe_k<false>, cdiv(n, TOKP_THREADS), TOKP_THREADS, 0, s, a);
+  }
 }
 
 // ---- stage 2: tokenize ------------------------------------------------------------------------------
@@ -35,7 +60,6 @@ extern "C" int scalce_batch_tokenize_begin(scalce_batch *b, void *stream) {
   b->tok_base = b->tok_done;
   b->tok_n = b->N - b->tok_done;
   const u64 N = b->tok_n;
-  const u8 *packed0 = b->packed[0].as<u8>() + b->tok_base * (u64)b->stride[0];
   b->jacobi_iters = 0;
   b->tie_fallback = false;
   b->sweep_no = 0;
@@ -62,10 +86,7 @@ extern "C" int scalce_batch_tokenize_begin(scalce_batch *b, void *stream) {
     return SCALCE_OK;
   }
   // pass A: every read (unless scalce_batch_chunk_plan / scalce_batch_rewindow have walked exactly these rows already: sharded runs)
-  if (!(b->tok_base == 0 && b->walk_rows == N && b->ws->walk_owner == b)) {
-    int rc = first_walk(b, b->tok_base, N, b->tok_base, s);
-    if (rc) return rc;
-  }
+  if (!(b->tok_base == 0 && b->walk_rows == N && b->ws->walk_owner == b)) launch_walk(b, WALK_FIRST, b->tok_base, N, b->tok_base, s);
   b->walk_rows = 0;  // (the scans below rewrite tok_pos)
   b->ws->walk_owner = nullptr;
   // tie reads: compact, then size the candidate lists by their hit counts
@@ -92,24 +113,7 @@ extern "C" int scalce_batch_tokenize_begin(scalce_batch *b, void *stream) {
   ENSURE(b, b->cand_pos, sizeof(u32) * (ncap + 2));
   ENSURE(b, b->cand_place, sizeof(u32) * (ncap + 2));
   if (ntie) {
-    TieArgs a;
-    a.next = c->d_next; a.outinfo = c->d_outinfo; a.packed = packed0; a.L = b->L[0]; a.stride = b->stride[0];
-    a.ntie = ntie; a.tie_read = b->tie_read.as<u32>(); a.tie_off = b->tie_off.as<u32>(); a.bucket_level = c->d_bucket_level;
-    a.tok_bucket = b->tok_bucket.as<u32>(); a.cand_bucket = b->cand_bucket.as<u32>(); a.cand_pos = b->cand_pos.as<u32>();
-    a.tie_ncand = b->tie_ncand.as<u32>();
-    a.lds_states = (u32)c->tok_lds_states;
-    a.kmer = c->d_kmer; a.id8_first = c->id8_first;
-    const int walk = token_walk(c);
-    if (walk == SCALCE_WALK_ANCHOR) {
-      AnchorArgs g;
-      anchor_args(c, b, packed0, N, g);
-      g.ntie = ntie; g.tie_read = a.tie_read; g.tie_off = a.tie_off; g.bucket_level = a.bucket_level;
-      g.cand_bucket = a.cand_bucket; g.cand_pos = a.cand_pos; g.tie_ncand = a.tie_ncand;
-      LAUNCH(tokenize_anchor_k<true>, cdiv(ntie, 256), 256, 0, s, g);
-    } else if (walk == SCALCE_WALK_KMER_T7) LAUNCH(tie_candidates_pipe_k<true>, cdiv(ntie, TOKP_THREADS), TOKP_THREADS, 0, s, a);
-    else if (walk == SCALCE_WALK_KMER) LAUNCH(tie_candidates_pipe_k<false>, cdiv(ntie, TOKP_THREADS), TOKP_THREADS, 0, s, a);
-    else if (a.lds_states) LAUNCH(tie_candidates_k<true>, cdiv(ntie, TOK_THREADS), TOK_THREADS, (size_t)a.lds_states * 20, s, a);
-    else LAUNCH(tie_candidates_k<false>, cdiv(ntie, TOK_THREADS), TOK_THREADS, 0, s, a);
+    launch_walk(b, WALK_CANDIDATES, b->tok_base, N, b->tok_base, s);
     HIP_TRY(c, hipMemsetAsync(b->choice.p, 0, sizeof(u32) * ntie, s));
   }
   // events in read order, stable-sorted by bucket
@@ -130,7 +134,7 @@ extern "C" int scalce_batch_tokenize_begin(scalce_batch *b, void *stream) {
     EventArgs a;
     a.nrec = N; a.tok_bucket = b->tok_bucket.as<u32>(); a.tok_pos = b->tok_pos.as<u32>(); a.tie_index = b->tie_index.as<u32>();
     a.tie_off = b->tie_off.as<u32>(); a.tie_ncand = b->tie_ncand.as<u32>(); a.cand_bucket = b->cand_bucket.as<u32>();
-    a.ev_off = b->ev_off.as<u32>(); a.ev_bucket = nullptr; a.ev_init = nullptr;  // (the keys carry bucket and flags)
+    a.ev_off = b->ev_off.as<u32>();
     // the events are sorted by bucket as (key, event) pairs, like the order stage's records (sequential passes; the
     // index-only passes gathered the bucket through the index, and so did the two kernels behind them)
     ENSURE(b, b->key_a, sizeof(u64) * ((size_t)nev + 2));   // (the order stage's 64-bit keys live in the same buffers)
@@ -165,7 +169,7 @@ extern "C" int scalce_batch_tokenize_begin(scalce_batch *b, void *stream) {
     LAUNCH(tie_place_k, cdiv(ntie, 256), 256, 0, s, ntie, b->tie_read.as<u32>(), b->tie_off.as<u32>(), b->tie_ncand.as<u32>(),
            b->ev_off.as<u32>(), b->ev_place.as<u32>(), cidx, b->cand_bucket.as<u32>(), seg_all, seg_t, b->cand_place.as<u32>(),
            b->cand_fixed.as<u32>());
-  // first prefix sums (per bucket) and counts; the sweeps follow (scalce_batch_tokenize_sweep)
+  // first prefix sums (per bucket) and counts; the tie-break follows (scalce_batch_tokenize_settle)
   b->dirty_cur = 0;
   HIP_TRY(c, hipMemsetAsync(b->dirty.p, 0, sizeof(u32) * nb1, s));  // first sweep: every bucket moved "before read 0"
   HIP_TRY(c, hipMemsetAsync(b->dirty.as<u32>() + 2 * (size_t)(nb1 + 64), 0, sizeof(u64) * nb1, s));  // prior seen so far
@@ -176,20 +180,25 @@ extern "C" int scalce_batch_tokenize_begin(scalce_batch *b, void *stream) {
   return SCALCE_OK;
 }
 
-// One Jacobi sweep, enqueued only: decisions of the tie reads against the current counts, then new prefix sums and
-// per-bucket counts for the buckets whose flags moved (seg_rescan_k looks at the dirty marks itself: nothing moved,
-// nothing to do).  flag[0] becomes 1 if any decision of this shard moved.
+// The counts a tie-break of rows [tok_base, N) starts from: the caller's cross-shard prior (or none) plus the reads of this
+// batch's earlier pieces (bin_size is cumulative, reads.cpp:246).
+static const uint64_t *fold_prior(scalce_batch *b, const uint64_t *d_prior, hipStream_t s) {
+  if (!b->tok_base) return d_prior;
+  if (!d_prior) return b->counts_total.as<uint64_t>();
+  const u32 nb1 = (u32)b->ctx->A.n_buckets + 1;
+  LAUNCH(add_counts_k, cdiv(nb1, 256), 256, 0, s, nb1, reinterpret_cast<const u64 *>(d_prior), b->counts_total.as<u64>(), b->prior_buf.as<u64>());
+  return b->prior_buf.as<uint64_t>();
+}
+
+// The global sweeps (SCALCE_TIE_WINDOW=0; the windows of tokenize_windows are the default).  One Jacobi sweep, enqueued
+// only: decisions of the tie reads against the current counts, then new prefix sums and per-bucket counts for the buckets
+// whose flags moved (seg_rescan_k looks at the dirty marks itself: nothing moved, nothing to do).  flag[0] becomes 1 if any
+// decision of this shard moved.  scalce_batch_tokenize_settle sends several out against the same prior counts with ONE
+// look at their flags.
 static int tokenize_sweep_enqueue(scalce_batch *b, const uint64_t *d_prior, u32 *flag, hipStream_t s) {
   scalce_ctx *c = b->ctx;
   const u32 nb1 = (u32)c->A.n_buckets + 1, ntie = b->ntie;
-  if (b->tok_base) {  // reads of this batch's earlier pieces count as well (bin_size is cumulative, reads.cpp:246)
-    if (d_prior) {
-      LAUNCH(add_counts_k, cdiv(nb1, 256), 256, 0, s, nb1, reinterpret_cast<const u64 *>(d_prior), b->counts_total.as<u64>(), b->prior_buf.as<u64>());
-      d_prior = b->prior_buf.as<uint64_t>();
-    } else {
-      d_prior = b->counts_total.as<uint64_t>();
-    }
-  }
+  d_prior = fold_prior(b, d_prior, s);
   u32 *d0 = b->dirty.as<u32>(), *d1 = d0 + nb1 + 64;
   u32 *dirty_in = b->dirty_cur ? d1 : d0, *dirty_out = b->dirty_cur ? d0 : d1;
   u64 *prior_seen = reinterpret_cast<u64 *>(d0 + 2 * (size_t)(nb1 + 64));
@@ -214,27 +223,19 @@ static int tokenize_sweep_enqueue(scalce_batch *b, const uint64_t *d_prior, u32 
   return SCALCE_OK;
 }
 
-// One sweep with the given cross-shard prior counts (SCALCE_OUT_BUCKET_COUNTS is current when it returns).
-// *changed = 1 if any decision of THIS shard moved.
-// The tie reads decided in input order by one wavefront (tie_sequential_k): what scalce_batch_tokenize falls back to when
-// the sweeps have not reached their fixed point after tie_max_sweeps() of them.  Leaves choice / chosen / G / counts as
-// the converged sweeps would.
+// sweeps allowed before the tie-break gives up sweeping: in all (global sweeps), or per window
 static u32 tie_max_sweeps() {
   const char *e = getenv("SCALCE_TIE_MAX_SWEEPS");  // (tests lower it to drive the fallback on ordinary input)
   const int v = e ? atoi(e) : 256;
   return (u32)(v < 1 ? 1 : v);
 }
+// The tie reads decided in input order by one wavefront (tie_sequential_k): what scalce_batch_tokenize_settle falls back to
+// when the sweeps -- of the windows or the global ones -- have not reached their fixed point after tie_max_sweeps() of
+// them.  Leaves choice / chosen / G / counts as the converged global sweeps would.
 static int tokenize_sequential(scalce_batch *b, const uint64_t *d_prior, hipStream_t s) {
   scalce_ctx *c = b->ctx;
   const u32 nb1 = (u32)c->A.n_buckets + 1, ntie = b->ntie;
-  if (b->tok_base) {
-    if (d_prior) {
-      LAUNCH(add_counts_k, cdiv(nb1, 256), 256, 0, s, nb1, reinterpret_cast<const u64 *>(d_prior), b->counts_total.as<u64>(), b->prior_buf.as<u64>());
-      d_prior = b->prior_buf.as<uint64_t>();
-    } else {
-      d_prior = b->counts_total.as<uint64_t>();
-    }
-  }
+  d_prior = fold_prior(b, d_prior, s);
   ENSURE(b, b->Gseg, sizeof(u32) * (nb1 + 2));
   TieSeqArgs a;
   a.ntie = ntie; a.nb1 = nb1; a.tie_off = b->tie_off.as<u32>(); a.tie_ncand = b->tie_ncand.as<u32>(); a.cand_bucket = b->cand_bucket.as<u32>();
@@ -256,8 +257,7 @@ static int tokenize_sequential(scalce_batch *b, const uint64_t *d_prior, hipStre
   return SCALCE_OK;
 }
 
-// Several sweeps against the same prior counts with ONE look at their flags (a sweep behind the local fixed point changes
-// nothing and costs next to nothing; a host round trip per sweep leaves the stream idle).  *changed = 1 if any moved.
+// Behind the tie-break: the batch's counts join the run's, and every row gets its bucket, end and tokens (finalize_k).
 extern "C" int scalce_batch_tokenize_end(scalce_batch *b, void *stream) {
   if (!b || !b->tok_open) return SCALCE_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
@@ -316,14 +316,7 @@ static int tokenize_windows(scalce_batch *b, const uint64_t *d_prior, bool *sett
   scalce_ctx *c = b->ctx;
   const u32 nb1 = (u32)c->A.n_buckets + 1, ntie = b->ntie, ncap = b->ncand_cap, ntev = b->ntev;
   *settled = false;
-  if (b->tok_base) {  // reads of this batch's earlier pieces count as well (bin_size is cumulative, reads.cpp:246)
-    if (d_prior) {
-      LAUNCH(add_counts_k, cdiv(nb1, 256), 256, 0, s, nb1, reinterpret_cast<const u64 *>(d_prior), b->counts_total.as<u64>(), b->prior_buf.as<u64>());
-      d_prior = b->prior_buf.as<uint64_t>();
-    } else {
-      d_prior = b->counts_total.as<uint64_t>();
-    }
-  }
+  d_prior = fold_prior(b, d_prior, s);
   u32 W = tie_window_reads();
   const u64 max_cells = 64ull << 20;  // (a million-core table: fewer, larger windows)
   if ((u64)cdiv(ntie, W) * nb1 > max_cells) W = (u32)cdiv(ntie, max_cells / nb1 ? max_cells / nb1 : 1);
@@ -485,8 +478,7 @@ extern "C" int scalce_batch_chunk_plan(scalce_batch *b, uint64_t carry_in, uint6
   ENSURE(b, b->tok_bucket, sizeof(u32) * (N + 1));
   ENSURE(b, b->tok_pos, sizeof(u32) * (N + 1));
   if (b->S_rows != N && !(b->tok_done == 0 && b->walk_rows == N && b->ws->walk_owner == b)) {  // (a second call with another carry_in only redoes the cuts)
-    int rc = first_walk(b, 0, N, 0, s);
-    if (rc) return rc;
+    launch_walk(b, WALK_FIRST, 0, N, 0, s);
     b->walk_rows = b->tok_done == 0 ? N : 0;  // (tok_bucket / tok_pos are indexed from the first row not tokenized yet)
     b->ws->walk_owner = b;
   }

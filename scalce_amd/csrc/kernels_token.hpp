@@ -5,12 +5,24 @@
 // read, the first one whose bucket currently holds the most reads (strict >), where "currently"
 // means all earlier reads of the run (bin_size is cumulative, reads.cpp:246).  Per read the scan
 // is independent; only reads that see two different cores of the same maximal length ("tie
-// reads") depend on earlier decisions.  The resolution here is a Jacobi fixed point over the
-// tie reads: every read's decision is re-evaluated in parallel from prefix counts of the current
-// decisions until nothing changes.  By induction on the input order the fixed point is unique
-// and equals the sequential result (the earliest undecided tie read only depends on settled
-// ones), so the outcome is bit-exact with -T 1.
+// reads") depend on earlier decisions.
+//
+// The walks (one per core-table shape, chosen when the table is loaded: WalkTables, automaton.hpp):
+// tokenize_kmer_pipe_k / tie_candidates_pipe_k with the k-mer block in LDS, tokenize_anchor_k
+// for tables too large for it; each as a first pass over every read and a candidate pass over the
+// tie reads.
+//
+// The tie-break is a Jacobi fixed point over the tie reads: every read's decision is re-evaluated
+// in parallel from prefix counts of the current decisions until nothing changes.  By induction on
+// the input order the fixed point is unique and equals the sequential result (the earliest
+// undecided tie read only depends on settled ones), so the outcome is bit-exact with -T 1.  It is
+// reached window by window (tie_window_fused_k; tie_window_sweep_k / _tail_k for windows that do
+// not fit a workgroup's LDS): a window of tie reads is swept until it is settled, and only then
+// the next one, which starts from final counts.  Fallbacks: the global sweeps over all tie reads at
+// once (jacobi_k + seg_rescan_k, SCALCE_TIE_WINDOW=0), and, when sweeping does not settle within
+// its bound, the decisions in input order by one wavefront (tie_sequential_k).
 #pragma once
+#include "automaton.hpp"
 #include "kernels_ingest.hpp"
 
 namespace scalce {
@@ -19,107 +31,29 @@ constexpr u32 kNoOutD = 0xFFFFFFFFu;
 constexpr int kLevelShiftD = 25;
 constexpr u32 kBucketMaskD = (1u << kLevelShiftD) - 1;
 
-// Top of the automaton staged in LDS: states are numbered in BFS order, so ids < LDS_STATES are
-// the shallowest (most visited) ones.  20 bytes per state.
-constexpr int TOK_THREADS = 512;  // 16 waves per CU share two 60 KB copies of the hot states (256: 8 waves, 30.7 ms)
-
 struct TokArgs {
-  const uint4 *next;    // 4 x u32 per state
+  const uint4 *next;    // 4 x u32 per state (bit 31 of a transition: the target state has an output)
   const u32 *outinfo;   // level<<25 | bucket, or kNoOutD
-  u32 n_states;
-  u32 lds_states;       // how many leading states to stage (0 = none)
+  u32 id8_first;        // first state of depth 8 (= n_states when there is none): ids are BFS ranks, so depth >= 8 <=> id >= this
   const u8 *packed;
   u64 nrec;
   int L, stride;
   u32 root_bucket;      // bucket id of "no core" (== number of real buckets)
   u32 *tok_bucket;      // first longest core (bucket id), or root_bucket
   u32 *tok_pos;         // bits 0-15: index of the core's last base; bits 16-30: hits at max level; bit 31: tie
-  // k-mer tables (tokenize_kmer_k), 52 KB: t7[16384] u16 | bits8[2048] u32 | out8[2048] u32 | rank8[2048] u16
-  const u32 *kmer;
-  u32 id8_first;        // first state of depth 8 (= n_states when there is none): ids are BFS ranks, so depth >= 8 <=> id >= this
-};
-constexpr u32 KMER_T7_WORDS = 16384 / 2, KMER_BITS_WORDS = 2048, KMER_WORDS = KMER_T7_WORDS + 2 * KMER_BITS_WORDS + 2048 / 2;
-
-__device__ __forceinline__ u32 base_at(const u8 *row, int i) { return (row[i >> 2] >> (6 - 2 * (i & 3))) & 3u; }
-
-template <bool USE_LDS>
-__global__ __launch_bounds__(TOK_THREADS) void tokenize_k(TokArgs a) {
-  extern __shared__ uint4 lds_dyn[];
-  uint4 *l_next = lds_dyn;
-  u32 *l_out = reinterpret_cast<u32 *>(lds_dyn + a.lds_states);
-  if (USE_LDS) {
-    for (u32 i = threadIdx.x; i < a.lds_states; i += TOK_THREADS) {
-      l_next[i] = a.next[i];
-      l_out[i] = a.outinfo[i];
-    }
-    __syncthreads();
-  }
-  const u64 r = (u64)blockIdx.x * TOK_THREADS + threadIdx.x;
-  if (r >= a.nrec) return;
-  const u32 *row = reinterpret_cast<const u32 *>(a.packed + r * (u64)a.stride);
-  u32 state = 0, best_lv = 0, best_b = a.root_bucket, best_pos = 0, hits = 0, tie = 0;
-  const int nw = (a.L + 15) >> 4;
-  for (int w = 0; w < nw; w++) {
-    const u32 word = row[w];  // byte j of the row = bases 4j..4j+3, first base in bits 7-6
-    const int cnt = (a.L - 16 * w) < 16 ? (a.L - 16 * w) : 16;
-    for (int k = 0; k < cnt; k++) {
-      const u32 c = (word >> (8 * (k >> 2) + 6 - 2 * (k & 3))) & 3u;
-      // one 4-byte transition (a 16-byte row per lane costs four times the LDS bank accesses); bit 31 = the target
-      // state has an output
-      u32 t;
-      if (USE_LDS && state < a.lds_states) t = reinterpret_cast<const u32 *>(l_next)[state * 4 + c];
-      else t = reinterpret_cast<const u32 *>(a.next)[(u64)state * 4 + c];
-      state = t & 0x7FFFFFFFu;
-      if (t >> 31) {
-        u32 info;
-        if (USE_LDS && state < a.lds_states) info = l_out[state]; else info = a.outinfo[state];
-        const u32 lv = info >> kLevelShiftD, b = info & kBucketMaskD;
-        if (lv > best_lv) {
-          best_lv = lv; best_b = b; best_pos = 16 * w + k; hits = 1; tie = 0;
-        } else if (lv == best_lv) {
-          hits++;
-          if (b != best_b) tie = 1;
-        }
-      }
-    }
-  }
-  a.tok_bucket[r] = best_b;
-  a.tok_pos[r] = best_pos | ((hits > 0x7FFF ? 0x7FFFu : hits) << 16) | (tie << 31);
-}
-
-// The same walk with most transitions replaced by lookups that do not depend on the previous state.  With thousands
-// of cores of 8 and more bases nearly every 7-mer is a trie node: the walk sits at depth 7-8 (tens of thousands of
-// states) and tokenize_k finds four of five transitions in L2 -- 260 GB of random sector reads per 50 M reads, which is
-// what bounds it.  But the state after a base is the longest suffix of the text that is a trie node, and when the state
-// BEFORE the base has depth <= 7 that suffix is at most 8 long: it is the node of the last 8 bases if they form one
-// (bits8 / rank8: states of one depth are numbered in lexicographic order) and otherwise the state the last 7 bases
-// lead to from the root (t7).  Only from states of depth >= 8 (a fifth of the positions) the transition itself is read.
-struct KmerTables {  // views of the 52 KB block in LDS
-  const u16 *t7;
-  const u32 *bits8, *out8;
-  const u16 *rank8;
-  u32 id8_first;
-  __device__ __forceinline__ void bind(const u32 *tab, u32 id8) {
-    t7 = reinterpret_cast<const u16 *>(tab);
-    bits8 = tab + KMER_T7_WORDS;
-    out8 = bits8 + KMER_BITS_WORDS;
-    rank8 = reinterpret_cast<const u16 *>(out8 + KMER_BITS_WORDS);
-    id8_first = id8;
-  }
-  // transition word (state | has-output << 31) for base c at position pos; `code` = the last 8 bases including c
-  __device__ __forceinline__ u32 step(const u32 *next, u32 state, u32 c, u32 code, int pos) const {
-    if (pos < 7 || state >= id8_first) return next[(u64)state * 4 + c];
-    const u32 wd = bits8[code >> 5], bit = code & 31;
-    if ((wd >> bit) & 1)
-      return (id8_first + rank8[code >> 5] + (u32)__popc(wd & ((1u << bit) - 1))) | (((out8[code >> 5] >> bit) & 1u) << 31);
-    const u32 e = t7[code & 0x3FFFu];
-    return (e & 0x7FFFu) | ((e >> 15) << 31);
-  }
+  const u32 *kmer;      // the k-mer block (KMER_WORDS, automaton.hpp)
 };
 
-// tokenize_kmer_k is bound by instruction issue (44 per base at 50 M x 100 bp): the lanes of a wave diverge over its four
-// ways to a transition (global row, 8-mer bit table, rank, 7-mer table) and the compiler walks them one after the other,
-// each behind its own s_waitcnt, with the output word of the new state (another global gather) behind that.  Here a base is
+// The first walk: per read the longest core, its last base, the hits at that length and whether two different cores are
+// among them.  Walked state by state, with thousands of cores of 8 and more bases, nearly every 7-mer is a trie node: the
+// walk sits at depth 7-8 (tens of thousands of states) and finds four of five transitions in L2 -- 260 GB of random sector
+// reads per 50 M reads.  But the state after a base is the longest suffix of the text that is a trie node, and when the
+// state BEFORE the base has depth <= 7 that suffix is at most 8 long: it is the node of the last 8 bases if they form one
+// (bits8 / rank8: states of one depth are numbered in lexicographic order) and otherwise the state the last 7 bases lead to
+// from the root (t7).  Only from states of depth >= 8 (a fifth of the positions) the transition itself is read.
+// Taken lane by lane that is bound by instruction issue: the lanes of a wave diverge over the four ways to a transition
+// (global row, 8-mer bit table, rank, 7-mer table) and the compiler walks them one after the other, each behind its own
+// s_waitcnt, with the output word of the new state (another global gather) behind that.  Here a base is
 // straight-line code: every lane issues ALL lookups of a base at once -- the table lookups do not depend on the state, only
 // the choice between them does; lanes that do not need the global row read row 0 (one line for the whole wave) --, the
 // bases of a 16-base word are unrolled (codes come from the byte-swapped words with one v_alignbit), and the output word of
@@ -210,69 +144,12 @@ struct TieArgs {
   const u32 *tok_bucket;
   u32 *cand_bucket, *cand_pos;
   u32 *tie_ncand;
-  u32 lds_states;
-  const u32 *kmer;       // k-mer tables as in TokArgs (USE_KMER)
   u32 id8_first;
+  const u32 *kmer;       // the k-mer block as in TokArgs
 };
 
-template <bool USE_LDS, bool USE_KMER = false>
-__global__ __launch_bounds__(TOK_THREADS) void tie_candidates_k(TieArgs a) {
-  // same staging of the shallow (hot) states as tokenize_k: the second walk used to go to global memory for every
-  // transition and took half as long as the first walk for a fifth of the reads
-  extern __shared__ uint4 lds_dyn[];
-  uint4 *l_next = lds_dyn;
-  u32 *l_out = reinterpret_cast<u32 *>(lds_dyn + a.lds_states);
-  KmerTables km;
-  if (USE_KMER) {  // the k-mer tables of tokenize_kmer_k instead of the staged states (53 KB of dynamic LDS)
-    u32 *tab = reinterpret_cast<u32 *>(lds_dyn);
-    for (u32 i = threadIdx.x; i < KMER_WORDS; i += TOK_THREADS) tab[i] = a.kmer[i];
-    __syncthreads();
-    km.bind(tab, a.id8_first);
-  } else if (USE_LDS) {
-    for (u32 i = threadIdx.x; i < a.lds_states; i += TOK_THREADS) {
-      l_next[i] = a.next[i];
-      l_out[i] = a.outinfo[i];
-    }
-    __syncthreads();
-  }
-  const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= a.ntie) return;
-  const u32 r = a.tie_read[t];
-  const u32 off = a.tie_off[t];
-  const u32 lvmax = a.bucket_level[a.tok_bucket[r]];
-  const u32 *row = reinterpret_cast<const u32 *>(a.packed + (u64)r * a.stride);
-  u32 state = 0, k = 0, code = 0;
-  const int nw = (a.L + 15) >> 4;
-  for (int w = 0; w < nw; w++) {
-    const u32 word = row[w];
-    const int cnt = (a.L - 16 * w) < 16 ? (a.L - 16 * w) : 16;
-    for (int q = 0; q < cnt; q++) {
-      const u32 c = (word >> (8 * (q >> 2) + 6 - 2 * (q & 3))) & 3u;
-      code = ((code << 2) | c) & 0xFFFFu;
-      u32 tr;
-      if (USE_KMER) tr = km.step(reinterpret_cast<const u32 *>(a.next), state, c, code, 16 * w + q);
-      else if (USE_LDS && state < a.lds_states) tr = reinterpret_cast<const u32 *>(l_next)[state * 4 + c];
-      else tr = reinterpret_cast<const u32 *>(a.next)[(u64)state * 4 + c];
-      state = tr & 0x7FFFFFFFu;
-      u32 info = kNoOutD;
-      if (tr >> 31) { if (!USE_KMER && USE_LDS && state < a.lds_states) info = l_out[state]; else info = a.outinfo[state]; }
-      if (info != kNoOutD && (info >> kLevelShiftD) == lvmax) {
-        const u32 bk = info & kBucketMaskD;
-        bool seen = false;
-        for (u32 j = 0; j < k; j++) seen |= (a.cand_bucket[off + j] == bk);
-        if (!seen) {
-          a.cand_bucket[off + k] = bk;
-          a.cand_pos[off + k] = (u32)(16 * w + q);
-          k++;
-        }
-      }
-    }
-  }
-  a.tie_ncand[t] = k;
-}
-
 // ---- core tables of realistic size: occurrences found from their STARTS, not by walking the automaton (round 4) ----------
-// The walk above costs one dependent transition per base, and with a million cores of 12-32 bases (9.9 M states, 158 MB of
+// A walk of the automaton costs one dependent transition per base, and with a million cores of 12-32 bases (9.9 M states, 158 MB of
 // rows) four of five of them are read from L2 or HBM: 2.3 ns per read against 0.32 with the 15 600-core table.  But the
 // automaton is not the contract -- what aho_search (reads.cpp:413-429) reports at position i is the LONGEST CORE ENDING
 // THERE, and its result only depends on the occurrences of the longest cores found anywhere in the read, in the order of
@@ -285,8 +162,8 @@ __global__ __launch_bounds__(TOK_THREADS) void tie_candidates_k(TieArgs a) {
 //     trie edge iff its bit in `child` is set), noting every node at which a core ends (outinfo's level == the depth).
 // Occurrences come out by start position; for cores of one length that is the order of their end positions, and only
 // the occurrences of the longest length seen matter at the end: the first of them (bucket, last base), how many, whether
-// two different cores are among them -- exactly what tokenize_k reports.  CANDS: the second pass over the tie reads
-// (tie_candidates_k's contract: distinct cores of the longest length in order of first appearance).
+// two different cores are among them -- exactly what tokenize_kmer_pipe_k reports.  CANDS: the second pass over the tie reads
+// (tie_candidates_pipe_k's contract: distinct cores of the longest length in order of first appearance).
 struct AnchorArgs {
   const u32 *next;       // 4 x u32 per state (bit 31: the target has an output)
   const u32 *outinfo;
@@ -437,8 +314,7 @@ __global__ __launch_bounds__(256) void tokenize_anchor_k(AnchorArgs a) {
 }
 
 // The second walk in the shape of tokenize_kmer_pipe_k: straight-line code per base, the output word of the state reached
-// looked at a base later.  tie_candidates_k<false, true> walks the same reads with a wait per lookup and 24 waves per CU:
-// 1.25 us per base and wave, 2.9 ms for the 9 M tie reads of a 50 M-read shard.
+// looked at a base later.
 template <bool T7_OUT>
 __global__ __launch_bounds__(TOKP_THREADS) void tie_candidates_pipe_k(TieArgs a) {
   __shared__ u32 t7w[KMER_T7_WORDS];
@@ -537,9 +413,9 @@ struct EventArgs {
   const u32 *tie_index;  // read -> tie index (valid when tie bit set)
   const u32 *tie_off, *tie_ncand, *cand_bucket;
   const u32 *ev_off;
-  u32 *ev_bucket;        // (may be null together with ev_init: the sort on (key, event) pairs carries both in the key)
-  u8 *ev_init;           // initial "chosen" flag: fixed reads 1, first candidate 1, others 0
-  u32 *ev_key;           // bucket << 2 | candidate of a tie read << 1 | initial flag: what the sort by bucket carries along (32 bits: buckets < 2^30)
+  // bucket << 2 | candidate of a tie read << 1 | initial "chosen" flag (fixed reads 1, first candidate 1, others 0): what
+  // the sort by bucket carries along (32 bits: buckets < 2^30)
+  u32 *ev_key;
 };
 __global__ __launch_bounds__(256) void events_fill_k(EventArgs a) {
   const u64 r = (u64)blockIdx.x * blockDim.x + threadIdx.x;
@@ -549,12 +425,10 @@ __global__ __launch_bounds__(256) void events_fill_k(EventArgs a) {
     const u32 t = a.tie_index[r], off = a.tie_off[t], k = a.tie_ncand[t];
     for (u32 j = 0; j < k; j++) {
       const u32 bk = a.cand_bucket[off + j];
-      if (a.ev_bucket) { a.ev_bucket[e + j] = bk; a.ev_init[e + j] = j == 0; }
       if (a.ev_key) a.ev_key[e + j] = (bk << 2) | 2u | (j == 0 ? 1u : 0u);
     }
   } else {
     const u32 bk = a.tok_bucket[r];
-    if (a.ev_bucket) { a.ev_bucket[e] = bk; a.ev_init[e] = 1; }
     if (a.ev_key) a.ev_key[e] = (bk << 2) | 1u;
   }
 }

@@ -46,8 +46,8 @@ class ShardResult(C.Structure):
 
 
 SHARD_PREPARE_ONLY, SHARD_CODER_ASYNC = 1, 2
-# scalce_patterns_walk, by SCALCE_WALK_* value
-WALKS = ("none", "kmer", "kmer_t7", "anchor", "states")
+# scalce_patterns_walk / scalce_patterns_walk_host, by SCALCE_WALK_* value
+WALKS = ("none", "kmer", "kmer_t7", "anchor")
 
 
 def lib():
@@ -149,6 +149,7 @@ def lib():
     L.scalce_copy_pieces.argtypes = [vp, vp, vp, vp, vp, C.c_uint32, u64, vp]
     L.scalce_patterns_describe_host.argtypes = [C.c_char_p, C.c_size_t, i32, vp, C.c_size_t, C.POINTER(C.c_int32),
                                                 C.POINTER(C.c_int32)]
+    L.scalce_patterns_walk_host.argtypes = [C.c_char_p, C.c_size_t, i32, C.POINTER(C.c_int)]
     L.scalce_selftest_ac.argtypes = [vp, u64, C.c_uint32, i32, C.POINTER(C.c_uint32)]
     L.scalce_ac_decode.argtypes = [vp, vp, vp, u64, u64, vp, vp]
     L.scalce_fastq_text_bytes.restype = u64
@@ -167,6 +168,13 @@ def qmap_init(stat, lossy_percentage):
     st = (C.c_int32 * 128)(*[int(x) for x in stat[:128]])
     lib().scalce_qmap_init(C.byref(q), st, int(lossy_percentage))
     return q.offset, np.array(list(q.values), dtype=np.int32)
+
+
+def walk_of_table(blob, is_text=False):
+    """Context.walk of a core table without a device: (name, K); ("none", 0) for a table the loaders refuse."""
+    k = C.c_int(0)
+    w = lib().scalce_patterns_walk_host(blob, len(blob), int(is_text), C.byref(k))
+    return WALKS[w], k.value
 
 
 class Context:

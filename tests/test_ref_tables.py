@@ -30,10 +30,13 @@ def describe(blob, is_text):
 
 @pytest.mark.parametrize("name", B.SHAPES)
 def test_shape_tables_load_as_built(name):
-    """each table loads (binary or text) into the automaton its shape calls for: the state counts the GPU tests rely on"""
+    """each table loads (binary or text) into the automaton its shape calls for: the state counts the GPU tests rely on,
+    and the walk the table selects (what test_walk_of_every_shape asserts of the loaded table on the device)"""
     t = B.shape(name)
     rc, ns, nb = describe(t.blob, t.text)
     assert rc == 0
+    walk = host.walk_of_table(t.blob, t.text)
+    assert walk == t.walk, f"{name}: table selects {walk}, built for {t.walk}"
     assert nb == len(set(t.cores))
     if t.note.startswith("states=="):
         assert ns == int(t.note.split("==")[1]) == B.n_states(t.cores)
@@ -41,6 +44,7 @@ def test_shape_tables_load_as_built(name):
         assert ns >= 1_000_000
     if not t.text:   # the binary table and its text form are one table
         assert describe(B.text_of(t.cores), True)[1:] == (ns, nb)
+        assert host.walk_of_table(B.text_of(t.cores), True) == walk
 
 
 def test_core_of_128_bases_is_refused_by_the_loader():
