@@ -69,7 +69,7 @@ extern "C" int scalce_batch_qinput_edges(scalce_batch *b, int mate, uint8_t edge
   *nsym = n;
   if (read_len) *read_len = b->L[mate];
   edge[0] = edge[1] = edge[2] = edge[3] = 0;
-  const u8 *q = b->q[mate].as<u8>();
+  const u8 *q = b->ws->q[mate].as<u8>();
   auto at = [&](u64 t) { return q + (t / L) * QS + (t % L); };
   // (on the caller's stream, behind the ingest: a device-wide wait would sit behind every coder that is running)
   if (n >= 2) {
@@ -140,6 +140,7 @@ static int materialize_frames(scalce_batch *b, int m) {
 
 extern "C" int scalce_batch_output(const scalce_batch *b, int which, int mate, const void **d_ptr, uint64_t *nbytes) {
   if (!b || !d_ptr || !nbytes || mate < 0 || mate >= b->nm) return SCALCE_ERR_ARG;
+  const scalce_workspace &w = *b->ws;
   const u32 nb1 = (u32)b->ctx->A.n_buckets + 1;
   if (b->nq && (which == SCALCE_OUT_QUAL || which == SCALCE_OUT_TABLE || which == SCALCE_OUT_FREQ4 || which == SCALCE_OUT_QSTREAM ||
                 which == SCALCE_OUT_QINPUT)) {  // -Q / -f: nothing quality-side exists
@@ -160,24 +161,24 @@ extern "C" int scalce_batch_output(const scalce_batch *b, int which, int mate, c
       break;
     case SCALCE_OUT_TABLE: *d_ptr = b->table[mate].p; *nbytes = sizeof(u32) * 512000; break;
     case SCALCE_OUT_FREQ4: *d_ptr = b->freq4[mate].p; *nbytes = sizeof(u64) * 512000; break;
-    case SCALCE_OUT_TOKENS: *d_ptr = b->tokens.p; *nbytes = sizeof(int32_t) * 2 * b->N; break;
+    case SCALCE_OUT_TOKENS: *d_ptr = w.tokens.p; *nbytes = sizeof(int32_t) * 2 * b->N; break;
     case SCALCE_OUT_PERM: *d_ptr = b->perm; *nbytes = sizeof(u32) * b->N; break;
     case SCALCE_OUT_QSTREAM: *d_ptr = b->qs(mate).p; *nbytes = b->N * (u64)b->L[mate]; break;
-    case SCALCE_OUT_BUCKET_COUNTS: *d_ptr = b->tok_open ? b->counts.p : b->counts_total.p; *nbytes = sizeof(u64) * nb1; break;
+    case SCALCE_OUT_BUCKET_COUNTS: *d_ptr = b->tok_open ? w.counts.p : b->counts_total.p; *nbytes = sizeof(u64) * nb1; break;
     case SCALCE_OUT_QINPUT:
       *nbytes = b->N * (u64)b->L[mate];
-      if (b->qstride[mate] == (u32)b->L[mate]) { *d_ptr = b->q[mate].p; break; }
+      if (b->qstride[mate] == (u32)b->L[mate]) { *d_ptr = w.q[mate].p; break; }
       {  // fused rows: the q' of every row as one array, put together on request
         scalce_batch *mb = const_cast<scalce_batch *>(b);
         if (hipSetDevice(b->ctx->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return SCALCE_ERR_HIP;
         int rc = ensure(mb, mb->q_compact, (size_t)*nbytes + 64);
         if (rc) return rc;
-        if (b->N) LAUNCH(compact_q_k, 4096, 256, 0, (hipStream_t) nullptr, b->N, b->q[mate].as<u8>(), b->qstride[mate], (u32)b->L[mate], mb->q_compact.as<u8>());
+        if (b->N) LAUNCH(compact_q_k, 4096, 256, 0, (hipStream_t) nullptr, b->N, w.q[mate].as<u8>(), b->qstride[mate], (u32)b->L[mate], mb->q_compact.as<u8>());
         if (hipDeviceSynchronize() != hipSuccess) return SCALCE_ERR_HIP;
         *d_ptr = mb->q_compact.p;
       }
       break;
-    case SCALCE_OUT_NAMELEN: *d_ptr = b->namelen.p; *nbytes = b->N; break;
+    case SCALCE_OUT_NAMELEN: *d_ptr = w.namelen.p; *nbytes = b->N; break;
     case SCALCE_OUT_BUCKET_NAME_BYTES: *d_ptr = b->bucket_name_bytes.p; *nbytes = b->bucket_name_bytes.p ? sizeof(u64) * nb1 : 0; break;
     default: return SCALCE_ERR_ARG;
   }

@@ -23,15 +23,15 @@ static int ac_prepare(AcJob &j, hipStream_t s, bool framed_output = true, bool f
   u32 *table = b->table[m].as<u32>();
   ENSURE(b, b->ac_tab[m], sizeof(uint4) * 512000);
   ENSURE(b, b->ac_cum[m], sizeof(u32) * 6400 * 81);
-  // one read-back for both: the largest context total (d_small64[12 + 4 m], low word) and the table's own coding cost
-  u64 *tinfo = b->d_small64 + 12 + 4 * m;
-  HIP_TRY(c, hipMemsetAsync(tinfo, 0, 3 * sizeof(u64), s));
+  // one read-back for both: the largest context total and the table's own coding cost
+  BatchScratch::TableInfo *tinfo = &b->d_scr->tinfo[m];
+  HIP_TRY(c, hipMemsetAsync(tinfo, 0, sizeof *tinfo, s));
   ENSURE(b, b->ac_tab8[m], sizeof(u64) * (6400 * 81 + 2));
-  LAUNCH(ac_table_k, cdiv(6400, 64), 64, 0, s, table, b->ac_tab[m].as<uint4>(), b->ac_cum[m].as<u32>(), reinterpret_cast<u32 *>(tinfo), b->ac_tab8[m].as<u64>(),
-         reinterpret_cast<unsigned long long *>(tinfo + 1));
-  u64 th[3] = {0, 0, 0};
-  { int rc = read_u64(b, tinfo, th, 3, s); if (rc) return rc; }
-  const u32 max_total = (u32)th[0];
+  LAUNCH(ac_table_k, cdiv(6400, 64), 64, 0, s, table, b->ac_tab[m].as<uint4>(), b->ac_cum[m].as<u32>(), reinterpret_cast<u32 *>(&tinfo->max_total), b->ac_tab8[m].as<u64>(),
+         tinfo->cost);
+  BatchScratch::TableInfo th = {0, {0, 0}};
+  { int rc = read_words(b, tinfo, &th, sizeof th / 4, s); if (rc) return rc; }
+  const u32 max_total = (u32)th.max_total;
   // above 2^30 a symbol's interval can collapse in the reference's 32-bit coder; only the general step
   // follows it there bit for bit
   j.general = max_total > (1u << 30) || getenv("SCALCE_AC_GENERAL") != nullptr;
@@ -41,8 +41,8 @@ static int ac_prepare(AcJob &j, hipStream_t s, bool framed_output = true, bool f
     u64 stride = AC_STRIDE;
     const char *scale_env = getenv("SCALCE_AC_STRIDE_SCALE");  // test hook: "0" = the reference's full stride, else a factor (too small on purpose)
     const bool full = scale_env && atof(scale_env) == 0.0;
-    if (!full && !full_stride && th[2]) {
-      double bytes_per_symbol = (double)th[1] / 256.0 / 8.0 / (double)th[2];
+    if (!full && !full_stride && th.cost[1]) {
+      double bytes_per_symbol = (double)th.cost[0] / 256.0 / 8.0 / (double)th.cost[1];
       if (scale_env) bytes_per_symbol *= atof(scale_env);
       const u64 est = (u64)((double)AC_BLOCK_SYMS * bytes_per_symbol * 1.08) + 65536;
       stride = std::min<u64>(AC_STRIDE, (est + 15) & ~15ull);
@@ -172,7 +172,7 @@ static int ac_launch(AcJob *jobs, int njobs, AcLaunchKind kind, hipStream_t s, h
   a.helper_prio = 0u;
   a.test_poison = getenv("SCALCE_AC_TEST_POISON") ? (u32)atoi(getenv("SCALCE_AC_TEST_POISON")) : 0u;  // test hook
   a.inplace_shift = getenv("SCALCE_AC_INPLACE_TEST") ? 2u : 0u;  // test hook: a block coded in place catches up with its input
-  a.simd_load = c->d_simd_load;
+  a.simd_load = c->d_simd_load.as<u32>();
   if (const char *e = getenv("SCALCE_AC_SLOW_THRESHOLD")) a.slow_threshold = (u32)atoi(e);  // test hook
   auto join = [&]() -> int {  // `s` continues behind everything enqueued on `ps` so far
     if (ps == s) return SCALCE_OK;
@@ -282,7 +282,7 @@ static int ac_frame(AcJob &j, hipStream_t s) {
   b->frame_virtual[m] = 0;
   if (!j.nblk) return SCALCE_OK;
   exclusive_scan<u64>(AcFrameLen{b->ac_sizes[m].as<u32>()}, j.nblk, StoreTo<u64>{b->ac_off[m].as<u64>()}, b->ac_scan.as<u64>(),
-                      b->d_small64 + 8 + m, s);
+                      &b->d_scr->frame_bytes[m], s);
   if (b->frame_on_demand) {  // the layout is all there is for now
     b->frame_virtual[m] = j.nblk;
     b->ent_pending[m] = j.nblk;
@@ -293,7 +293,7 @@ static int ac_frame(AcJob &j, hipStream_t s) {
     // of a capacity that is little more than half used is a shard less in flight): the size comes back first -- the coder has
     // finished, this is a wait of microseconds -- and the buffer grows when a shard codes worse than any before it
     u64 total = 0;
-    { int rc = read_u64(b, b->d_small64 + 8 + m, &total, 1, s); if (rc) return rc; }
+    { int rc = read_u64(b, &b->d_scr->frame_bytes[m], &total, 1, s); if (rc) return rc; }
     if (b->out_qual[m].cap < total + 64) ENSURE(b, b->out_qual[m], (size_t)(total + total / 16) + (32u << 20));
   }
   LAUNCH(ac_frame_k, dim3(cdiv(b->ac_stride[m], 16 * 256), j.nblk), 256, 0, s, b->ac_base[m], b->ac_stride[m],
@@ -391,7 +391,7 @@ static int entropy_collect(scalce_batch *b, hipStream_t s) {
       b->frame_off_host[m].resize(b->frame_virtual[m]);
       HIP_TRY(b->ctx, hipMemcpyAsync(b->frame_off_host[m].data(), b->ac_off[m].p, sizeof(u64) * b->frame_virtual[m], hipMemcpyDeviceToHost, s));
     }
-    { int rc = read_u64(b, b->d_small64 + 8 + m, &total, 1, s); if (rc) return rc; }
+    { int rc = read_u64(b, &b->d_scr->frame_bytes[m], &total, 1, s); if (rc) return rc; }
     b->out_qual_bytes[m] = total;
     b->k_out_bytes += total - 4ull * b->ent_pending[m];
     b->ent_pending[m] = 0;
@@ -453,9 +453,9 @@ static int entropy_windowed(scalce_batch *b, const uint32_t *d_table_override, h
     for (int i = 0; i < nj; i++) {
       const int m = jobs[i].m;
       exclusive_scan<u64>(AcFrameLen{b->ac_sizes[m].as<u32>()}, jobs[i].nblk, StoreTo<u64>{b->ac_off[m].as<u64>()}, b->ac_scan.as<u64>(),
-                          b->d_small64 + 8 + m, s);
+                          &b->d_scr->frame_bytes[m], s);
       u64 total = 0;
-      if ((rc = read_u64(b, b->d_small64 + 8 + m, &total, 1, s))) return rc;
+      if ((rc = read_u64(b, &b->d_scr->frame_bytes[m], &total, 1, s))) return rc;
       if (first) {  // size the framed stream from the first window's ratio; it grows if a later window codes worse
         const u64 est = (u64)((double)total / (double)jobs[i].nsym * 1.03 * (double)nsym[m]) + (64u << 20);
         ENSURE(b, b->out_qual[m], est);

@@ -1,21 +1,22 @@
 // host_ingest.inc -- part of scalce_hip.hip (one translation unit; included there, in this order): stage 0 (ingest: one piece, appended pieces, a moved window of rows) and stage 1 (quality statistics)
 // ---- stage 0: ingest ------------------------------------------------------------------------------
-// newline count of one mate's text; the per-tile bases stay in b->tile[mate] for piece_unpack
+// newline count of one mate's text; the per-tile bases stay in the workspace's tile[mate] for piece_unpack
 static int piece_count(scalce_batch *b, int mate, const u8 *d_text, u64 nbytes, hipStream_t s, u64 *nlines, u8 *last) {
+  scalce_workspace &w = *b->ws;
   scalce_ctx *c = b->ctx;
   if (((uintptr_t)d_text & 15) != 0) { set_err(c, "FASTQ text must be 16-byte aligned"); return SCALCE_ERR_ARG; }
   if (nbytes > b->max_text) b->max_text = nbytes;  // max_text only sizes the first allocations; everything below grows
   b->text_bytes[mate] = nbytes;
   const u32 ntiles = cdiv(nbytes, IDX_TILE);
-  ENSURE(b, b->tile[mate], (ntiles + 8) * sizeof(u64));
-  ENSURE(b, b->scan_ws, (scan_ws_elems(ntiles) + 64) * sizeof(u64));
-  u64 *tile = b->tile[mate].as<u64>();  // [ntiles] counts -> bases
+  ENSURE(b, w.tile[mate], (ntiles + 8) * sizeof(u64));
+  ENSURE(b, w.scan_ws, (scan_ws_elems(ntiles) + 64) * sizeof(u64));
+  u64 *tile = w.tile[mate].as<u64>();  // [ntiles] counts -> bases
   *nlines = 0;
   *last = '\n';
   if (ntiles) {
     LAUNCH(index_count_k, ntiles, IDX_THREADS, 0, s, d_text, nbytes, tile);
-    exclusive_scan<u64>(LoadAs<u64, u64>{tile}, ntiles, StoreTo<u64>{tile}, b->scan_ws.as<u64>(), b->d_small64 + 4 + mate, s);
-    HIP_TRY(c, hipMemcpyAsync(nlines, b->d_small64 + 4 + mate, sizeof(u64), hipMemcpyDeviceToHost, s));
+    exclusive_scan<u64>(LoadAs<u64, u64>{tile}, ntiles, StoreTo<u64>{tile}, w.scan_ws.as<u64>(), &b->d_scr->nlines[mate], s);
+    HIP_TRY(c, hipMemcpyAsync(nlines, &b->d_scr->nlines[mate], sizeof(u64), hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipMemcpyAsync(last, d_text + nbytes - 1, 1, hipMemcpyDeviceToHost, s));
   }
   return SCALCE_OK;
@@ -24,14 +25,15 @@ static int piece_count(scalce_batch *b, int mate, const u8 *d_text, u64 nbytes, 
 // the line index of the piece (index_write_k), built when something needs it: the indexed unpack kernels, names longer
 // than a cell, scalce_batch_text_offset (interleaved: mate 0's, which is both mates')
 static int ensure_line_index(scalce_batch *b, int mate, hipStream_t s) {
+  scalce_workspace &w = *b->ws;
   if (b->line_index_ok[mate]) return SCALCE_OK;
   const u64 nrec = b->NP, nbytes = b->text_bytes[mate];
-  if (nrec > b->piece_rows_cap || !b->line_end[mate].p) {
-    if (nrec > b->piece_rows_cap) b->piece_rows_cap = nrec;
-    ENSURE(b, b->line_end[mate], sizeof(u64) * b->unit_lines() * (b->piece_rows_cap + 1));
+  if (nrec > w.piece_rows_cap || !w.line_end[mate].p) {
+    if (nrec > w.piece_rows_cap) w.piece_rows_cap = nrec;
+    ENSURE(b, w.line_end[mate], sizeof(u64) * b->unit_lines() * (w.piece_rows_cap + 1));
   }
   const u32 ntiles = cdiv(nbytes, IDX_TILE);
-  if (ntiles) LAUNCH(index_write_k, ntiles, IDX_THREADS, 0, s, b->piece_text[mate], nbytes, b->tile[mate].as<u64>(), b->line_end[mate].as<u64>(), b->unit_lines() * nrec);
+  if (ntiles) LAUNCH(index_write_k, ntiles, IDX_THREADS, 0, s, b->piece_text[mate], nbytes, w.tile[mate].as<u64>(), w.line_end[mate].as<u64>(), b->unit_lines() * nrec);
   b->line_index_ok[mate] = true;
   return SCALCE_OK;
 }
@@ -43,6 +45,7 @@ static int ensure_line_index(scalce_batch *b, int mate, hipStream_t s) {
 // IL: called for mate 0 with the one text, which it ingests for both mates -- nrec pairs, one count, one line index.
 template <int LPR, bool QOUT, bool IL>
 static int piece_unpack_t(scalce_batch *b, int mate, const u8 *d_text, u64 nbytes, u64 nrec, hipStream_t s) {
+  scalce_workspace &w = *b->ws;
   constexpr auto k_tiles2 = &ingest_tiles2_k<LPR, QOUT, IL>;
   constexpr auto k_unpack_tiled = &unpack_tiled_k<LPR, QOUT, IL>;
   constexpr auto k_unpack = &unpack_k<LPR, QOUT, IL>;
@@ -62,29 +65,30 @@ static int piece_unpack_t(scalce_batch *b, int mate, const u8 *d_text, u64 nbyte
     UnpackArgs a;
     a.text = d_text; a.nbytes = nbytes; a.line_end = nullptr; a.nrec = nrec;
     a.L = b->L[m]; a.stride = b->stride[m]; a.mate = m; a.use_names = b->p.use_names; a.no_ac = b->p.no_ac;
-    a.packed = b->packed[m].as<u8>() + b->base * (u64)b->stride[m];
-    a.q = QOUT ? b->q[m].as<u8>() + b->base * (u64)b->qstride[m] : nullptr;
+    a.packed = w.packed[m].as<u8>() + b->base * (u64)b->stride[m];
+    a.q = QOUT ? w.q[m].as<u8>() + b->base * (u64)b->qstride[m] : nullptr;
     a.qstride = b->qstride[m];
     a.cellstride = 16;
     a.packed2 = nullptr;
-    a.namelen = b->namelen.as<u8>() + b->base;
-    a.namecell = (m == 0 && b->p.use_names) ? b->namecell.as<u8>() + 16 * b->base : nullptr;
+    a.namelen = w.namelen.as<u8>() + b->base;
+    a.namecell = (m == 0 && b->p.use_names) ? w.namecell.as<u8>() + 16 * b->base : nullptr;
     a.qlut = b->d_qlut[m]; a.err = b->d_err;
     a.q_affine = b->q_affine[m];
-    a.max_namelen = b->d_small + 16;
+    a.max_namelen = &b->d_scr->ingest.max_namelen;
     return a;
   };
   UnpackArgs a = args_of(mate);
   const bool fused_rows = b->fused && mate == 0;  // (never under IL: fused rows are single-end)
   if (fused_rows) a.packed2 = a.q + b->row_cell_off;  // a copy of the packed words lies behind the row's q'
-  u32 *slow = b->d_small + 17;
-  u64 *d_consumed = b->d_small64 + 2 + mate;  // (slots 1..3 are the emit stage's, long after this)
-  if (mate == 0) HIP_TRY(c, hipMemsetAsync(b->d_small + 16, 0, 2 * sizeof(u32), s));
+  BatchScratch::IngestFlags *d_flags = &b->d_scr->ingest;  // mate 0 finds the longest name; every text may turn out slow
+  u32 *slow = &d_flags->slow;
+  u64 *d_consumed = &b->d_scr->consumed[mate];
+  if (mate == 0) HIP_TRY(c, hipMemsetAsync(d_flags, 0, sizeof *d_flags, s));
   else HIP_TRY(c, hipMemsetAsync(slow, 0, sizeof(u32), s));
-  // one pass behind the count for the usual read lengths (ingest_tiles_k); the indexed kernels otherwise, and when a
+  // one pass behind the count for the usual read lengths (ingest_tiles2_k); the indexed kernels otherwise, and when a
   // record turns out not to fit the tile overlap
   bool fused = a.L >= 16 && a.L <= 160 && !getenv("SCALCE_INGEST_INDEXED");
-  u32 flags[2] = {0, 0};
+  BatchScratch::IngestFlags flags = {0, 0};
   for (int m = mate; m < mate + NMATE; m++) b->mm_valid[m] = false;
   if (IL) fused = fused && b->L[1] >= 16 && b->L[1] <= 160;
   if (fused) {
@@ -95,10 +99,10 @@ static int piece_unpack_t(scalce_batch *b, int mate, const u8 *d_text, u64 nbyte
       const int m = mate + i;
       IngestArgs ia;
       ia.u = i ? args_of(m) : a;
-      ia.tile_base = b->tile[mate].as<u64>();
+      ia.tile_base = w.tile[mate].as<u64>();
       ia.consumed = d_consumed;
       ia.slow = slow;
-      if (QOUT) ENSURE(b, b->tile_mm[m], sizeof(u16) * ((size_t)ntiles2 + 8));
+      if (QOUT) ENSURE(b, w.tile_mm[m], sizeof(u16) * ((size_t)ntiles2 + 8));
       Ingest2Args &g = ga[i];
       g.i = ia;
       const u64 S = (u64)ia.u.stride / 4, W = ((u64)ia.u.L + 15) / 16;
@@ -106,25 +110,25 @@ static int piece_unpack_t(scalce_batch *b, int mate, const u8 *d_text, u64 nbyte
       g.magic_w = ((1ull << 32) + W - 1) / W;
       g.step_ks = (u32)(ING_THREADS / S); g.step_rs = (u32)(ING_THREADS % S);
       g.step_kw = (u32)(ING_THREADS / W); g.step_rw = (u32)(ING_THREADS % W);
-      g.tile_minmax = QOUT ? b->tile_mm[m].as<u16>() : nullptr;
+      g.tile_minmax = QOUT ? w.tile_mm[m].as<u16>() : nullptr;
     }
     if (!IL) ga[1] = ga[0];
     LAUNCH(k_tiles2, ntiles2, ING_THREADS, 0, s, ga[0], ga[1]);
     if (QOUT)
       for (int m = mate; m < mate + NMATE; m++) {
         b->mm_valid[m] = true;
-        b->ws->tile_mm_owner[m] = b;
+        w.tile_mm_owner[m] = b;
       }
-    { int rc = read_u32(b, b->d_small + 16, flags, 2, s); if (rc) return rc; }
-    if (flags[1]) {  // a record longer than the overlap: redo the piece the indexed way
+    { int rc = read_words(b, d_flags, &flags, sizeof flags / 4, s); if (rc) return rc; }
+    if (flags.slow) {  // a record longer than the overlap: redo the piece the indexed way
       fused = false;
       for (int m = mate; m < mate + NMATE; m++) b->mm_valid[m] = false;
     }
   }
   if (!fused) {
     { int rc = ensure_line_index(b, mate, s); if (rc) return rc; }
-    a.line_end = b->line_end[mate].as<u64>();
-    if (mate == 0) HIP_TRY(c, hipMemsetAsync(b->d_small + 16, 0, sizeof(u32), s));
+    a.line_end = w.line_end[mate].as<u64>();
+    if (mate == 0) HIP_TRY(c, hipMemsetAsync(&d_flags->max_namelen, 0, sizeof(u32), s));
     u8 *row_q = a.q;
     if (fused_rows) {  // the indexed kernels write rows back to back: into an array of the piece's own, fused behind them
       ENSURE(b, b->fuse_q, (size_t)a.L * nrec + 64);
@@ -143,25 +147,25 @@ static int piece_unpack_t(scalce_batch *b, int mate, const u8 *d_text, u64 nbyte
       LAUNCH(fuse_rows_k, cdiv(nrec, 256), 256, 0, s, nrec, b->fuse_q.as<u8>(), (u32)a.L, (const u8 *)nullptr, a.packed, (u32)a.stride, b->row_pwords,
              row_q, b->qstride[0], b->row_cell_off);
     LAUNCH(k_last_end, 1, 1, 0, s, a.line_end, nrec, d_consumed);
-    { int rc = read_u32(b, b->d_small + 16, flags, 1, s); if (rc) return rc; }
+    { int rc = read_u32(b, &d_flags->max_namelen, &flags.max_namelen, 1, s); if (rc) return rc; }
   }
   { u64 v = 0; int rc = read_u64(b, d_consumed, &v, 1, s); if (rc) return rc; b->piece_consumed[mate] = v; }
   if (mate == 0 && b->p.use_names) {
     // names that do not fit their 16-byte cell go to the long-name store (input order): the text is not needed again
-    const u32 maxlen = flags[0];
+    const u32 maxlen = flags.max_namelen;
     if (maxlen > 15) {
       { int rc = ensure_line_index(b, mate, s); if (rc) return rc; }
-      if (!b->name_in_off.p) {
-        ENSURE(b, b->name_in_off, sizeof(u64) * (b->row_cap + 2));
-        HIP_TRY(c, hipMemsetAsync(b->name_in_off.p, 0, sizeof(u64) * (b->row_cap + 2), s));
+      if (!w.name_in_off.p) {
+        ENSURE(b, w.name_in_off, sizeof(u64) * (w.row_cap + 2));
+        HIP_TRY(c, hipMemsetAsync(w.name_in_off.p, 0, sizeof(u64) * (w.row_cap + 2), s));
       }
-      ENSURE(b, b->scan_ws, sizeof(u64) * (scan_ws_elems(nrec) + 64));
-      u64 *off = b->name_in_off.as<u64>() + b->base;
-      exclusive_scan<u64>(LongNameLen{a.namelen}, nrec, StoreTo<u64>{off}, b->scan_ws.as<u64>(), b->d_small64 + 6, s);
+      ENSURE(b, w.scan_ws, sizeof(u64) * (scan_ws_elems(nrec) + 64));
+      u64 *off = w.name_in_off.as<u64>() + b->base;
+      exclusive_scan<u64>(LongNameLen{a.namelen}, nrec, StoreTo<u64>{off}, w.scan_ws.as<u64>(), &b->d_scr->long_names_bytes, s);
       u64 total = 0;
-      { int rc = read_u64(b, b->d_small64 + 6, &total, 1, s); if (rc) return rc; }
-      { int rc = ensure_keep(b, b->names_in, b->names_in_used + total + 64, b->names_in_used, s); if (rc) return rc; }
-      LAUNCH(k_long_names, cdiv(nrec, 256), 256, 0, s, nrec, d_text, b->line_end[mate].as<u64>(), a.namelen, off, b->names_in_used, b->names_in.as<u8>());
+      { int rc = read_u64(b, &b->d_scr->long_names_bytes, &total, 1, s); if (rc) return rc; }
+      { int rc = ensure_keep(b, w.names_in, b->names_in_used + total + 64, b->names_in_used, s); if (rc) return rc; }
+      LAUNCH(k_long_names, cdiv(nrec, 256), 256, 0, s, nrec, d_text, w.line_end[mate].as<u64>(), a.namelen, off, b->names_in_used, w.names_in.as<u8>());
       b->names_in_used += total;
     }
   }
@@ -304,8 +308,8 @@ extern "C" int scalce_batch_rewindow(scalce_batch *b, uint64_t keep_first, uint6
   hipStream_t s = (hipStream_t)stream;
   HIP_TRY(c, hipSetDevice(c->device));
   if (b->tok_open || b->tok_done) { set_err(c, "rewindow: the rows have been tokenized already"); return SCALCE_ERR_ARG; }
-  scalce_workspace *w = b->ws;
-  const bool walked = b->walk_rows == b->N && w->walk_owner == b && b->N > 0;  // (scalce_batch_chunk_plan has been here)
+  scalce_workspace &w = *b->ws;
+  const bool walked = b->walk_rows == b->N && w.walk_owner == b && b->N > 0;  // (scalce_batch_chunk_plan has been here)
   const bool have_front = front_bytes[0] != 0;
   uint64_t used[2];
   const u64 fb[2] = {front_bytes[0], b->nm == 2 ? front_bytes[1] : 0}, bb[2] = {back_bytes[0], b->nm == 2 ? back_bytes[1] : 0};
@@ -318,19 +322,19 @@ extern "C" int scalce_batch_rewindow(scalce_batch *b, uint64_t keep_first, uint6
   if (!have_front && keep_first == 0) {
     b->N = keep_rows;  // only the back end moves: rows beyond keep_rows are dropped where they lie
     if (walked) {
-      int rc = ensure_keep(b, b->tok_bucket, sizeof(u32) * (rows_bound + 1), sizeof(u32) * keep_rows, s);
-      if (!rc) rc = ensure_keep(b, b->tok_pos, sizeof(u32) * (rows_bound + 1), sizeof(u32) * keep_rows, s);
+      int rc = ensure_keep(b, w.tok_bucket, sizeof(u32) * (rows_bound + 1), sizeof(u32) * keep_rows, s);
+      if (!rc) rc = ensure_keep(b, w.tok_pos, sizeof(u32) * (rows_bound + 1), sizeof(u32) * keep_rows, s);
       if (rc) return rc;
     }
   } else {
     // the row arrays change places with the workspace's second set; the new set is filled [front | kept | back]
-    DBuf *cur[] = {&b->packed[0], &b->packed[1], &b->q[0], &b->q[1], &b->namelen, &b->namecell, &b->name_in_off, &b->tok_bucket, &b->tok_pos};
-    DBuf *alt[] = {&w->alt_packed[0], &w->alt_packed[1], &w->alt_q[0], &w->alt_q[1], &w->alt_namelen, &w->alt_namecell, &w->alt_name_in_off,
-                   &w->alt_tok_bucket, &w->alt_tok_pos};
+    DBuf *cur[] = {&w.packed[0], &w.packed[1], &w.q[0], &w.q[1], &w.namelen, &w.namecell, &w.name_in_off, &w.tok_bucket, &w.tok_pos};
+    DBuf *alt[] = {&w.alt_packed[0], &w.alt_packed[1], &w.alt_q[0], &w.alt_q[1], &w.alt_namelen, &w.alt_namecell, &w.alt_name_in_off,
+                   &w.alt_tok_bucket, &w.alt_tok_pos};
     const size_t elem[] = {(size_t)b->stride[0], (size_t)b->stride[1], (size_t)b->qstride[0], (size_t)b->qstride[1], 1, 16, 8, 4, 4};
     for (size_t i = 0; i < sizeof(cur) / sizeof(cur[0]); i++) {
       if (!cur[i]->p) continue;             // (an array this batch does not use: mate 2, names, long names)
-      const bool tok = cur[i] == &b->tok_bucket || cur[i] == &b->tok_pos;
+      const bool tok = cur[i] == &w.tok_bucket || cur[i] == &w.tok_pos;
       ENSURE(b, *alt[i], std::max<size_t>(cur[i]->cap, tok ? sizeof(u32) * (rows_bound + 1) : 0));  // same capacity: reserve_rows sees one row_cap for both sets
       std::swap(*cur[i], *alt[i]);
     }
@@ -347,9 +351,9 @@ extern "C" int scalce_batch_rewindow(scalce_batch *b, uint64_t keep_first, uint6
     if (keep_rows) {
       for (size_t i = 0; i < sizeof(cur) / sizeof(cur[0]); i++) {
         if (!cur[i]->p || !alt[i]->p) continue;
-        const bool tok = cur[i] == &b->tok_bucket || cur[i] == &b->tok_pos;
+        const bool tok = cur[i] == &w.tok_bucket || cur[i] == &w.tok_pos;
         if (tok && !walked) continue;
-        if (cur[i] == &b->name_in_off && !names_used) continue;
+        if (cur[i] == &w.name_in_off && !names_used) continue;
         HIP_TRY(c, hipMemcpyAsync(cur[i]->as<u8>() + nfront * elem[i], alt[i]->as<u8>() + keep_first * elem[i], keep_rows * elem[i],
                                   hipMemcpyDeviceToDevice, s));
       }
@@ -365,11 +369,11 @@ extern "C" int scalce_batch_rewindow(scalce_batch *b, uint64_t keep_first, uint6
     if (used[0] != bb[0] || (b->nm == 2 && used[1] != bb[1])) { set_err(c, "rewindow: the back text is not whole records"); return SCALCE_ERR_FORMAT; }
   }
   // the first walk of the rows that came in (the kept rows keep theirs)
-  if (walked && b->tok_bucket.cap >= sizeof(u32) * (b->N + 1) && b->tok_pos.cap >= sizeof(u32) * (b->N + 1)) {
+  if (walked && w.tok_bucket.cap >= sizeof(u32) * (b->N + 1) && w.tok_pos.cap >= sizeof(u32) * (b->N + 1)) {
     launch_walk(b, WALK_FIRST, 0, nfront, 0, s);
     launch_walk(b, WALK_FIRST, nkept_end, b->N - nkept_end, 0, s);
     b->walk_rows = b->N;
-    w->walk_owner = b;
+    w.walk_owner = b;
   } else {
     b->walk_rows = 0;  // (scalce_batch_tokenize_begin walks every row)
   }
@@ -410,6 +414,7 @@ extern "C" int scalce_batch_set_fused_rows(scalce_batch *b, int on) {
 // ---- stage 1: quality statistics -------------------------------------------------------------------
 extern "C" int scalce_batch_quality(scalce_batch *b, void *stream) {
   if (!b) return SCALCE_ERR_ARG;
+  scalce_workspace &w = *b->ws;
   if (b->nq) return SCALCE_OK;  // -Q / -f: no qualities, no statistics (compress.cpp:689,697) -- nothing is launched
   hipStream_t s = (hipStream_t)stream;
   scalce_ctx *c = b->ctx;
@@ -424,15 +429,15 @@ extern "C" int scalce_batch_quality(scalce_batch *b, void *stream) {
     if (b->p.no_ac) continue;  // statistics are skipped under -A (qualities.cpp:185)
     const u64 n = b->NP * (u64)b->L[m], before = b->base * (u64)b->L[m];
     if (!n) continue;
-    const u8 *q = b->q[m].as<u8>() + b->base * (u64)b->qstride[m];  // the piece's first row
-    u32 *minmax = b->d_small + 24;  // smallest / largest symbol of the piece
+    const u8 *q = w.q[m].as<u8>() + b->base * (u64)b->qstride[m];  // the piece's first row
+    u32 *minmax = b->d_scr->minmax;  // smallest / largest symbol of the piece
     HIP_TRY(c, hipMemsetAsync(minmax, 0xFF, sizeof(u32), s));
     HIP_TRY(c, hipMemsetAsync(minmax + 1, 0, sizeof(u32), s));
     // the ingest kernel left the range of every tile of the piece's text -- in the WORKSPACE: if another batch that shares it
     // has ingested since, the ranges are that batch's, and the piece's own q' rows are scanned instead
-    if (b->mm_valid[m] && b->ws->tile_mm_owner[m] == b) {
+    if (b->mm_valid[m] && w.tile_mm_owner[m] == b) {
       const u32 nt = cdiv(b->text_bytes[m], ING_TILE);
-      LAUNCH(tile_minmax_reduce_k, cdiv(nt, 256 * 16) ? cdiv(nt, 256 * 16) : 1, 256, 0, s, b->tile_mm[m].as<u16>(), nt, minmax);
+      LAUNCH(tile_minmax_reduce_k, cdiv(nt, 256 * 16) ? cdiv(nt, 256 * 16) : 1, 256, 0, s, w.tile_mm[m].as<u16>(), nt, minmax);
     } else if (b->qstride[m] != (u32)b->L[m]) {
       // (fused rows and no tile ranges -- another batch of the workspace has ingested since: the whole alphabet, more passes)
       static const u32 whole[2] = {0u, 79u};
@@ -440,12 +445,12 @@ extern "C" int scalce_batch_quality(scalce_batch *b, void *stream) {
     } else {
       LAUNCH(sym_range_k, 2048, 256, 0, s, q, n, minmax);
     }
-    u32 *prev = b->d_small + 20 + 2 * m;  // the two symbols in front of this piece
-    LAUNCH(tri_prev_k, 1, 1, 0, s, b->q[m].as<u8>(), (u32)b->L[m], b->qstride[m], before, b->p.qprev[m][0], b->p.qprev[m][1], prev);
-    u32 *range = b->d_small + 28;  // {lo, A, all symbols inside}: span of the symbols that occur
+    u32 *prev = b->d_scr->prev[m];  // the two symbols in front of this piece
+    LAUNCH(tri_prev_k, 1, 1, 0, s, w.q[m].as<u8>(), (u32)b->L[m], b->qstride[m], before, b->p.qprev[m][0], b->p.qprev[m][1], prev);
+    u32 *range = b->d_scr->range;  // {lo, A, all symbols inside}: span of the symbols that occur
     LAUNCH(tri_range_k, 1, 1, 0, s, minmax, prev, range);
-    unsigned long long *tiles = reinterpret_cast<unsigned long long *>(b->d_small64 + 300);  // one tile counter per pass
-    HIP_TRY(c, hipMemsetAsync(tiles, 0, sizeof(u64) * TRI_MAX_PASSES, s));
+    unsigned long long *tiles = b->d_scr->tri_tiles;  // one tile counter per pass
+    HIP_TRY(c, hipMemsetAsync(tiles, 0, sizeof b->d_scr->tri_tiles, s));
     for (u32 pass = 0; pass < 3; pass++)  // pass 0, pass 1, and whatever a wide alphabet needs behind them in one launch
       LAUNCH(trigram_pass_k, b->tri_grid, TRI_THREADS, 0, s, q, n, prev, pass, pass < 2 ? pass + 1 : (u32)TRI_MAX_PASSES, range, b->freq4[m].as<u64>(), tiles,
              (u32)b->L[m], b->qstride[m]);
@@ -454,9 +459,9 @@ extern "C" int scalce_batch_quality(scalce_batch *b, void *stream) {
       const u64 carried = p1 ? (p0 ? 2 : 1) : 0;
       const u64 have = carried + before >= 2 ? 2 : carried + before;
       b->tri_expected[m] += n > 2 - have ? n - (2 - have) : 0;
-      u64 *acc = b->d_small64 + 400 + 2 * m;
-      HIP_TRY(c, hipMemsetAsync(acc, 0, 2 * sizeof(u64), s));
-      LAUNCH(tri_check_k, 64, 256, 0, s, b->freq4[m].as<u64>(), b->tri_expected[m], acc, reinterpret_cast<u32 *>(acc + 1), b->d_err);
+      BatchScratch::TriCheck *chk = &b->d_scr->tri_check[m];
+      HIP_TRY(c, hipMemsetAsync(chk, 0, sizeof *chk, s));
+      LAUNCH(tri_check_k, 64, 256, 0, s, b->freq4[m].as<u64>(), b->tri_expected[m], &chk->acc, &chk->done, b->d_err);
     }
   }
   return SCALCE_OK;

@@ -2,56 +2,57 @@
 // ---- stage 3: order ----------------------------------------------------------------------------------
 extern "C" int scalce_batch_order(scalce_batch *b, void *stream) {
   if (!b) return SCALCE_ERR_ARG;
+  scalce_workspace &w = *b->ws;
   hipStream_t s = (hipStream_t)stream;
   scalce_ctx *c = b->ctx;
   HIP_TRY(c, hipSetDevice(c->device));
   StageTimer tm(b, ST_ORDER, s);
   const u64 N = b->N;
   const u32 nb1 = (u32)c->A.n_buckets + 1;
-  ENSURE(b, b->perm_a, sizeof(u32) * (N + 2));
-  ENSURE(b, b->perm_b, sizeof(u32) * (N + 2));
-  ENSURE(b, b->hist, sizeof(u32) * radix_hist_elems(N));
-  ENSURE(b, b->scan_ws, sizeof(u64) * (scan_ws_elems(radix_hist_elems(N)) + scan_ws_elems(N + 1) + 1024));
-  b->perm = b->perm_a.as<u32>();
+  ENSURE(b, w.perm_a, sizeof(u32) * (N + 2));
+  ENSURE(b, w.perm_b, sizeof(u32) * (N + 2));
+  ENSURE(b, w.hist, sizeof(u32) * radix_hist_elems(N));
+  ENSURE(b, w.scan_ws, sizeof(u64) * (scan_ws_elems(radix_hist_elems(N)) + scan_ws_elems(N + 1) + 1024));
+  b->perm = w.perm_a.as<u32>();
   b->sorted_keys = nullptr;
   b->nchunks = 1;
   if (!N) return SCALCE_OK;
-  u32 *ws32 = b->scan_ws.as<u32>();
+  u32 *ws32 = w.scan_ws.as<u32>();
   // spill chunks: given explicitly (sharded runs: one chunk per shard) or by the -B rule
   if (!b->explicit_chunks.empty()) {
     const u32 nc = (u32)b->explicit_chunks.size();
-    ENSURE(b, b->chunk, sizeof(u32) * (N + 2));
-    ENSURE(b, b->chunk_start, sizeof(u64) * (nc + 2));
+    ENSURE(b, w.chunk, sizeof(u32) * (N + 2));
+    ENSURE(b, w.chunk_start, sizeof(u64) * (nc + 2));
     std::vector<u64> cs(b->explicit_chunks.begin(), b->explicit_chunks.end());
     cs.push_back(N);
-    HIP_TRY(c, hipMemcpyAsync(b->chunk_start.p, cs.data(), sizeof(u64) * cs.size(), hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemcpyAsync(b->d_small + 8, &nc, sizeof(u32), hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(w.chunk_start.p, cs.data(), sizeof(u64) * cs.size(), hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(&b->d_scr->nchunks, &nc, sizeof(u32), hipMemcpyHostToDevice, s));
     HIP_TRY(c, hipStreamSynchronize(s));
     b->nchunks = nc;
-    if (nc > 1) LAUNCH(chunk_assign_k, cdiv(N, 256), 256, 0, s, N, b->chunk_start.as<u64>(), b->d_small + 8, b->chunk.as<u32>());
+    if (nc > 1) LAUNCH(chunk_assign_k, cdiv(N, 256), 256, 0, s, N, w.chunk_start.as<u64>(), &b->d_scr->nchunks, w.chunk.as<u32>());
   } else if (b->p.bucket_set_size) {
-    ENSURE(b, b->S, sizeof(u64) * (N + 2));
+    ENSURE(b, w.S, sizeof(u64) * (N + 2));
     b->S_rows = ~0ull;
-    ENSURE(b, b->chunk, sizeof(u32) * (N + 2));
+    ENSURE(b, w.chunk, sizeof(u32) * (N + 2));
     const u32 max_chunks = 4096;
-    ENSURE(b, b->chunk_start, sizeof(u64) * (max_chunks + 2));
+    ENSURE(b, w.chunk_start, sizeof(u64) * (max_chunks + 2));
     // (-Q / -f: rd.sz holds no quality bytes, compress.cpp:689-702 -- the cuts fall elsewhere than with qualities)
-    RecSize rs{b->bucket.as<u32>(), c->d_bucket_level, b->namelen.as<u8>(), b->L[0], b->L[1], b->p.paired, b->p.use_names, !b->nq};
-    u64 *S = b->S.as<u64>();
-    exclusive_scan<u64>(rs, N, StoreTo<u64>{S}, b->scan_ws.as<u64>(), S + N, s);
-    LAUNCH(chunk_bounds_k, 1, 1, 0, s, S, N, (u64)b->p.bucket_set_size, max_chunks, b->chunk_start.as<u64>(), b->d_small + 8);
-    int rc = read_u32(b, b->d_small + 8, &b->nchunks, 1, s);
+    RecSize rs{w.bucket.as<u32>(), c->d_bucket_level.as<u32>(), w.namelen.as<u8>(), b->L[0], b->L[1], b->p.paired, b->p.use_names, !b->nq};
+    u64 *S = w.S.as<u64>();
+    exclusive_scan<u64>(rs, N, StoreTo<u64>{S}, w.scan_ws.as<u64>(), S + N, s);
+    LAUNCH(chunk_bounds_k, 1, 1, 0, s, S, N, (u64)b->p.bucket_set_size, max_chunks, w.chunk_start.as<u64>(), &b->d_scr->nchunks);
+    int rc = read_u32(b, &b->d_scr->nchunks, &b->nchunks, 1, s);
     if (rc) return rc;
     if (b->nchunks > 1)
-      LAUNCH(chunk_assign_k, cdiv(N, 256), 256, 0, s, N, b->chunk_start.as<u64>(), b->d_small + 8, b->chunk.as<u32>());
+      LAUNCH(chunk_assign_k, cdiv(N, 256), 256, 0, s, N, w.chunk_start.as<u64>(), &b->d_scr->nchunks, w.chunk.as<u32>());
   }
   const u32 *src = nullptr;
-  u32 *dst = b->perm_a.as<u32>(), *alt = b->perm_b.as<u32>();
+  u32 *dst = w.perm_a.as<u32>(), *alt = w.perm_b.as<u32>();
   auto flip = [&]() { src = dst; u32 *t = dst; dst = alt; alt = t; };
   const int ndig = (b->L[0] + 3) / 4;
   const bool two_phase = getenv("SCALCE_ORDER_SINGLE_PHASE") == nullptr;  // test hook: all digits in one go
   const int ndig1 = two_phase ? (ndig < PREFIX_DIGITS ? ndig : PREFIX_DIGITS) : ndig;
-  const u32 *chunk_or_null = b->nchunks > 1 ? b->chunk.as<u32>() : nullptr;
+  const u32 *chunk_or_null = b->nchunks > 1 ? w.chunk.as<u32>() : nullptr;
   int bits = 1;
   while ((1u << bits) < nb1 && bits < 31) bits++;
   int cbits = 0;
@@ -64,13 +65,13 @@ extern "C" int scalce_batch_order(scalce_batch *b, void *stream) {
   u64 *sorted_keys = nullptr;
   const u32 end_bits = (16 + PREFIX_BITS + cbits + bits <= 64) ? 16u : 0u;
   if (by_pairs) {
-    ENSURE(b, b->key_a, sizeof(u64) * (N + 2));
-    ENSURE(b, b->key_b, sizeof(u64) * (N + 2));
-    u64 *ka = b->key_a.as<u64>(), *kb = b->key_b.as<u64>();
-    LAUNCH(order_keys_k, cdiv(N, 256), 256, 0, s, (u32)N, b->bucket.as<u32>(), chunk_or_null, (u32)cbits, b->packed[0].as<u8>(),
-           b->endv.as<u16>(), b->L[0], b->stride[0], ndig1, end_bits, ka);
+    ENSURE(b, w.key_a, sizeof(u64) * (N + 2));
+    ENSURE(b, w.key_b, sizeof(u64) * (N + 2));
+    u64 *ka = w.key_a.as<u64>(), *kb = w.key_b.as<u64>();
+    LAUNCH(order_keys_k, cdiv(N, 256), 256, 0, s, (u32)N, w.bucket.as<u32>(), chunk_or_null, (u32)cbits, w.packed[0].as<u8>(),
+           w.endv.as<u16>(), b->L[0], b->stride[0], ndig1, end_bits, ka);
     for (int sh = (int)end_bits; sh < (int)end_bits + PREFIX_BITS + cbits + bits; sh += 8) {
-      radix_pass_kv(ka, src, kb, dst, (u32)N, (u32)sh, b->hist.as<u32>(), ws32, s);
+      radix_pass_kv(ka, src, kb, dst, (u32)N, (u32)sh, w.hist.as<u32>(), ws32, s);
       flip();
       u64 *t = ka; ka = kb; kb = t;
     }
@@ -82,17 +83,17 @@ extern "C" int scalce_batch_order(scalce_batch *b, void *stream) {
   } else {
     // phase 1: first ndig1 key digits (least significant first), then chunk, then bucket
     for (int d = ndig1 - 1; d >= 0; d--) {
-      radix_pass(src, dst, (u32)N, KeyDigit{b->packed[0].as<u8>(), b->endv.as<u16>(), b->L[0], b->stride[0], d}, b->hist.as<u32>(),
+      radix_pass(src, dst, (u32)N, KeyDigit{w.packed[0].as<u8>(), w.endv.as<u16>(), b->L[0], b->stride[0], d}, w.hist.as<u32>(),
                  ws32, s);
       flip();
     }
     if (b->nchunks > 1)
       for (int sh = 0; (1u << sh) < b->nchunks; sh += 8) {
-        radix_pass(src, dst, (u32)N, DigitOfArray{b->chunk.as<u32>(), sh}, b->hist.as<u32>(), ws32, s);
+        radix_pass(src, dst, (u32)N, DigitOfArray{w.chunk.as<u32>(), sh}, w.hist.as<u32>(), ws32, s);
         flip();
       }
     for (int sh = 0; sh < bits; sh += 8) {
-      radix_pass(src, dst, (u32)N, DigitOfArray{b->bucket.as<u32>(), sh}, b->hist.as<u32>(), ws32, s);
+      radix_pass(src, dst, (u32)N, DigitOfArray{w.bucket.as<u32>(), sh}, w.hist.as<u32>(), ws32, s);
       flip();
     }
   }
@@ -100,50 +101,50 @@ extern "C" int scalce_batch_order(scalce_batch *b, void *stream) {
   b->order_run_members = 0;
   if (ndig1 < ndig) {
     // phase 2: records that still tie on (bucket, chunk, prefix) are sorted on the remaining digits, run by run
-    ENSURE(b, b->run_head, N + 64);
-    ENSURE(b, b->run_hcount, sizeof(u32) * (N + 2));
-    ENSURE(b, b->run_rank, sizeof(u32) * (N + 2));
-    ENSURE(b, b->runid, sizeof(u32) * (N + 2));
-    RunArgs ra{(u32)N, perm1, b->bucket.as<u32>(), chunk_or_null, b->packed[0].as<u8>(), b->endv.as<u16>(), b->L[0], b->stride[0], ndig1};
-    u8 *head = b->run_head.as<u8>();
+    ENSURE(b, w.run_head, N + 64);
+    ENSURE(b, w.run_hcount, sizeof(u32) * (N + 2));
+    ENSURE(b, w.run_rank, sizeof(u32) * (N + 2));
+    ENSURE(b, w.runid, sizeof(u32) * (N + 2));
+    RunArgs ra{(u32)N, perm1, w.bucket.as<u32>(), chunk_or_null, w.packed[0].as<u8>(), w.endv.as<u16>(), b->L[0], b->stride[0], ndig1};
+    u8 *head = w.run_head.as<u8>();
     if (sorted_keys) LAUNCH(run_heads_keys_k, cdiv(N, 256), 256, 0, s, (u32)N, sorted_keys, end_bits, head);
     else LAUNCH(run_heads_k, cdiv(N, 256), 256, 0, s, ra, head);
-    exclusive_scan<u32>(LoadAs<u8, u32>{head}, N, StoreTo<u32>{b->run_hcount.as<u32>()}, ws32, (u32 *)nullptr, s);
-    exclusive_scan<u32>(RunMember{head, (u32)N}, N, StoreTo<u32>{b->run_rank.as<u32>()}, ws32, b->d_small + 9, s);
+    exclusive_scan<u32>(LoadAs<u8, u32>{head}, N, StoreTo<u32>{w.run_hcount.as<u32>()}, ws32, (u32 *)nullptr, s);
+    exclusive_scan<u32>(RunMember{head, (u32)N}, N, StoreTo<u32>{w.run_rank.as<u32>()}, ws32, &b->d_scr->run_members, s);
     u32 M = 0;
-    { int rc = read_u32(b, b->d_small + 9, &M, 1, s); if (rc) return rc; }
+    { int rc = read_u32(b, &b->d_scr->run_members, &M, 1, s); if (rc) return rc; }
     b->order_run_members = M;
     if (M) {
-      ENSURE(b, b->run_items_a, sizeof(u32) * (M + 2));
-      ENSURE(b, b->run_items_b, sizeof(u32) * (M + 2));
-      ENSURE(b, b->run_pos, sizeof(u32) * (M + 2));
-      LAUNCH(run_compact_k, cdiv(N, 256), 256, 0, s, (u32)N, head, b->run_rank.as<u32>(), b->run_hcount.as<u32>(), perm1,
-             b->run_items_a.as<u32>(), b->run_pos.as<u32>(), b->runid.as<u32>());
+      ENSURE(b, w.run_items_a, sizeof(u32) * (M + 2));
+      ENSURE(b, w.run_items_b, sizeof(u32) * (M + 2));
+      ENSURE(b, w.run_pos, sizeof(u32) * (M + 2));
+      LAUNCH(run_compact_k, cdiv(N, 256), 256, 0, s, (u32)N, head, w.run_rank.as<u32>(), w.run_hcount.as<u32>(), perm1,
+             w.run_items_a.as<u32>(), w.run_pos.as<u32>(), w.runid.as<u32>());
       bool small_done = false;
       {  // runs of up to 32 members are sorted where they stand (run_small_sort_k)
-        u32 *any_large = b->d_small + 10;
+        u32 *any_large = &b->d_scr->any_large;
         HIP_TRY(c, hipMemsetAsync(any_large, 0, sizeof(u32), s));
-        LAUNCH(run_small_sort_k, cdiv(M, 256), 256, 0, s, M, b->run_pos.as<u32>(), head, (u32)N, perm1, sorted_keys, end_bits,
-               b->packed[0].as<u8>(), b->endv.as<u16>(), b->L[0], b->stride[0], ndig1, ndig, any_large);
+        LAUNCH(run_small_sort_k, cdiv(M, 256), 256, 0, s, M, w.run_pos.as<u32>(), head, (u32)N, perm1, sorted_keys, end_bits,
+               w.packed[0].as<u8>(), w.endv.as<u16>(), b->L[0], b->stride[0], ndig1, ndig, any_large);
         u32 large = 0;
         { int rc = read_u32(b, any_large, &large, 1, s); if (rc) return rc; }
         small_done = large == 0;
       }
       if (!small_done) {
-      const u32 *rs = b->run_items_a.as<u32>();
-      u32 *rd = b->run_items_b.as<u32>(), *ralt = b->run_items_a.as<u32>();
+      const u32 *rs = w.run_items_a.as<u32>();
+      u32 *rd = w.run_items_b.as<u32>(), *ralt = w.run_items_a.as<u32>();
       auto rflip = [&]() { rs = rd; u32 *t = rd; rd = ralt; ralt = t; };
       for (int d = ndig - 1; d >= ndig1; d--) {
-        radix_pass(rs, rd, M, KeyDigit{b->packed[0].as<u8>(), b->endv.as<u16>(), b->L[0], b->stride[0], d}, b->hist.as<u32>(), ws32, s);
+        radix_pass(rs, rd, M, KeyDigit{w.packed[0].as<u8>(), w.endv.as<u16>(), b->L[0], b->stride[0], d}, w.hist.as<u32>(), ws32, s);
         rflip();
       }
       int rbits = 1;
       while ((1ull << rbits) <= N && rbits < 32) rbits++;  // run ids are at most N
       for (int sh = 0; sh < rbits; sh += 8) {
-        radix_pass(rs, rd, M, DigitOfArray{b->runid.as<u32>(), sh}, b->hist.as<u32>(), ws32, s);
+        radix_pass(rs, rd, M, DigitOfArray{w.runid.as<u32>(), sh}, w.hist.as<u32>(), ws32, s);
         rflip();
       }
-      LAUNCH(run_scatter_k, cdiv(M, 256), 256, 0, s, M, rs, b->run_pos.as<u32>(), perm1, sorted_keys, end_bits, b->endv.as<u16>());
+      LAUNCH(run_scatter_k, cdiv(M, 256), 256, 0, s, M, rs, w.run_pos.as<u32>(), perm1, sorted_keys, end_bits, w.endv.as<u16>());
       }
     }
   }
@@ -154,49 +155,50 @@ extern "C" int scalce_batch_order(scalce_batch *b, void *stream) {
 // ---- stage 4: emit -----------------------------------------------------------------------------------
 extern "C" int scalce_batch_emit(scalce_batch *b, void *stream) {
   if (!b) return SCALCE_ERR_ARG;
+  scalce_workspace &w = *b->ws;
   hipStream_t s = (hipStream_t)stream;
   scalce_ctx *c = b->ctx;
   HIP_TRY(c, hipSetDevice(c->device));
   StageTimer tm(b, ST_EMIT, s);
   const u64 N = b->N;
   const u32 nb1 = (u32)c->A.n_buckets + 1;
-  ENSURE(b, b->bucket_first, sizeof(u64) * (nb1 + 2));
-  ENSURE(b, b->bucket_off, sizeof(u64) * (nb1 + 2));
-  ENSURE(b, b->scan_ws, sizeof(u64) * (scan_ws_elems(nb1) + scan_ws_elems(N + 1) + 1024));
-  u64 *ws = b->scan_ws.as<u64>();
+  ENSURE(b, w.bucket_first, sizeof(u64) * (nb1 + 2));
+  ENSURE(b, w.bucket_off, sizeof(u64) * (nb1 + 2));
+  ENSURE(b, w.scan_ws, sizeof(u64) * (scan_ws_elems(nb1) + scan_ws_elems(N + 1) + 1024));
+  u64 *ws = w.scan_ws.as<u64>();
   u64 *counts = b->counts_total.as<u64>();  // reads per bucket over every piece of the batch
   if (!counts) { set_err(c, "tokenize first"); return SCALCE_ERR_ARG; }
-  exclusive_scan<u64>(LoadAs<u64, u64>{counts}, nb1, StoreTo<u64>{b->bucket_first.as<u64>()}, ws, b->d_small64 + 1, s);
-  exclusive_scan<u64>(BucketBytes{counts, c->d_bucket_level, b->L[0], b->sz_meta}, nb1, StoreTo<u64>{b->bucket_off.as<u64>()}, ws,
-                      b->d_small64 + 2, s);
+  exclusive_scan<u64>(LoadAs<u64, u64>{counts}, nb1, StoreTo<u64>{w.bucket_first.as<u64>()}, ws, &b->d_scr->emit.reads, s);
+  exclusive_scan<u64>(BucketBytes{counts, c->d_bucket_level.as<u32>(), b->L[0], b->sz_meta}, nb1, StoreTo<u64>{w.bucket_off.as<u64>()}, ws,
+                      &b->d_scr->emit.read_bytes, s);
   if (b->p.use_names) {
-    ENSURE(b, b->name_off, sizeof(u64) * (N + 2));
-    ENSURE(b, b->outlen, N + 64);
+    ENSURE(b, w.name_off, sizeof(u64) * (N + 2));
+    ENSURE(b, w.outlen, N + 64);
     // the name cells are gathered through the permutation ONCE, into output order: their first byte is the length the scan
     // wants, and emit_names_sorted_k then reads them in sequence (name_outlen_k + emit_names_k gathered twice)
     // (not in lean mode: a run sized for most of HBM has no 16 bytes per read to spare, and allocating and releasing
     //  3 GB costs more than the second gather)
-    const bool cells = b->namecell.p != nullptr && !b->lean;
+    const bool cells = w.namecell.p != nullptr && !b->lean;
     b->names_from_sorted_cells = cells;
-    if (cells) ENSURE(b, b->cell_sorted, 16 * (N + 4));
-    if (N && cells) LAUNCH(name_cells_sorted_k, cdiv(N, 256), 256, 0, s, N, b->perm, b->namecell.as<u8>(), b->cell_sorted.as<u8>(), b->outlen.as<u8>());
-    else if (N) LAUNCH(name_outlen_k, cdiv(N, 256), 256, 0, s, N, b->perm, b->namelen.as<u8>(), b->outlen.as<u8>());
-    exclusive_scan<u64>(NameLenSeq{b->outlen.as<u8>()}, N, StoreTo<u64>{b->name_off.as<u64>()}, ws, b->d_small64 + 3, s);
+    if (cells) ENSURE(b, w.cell_sorted, 16 * (N + 4));
+    if (N && cells) LAUNCH(name_cells_sorted_k, cdiv(N, 256), 256, 0, s, N, b->perm, w.namecell.as<u8>(), w.cell_sorted.as<u8>(), w.outlen.as<u8>());
+    else if (N) LAUNCH(name_outlen_k, cdiv(N, 256), 256, 0, s, N, b->perm, w.namelen.as<u8>(), w.outlen.as<u8>());
+    exclusive_scan<u64>(NameLenSeq{w.outlen.as<u8>()}, N, StoreTo<u64>{w.name_off.as<u64>()}, ws, &b->d_scr->emit.name_bytes, s);
     ENSURE(b, b->bucket_name_bytes, sizeof(u64) * (nb1 + 1));
-    LAUNCH(bucket_name_bytes_k, cdiv(nb1, 256), 256, 0, s, nb1, b->bucket_first.as<u64>(), counts, b->name_off.as<u64>(), b->d_small64 + 3, N,
+    LAUNCH(bucket_name_bytes_k, cdiv(nb1, 256), 256, 0, s, nb1, w.bucket_first.as<u64>(), counts, w.name_off.as<u64>(), &b->d_scr->emit.name_bytes, N,
            b->bucket_name_bytes.as<u64>());
   }
-  u64 h[4] = {0, 0, 0, 0};
-  { int rc = read_u64(b, b->d_small64, h, 4, s); if (rc) return rc; }
-  b->out_reads_bytes[0] = h[2];
-  b->out_names_bytes = b->p.use_names ? h[3] : 0;
-  ENSURE(b, b->out_reads[0], h[2] + 64);
+  BatchScratch::EmitTotals h = {0, 0, 0};
+  { int rc = read_words(b, &b->d_scr->emit, &h, sizeof h / 4, s); if (rc) return rc; }
+  b->out_reads_bytes[0] = h.read_bytes;
+  b->out_names_bytes = b->p.use_names ? h.name_bytes : 0;
+  ENSURE(b, b->out_reads[0], h.read_bytes + 64);
   ENSURE(b, b->out_names, b->out_names_bytes + 64);
   if (N) {
     EmitArgs a;
-    a.nrec = N; a.perm = b->perm; a.bucket = b->bucket.as<u32>(); a.end = b->endv.as<u16>(); a.packed = b->packed[0].as<u8>();
-    a.L = b->L[0]; a.stride = b->stride[0]; a.sz_meta = b->sz_meta; a.bucket_level = c->d_bucket_level;
-    a.bucket_pattern = c->d_bucket_pattern; a.bucket_first = b->bucket_first.as<u64>(); a.bucket_off = b->bucket_off.as<u64>();
+    a.nrec = N; a.perm = b->perm; a.bucket = w.bucket.as<u32>(); a.end = w.endv.as<u16>(); a.packed = w.packed[0].as<u8>();
+    a.L = b->L[0]; a.stride = b->stride[0]; a.sz_meta = b->sz_meta; a.bucket_level = c->d_bucket_level.as<u32>();
+    a.bucket_pattern = c->d_bucket_pattern.as<int32_t>(); a.bucket_first = w.bucket_first.as<u64>(); a.bucket_off = w.bucket_off.as<u64>();
     a.counts = counts; a.out = b->out_reads[0].as<u8>();
     a.keys = b->sorted_keys; a.key_bucket_shift = b->key_bucket_shift; a.key_bucket_mask = b->key_bucket_mask;
     a.key_end_bits = b->key_end_bits;
@@ -207,7 +209,7 @@ extern "C" int scalce_batch_emit(scalce_batch *b, void *stream) {
       // thread's loads in flight at once.  One random line per record instead of three (packed row + q' row for
       // gather_rows_k, each paying its own).
       ENSURE(b, b->qs(0), (size_t)b->L[0] * N + 64 + AC_INPLACE_PAD);
-      a.frow = b->q[0].as<u8>(); a.stride = (int)b->qstride[0]; a.cell_off = b->row_cell_off; a.pwords = (int)b->row_pwords;
+      a.frow = w.q[0].as<u8>(); a.stride = (int)b->qstride[0]; a.cell_off = b->row_cell_off; a.pwords = (int)b->row_pwords;
       a.packed = a.frow + b->row_cell_off;
       a.qunits = ((u32)b->L[0] + 15) / 16;
       a.qmagic = ((1ull << 32) + a.qunits - 1) / a.qunits;
@@ -221,49 +223,48 @@ extern "C" int scalce_batch_emit(scalce_batch *b, void *stream) {
     } else
     LAUNCH(emit_reads_k<false>, cdiv(N, 256), 256, 0, s, a);
     if (b->p.use_names && b->names_from_sorted_cells)
-      LAUNCH(emit_names_sorted_k, cdiv(N, 256), 256, 0, s, N, b->perm, b->cell_sorted.as<u8>(), b->name_in_off.as<u64>(),
-             b->names_in.as<u8>(), b->name_off.as<u64>(), b->out_names.as<u8>());
+      LAUNCH(emit_names_sorted_k, cdiv(N, 256), 256, 0, s, N, b->perm, w.cell_sorted.as<u8>(), w.name_in_off.as<u64>(),
+             w.names_in.as<u8>(), w.name_off.as<u64>(), b->out_names.as<u8>());
     else if (b->p.use_names)
-      LAUNCH(emit_names_k, cdiv(N, 256), 256, 0, s, N, b->perm, b->namecell.as<u8>(), b->name_in_off.as<u64>(),
-             b->names_in.as<u8>(), b->name_off.as<u64>(), b->out_names.as<u8>());
+      LAUNCH(emit_names_k, cdiv(N, 256), 256, 0, s, N, b->perm, w.namecell.as<u8>(), w.name_in_off.as<u64>(),
+             w.names_in.as<u8>(), w.name_off.as<u64>(), b->out_names.as<u8>());
     for (int m = 0; m < b->nm && !b->nq; m++) {  // (-Q / -f: no quality stream)
-      const u32 w = (u32)b->L[m];
+      const u32 width = (u32)b->L[m];
       if (m == 0 && b->fused) continue;  // (emit_reads_k<true> has done it)
-      ENSURE(b, b->qs(m), (size_t)w * N + 64 + AC_INPLACE_PAD);
-      LAUNCH(gather_rows_k, gather_grid(N, w), 256, 0, s, N, b->perm, b->q[m].as<u8>(), (u64)b->qstride[m], w, b->qs(m).as<u8>());
+      ENSURE(b, b->qs(m), (size_t)width * N + 64 + AC_INPLACE_PAD);
+      LAUNCH(gather_rows_k, gather_grid(N, width), 256, 0, s, N, b->perm, w.q[m].as<u8>(), (u64)b->qstride[m], width, b->qs(m).as<u8>());
       if (b->lean) {
         // q' in input order is dead once its reordered copy exists.  Mate 1's buffer becomes mate 2's reordered stream (an
         // allocation and a release of tens of GB each cost a good part of a second), the last one is released.
         HIP_TRY(c, hipStreamSynchronize(s));
-        if (m == 0 && b->nm == 2 && !b->qs(1).p && b->q[0].cap >= (size_t)b->L[1] * N + 64) {
-          b->qs(1) = b->q[0];
-          b->q[0] = DBuf();
+        if (m == 0 && b->nm == 2 && !b->qs(1).p && w.q[0].cap >= (size_t)b->L[1] * N + 64) {
+          b->qs(1) = std::move(w.q[0]);
         } else {
-          release(b->q[m]);
+          w.q[m].release();
         }
       }
     }
     if (b->nm == 2) {  // mate 2: bare packed reads in the same order (compress.cpp:380-383 with fR = file 4)
-      const u32 w = (u32)b->szr[1];
-      b->out_reads_bytes[1] = N * w;
-      ENSURE(b, b->out_reads[1], N * w + 64);
-      LAUNCH(gather_rows_k, gather_grid(N, w), 256, 0, s, N, b->perm, b->packed[1].as<u8>(), (u64)b->stride[1], w,
+      const u32 width = (u32)b->szr[1];
+      b->out_reads_bytes[1] = N * width;
+      ENSURE(b, b->out_reads[1], N * width + 64);
+      LAUNCH(gather_rows_k, gather_grid(N, width), 256, 0, s, N, b->perm, w.packed[1].as<u8>(), (u64)b->stride[1], width,
              b->out_reads[1].as<u8>());
     }
   } else if (b->nm == 2) b->out_reads_bytes[1] = 0;
   if (b->lean) {  // nothing behind this stage reads the rows, the tokens or the sort scratch
     HIP_TRY(c, hipStreamSynchronize(s));
-    DBuf *dead[] = {&b->packed[0], &b->packed[1], &b->namecell, &b->names_in, &b->name_in_off, &b->name_off, &b->outlen, &b->cell_sorted,
-                    &b->line_end[0], &b->line_end[1], &b->tile[0], &b->tile[1], &b->tok_bucket, &b->tok_pos, &b->tie_index,
-                    &b->tie_read, &b->tie_off, &b->tie_ncand, &b->cand_bucket, &b->cand_pos, &b->choice, &b->ev_off,
-                    &b->ev_sorted, &b->ev_tmp, &b->ev_place, &b->chosen, &b->G, &b->cand_place,
-                    &b->bucket, &b->endv, &b->tokens, &b->chunk, &b->perm_a, &b->perm_b, &b->key_a, &b->key_b, &b->hist, &b->S,
-                    &b->run_head, &b->run_hcount, &b->run_rank, &b->runid, &b->run_items_a, &b->run_items_b, &b->run_pos};
+    DBuf *dead[] = {&w.packed[0], &w.packed[1], &w.namecell, &w.names_in, &w.name_in_off, &w.name_off, &w.outlen, &w.cell_sorted,
+                    &w.line_end[0], &w.line_end[1], &w.tile[0], &w.tile[1], &w.tok_bucket, &w.tok_pos, &w.tie_index,
+                    &w.tie_read, &w.tie_off, &w.tie_ncand, &w.cand_bucket, &w.cand_pos, &w.choice, &w.ev_off,
+                    &w.ev_sorted, &w.ev_tmp, &w.ev_place, &w.chosen, &w.G, &w.cand_place,
+                    &w.bucket, &w.endv, &w.tokens, &w.chunk, &w.perm_a, &w.perm_b, &w.key_a, &w.key_b, &w.hist, &w.S,
+                    &w.run_head, &w.run_hcount, &w.run_rank, &w.runid, &w.run_items_a, &w.run_items_b, &w.run_pos};
     for (DBuf *d : dead)
-      if (d->cap >= (256u << 20)) release(*d);  // (the big ones; releasing dozens of small buffers only costs time)
+      if (d->cap >= (256u << 20)) d->release();  // (the big ones; releasing dozens of small buffers only costs time)
     b->perm = nullptr;
     b->sorted_keys = nullptr;
-    b->row_cap = 0;
+    w.row_cap = 0;
   }
   return SCALCE_OK;
 }

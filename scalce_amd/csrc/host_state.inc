@@ -1,22 +1,33 @@
 // host_state.inc -- part of scalce_hip.hip (one translation unit; included there, in this order): context, core tables on the device, grow-only buffers, the shared workspace, the batch, read-backs
-struct scalce_ctx {
+struct DBuf {  // grow-only device buffer; owns its memory (freed on the device that is current when it dies: hipSetDevice first)
+  void *p = nullptr;
+  size_t cap = 0;
+  DBuf() = default;
+  DBuf(DBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+  DBuf &operator=(DBuf &&o) noexcept { if (this != &o) { release(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; } return *this; }
+  ~DBuf() { release(); }
+  void release() { if (p) hipFree(p); p = nullptr; cap = 0; }
+  template <typename T> T *as() const { return static_cast<T *>(p); }
+};
+static_assert(!std::is_copy_constructible<DBuf>::value && !std::is_copy_assignable<DBuf>::value, "a DBuf is handed over with std::move");
+
+// the loaded table on the device (upload_tables): replaced as a whole by the next table
+struct DeviceTables {
+  DBuf d_next, d_outinfo, d_bucket_pattern, d_bucket_level;
+  DBuf d_kmer;  // the k-mer block of the k-mer walks (null under the anchor walk, which does not read it)
+  // anchor tables of tokenize_anchor_k, or null
+  DBuf d_anchor_bits, d_anchor_rank, d_child_bits;
+  DBuf d_anchor_single;  // per depth-K node: the ONE core below it (length, bucket, packed suffix), or 0 = walk
+};
+struct scalce_ctx : DeviceTables {
   int device = 0;
   std::string err;
   Automaton A;
   bool have_patterns = false;
-  uint4 *d_next = nullptr;
-  u32 *d_outinfo = nullptr;
-  int32_t *d_bucket_pattern = nullptr;
-  u32 *d_bucket_level = nullptr;
   // what the table's walk reads (WalkTables, automaton.hpp): chosen and built when the table is loaded
   int walk = SCALCE_WALK_NONE;
-  u32 *d_kmer = nullptr;      // the k-mer block of the k-mer walks (null under the anchor walk, which does not read it)
   u32 id8_first = 0;
-  u32 *d_simd_load = nullptr;  // per (XCC, SE, SH, CU, SIMD): coder waves resident there (ac_encode_k's role choice)
-  // anchor tables of tokenize_anchor_k, or null
-  u64 *d_anchor_bits = nullptr;
-  u32 *d_anchor_rank = nullptr, *d_child_bits = nullptr;
-  uint4 *d_anchor_single = nullptr;  // per depth-K node: the ONE core below it (length, bucket, packed suffix), or 0 = walk
+  DBuf d_simd_load;  // per (XCC, SE, SH, CU, SIMD): coder waves resident there (ac_encode_k's role choice)
   u32 anchor_K = 0, anchor_idK = 0;
 };
 
@@ -40,6 +51,28 @@ void scalce_set_last_error(scalce_ctx *c, const char *msg) { if (c) c->err = msg
     }                                                                                    \
   } while (0)
 
+// A launch that the runtime refuses (a grid beyond 2^32 threads, say) must not pass for a kernel that ran: HIP's "last
+// error" is overwritten by the next call that succeeds, so it is looked at right behind every launch and kept until
+// scalce_batch_finish / the next read-back reports it.
+static thread_local hipError_t g_launch_err = hipSuccess;
+static thread_local const char *g_launch_what = "";
+#define LAUNCH(kernel, grid, block, shmem, stream, ...)                                              \
+  do {                                                                                               \
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), shmem, stream, __VA_ARGS__);                 \
+    const hipError_t le_ = hipGetLastError();                                                        \
+    if (le_ != hipSuccess && g_launch_err == hipSuccess) { g_launch_err = le_; g_launch_what = #kernel; } \
+  } while (0)
+static int launch_failed(scalce_ctx *c) {
+  if (g_launch_err == hipSuccess) return SCALCE_OK;
+  set_err(c, "launch of %s failed: %s", g_launch_what, hipGetErrorString(g_launch_err));
+  g_launch_err = hipSuccess;
+  return SCALCE_ERR_HIP;
+}
+static inline u32 cdiv(u64 a, u64 b) {
+  const u64 q = (a + b - 1) / b;
+  return q > 0x7FFFFFFFull ? 0x7FFFFFFFu : (u32)q;  // callers whose grids can get there use grid-stride kernels
+}
+
 extern "C" int scalce_ctx_create(int device, scalce_ctx **out) {
   if (!out) return SCALCE_ERR_ARG;
   scalce_ctx *c = new scalce_ctx();
@@ -57,42 +90,32 @@ extern "C" int scalce_ctx_create(int device, scalce_ctx **out) {
     return SCALCE_ERR_HIP;
   }
   *out = c;
-  HIP_TRY(c, hipMalloc(&c->d_simd_load, sizeof(u32) * AC_SIMD_KEYS));
-  HIP_TRY(c, hipMemset(c->d_simd_load, 0, sizeof(u32) * AC_SIMD_KEYS));
+  HIP_TRY(c, hipMalloc(&c->d_simd_load.p, sizeof(u32) * AC_SIMD_KEYS));
+  c->d_simd_load.cap = sizeof(u32) * AC_SIMD_KEYS;
+  HIP_TRY(c, hipMemset(c->d_simd_load.p, 0, sizeof(u32) * AC_SIMD_KEYS));
   return SCALCE_OK;
 }
 
 static void free_tables(scalce_ctx *c) {
-  if (c->d_next) hipFree(c->d_next);
-  if (c->d_outinfo) hipFree(c->d_outinfo);
-  if (c->d_bucket_pattern) hipFree(c->d_bucket_pattern);
-  if (c->d_bucket_level) hipFree(c->d_bucket_level);
-  if (c->d_kmer) hipFree(c->d_kmer);
-  c->d_kmer = nullptr;
-  if (c->d_anchor_bits) hipFree(c->d_anchor_bits);
-  if (c->d_anchor_rank) hipFree(c->d_anchor_rank);
-  if (c->d_child_bits) hipFree(c->d_child_bits);
-  if (c->d_anchor_single) hipFree(c->d_anchor_single);
-  c->d_anchor_single = nullptr;
-  c->d_anchor_bits = nullptr; c->d_anchor_rank = nullptr; c->d_child_bits = nullptr; c->anchor_K = 0;
-  c->d_next = nullptr; c->d_outinfo = nullptr; c->d_bucket_pattern = nullptr; c->d_bucket_level = nullptr;
+  static_cast<DeviceTables &>(*c) = DeviceTables();
+  c->anchor_K = 0;
 }
 
 extern "C" void scalce_ctx_destroy(scalce_ctx *c) {
   if (!c) return;
-  free_tables(c);
-  if (c->d_simd_load) hipFree(c->d_simd_load);
+  hipSetDevice(c->device);  // (the tables free themselves: on their device)
   delete c;
 }
 extern "C" const char *scalce_last_error(const scalce_ctx *c) { return c ? c->err.c_str() : "null context"; }
 
-template <typename T>
-static int upload(scalce_ctx *c, T **d, const void *src, size_t bytes) {
-  HIP_TRY(c, hipMalloc(d, bytes));
-  HIP_TRY(c, hipMemcpy(*d, src, bytes, hipMemcpyHostToDevice));
+static int upload(scalce_ctx *c, DBuf &d, const void *src, size_t bytes) {
+  d.release();
+  HIP_TRY(c, hipMalloc(&d.p, bytes));
+  d.cap = bytes;
+  HIP_TRY(c, hipMemcpy(d.p, src, bytes, hipMemcpyHostToDevice));
   return SCALCE_OK;
 }
-#define UPLOAD(c, dptr, vec) do { int rc_ = upload(c, &(dptr), (vec).data(), sizeof((vec)[0]) * (vec).size()); if (rc_) return rc_; } while (0)
+#define UPLOAD(c, dptr, vec) do { int rc_ = upload(c, dptr, (vec).data(), sizeof((vec)[0]) * (vec).size()); if (rc_) return rc_; } while (0)
 // the loaded table on the device: the DFA, the bucket tables and what its walk reads (build_walk_tables)
 static int upload_tables(scalce_ctx *c) {
   free_tables(c);
@@ -184,23 +207,20 @@ extern "C" void scalce_params_default(scalce_params *p) {
 }
 
 // ------------------------------------------------------------------------------------------------
-struct DBuf {  // grow-only device buffer
-  void *p = nullptr;
-  size_t cap = 0;
-  template <typename T> T *as() const { return static_cast<T *>(p); }
-};
-
 enum { ST_INGEST = 0, ST_QUALITY, ST_TOKENIZE, ST_ORDER, ST_EMIT, ST_ENTROPY, ST_COUNT };
 
 // Device buffers of the FRONT stages (ingest .. emit): rows, tokens, tie-break events, sort scratch.  Nothing behind the
 // emit stage reads them -- the coder works on the reordered stream and writes the coded one -- so batches whose front stages
 // run one after the other on one stream can share a single set (scalce_workspace): with six shards in flight that is the
 // difference between 35 GB and 15 GB of HBM per shard (50 M reads x 100 bp).
+// The rule: everything in here is valid for a batch only until another batch of the same workspace runs the stage that writes
+// it; the *_owner fields mark the cases where a later stage checks.  (Stage code: `w.packed[m]` is the workspace's, `b->` the batch's.)
 struct scalce_workspace {
   scalce_ctx *ctx = nullptr;
   u64 row_cap = 0;           // rows the run-wide arrays hold
   u64 piece_rows_cap = 0;    // records one piece may bring (size of the line index)
-  DBuf line_end[2], tile[2], packed[2], q[2], namelen, namecell, outlen, names_in, name_in_off, prior_buf;
+  DBuf line_end[2], tile[2], packed[2], q[2], namelen, namecell, outlen;
+  DBuf names_in, name_in_off, prior_buf;  // names longer than a cell, input order
   DBuf tok_bucket, tok_pos, tie_index, tie_read, tie_off, tie_ncand, cand_bucket, cand_pos, choice;
   DBuf ev_off, ev_sorted, ev_tmp, ev_place, chosen, G, seg, dirty, cand_place, Gseg, cand_fixed;
   DBuf bucket, endv, tokens, counts, bucket_first, bucket_off, chunk, chunk_start;
@@ -214,36 +234,55 @@ struct scalce_workspace {
   DBuf qs_shared[2];                         // reordered q' stream of batches that only pass it on (scalce_batch_set_stream_scratch)
   DBuf alt_packed[2], alt_q[2], alt_namelen, alt_namecell, alt_name_in_off, alt_tok_bucket, alt_tok_pos;  // second set of row arrays (scalce_batch_rewindow)
   hipStream_t side = nullptr;                // the quality statistics beside the tie-break's sweeps (quality_beside): ONE more stream per workspace
-  void free_all() {
-    DBuf *all[] = {&line_end[0], &line_end[1], &tile[0], &tile[1], &packed[0], &packed[1], &q[0], &q[1], &namelen, &namecell, &outlen,
-                   &names_in, &name_in_off, &prior_buf, &tok_bucket, &tok_pos, &tie_index, &tie_read, &tie_off, &tie_ncand, &cand_bucket,
-                   &cand_pos, &choice, &ev_off, &ev_sorted, &ev_tmp, &ev_place, &chosen, &G, &seg, &dirty,
-                   &cand_place, &Gseg, &cand_fixed, &bucket, &endv, &tokens, &counts, &bucket_first, &bucket_off, &chunk, &chunk_start, &perm_a,
-                   &perm_b, &key_a, &key_b, &hist, &scan_ws, &S, &run_head, &run_hcount, &run_rank, &runid, &run_items_a, &run_items_b,
-                   &run_pos, &name_off, &tw_cells, &tw_cand, &tw_bits, &tw_base, &tile_mm[0], &tile_mm[1], &cell_sorted, &qs_shared[0], &qs_shared[1],
-                   &alt_packed[0], &alt_packed[1], &alt_q[0], &alt_q[1], &alt_namelen, &alt_namecell, &alt_name_in_off, &alt_tok_bucket, &alt_tok_pos};
-    for (DBuf *d : all)
-      if (d->p) { hipFree(d->p); d->p = nullptr; d->cap = 0; }
-    row_cap = piece_rows_cap = 0;
-    if (side) { hipStreamDestroy(side); side = nullptr; }
-  }
+  ~scalce_workspace() { if (side) hipStreamDestroy(side); }
+};
+
+// The counters of a batch that kernels write and the host reads back: ONE device allocation, a field per use, grouped by the
+// stage that writes it.  The host only takes addresses in it (&b->d_scr->nev, b->d_scr->tri_tiles); nothing is cleared at
+// creation, every stage presets what it needs.  What is cleared or read back together is one array or one struct (sizeof at
+// the call site), and no field is lent from one stage to another: a new counter is a new field.
+constexpr int SWEEPS_PER_LOOK = 4;  // global sweeps sent out per look at their flags (scalce_batch_tokenize_settle)
+struct BatchScratch {
+  // ---- ingest
+  u64 nlines[2];         // newlines of a mate's text (piece_count)
+  u64 consumed[2];       // per mate: text offset behind the last record taken (piece_unpack_t)
+  u64 long_names_bytes;  // what the piece adds to the long-name store
+  u64 text_offset;       // scalce_batch_text_offset
+  struct IngestFlags {   // cleared and read back as one
+    u32 max_namelen;     // longest name of the piece
+    u32 slow;            // a record did not fit the tile overlap: the piece is redone the indexed way
+  } ingest;
+  // ---- quality statistics (scalce_batch_quality).  Written on the workspace's SIDE stream while the tokenizer runs on the
+  // main one (quality_beside): nothing in this group may be lent to the tokenizer, or to anything else that can run beside it.
+  unsigned long long tri_tiles[TRI_MAX_PASSES];  // one tile counter per pass of trigram_pass_k
+  struct TriCheck { u64 acc; u32 done, pad; } tri_check[2];  // tri_check_k, per mate: cleared as one
+  u32 minmax[2];         // smallest / largest symbol of the piece
+  u32 prev[2][2];        // per mate: the two symbols in front of the piece
+  u32 range[3];          // {lo, A, all symbols inside}: span of the symbols that occur
+  // ---- tokenize
+  u64 cut_carry;         // bytes in the chunk left open behind the last cut (scalce_batch_chunk_plan)
+  u32 ncuts;             // ... and how many cuts
+  u32 ntie, ncand, nev, ntev;        // totals of the four scans that size the tie-break (scalce_batch_tokenize_begin)
+  u32 sweep_moved[SWEEPS_PER_LOOK];  // per global sweep: a decision moved
+  // ---- order
+  u32 nchunks;           // spill chunks (chunk_bounds_k or the caller's; chunk_assign_k reads it)
+  u32 run_members;       // records in the runs that phase 2 sorts
+  u32 any_large;         // a run too long for run_small_sort_k
+  // ---- emit
+  struct EmitTotals { u64 reads, read_bytes, name_bytes; } emit;  // totals of its three scans, read back in one go
+  // ---- entropy
+  u64 frame_bytes[2];    // per mate: the framed stream (ac_frame, entropy_windowed)
+  struct TableInfo {     // per mate, ac_table_k: cleared and read back as one
+    u64 max_total;       // largest context total (a u32 atomicMax on the low word)
+    unsigned long long cost[2];  // the table's own coding cost in 1/256 bit, and the symbols it counts
+  } tinfo[2];
 };
 
 struct scalce_batch {
-  scalce_workspace *ws;   // front-stage buffers: the batch's own, or shared with other batches (scalce_batch_create_shared)
+  scalce_workspace *ws;  // front-stage buffers: the batch's own, or shared with other batches (scalce_batch_create_shared)
   bool owns_ws;
-  explicit scalce_batch(scalce_workspace *w, bool owns)
-      : ws(w), owns_ws(owns), row_cap(w->row_cap), piece_rows_cap(w->piece_rows_cap), line_end(w->line_end), tile(w->tile),
-        packed(w->packed), q(w->q), namelen(w->namelen), namecell(w->namecell), outlen(w->outlen), names_in(w->names_in),
-        name_in_off(w->name_in_off), prior_buf(w->prior_buf), tok_bucket(w->tok_bucket), tok_pos(w->tok_pos), tie_index(w->tie_index),
-        tie_read(w->tie_read), tie_off(w->tie_off), tie_ncand(w->tie_ncand), cand_bucket(w->cand_bucket), cand_pos(w->cand_pos),
-        choice(w->choice), ev_off(w->ev_off), ev_sorted(w->ev_sorted), ev_tmp(w->ev_tmp),
-        ev_place(w->ev_place), chosen(w->chosen), G(w->G), seg(w->seg), dirty(w->dirty), cand_place(w->cand_place), Gseg(w->Gseg), cand_fixed(w->cand_fixed),
-        bucket(w->bucket), endv(w->endv), tokens(w->tokens), counts(w->counts), bucket_first(w->bucket_first), bucket_off(w->bucket_off),
-        chunk(w->chunk), chunk_start(w->chunk_start), perm_a(w->perm_a), perm_b(w->perm_b), key_a(w->key_a), key_b(w->key_b), hist(w->hist),
-        scan_ws(w->scan_ws), S(w->S), run_head(w->run_head), run_hcount(w->run_hcount), run_rank(w->run_rank), runid(w->runid),
-        run_items_a(w->run_items_a), run_items_b(w->run_items_b), run_pos(w->run_pos), name_off(w->name_off),
-        tw_cells(w->tw_cells), tw_cand(w->tw_cand), tw_bits(w->tw_bits), tw_base(w->tw_base), tile_mm(w->tile_mm), cell_sorted(w->cell_sorted) {}
+  scalce_batch(scalce_workspace *w, bool owns) : ws(w), owns_ws(owns) {}
+  ~scalce_batch();
   scalce_ctx *ctx = nullptr;
   scalce_params p;
   u64 max_reads = 0, max_text = 0;
@@ -263,8 +302,6 @@ struct scalce_batch {
   // bases, q', names and tokens are run-wide arrays indexed by row; the text of a piece is dead once it is ingested.
   u64 N = 0, base = 0, NP = 0;
   u64 tok_done = 0, tok_base = 0, tok_n = 0;  // rows tokenized so far / the rows of the tokenization in progress
-  u64 &row_cap;              // (of the workspace) rows the run-wide arrays hold
-  u64 &piece_rows_cap;       // (of the workspace) records one piece may bring
   bool appending = false;    // the pieces came through scalce_batch_append
   bool lean = false;         // release what a stage no longer needs (runs sized for most of HBM)
   u64 tri_expected[2] = {0, 0};  // trigrams counted so far (tri_check_k)
@@ -279,18 +316,11 @@ struct scalce_batch {
   bool ingested[2] = {false, false};
   // device state
   DevErr *d_err = nullptr;
-  u32 *d_small = nullptr;    // scratch counters: [0..15]
-  u64 *d_small64 = nullptr;
+  BatchScratch *d_scr = nullptr;  // the counters the stages read back (device memory: the host only takes addresses in it)
   u32 *h_pub = nullptr, *h_pub_dev = nullptr;  // a page of fine-grained host memory the read-backs are published into (read_words)
   u32 pub_seq = 0;
   u8 *d_qlut[2] = {nullptr, nullptr};
   int q_affine[2] = {-1, -1};  // the quality map is q - offset for every character: no table lookups in the ingest kernel
-  // front-stage buffers (of the workspace)
-  DBuf (&line_end)[2], (&tile)[2], (&packed)[2], (&q)[2], &namelen, &namecell, &outlen;
-  DBuf &names_in, &name_in_off, &prior_buf;  // names longer than a cell, input order
-  DBuf &tok_bucket, &tok_pos, &tie_index, &tie_read, &tie_off, &tie_ncand, &cand_bucket, &cand_pos, &choice;
-  DBuf &ev_off, &ev_sorted, &ev_tmp, &ev_place, &chosen, &G, &seg, &dirty, &cand_place, &Gseg, &cand_fixed;
-  DBuf &bucket, &endv, &tokens, &counts, &bucket_first, &bucket_off, &chunk, &chunk_start;
   // what the coder and the caller read behind the emit stage: the batch's own
   DBuf freq4[2], table[2], qs_own[2], counts_total, bucket_name_bytes, ac_scan;
   // The reordered q' stream: the batch's own (the coder reads it long after the emit stage), or -- scalce_batch_set_stream_scratch,
@@ -301,12 +331,7 @@ struct scalce_batch {
   const DBuf &qs(int m) const { return qs_in_ws ? ws->qs_shared[m] : qs_own[m]; }
   const u64 *sorted_keys = nullptr;  // phase-1 keys in output order (order stage), consumed by the emit stage
   u32 key_end_bits = 0, key_bucket_shift = 0, key_bucket_mask = 0;
-  DBuf &perm_a, &perm_b, &key_a, &key_b, &hist, &scan_ws, &S, &run_head, &run_hcount, &run_rank, &runid, &run_items_a, &run_items_b, &run_pos;
-  DBuf &name_off;
-  DBuf &tw_cells, &tw_cand, &tw_bits, &tw_base;
-  DBuf (&tile_mm)[2];
-  DBuf &cell_sorted;
-  bool mm_valid[2] = {false, false};  // tile_mm[m] holds the symbol ranges of the piece ingested last
+  bool mm_valid[2] = {false, false};  // the workspace's tile_mm[m] holds the symbol ranges of the piece ingested last
   bool names_from_sorted_cells = false;
   u32 order_run_members = 0;
   DBuf out_reads[2], out_names, ac_tab[2], ac_tab8[2], ac_cum[2], ac_blocks[2], ac_sizes[2], ac_off[2], ac_desc, out_qual[2];
@@ -350,7 +375,7 @@ struct scalce_batch {
   // with ONE random line (emit_reads_k<true>).  Otherwise qstride[m] = L[m]: rows back to back.
   bool fused = false;
   u32 qstride[2] = {0, 0}, row_cell_off = 0, row_pwords = 0;
-  DBuf q_compact, fuse_q, fuse_cells;  // SCALCE_OUT_QINPUT of fused rows on request; classic arrays of a piece the indexed kernels took
+  DBuf q_compact, fuse_q;  // SCALCE_OUT_QINPUT of fused rows on request; classic arrays of a piece the indexed kernels took
   u64 ac_stride[2] = {0, 0};
   // Coding in place (scalce_batch_set_code_in_place): the coder's output goes over the symbols it has consumed -- block k's bytes
   // begin where block k's symbols began, ac_base = the reordered stream itself, ac_stride = 10 MiB -- and the batch holds no
@@ -379,8 +404,7 @@ static int ensure(scalce_batch *b, DBuf &d, size_t bytes) {
   //  names the ones that still happen after the warm-up)
   static const bool dbg = getenv("SCALCE_TRACE") != nullptr;
   if (dbg) fprintf(stderr, "scalce: batch %p grows a buffer from %zu to %zu bytes\n", (void *)b, d.cap, bytes);
-  if (d.p) hipFree(d.p);
-  d.p = nullptr; d.cap = 0;
+  d.release();
   bytes = (bytes + 255) & ~size_t(255);
   hipError_t e = hipMalloc(&d.p, bytes);
   if (e != hipSuccess) {
@@ -415,33 +439,15 @@ static int ensure_keep(scalce_batch *b, DBuf &d, size_t bytes, size_t used, hipS
   d.cap = want;
   return SCALCE_OK;
 }
-static void release(DBuf &d) {
-  if (d.p) hipFree(d.p);
-  d.p = nullptr;
-  d.cap = 0;
-}
-
-static void free_all(scalce_batch *b) {
-  DBuf *all[] = {&b->freq4[0], &b->freq4[1], &b->table[0], &b->table[1], &b->qs_own[0], &b->qs_own[1], &b->counts_total, &b->bucket_name_bytes,
-                 &b->ac_scan, &b->out_reads[0], &b->out_reads[1], &b->out_names, &b->ac_tab[0], &b->ac_cum[0], &b->ac_blocks[0],
-                 &b->ac_sizes[0], &b->ac_off[0], &b->ac_tab[1], &b->ac_cum[1], &b->ac_blocks[1], &b->ac_sizes[1], &b->ac_off[1],
-                 &b->ac_desc, &b->out_qual[0], &b->out_qual[1], &b->ac_tab8[0], &b->ac_tab8[1], &b->q_compact, &b->fuse_q, &b->fuse_cells,
-                 &b->ac_log[0], &b->ac_log[1]};
-  for (DBuf *d : all)
-    if (d->p) { hipFree(d->p); d->p = nullptr; d->cap = 0; }
-  if (b->owns_ws) { b->ws->free_all(); delete b->ws; }
-  if (b->d_err) hipFree(b->d_err);
-  if (b->d_small) hipFree(b->d_small);
-  if (b->d_small64) hipFree(b->d_small64);
-  if (b->h_pub) hipHostFree(b->h_pub);
-  for (int m = 0; m < 2; m++) if (b->d_qlut[m]) hipFree(b->d_qlut[m]);
-  if (b->ac_desc_host) hipHostFree(b->ac_desc_host);
-  if (b->ev_fork) hipEventDestroy(b->ev_fork);
-  if (b->ev_side) hipEventDestroy(b->ev_side);
-  if (b->ev0) hipEventDestroy(b->ev0);
-  if (b->ev1) hipEventDestroy(b->ev1);
-  if (b->ev_group) hipEventDestroy(b->ev_group);
-  for (auto &pr : b->kev) { hipEventDestroy(pr.first); hipEventDestroy(pr.second); }
+scalce_batch::~scalce_batch() {  // (the DBufs free themselves)
+  if (owns_ws) delete ws;
+  if (d_err) hipFree(d_err);
+  if (d_scr) hipFree(d_scr);
+  if (h_pub) hipHostFree(h_pub);
+  for (int m = 0; m < 2; m++) if (d_qlut[m]) hipFree(d_qlut[m]);
+  if (ac_desc_host) hipHostFree(ac_desc_host);
+  for (hipEvent_t e : {ev_fork, ev_side, ev0, ev1, ev_group}) if (e) hipEventDestroy(e);
+  for (auto &pr : kev) { hipEventDestroy(pr.first); hipEventDestroy(pr.second); }
 }
 
 static inline int sz_read(int l) { return (l + 3) / 4; }
@@ -450,21 +456,22 @@ constexpr size_t AC_INPLACE_PAD = 65536;
 
 // run-wide arrays indexed by row: room for `rows` of them, the first `used` rows kept
 static int reserve_rows(scalce_batch *b, u64 rows, u64 used, hipStream_t s) {
-  if (rows <= b->row_cap) return SCALCE_OK;
+  scalce_workspace &w = *b->ws;
+  if (rows <= w.row_cap) return SCALCE_OK;
   if (rows >= (1ull << 32) - 64) { set_err(b->ctx, "a batch holds fewer than 2^32 reads"); return SCALCE_ERR_CAPACITY; }
-  if (b->row_cap && rows < b->row_cap + b->row_cap / 4) rows = b->row_cap + b->row_cap / 4;  // grow in steps
+  if (w.row_cap && rows < w.row_cap + w.row_cap / 4) rows = w.row_cap + w.row_cap / 4;  // grow in steps
   int rc;
   for (int m = 0; m < b->nm; m++) {
-    if ((rc = ensure_keep(b, b->packed[m], (size_t)b->stride[m] * rows + 64, (size_t)b->stride[m] * used, s))) return rc;
-    if (!b->nq && (rc = ensure_keep(b, b->q[m], (size_t)b->qstride[m] * rows + 64, (size_t)b->qstride[m] * used, s))) return rc;
+    if ((rc = ensure_keep(b, w.packed[m], (size_t)b->stride[m] * rows + 64, (size_t)b->stride[m] * used, s))) return rc;
+    if (!b->nq && (rc = ensure_keep(b, w.q[m], (size_t)b->qstride[m] * rows + 64, (size_t)b->qstride[m] * used, s))) return rc;
   }
-  if ((rc = ensure_keep(b, b->namelen, rows + 64, used, s))) return rc;
-  if (b->p.use_names && (rc = ensure_keep(b, b->namecell, 16 * (rows + 8), 16 * used, s))) return rc;
-  if (b->name_in_off.p && (rc = ensure_keep(b, b->name_in_off, sizeof(u64) * (rows + 2), sizeof(u64) * used, s))) return rc;
-  if ((rc = ensure_keep(b, b->bucket, sizeof(u32) * (rows + 1), sizeof(u32) * used, s))) return rc;
-  if ((rc = ensure_keep(b, b->endv, sizeof(u16) * (rows + 1), sizeof(u16) * used, s))) return rc;
-  if ((rc = ensure_keep(b, b->tokens, sizeof(int32_t) * 2 * (rows + 1), sizeof(int32_t) * 2 * used, s))) return rc;
-  b->row_cap = rows;
+  if ((rc = ensure_keep(b, w.namelen, rows + 64, used, s))) return rc;
+  if (b->p.use_names && (rc = ensure_keep(b, w.namecell, 16 * (rows + 8), 16 * used, s))) return rc;
+  if (w.name_in_off.p && (rc = ensure_keep(b, w.name_in_off, sizeof(u64) * (rows + 2), sizeof(u64) * used, s))) return rc;
+  if ((rc = ensure_keep(b, w.bucket, sizeof(u32) * (rows + 1), sizeof(u32) * used, s))) return rc;
+  if ((rc = ensure_keep(b, w.endv, sizeof(u16) * (rows + 1), sizeof(u16) * used, s))) return rc;
+  if ((rc = ensure_keep(b, w.tokens, sizeof(int32_t) * 2 * (rows + 1), sizeof(int32_t) * 2 * used, s))) return rc;
+  w.row_cap = rows;
   return SCALCE_OK;
 }
 
@@ -476,8 +483,7 @@ extern "C" int scalce_workspace_create(scalce_ctx *c, scalce_workspace **out) {
 }
 extern "C" void scalce_workspace_destroy(scalce_workspace *w) {
   if (!w) return;
-  hipSetDevice(w->ctx->device);
-  w->free_all();
+  hipSetDevice(w->ctx->device);  // (in front of every delete: the buffers free themselves on the current device)
   delete w;
 }
 
@@ -532,8 +538,7 @@ static int batch_create(scalce_ctx *c, const scalce_params *p, uint64_t max_read
   *out = b;
   HIP_TRY(c, hipMalloc(&b->d_err, sizeof(DevErr)));
   HIP_TRY(c, hipMemset(b->d_err, 0, sizeof(DevErr)));
-  HIP_TRY(c, hipMalloc(&b->d_small, 64 * sizeof(u32)));
-  HIP_TRY(c, hipMalloc(&b->d_small64, 512 * sizeof(u64)));
+  HIP_TRY(c, hipMalloc(&b->d_scr, sizeof(BatchScratch)));
   if (hipHostMalloc(reinterpret_cast<void **>(&b->h_pub), 4096, hipHostMallocCoherent | hipHostMallocMapped | hipHostMallocPortable) == hipSuccess) {
     memset(b->h_pub, 0, 4096);
     if (hipHostGetDevicePointer(reinterpret_cast<void **>(&b->h_pub_dev), b->h_pub, 0) != hipSuccess) { hipHostFree(b->h_pub); b->h_pub = nullptr; }
@@ -559,17 +564,16 @@ static int batch_create(scalce_ctx *c, const scalce_params *p, uint64_t max_read
   // a record is at least "@x", L bases, "+", L qualities and four newlines (">x", L bases and two newlines under -f): what
   // one piece of max_text bytes can bring
   const u64 per_piece = max_text / (b->lpr == 2 ? (u64)b->L[0] + 4 : 2 * (u64)b->L[0] + 7) + 2;
-  b->piece_rows_cap = per_piece < max_reads ? per_piece : max_reads;
+  w->piece_rows_cap = per_piece < max_reads ? per_piece : max_reads;
   // (the line index of a piece, 32 bytes per record, is only built when something asks for it: ensure_line_index)
   { int rc = reserve_rows(b, max_reads, 0, nullptr); if (rc) return rc; }
-  ENSURE(b, b->scan_ws, sizeof(u64) * (scan_ws_elems(4 * b->piece_rows_cap + 1024) + 4096));
+  ENSURE(b, w->scan_ws, sizeof(u64) * (scan_ws_elems(4 * w->piece_rows_cap + 1024) + 4096));
   return SCALCE_OK;
 }
 
 extern "C" void scalce_batch_destroy(scalce_batch *b) {
   if (!b) return;
   hipSetDevice(b->ctx->device);
-  free_all(b);
   delete b;
 }
 
@@ -592,7 +596,6 @@ struct StageTimer {
   }
 };
 
-static int launch_failed(scalce_ctx *c);
 // ---- read-backs ----------------------------------------------------------------------------------------------
 // A few counters per stage size the next launches: ~34 read-backs per shard.  As hipMemcpyAsync into pageable memory +
 // hipStreamSynchronize each left the stream idle for ~40 us (a blit kernel, then the runtime's wake-up): 1.4 ms of a shard's
@@ -606,7 +609,6 @@ __global__ __launch_bounds__(64) void publish_k(const u32 *src, u32 nwords, u32 
   __syncthreads();
   if (threadIdx.x == 0) __hip_atomic_store(&page[0], seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
-static int launch_failed(scalce_ctx *c);
 static int read_words(scalce_batch *b, const void *d, void *h, u32 nwords, hipStream_t s) {
   { int rc = launch_failed(b->ctx); if (rc) return rc; }
   if (b->h_pub && nwords <= PUB_WORDS) {
@@ -635,7 +637,6 @@ static int read_words(scalce_batch *b, const void *d, void *h, u32 nwords, hipSt
 static int read_u32(scalce_batch *b, const u32 *d, u32 *h, int n, hipStream_t s) { return read_words(b, d, h, (u32)n, s); }
 static int read_u64(scalce_batch *b, const u64 *d, u64 *h, int n, hipStream_t s) { return read_words(b, d, h, 2u * (u32)n, s); }
 
-static int launch_failed(scalce_ctx *c);
 static int check_device_error(scalce_batch *b, hipStream_t s) {
   { int rc = launch_failed(b->ctx); if (rc) return rc; }
   DevErr e;
@@ -651,26 +652,4 @@ static int check_device_error(scalce_batch *b, hipStream_t s) {
           (unsigned long long)e.where, e.aux);
   hipMemsetAsync(b->d_err, 0, sizeof(DevErr), s);
   return SCALCE_ERR_FORMAT;
-}
-
-// A launch that the runtime refuses (a grid beyond 2^32 threads, say) must not pass for a kernel that ran: HIP's "last
-// error" is overwritten by the next call that succeeds, so it is looked at right behind every launch and kept until
-// scalce_batch_finish / the next read-back reports it.
-static thread_local hipError_t g_launch_err = hipSuccess;
-static thread_local const char *g_launch_what = "";
-#define LAUNCH(kernel, grid, block, shmem, stream, ...)                                              \
-  do {                                                                                               \
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), shmem, stream, __VA_ARGS__);                 \
-    const hipError_t le_ = hipGetLastError();                                                        \
-    if (le_ != hipSuccess && g_launch_err == hipSuccess) { g_launch_err = le_; g_launch_what = #kernel; } \
-  } while (0)
-static int launch_failed(scalce_ctx *c) {
-  if (g_launch_err == hipSuccess) return SCALCE_OK;
-  set_err(c, "launch of %s failed: %s", g_launch_what, hipGetErrorString(g_launch_err));
-  g_launch_err = hipSuccess;
-  return SCALCE_ERR_HIP;
-}
-static inline u32 cdiv(u64 a, u64 b) {
-  const u64 q = (a + b - 1) / b;
-  return q > 0x7FFFFFFFull ? 0x7FFFFFFFu : (u32)q;  // callers whose grids can get there use grid-stride kernels
 }

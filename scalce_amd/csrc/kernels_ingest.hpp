@@ -418,9 +418,9 @@ struct IngestArgs {
   u32 *slow;                 // set when a record does not fit the overlap
 };
 
-// The same pass with the unpack spread over all lanes.  ingest_tiles_k gives a record to two threads that walk its 4-byte
-// groups one after the other: a 16 KB tile holds ~70 records of 100 bp, so 140 of the 256 threads run 25-step loops while
-// the others wait -- three quarters of the kernel's issue slots.  Here one thread per record only looks at the record's
+// ingest_tiles2_k: that pass with the unpack spread over all lanes.  Its first form gave a record to two threads that walked
+// its 4-byte groups one after the other: a 16 KB tile holds ~70 records of 100 bp, so 140 of the 256 threads ran 25-step loops
+// while the others waited -- three quarters of the kernel's issue slots.  Here one thread per record only looks at the record's
 // structure (lines, name); the bases are then packed in units of one output word (16 bases) and the qualities in units of
 // four symbols, units dealt to the lanes in order: every lane busy, consecutive lanes write consecutive words of the
 // packed rows and of the q' rows (both are back to back in memory), no staging of q' in LDS.  The smallest and largest q'
@@ -764,7 +764,7 @@ __global__ __launch_bounds__(256) void tile_minmax_reduce_k(const u16 *tile_minm
 // The 80^3 x u64 table (4 MB) does not fit LDS and hot trigrams would serialise global atomics, so the
 // table is built in slices of leading symbols p0: the slice lives in LDS, every workgroup streams the whole
 // q' array with 16-byte loads and counts only the trigrams of its slice with LDS atomics, then adds its
-// non-zero counters to the global table.  Only the range [lo, lo + A) of symbols that occur (sym_hist_k, plus
+// non-zero counters to the global table.  Only the range [lo, lo + A) of symbols that occur (sym_range_k, plus
 // the two carried-in ones) is laid out, A^2 counters per leading symbol, so a 39-symbol alphabet (q' 2..40)
 // fits 20 leading symbols into 122 KB and needs 2 streaming passes instead of the 8 that 6400-counter rows
 // of the full 80-symbol alphabet took; a full alphabet still works (4 leading symbols per pass, 20 passes).
