@@ -349,6 +349,21 @@ int scalce_selftest_ac(scalce_ctx *ctx, uint64_t ncases, uint32_t seed, int gene
 int scalce_ac_decode(scalce_ctx *ctx, const uint32_t *table_host, const uint8_t *d_blocks, uint64_t nbytes,
                      uint64_t nsymbols, uint8_t *d_symbols_out, void *stream);
 
+/* The same decoder in two steps, for a caller that decodes a stream in runs of whole frames (scalce_stream_decompress):
+ * scalce_ac_decoder_create prepares once per archive what depends on the table alone -- interval table, compact rows, the
+ * ranking of the hot symbols, the choice of kernel --; scalce_ac_decoder_launch enqueues the decode of `nframes` whole
+ * frames that begin at d_frames (any frame of the stream) into d_symbols_out: nsymbols of them, SCALCE_AC_BLOCK per frame
+ * but the last of the stream.  d_off / d_size (nframes entries each) and d_bad (one word) are device scratch of the
+ * caller: the frame walk fills them on the stream, the decoder reads them; *d_bad != 0 afterwards: the bytes end before
+ * the frames do ("(ERROR) truncated quality stream").  The launch allocates nothing and waits for nothing. */
+typedef struct scalce_ac_decoder scalce_ac_decoder;
+int scalce_ac_decoder_create(scalce_ctx *ctx, const uint32_t *table_host, void *stream, scalce_ac_decoder **out);
+void scalce_ac_decoder_destroy(scalce_ac_decoder *d);
+uint64_t scalce_ac_decoder_device_bytes(const scalce_ac_decoder *d);  /* device memory the decoder holds */
+int scalce_ac_decoder_launch(scalce_ac_decoder *d, const uint8_t *d_frames, uint64_t nbytes, uint32_t nframes,
+                             uint64_t nsymbols, uint64_t *d_off, uint32_t *d_size, uint32_t *d_bad, uint8_t *d_symbols_out,
+                             void *stream);
+
 /* Records back to FASTQ text on the device: the per-record body of decompress.cpp:240-366 -- bucket directory
  * (:262-270), un-rotation of the 2-bit bases around the core (:331-345), N where the quality is 0 (:350-351), name
  * line (:290-299; library mode "@<library>.<index>" :300-304), '+' line, qualities + phred offset.
@@ -380,6 +395,79 @@ int scalce_fastq_records_interleaved(scalce_ctx *ctx, const int read_len[2], con
                                      const int64_t phred_offset[2], const uint8_t *const names_host[2],
                                      const uint64_t names_bytes[2], const char *library, uint8_t *d_out, uint64_t out_cap,
                                      uint64_t *out_bytes, uint64_t *pair_offsets_host, void *stream);
+
+/* One WINDOW of whole records of an archive, everything on the device and relative to the window: what
+ * scalce_fastq_records does for a whole archive, enqueued for records first_record .. first_record + nrecords - 1.
+ *   d_reads      the slice of the read stream from the window's first record on; bucket headers stay inline;
+ *   d_dir        the buckets that have records in the window: `first` counts from the window's first record, `off` from
+ *                d_reads (has_buckets = 0, mate 2: one entry, core_len 0, rec_bytes = (read_len + 3) / 4);
+ *   d_qual       the window's first symbol, any byte address; NULL: two-line records;
+ *   d_names / d_name_off   the window's name records and where each starts in them (nrecords + 1 entries), or NULL / NULL:
+ *                library mode, names "<library>.<first_record + k>";
+ *   d_out        the window's text;  d_record_offsets (optional, nrecords + 1): where each record starts in it;
+ *   interleave   0, or 1 / 2 for mate 1 / 2 of an interleaved text: both mates of the window go into ONE window text,
+ *                pair_read_len and d_pair_name_off (the other mate's, nrecords + 1 entries) say where. */
+typedef struct {
+  uint64_t first, off;     /* first record of the bucket (window-relative), byte offset of that record in d_reads */
+  uint32_t core_len, rec_bytes;
+  char core[32];
+} scalce_fq_bucket;
+typedef struct {
+  const uint8_t *d_reads;
+  const scalce_fq_bucket *d_dir;
+  uint32_t nbuckets;
+  int32_t read_len, has_buckets, mate_digit;
+  uint64_t nrecords, first_record;
+  const uint8_t *d_qual;
+  int64_t phred_offset;
+  const uint8_t *d_names;
+  const uint64_t *d_name_off;
+  const char *library;
+  uint8_t *d_out;
+  uint64_t *d_record_offsets;
+  int32_t interleave, pair_read_len;
+  const uint64_t *d_pair_name_off;
+} scalce_fq_window;
+int scalce_fastq_records_window(scalce_ctx *ctx, const scalce_fq_window *w, void *stream);
+
+/* ---- archives of any size back to text: windows of whole records through the device (stream_decode.cpp) ---------------
+ * The counterpart of scalce_stream_compress.  rd[m][0..2] deliver the bytes of mate m's .scalcer, .scalcen and .scalceq
+ * files, out of their containers, headers included (scalce_read_fn's contract: any number of bytes up to cap, 0 at the
+ * end, < 0 on error); the library parses the headers.  The archive moves through the device in windows of whole records
+ * of at most window_text_bytes of FASTQ text (at least one record; two-line records count as their four-line FASTQ): device and pinned host memory are sized from the window,
+ * the read length and the core table, never from the archive.  While a window is decoded and turned into text the next
+ * one is read and comes up and the previous one goes down and is handed to wr, in order, from a thread of its own:
+ *   wr(user, mate, first_record, nrecords, text, nbytes, record_offsets)   text: pinned host memory, valid during the call;
+ *      record_offsets (nrecords + 1 entries, window-relative) only when `split` is set, else NULL; != 0 ends the session.
+ * Two mates that are not interleaved go one after the other through the same buffers (mate = 0, then 1); interleaved,
+ * both mates of a window form one text (mate = 0, records = pairs).  Nothing further is launched after an error. */
+typedef struct {
+  int32_t mates;             /* 1, or 2 (-r, -i) */
+  int32_t interleave;        /* both mates into ONE text, mate 1 then mate 2 of each pair */
+  int32_t no_qualities;      /* two-line records; the .scalceq streams are not read (rd[m][2] may be NULL) */
+  int32_t mate_digit;        /* names ending in "/x" get the mate's digit (paired archives) */
+  int32_t ignore_names;      /* -n: the name stream's mode byte is not consulted, names are <library>.<index> */
+  int32_t split;             /* != 0: hand record_offsets to wr */
+  const char *library;       /* with ignore_names: the library name to print */
+  uint64_t window_text_bytes; /* 0: SCALCE_WINDOW_TEXT_DEFAULT */
+} scalce_unpack_params;
+#define SCALCE_WINDOW_TEXT_DEFAULT (1ull << 30)
+typedef int (*scalce_write_fn)(void *user, int mate, uint64_t first_record, uint64_t nrecords, const void *text,
+                               uint64_t nbytes, const uint64_t *record_offsets);
+typedef struct {
+  uint64_t windows;            /* handed to wr */
+  uint64_t window_text_bytes;  /* the bound in force */
+  uint64_t peak_device_bytes;  /* sum of the session's own live device allocations, at its highest */
+  uint64_t pinned_host_bytes;
+  uint64_t records[2];         /* per mate (interleaved: pairs, in [0] and [1]) */
+  double total_s, setup_s, read_wait_s, decode_s, records_s, write_wait_s, write_s;
+                               /* read_wait: in rd; decode / records: device time of the kernels; write_wait: the session
+                                  waiting for a window buffer that wr still holds; write: inside wr */
+  int32_t error_mate, error_stream;  /* on failure: which stream of which mate (0 r, 1 n, 2 q), or -1 */
+  int32_t error_wants_file;    /* the message in errbuf is a predicate: put the stream's file name in front of it */
+} scalce_unpack_stats;
+int scalce_stream_decompress(scalce_ctx *ctx, const scalce_unpack_params *p, scalce_read_fn rd[2][3], void *user[2][3],
+                             scalce_write_fn wr, void *wr_user, scalce_unpack_stats *stats, char *errbuf, size_t errcap);
 
 /* ---- runs sharded over several GPUs: one process per GPU, ONE archive -----------------------------------------
  * The reference has no distributed mode; what it carries across reads is what ranks exchange (see comm.cpp).  The

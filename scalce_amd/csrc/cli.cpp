@@ -69,6 +69,7 @@ struct Options {
   bool pairs() const { return paired || interleave; }  // two mates, whichever way they come in
   uint64_t bucket_set_size = 4ull << 30;  // main.cpp:68
   std::string out, library, patterns, temp = "__temp__", patterns_bin;
+  uint64_t window = 0;                    // --window: bytes of FASTQ text per decompression window (0: the library's default)
   int gpus = 1;                           // --gpus N: one process per GPU, ONE archive (plain-text input, -c no)
   int container = 1;                      // 0 plain, 1 gzip (main.cpp:181-184 at -T 1)
   uint64_t first_file_bytes[2] = {0, 0};  // --gpus over several files written out as one: where the first file ends (the
@@ -100,6 +101,9 @@ static const char *HELP_TEXT =
     "                              the hot path itself runs on the GPU\n"
     "  -t, --temp-directory STR    accepted for compatibility (nothing is spilled)\n"
     "  -S, --split-reads INT       decompression: reads per output part\n"
+    "      --window NUM[K|M|G]     decompression: bytes of FASTQ text per window (default 1G; -Q counts a record as its FASTQ).  The archive moves through the\n"
+    "                              device in windows of whole records -- at least one record each --, so memory follows the\n"
+    "                              window, not the archive, and -o - writes each window as it arrives\n"
     "  -d, --decompress    -v, --version    -h, --help\n"
     "      --gpus N                compress on N GPUs, one process each, into ONE archive that is byte for byte the archive of\n"
     "                              one GPU (and of the reference at -T 1 with the same -B); input: one plain FASTQ file (pair), -c no\n"
@@ -1079,214 +1083,130 @@ static std::string scalce_name(std::string path, char c) {  // get_file_name, de
   if (p != std::string::npos && p + 7 < path.size()) path[p + 7] = c;
   return path;
 }
-struct Reader {
-  std::vector<uint8_t> v;
-  size_t pos = 0;
-  size_t read(void *dst, size_t n) {
-    size_t k = pos + n <= v.size() ? n : (v.size() - pos);
-    memcpy(dst, v.data() + pos, k);
-    pos += k;
-    return k;
+// one file of the archive behind scalce_read_fn: a gzip container through the parallel reader, which streams (no seek), or
+// a plain file through pread
+struct ArchiveFile {
+  std::string path;
+  bool gz = false;
+  scalce_host::ParGz z;
+  int fd = -1;
+  uint64_t off = 0;
+  void open(const std::string &p) {
+    path = p;
+    gz = is_gzip(p);  // container sniffing (decompress.cpp:99-113)
+    if (gz) { if (!z.open(p, g_threads_gz())) FAIL("Cannot read file %s\n", p.c_str()); }
+    else if ((fd = ::open(p.c_str(), O_RDONLY)) < 0) FAIL("Cannot read file %s\n", p.c_str());
+  }
+  static int64_t read(void *user, void *dst, uint64_t cap) {
+    ArchiveFile *f = static_cast<ArchiveFile *>(user);
+    if (f->gz) return f->z.read(dst, cap);
+    const ssize_t k = ::pread(f->fd, dst, (size_t)std::min<uint64_t>(cap, 1u << 30), (off_t)f->off);
+    if (k > 0) f->off += (uint64_t)k;
+    return (int64_t)k;
+  }
+  ~ArchiveFile() { if (fd >= 0) ::close(fd); }
+};
+
+// the text of the windows, as they arrive, into OUT_<m>.fastq -- or, with -S n, into a new part every n records (pairs
+// under -i; decompress.cpp:276-287), cut at the window's record offsets, across window boundaries
+struct TextSink {
+  const Options *o = nullptr;
+  struct PerMate {
+    OutFile f;
+    bool open = false;
+    int part = 0;
+    uint64_t in_part = 0, files = 0;
+    char fn[4096];
+  } pm[2];
+  void open_next(int m) {
+    PerMate &x = pm[m];
+    x.part++;
+    if (o->out == "-") snprintf(x.fn, sizeof x.fn, "-");
+    else if (o->split) snprintf(x.fn, sizeof x.fn, "%s.%d_%d.fastq", o->out.c_str(), x.part, m + 1);
+    else snprintf(x.fn, sizeof x.fn, "%s_%d.fastq", o->out.c_str(), m + 1);
+    x.f.open(x.fn, false);
+    x.open = true;
+    x.in_part = 0;
+    x.files++;
+  }
+  void close_part(int m) {
+    PerMate &x = pm[m];
+    if (x.f.f == stdout) fflush(stdout);
+    x.f.close();
+    x.open = false;
+    LOG("Created %s with %lld %s\n", x.fn, (long long)x.in_part, o->interleave ? "pairs" : "reads");
+  }
+  static int write(void *user, int m, uint64_t, uint64_t nrec, const void *text, uint64_t nbytes, const uint64_t *roff) {
+    TextSink *t = static_cast<TextSink *>(user);
+    PerMate &x = t->pm[m];
+    const uint8_t *b = static_cast<const uint8_t *>(text);
+    if (!t->o->split) {
+      if (!x.open) t->open_next(m);
+      x.f.write(b, nbytes);
+      x.in_part += nrec;
+      if (x.f.f == stdout) fflush(stdout);  // -o -: a window is out when it has arrived
+      return 0;
+    }
+    for (uint64_t k = 0; k < nrec;) {
+      if (!x.open) t->open_next(m);
+      const uint64_t take = std::min<uint64_t>((uint64_t)t->o->split - x.in_part, nrec - k);
+      x.f.write(b + roff[k], roff[k + take] - roff[k]);
+      x.in_part += take;
+      k += take;
+      if (x.in_part == (uint64_t)t->o->split) t->close_part(m);
+    }
+    return 0;
+  }
+  void finish(int m) {  // (an archive without records still gives its one empty file)
+    if (!pm[m].open && !pm[m].files) open_next(m);
+    if (pm[m].open) close_part(m);
   }
 };
 
-// records of a .scalcer payload (behind its 16-byte header): mate 1 walks the bucket headers -- [i32 core][u64 count], then
-// count records of SZ_READ(L - core length) + metadata bytes (decompress.cpp:262-270) --, mate 2 holds bare records
-static uint64_t read_stream_records(scalce_ctx *ctx, const uint8_t *p, uint64_t n, int L, bool buckets) {
-  if (!buckets) return n / (uint64_t)((L + 3) / 4);
-  const uint64_t meta = L > 255 ? 2 : 1;
-  uint64_t pos = 0, k = 0;
-  while (pos + 12 <= n) {
-    int32_t core;
-    uint64_t cnt;
-    memcpy(&core, p + pos, 4);
-    memcpy(&cnt, p + pos + 4, 8);
-    pos += 12;
-    const int cl = core == SCALCE_ROOT_CORE ? 0 : scalce_pattern_length(ctx, core);
-    if (cl < 0 || cl > L) FAIL("archive refers to core %d which the core table does not have\n", core);
-    const uint64_t rb = (uint64_t)((L - cl + 3) / 4) + meta;
-    if (cnt > (n - pos) / rb) FAIL("truncated read stream\n");
-    pos += cnt * rb;
-    k += cnt;
-  }
-  return k;
-}
-
+// One path for every archive: scalce_stream_decompress moves it through the device in windows of whole records.  The read
+// callbacks hand out the files as they are read, the write callback writes each window's text as it arrives.
 static int do_decompress(const Options &o, const std::string &path, scalce_ctx *ctx) {
   const double t0 = now();
   const int nm = o.pairs() ? 2 : 1;
   std::string base[2] = {path, path};
   if (o.pairs() && !second_file(path, base[1])) FAIL("Cannot get file name for paired end for file %s.\n", path.c_str());
-  Reader R[2], Q[2], Nn[2];
-  int32_t len[2] = {0, 0}, no_ac = 0;
-  int64_t phred[2] = {0, 0};
-  {  // the archive's files side by side (each by its own pread threads): 54 GB of a 200 M-pair archive one after the other were
-     // 10 of the run's 35 s
-    std::vector<std::thread> rd;
-    for (int m = 0; m < nm; m++) {
-      rd.emplace_back([&, m]() { R[m].v = read_whole(scalce_name(base[m], 'r')); });  // container sniffing (decompress.cpp:99-113)
-      rd.emplace_back([&, m]() { Nn[m].v = read_whole(scalce_name(base[m], 'n')); });
-      rd.emplace_back([&, m]() { Q[m].v = read_whole(scalce_name(base[m], 'q')); });
+  ArchiveFile files[2][3];
+  scalce_read_fn rd[2][3];
+  void *user[2][3];
+  static const char ext[3] = {'r', 'n', 'q'};
+  for (int m = 0; m < 2; m++)
+    for (int k = 0; k < 3; k++) {
+      rd[m][k] = m < nm ? ArchiveFile::read : nullptr;
+      user[m][k] = &files[m][k];
+      if (m < nm) files[m][k].open(scalce_name(base[m], ext[k]));
     }
-    for (auto &t : rd) t.join();
+  scalce_unpack_params p;
+  memset(&p, 0, sizeof p);
+  p.mates = nm;
+  p.interleave = o.interleave;
+  p.no_qualities = o.fasta || o.no_qual;  // -d -Q / -d -f: two-line records, whatever the .scalceq holds (decompress.cpp:159-168)
+  p.mate_digit = o.pairs();
+  p.ignore_names = !o.use_names;          // decompress.cpp:219-237
+  p.library = o.library.c_str();
+  p.split = o.split;
+  p.window_text_bytes = o.window;
+  TextSink sink;
+  sink.o = &o;
+  scalce_unpack_stats st;
+  char err[1024] = "";
+  const int rc = scalce_stream_decompress(ctx, &p, rd, user, TextSink::write, &sink, &st, err, sizeof err);
+  if (rc) {
+    // (parts already written stay where they are)
+    if (st.error_wants_file && st.error_mate >= 0 && st.error_stream >= 0)
+      FAIL("%s %s\n", st.error_stream == 0 ? base[st.error_mate].c_str() : files[st.error_mate][st.error_stream].path.c_str(), err);
+    fprintf(stderr, "%s%s\n", strncmp(err, "(ERROR)", 7) ? "(ERROR) " : "", err);
+    exit(1);
   }
-  for (int m = 0; m < nm; m++) {
-    uint8_t mg[8];
-    if (R[m].read(mg, 8) != 8 || memcmp(mg, MAGIC, 7)) FAIL("%s is not a scalce archive\n", base[m].c_str());
-    no_ac = 0;
-    if (mg[6] == '2' && mg[7] >= '2') R[m].read(&no_ac, 4);
-    Q[m].read(mg, 8);
-    Nn[m].read(mg, 8);
-    R[m].read(&len[m], 4);
-    Q[m].read(&phred[m], 8);
-  }
-  // -d -Q / -d -f: two-line records, whatever the .scalceq holds (decompress.cpp:159-168 does not read it).  Without either, an
-  // archive made with -Q / -f -- a .scalceq that ends behind its 16-byte header while the read stream holds records -- is an
-  // error: decoding qualities that are not there would misread it.
-  const bool no_qual = o.fasta || o.no_qual;
-  for (int m = 0; m < nm && !no_qual; m++)
-    if (Q[m].pos >= Q[m].v.size() && read_stream_records(ctx, R[m].v.data() + R[m].pos, R[m].v.size() - R[m].pos, len[m], m == 0))
-      FAIL("%s holds no qualities: the archive was made with -Q or -f; decompress it with -Q\n", scalce_name(base[m], 'q').c_str());
-  uint8_t names = 0;
-  std::string library = o.library;
-  if (o.use_names) {  // decompress.cpp:219-237
-    for (int m = 0; m < nm; m++) Nn[m].read(&names, 1);
-    if (!names)
-      for (int m = 0; m < nm; m++) {
-        int64_t idx;
-        Nn[m].read(&idx, 8);
-        library.assign((const char *)Nn[m].v.data() + Nn[m].pos, Nn[m].v.size() - Nn[m].pos);
-      }
-  }
-  // A mate's text comes down and is written by a thread of its own while the next mate is read, decoded and turned into text:
-  // writing 63 GB of FASTQ per mate (200 M pairs x 150 bp) is most of the run, and the two mates are two files.
-  std::vector<std::thread> writers;
-  // a file's bytes are dropped as soon as the device has them, by a thread of its own: returning the 54 GB of a 200 M-pair
-  // archive to the system took 4.5 s at the end of the run
-  std::vector<std::thread> droppers;
-  auto release = [&droppers](std::vector<uint8_t> &v) {
-    if (v.size() < (64u << 20)) return;
-    droppers.emplace_back([old = std::move(v)]() mutable { std::vector<uint8_t>().swap(old); });
-    v.clear();
-  };
-  const double t_files = now() - t0;
-  double t_decode = 0, t_records = 0;
-  std::atomic<double> t_write{0};
-  // the text of `nrec` records (pairs under -i) comes down in slices through pinned buffers while the previous slices are
-  // being written; roff: where every record (pair) starts, for -S
-  auto writer = [&o, &t_write](int m, uint64_t nrec, uint64_t text_bytes, void *d_text, std::vector<uint64_t> roff) {
-    return [&o, &t_write, m, nrec, text_bytes, d_text, roff = std::move(roff)]() {
-      const double tw = now();
-      HIPOK(hipSetDevice(0));
-      Downloader down;
-      char fn[4096];
-      int part = 1;
-      const uint64_t per = o.split ? (uint64_t)o.split : (nrec ? nrec : 1);
-      for (uint64_t k0 = 0; k0 < nrec || k0 == 0; k0 += per, part++) {  // decompress.cpp:276-287: a new file every -S reads
-        const uint64_t k1 = std::min<uint64_t>(nrec, k0 + per);
-        const uint64_t b0 = o.split ? roff[(size_t)k0] : 0, b1 = o.split ? roff[(size_t)k1] : text_bytes;
-        if (o.out == "-") snprintf(fn, sizeof fn, "-");
-        else if (o.split) snprintf(fn, sizeof fn, "%s.%d_%d.fastq", o.out.c_str(), part, m + 1);
-        else snprintf(fn, sizeof fn, "%s_%d.fastq", o.out.c_str(), m + 1);
-        OutFile fo;
-        fo.open(fn, false);
-        down.range_to_file(static_cast<const uint8_t *>(d_text) + b0, b1 - b0, fo);
-        fo.close();
-        LOG("Created %s with %lld %s\n", fn, (long long)(k1 - k0), o.interleave ? "pairs" : "reads");
-        if (!nrec) break;
-      }
-      hipFree(d_text);
-      const double dt = now() - tw;
-      for (double cur = t_write.load(); !t_write.compare_exchange_weak(cur, cur + dt);) {}
-    };
-  };
-  // -i: what the loop leaves of each mate for the one interleaved text behind it
-  void *il_q[2] = {nullptr, nullptr};
-  uint64_t il_nrec[2] = {0, 0}, il_nnames[2] = {0, 0};
-  const uint8_t *il_npay[2] = {nullptr, nullptr};
-  for (int m = 0; m < nm; m++) {
-    const int L = len[m];
-    const double ta = now();
-    // qualities: arithmetic decoder on the device, or the raw q - offset bytes of a -A archive
-    void *d_q = nullptr;
-    uint64_t total = 0;
-    if (no_qual) {  // nothing to decode: the records are counted in the read stream
-      total = read_stream_records(ctx, R[m].v.data() + R[m].pos, R[m].v.size() - R[m].pos, L, m == 0) * (uint64_t)L;
-    } else if (!no_ac) {  // table + total + blocks -> GPU decoder
-      std::vector<uint32_t> table(QTABLE_WORDS);
-      if (Q[m].read(table.data(), QTABLE_WORDS * 4) != QTABLE_WORDS * 4) FAIL("truncated quality table\n");
-      Q[m].read(&total, 8);
-      const size_t nb = Q[m].v.size() - Q[m].pos;
-      void *d_in = nullptr;
-      HIPOK(hipMalloc(&d_in, nb + 64));
-      HIPOK(hipMalloc(&d_q, total + 64));
-      HIPOK(hipMemcpy(d_in, Q[m].v.data() + Q[m].pos, nb, hipMemcpyHostToDevice));
-      release(Q[m].v);  // (gigabytes go back to the system beside the decoder, not behind the run)
-      SCOK(ctx, scalce_ac_decode(ctx, table.data(), (const uint8_t *)d_in, nb, total, (uint8_t *)d_q, nullptr));
-      hipFree(d_in);
-    } else {
-      total = Q[m].v.size() - Q[m].pos;
-      HIPOK(hipMalloc(&d_q, total + 64));
-      HIPOK(hipMemcpy(d_q, Q[m].v.data() + Q[m].pos, total, hipMemcpyHostToDevice));
-    }
-    const uint64_t nrec = L ? total / (uint64_t)L : 0;
-    // records -> FASTQ text on the device (decompress.cpp:240-366).  Mate 1's bucket directory gives the core of every
-    // record; mate-2 records carry no core (the reference lets `corlen` of the LAST mate-1 bucket leak into the mate-2
-    // pass, decompress.cpp:250,269,332 -- not reproduced).
-    const uint8_t *npay = names ? Nn[m].v.data() + Nn[m].pos : nullptr;
-    const uint64_t nbytes_names = names ? Nn[m].v.size() - Nn[m].pos : 0;
-    if (names && nbytes_names < nrec) FAIL("truncated name stream\n");
-    if (o.interleave) {  // both mates go into one text behind this loop
-      il_q[m] = d_q; il_nrec[m] = nrec; il_npay[m] = npay; il_nnames[m] = nbytes_names;
-      t_decode += now() - ta;
-      continue;
-    }
-    const uint64_t cap = (no_qual ? scalce_fasta_text_bytes : scalce_fastq_text_bytes)(L, nrec, nbytes_names, names ? nullptr : library.c_str());
-    void *d_text = nullptr;
-    HIPOK(hipMalloc(&d_text, cap + 64));
-    const double tb = now();
-    t_decode += tb - ta;
-    uint64_t text_bytes = 0;
-    std::vector<uint64_t> roff;
-    if (o.split) roff.resize((size_t)nrec + 1);
-    SCOK(ctx, scalce_fastq_records(ctx, L, m == 0, R[m].v.data() + R[m].pos, R[m].v.size() - R[m].pos, nrec, (const uint8_t *)d_q,
-                                   phred[m], npay, nbytes_names, library.c_str(), o.pairs() ? '1' + m : 0, (uint8_t *)d_text, cap,
-                                   &text_bytes, o.split ? roff.data() : nullptr, nullptr));
-    hipFree(d_q);
-    release(R[m].v);
-    release(Nn[m].v);
-    t_records += now() - tb;
-    auto write_out = writer(m, nrec, text_bytes, d_text, std::move(roff));
-    if (nm == 2 && o.out != "-") writers.emplace_back(std::move(write_out));  // (stdout takes one mate: decompress.cpp refuses -r with "-")
-    else write_out();
-  }
-  if (o.interleave) {  // records of both mates -> ONE text, mate 1 then mate 2 of every pair (scalce_fastq_records_interleaved)
-    if (il_nrec[0] != il_nrec[1])
-      FAIL("(ERROR) the mates of %s hold %llu and %llu records\n", path.c_str(), (unsigned long long)il_nrec[0], (unsigned long long)il_nrec[1]);
-    const double tb = now();
-    const uint64_t npairs = il_nrec[0];
-    uint64_t cap = 0;
-    for (int m = 0; m < 2; m++)
-      cap += (no_qual ? scalce_fasta_text_bytes : scalce_fastq_text_bytes)(len[m], npairs, il_nnames[m], names ? nullptr : library.c_str());
-    void *d_text = nullptr;
-    HIPOK(hipMalloc(&d_text, cap + 64));
-    uint64_t text_bytes = 0;
-    std::vector<uint64_t> poff;
-    if (o.split) poff.resize((size_t)npairs + 1);
-    const int rl[2] = {len[0], len[1]};
-    const uint8_t *rh[2] = {R[0].v.data() + R[0].pos, R[1].v.data() + R[1].pos};
-    const uint64_t rb[2] = {R[0].v.size() - R[0].pos, R[1].v.size() - R[1].pos};
-    const uint8_t *dq[2] = {(const uint8_t *)il_q[0], (const uint8_t *)il_q[1]};
-    SCOK(ctx, scalce_fastq_records_interleaved(ctx, rl, rh, rb, npairs, dq, phred, il_npay, il_nnames, library.c_str(), (uint8_t *)d_text, cap,
-                                               &text_bytes, o.split ? poff.data() : nullptr, nullptr));
-    for (int m = 0; m < 2; m++) { hipFree(il_q[m]); release(R[m].v); release(Nn[m].v); }
-    t_records += now() - tb;
-    writer(0, npairs, text_bytes, d_text, std::move(poff))();
-  }
-  for (auto &t : writers) t.join();
-  for (auto &t : droppers) t.join();
+  for (int m = 0; m < (o.interleave ? 1 : nm); m++) sink.finish(m);
   LOG("\tTime elapsed: %.2f s (archive files read %.2f; qualities up and decoded %.2f; records to text %.2f; text down and written %.2f%s)\n",
-      now() - t0, t_files, t_decode, t_records, t_write.load(), nm == 2 && !o.interleave ? ", a thread per mate beside the next mate's decode" : "");
+      now() - t0, st.read_wait_s, st.decode_s, st.records_s, st.write_s, nm == 2 && !o.interleave ? ", one mate after the other" : "");
+  LOG("\tWindows: %llu of up to %llu bytes of text; device memory held at most %llu bytes\n", (unsigned long long)st.windows,
+      (unsigned long long)st.window_text_bytes, (unsigned long long)st.peak_device_bytes);
   return 0;
 }
 
@@ -1300,7 +1220,7 @@ int main(int argc, char **argv) {
                                      {"bucket-set-size", 1, 0, 'B'}, {"paired-end", 0, 0, 'r'}, {"skip-names", 1, 0, 'n'},
                                      {"split-reads", 1, 0, 'S'}, {"fasta", 0, 0, 'f'}, {"threads", 1, 0, 'T'},
                                      {"version", 0, 0, 'v'}, {"no-arithmetic", 0, 0, 'A'}, {"patterns-bin", 1, 0, 1000},
-                                     {"gpus", 1, 0, 1001}, {"interleave", 0, 0, 'i'}, {0, 0, 0, 0}};
+                                     {"gpus", 1, 0, 1001}, {"interleave", 0, 0, 'i'}, {"window", 1, 0, 1002}, {0, 0, 0, 0}};
   int opt;
   while ((opt = getopt_long(argc, argv, "vhp:T:dc:o:fs:t:B:rQAn:P:S:i", long_opt, 0)) != -1) {
     switch (opt) {
@@ -1336,6 +1256,13 @@ int main(int argc, char **argv) {
       case 'n': o.use_names = false; o.library = optarg; break;
       case 1000: o.patterns_bin = optarg; break;
       case 1001: o.gpus = atoi(optarg); break;
+      case 1002: {
+        char *e = nullptr;
+        const unsigned long long v = strtoull(optarg, &e, 10);
+        const uint64_t unit = *e == 'K' ? 1ull << 10 : *e == 'M' ? 1ull << 20 : *e == 'G' ? 1ull << 30 : 1;
+        if (e == optarg || !v || (*e && (unit == 1 || e[1]))) FAIL("--window takes a positive number of bytes, optionally ended with K, M or G.\n");
+        o.window = v * unit;
+      } break;
       default: fputs(HELP_TEXT, stdout); return 0;
     }
   }

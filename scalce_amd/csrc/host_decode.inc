@@ -1,43 +1,39 @@
 // host_decode.inc -- part of scalce_hip.hip (one translation unit; included there, in this order): the inverse path: arithmetic decoder dispatch and records -> FASTQ text
 // ---- decode ---------------------------------------------------------------------------------------------
-extern "C" int scalce_ac_decode(scalce_ctx *c, const uint32_t *table_host, const uint8_t *d_blocks, uint64_t nbytes,
-                                uint64_t nsym, uint8_t *d_out, void *stream) {
-  if (!c || !table_host || !d_blocks || !d_out) return SCALCE_ERR_ARG;
+#include <memory>
+// What depends only on the table, prepared once per archive: the interval table (ac_table_k), the compact rows
+// (ac_dec_rows_k), the ranking of the hot symbols and the choice between ac_decode_tight_k and ac_decode_k.  A launch then
+// takes a run of whole frames that starts at any frame of the stream.
+struct scalce_ac_decoder {
+  scalce_ctx *c = nullptr;
+  u32 *d_table = nullptr, *d_cum = nullptr;  // (d_cum: ac_table_k writes the cumulative counts beside the intervals)
+  uint4 *d_tab = nullptr;
+  uint2 *d_rows = nullptr;
+  u64 device_bytes = 0;
+  bool cached = false, tight = false;
+  int wpb_forced = -1;    // test hook SCALCE_AC_DECODE_WPB: chains per workgroup (2, 4, 8, 16); 0 = the plain decoder
+  AcDecCachedArgs ca;
+};
+extern "C" void scalce_ac_decoder_destroy(scalce_ac_decoder *d) {
+  if (!d) return;
+  hipFree(d->d_table); hipFree(d->d_cum); hipFree(d->d_tab); hipFree(d->d_rows);
+  delete d;
+}
+extern "C" uint64_t scalce_ac_decoder_device_bytes(const scalce_ac_decoder *d) { return d ? d->device_bytes : 0; }
+extern "C" int scalce_ac_decoder_create(scalce_ctx *c, const uint32_t *table_host, void *stream, scalce_ac_decoder **out) {
+  if (!c || !table_host || !out) return SCALCE_ERR_ARG;
+  *out = nullptr;
   hipStream_t s = (hipStream_t)stream;
   HIP_TRY(c, hipSetDevice(c->device));
-  const u32 nblk = cdiv(nsym, AC_BLOCK_SYMS);
-  if (!nblk) return SCALCE_OK;
-  // walk the [u32 size][bytes] frames: the walk is serial by nature (each size says where the next one is), so a small
-  // device kernel follows the chain once and the host takes all offsets with one copy (a blocking 4-byte copy per block was
-  // 477 round trips for a 50 M-read shard, 5 724 for 200 M pairs)
-  std::vector<u64> off(nblk);
-  std::vector<u32> sz(nblk);
-  {
-    u64 *d_walk = nullptr;
-    HIP_TRY(c, hipMalloc(&d_walk, sizeof(u64) * ((size_t)nblk * 2 + 2)));
-    LAUNCH(ac_frame_walk_k, 1, 1, 0, s, d_blocks, (u64)nbytes, nblk, d_walk);
-    std::vector<u64> w((size_t)nblk * 2 + 2);
-    hipError_t e = hipMemcpyAsync(w.data(), d_walk, sizeof(u64) * w.size(), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    hipFree(d_walk);
-    if (e != hipSuccess) { set_err(c, "reading the block frames: %s", hipGetErrorString(e)); return SCALCE_ERR_HIP; }
-    if (w[(size_t)nblk * 2] != 0) { set_err(c, "(ERROR) truncated quality stream"); return SCALCE_ERR_FORMAT; }
-    for (u32 i = 0; i < nblk; i++) { off[i] = w[2 * (size_t)i]; sz[i] = (u32)w[2 * (size_t)i + 1]; }
-  }
-  u32 *d_table = nullptr, *d_cum = nullptr, *d_sz = nullptr;
-  uint4 *d_tab = nullptr;
-  u64 *d_off = nullptr;
-  HIP_TRY(c, hipMalloc(&d_table, sizeof(u32) * 512000));
-  HIP_TRY(c, hipMalloc(&d_cum, sizeof(u32) * 6400 * 81));
-  HIP_TRY(c, hipMalloc(&d_tab, sizeof(uint4) * 512000));
-  HIP_TRY(c, hipMalloc(&d_off, sizeof(u64) * nblk));
-  HIP_TRY(c, hipMalloc(&d_sz, sizeof(u32) * nblk));
-  HIP_TRY(c, hipMemcpyAsync(d_table, table_host, sizeof(u32) * 512000, hipMemcpyHostToDevice, s));
-  HIP_TRY(c, hipMemcpyAsync(d_off, off.data(), sizeof(u64) * nblk, hipMemcpyHostToDevice, s));
-  HIP_TRY(c, hipMemcpyAsync(d_sz, sz.data(), sizeof(u32) * nblk, hipMemcpyHostToDevice, s));
-  LAUNCH(ac_table_k, cdiv(6400, 64), 64, 0, s, d_table, d_tab, d_cum, (u32 *)nullptr);
-  AcDecArgs a;
-  a.in = d_blocks; a.blk_off = d_off; a.blk_size = d_sz; a.nsym = nsym; a.tab = d_tab; a.out = d_out;
+  std::unique_ptr<scalce_ac_decoder, void (*)(scalce_ac_decoder *)> d(new scalce_ac_decoder, scalce_ac_decoder_destroy);
+  d->c = c;
+  memset(&d->ca, 0, sizeof d->ca);
+  HIP_TRY(c, hipMalloc(&d->d_table, sizeof(u32) * 512000));
+  HIP_TRY(c, hipMalloc(&d->d_tab, sizeof(uint4) * 512000));
+  HIP_TRY(c, hipMalloc(&d->d_cum, sizeof(u32) * 6400 * 81));
+  d->device_bytes = (sizeof(u32) + sizeof(uint4)) * 512000 + sizeof(u32) * 6400 * 81;
+  HIP_TRY(c, hipMemcpyAsync(d->d_table, table_host, sizeof(u32) * 512000, hipMemcpyHostToDevice, s));
+  LAUNCH(ac_table_k, cdiv(6400, 64), 64, 0, s, d->d_table, d->d_tab, d->d_cum, (u32 *)nullptr);
   // span of the symbols that occur (scaled count > 1 in some context) and their totals: what the compact rows hold and
   // which contexts go to LDS.  (A symbol outside the span can still be coded -- one occurrence scales down to the
   // floor count 1 -- and takes the full-row path in the kernel.)
@@ -48,16 +44,13 @@ extern "C" int scalce_ac_decode(scalce_ctx *c, const uint32_t *table_host, const
       const u32 v = table_host[(size_t)ctx * AC_D + sy];
       if (v > 1) { smin = std::min(smin, sy); smax = std::max(smax, sy); tot[sy] += v; }
     }
-  uint2 *d_rows = nullptr;
-  const char *wpb_env = getenv("SCALCE_AC_DECODE_WPB");  // test hook: chains per workgroup (2, 4, 8, 16); 0 = the plain decoder
-  const bool cached = smin <= smax && smax - smin + 2 <= 64 && !(wpb_env && atoi(wpb_env) == 0);
-  if (cached) {
-    AcDecCachedArgs ca;
-    memset(&ca, 0, sizeof ca);
-    ca.d = a;
+  const char *wpb_env = getenv("SCALCE_AC_DECODE_WPB");
+  if (wpb_env) d->wpb_forced = atoi(wpb_env);
+  d->cached = smin <= smax && smax - smin + 2 <= 64 && d->wpb_forced != 0;
+  if (d->cached) {
+    AcDecCachedArgs &ca = d->ca;
     ca.smin = smin;
     ca.S1 = smax - smin + 2;
-    ca.nblk = nblk;
     std::vector<u32> order;
     for (u32 sy = smin; sy <= smax; sy++) if (tot[sy]) order.push_back(sy);
     std::stable_sort(order.begin(), order.end(), [&](u32 x, u32 y) { return tot[x] > tot[y]; });
@@ -66,39 +59,88 @@ extern "C" int scalce_ac_decode(scalce_ctx *c, const uint32_t *table_host, const
     ca.W = W;
     memset(ca.rank, 0xFF, sizeof ca.rank);
     for (u32 r = 0; r < W; r++) { ca.hot[r] = (u8)order[r]; ca.rank[order[r]] = (u8)r; }
-    HIP_TRY(c, hipMalloc(&d_rows, sizeof(uint2) * (6400 * ca.S1 + 64)));  // (+ 64: ac_decode_fast_k reads a row with all lanes)
-    HIP_TRY(c, hipMemsetAsync(d_rows + 6400 * (size_t)ca.S1, 0, sizeof(uint2) * 64, s));
-    LAUNCH(ac_dec_rows_k, cdiv(6400u * ca.S1, 256), 256, 0, s, d_tab, smin, ca.S1, d_rows);
-    ca.rows = d_rows;
-    // Waves of a workgroup share the LDS cache of hot rows (one workgroup per CU): two chains per workgroup keep the
-    // latency of a block lowest; from 512 blocks on, eight per workgroup -- two chains per SIMD interleave their issue
-    // slots -- put four times as many blocks in flight.
+    HIP_TRY(c, hipMalloc(&d->d_rows, sizeof(uint2) * (6400 * ca.S1 + 64)));  // (+ 64: a row is read with all lanes)
+    d->device_bytes += sizeof(uint2) * (6400 * (u64)ca.S1 + 64);
+    HIP_TRY(c, hipMemsetAsync(d->d_rows + 6400 * (size_t)ca.S1, 0, sizeof(uint2) * 64, s));
+    LAUNCH(ac_dec_rows_k, cdiv(6400u * ca.S1, 256), 256, 0, s, d->d_tab, smin, ca.S1, d->d_rows);
+    ca.rows = d->d_rows;
     // ONE cached decoder (round 5; rounds 2-4 kept four): ac_decode_tight_k, the loop written by hand for the scalar unit.  It
     // needs what every table of quality strings gives -- no symbol 79 among those that occur (that symbol marks "last of its
     // context" in the rows) and no context total above 2^29 (as for the encoder's plain step); any other table takes the plain
-    // decoder below, the reference's own loop (arithmetic.cpp:196-268) a wavefront per block.
+    // decoder, the reference's own loop (arithmetic.cpp:196-268) a wavefront per block.
     u64 max_total = 0;
     for (u32 ctx = 0; ctx < 6400; ctx++) {
       u64 t = 0;
       for (u32 sy = 0; sy < AC_D; sy++) t += table_host[(size_t)ctx * AC_D + sy];
       max_total = std::max(max_total, t);
     }
-    if (smax < AC_D - 1 && max_total <= (1ull << 29)) {
-      int wpb = nblk <= 512 ? 2 : nblk <= 1024 ? 4 : nblk <= 2048 ? 8 : 16;  // 16 = four chains per SIMD: a chain issues one instruction in five cycles
-      if (wpb_env) wpb = atoi(wpb_env);
-      if (wpb == 2) LAUNCH(ac_decode_tight_k<2>, cdiv(nblk, 2), 128, 0, s, ca);
-      else if (wpb == 4) LAUNCH(ac_decode_tight_k<4>, cdiv(nblk, 4), 256, 0, s, ca);
-      else if (wpb == 16) LAUNCH(ac_decode_tight_k<16>, cdiv(nblk, 16), 1024, 0, s, ca);
-      else LAUNCH(ac_decode_tight_k<8>, cdiv(nblk, 8), 512, 0, s, ca);
-    } else {
-      LAUNCH(ac_decode_k, nblk, 64, 0, s, a);
-    }
+    d->tight = smax < AC_D - 1 && max_total <= (1ull << 29);
+  }
+  HIP_TRY(c, hipStreamSynchronize(s));  // (table_host is the caller's again)
+  if (int rc = launch_failed(c)) return rc;
+  *out = d.release();
+  return SCALCE_OK;
+}
+// Enqueues the decode of `nframes` whole frames that begin at d_frames (nbytes of them are there) into d_out: nsym symbols,
+// AC_BLOCK_SYMS per frame but the last.  d_off / d_size (nframes entries) and d_bad (one word) are the caller's scratch: the
+// walk fills them and the decoder reads them, nothing comes back to the host in between -- the caller reads *d_bad once the
+// stream has got there.  Nothing is allocated and nothing waits.
+extern "C" int scalce_ac_decoder_launch(scalce_ac_decoder *d, const uint8_t *d_frames, uint64_t nbytes, uint32_t nframes,
+                                        uint64_t nsym, uint64_t *d_off, uint32_t *d_size, uint32_t *d_bad, uint8_t *d_out,
+                                        void *stream) {
+  if (!d || !d_frames || !d_off || !d_size || !d_bad || !d_out) return SCALCE_ERR_ARG;
+  if (!nframes) return SCALCE_OK;
+  if (nsym > (u64)nframes * AC_BLOCK_SYMS || nsym <= (u64)(nframes - 1) * AC_BLOCK_SYMS) return SCALCE_ERR_ARG;
+  scalce_ctx *c = d->c;
+  hipStream_t s = (hipStream_t)stream;
+  const u32 nblk = nframes;
+  // the walk is serial by nature (each size says where the next one is): a small kernel follows the chain of this launch's frames
+  LAUNCH(ac_frame_walk_k, 1, 1, 0, s, d_frames, (u64)nbytes, nblk, reinterpret_cast<u64 *>(d_off), d_size, d_bad);
+  AcDecArgs a;
+  a.in = d_frames; a.blk_off = reinterpret_cast<const u64 *>(d_off); a.blk_size = d_size; a.nsym = nsym; a.tab = d->d_tab; a.out = d_out;
+  if (d->cached && d->tight) {
+    AcDecCachedArgs ca = d->ca;
+    ca.d = a;
+    ca.nblk = nblk;
+    // Waves of a workgroup share the LDS cache of hot rows (one workgroup per CU): two chains per workgroup keep the
+    // latency of a block lowest; from 512 blocks on, eight per workgroup -- two chains per SIMD interleave their issue
+    // slots -- put four times as many blocks in flight.  The choice follows the frames of THIS launch.
+    int wpb = nblk <= 512 ? 2 : nblk <= 1024 ? 4 : nblk <= 2048 ? 8 : 16;  // 16 = four chains per SIMD: a chain issues one instruction in five cycles
+    if (d->wpb_forced > 0) wpb = d->wpb_forced;
+    if (wpb == 2) LAUNCH(ac_decode_tight_k<2>, cdiv(nblk, 2), 128, 0, s, ca);
+    else if (wpb == 4) LAUNCH(ac_decode_tight_k<4>, cdiv(nblk, 4), 256, 0, s, ca);
+    else if (wpb == 16) LAUNCH(ac_decode_tight_k<16>, cdiv(nblk, 16), 1024, 0, s, ca);
+    else LAUNCH(ac_decode_tight_k<8>, cdiv(nblk, 8), 512, 0, s, ca);
   } else {
     LAUNCH(ac_decode_k, nblk, 64, 0, s, a);
   }
-  HIP_TRY(c, hipStreamSynchronize(s));
-  hipFree(d_table); hipFree(d_cum); hipFree(d_tab); hipFree(d_off); hipFree(d_sz);
-  if (d_rows) hipFree(d_rows);
+  return launch_failed(c);
+}
+
+// the whole stream at once: a decoder made for this call, one launch over all its frames
+extern "C" int scalce_ac_decode(scalce_ctx *c, const uint32_t *table_host, const uint8_t *d_blocks, uint64_t nbytes,
+                                uint64_t nsym, uint8_t *d_out, void *stream) {
+  if (!c || !table_host || !d_blocks || !d_out) return SCALCE_ERR_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  HIP_TRY(c, hipSetDevice(c->device));
+  const u32 nblk = cdiv(nsym, AC_BLOCK_SYMS);
+  if (!nblk) return SCALCE_OK;
+  scalce_ac_decoder *dec = nullptr;
+  if (int rc = scalce_ac_decoder_create(c, table_host, stream, &dec)) return rc;
+  u64 *d_off = nullptr;
+  u32 *d_sz = nullptr;  // nblk sizes and, behind them, the walk's verdict
+  hipError_t e = hipMalloc(&d_off, sizeof(u64) * nblk);
+  if (e == hipSuccess) e = hipMalloc(&d_sz, sizeof(u32) * ((size_t)nblk + 1));
+  int rc = SCALCE_OK;
+  u32 bad = 0;
+  if (e == hipSuccess) rc = scalce_ac_decoder_launch(dec, d_blocks, nbytes, nblk, nsym, reinterpret_cast<uint64_t *>(d_off), d_sz, d_sz + nblk, d_out, stream);
+  if (e == hipSuccess && !rc) e = hipMemcpyAsync(&bad, d_sz + nblk, sizeof bad, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess && !rc) e = hipStreamSynchronize(s);
+  hipFree(d_off); hipFree(d_sz);
+  scalce_ac_decoder_destroy(dec);
+  if (rc) return rc;
+  if (e != hipSuccess) { set_err(c, "decoding the quality stream: %s", hipGetErrorString(e)); return SCALCE_ERR_HIP; }
+  if (bad) { set_err(c, "(ERROR) truncated quality stream"); return SCALCE_ERR_FORMAT; }
   return SCALCE_OK;
 }
 
@@ -131,6 +173,38 @@ static bool name_offsets(const uint8_t *names_host, uint64_t names_bytes, uint64
   name_off[nrecords] = pos;
   return true;
 }
+// a wavefront per FQ_RECORDS_PER_WAVE records of the window (or archive) that `a` describes
+static void launch_records(const FqArgs &a, bool qual, hipStream_t s) {
+  const u64 waves = (a.nrecords + FQ_RECORDS_PER_WAVE - 1) / FQ_RECORDS_PER_WAVE;
+  if (qual) LAUNCH(fastq_records_k<true>, cdiv(waves, 4), 256, 0, s, a);
+  else LAUNCH(fastq_records_k<false>, cdiv(waves, 4), 256, 0, s, a);
+}
+static_assert(sizeof(scalce_fq_bucket) == sizeof(FqBucket) && offsetof(scalce_fq_bucket, core) == offsetof(FqBucket, core) &&
+              offsetof(scalce_fq_bucket, rec_bytes) == offsetof(FqBucket, rec_bytes), "scalce_fq_bucket is FqBucket");
+// One window of whole records, everything resident and window-relative (scalce_fq_window): enqueues the kernel, nothing else
+extern "C" int scalce_fastq_records_window(scalce_ctx *c, const scalce_fq_window *w, void *stream) {
+  if (!c || !w || w->read_len <= 0 || !w->d_reads || !w->d_dir || !w->nbuckets || !w->d_out) return SCALCE_ERR_ARG;
+  if ((w->d_names != nullptr) != (w->d_name_off != nullptr) || (!w->d_names && !w->library)) return SCALCE_ERR_ARG;
+  if (w->interleave && w->d_names && !w->d_pair_name_off) return SCALCE_ERR_ARG;
+  if (!w->nrecords) return SCALCE_OK;
+  FqArgs a;
+  memset(&a, 0, sizeof a);
+  if (!w->d_names) {
+    const size_t n = strlen(w->library);
+    if (n >= sizeof a.lib) { set_err(c, "library name longer than %zu characters", sizeof a.lib - 1); return SCALCE_ERR_ARG; }
+    a.lib_len = (u32)n;
+    memcpy(a.lib, w->library, n);
+  }
+  a.reads = w->d_reads; a.dir = reinterpret_cast<const FqBucket *>(w->d_dir); a.nbuckets = w->nbuckets;
+  a.nrecords = w->nrecords; a.first = w->first_record; a.L = (u32)w->read_len;
+  a.sz_meta = w->has_buckets ? (w->read_len > 255 ? 2u : 1u) : 0u;
+  a.qual = w->d_qual; a.phred = (u32)w->phred_offset; a.names = w->d_names; a.name_off = reinterpret_cast<const u64 *>(w->d_name_off);
+  a.mate_digit = (u32)w->mate_digit; a.out = w->d_out; a.rec_off = reinterpret_cast<u64 *>(w->d_record_offsets);
+  a.il = (u32)w->interleave; a.pair_L = (u32)w->pair_read_len; a.pair_name_off = reinterpret_cast<const u64 *>(w->d_pair_name_off);
+  launch_records(a, w->d_qual != nullptr, (hipStream_t)stream);
+  return launch_failed(c);
+}
+
 // -d -i: this mate's records go into the text both mates share (FqArgs::il)
 struct FqPairHost {
   u32 il;                        // 1: mate 1, 2: mate 2
@@ -230,9 +304,7 @@ static int fastq_records_impl(scalce_ctx *c, int read_len, int has_buckets, cons
   a.qual = d_qual; a.phred = (u32)phred_offset; a.names = d_names; a.name_off = d_noff;
   a.mate_digit = (u32)mate_digit; a.out = d_out; a.rec_off = d_roff;
   if (pair) { a.il = pair->il; a.pair_L = (u32)pair->pair_L; a.pair_name_off = d_pnoff; }
-  const u64 waves = (nrecords + FQ_RECORDS_PER_WAVE - 1) / FQ_RECORDS_PER_WAVE;
-  if (qual) LAUNCH(fastq_records_k<true>, cdiv(waves, 4), 256, 0, s, a);
-  else LAUNCH(fastq_records_k<false>, cdiv(waves, 4), 256, 0, s, a);
+  launch_records(a, qual, s);
   if (record_offsets_host)
     FQ_TRY(hipMemcpyAsync(record_offsets_host, d_roff, sizeof(u64) * (nrecords + 1), hipMemcpyDeviceToHost, s));
   FQ_TRY(hipStreamSynchronize(s));

@@ -1150,21 +1150,24 @@ __global__ __launch_bounds__(256) void ac_frame_window_k(const u8 *blocks, u64 s
   }
 }
 
-// follows the [u32 size][bytes] chain of a framed stream: out[2i] = byte offset of block i's data, out[2i+1] = its size;
-// out[2 nblk] != 0 when the stream ends before `nblk` frames do
-__global__ void ac_frame_walk_k(const u8 *in, u64 nbytes, u32 nblk, u64 *out) {
+// follows the [u32 size][bytes] chain of `nblk` frames that begin at `in` (the first frame of a window of the stream, or of
+// the stream): off[i] = byte offset of block i's data from `in`, size[i] = its size -- what AcDecArgs reads, so a decoder
+// launch behind the walk needs no copy in between; *bad != 0 when the bytes end before `nblk` frames do (those frames get
+// offset 0, size 0)
+__global__ void ac_frame_walk_k(const u8 *in, u64 nbytes, u32 nblk, u64 *off, u32 *size, u32 *bad_out) {
   if (threadIdx.x || blockIdx.x) return;
   u64 pos = 0;
-  u64 bad = 0;
+  u32 bad = 0;
   for (u32 i = 0; i < nblk; i++) {
-    if (bad || pos + 4 > nbytes) { bad = 1; out[2 * (u64)i] = 0; out[2 * (u64)i + 1] = 0; continue; }
+    if (bad || pos + 4 > nbytes) { bad = 1; off[i] = 0; size[i] = 0; continue; }
     const u32 sz = (u32)in[pos] | ((u32)in[pos + 1] << 8) | ((u32)in[pos + 2] << 16) | ((u32)in[pos + 3] << 24);
-    out[2 * (u64)i] = pos + 4;
-    out[2 * (u64)i + 1] = sz;
-    pos += 4 + (u64)sz;
-    if (pos > nbytes) bad = 1;
+    pos += 4;
+    if (sz > nbytes - pos) { bad = 1; off[i] = 0; size[i] = 0; continue; }
+    off[i] = pos;
+    size[i] = sz;
+    pos += (u64)sz;
   }
-  out[2 * (u64)nblk] = bad;
+  *bad_out = bad;
 }
 
 // ---- decoder (next row): ac_decoder::read_single, arithmetic.cpp:196-244 -------------------

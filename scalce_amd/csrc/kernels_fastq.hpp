@@ -21,8 +21,11 @@ struct FqArgs {
   const FqBucket *dir;
   u32 nbuckets;
   u64 nrecords;
+  u64 first;                // A WINDOW of an archive: the archive-wide index of its first record (0: the whole archive).
+                            // Everything else -- reads, dir, qual, name_off, rec_off, out -- is relative to the window
   u32 L, sz_meta;           // sz_meta = 0: no end metadata (mate 2)
-  const u8 *qual;           // nrecords x L decoded quality symbols (unused when QUAL = false)
+  const u8 *qual;           // nrecords x L decoded quality symbols from the window's first record on, any byte address
+                            // (unused when QUAL = false)
   u32 phred;
   const u8 *names;          // [u8 n][n bytes]... or nullptr: library mode
   const u64 *name_off;      // start of each record's length byte, nrecords + 1 entries
@@ -62,6 +65,13 @@ __device__ __forceinline__ u64 fq_record_at(u64 K, u32 L, const u64 *name_off, u
   if (name_off) return (name_off[K] - K) + K * ((QUAL ? 2ull : 1ull) * L + FIXED);
   return K * (lib_len + (QUAL ? 2ull : 1ull) * L + FIXED + 1) + fq_digits_below(K);
 }
+// the same inside a window that begins at record `first` (K counts from the window's first record): name offsets are the
+// window's own, library names print the archive-wide index, so their digits are those of first .. first + K - 1
+template <bool QUAL>
+__device__ __forceinline__ u64 fq_window_at(u64 K, u64 first, u32 L, const u64 *name_off, u32 lib_len) {
+  if (name_off || !first) return fq_record_at<QUAL>(K, L, name_off, lib_len);
+  return fq_record_at<QUAL>(first + K, L, nullptr, lib_len) - fq_record_at<QUAL>(first, L, nullptr, lib_len);
+}
 
 template <bool QUAL>
 __global__ __launch_bounds__(256) void fastq_records_k(FqArgs a) {
@@ -96,10 +106,10 @@ __global__ __launch_bounds__(256) void fastq_records_k(FqArgs a) {
       n = a.names[no];
       nm = a.names + no + 1;
     } else {
-      n = a.lib_len + 1 + fq_digits(K);
+      n = a.lib_len + 1 + fq_digits(a.first + K);
     }
-    at = fq_record_at<QUAL>(K, L, a.names ? a.name_off : nullptr, a.lib_len);
-    if (a.il) at += fq_record_at<QUAL>(a.il == 1 ? K : K + 1, a.pair_L, a.names ? a.pair_name_off : nullptr, a.lib_len);
+    at = fq_window_at<QUAL>(K, a.first, L, a.names ? a.name_off : nullptr, a.lib_len);
+    if (a.il) at += fq_window_at<QUAL>(a.il == 1 ? K : K + 1, a.first, a.pair_L, a.names ? a.pair_name_off : nullptr, a.lib_len);
     if (a.rec_off && lane == 0) a.rec_off[K] = at;
     const u8 *q = QUAL ? a.qual + K * (u64)L : nullptr;
     u8 *o = a.out + at;
@@ -114,7 +124,7 @@ __global__ __launch_bounds__(256) void fastq_records_k(FqArgs a) {
         else if (j < a.lib_len) c = (u8)a.lib[j];
         else if (j == a.lib_len) c = '.';
         else {  // decimal digit of K, most significant first
-          u64 v = K;
+          u64 v = a.first + K;
           for (u32 r = n - 1 - j; r; r--) v /= 10;
           c = (u8)('0' + v % 10);
         }
@@ -140,8 +150,8 @@ __global__ __launch_bounds__(256) void fastq_records_k(FqArgs a) {
       o[t] = c;
     }
     if (a.rec_off && lane == 0 && K + 1 == a.nrecords)
-      a.rec_off[K + 1] = a.il ? fq_record_at<QUAL>(K + 1, L, a.names ? a.name_off : nullptr, a.lib_len) +
-                                    fq_record_at<QUAL>(K + 1, a.pair_L, a.names ? a.pair_name_off : nullptr, a.lib_len)
+      a.rec_off[K + 1] = a.il ? fq_window_at<QUAL>(K + 1, a.first, L, a.names ? a.name_off : nullptr, a.lib_len) +
+                                    fq_window_at<QUAL>(K + 1, a.first, a.pair_L, a.names ? a.pair_name_off : nullptr, a.lib_len)
                               : at + len;
   }
 }

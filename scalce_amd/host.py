@@ -409,6 +409,70 @@ def stream_compress(ctx, params, read1, read2=None, piece_bytes=0, reads_hint=0,
     return b, st
 
 
+class UnpackParams(C.Structure):
+    _fields_ = [("mates", C.c_int32), ("interleave", C.c_int32), ("no_qualities", C.c_int32), ("mate_digit", C.c_int32),
+                ("ignore_names", C.c_int32), ("split", C.c_int32), ("library", C.c_char_p), ("window_text_bytes", C.c_uint64)]
+
+
+class UnpackStats(C.Structure):
+    _fields_ = [("windows", C.c_uint64), ("window_text_bytes", C.c_uint64), ("peak_device_bytes", C.c_uint64),
+                ("pinned_host_bytes", C.c_uint64), ("records", C.c_uint64 * 2), ("total_s", C.c_double), ("setup_s", C.c_double),
+                ("read_wait_s", C.c_double), ("decode_s", C.c_double), ("records_s", C.c_double), ("write_wait_s", C.c_double),
+                ("write_s", C.c_double), ("error_mate", C.c_int32), ("error_stream", C.c_int32), ("error_wants_file", C.c_int32)]
+
+
+WRITE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64))
+
+
+def stream_decompress(ctx, readers, write, mates=1, interleave=False, no_qualities=False, mate_digit=None, library=None,
+                      split=0, window_text_bytes=0):
+    """scalce_stream_decompress: an archive back to text in windows of whole records.  readers[m] = the three callables
+    (cap) -> bytes of mate m's .scalcer, .scalcen and .scalceq streams (b"" at the end; raise for a read error);
+    write(mate, first_record, nrecords, text_bytes, record_offsets or None) receives every window in order, from the
+    library's writer thread (raise to end the session).  library: print names as <library>.<index> whatever the archive
+    holds (-n).  Returns UnpackStats."""
+    keep = []
+
+    def wrap(fn):
+        def cb(_user, dst, cap):
+            try:
+                data = fn(int(cap))
+            except Exception:  # noqa: BLE001 - reported to the library as a read error
+                return -1
+            if data:
+                C.memmove(dst, data, len(data))
+            return len(data)
+        keep.append(READ_FN(cb))
+        return keep[-1]
+
+    def wcb(_user, mate, first, nrec, text, nbytes, roff):
+        try:
+            offs = [roff[i] for i in range(nrec + 1)] if roff else None
+            write(int(mate), int(first), int(nrec), C.string_at(text, nbytes), offs)
+        except Exception:  # noqa: BLE001 - reported to the library as a failed write
+            return 1
+        return 0
+    wfn = WRITE_FN(wcb)
+    rd = ((READ_FN * 3) * 2)()
+    user = ((C.c_void_p * 3) * 2)()
+    for m in range(mates):
+        for k in range(3):
+            if readers[m][k] is not None:
+                rd[m][k] = wrap(readers[m][k])
+    p = UnpackParams(mates, int(interleave), int(no_qualities), int(mates == 2 if mate_digit is None else mate_digit),
+                     int(library is not None), int(split), library.encode() if library is not None else None, int(window_text_bytes))
+    st = UnpackStats()
+    msg = C.create_string_buffer(1024)
+    L = ctx.L
+    L.scalce_stream_decompress.argtypes = [C.c_void_p, C.POINTER(UnpackParams), C.c_void_p, C.c_void_p, WRITE_FN, C.c_void_p,
+                                           C.POINTER(UnpackStats), C.c_char_p, C.c_size_t]
+    L.scalce_stream_decompress.restype = C.c_int
+    rc = L.scalce_stream_decompress(ctx.h, C.byref(p), C.cast(rd, C.c_void_p), C.cast(user, C.c_void_p), wfn, None, C.byref(st), msg, len(msg))
+    if rc:
+        raise ScalceError(f"[{rc}] " + msg.value.decode(errors="replace"))
+    return st
+
+
 class Workspace:
     """Front-stage device buffers shared by several batches (scalce_workspace): see include/scalce_hip.h."""
 
