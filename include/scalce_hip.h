@@ -465,6 +465,7 @@ typedef struct {
                                   waiting for a window buffer that wr still holds; write: inside wr */
   int32_t error_mate, error_stream;  /* on failure: which stream of which mate (0 r, 1 n, 2 q), or -1 */
   int32_t error_wants_file;    /* the message in errbuf is a predicate: put the stream's file name in front of it */
+  uint64_t decode_batches[2];  /* per mate: decoder batches enqueued (runs of whole frames, one scalce_ac_decoder_launch each) */
 } scalce_unpack_stats;
 int scalce_stream_decompress(scalce_ctx *ctx, const scalce_unpack_params *p, scalce_read_fn rd[2][3], void *user[2][3],
                              scalce_write_fn wr, void *wr_user, scalce_unpack_stats *stats, char *errbuf, size_t errcap);

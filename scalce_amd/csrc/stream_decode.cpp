@@ -451,6 +451,7 @@ struct Session {
     x.frames_left -= k;
     x.syms_left -= nsym;
     x.enq = b;
+    S.decode_batches[m]++;
     return SCALCE_OK;
   }
   // whole records of mate m that the decoded symbols still hold; moves on to the next batch when that is none

@@ -45,6 +45,21 @@ class ShardResult(C.Structure):
                 ("keep", C.c_void_p * 8), ("keep_bytes", C.c_uint64 * 8), ("magic", C.c_uint32)]
 
 
+class FqBucket(C.Structure):
+    """scalce_fq_bucket: one bucket of a window's directory (host_decode.inc asserts the layout against the kernel's)"""
+    _fields_ = [("first", C.c_uint64), ("off", C.c_uint64), ("core_len", C.c_uint32), ("rec_bytes", C.c_uint32),
+                ("core", C.c_char * 32)]
+
+
+class FqWindow(C.Structure):
+    """scalce_fq_window: every pointer is the caller's device memory (library: host)"""
+    _fields_ = [("d_reads", C.c_void_p), ("d_dir", C.c_void_p), ("nbuckets", C.c_uint32), ("read_len", C.c_int32),
+                ("has_buckets", C.c_int32), ("mate_digit", C.c_int32), ("nrecords", C.c_uint64), ("first_record", C.c_uint64),
+                ("d_qual", C.c_void_p), ("phred_offset", C.c_int64), ("d_names", C.c_void_p), ("d_name_off", C.c_void_p),
+                ("library", C.c_char_p), ("d_out", C.c_void_p), ("d_record_offsets", C.c_void_p), ("interleave", C.c_int32),
+                ("pair_read_len", C.c_int32), ("d_pair_name_off", C.c_void_p)]
+
+
 SHARD_PREPARE_ONLY, SHARD_CODER_ASYNC = 1, 2
 # scalce_patterns_walk / scalce_patterns_walk_host, by SCALCE_WALK_* value
 WALKS = ("none", "kmer", "kmer_t7", "anchor")
@@ -158,6 +173,13 @@ def lib():
     L.scalce_fasta_text_bytes.argtypes = [i32, u64, u64, C.c_char_p]
     L.scalce_fastq_records.argtypes = [vp, i32, i32, vp, u64, u64, vp, C.c_int64, vp, u64, C.c_char_p, i32, vp, u64,
                                        C.POINTER(u64), vp, vp]
+    L.scalce_ac_decoder_create.argtypes = [vp, vp, vp, C.POINTER(vp)]
+    L.scalce_ac_decoder_destroy.argtypes = [vp]
+    L.scalce_ac_decoder_destroy.restype = None
+    L.scalce_ac_decoder_device_bytes.argtypes = [vp]
+    L.scalce_ac_decoder_device_bytes.restype = u64
+    L.scalce_ac_decoder_launch.argtypes = [vp, vp, u64, C.c_uint32, u64, vp, vp, vp, vp, vp]
+    L.scalce_fastq_records_window.argtypes = [vp, C.POINTER(FqWindow), vp]
     _LIB = L
     return L
 
@@ -270,9 +292,64 @@ class Context:
         t = np.ascontiguousarray(table_u32, dtype=np.uint32)
         self._check(self.L.scalce_ac_decode(self.h, t.ctypes.data, d_blocks, int(nbytes), int(nsym), d_out, stream))
 
+    def ac_decoder(self, table_u32, stream=0):
+        """What scalce_ac_decoder_create prepares from a table, once: launch() then decodes runs of whole frames."""
+        return AcDecoder(self, table_u32, stream)
+
+    def fastq_records_window(self, d_reads, d_dir, nbuckets, read_len, nrecords, d_out, first_record=0, has_buckets=True,
+                             mate_digit=0, d_qual=None, phred=33, d_names=None, d_name_off=None, library=None,
+                             d_record_offsets=None, interleave=0, pair_read_len=0, d_pair_name_off=None, stream=0):
+        """One window of whole records into text (scalce_fastq_records_window): enqueues the kernel on `stream`, nothing else.
+        Every d_* is a device pointer of the caller's, at any byte address the entry allows; d_dir points at `nbuckets`
+        FqBucket entries, window-relative; library: str or bytes, for names "<library>.<first_record + k>"."""
+        if isinstance(library, str):
+            library = library.encode()
+        w = FqWindow(d_reads, d_dir, int(nbuckets), int(read_len), int(has_buckets), int(mate_digit), int(nrecords),
+                     int(first_record), d_qual, int(phred), d_names, d_name_off, library, d_out, d_record_offsets,
+                     int(interleave), int(pair_read_len), d_pair_name_off)
+        self._check(self.L.scalce_fastq_records_window(self.h, C.byref(w), stream))
+
     def close(self):
         if self.h:
             self.L.scalce_ctx_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class AcDecoder:
+    """scalce_ac_decoder: the arithmetic decoder of one table (scalce_ac_decoder_create / _launch / _destroy)."""
+
+    def __init__(self, ctx, table_u32, stream=0):
+        self.ctx = ctx
+        self.h = C.c_void_p()
+        t = np.ascontiguousarray(table_u32, dtype=np.uint32)
+        ctx._check(ctx.L.scalce_ac_decoder_create(ctx.h, t.ctypes.data, stream, C.byref(self.h)))
+
+    @property
+    def device_bytes(self):
+        return int(self.ctx.L.scalce_ac_decoder_device_bytes(self.h))
+
+    def launch(self, d_frames, nbytes, nframes, nsym, d_out, stream=0):
+        """Decodes `nframes` whole frames that begin at d_frames (nbytes of them are there) into d_out and waits for it.
+        Returns the frame walk's verdict word: != 0, the bytes end before the frames do."""
+        import torch
+        dev = f"cuda:{self.ctx.device}"
+        d_off = torch.zeros(max(1, int(nframes)), dtype=torch.int64, device=dev)
+        d_size = torch.zeros(int(nframes) + 1, dtype=torch.int32, device=dev)  # the sizes and, behind them, the verdict
+        d_bad = d_size.data_ptr() + 4 * int(nframes)
+        self.ctx._check(self.ctx.L.scalce_ac_decoder_launch(self.h, d_frames, int(nbytes), int(nframes), int(nsym), d_off.data_ptr(),
+                                                            d_size.data_ptr(), d_bad, d_out, stream))
+        torch.cuda.synchronize(dev)
+        return int(d_size[int(nframes)].item()) & 0xFFFFFFFF
+
+    def close(self):
+        if self.h:
+            self.ctx.L.scalce_ac_decoder_destroy(self.h)
             self.h = C.c_void_p()
 
     def __del__(self):
@@ -418,7 +495,8 @@ class UnpackStats(C.Structure):
     _fields_ = [("windows", C.c_uint64), ("window_text_bytes", C.c_uint64), ("peak_device_bytes", C.c_uint64),
                 ("pinned_host_bytes", C.c_uint64), ("records", C.c_uint64 * 2), ("total_s", C.c_double), ("setup_s", C.c_double),
                 ("read_wait_s", C.c_double), ("decode_s", C.c_double), ("records_s", C.c_double), ("write_wait_s", C.c_double),
-                ("write_s", C.c_double), ("error_mate", C.c_int32), ("error_stream", C.c_int32), ("error_wants_file", C.c_int32)]
+                ("write_s", C.c_double), ("error_mate", C.c_int32), ("error_stream", C.c_int32), ("error_wants_file", C.c_int32),
+                ("decode_batches", C.c_uint64 * 2)]
 
 
 WRITE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64))

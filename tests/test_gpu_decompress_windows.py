@@ -5,8 +5,10 @@ import os
 import re
 import subprocess
 
+import numpy as np
 import pytest
 
+import decode_ref as R
 import oraclelib as O
 from scalce_amd import synth
 
@@ -223,3 +225,139 @@ def test_stdout_gets_the_windows(tmp_path):
     run_cli("-d", "--window", "256K", "-o", d / "f", d / "a_1.scalcen")
     r = run_cli("-d", "--window", "256K", "-o", "-", d / "a_1.scalcen")
     assert r.stdout == read(d / "f_1.fastq") and windows_line(r)[0] >= 6
+
+
+# ---- 9: the decoder's batches: carry at odd alignments, a batch cut short, archives that do not say how many records ------
+def file_readers(d, stem, mates):
+    def reader(path):
+        f = open(path, "rb")
+        return lambda cap: f.read(cap)
+    return [[reader(d / f"{stem}_{m}.scalce{e}") for e in "rnq"] for m in range(1, mates + 1)]
+
+
+def batches_of(d, stem, mates, window, **kw):
+    """scalce_stream_decompress on the files the CLI read: (UnpackStats, the text per mate)"""
+    from scalce_amd import host
+    ctx = host.Context(0, patterns_bin=read(PBIN))
+    got = {}
+    st = host.stream_decompress(ctx, file_readers(d, stem, mates), lambda mate, first, n, text, offs: got.setdefault(mate, []).append(text),
+                                mates=mates, window_text_bytes=window, **kw)
+    return st, [b"".join(got[m]) for m in sorted(got)]
+
+
+def test_carry_of_41_bytes_between_single_frame_batches(tmp_path):
+    """--window 2M on reads of 101 bases: one frame per decoder batch, two frames, and 10 485 760 mod 101 = 41 symbols of the
+    first carried in front of the second -- the decoder writes at Y + 41"""
+    d = tmp_path
+    n, L = 105000, 101
+    assert n * L > 10485760 and 10485760 % L == 41
+    make_inputs(d, n, L, False, seed=79)
+    want = oracle_text(d, [], [], False)
+    r = run_cli("-d", "--window", "2M", "-o", d / "back", d / "orc_1.scalcen")
+    assert read(d / "back_1.fastq") == want[0]
+    st, text = batches_of(d, "orc", 1, 2 << 20)
+    assert text[0] == want[0]
+    assert list(st.decode_batches) == [2, 0] and st.records[0] == n
+    assert windows_line(r)[0] == st.windows >= -(-len(want[0]) // (2 << 20))
+
+
+@pytest.mark.parametrize("n", [70000, 140000], ids=["70k_pairs", "140k_pairs"])
+def test_interleaved_mates_each_with_a_carry_of_their_own(n, tmp_path):
+    """-i, mates of 75 and 151 bases, --window 2M: one frame per batch in either mate.  Mate 2's second frame begins 18 symbols
+    into a record (10 485 760 mod 151).  Mate 1 has a second frame, and its carry of 10 (10 485 760 mod 75), from 139 811 pairs
+    on: at 70 000 pairs its stream is one frame and one batch beside mate 2's two; at 140 000 pairs mate 1 has two batches and
+    mate 2 three, both write behind a carry, and their batches change at different windows.  (The larger case reads 31.6 M
+    bases through the oracle twice: about 13 s, most of it on the CPU.  No smaller input gives mate 1 a second frame.)"""
+    d = tmp_path
+    assert 10485760 % 75 == 10 and 10485760 % 151 == 18
+    synth.write_fastq(str(d / "in_1.fq"), n, 75, seed=89, n_frac=0.003, dup_frac=0.1, paired_suffix="/1")
+    synth.write_fastq(str(d / "in_2.fq"), n, 151, seed=90, paired_suffix="/2")
+    want = interleaved(*oracle_text(d, ["-r"], ["-r"], True))
+    r = run_cli("-d", "-i", "--window", "2M", "-o", d / "back", d / "orc_1.scalcen")
+    assert read(d / "back_1.fastq") == want
+    st, text = batches_of(d, "orc", 2, 2 << 20, interleave=True)
+    assert text == [want]
+    assert list(st.decode_batches) == {70000: [1, 2], 140000: [2, 3]}[n] and list(st.records) == [n, n]
+    assert windows_line(r)[0] == st.windows >= -(-len(want) // (2 << 20))
+
+
+def test_batch_cut_short_by_frames_that_code_badly():
+    """Three frames per batch (a window of 5.5 MB of text: 8 x 26 699 records x 100 > 2 x 10 485 760) and a stream that codes
+    to three quarters of its symbols: the staging buffer takes two frames, not three, and the first batch is cut to them.
+    The archive is built in memory -- made-up names, one root bucket, 3 x 10 485 760 + 50 000 symbols drawn uniformly from
+    1..62 under a table of equal counts -- and coded by the oracle.  This is the smallest stream that reaches the cut."""
+    from scalce_amd import host
+    L, nsym, window = 100, 3 * R.FRAME + 50000, 5_500_000
+    nrec = nsym // L
+    rng = np.random.default_rng(97)
+    sym = rng.integers(1, 63, size=nsym).astype(np.uint8)
+    bases = np.frombuffer(b"ACGT", dtype=np.uint8)[rng.integers(0, 4, size=(nrec, L))]
+    table = np.ones((6400, 80), dtype=np.uint32)
+    table[:, 1:63] = 16
+    coded = R.framed(table.reshape(-1), sym)
+    sizes = [sz for _, sz in R.frames_of(coded, 4)]
+    assert window // (2 * L + 6) * 8 * L > 2 * R.FRAME
+    # three coded frames exceed 2 x 10 485 760 bytes and any two do not -- by more than the few KB the staging buffer has beside
+    # that: whatever its exact size, it takes two of these frames and not three
+    assert sum(4 + s for s in sizes[:3]) > 2 * R.FRAME + (1 << 20)
+    assert all(8 + sizes[i] + sizes[j] < 2 * R.FRAME - (1 << 20) for i in range(4) for j in range(i))
+    files = [R.read_stream_file(L, np.array([R.ROOT_CORE], dtype="<i4").tobytes() + np.array([nrec], dtype="<u8").tobytes() + R.pack_root_records(bases)),
+             R.name_stream_file(library=b"cut"), R.quality_stream_file(33, table.reshape(-1), nsym, coded)]
+    want = R.text_of_uniform(bases, sym[:nrec * L].reshape(nrec, L), b"cut", 0, 33)
+
+    def reader(data):
+        pos = [0]
+
+        def rd(cap):
+            out = data[pos[0]:pos[0] + cap]
+            pos[0] += len(out)
+            return out
+        return rd
+    got = []
+    ctx = host.Context(0, patterns_bin=read(PBIN))
+    st = host.stream_decompress(ctx, [[reader(f) for f in files]], lambda mate, first, n, text, offs: got.append(text), window_text_bytes=window)
+    assert st.decode_batches[0] == 2 and st.records[0] == nrec
+    text = b"".join(got)
+    assert len(text) == len(want) and text == want
+    print(f"cut batch: {st.windows} windows, decode {st.decode_s:.2f} s, total {st.total_s:.2f} s")
+
+
+def greedy_windows(n, L, lib, window):
+    """records per window when every window takes as many whole records as its text bound allows: a record of made-up names is
+    "@<lib>.<index>" and 2 L + 6 more bytes of FASTQ, and no window holds more than window / (2 L + 6) records"""
+    out, first = [], 0
+    while first < n:
+        k = text = 0
+        while first + k < n and k < window // (2 * L + 6) and text + len(lib) + 1 + len(str(first + k)) + 2 * L + 6 <= window:
+            text += len(lib) + 1 + len(str(first + k)) + 2 * L + 6
+            k += 1
+        out.append(k)
+        first += k
+    return out
+
+
+@pytest.mark.parametrize("flag", ["-Q", "-A"])
+@pytest.mark.parametrize("count", ["5R", "5R+1", "5_windows", "5_windows+1"])
+def test_record_count_from_the_streams_under_small_windows(flag, count, tmp_path):
+    """-Q -n lib and -A -n lib: neither a name stream nor a symbol count says how many records there are, the read stream
+    (-Q) or the raw quality rows (-A) end the archive.  --window 64K; the archive holds a multiple of R = window / (2 L + 6)
+    records, or ends with the last record that the fifth window's text takes -- and one record more."""
+    d = tmp_path
+    L, window = 100, 64 << 10
+    R_ = window // (2 * L + 6)
+    five = sum(greedy_windows(10 * R_, L, "lib", window)[:5])
+    n = {"5R": 5 * R_, "5R+1": 5 * R_ + 1, "5_windows": five, "5_windows+1": five + 1}[count]
+    make_inputs(d, n, L, False, seed=101)
+    cflags = ["-n", "lib"] + (["-A"] if flag == "-A" else [])
+    want = oracle_text(d, cflags, ["-n", "lib"], False)[0]
+    if flag == "-Q":
+        want = two_line(want)
+        run_cli("-Q", "-n", "lib", "-c", "no", "-o", d / "hip", d / "in_1.fq")
+    stem = "hip" if flag == "-Q" else "orc"
+    r = run_cli("-d", "-n", "lib", *(["-Q"] if flag == "-Q" else []), "--window", "64K", "-o", d / "back", d / f"{stem}_1.scalcen")
+    assert read(d / "back_1.fastq") == want
+    assert want.count(b"\n") == n * (2 if flag == "-Q" else 4) and b"@lib.%d\n" % (n - 1) in want
+    nwin = windows_line(r)[0]
+    assert nwin == len(greedy_windows(n, L, "lib", window))
+    if count.startswith("5_windows"):
+        assert nwin == (6 if count.endswith("+1") else 5)
