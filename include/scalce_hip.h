@@ -216,7 +216,10 @@ int scalce_batch_tokenize_settle(scalce_batch *b, const uint64_t *d_prior_counts
 /* Sharded runs: the cuts the -B rule makes inside this batch's rows when `carry_in` bytes of records are already in the
  * chunk that is open where they begin (the rows of the ranks before): cuts_host[i] = row in front of which chunk i + 1
  * begins (1 .. N; at most cap), carry_out = bytes in the chunk still open behind the last row.  Needs the rows ingested,
- * not tokenized (record sizes depend on the core's length only). */
+ * not tokenized (record sizes depend on the core's length only).  *ncuts == cap says that the list may be cut short: the
+ * cuts returned are the first cap of the plan, *carry_out is then the size of every row behind the last of them and no
+ * carry.  A caller passes a cap above any plan it accepts and takes *ncuts == cap for SCALCE_ERR_CAPACITY
+ * (scalce_sharded_compress: 4000 cuts per rank).  A batch without rows: no cuts, *carry_out = carry_in. */
 int scalce_batch_chunk_plan(scalce_batch *b, uint64_t carry_in, uint64_t *cuts_host, uint32_t cap, uint32_t *ncuts,
                             uint64_t *carry_out, void *stream);
 /* Byte offset, in the text of the piece ingested last, at which record `row` (0 .. rows of that piece) begins; runs on
@@ -226,7 +229,10 @@ int scalce_batch_text_offset(scalce_batch *b, int mate, uint64_t row, uint64_t *
  * move to the nearest cut, compress.cpp:702-715): rows [keep_first, keep_first + keep_rows) of the batch stay as they are, the
  * records of `front` (FASTQ text on the device, whole records, 16-byte aligned; [mate]) become rows in front of them, those of
  * `back` rows behind them.  Only the records that arrive are ingested and walked; the quality statistics are not touched (every
- * record was counted by the rank that ingested it first).  Before any tokenization of the batch. */
+ * record was counted by the rank that ingested it first).  Before any tokenization of the batch (SCALCE_ERR_ARG behind one, and
+ * for an interleaved batch, nothing has moved then); a text that does not end with its last record, or whose mates hold different
+ * numbers of records, is SCALCE_ERR_FORMAT ("rewindow: the front / back text is not whole records: ..."): the batch has given up
+ * its rows by then, and scalce_batch_reset or a new ingest starts it over. */
 int scalce_batch_rewindow(scalce_batch *b, uint64_t keep_first, uint64_t keep_rows, const uint8_t *const front[2],
                           const uint64_t front_bytes[2], const uint8_t *const back[2], const uint64_t back_bytes[2], void *stream);
 /* Spill-chunk boundaries given by the caller instead of the -B rule: starts[0] = 0 < starts[1] < ...;

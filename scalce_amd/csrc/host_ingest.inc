@@ -294,6 +294,14 @@ extern "C" int scalce_batch_append(scalce_batch *b, const uint8_t *d_text1, uint
   return SCALCE_OK;
 }
 
+// ingest_piece's verdict on the shape of a text that arrived at scalce_batch_rewindow (lines that make no whole records, no
+// trailing newline, mates with different numbers of records), under rewindow's name and with ingest_piece's own words behind it
+static int not_whole_records(scalce_ctx *c, const char *which) {
+  const std::string why = c->err;
+  set_err(c, "rewindow: the %s text is not whole records: %s", which, why.c_str());
+  return SCALCE_ERR_FORMAT;
+}
+
 // Sharded runs: the rows this rank holds change at both ends (rank boundaries move to spill-chunk boundaries, sharded.cpp) --
 // rows [keep_first, keep_first + keep_rows) stay, the records of `front` go in front of them, those of `back` behind (FASTQ text,
 // whole records, either may be empty).  Rounds 1-4 rebuilt the whole range from text: a second ingest and a second first walk of
@@ -301,6 +309,8 @@ extern "C" int scalce_batch_append(scalce_batch *b, const uint8_t *d_text1, uint
 // swapped against a second set in the workspace, the new set takes [front | kept | back] -- only the moved records are ingested
 // and walked, the kept rows are one device copy (rows, name cells, tokens: ~185 bytes per read); nothing at all is copied when
 // only the back end moves.  Quality statistics are NOT touched: every record was counted by the rank that ingested it first.
+// An error behind the argument checks leaves the batch between the two sets of row arrays: its rows are gone, the next reset /
+// ingest starts it over.
 extern "C" int scalce_batch_rewindow(scalce_batch *b, uint64_t keep_first, uint64_t keep_rows, const uint8_t *const front[2],
                                      const uint64_t front_bytes[2], const uint8_t *const back[2], const uint64_t back_bytes[2], void *stream) {
   if (!b || !front || !back || !front_bytes || !back_bytes || keep_first + keep_rows > b->N || b->il) return SCALCE_ERR_ARG;
@@ -343,6 +353,7 @@ extern "C" int scalce_batch_rewindow(scalce_batch *b, uint64_t keep_first, uint6
     b->N = b->base = b->NP = 0;
     if (have_front) {
       int rc = ingest_piece(b, front, fb, true, used, s);
+      if (rc == SCALCE_ERR_FORMAT) return not_whole_records(c, "front");
       if (rc) return rc;
       if (used[0] != fb[0] || (b->nm == 2 && used[1] != fb[1])) { set_err(c, "rewindow: the front text is not whole records"); return SCALCE_ERR_FORMAT; }
     }
@@ -365,6 +376,7 @@ extern "C" int scalce_batch_rewindow(scalce_batch *b, uint64_t keep_first, uint6
   const u64 nkept_end = b->N;
   if (bb[0]) {
     int rc = ingest_piece(b, back, bb, true, used, s);
+    if (rc == SCALCE_ERR_FORMAT) return not_whole_records(c, "back");
     if (rc) return rc;
     if (used[0] != bb[0] || (b->nm == 2 && used[1] != bb[1])) { set_err(c, "rewindow: the back text is not whole records"); return SCALCE_ERR_FORMAT; }
   }

@@ -514,7 +514,8 @@ extern "C" int scalce_batch_text_offset(scalce_batch *b, int mate, uint64_t row,
   hipStream_t s = (hipStream_t)stream;
   if (!b || !offset || mate < 0 || mate >= b->nm || row > b->NP) return SCALCE_ERR_ARG;
   *offset = 0;
-  if (!row) return SCALCE_OK;
+  const u64 line = b->il ? (u64)b->lpr * (2 * row + (u64)mate) : (u64)b->lpr * row;
+  if (!line) return SCALCE_OK;  // (-i: mate 2 of row 0 is the text's second record, not its first byte)
   HIP_TRY(b->ctx, hipSetDevice(b->ctx->device));
   // from the per-tile newline counts of the piece (its text must still be where it was): no line index is built for this
   const int tm = b->il ? 0 : mate;  // (-i: one text, mate m of row r is its record 2r + m)
@@ -523,7 +524,6 @@ extern "C" int scalce_batch_text_offset(scalce_batch *b, int mate, uint64_t row,
   if (!ntiles || !b->piece_text[tm]) { set_err(b->ctx, "no piece ingested"); return SCALCE_ERR_ARG; }
   // on the caller's stream, behind the ingest that produced the tile counts
   u64 *d_out = &b->d_scr->text_offset;
-  const u64 line = b->il ? (u64)b->lpr * (2 * row + (u64)mate) : (u64)b->lpr * row;
   LAUNCH(line_offset_k, 1, 64, 0, s, b->piece_text[tm], nbytes, b->ws->tile[tm].as<u64>(), ntiles, line, d_out);
   u64 v = 0;
   { int rc = read_u64(b, d_out, &v, 1, s); if (rc) return rc; }

@@ -61,6 +61,7 @@ class FqWindow(C.Structure):
 
 
 SHARD_PREPARE_ONLY, SHARD_CODER_ASYNC = 1, 2
+APPEND_FINAL, APPEND_NO_QUALITY, APPEND_NO_TOKENIZE = 1, 2, 4  # SCALCE_APPEND_*
 # scalce_patterns_walk / scalce_patterns_walk_host, by SCALCE_WALK_* value
 WALKS = ("none", "kmer", "kmer_t7", "anchor")
 
@@ -148,6 +149,9 @@ def lib():
     L.scalce_ac_scale.argtypes = [vp, vp, C.c_uint32, vp, vp]
     L.scalce_batch_chunk_plan.argtypes = [vp, u64, C.POINTER(u64), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(u64), vp]
     L.scalce_batch_text_offset.argtypes = [vp, i32, u64, C.POINTER(u64), vp]
+    L.scalce_batch_rewindow.argtypes = [vp, u64, u64, C.POINTER(vp), C.POINTER(u64), C.POINTER(vp), C.POINTER(u64), vp]
+    L.scalce_batch_qinput_edges.argtypes = [vp, i32, C.POINTER(C.c_uint8), C.POINTER(u64), C.POINTER(C.c_int32), vp]
+    L.scalce_batch_set_fused_rows.argtypes = [vp, i32]
     L.scalce_comm_unique_id.argtypes = [C.c_char_p]
     L.scalce_comm_create_rccl.argtypes = [i32, i32, i32, C.c_char_p, C.POINTER(vp)]
     L.scalce_comm_create_shm.argtypes = [i32, i32, i32, C.c_char_p, u64, C.POINTER(vp)]
@@ -605,10 +609,11 @@ class Batch:
     def ingest(self, mate, d_text, nbytes, stream=0):
         self._check(self.L.scalce_batch_ingest(self.h, mate, d_text, int(nbytes), stream))
 
-    def append(self, d_text1, n1, d_text2=None, n2=0, final=False, stream=0):
-        """Next piece of the read stream behind the rows already held; returns the bytes consumed per mate."""
+    def append(self, d_text1, n1, d_text2=None, n2=0, final=False, stream=0, flags=0):
+        """Next piece of the read stream behind the rows already held; returns the bytes consumed per mate.
+        flags: APPEND_NO_QUALITY / APPEND_NO_TOKENIZE beside `final` (APPEND_FINAL)."""
         used = (C.c_uint64 * 2)()
-        self._check(self.L.scalce_batch_append(self.h, d_text1, int(n1), d_text2, int(n2), int(final), used, stream))
+        self._check(self.L.scalce_batch_append(self.h, d_text1, int(n1), d_text2, int(n2), int(bool(final)) | int(flags), used, stream))
         return used[0], used[1]
 
     def reset(self):
@@ -630,8 +635,44 @@ class Batch:
         self._check(self.L.scalce_batch_tokenize_end(self.h, stream))
 
     def set_chunks(self, starts):
+        """Spill-chunk starts for the order stage instead of the -B rule; None: back to the -B rule."""
+        if starts is None:
+            self._check(self.L.scalce_batch_set_chunks(self.h, None, 0))
+            return
         a = (C.c_uint64 * len(starts))(*[int(x) for x in starts])
         self._check(self.L.scalce_batch_set_chunks(self.h, a, len(starts)))
+
+    def set_fused_rows(self, on=True):
+        self._check(self.L.scalce_batch_set_fused_rows(self.h, int(on)))
+
+    def chunk_plan(self, carry_in, cap, stream=0):
+        """scalce_batch_chunk_plan -> (cuts, carry_out); len(cuts) == cap: the list may be cut short (see the header)."""
+        cuts = np.zeros(max(1, int(cap)), dtype=np.uint64)
+        n, carry = C.c_uint32(0), C.c_uint64(0)
+        self._check(self.L.scalce_batch_chunk_plan(self.h, int(carry_in), cuts.ctypes.data_as(C.POINTER(C.c_uint64)), int(cap),
+                                                   C.byref(n), C.byref(carry), stream))
+        return cuts[: n.value].copy(), int(carry.value)
+
+    def text_offset(self, mate, row, stream=0):
+        off = C.c_uint64(0)
+        self._check(self.L.scalce_batch_text_offset(self.h, int(mate), int(row), C.byref(off), stream))
+        return int(off.value)
+
+    def rewindow(self, keep_first, keep_rows, front, back, stream=0):
+        """scalce_batch_rewindow; front / back = [(device ptr or None, nbytes)] per mate."""
+        def arrays(pieces):
+            pieces = list(pieces) + [(None, 0)] * (2 - len(pieces))
+            return (C.c_void_p * 2)(*[p for p, _ in pieces]), (C.c_uint64 * 2)(*[int(n) for _, n in pieces])
+        fp, fn = arrays(front)
+        bp, bn = arrays(back)
+        self._check(self.L.scalce_batch_rewindow(self.h, int(keep_first), int(keep_rows), fp, fn, bp, bn, stream))
+
+    def qinput_edges(self, mate, stream=0):
+        """scalce_batch_qinput_edges -> (edge[4], nsym, read_len)"""
+        edge = (C.c_uint8 * 4)()
+        nsym, rl = C.c_uint64(0), C.c_int32(0)
+        self._check(self.L.scalce_batch_qinput_edges(self.h, int(mate), edge, C.byref(nsym), C.byref(rl), stream))
+        return list(edge), int(nsym.value), int(rl.value)
 
     def entropy_stream(self, mate, d_table, d_symbols, nsym, stream=0):
         self._check(self.L.scalce_batch_entropy_stream(self.h, mate, d_table, d_symbols, int(nsym), stream))
