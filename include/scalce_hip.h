@@ -340,8 +340,10 @@ int scalce_memcpy_d2h(scalce_ctx *ctx, void *dst_host, const void *src_dev, uint
 int scalce_memcpy_h2d(scalce_ctx *ctx, void *dst_dev, const void *src_host, uint64_t nbytes);
 int scalce_memcpy_d2d(scalce_ctx *ctx, void *dst_dev, const void *src_dev, uint64_t nbytes, void *stream); /* async */
 /* diagnostics of the last run: tie reads, candidate events, fixed-point sweeps, spill chunks, records that
- * needed the second sort phase, 1 if the tie-break ended in the sequential fallback (tie_sequential_k) */
-int scalce_batch_stats(const scalce_batch *b, uint32_t out[6]);
+ * needed the second sort phase, 1 if the tie-break ended in the sequential fallback (tie_sequential_k), the second
+ * sort phase's `any_large` as read back: != 0 when a run of more than 32 records with bases behind the 16-base prefix sent
+ * every run through the radix passes, 0 when the runs were sorted where they stood or the phase did not run */
+int scalce_batch_stats(const scalce_batch *b, uint32_t out[7]);
 
 /* Device self-test of the arithmetic coder's closed-form step (multiply-high by reciprocal fractions, merged
  * renormalisation shift) against the literal loop of arithmetic.cpp:122-152 on `ncases` random and crafted

@@ -241,11 +241,12 @@ extern "C" int scalce_memcpy_d2d(scalce_ctx *c, void *dst, const void *src, uint
   HIP_TRY(c, hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToDevice, (hipStream_t)stream));
   return SCALCE_OK;
 }
-extern "C" int scalce_batch_stats(const scalce_batch *b, uint32_t out[6]) {
+extern "C" int scalce_batch_stats(const scalce_batch *b, uint32_t out[7]) {
   if (!b || !out) return SCALCE_ERR_ARG;
   out[0] = b->ntie; out[1] = b->nev; out[2] = b->jacobi_iters; out[3] = b->nchunks;
   out[4] = b->order_run_members;
   out[5] = b->tie_fallback ? 1u : 0u;
+  out[6] = b->order_radix_fallback;
   return SCALCE_OK;
 }
 

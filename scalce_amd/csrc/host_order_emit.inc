@@ -34,8 +34,13 @@ extern "C" int scalce_batch_order(scalce_batch *b, void *stream) {
     ENSURE(b, w.S, sizeof(u64) * (N + 2));
     b->S_rows = ~0ull;
     ENSURE(b, w.chunk, sizeof(u32) * (N + 2));
-    const u32 max_chunks = 4096;
-    ENSURE(b, w.chunk_start, sizeof(u64) * (max_chunks + 2));
+    // No cap on the cuts (the reference has none, compress.cpp:708-715).  A chunk holds at least one record and every chunk but
+    // the last at least -B bytes, and no record is larger than rec_max: that bounds the chunks from the host, without a read-back.
+    const u64 rec_max = 1 + 255 + 40 + (u64)b->szr[0] + (u64)b->L[0] + (b->p.paired ? (u64)b->szr[1] + (u64)b->L[1] : 0);
+    u64 chunks_max = N * rec_max / (u64)b->p.bucket_set_size + 1;
+    if (chunks_max > N) chunks_max = N;
+    const u32 max_chunks = (u32)chunks_max + 1;  // (chunk_bounds_k makes fewer cuts than this)
+    ENSURE(b, w.chunk_start, sizeof(u64) * (chunks_max + 2));
     // (-Q / -f: rd.sz holds no quality bytes, compress.cpp:689-702 -- the cuts fall elsewhere than with qualities)
     RecSize rs{w.bucket.as<u32>(), c->d_bucket_level.as<u32>(), w.namelen.as<u8>(), b->L[0], b->L[1], b->p.paired, b->p.use_names, !b->nq};
     u64 *S = w.S.as<u64>();
@@ -43,6 +48,11 @@ extern "C" int scalce_batch_order(scalce_batch *b, void *stream) {
     LAUNCH(chunk_bounds_k, 1, 1, 0, s, S, N, (u64)b->p.bucket_set_size, max_chunks, w.chunk_start.as<u64>(), &b->d_scr->nchunks);
     int rc = read_u32(b, &b->d_scr->nchunks, &b->nchunks, 1, s);
     if (rc) return rc;
+    if (b->nchunks == CHUNKS_OVERFLOW) {
+      b->nchunks = 1;
+      set_err(c, "the -B rule cuts more than the %llu spill chunks the order stage allowed for", (unsigned long long)chunks_max);
+      return SCALCE_ERR_CAPACITY;
+    }
     if (b->nchunks > 1)
       LAUNCH(chunk_assign_k, cdiv(N, 256), 256, 0, s, N, w.chunk_start.as<u64>(), &b->d_scr->nchunks, w.chunk.as<u32>());
   }
@@ -56,9 +66,9 @@ extern "C" int scalce_batch_order(scalce_batch *b, void *stream) {
   int bits = 1;
   while ((1u << bits) < nb1 && bits < 31) bits++;
   int cbits = 0;
-  while (b->nchunks > 1 && (1u << cbits) < b->nchunks) cbits++;
-  // phase 1 on (key, read) pairs when bucket | chunk | 32 prefix bits fit 64 bits (always, short of millions of cores
-  // together with thousands of chunks): every pass then reads and writes sequentially.  The index-only passes below
+  while (b->nchunks > 1 && (1ull << cbits) < b->nchunks) cbits++;
+  // phase 1 on (key, read) pairs when bucket | chunk | 32 prefix bits fit 64 bits (always, short of a million cores
+  // together with more than 4096 chunks): every pass then reads and writes sequentially.  The index-only passes below
   // gather a digit through the index in every pass: 8 GB of sector fetches per pass at 50 M reads, and the scattered
   // accesses are what slows a coder launch running beside the order stage most (tools/coder_beside.py).
   const bool by_pairs = two_phase && PREFIX_BITS + cbits + bits <= 64;
@@ -88,7 +98,7 @@ extern "C" int scalce_batch_order(scalce_batch *b, void *stream) {
       flip();
     }
     if (b->nchunks > 1)
-      for (int sh = 0; (1u << sh) < b->nchunks; sh += 8) {
+      for (int sh = 0; (1ull << sh) < b->nchunks; sh += 8) {
         radix_pass(src, dst, (u32)N, DigitOfArray{w.chunk.as<u32>(), sh}, w.hist.as<u32>(), ws32, s);
         flip();
       }
@@ -99,6 +109,7 @@ extern "C" int scalce_batch_order(scalce_batch *b, void *stream) {
   }
   u32 *perm1 = const_cast<u32 *>(src);
   b->order_run_members = 0;
+  b->order_radix_fallback = 0;
   if (ndig1 < ndig) {
     // phase 2: records that still tie on (bucket, chunk, prefix) are sorted on the remaining digits, run by run
     ENSURE(b, w.run_head, N + 64);
@@ -128,6 +139,7 @@ extern "C" int scalce_batch_order(scalce_batch *b, void *stream) {
                w.packed[0].as<u8>(), w.endv.as<u16>(), b->L[0], b->stride[0], ndig1, ndig, any_large);
         u32 large = 0;
         { int rc = read_u32(b, any_large, &large, 1, s); if (rc) return rc; }
+        b->order_radix_fallback = large;
         small_done = large == 0;
       }
       if (!small_done) {
@@ -258,7 +270,7 @@ extern "C" int scalce_batch_emit(scalce_batch *b, void *stream) {
                     &w.line_end[0], &w.line_end[1], &w.tile[0], &w.tile[1], &w.tok_bucket, &w.tok_pos, &w.tie_index,
                     &w.tie_read, &w.tie_off, &w.tie_ncand, &w.cand_bucket, &w.cand_pos, &w.choice, &w.ev_off,
                     &w.ev_sorted, &w.ev_tmp, &w.ev_place, &w.chosen, &w.G, &w.cand_place,
-                    &w.bucket, &w.endv, &w.tokens, &w.chunk, &w.perm_a, &w.perm_b, &w.key_a, &w.key_b, &w.hist, &w.S,
+                    &w.bucket, &w.endv, &w.tokens, &w.chunk, &w.chunk_start, &w.perm_a, &w.perm_b, &w.key_a, &w.key_b, &w.hist, &w.S,
                     &w.run_head, &w.run_hcount, &w.run_rank, &w.runid, &w.run_items_a, &w.run_items_b, &w.run_pos};
     for (DBuf *d : dead)
       if (d->cap >= (256u << 20)) d->release();  // (the big ones; releasing dozens of small buffers only costs time)

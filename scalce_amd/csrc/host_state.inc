@@ -334,6 +334,7 @@ struct scalce_batch {
   bool mm_valid[2] = {false, false};  // the workspace's tile_mm[m] holds the symbol ranges of the piece ingested last
   bool names_from_sorted_cells = false;
   u32 order_run_members = 0;
+  u32 order_radix_fallback = 0;  // any_large as read back: phase 2 went through the radix passes (0: it did not, or did not run)
   DBuf out_reads[2], out_names, ac_tab[2], ac_tab8[2], ac_cum[2], ac_blocks[2], ac_sizes[2], ac_off[2], ac_desc, out_qual[2];
   AcBlockDesc *ac_desc_host = nullptr;  // block descriptors of the last coder launch this shard led: pinned, so that the
   u32 ac_desc_cap = 0;                  // asynchronous upload never reads memory the next launch is already rewriting

@@ -164,7 +164,10 @@ __global__ __launch_bounds__(256) void run_small_sort_k(u32 M, const u32 *pos_li
 
 // spill chunks (compress.cpp:702-715): running size of the records since the last dump; when it
 // reaches -B the current read closes the chunk.  rec_size is scanned inclusively into S; the
-// boundaries are found by one thread with binary searches (there are few chunks).
+// boundaries are found by one thread with one binary search per chunk.  There are few chunks at any -B in
+// use (a handful at the default of 4 GB); a -B of a few records' size makes that one thread walk as many
+// chunks as there are records, which is slow and still right: the cuts are never capped, `max_chunks` only
+// says how many entries chunk_start has (the host sizes it from the input so that the rule never gets there).
 struct RecSize {
   const u32 *bucket;
   const u32 *bucket_level;
@@ -177,6 +180,7 @@ struct RecSize {
     return sz + 40;  // + sizeof(bin_node), compress.cpp:702
   }
 };
+constexpr u32 CHUNKS_OVERFLOW = 0xFFFFFFFFu;  // chunk_bounds_k's count when chunk_start is too short for the cuts
 __global__ void chunk_bounds_k(const u64 *S /*exclusive prefix, S[n] = total*/, u64 n, u64 limit, u32 max_chunks,
                                u64 *chunk_start /*[max_chunks+1]*/, u32 *nchunks) {
   if (threadIdx.x || blockIdx.x) return;
@@ -195,6 +199,9 @@ __global__ void chunk_bounds_k(const u64 *S /*exclusive prefix, S[n] = total*/, 
     start = lo + 1;
     chunk_start[++c] = start;
   }
+  // out of entries with a cut still to make: said aloud (the host's bound on the chunks has fallen behind RecSize), never a
+  // last chunk that quietly takes the rest
+  if (start < n && c + 1 >= max_chunks && S[n] - S[start] >= limit) { *nchunks = CHUNKS_OVERFLOW; return; }
   if (chunk_start[c] < n || c == 0) c++;  // trailing partial chunk (compress.cpp:799-801)
   chunk_start[c] = n;
   *nchunks = c;

@@ -747,9 +747,10 @@ class Batch:
         self._check(self.L.scalce_batch_qual_window(self.h, mate, int(offset), int(nbytes), dst, stream))
 
     def stats(self):
-        a = (C.c_uint32 * 6)()
+        a = (C.c_uint32 * 7)()
         self._check(self.L.scalce_batch_stats(self.h, a))
-        return dict(tie_reads=a[0], events=a[1], jacobi_iters=a[2], chunks=a[3], order_run_members=a[4], tie_fallback=a[5])
+        return dict(tie_reads=a[0], events=a[1], jacobi_iters=a[2], chunks=a[3], order_run_members=a[4], tie_fallback=a[5],
+                    order_radix_fallback=a[6])
 
     def stage_reset(self, enable=True):
         self.L.scalce_batch_stage_reset(self.h, int(enable))

@@ -76,3 +76,63 @@ def craft_straddle(n, cum, total, rng, first2=(9, 12)):
         lo, hi = nl, nh
         out.append(pick)
     return np.array(out[:n], dtype=np.uint8), maxpend
+
+
+# ---- what the order stage sorts by, restated in numpy from the oracle's tokens (test_gpu_order_emit, test_gpu_scale) ----
+_CODE = np.zeros(256, dtype=np.uint64)
+for _i, _c in enumerate(b"ACGT"):
+    _CODE[_c] = _CODE[_c | 0x20] = _i   # every other letter counts as A (const.cpp:47-49)
+PREFIX_BASES = 16      # PREFIX_DIGITS * 4, kernels_order.hpp
+RUN_SMALL_MAX = 32     # kernels_order.hpp
+
+
+def key16(bases, end):
+    """The first 16 bases behind the core, padded with A past the read's end (_POS, reads.cpp:557-558), as one number."""
+    n, L = bases.shape
+    idx = np.asarray(end, dtype=np.int64)[:, None] + np.arange(PREFIX_BASES)[None, :]
+    c = _CODE[bases[np.arange(n)[:, None], np.minimum(idx, L - 1)]] * (idx < L)
+    return (c << (2 * (PREFIX_BASES - 1 - np.arange(PREFIX_BASES))).astype(np.uint64)[None, :]).sum(axis=1, dtype=np.uint64)
+
+
+def record_sizes(pat, pattern_lens, name_lens, L, L2=0):
+    """What a record adds to the open spill chunk (compress.cpp:689-702): name, rotated bases, qualities, mate 2, bin_node."""
+    level = np.where(pat >= 0, pattern_lens[np.maximum(pat, 0)], 0)
+    sz = 1 + np.asarray(name_lens, dtype=np.int64) + (L - level + 3) // 4 + L + 40
+    return sz + ((L2 + 3) // 4 + L2 if L2 else 0)
+
+
+def chunks_by_rule(sizes, limit):
+    """The -B rule (compress.cpp:708-715): the record with which the open chunk reaches `limit` bytes closes it.
+    -> (chunk of every record, number of chunks)"""
+    n = len(sizes)
+    S = np.concatenate([[0], np.cumsum(sizes)])
+    chunk = np.zeros(n, dtype=np.int32)
+    start = c = 0
+    while start < n:
+        r = min(int(np.searchsorted(S, S[start] + limit, side="left")), n)   # the chunk is [start, r)
+        chunk[start:r] = c
+        c += 1
+        start = r
+    return chunk, c
+
+
+def runs_in_order(perm, pat, chunk, key):
+    """Runs of records that tie on (bucket, chunk, 16-base prefix), along a permutation that has them side by side (any
+    order that is sorted by these three: the oracle's).  -> (first position, length) of every run, singles included"""
+    p = np.asarray(perm, dtype=np.int64)
+    chunk = np.zeros(len(p), dtype=np.int32) if chunk is None else chunk
+    same = (pat[p][1:] == pat[p][:-1]) & (chunk[p][1:] == chunk[p][:-1]) & (key[p][1:] == key[p][:-1])
+    starts = np.flatnonzero(np.concatenate([[True], ~same]))
+    return starts, np.diff(np.append(starts, len(p)))
+
+
+def order_expectation(bases, pat, end, perm, chunk=None):
+    """What scalce_batch_stats must report for this input: (records in runs of two or more = order_run_members, whether a
+    run of more than RUN_SMALL_MAX has a member with bases behind the prefix = order_radix_fallback != 0), and the runs."""
+    L = bases.shape[1]
+    starts, lens = runs_in_order(perm, pat, chunk, key16(bases, end))
+    if L <= PREFIX_BASES:   # the prefix is the whole key: no second phase
+        return 0, False, starts, lens
+    behind = (end + PREFIX_BASES < L)[np.asarray(perm, dtype=np.int64)]
+    fallback = any(behind[s:s + n].any() for s, n in zip(starts[lens > RUN_SMALL_MAX], lens[lens > RUN_SMALL_MAX]))
+    return int(lens[lens > 1].sum()), fallback, starts, lens

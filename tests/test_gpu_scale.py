@@ -8,7 +8,7 @@ import pytest
 
 import bigtable
 import oraclelib as O
-from gpu_util import device_bytes
+from gpu_util import chunks_by_rule, device_bytes, order_expectation, record_sizes
 from scalce_amd import host, synth
 
 pytestmark = pytest.mark.gpu
@@ -24,21 +24,72 @@ def run_tokens(ctx, bases, L):
     return b
 
 
-def test_million_core_table():
+@pytest.fixture(scope="module")
+def million():
+    """the table of a million cores, once for the module: (cores by length, device context, oracle trie)"""
+    blob, vals = bigtable.build()
+    return vals, host.Context(0, patterns_bin=blob), O.Trie(blob=blob)
+
+
+def test_million_core_table(million):
     """1 M cores of 12..32 bases = 9.9 M automaton states (the k-mer tables in LDS only cover states of depth <= 7: four of
     five transitions go back to 16-byte rows in L2 / HBM): tokens and order against the oracle's trie walk."""
-    blob, vals = bigtable.build()
-    ctx = host.Context(0, patterns_bin=blob)
+    vals, ctx, trie = million
     assert ctx.n_patterns == 1_000_000 and ctx.n_states > 9_000_000
     n, L = 300_000, 100
     bases = bigtable.reads_with_cores(n, L, vals)
     b = run_tokens(ctx, bases, L)
-    trie = O.Trie(blob=blob)
     pat, end = trie.tokenize(bases)
     assert (pat >= 0).mean() > 0.8
     tok = b.output(host.OUT_TOKENS, 0, np.int32).reshape(-1, 2)
     assert (tok[:, 0] == pat).all() and (tok[:, 1] == end).all()
     assert (b.output(host.OUT_PERM, 0, np.uint32) == trie.order(bases, pat, end)).all()
+
+
+def test_million_cores_and_thousands_of_chunks_sort_on_indices(million):
+    """Bucket (20 bits for a million cores), chunk (13 bits for more than 4096 of them) and the 32 prefix bits do not fit one
+    64-bit key: phase 1 runs on indices, digit by digit through the permutation, and the runs are found by comparing
+    neighbours' buckets, chunks and prefixes (run_heads_k).  -B 1000 cuts 30 000 reads into about 5000 chunks of six; exact
+    and near duplicates are neighbours in the input, so that some share a chunk and form runs."""
+    vals, ctx, trie = million
+    n, L, B = 30_000, 100, 1000
+    rng = np.random.default_rng(8)
+    bases = bigtable.reads_with_cores(n, L, vals, seed=6)
+    src = rng.choice(n - 2, size=6000, replace=False)
+    exact, near = src[:3000], src[3000:]
+    bases[exact + 1] = bases[exact]
+    bases[near + 1] = bases[near]
+    bases[near + 1, L - 1 - rng.integers(0, 8, size=len(near))] = ord("G")   # near: the same but for one of the last bases
+    pat, end = trie.tokenize(bases)
+    plens = np.repeat([ln for ln, _ in bigtable.GROUPS_1M], [cnt for _, cnt in bigtable.GROUPS_1M])
+    probe = rng.integers(0, len(plens), size=2000)
+    assert all(len(trie.pattern(int(p))) == plens[p] for p in probe)
+    names = np.array([2 + len(str(i)) for i in range(n)])   # "s.<i>"
+    chunk, nchunks = chunks_by_rule(record_sizes(pat, plens, names, L), B)
+    assert nchunks > 4096
+    bits = cbits = 1
+    while (1 << bits) < ctx.n_buckets + 1:
+        bits += 1
+    while (1 << cbits) < nchunks:
+        cbits += 1
+    assert 32 + cbits + bits > 64, "bucket | chunk | prefix fit one key: this is the sort on (key, read) pairs"
+    perm = trie.order(bases, pat, end, chunk)
+    members, fallback, _, lens = order_expectation(bases, pat, end, perm, chunk)
+    assert members > 1000 and not fallback
+    quals = np.full(bases.shape, ord("I"), dtype=np.uint8)
+    fq = synth.fastq_bytes_fast(bases, quals)
+    t = device_bytes(fq)
+    b = host.Batch(ctx, L, n + 8, len(fq) + 64, bucket_set_size=B)
+    b.front(t.data_ptr(), len(fq))
+    b.finish()
+    st = b.stats()
+    tok = b.output(host.OUT_TOKENS, 0, np.int32).reshape(-1, 2)
+    assert (tok[:, 0] == pat).all() and (tok[:, 1] == end).all()
+    assert st["chunks"] == nchunks
+    got = b.output(host.OUT_PERM, 0, np.uint32)
+    bad = np.flatnonzero(got != perm)
+    assert len(bad) == 0, f"permutation differs at {len(bad)} of {n} positions, first {bad[:5]} ({st})"
+    assert st["order_run_members"] == members > 0 and st["order_radix_fallback"] == 0
 
 
 def stress_inputs(kind, n, L, rng):
