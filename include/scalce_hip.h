@@ -219,7 +219,8 @@ int scalce_batch_tokenize_settle(scalce_batch *b, const uint64_t *d_prior_counts
  * not tokenized (record sizes depend on the core's length only).  *ncuts == cap says that the list may be cut short: the
  * cuts returned are the first cap of the plan, *carry_out is then the size of every row behind the last of them and no
  * carry.  A caller passes a cap above any plan it accepts and takes *ncuts == cap for SCALCE_ERR_CAPACITY
- * (scalce_sharded_compress: 4000 cuts per rank).  A batch without rows: no cuts, *carry_out = carry_in. */
+ * (scalce_sharded_compress: SCALCE_SHARD_CUT_CAP cuts per rank).  A batch without rows: no cuts, *carry_out = carry_in. */
+#define SCALCE_SHARD_CUT_CAP 4000
 int scalce_batch_chunk_plan(scalce_batch *b, uint64_t carry_in, uint64_t *cuts_host, uint32_t cap, uint32_t *ncuts,
                             uint64_t *carry_out, void *stream);
 /* Byte offset, in the text of the piece ingested last, at which record `row` (0 .. rows of that piece) begins; runs on
@@ -483,8 +484,8 @@ int scalce_stream_decompress(scalce_ctx *ctx, const scalce_unpack_params *p, sca
  * archive of a sharded run is byte for byte the archive of the same input on one GPU -- and of the reference at -T 1 with
  * the same -B -- for any number of ranks: rank boundaries are moved to the nearest spill-chunk boundary of the run-wide -B
  * rule (records change owner as text, once), so that "rank-major inside a bucket" IS the merge order of compress.cpp:104-159.
- * -B must be set (the reference's default is 4G) and must cut the run at least once; ranks whose share is smaller than a
- * chunk may end up without records. */
+ * -B must be set (the reference's default is 4G).  Ranks whose share is smaller than a chunk may end up without records; a
+ * run that -B does not cut at all is ONE chunk, whose rows all go to rank 0 (scalce_shard_plan_boundaries). */
 typedef struct scalce_comm scalce_comm;
 #define SCALCE_COMM_ID_BYTES 128
 int scalce_comm_unique_id(uint8_t id[SCALCE_COMM_ID_BYTES]);  /* rank 0 makes it, the launcher hands it to every rank */
@@ -545,12 +546,21 @@ int scalce_sharded_compress(scalce_comm *comm, scalce_ctx *ctx, scalce_batch *b,
                             scalce_shard_result *result);
 void scalce_shard_result_free(scalce_shard_result *r);
 /* The host-side plan math of a sharded run on its own (no device needed; see sharded.cpp): rank boundaries g[0..world]
- * moved to the nearest cut of the run-wide -B rule, and the deal of the run-wide reordered quality stream in contiguous
- * ranges of whole 10 MiB blocks. */
+ * moved to the nearest cut of the run-wide -B rule; the deal of the run-wide reordered quality stream in contiguous
+ * ranges of whole 10 MiB blocks; the trigram counters (p0 * 80 + p1) * 80 + s that straddle the boundary in front of a
+ * rank's original piece (nsym[r] symbols per rank, edges + r * edge_stride = its scalce_batch_qinput_edges); and the
+ * pieces of _plan_blocks split into those that read the local stream (own_src relative to *local_off) and those that
+ * read a receive buffer holding only what other ranks sent.  SCALCE_ERR_ARG on arguments or a plan that make no sense. */
 int scalce_shard_plan_boundaries(int world, const uint64_t *g, const uint64_t *cuts_sorted, uint64_t ncuts, uint64_t *gn);
 int scalce_shard_plan_blocks(int world, int rank, uint32_t nb1, const uint64_t *counts /*[world][nb1]*/, uint64_t read_len,
                              uint64_t *send_bytes, uint64_t *recv_bytes, uint64_t *lo, uint64_t *hi, uint64_t *piece_src,
                              uint64_t *piece_dst, uint64_t *npieces);
+int scalce_shard_plan_edge_trigrams(int world, int rank, const uint64_t *nsym /*[world]*/, const uint8_t *edges, uint64_t edge_stride,
+                                    uint32_t keys[2], uint32_t *nkeys);
+int scalce_shard_plan_own_pieces(int world, int rank, const uint64_t *send_bytes, const uint64_t *recv_bytes, const uint64_t *piece_src,
+                                 const uint64_t *piece_dst, uint64_t npieces, uint64_t *own_src, uint64_t *own_dst, uint64_t *nown,
+                                 uint64_t *own_total, uint64_t *local_off, uint64_t *other_src, uint64_t *other_dst, uint64_t *nother,
+                                 uint64_t *other_total);
 
 /* ---- shards in flight (pipeline.cpp) -----------------------------------------------------------------------------
  * The reference keeps its cores busy by handing -T blocks of a batch to coder threads while the reader goes on

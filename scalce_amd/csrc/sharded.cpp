@@ -33,7 +33,7 @@ void scalce_set_last_error(scalce_ctx *c, const char *msg);  // (host_state.inc:
 namespace {
 
 typedef uint64_t u64;
-constexpr u64 AC_BLOCK = 10ull * 1024 * 1024;
+constexpr uint32_t RESULT_MAGIC = 0x5CA1CE5Du;  // scalce_shard_result::magic of a result that this file filled
 
 __global__ void add_counts_into_k(uint32_t nb1, const u64 *mine, u64 *acc) {
   const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
@@ -158,8 +158,8 @@ extern "C" int scalce_shard_plan_blocks(int world, int rank, uint32_t nb1, const
   u64 total_reads = 0;
   for (int r = 0; r < world; r++)
     for (uint32_t k = 0; k < nb1; k++) { Cg[k] += C[(size_t)r * nb1 + k]; total_reads += C[(size_t)r * nb1 + k]; }
-  const u64 total = total_reads * L, nblk = (total + AC_BLOCK - 1) / AC_BLOCK;
-  auto lo_of = [&](int d) { return std::min<u64>(total, ((u64)d * nblk / world) * AC_BLOCK); };
+  const u64 total = total_reads * L, nblk = (total + SCALCE_AC_BLOCK - 1) / SCALCE_AC_BLOCK;
+  auto lo_of = [&](int d) { return std::min<u64>(total, ((u64)d * nblk / world) * SCALCE_AC_BLOCK); };
   std::vector<u64> g0((size_t)world * nb1);  // run-wide start of every (rank, bucket) piece
   {
     u64 base = 0;
@@ -199,9 +199,63 @@ extern "C" int scalce_shard_plan_blocks(int world, int rank, uint32_t nb1, const
   if (npieces) *npieces = np;
   return SCALCE_OK;
 }
+// The trigrams that straddle the boundary in front of `rank`'s ORIGINAL piece (qualities.cpp:179-198: prev[] runs across reads):
+// nsym[r] = symbols of rank r's piece, edges + r * edge_stride = its four edge symbols in scalce_batch_qinput_edges' layout
+// ([0..1] the first two, [2..3] the last two; a piece of one symbol is read from [0] only).  keys[0 .. *nkeys) = the zero, one
+// or two counters (p0 * 80 + p1) * 80 + s that this rank adds to its own.  Pieces in front may be empty or short: the two
+// symbols in front then come from several ranks.
+extern "C" int scalce_shard_plan_edge_trigrams(int world, int rank, const uint64_t *nsym, const uint8_t *edges, uint64_t edge_stride,
+                                               uint32_t keys[2], uint32_t *nkeys) {
+  if (world < 1 || rank < 0 || rank >= world || !nsym || !edges || edge_stride < 4 || !keys || !nkeys) return SCALCE_ERR_ARG;
+  *nkeys = 0;
+  const u64 own = nsym[rank];
+  if (rank > 0 && own) {
+    std::vector<uint32_t> before;  // up to two symbols in front of the piece, nearest last
+    for (int r = rank - 1; r >= 0 && before.size() < 2; r--) {
+      const u64 nsy = nsym[r];
+      const uint8_t *e = edges + (size_t)r * edge_stride;
+      if (nsy >= 2) { if (before.empty()) { before.push_back(e[3]); before.push_back(e[2]); } else before.push_back(e[3]); }
+      else if (nsy == 1) before.push_back(e[0]);
+    }
+    const uint8_t *me = edges + (size_t)rank * edge_stride;
+    const uint32_t s0 = me[0], s1 = own >= 2 ? me[1] : 0xFFFFu;
+    // before[0] = the symbol right in front (p1), before[1] = the one before that (p0)
+    if (before.size() >= 2 && s0 < 80 && before[0] < 80 && before[1] < 80) keys[(*nkeys)++] = (before[1] * 80 + before[0]) * 80 + s0;
+    if (before.size() >= 1 && own >= 2 && s0 < 80 && s1 < 80 && before[0] < 80) keys[(*nkeys)++] = (before[0] * 80 + s0) * 80 + s1;
+  }
+  return SCALCE_OK;
+}
+// The pieces of scalce_shard_plan_blocks split by where their bytes are read.  What stays on a rank never goes through the
+// transport, so the receive buffer only holds what OTHER ranks send, in rank order.  Pieces are source-major: [from ranks in
+// front | own | from ranks behind].  The own ones read the local stream: own_src is relative to the start of the own range
+// there, *local_off is that start.  The others read the compacted receive buffer: other_src has the own bytes taken out.
+// Every list holds up to npieces entries.  SCALCE_ERR_ARG too when the plan disagrees with itself: send_bytes[rank] is not
+// recv_bytes[rank], or the pieces of either kind do not add up to its bytes.
+extern "C" int scalce_shard_plan_own_pieces(int world, int rank, const uint64_t *send_bytes, const uint64_t *recv_bytes,
+                                            const uint64_t *piece_src, const uint64_t *piece_dst, uint64_t npieces, uint64_t *own_src,
+                                            uint64_t *own_dst, uint64_t *nown, uint64_t *own_total, uint64_t *local_off,
+                                            uint64_t *other_src, uint64_t *other_dst, uint64_t *nother, uint64_t *other_total) {
+  if (world < 1 || rank < 0 || rank >= world || !send_bytes || !recv_bytes || !nown || !own_total || !local_off || !nother || !other_total)
+    return SCALCE_ERR_ARG;
+  if (npieces && (!piece_src || !piece_dst || !own_src || !own_dst || !other_src || !other_dst)) return SCALCE_ERR_ARG;
+  u64 self_at = 0, recv_total = 0;  // where the own bytes would lie in a full receive buffer
+  *local_off = 0;                   // where they lie in the local stream
+  for (int r = 0; r < rank; r++) { self_at += recv_bytes[r]; *local_off += send_bytes[r]; }
+  for (int r = 0; r < world; r++) recv_total += recv_bytes[r];
+  const u64 self_bytes = recv_bytes[rank];
+  *nown = *nother = *own_total = *other_total = 0;
+  if (self_bytes != send_bytes[rank]) return SCALCE_ERR_ARG;
+  for (u64 i = 0; i < npieces; i++) {
+    const u64 len = (i + 1 < npieces ? piece_src[i + 1] : recv_total) - piece_src[i];
+    if (piece_src[i] >= self_at && piece_src[i] < self_at + self_bytes) { own_src[*nown] = piece_src[i] - self_at; own_dst[(*nown)++] = piece_dst[i]; *own_total += len; }
+    else { other_src[*nother] = piece_src[i] < self_at ? piece_src[i] : piece_src[i] - self_bytes; other_dst[(*nother)++] = piece_dst[i]; *other_total += len; }
+  }
+  if (npieces && (*own_total != self_bytes || *other_total != recv_total - self_bytes)) return SCALCE_ERR_ARG;
+  return SCALCE_OK;
+}
 
 extern "C" void scalce_shard_result_free(scalce_shard_result *r) {
-  if (!r || r->magic != 0x5CA1CE5Du) return;
+  if (!r || r->magic != RESULT_MAGIC) return;
   free(r->counts);
   free(r->name_bytes);
   r->counts = r->name_bytes = nullptr;
@@ -209,86 +263,94 @@ extern "C" void scalce_shard_result_free(scalce_shard_result *r) {
   r->magic = 0;
 }
 
-extern "C" int scalce_sharded_compress(scalce_comm *comm, scalce_ctx *ctx, scalce_batch *b, const uint8_t *d_text1, uint64_t n1,
-                                       const uint8_t *d_text2, uint64_t n2, int flags, void *stream, void *coder_stream,
-                                       scalce_shard_result *res) {
-  if (!comm || !ctx || !b || !res) return SCALCE_ERR_ARG;
-  {
-    scalce_params bp;
-    if (scalce_batch_params(b, &bp) != SCALCE_OK) return SCALCE_ERR_ARG;
-    if (bp.fasta || bp.no_qualities) {
-      scalce_set_last_error(ctx, "records without qualities (-f / -Q) are compressed on one GPU: sharded runs do not take them");
-      return SCALCE_ERR_ARG;
-    }
-    if (bp.interleaved) {
-      scalce_set_last_error(ctx, "interleaved input (-i) is compressed on one GPU: sharded runs do not take it");
-      return SCALCE_ERR_ARG;
-    }
+namespace {
+
+u64 clampu(u64 x, u64 a, u64 b) { return x < a ? a : (x > b ? b : x); }
+
+// Step 3: where the text of the other ranks lands in the receive buffer.  Everything but the rows that stay goes through the
+// transport: what comes from the ranks in front (before_self bytes) lies at 0, what comes from the ranks behind (after_self
+// bytes) at the offset returned -- the two parts land 16-byte aligned (the ingest kernels read their text in aligned 16-byte
+// words).  recv_off[rank] is an offset like any other: nothing is received there.
+u64 exchange_recv_layout(int W, int rank, const std::vector<uint64_t> &recvb, std::vector<uint64_t> &recv_off, u64 &before_self, u64 &after_self) {
+  before_self = after_self = 0;
+  for (int src = 0; src < W; src++) { if (src < rank) before_self += recvb[src]; else if (src > rank) after_self += recvb[src]; }
+  const u64 back_at = (before_self + 15) & ~15ull;
+  u64 fa = 0, ba = back_at;
+  for (int r = 0; r < W; r++) {
+    if (r < rank) { recv_off[r] = fa; fa += recvb[r]; } else { recv_off[r] = ba; ba += r == rank ? 0 : recvb[r]; }
   }
-  hipStream_t s = (hipStream_t)stream;
-  const int W = scalce_comm_world(comm), rank = scalce_comm_rank(comm);
-  if (W > 64) return SCALCE_ERR_ARG;
-  {  // a result of an earlier call on this slot keeps its buffers; everything else starts from zero
-    scalce_shard_result keep = *res;
-    const bool reuse = res->magic == 0x5CA1CE5Du && res->world == W && res->nb1 == (uint32_t)scalce_patterns_buckets(ctx) + 1;
-    memset(res, 0, sizeof *res);
-    if (reuse) {
-      res->counts = keep.counts;
-      res->name_bytes = keep.name_bytes;
-      memcpy(res->keep, keep.keep, sizeof keep.keep);
-      memcpy(res->keep_bytes, keep.keep_bytes, sizeof keep.keep_bytes);
-    }
-    res->magic = 0x5CA1CE5Du;
-  }
-  res->world = W;
-  res->rank = rank;
-  // The reordered q' stream of this call is only passed on (step 8): it lives in the workspace the batch shares with the other
-  // shards in flight, not in the batch -- 5 GB less per slot at 50 M reads of 100 bp.  (Not under -A: the stream is the output.)
-  struct StreamScratch {
-    scalce_batch *b; bool on;
-    ~StreamScratch() { if (on) scalce_batch_set_stream_scratch(b, 0); }
-  } stream_scratch{b, scalce_batch_set_stream_scratch(b, 1) == SCALCE_OK};
-  static thread_local std::string last_error;
+  return back_at;
+}
+
+// One call of scalce_sharded_compress: what its steps share, and one member function per step, in the order they run.
+struct ShardRun {
+  scalce_comm *const comm;
+  scalce_ctx *const ctx;
+  scalce_batch *const b;
+  scalce_shard_result *const res;
+  const hipStream_t s;
+  const int W, rank;
+  const uint8_t *const text[2];
+  const u64 nbytes[2];
+  const int nm;
+  int L[2] = {0, 0};  // symbols per row
+  DevMem mem;
+  u64 *d_small = nullptr, *d_gather = nullptr;  // a rank's words of a small all-gather / everybody's
+  Fail local_err{"", 0};
+  uint32_t nb1 = 0;
+  u64 N0 = 0, N = 0;             // rows of the own piece as it was handed in / of the rows held once the boundaries have moved
+  std::vector<u64> meta;         // of every rank: rows, L[0], L[1], status of the first pass
+  std::vector<u64> g, gn;        // run-wide index of every rank's first record: as handed in / moved to the nearest cut
+  std::vector<u64> cuts_global;  // run-wide rows in front of which a chunk begins
+  uint8_t edge[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
+  uint32_t *d_table = nullptr;
   // SCALCE_TRACE=1: where a rank's time goes (the stream is drained at every mark: for looking, not for timing runs)
   const bool trace = getenv("SCALCE_TRACE") != nullptr;
   double t_last = 0;
-  auto now = []() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec + 1e-9 * ts.tv_nsec; };
-  auto mark = [&](const char *what) {
+
+  ShardRun(scalce_comm *comm, scalce_ctx *ctx, scalce_batch *b, scalce_shard_result *res, hipStream_t s, int W, int rank, const uint8_t *d_text1,
+           uint64_t n1, const uint8_t *d_text2, uint64_t n2)
+      : comm(comm), ctx(ctx), b(b), res(res), s(s), W(W), rank(rank), text{d_text1, d_text2}, nbytes{n1, n2}, nm(d_text2 ? 2 : 1) {}
+
+  void mark(const char *what) {
     if (!trace) return;
     hipStreamSynchronize(s);
-    const double t = now();
+    timespec ts;
+    clock_gettime(CLOCK_MONOTONIC, &ts);
+    const double t = ts.tv_sec + 1e-9 * ts.tv_nsec;
     if (t_last > 0) fprintf(stderr, "  [rank %d] %-28s %8.2f ms\n", rank, what, (t - t_last) * 1e3);
     t_last = t;
-  };
-  mark("start");
-  try {
-    DevMem mem;
-    const uint8_t *text[2] = {d_text1, d_text2};
-    u64 nbytes[2] = {n1, n2};
-    const void *dp = nullptr;
-    uint64_t nb = 0;
-    // ---- 1. first pass over the own piece: rows + quality counters, no tie-break yet
-    // A failure that only ONE rank sees -- a malformed record in its byte range, a read of another length, a buffer that
-    // is too small -- must not leave the others waiting in the next collective for ever.  Rank-local work runs under
-    // local(): what it throws is kept, the rank goes on to the next exchange with empty hands, and the status travels with
-    // an exchange that happens anyway (or with agree(), one word per rank) -- then every rank throws together.
-    Fail local_err{"", 0};
-    auto local = [&](auto &&fn) {
-      if (local_err.rc) return;
-      try { fn(); } catch (const Fail &f) { local_err = f; if (!local_err.rc) local_err.rc = SCALCE_ERR_HIP; }
-    };
-    auto together = [&](const std::vector<u64> &status, size_t stride, size_t at, const char *where) {
-      for (int r = 0; r < W; r++)
-        if (status[(size_t)r * stride + at]) {
-          if (r == rank && local_err.rc) throw local_err;
-          throw Fail{std::string("rank ") + std::to_string(r) + " failed (" + where + "); see its message", (int)status[(size_t)r * stride + at]};
-        }
-      if (local_err.rc) throw local_err;  // (cannot happen: the own status was in the exchange)
-    };
+  }
+  // A failure that only ONE rank sees -- a malformed record in its byte range, a read of another length, a buffer that
+  // is too small -- must not leave the others waiting in the next collective for ever.  Rank-local work runs under
+  // local(): what it throws is kept, the rank goes on to the next exchange with empty hands, and the status travels with
+  // an exchange that happens anyway (or with agree(), one word per rank) -- then every rank throws together.
+  template <typename F> void local(F &&fn) {
+    if (local_err.rc) return;
+    try { fn(); } catch (const Fail &f) { local_err = f; if (!local_err.rc) local_err.rc = SCALCE_ERR_HIP; }
+  }
+  void together(const std::vector<u64> &status, size_t stride, size_t at, const char *where) {
+    for (int r = 0; r < W; r++)
+      if (status[(size_t)r * stride + at]) {
+        if (r == rank && local_err.rc) throw local_err;
+        throw Fail{std::string("rank ") + std::to_string(r) + " failed (" + where + "); see its message", (int)status[(size_t)r * stride + at]};
+      }
+    if (local_err.rc) throw local_err;  // (cannot happen: the own status was in the exchange)
+  }
+  void agree(const char *where) {  // one status word per rank; a run of one rank has nobody to ask
+    if (W == 1) {
+      if (local_err.rc) throw local_err;
+      return;
+    }
+    u64 mine = (u64)local_err.rc;
+    std::vector<u64> all = gather_host<u64>(comm, &mine, 1, d_small, d_gather, s);
+    together(all, 1, 0, where);
+  }
+
+  // ---- 1. first pass over the own piece: rows + quality counters, no tie-break yet
+  void first_pass() {
+    mark("start");
     uint64_t used[2] = {0, 0};
-    u64 N0 = 0;
-    const int nm = text[1] ? 2 : 1;
-    int L[2] = {0, 0};
     local([&] {
       SH_RC(ctx, scalce_batch_reset(b));
       SH_RC(ctx, scalce_batch_append(b, text[0], nbytes[0], text[1], nbytes[1], SCALCE_APPEND_FINAL | SCALCE_APPEND_NO_TOKENIZE, used, s));
@@ -303,79 +365,68 @@ extern "C" int scalce_sharded_compress(scalce_comm *comm, scalce_ctx *ctx, scalc
     });
     if (local_err.rc) N0 = 0;
     mark("first pass (ingest+quality)");
-    const uint32_t nb1 = (uint32_t)scalce_patterns_buckets(ctx) + 1;
+    nb1 = (uint32_t)scalce_patterns_buckets(ctx) + 1;
     res->nb1 = nb1;
-    u64 *d_small = mem.alloc<u64>(4096 + 64 * (size_t)W);
-    u64 *d_gather = mem.alloc<u64>((size_t)W * 4096 + (size_t)W * 64 * W);
-    auto agree = [&](const char *where) {  // one status word per rank
-      u64 mine = (u64)local_err.rc;
-      std::vector<u64> all = gather_host<u64>(comm, &mine, 1, d_small, d_gather, s);
-      together(all, 1, 0, where);
-    };
+    d_small = mem.alloc<u64>(4096 + 64 * (size_t)W);
+    d_gather = mem.alloc<u64>((size_t)W * 4096 + (size_t)W * 64 * W);
     // rows and read lengths of everyone (a rank without reads learns the read length here), and how the first pass went
-    std::vector<u64> meta;
-    {
-      u64 mine[4] = {N0, (u64)L[0], (u64)L[1], (u64)local_err.rc};
-      meta = gather_host<u64>(comm, mine, 4, d_small, d_gather, s);
-      together(meta, 4, 3, "first pass over its piece of the input");
-      for (int r = 0; r < W; r++)
-        for (int m = 0; m < nm; m++) {
-          const int Lr = (int)meta[4 * r + 1 + m];
-          if (!L[m] && Lr) L[m] = Lr;
-          // every rank sees the same table: they all stop here together (the reference: compress.cpp:628-634)
-          if (Lr && L[m] && Lr != L[m]) throw Fail{"(ERROR) reads of different lengths in the input (" + std::to_string(L[m]) + " vs " + std::to_string(Lr) + ")", SCALCE_ERR_FORMAT};
-        }
-    }
-    std::vector<u64> g(W + 1, 0);  // run-wide index of every rank's first record
+    u64 mine[4] = {N0, (u64)L[0], (u64)L[1], (u64)local_err.rc};
+    meta = gather_host<u64>(comm, mine, 4, d_small, d_gather, s);
+    together(meta, 4, 3, "first pass over its piece of the input");
+    for (int r = 0; r < W; r++)
+      for (int m = 0; m < nm; m++) {
+        const int Lr = (int)meta[4 * r + 1 + m];
+        if (!L[m] && Lr) L[m] = Lr;
+        // every rank sees the same table: they all stop here together (the reference: compress.cpp:628-634)
+        if (Lr && L[m] && Lr != L[m]) throw Fail{"(ERROR) reads of different lengths in the input (" + std::to_string(L[m]) + " vs " + std::to_string(Lr) + ")", SCALCE_ERR_FORMAT};
+      }
+    g.assign(W + 1, 0);
     for (int r = 0; r < W; r++) g[r + 1] = g[r] + meta[4 * r];
-    const u64 total_reads = g[W];
-    res->reads_total = total_reads;
+    res->reads_total = g[W];
     // the first two and last two q' symbols of the own piece: trigrams that straddle a rank boundary (step 4)
-    uint8_t edge[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
     for (int m = 0; m < nm; m++) {
       uint64_t ns = 0;
       SH_RC(ctx, scalce_batch_qinput_edges(b, m, edge[m], &ns, nullptr, s));
-      nb = ns;
     }
-    // ---- 2. spill chunks of the run-wide -B rule: a chain of carries, then everybody learns every cut
-    std::vector<u64> cuts_global;  // run-wide rows in front of which a chunk begins
-    {
-      const uint32_t CAP = 4000;
-      std::vector<uint64_t> cuts(CAP);
-      uint32_t nc = 0;
-      uint64_t carry_out = 0;
-      local([&] { SH_RC(ctx, scalce_batch_chunk_plan(b, 0, cuts.data(), CAP, &nc, &carry_out, s)); });  // sizes of all rows: every rank at once
-      u64 carry_in = 0;
-      for (int k = 0; k < W; k++) {  // rank k can cut once it knows what rank k - 1 left open
-        if (k == rank) local([&] { SH_RC(ctx, scalce_batch_chunk_plan(b, carry_in, cuts.data(), CAP, &nc, &carry_out, s)); });
-        if (W > 1) {
-          u64 mine = k == rank ? carry_out : 0;
-          std::vector<u64> all = gather_host<u64>(comm, &mine, 1, d_small, d_gather, s);
-          if (rank == k + 1) carry_in = all[k];
-        }
+  }
+
+  // ---- 2. spill chunks of the run-wide -B rule: a chain of carries, then everybody learns every cut
+  void spill_chunk_cuts() {
+    const uint32_t CAP = SCALCE_SHARD_CUT_CAP;
+    std::vector<uint64_t> cuts(CAP);
+    uint32_t nc = 0;
+    uint64_t carry_out = 0;
+    local([&] { SH_RC(ctx, scalce_batch_chunk_plan(b, 0, cuts.data(), CAP, &nc, &carry_out, s)); });  // sizes of all rows: every rank at once
+    u64 carry_in = 0;
+    for (int k = 0; k < W; k++) {  // rank k can cut once it knows what rank k - 1 left open
+      if (k == rank) local([&] { SH_RC(ctx, scalce_batch_chunk_plan(b, carry_in, cuts.data(), CAP, &nc, &carry_out, s)); });
+      if (W > 1) {
+        u64 mine = k == rank ? carry_out : 0;
+        std::vector<u64> all = gather_host<u64>(comm, &mine, 1, d_small, d_gather, s);
+        if (rank == k + 1) carry_in = all[k];
       }
-      local([&] { if (nc >= CAP) throw Fail{"more than 4000 spill chunks on one rank: -B is too small for this input", SCALCE_ERR_CAPACITY}; });
-      if (local_err.rc) nc = 0;
-      std::vector<u64> mine(CAP + 2, 0);
-      mine[0] = nc;
-      mine[CAP + 1] = (u64)local_err.rc;
-      for (uint32_t i = 0; i < nc; i++) mine[1 + i] = g[rank] + cuts[i];
-      std::vector<u64> all = gather_host<u64>(comm, mine.data(), CAP + 2, d_small, d_gather, s);
-      together(all, CAP + 2, CAP + 1, "spill-chunk plan");
-      for (int r = 0; r < W; r++)
-        for (u64 i = 0; i < all[(size_t)r * (CAP + 2)]; i++) cuts_global.push_back(all[(size_t)r * (CAP + 2) + 1 + i]);
-      std::sort(cuts_global.begin(), cuts_global.end());
-      res->chunks_total = (uint32_t)cuts_global.size() + ((cuts_global.empty() || cuts_global.back() < total_reads) ? 1 : 0);
     }
+    local([&] { if (nc >= CAP) throw Fail{"more than " + std::to_string(CAP) + " spill chunks on one rank: -B is too small for this input", SCALCE_ERR_CAPACITY}; });
+    if (local_err.rc) nc = 0;
+    std::vector<u64> mine(CAP + 2, 0);
+    mine[0] = nc;
+    mine[CAP + 1] = (u64)local_err.rc;
+    for (uint32_t i = 0; i < nc; i++) mine[1 + i] = g[rank] + cuts[i];
+    std::vector<u64> all = gather_host<u64>(comm, mine.data(), CAP + 2, d_small, d_gather, s);
+    together(all, CAP + 2, CAP + 1, "spill-chunk plan");
+    for (int r = 0; r < W; r++)
+      for (u64 i = 0; i < all[(size_t)r * (CAP + 2)]; i++) cuts_global.push_back(all[(size_t)r * (CAP + 2) + 1 + i]);
+    std::sort(cuts_global.begin(), cuts_global.end());
+    res->chunks_total = (uint32_t)cuts_global.size() + ((cuts_global.empty() || cuts_global.back() < g[W]) ? 1 : 0);
     mark("record sizes + cuts");
-    // ---- 3. rank boundaries move to the nearest cut; the records in between change owner as text
-    std::vector<u64> gn(W + 1);
-    {
-      const int prc = scalce_shard_plan_boundaries(W, g.data(), cuts_global.data(), cuts_global.size(), gn.data());
-      // (every rank computes the same plan from the same cuts: they all leave here together)
-      if (prc) throw Fail{"internal: rank boundaries could not be planned", SCALCE_ERR_ARG};
-    }
-    auto clampu = [](u64 x, u64 a, u64 b) { return x < a ? a : (x > b ? b : x); };
+  }
+
+  // ---- 3. rank boundaries move to the nearest cut; the records in between change owner as text
+  void move_boundaries_and_exchange_rows() {
+    gn.assign(W + 1, 0);
+    // (every rank computes the same plan from the same cuts: they all leave here together)
+    if (scalce_shard_plan_boundaries(W, g.data(), cuts_global.data(), cuts_global.size(), gn.data()))
+      throw Fail{"internal: rank boundaries could not be planned", SCALCE_ERR_ARG};
     res->first_read = gn[rank];
     res->reads_local = gn[rank + 1] - gn[rank];
     res->moved_in[0] = gn[rank] < g[rank] ? g[rank] - clampu(gn[rank], 0, g[rank]) : 0;
@@ -404,20 +455,13 @@ extern "C" int scalce_sharded_compress(scalce_comm *comm, scalce_ctx *ctx, scalc
         // who receives how much from whom
         std::vector<u64> all = gather_host<u64>(comm, sendb.data(), (size_t)W, d_small, d_gather, s);
         for (int src = 0; src < W; src++) recvb[src] = all[(size_t)src * W + rank];
+        std::vector<uint64_t> ro(W);
         u64 before_self = 0, after_self = 0;
-        for (int src = 0; src < W; src++) { if (src < rank) before_self += recvb[src]; else if (src > rank) after_self += recvb[src]; }
-        // everything but the rows that stay goes through the transport; the two parts land 16-byte aligned (the ingest kernels
-        // read their text in aligned 16-byte words)
-        const u64 back_at = (before_self + 15) & ~15ull;
+        const u64 back_at = exchange_recv_layout(W, rank, recvb, ro, before_self, after_self);
         uint8_t *d_recv = mem.alloc<uint8_t>(back_at + after_self + 256);
-        std::vector<uint64_t> sb = sendb, rb = recvb, so(W), ro(W);
+        std::vector<uint64_t> sb = sendb, rb = recvb, so(start.begin(), start.begin() + W);
         sb[rank] = 0;
         rb[rank] = 0;
-        u64 fa = 0, ba = back_at;
-        for (int r = 0; r < W; r++) {
-          so[r] = start[r];
-          if (r < rank) { ro[r] = fa; fa += rb[r]; } else { ro[r] = ba; ba += rb[r]; }
-        }
         SH_CM(comm, scalce_comm_all_to_all_vo(comm, text[m], so.data(), sb.data(), d_recv, ro.data(), rb.data(), s));
         front_text[m] = d_recv; front_bytes[m] = before_self;
         back_text[m] = d_recv + back_at; back_bytes[m] = after_self;
@@ -428,12 +472,13 @@ extern "C" int scalce_sharded_compress(scalce_comm *comm, scalce_ctx *ctx, scalc
         if (scalce_batch_reads(b) != res->reads_local) throw Fail{"internal: row count after the exchange differs from the plan", SCALCE_ERR_ARG};
       });
     }
-    if (W > 1) agree("exchange of rows between ranks");
-    else if (local_err.rc) throw local_err;
+    agree("exchange of rows between ranks");
     mark("exchange + re-ingest");
-    const u64 N = scalce_batch_reads(b);
-    // ---- 4. run-wide quality model: trigrams across the ORIGINAL piece boundaries, all-reduce, scaling
-    uint32_t *d_table = nullptr;
+    N = scalce_batch_reads(b);
+  }
+
+  // ---- 4. run-wide quality model: trigrams across the ORIGINAL piece boundaries, all-reduce, scaling
+  void quality_model() {
     scalce_params bp;
     SH_RC(ctx, scalce_batch_params(b, &bp));
     if (L[0] && !bp.no_ac) {  // (-A: no statistics, the q' rows are stored as they are)
@@ -443,180 +488,169 @@ extern "C" int scalce_sharded_compress(scalce_comm *comm, scalce_ctx *ctx, scalc
       std::vector<uint8_t> edges = gather_host<uint8_t>(comm, ed.data(), 8, d_e, reinterpret_cast<uint8_t *>(d_gather), s);
       d_table = keep_alloc<uint32_t>(res, 2, 2 * 512000);
       for (int m = 0; m < nm; m++) {
+        const void *dp = nullptr;
+        uint64_t nb = 0;
         SH_RC(ctx, scalce_batch_output(b, SCALCE_OUT_FREQ4, m, &dp, &nb));
         u64 *d_f4 = static_cast<u64 *>(const_cast<void *>(dp));
-        // symbols next to the boundary in front of this rank's ORIGINAL piece (pieces before it may be empty or short)
-        std::vector<uint32_t> keys;
-        const u64 own = meta[4 * rank] * (u64)L[m];
-        if (rank > 0 && own) {
-          std::vector<uint32_t> before;  // up to two symbols in front of the piece, nearest last
-          for (int r = rank - 1; r >= 0 && before.size() < 2; r--) {
-            const u64 nsy = meta[4 * r] * (u64)L[m];
-            const uint8_t *e = &edges[(size_t)r * 8 + 4 * m];
-            if (nsy >= 2) { if (before.empty()) { before.push_back(e[3]); before.push_back(e[2]); } else before.push_back(e[3]); }
-            else if (nsy == 1) before.push_back(e[0]);
-          }
-          const uint8_t *me = &edges[(size_t)rank * 8 + 4 * m];
-          const uint32_t s0 = me[0], s1 = own >= 2 ? me[1] : 0xFFFFu;
-          // before[0] = the symbol right in front (p1), before[1] = the one before that (p0)
-          if (before.size() >= 2 && s0 < 80 && before[0] < 80 && before[1] < 80) keys.push_back((before[1] * 80 + before[0]) * 80 + s0);
-          if (before.size() >= 1 && own >= 2 && s0 < 80 && s1 < 80 && before[0] < 80) keys.push_back((before[0] * 80 + s0) * 80 + s1);
-        }
-        if (!keys.empty()) {
+        std::vector<u64> nsym(W);
+        for (int r = 0; r < W; r++) nsym[r] = meta[4 * r] * (u64)L[m];
+        uint32_t keys[2], nkeys = 0;
+        if (scalce_shard_plan_edge_trigrams(W, rank, nsym.data(), &edges[4 * m], 8, keys, &nkeys))
+          throw Fail{"internal: trigrams across the rank boundary could not be planned", SCALCE_ERR_ARG};
+        if (nkeys) {
           uint32_t *d_k = reinterpret_cast<uint32_t *>(d_small);
-          SH_HIP(hipMemcpyAsync(d_k, keys.data(), keys.size() * 4, hipMemcpyHostToDevice, s));
-          hipLaunchKernelGGL(add_ones_k, dim3(1), dim3(1), 0, s, d_f4, d_k, (uint32_t)keys.size());
+          SH_HIP(hipMemcpyAsync(d_k, keys, nkeys * 4, hipMemcpyHostToDevice, s));
+          hipLaunchKernelGGL(add_ones_k, dim3(1), dim3(1), 0, s, d_f4, d_k, nkeys);
           SH_HIP(hipStreamSynchronize(s));
         }
         SH_CM(comm, scalce_comm_all_reduce_sum_u64(comm, reinterpret_cast<uint64_t *>(d_f4), 512000, s));
-        const u64 symbols = total_reads * (u64)L[m];
+        const u64 symbols = g[W] * (u64)L[m];
         SH_RC(ctx, scalce_ac_scale(ctx, reinterpret_cast<const uint64_t *>(d_f4), (uint32_t)(1 + symbols / 0xFFFFFFFFull), d_table + 512000 * (size_t)m, s));  // compress.cpp:297-303
       }
     }
     mark("quality model");
-    // ---- 5. tie-break across ranks.  bin_size is cumulative over the run (reads.cpp:246): a rank's tie reads are decided
-    // against the FINAL counts of every rank in front of it.  Rounds 1-3 iterated: all-gather of everybody's counts, a few
-    // global sweeps, until no rank moved (~13 rounds, 27 ms per 50 M-read shard).  Round 4: the ranks form a chain.  Rank r
-    // waits for the counts of ranks 0 .. r-1 from rank r-1 (one message: [status][buckets + 1 counts]), settles its own tie
-    // reads against them window by window (scalce_batch_tokenize_settle: the tie-break of a batch on its own, exact given its
-    // prior), adds its counts and hands the sum to rank r+1.  A rank only spends its own settle; what the chain adds is a
-    // start-up skew of one settle per rank in front -- with several shards in flight the ranks work on different shards.
-    {
-      const uint32_t stride = nb1 + 1;
-      u64 *d_msg = nullptr;  // the chain's message: [0] status of the ranks in front (0 = fine), [1 ..] their counts per bucket
-      local([&] { d_msg = mem.alloc<u64>(stride); });  // (before the agree(): a rank that cannot even hold the message stops everybody there)
-      local([&] { SH_RC(ctx, scalce_batch_tokenize_begin(b, s)); });
-      if (W > 1) agree("tokenizer"); else if (local_err.rc) throw local_err;
-      {
-        // Everything between the receive and the send runs under local(): whatever fails here -- the receive itself, a copy,
-        // the settle, the counts -- this rank still SENDS (status = its error code), so the rank behind never sits in a receive
-        // that nobody answers (RCCL has no timeout), and every rank reaches the agree() below and throws there together.
-        u64 upstream = 0;
-        if (rank > 0) {
-          // (the receive is posted even when this rank has already failed: the rank in front sends in any case, and a send
-          //  that nobody takes would block its stream in front of the agree() below)
-          try {
-            SH_CM(comm, scalce_comm_recv(comm, d_msg, (size_t)stride * 8, rank - 1, s));
-            SH_HIP(hipMemcpyAsync(&upstream, d_msg, 8, hipMemcpyDeviceToHost, s));
-            SH_HIP(hipStreamSynchronize(s));
-          } catch (const Fail &f) {
-            if (!local_err.rc) { local_err = f; if (!local_err.rc) local_err.rc = SCALCE_ERR_HIP; }
-          }
-        } else {
-          local([&] { SH_HIP(hipMemsetAsync(d_msg, 0, (size_t)stride * 8, s)); });
-        }
-        if (!upstream)
-          local([&] { SH_RC(ctx, scalce_batch_tokenize_settle(b, rank > 0 ? reinterpret_cast<const uint64_t *>(d_msg + 1) : nullptr, s)); });
-        else
-          local([&] { SH_RC(ctx, scalce_batch_tokenize_settle(b, nullptr, s)); });  // (a rank in front failed: the run ends at the next agree())
-        res->rounds = 1;
-        res->sweeps = 0;
-        if (rank + 1 < W) {
-          local([&] {
-            SH_RC(ctx, scalce_batch_output(b, SCALCE_OUT_BUCKET_COUNTS, 0, &dp, &nb));
-            hipLaunchKernelGGL(add_counts_into_k, dim3((nb1 + 255) / 256), dim3(256), 0, s, nb1, static_cast<const u64 *>(dp), d_msg + 1);
-          });
-          // the message goes out whatever happened above; only a send that itself fails is left to the transport's own error
-          // (the peer of a dead communicator gets an error from its receive, not a hang)
-          const u64 status = upstream ? upstream : (local_err.rc ? 2 + (u64)local_err.rc : 0);
-          hipError_t he = hipMemcpyAsync(d_msg, &status, 8, hipMemcpyHostToDevice, s);
-          if (he == hipSuccess) he = hipStreamSynchronize(s);  // `status` is a stack variable
-          const int src = scalce_comm_send(comm, d_msg, (size_t)stride * 8, rank + 1, s);
-          if (!local_err.rc) {
-            if (he != hipSuccess) local_err = Fail{std::string("tie-break chain, status word: ") + hipGetErrorString(he), SCALCE_ERR_HIP};
-            else if (src) local_err = Fail{std::string("scalce_comm_send (tie-break chain): ") + scalce_comm_error(comm), src};
-          }
-        }
+  }
+
+  // ---- 5. tie-break across ranks.  bin_size is cumulative over the run (reads.cpp:246): a rank's tie reads are decided
+  // against the FINAL counts of every rank in front of it.  Rounds 1-3 iterated: all-gather of everybody's counts, a few
+  // global sweeps, until no rank moved (~13 rounds, 27 ms per 50 M-read shard).  Round 4: the ranks form a chain.  Rank r
+  // waits for the counts of ranks 0 .. r-1 from rank r-1 (one message: [status][buckets + 1 counts]), settles its own tie
+  // reads against them window by window (scalce_batch_tokenize_settle: the tie-break of a batch on its own, exact given its
+  // prior), adds its counts and hands the sum to rank r+1.  A rank only spends its own settle; what the chain adds is a
+  // start-up skew of one settle per rank in front -- with several shards in flight the ranks work on different shards.
+  void tie_break_chain() {
+    const uint32_t stride = nb1 + 1;
+    u64 *d_msg = nullptr;  // the chain's message: [0] status of the ranks in front (0 = fine), [1 ..] their counts per bucket
+    local([&] { d_msg = mem.alloc<u64>(stride); });  // (before the agree(): a rank that cannot even hold the message stops everybody there)
+    local([&] { SH_RC(ctx, scalce_batch_tokenize_begin(b, s)); });
+    agree("tokenizer");
+    // Everything between the receive and the send runs under local(): whatever fails here -- the receive itself, a copy,
+    // the settle, the counts -- this rank still SENDS (status = its error code), so the rank behind never sits in a receive
+    // that nobody answers (RCCL has no timeout), and every rank reaches the agree() of step 6 and throws there together.
+    u64 upstream = 0;
+    if (rank > 0) {
+      // (the receive is posted even when this rank has already failed: the rank in front sends in any case, and a send
+      //  that nobody takes would block its stream in front of the agree() of step 6)
+      try {
+        SH_CM(comm, scalce_comm_recv(comm, d_msg, (size_t)stride * 8, rank - 1, s));
+        SH_HIP(hipMemcpyAsync(&upstream, d_msg, 8, hipMemcpyDeviceToHost, s));
+        SH_HIP(hipStreamSynchronize(s));
+      } catch (const Fail &f) {
+        if (!local_err.rc) { local_err = f; if (!local_err.rc) local_err.rc = SCALCE_ERR_HIP; }
+      }
+    } else {
+      local([&] { SH_HIP(hipMemsetAsync(d_msg, 0, (size_t)stride * 8, s)); });
+    }
+    if (!upstream)
+      local([&] { SH_RC(ctx, scalce_batch_tokenize_settle(b, rank > 0 ? reinterpret_cast<const uint64_t *>(d_msg + 1) : nullptr, s)); });
+    else
+      local([&] { SH_RC(ctx, scalce_batch_tokenize_settle(b, nullptr, s)); });  // (a rank in front failed: the run ends at the next agree())
+    res->rounds = 1;
+    res->sweeps = 0;
+    if (rank + 1 < W) {
+      local([&] {
+        const void *dp = nullptr;
+        uint64_t nb = 0;
+        SH_RC(ctx, scalce_batch_output(b, SCALCE_OUT_BUCKET_COUNTS, 0, &dp, &nb));
+        hipLaunchKernelGGL(add_counts_into_k, dim3((nb1 + 255) / 256), dim3(256), 0, s, nb1, static_cast<const u64 *>(dp), d_msg + 1);
+      });
+      // the message goes out whatever happened above; only a send that itself fails is left to the transport's own error
+      // (the peer of a dead communicator gets an error from its receive, not a hang)
+      const u64 status = upstream ? upstream : (local_err.rc ? 2 + (u64)local_err.rc : 0);
+      hipError_t he = hipMemcpyAsync(d_msg, &status, 8, hipMemcpyHostToDevice, s);
+      if (he == hipSuccess) he = hipStreamSynchronize(s);  // `status` is a stack variable
+      const int src = scalce_comm_send(comm, d_msg, (size_t)stride * 8, rank + 1, s);
+      if (!local_err.rc) {
+        if (he != hipSuccess) local_err = Fail{std::string("tie-break chain, status word: ") + hipGetErrorString(he), SCALCE_ERR_HIP};
+        else if (src) local_err = Fail{std::string("scalce_comm_send (tie-break chain): ") + scalce_comm_error(comm), src};
       }
     }
     mark("tie-break");
-    // ---- 6. order (the run's cuts inside this rank's rows are its chunks) and emit
-    {
-      std::vector<uint64_t> starts(1, 0);
-      for (u64 c : cuts_global)
-        if (c > gn[rank] && c < gn[rank + 1]) starts.push_back(c - gn[rank]);
-      local([&] {
-        SH_RC(ctx, scalce_batch_set_chunks(b, starts.data(), (uint32_t)starts.size()));
-        SH_RC(ctx, scalce_batch_order(b, s));
-        SH_RC(ctx, scalce_batch_emit(b, s));
-        SH_RC(ctx, scalce_batch_set_chunks(b, nullptr, 0));
-      });
-      if (W > 1) agree("order and emit stages"); else if (local_err.rc) throw local_err;
-    }
+  }
+
+  // ---- 6. order (the run's cuts inside this rank's rows are its chunks) and emit
+  void order_and_emit() {
+    std::vector<uint64_t> starts(1, 0);
+    for (u64 c : cuts_global)
+      if (c > gn[rank] && c < gn[rank + 1]) starts.push_back(c - gn[rank]);
+    local([&] {
+      SH_RC(ctx, scalce_batch_set_chunks(b, starts.data(), (uint32_t)starts.size()));
+      SH_RC(ctx, scalce_batch_order(b, s));
+      SH_RC(ctx, scalce_batch_emit(b, s));
+      SH_RC(ctx, scalce_batch_set_chunks(b, nullptr, 0));
+    });
+    agree("order and emit stages");
     mark("order + emit");
-    // ---- 7. who holds how much of every bucket
+  }
+
+  // ---- 7. who holds how much of every bucket
+  void bucket_layout() {
     if (!res->counts) res->counts = static_cast<uint64_t *>(calloc((size_t)W * nb1, 8));
     if (!res->name_bytes) res->name_bytes = static_cast<uint64_t *>(calloc((size_t)W * nb1, 8));
     memset(res->name_bytes, 0, (size_t)W * nb1 * 8);
-    {
-      u64 *d_all = mem.alloc<u64>((size_t)W * nb1);
-      SH_RC(ctx, scalce_batch_output(b, SCALCE_OUT_BUCKET_COUNTS, 0, &dp, &nb));
+    const void *dp = nullptr;
+    uint64_t nb = 0;
+    u64 *d_all = mem.alloc<u64>((size_t)W * nb1);
+    SH_RC(ctx, scalce_batch_output(b, SCALCE_OUT_BUCKET_COUNTS, 0, &dp, &nb));
+    SH_CM(comm, scalce_comm_all_gather(comm, dp, d_all, (size_t)nb1 * 8, s));
+    SH_HIP(hipMemcpyAsync(res->counts, d_all, (size_t)W * nb1 * 8, hipMemcpyDeviceToHost, s));
+    SH_HIP(hipStreamSynchronize(s));
+    SH_RC(ctx, scalce_batch_output(b, SCALCE_OUT_BUCKET_NAME_BYTES, 0, &dp, &nb));
+    if (nb) {
       SH_CM(comm, scalce_comm_all_gather(comm, dp, d_all, (size_t)nb1 * 8, s));
-      SH_HIP(hipMemcpyAsync(res->counts, d_all, (size_t)W * nb1 * 8, hipMemcpyDeviceToHost, s));
+      SH_HIP(hipMemcpyAsync(res->name_bytes, d_all, (size_t)W * nb1 * 8, hipMemcpyDeviceToHost, s));
       SH_HIP(hipStreamSynchronize(s));
-      SH_RC(ctx, scalce_batch_output(b, SCALCE_OUT_BUCKET_NAME_BYTES, 0, &dp, &nb));
-      if (nb) {
-        SH_CM(comm, scalce_comm_all_gather(comm, dp, d_all, (size_t)nb1 * 8, s));
-        SH_HIP(hipMemcpyAsync(res->name_bytes, d_all, (size_t)W * nb1 * 8, hipMemcpyDeviceToHost, s));
-        SH_HIP(hipStreamSynchronize(s));
-      }
     }
     mark("bucket layout");
-    // ---- 8. the run-wide reordered quality stream in contiguous block ranges, one range per rank; code it
+  }
+
+  // ---- 8. the run-wide reordered quality stream in contiguous block ranges, one range per rank; code it
+  void block_ranges_and_coder(int flags, void *coder_stream) {
+    const void *dp = nullptr;
+    uint64_t nb = 0;
     if (d_table && L[0]) {
-      const uint64_t *C = res->counts;
       for (int m = 0; m < nm; m++) {
         const u64 Lm = (u64)L[m];
         std::vector<uint64_t> sendb(W), recvb(W), psrc((size_t)W * nb1), pdst((size_t)W * nb1);
         uint64_t lo = 0, hi = 0, np = 0;
-        if (scalce_shard_plan_blocks(W, rank, nb1, C, Lm, sendb.data(), recvb.data(), &lo, &hi, psrc.data(), pdst.data(), &np))
+        if (scalce_shard_plan_blocks(W, rank, nb1, res->counts, Lm, sendb.data(), recvb.data(), &lo, &hi, psrc.data(), pdst.data(), &np))
           throw Fail{"internal: block-range plan is inconsistent", SCALCE_ERR_ARG};
-        psrc.resize(np);
-        pdst.resize(np);
-        u64 recv_total = 0;
-        for (int r = 0; r < W; r++) recv_total += recvb[r];
         SH_RC(ctx, scalce_batch_output(b, SCALCE_OUT_QSTREAM, m, &dp, &nb));
         if (nb != N * Lm) throw Fail{"internal: reordered stream has an unexpected size", SCALCE_ERR_ARG};
         // What stays on this rank never goes through the transport: its pieces are copied straight from the local stream
         // (at one rank that is everything: 5 GB per 50 M-read shard that round 4 sent to itself through ncclSend / ncclRecv,
         // 16 of that path's 19 ms).  The receive buffer only holds what other ranks send, in rank order.
-        u64 self_at = 0, local_off = 0;   // where the own bytes would lie in a full receive buffer / where they lie in the local stream
-        for (int r = 0; r < rank; r++) { self_at += recvb[r]; local_off += sendb[r]; }
-        const u64 self_bytes = recvb[rank];
-        if (self_bytes != sendb[rank]) throw Fail{"internal: block-range plan disagrees with itself about the bytes that stay", SCALCE_ERR_ARG};
-        std::vector<uint64_t> sb = sendb, rb = recvb;
-        sb[rank] = 0;
-        rb[rank] = 0;
-        uint8_t *d_got = mem.alloc<uint8_t>(recv_total - self_bytes);
+        std::vector<uint64_t> ps_o(np), pd_o(np), ps_x(np), pd_x(np);
+        uint64_t n_o = 0, n_x = 0, own_total = 0, other_total = 0, local_off = 0;
+        const int split = scalce_shard_plan_own_pieces(W, rank, sendb.data(), recvb.data(), psrc.data(), pdst.data(), np, ps_o.data(), pd_o.data(),
+                                                       &n_o, &own_total, &local_off, ps_x.data(), pd_x.data(), &n_x, &other_total);
+        if (split && recvb[rank] != sendb[rank]) throw Fail{"internal: block-range plan disagrees with itself about the bytes that stay", SCALCE_ERR_ARG};
+        u64 recv_other = 0;
+        for (int r = 0; r < W; r++) recv_other += r == rank ? 0 : recvb[r];
+        uint8_t *d_got = mem.alloc<uint8_t>(recv_other);
         uint8_t *d_mine = keep_alloc<uint8_t>(res, m, hi - lo + 16);
         // (the send buffer is the local stream itself, every range where it lies; the own range is the hole in the middle)
         if (W > 1) {
-          std::vector<uint64_t> so(W), ro(W);
-          u64 a = 0, g = 0;
-          for (int r = 0; r < W; r++) { so[r] = a; ro[r] = g; a += sendb[r]; g += rb[r]; }
+          std::vector<uint64_t> sb = sendb, rb = recvb, so(W), ro(W);
+          sb[rank] = 0;
+          rb[rank] = 0;
+          u64 a = 0, got = 0;
+          for (int r = 0; r < W; r++) { so[r] = a; ro[r] = got; a += sendb[r]; got += rb[r]; }
           SH_CM(comm, scalce_comm_all_to_all_vo(comm, dp, so.data(), sb.data(), d_got, ro.data(), rb.data(), s));
         }
-        if (!psrc.empty()) {
-          // pieces are source-major: [from ranks in front | own | from ranks behind]; the own ones read the local stream
-          std::vector<uint64_t> ps_o, pd_o, ps_x, pd_x;
-          u64 own_total = 0, other_total = 0;
-          for (size_t i = 0; i < psrc.size(); i++) {
-            const u64 len = (i + 1 < psrc.size() ? psrc[i + 1] : recv_total) - psrc[i];
-            if (psrc[i] >= self_at && psrc[i] < self_at + self_bytes) { ps_o.push_back(psrc[i] - self_at); pd_o.push_back(pdst[i]); own_total += len; }
-            else { ps_x.push_back(psrc[i] < self_at ? psrc[i] : psrc[i] - self_bytes); pd_x.push_back(pdst[i]); other_total += len; }
+        if (split) throw Fail{"internal: block-range pieces do not add up", SCALCE_ERR_ARG};  // (behind the exchange, which the others are in)
+        if (np) {
+          uint64_t *d_ps = mem.alloc<uint64_t>(np), *d_pd = mem.alloc<uint64_t>(np);
+          if (n_x) {
+            SH_HIP(hipMemcpyAsync(d_ps, ps_x.data(), n_x * 8, hipMemcpyHostToDevice, s));
+            SH_HIP(hipMemcpyAsync(d_pd, pd_x.data(), n_x * 8, hipMemcpyHostToDevice, s));
+            SH_RC(ctx, scalce_copy_pieces(ctx, d_got, d_mine, d_ps, d_pd, (uint32_t)n_x, other_total, s));
           }
-          if (own_total != self_bytes || other_total != recv_total - self_bytes) throw Fail{"internal: block-range pieces do not add up", SCALCE_ERR_ARG};
-          uint64_t *d_ps = mem.alloc<uint64_t>(psrc.size()), *d_pd = mem.alloc<uint64_t>(psrc.size());
-          if (!ps_x.empty()) {
-            SH_HIP(hipMemcpyAsync(d_ps, ps_x.data(), ps_x.size() * 8, hipMemcpyHostToDevice, s));
-            SH_HIP(hipMemcpyAsync(d_pd, pd_x.data(), pd_x.size() * 8, hipMemcpyHostToDevice, s));
-            SH_RC(ctx, scalce_copy_pieces(ctx, d_got, d_mine, d_ps, d_pd, (uint32_t)ps_x.size(), other_total, s));
-          }
-          if (!ps_o.empty()) {
-            uint64_t *d_ps2 = d_ps + ps_x.size(), *d_pd2 = d_pd + ps_x.size();
-            SH_HIP(hipMemcpyAsync(d_ps2, ps_o.data(), ps_o.size() * 8, hipMemcpyHostToDevice, s));
-            SH_HIP(hipMemcpyAsync(d_pd2, pd_o.data(), pd_o.size() * 8, hipMemcpyHostToDevice, s));
-            SH_RC(ctx, scalce_copy_pieces(ctx, static_cast<const uint8_t *>(dp) + local_off, d_mine, d_ps2, d_pd2, (uint32_t)ps_o.size(), own_total, s));
+          if (n_o) {
+            uint64_t *d_ps2 = d_ps + n_x, *d_pd2 = d_pd + n_x;
+            SH_HIP(hipMemcpyAsync(d_ps2, ps_o.data(), n_o * 8, hipMemcpyHostToDevice, s));
+            SH_HIP(hipMemcpyAsync(d_pd2, pd_o.data(), n_o * 8, hipMemcpyHostToDevice, s));
+            SH_RC(ctx, scalce_copy_pieces(ctx, static_cast<const uint8_t *>(dp) + local_off, d_mine, d_ps2, d_pd2, (uint32_t)n_o, own_total, s));
           }
           SH_HIP(hipStreamSynchronize(s));  // the piece lists are host vectors of this scope
         }
@@ -646,9 +680,62 @@ extern "C" int scalce_sharded_compress(scalce_comm *comm, scalce_ctx *ctx, scalc
     }
     mark("block ranges + coder");
     SH_HIP(hipStreamSynchronize(s));
+  }
+};
+
+}  // namespace
+
+extern "C" int scalce_sharded_compress(scalce_comm *comm, scalce_ctx *ctx, scalce_batch *b, const uint8_t *d_text1, uint64_t n1,
+                                       const uint8_t *d_text2, uint64_t n2, int flags, void *stream, void *coder_stream,
+                                       scalce_shard_result *res) {
+  if (!comm || !ctx || !b || !res) return SCALCE_ERR_ARG;
+  {
+    scalce_params bp;
+    if (scalce_batch_params(b, &bp) != SCALCE_OK) return SCALCE_ERR_ARG;
+    if (bp.fasta || bp.no_qualities) {
+      scalce_set_last_error(ctx, "records without qualities (-f / -Q) are compressed on one GPU: sharded runs do not take them");
+      return SCALCE_ERR_ARG;
+    }
+    if (bp.interleaved) {
+      scalce_set_last_error(ctx, "interleaved input (-i) is compressed on one GPU: sharded runs do not take it");
+      return SCALCE_ERR_ARG;
+    }
+  }
+  const int W = scalce_comm_world(comm), rank = scalce_comm_rank(comm);
+  if (W > 64) return SCALCE_ERR_ARG;
+  {  // a result of an earlier call on this slot keeps its buffers; everything else starts from zero
+    scalce_shard_result keep = *res;
+    const bool reuse = res->magic == RESULT_MAGIC && res->world == W && res->nb1 == (uint32_t)scalce_patterns_buckets(ctx) + 1;
+    memset(res, 0, sizeof *res);
+    if (reuse) {
+      res->counts = keep.counts;
+      res->name_bytes = keep.name_bytes;
+      memcpy(res->keep, keep.keep, sizeof keep.keep);
+      memcpy(res->keep_bytes, keep.keep_bytes, sizeof keep.keep_bytes);
+    }
+    res->magic = RESULT_MAGIC;
+  }
+  res->world = W;
+  res->rank = rank;
+  // The reordered q' stream of this call is only passed on (step 8): it lives in the workspace the batch shares with the other
+  // shards in flight, not in the batch -- 5 GB less per slot at 50 M reads of 100 bp.  (Not under -A: the stream is the output.)
+  struct StreamScratch {
+    scalce_batch *b; bool on;
+    ~StreamScratch() { if (on) scalce_batch_set_stream_scratch(b, 0); }
+  } stream_scratch{b, scalce_batch_set_stream_scratch(b, 1) == SCALCE_OK};
+  try {
+    ShardRun run(comm, ctx, b, res, (hipStream_t)stream, W, rank, d_text1, n1, d_text2, n2);
+    run.first_pass();
+    run.spill_chunk_cuts();
+    run.move_boundaries_and_exchange_rows();
+    run.quality_model();
+    run.tie_break_chain();
+    run.order_and_emit();
+    run.bucket_layout();
+    run.block_ranges_and_coder(flags, coder_stream);
     return SCALCE_OK;
   } catch (const Fail &f) {
-    last_error = f.msg;
+    scalce_set_last_error(ctx, f.msg.c_str());
     fprintf(stderr, "scalce_sharded_compress (rank %d of %d): %s\n", rank, W, f.msg.c_str());
     scalce_shard_result_free(res);
     return f.rc ? f.rc : SCALCE_ERR_HIP;

@@ -417,7 +417,7 @@ def sharded_compress(comm, ctx, batch, d_text1, n1, d_text2=None, n2=0, flags=0,
     rc = ctx.L.scalce_sharded_compress(comm.h, ctx.h, batch.h, d_text1, int(n1), d_text2, int(n2), int(flags), stream, coder_stream,
                                        C.byref(res))
     if rc:
-        raise ScalceError(f"[{rc}] sharded run failed on rank {comm.rank} (message on stderr)")
+        raise ScalceError(f"[{rc}] sharded run failed on rank {comm.rank}: " + ctx.L.scalce_last_error(ctx.h).decode(errors="replace"))
     return res
 
 
@@ -437,6 +437,41 @@ def shard_plan_blocks(world, rank, nb1, counts, read_len):
     if rc:
         raise ScalceError(f"[{rc}] scalce_shard_plan_blocks")
     return send, recv, int(lo.value), int(hi.value), ps[: npc.value].copy(), pd[: npc.value].copy()
+
+
+def shard_plan_edge_trigrams(world, rank, nsym, edges):
+    """scalce_shard_plan_edge_trigrams: the trigram counters that straddle the boundary in front of `rank`'s original piece.
+    nsym = [world] symbols per piece, edges = [world][4] in scalce_batch_qinput_edges' layout.  Returns the list of keys."""
+    L = lib()
+    L.scalce_shard_plan_edge_trigrams.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint8), C.c_uint64,
+                                                  C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    ns = np.ascontiguousarray(nsym, dtype=np.uint64)
+    ed = np.ascontiguousarray(edges, dtype=np.uint8).reshape(world, 4)
+    keys, nk = (C.c_uint32 * 2)(), C.c_uint32()
+    rc = L.scalce_shard_plan_edge_trigrams(world, rank, ns.ctypes.data_as(C.POINTER(C.c_uint64)), ed.ctypes.data_as(C.POINTER(C.c_uint8)), 4,
+                                           keys, C.byref(nk))
+    if rc:
+        raise ScalceError(f"[{rc}] scalce_shard_plan_edge_trigrams")
+    return list(keys[: nk.value])
+
+
+def shard_plan_own_pieces(world, rank, send_bytes, recv_bytes, piece_src, piece_dst):
+    """scalce_shard_plan_own_pieces: the pieces of shard_plan_blocks split into those that read the local stream and those
+    that read the receive buffer without the own bytes.
+    Returns (own_src, own_dst, own_total, local_off, other_src, other_dst, other_total)."""
+    L = lib()
+    u64p = C.POINTER(C.c_uint64)
+    L.scalce_shard_plan_own_pieces.argtypes = [C.c_int, C.c_int, u64p, u64p, u64p, u64p, C.c_uint64] + [u64p] * 9
+    ins = [np.ascontiguousarray(a, dtype=np.uint64) for a in (send_bytes, recv_bytes, piece_src, piece_dst)]
+    n = len(ins[2])
+    os_, od, xs, xd = (np.zeros(n + 1, np.uint64) for _ in range(4))
+    no, ot, off, nx, xt = (C.c_uint64() for _ in range(5))
+    rc = L.scalce_shard_plan_own_pieces(world, rank, *(a.ctypes.data_as(u64p) for a in ins), n, os_.ctypes.data_as(u64p), od.ctypes.data_as(u64p),
+                                        C.byref(no), C.byref(ot), C.byref(off), xs.ctypes.data_as(u64p), xd.ctypes.data_as(u64p), C.byref(nx),
+                                        C.byref(xt))
+    if rc:
+        raise ScalceError(f"[{rc}] scalce_shard_plan_own_pieces")
+    return os_[: no.value].copy(), od[: no.value].copy(), int(ot.value), int(off.value), xs[: nx.value].copy(), xd[: nx.value].copy(), int(xt.value)
 
 
 def shard_result_free(res):

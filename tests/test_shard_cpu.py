@@ -106,3 +106,73 @@ def test_collectives_across_processes(world):
     logs = [p.communicate(timeout=120)[0] for p in procs]
     for r, p in enumerate(procs):
         assert p.returncode == 0 and f"rank {r} ok" in logs[r], logs[r][-2000:]
+
+
+def test_edge_trigrams_complete_the_histogram():
+    """Pieces of 0, 1, 2, 3 or 7 symbols in every combination over 1 to 5 ranks: the trigrams of every piece on its own plus
+    the keys each rank adds for the boundary in front of it are the trigrams of the whole stream."""
+    import itertools
+    from collections import Counter
+
+    def trigrams(s):
+        return [(s[i - 2] * 80 + s[i - 1]) * 80 + s[i] for i in range(2, len(s))]
+
+    rng = np.random.default_rng(80)
+    cases = 0
+    for world in range(1, 6):
+        for lens in itertools.product((0, 1, 2, 3, 7), repeat=world):
+            pieces = [rng.integers(0, 80, size=n).tolist() for n in lens]
+            edges = np.full((world, 4), 255, dtype=np.uint8)  # (slots the layout leaves unset must not be read)
+            for r, p in enumerate(pieces):
+                if len(p) >= 2:
+                    edges[r] = [p[0], p[1], p[-2], p[-1]]
+                elif len(p) == 1:
+                    edges[r, 0] = p[0]
+            got = []
+            for r, p in enumerate(pieces):
+                keys = host.shard_plan_edge_trigrams(world, r, lens, edges)
+                assert len(keys) <= 2
+                got += trigrams(p) + keys
+            assert Counter(got) == Counter(trigrams(sum(pieces, []))), (lens, pieces)
+            cases += 1
+    assert cases == 3905
+
+
+@pytest.mark.parametrize("world,nb1,scale", [(2, 10, 50000), (3, 30, 11000), (4, 17, 15000), (4, 30, 8500)])
+def test_own_and_other_pieces_materialised(world, nb1, scale):
+    """What a rank's block range holds is the same bytes whether every piece is read from the full receive buffer (the own
+    bytes in the middle) or the own pieces from the local stream and the others from the buffer without the own bytes."""
+    L = 100
+    rng = np.random.default_rng(world * 100 + nb1)
+    Cm = rng.integers(0, scale, size=(world, nb1)).astype(np.uint64)
+    Cm[rng.random(size=Cm.shape) < 0.2] = 0
+    assert 30e6 <= int(Cm.sum()) * L <= 60e6
+    streams = [rng.integers(0, 256, size=int(Cm[r].sum()) * L, dtype=np.uint8) for r in range(world)]
+    plans = [host.shard_plan_blocks(world, r, nb1, Cm, L) for r in range(world)]
+
+    def apply(src, psrc, pdst, total, out):
+        ends = list(psrc[1:]) + [total]
+        for a, e, d in zip(map(int, psrc), map(int, ends), map(int, pdst)):
+            out[d : d + e - a] = src[a:e]
+
+    for rank in range(world):
+        send, recv, lo, hi, psrc, pdst = plans[rank]
+        assert hi > lo  # every rank owns a range
+        parts = []  # what every source sends to `rank`, where it lies in the source's local stream
+        for src in range(world):
+            s_send = plans[src][0]
+            at = int(s_send[:rank].sum())
+            assert int(s_send[rank]) == int(recv[src])
+            parts.append(streams[src][at : at + int(s_send[rank])])
+        full = np.concatenate(parts)
+        want = np.zeros(hi - lo, dtype=np.uint8)
+        apply(full, psrc, pdst, len(full), want)
+
+        own_src, own_dst, own_total, local_off, oth_src, oth_dst, oth_total = host.shard_plan_own_pieces(world, rank, send, recv, psrc, pdst)
+        assert len(own_src) + len(oth_src) == len(psrc) and own_total == int(recv[rank]) and own_total + oth_total == len(full)
+        assert local_off == int(send[:rank].sum())
+        compacted = np.concatenate(parts[:rank] + parts[rank + 1 :])
+        got = np.zeros(hi - lo, dtype=np.uint8)
+        apply(compacted, oth_src, oth_dst, oth_total, got)
+        apply(streams[rank][local_off:], own_src, own_dst, own_total, got)
+        assert np.array_equal(got, want)
