@@ -193,6 +193,7 @@ int scalce_batch_set_stream_scratch(scalce_batch *b, int on);
  * batches (SCALCE_ERR_ARG); a stream handed in by the caller (sharded runs) is never coded in place. */
 int scalce_batch_set_code_in_place(scalce_batch *b, int on);
 uint64_t scalce_batch_reruns(const scalce_batch *b);  /* shards of this batch that had to be run again from their text */
+int scalce_batch_coder_round(const scalce_batch *b);  /* symbols per round of the last one-block-per-lane coder launch this batch led; 0: none */
 /* edge[0..1] = the first two, edge[2..3] = the last two q' symbols of the rows held (input order), *nsym = how many there are,
  * *read_len (may be NULL) = symbols per row: what a rank of a sharded run tells its neighbours (qualities.cpp:179-198: prev[]
  * runs across reads, so two trigrams straddle every rank boundary).  Runs on `stream` and synchronises it. */

@@ -83,8 +83,11 @@ static int ac_prepare(AcJob &j, hipStream_t s, bool framed_output = true, bool f
 //   invert, kernels_acl.hpp)
 //
 //   lanes per workgroup (64 only): SCALCE_AC_LANES_USED if set (ac_lanes_override); else AC_GROUP_LAST:
-//   clamp(ceil(blocks / CUs), 8, 64), the others 32.  ac_launch runs rows of up to 48 lanes as <true, 1, 48, 5>, wider
-//   ones as <true, 1, 64, 5>.
+//   clamp(ceil(blocks / CUs), 8, 64), the others 32.
+//
+//   symbols per round (64 only): rows of up to 48 lanes 32, or SCALCE_AC_ROUND (16 | 32) if set; wider rows 16 (their arrays
+//   do not fit into the LDS at 32).  ac_launch runs rows of up to 48 lanes as <true, 1, 48, 3, 32> or <true, 1, 48, 5, 16> --
+//   either way the gather wave is 64 symbols ahead of the chain -- and wider ones as <true, 1, 64, 5, 16>.
 //
 // One block per workgroup has the lowest latency of a block; four take 0.57 x the SIMD time per block at 1.2 x the
 // latency.  Paired reads: both mates' streams in ONE launch instead of two launches of the one-block kernel behind each
@@ -99,6 +102,7 @@ enum AcLaunchKind { AC_SINGLE, AC_PAIRED, AC_RECODE, AC_WINDOW, AC_GROUP, AC_GRO
 struct AcShape {
   int blocks_per_wg;  // 1 = ac_encode_k, 4 / 8 = ac_encode_rows_k, 64 = ac_encode_lanes_k (one block per lane)
   u32 lanes;          // ac_encode_lanes_k: blocks per workgroup
+  int round;          // ac_encode_lanes_k: symbols per block and round (16 or 32)
 };
 
 // SCALCE_AC_BLOCKS_PER_WG (tests, tools/coder_alone.py): 4, 8 or 64; 0 = no override
@@ -127,6 +131,15 @@ static u32 ac_lanes_override() {
   return (u32)(v < 1 || v > 64 ? 32 : v);
 }
 
+// Symbols per round of ac_encode_lanes_k for rows of up to 48 lanes: SCALCE_AC_ROUND = 16 or 32 (tests, measurements; the
+// same bytes either way); 0 = not set or anything else.
+static int ac_round_override() {
+  const char *e = getenv("SCALCE_AC_ROUND");
+  const int v = e ? atoi(e) : 0;
+  return v == 16 || v == 32 ? v : 0;
+}
+constexpr int AC_ROUND_DEFAULT = 32;  // (measured: DESIGN.md section 5)
+
 static AcShape ac_shape(AcLaunchKind kind, u32 blocks, bool general, int device) {
   const int over = ac_blocks_override();
   int bpw;
@@ -146,7 +159,8 @@ static AcShape ac_shape(AcLaunchKind kind, u32 blocks, bool general, int device)
     if (!n_cus) { hipDeviceProp_t pr; n_cus = hipGetDeviceProperties(&pr, device) == hipSuccess && pr.multiProcessorCount > 0 ? pr.multiProcessorCount : 256; }
     lanes = std::min<u32>(std::max<u32>(cdiv(blocks, (u32)n_cus), 8u), 64u);
   }
-  return AcShape{bpw, lanes ? lanes : 32u};
+  if (!lanes) lanes = 32u;
+  return AcShape{bpw, lanes, lanes <= 48 ? (ac_round_override() ? ac_round_override() : AC_ROUND_DEFAULT) : 16};
 }
 
 // ONE launch over the blocks of all jobs, in the shape ac_shape gives `kind`.
@@ -256,8 +270,10 @@ static int ac_launch(AcJob *jobs, int njobs, AcLaunchKind kind, hipStream_t s, h
       // (two sets of four waves per CU -- a chain or sink sharing its SIMD with a light wave of the other set -- cost a third fewer
       //  CU-seconds and 35 % more latency per launch: 98 against 75 ms per shard with fifteen slots, round 5; waves on shared CUs at
       //  raised priority: +5 %, round 3.  Both removed.)
-      if (a.lanes_used <= 48) LAUNCH((ac_encode_lanes_k<true, 1, 48, 5>), cdiv(total, a.lanes_used), 256, 0, s, a);  // (rows of 48: LDS for a longer staging ring)
-      else LAUNCH((ac_encode_lanes_k<true, 1, 64, 5>), cdiv(total, a.lanes_used), 256, 0, s, a);
+      lead->ac_round_launched = shape.round;  // (scalce_batch_coder_round: tests)
+      if (a.lanes_used <= 48 && shape.round == 32) LAUNCH((ac_encode_lanes_k<true, 1, 48, 3, 32>), cdiv(total, a.lanes_used), 256, 0, s, a);
+      else if (a.lanes_used <= 48) LAUNCH((ac_encode_lanes_k<true, 1, 48, 5, 16>), cdiv(total, a.lanes_used), 256, 0, s, a);  // (rows of 48: LDS for a longer staging ring)
+      else LAUNCH((ac_encode_lanes_k<true, 1, 64, 5, 16>), cdiv(total, a.lanes_used), 256, 0, s, a);
     } else if (shape.blocks_per_wg == 8) {
       if (general) LAUNCH((ac_encode_rows_k<true, 8>), cdiv(total, 8), 320, 0, s, a);
       else LAUNCH((ac_encode_rows_k<false, 8>), cdiv(total, 8), 320, 0, s, a);

@@ -405,6 +405,7 @@ extern "C" void scalce_batch_set_lean(scalce_batch *b, int lean) {
   if (b->lean) unfuse(b);
 }
 extern "C" uint64_t scalce_batch_reruns(const scalce_batch *b) { return b ? b->reruns : 0; }
+extern "C" int scalce_batch_coder_round(const scalce_batch *b) { return b ? b->ac_round_launched : 0; }
 extern "C" int scalce_batch_set_code_in_place(scalce_batch *b, int on) {
   if (!b) return SCALCE_ERR_ARG;
   if (on && (b->p.no_ac || b->lean)) return SCALCE_ERR_ARG;

@@ -356,6 +356,7 @@ struct scalce_batch {
   bool quality_deferred = false, side_busy = false;
   u32 tri_grid = 256;  // workgroups of trigram_pass_k (one per CU)
   // HIP-event pairs around every ac_encode_k launch (the dominant kernel); read by scalce_batch_kernel_ms
+  int ac_round_launched = 0;  // symbols per round of the last ac_encode_lanes_k launch this batch led (0: none yet)
   bool ktiming = false;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> kev;
   size_t kev_used = 0;

@@ -19,23 +19,31 @@
 // registers: add B at the current bit offset, move on by t, store a word whenever 32 bits are complete; a carry beyond
 // the last complete word (it needs 32 ones in a row there) walks back through the stored words, rarely.
 //
-// Workgroup = four wavefronts (one per SIMD of a CU) over the same 64 blocks, rounds of 16 symbols per block:
-//   gather  lane b reads block b's symbols 16 at a time, forms the contexts and fetches the table rows
-//           {g(c_lo), g(c_hi)} (kernels_ac.hpp: reciprocal fractions) three rounds ahead, straight into LDS
-//           (global_load_lds_dwordx4: the row of lane b lands at ops[slot][step][b], no register in between)
-//   chain   16 x { ds_read_b128 operands, 14 VALU: A, B, D, nlo, renorm count, new (lo, M), Q += t ; ds_write_b64 (B, Q) }
+// Workgroup = four wavefronts (one per SIMD of a CU) over the same 64 blocks, rounds of STEPS symbols per block (32 for
+// rows of up to 48 lanes, 16 for rows of 64; SCALCE_AC_ROUND picks 16 for the narrow rows as well -- the same bytes):
+//   gather  lane b reads block b's symbols 128 at a time, forms the contexts and fetches the table rows
+//           {g(c_lo), g(c_hi)} (kernels_ac.hpp: reciprocal fractions) 64 symbols ahead (SLOTS - 1 rounds), straight into
+//           LDS (global_load_lds_dwordx4: the row of lane b lands at ops[slot][step][b], no register in between)
+//   chain   STEPS x ds_read_b128 operands up front, then STEPS x { 14 VALU: A, B, D, nlo, renorm count, new (lo, M), Q += t }
+//           with a ds_write_b128 of two steps' (Q, B) behind every second, and ONCE per round the exit test (a v_max3 per
+//           two steps, the compares of fast_ok / fix, two branches on vector conditions) and the barrier.
 //           Q = 16 + bits dropped so far = where the top bit of the next B belongs in the block's bit stream.
 //           Rounds that are not plain for a lane -- the first (two raw symbols), a block's tail, a symbol that is the
 //           last of its context, a range that renormalises to the full 2^32 -- are redone for those lanes by the
 //           general step under the exec mask
 //   sink    lane b adds block b's (B, Q) records of the previous round into its accumulator and reports, per step, the word
-//           that may still take a carry and its index (two steps per 16-byte record: round 4 -- in round 3 this wave stored
+//           that may still take a carry and its index; once per round room(), the vote on a counted carry, the published
+//           count of final words (two steps per 16-byte record: round 4 -- in round 3 this wave stored
 //           the word into the staging ring itself, an LDS instruction and two of address arithmetic per step of the wave
 //           that sets the pace of a round)
 //   writer  puts the reported words into its staging ring, in step order, and moves those that are final from the ring to
 //           the block's output, a 128-byte line per lane and visit
-// One LDS-only barrier per round.  Contexts depend on symbols only, never on coder state, which is why the gather
-// wave can run ahead.  Measured costs behind this split: tools/ubench_lds.hip (a DS instruction costs a wave 17-35 cycles
+// One LDS-only barrier per round.  A round is NOT all step: of the ~1750 cycles a round of 16 takes, the chain's 16 x 14
+// VALU instructions are about half; the operand reads' first round trip, the record writes, the exit test with its
+// branches and the barrier -- and the like in the sink and writer waves, which meet the chain at that barrier -- are paid
+// per round whatever its length (counters: tools/pmc_coder.sh, profiles/r06_*_coder_pmc.json: 43 % of the wave cycles
+// parked at rounds of 16).  Hence rounds of 32 wherever the LDS holds them.
+// Contexts depend on symbols only, never on coder state, which is why the gather wave can run ahead.  Measured costs behind this split: tools/ubench_lds.hip (a DS instruction costs a wave 17-35 cycles
 // whatever its width, a branch on a VALU result ~30, a VALU instruction 4), DESIGN.md section 5.
 // Only for tables whose largest context total is <= 2^29 (the host checks, as for the plain path of ac_encode_k):
 // every symbol then keeps an interval of at least two values, and the reference's coder never runs into the inverted
@@ -45,7 +53,10 @@
 
 namespace scalce {
 
-constexpr int ACL_STEPS = 16;  // symbols per block and round
+// Symbols per block and round are a template parameter of the kernel (STEPS): 32 for rows of up to 48 lanes, 16 for rows of
+// 64, whose arrays do not fit into the LDS at 32 (AclShared).  What a round costs besides its steps -- the barrier, the
+// operand reads' first round trip, the record writes' tail, the exit test and its branches, the sink's room() / vote /
+// publish, the writer's drain ballot -- is paid per ROUND; the coded bytes do not depend on the round length.
 
 // general step on a well-formed state, reporting what the sink needs: B = offset added to lo, t = bits dropped
 __device__ __forceinline__ void acl_step_general(u32 &lo, u32 &hi, const uint4 g, u32 &B, u32 &t) {
@@ -97,10 +108,15 @@ __device__ __forceinline__ void acl_step_plain(u32 &lo, u32 &M, const uint4 g, u
 //   * the notes -- word indices, in a log that grows down from the end of the block's own output buffer -- are applied by
 //     finish(): additions commute.  (Resolved on the spot, a loop of loads and stores in the step sequence, the compiler
 //     put s_waitcnt vmcnt(0) in front of every store of the following steps.)
-// staging ring of the writer wave, words per lane: it takes whole 128-byte lines (32 words) out and puts at most 16 words
-// per round in front of them: 31 + 16 + 16 + 2 <= WORDS.
-template <int LW, int SETS> struct AclRing { static constexpr int WORDS = 64; };
-template <int LW>
+// staging ring of the writer wave, words per lane: it takes whole 128-byte lines (32 words) out -- up to 31 final words
+// stay behind -- and a round puts at most STEPS words (a step completes at most one) and the word that may still take a
+// carry in front of them.  At the end of a block the writer applies the records of TWO rounds before it drains once, so
+// up to 31 + STEPS + STEPS + 2 words are live: that is the bound, not spare room, and the ring is the power of two that
+// holds it -- 128 words for rounds of 32 (97).  Rounds of 16 keep their 64 words: a step drops fewer than 32 bits while
+// every symbol keeps an interval of two values (the host's condition for this kernel), so two rounds of 16 complete at
+// most 31 words, 31 + 31 + 2.  Do not shrink either.
+template <int LW, int SETS, int STEPS> struct AclRing { static constexpr int WORDS = STEPS <= 16 ? 64 : 128; };
+template <int LW, int STEPS>
 struct AclSink {
   SCALCE_GLOBAL u32 *dst;
   u32 wcap;      // words the block may write
@@ -124,8 +140,8 @@ struct AclSink {
   }
   // room for a round's words and notes?  (once per round: a lane that runs out of room stops and reports)
   __device__ __forceinline__ bool room() {
-    if ((Qb >> 5) + 2 * ACL_STEPS + 2 + (logcap ? 0u : nlog) >= wcap) over = true;
-    if (logcap && nlog + ACL_STEPS + 2 >= logcap) over = true;
+    if ((Qb >> 5) + 2 * STEPS + 2 + (logcap ? 0u : nlog) >= wcap) over = true;
+    if (logcap && nlog + STEPS + 2 >= logcap) over = true;
     return !over;
   }
   // the step: X += B at bit Qb, then on to Qa.  Reports the word that may still take a carry as it stands now (val) and
@@ -213,11 +229,13 @@ struct AclSink {
 };
 
 // LW = lanes (blocks) of a set of four waves, SLOTS = operand ring: the gather wave runs SLOTS - 1 rounds ahead of the chain
-template <int LW, int SLOTS, int RINGW>
+// STEPS = symbols per block and round.  LW = 48, SLOTS = 3, STEPS = 32: ops 73 728 + rec 24 576 + fifo 24 576 + ring (128 words)
+// 24 576 + pub / final_lo 576 = 148 032 bytes of the CU's 160 KiB; a fourth slot or rows of 64 lanes do not fit at 32.
+template <int LW, int SLOTS, int STEPS, int RINGW>
 struct AclShared {
-  uint4 ops[SLOTS][ACL_STEPS][LW];      // gather -> chain: operands of a round (slot = round % SLOTS), written by LDS-direct loads
-  uint4 rec[2][ACL_STEPS / 2][LW];      // chain -> sink: (Q, B) of two steps of a round per entry
-  uint4 fifo[2][ACL_STEPS / 2][LW];     // sink -> writer: (val, wq) of two steps per entry (AclSink::step)
+  uint4 ops[SLOTS][STEPS][LW];          // gather -> chain: operands of a round (slot = round % SLOTS), written by LDS-direct loads
+  uint4 rec[2][STEPS / 2][LW];          // chain -> sink: (Q, B) of two steps of a round per entry
+  uint4 fifo[2][STEPS / 2][LW];         // sink -> writer: (val, wq) of two steps per entry (AclSink::step)
   u32 stage[RINGW][LW];                 // writer: coded words on their way out -- word k of the block in slot (k + 1) & (WORDS - 1)
   u32 pub[2][LW];                       // sink -> writer: words below this index are final
   u32 final_lo[LW];
@@ -249,10 +267,12 @@ __device__ __forceinline__ void acl_wait_vm() {
 //     SIMD 0: chain A + gather B    SIMD 1: chain B + gather A    SIMD 2: sink A + writer B    SIMD 3: sink B + writer A
 // A CU then codes 2 x LW blocks at (nearly) the pace of LW.  Each wave claims 256 registers: two per SIMD, nothing else.
 // LDS holds both sets (LW = 48, SLOTS = 3: 2 x 73 KB).  One barrier per round for all eight waves.
-template <bool EXCLUSIVE, int SETS, int LW, int SLOTS>
+template <bool EXCLUSIVE, int SETS, int LW, int SLOTS, int STEPS>
 __global__ __launch_bounds__(256 * SETS) void ac_encode_lanes_k(AcEncArgs a) {
-  static_assert(SLOTS >= 3 && SLOTS <= 9 && LW <= 64 && (SETS == 1 || SETS == 2), "");
-  __shared__ AclShared<LW, SLOTS, AclRing<LW, SETS>::WORDS> shs[SETS];
+  static_assert(SLOTS >= 3 && SLOTS <= 9 && LW <= 64 && (SETS == 1 || SETS == 2) && (STEPS == 16 || STEPS == 32), "");
+  using Shared = AclShared<LW, SLOTS, STEPS, AclRing<LW, SETS, STEPS>::WORDS>;
+  static_assert(sizeof(Shared) * SETS <= 160 * 1024, "the workgroup's arrays must fit into the LDS of a CU");
+  __shared__ Shared shs[SETS];
   const int lane = lane_id();
   const int w = wave_id();
   // SETS == 1: 0 chain, 1 gather, 2 sink, 3 writer: the four SIMDs of the CU.  SETS == 2: see above.
@@ -261,7 +281,7 @@ __global__ __launch_bounds__(256 * SETS) void ac_encode_lanes_k(AcEncArgs a) {
   const u32 stab = a.pairing == 1 ? 0x01011010u : a.pairing == 2 ? 0x01011010u : 0x01011010u;  // set of wave w
   const int role = SETS == 1 ? w : (int)((rtab >> (4 * w)) & 15u);
   const int set = SETS == 1 ? 0 : (int)((stab >> (4 * w)) & 15u);
-  AclShared<LW, SLOTS, AclRing<LW, SETS>::WORDS> &sh = shs[set];
+  Shared &sh = shs[set];
   // Workgroups are dealt to the 8 XCDs in turn (b and b + 8 share one: MI355X_MICROARCH.md, Workgroup dispatch), and
   // every XCD has an L2 of its own.  A launch holds the blocks of several streams back to back, each stream with its own
   // 4 MB table: the workgroups of an XCD take CONSECUTIVE groups of blocks, so that an L2 serves one or two tables
@@ -274,12 +294,12 @@ __global__ __launch_bounds__(256 * SETS) void ac_encode_lanes_k(AcEncArgs a) {
   const bool have = blk < a.nblocks && (u32)lane < bpw;
   const SCALCE_GLOBAL AcBlockDesc *dp = (const SCALCE_GLOBAL AcBlockDesc *)a.desc + (have ? blk : 0u);
   const u32 n = have ? dp->n : 0u;
-  const u32 nr = (n + ACL_STEPS - 1) / ACL_STEPS;  // rounds of this lane's block
+  const u32 nr = (n + STEPS - 1) / STEPS;  // rounds of this lane's block
   u32 nr_wg = nr;                                    // rounds of the workgroup = those of its longest block
   if (SETS == 2) {                                   // (the other set's blocks as well: one barrier serves both)
     const u32 oblk = (wg * SETS + (u32)(set ^ 1)) * bpw + (u32)lane;
     const u32 on = oblk < a.nblocks && (u32)lane < bpw ? ((const SCALCE_GLOBAL AcBlockDesc *)a.desc + oblk)->n : 0u;
-    const u32 onr = (on + ACL_STEPS - 1) / ACL_STEPS;
+    const u32 onr = (on + STEPS - 1) / STEPS;
     nr_wg = onr > nr_wg ? onr : nr_wg;
   }
 #pragma unroll
@@ -310,21 +330,32 @@ __global__ __launch_bounds__(256 * SETS) void ac_encode_lanes_k(AcEncArgs a) {
     constexpr int AHEAD = SLOTS - 1;
     const SCALCE_GLOBAL u8 *sp = (const SCALCE_GLOBAL u8 *)dp->sym;
     const SCALCE_GLOBAL u64 *tab = (const SCALCE_GLOBAL u64 *)dp->tab;  // compact: [6400][81] bounds (ac_table_k)
-    // 16 symbols of round k.  The block's symbols are 16-byte aligned (blocks start at multiples of 10 MiB of a 16-byte
-    // aligned stream); a read that starts inside the block may run up to 15 bytes past its end (the stream buffers are
-    // padded), one that would start past it falls back to the block's first symbols -- garbage nobody uses either way.
-    auto sym_addr = [&](u32 k) -> const SCALCE_GLOBAL u8 * {
-      const u32 off = k * ACL_STEPS < n ? k * ACL_STEPS : 0u;
+    // Symbols travel in pieces of 16: V pieces make a round.  The block's symbols are 16-byte aligned (blocks start at
+    // multiples of 10 MiB of a 16-byte aligned stream); a read that starts inside the block may run up to 15 bytes past its
+    // end (the stream buffers are padded), one that would start past it falls back to the block's first symbols -- garbage
+    // nobody uses either way.
+    constexpr int V = STEPS / 16;   // pieces per round
+    constexpr int RPC = 8 / V;      // rounds per 128-byte chunk of symbols
+    constexpr int P = 2 * RPC;      // ... and per pair of chunks
+    static_assert(AHEAD <= RPC && (AHEAD - 1) * STEPS <= 63, "");
+    auto sym_addr = [&](u32 u) -> const SCALCE_GLOBAL u8 * {  // piece u of the block
+      const u32 off = u * 16u < n ? u * 16u : 0u;
       return sp + off;
     };
     u32 p0 = 0, p1 = 0;  // the two symbols in front of the next round to be addressed
-    // 16 LDS-direct loads: bounds c and c + 1 of context (p0, p1) in the lane's table -> ops[k % SLOTS][j][lane]
-    auto request = [&](const u32x4 sy, u32 k) {
+    // STEPS LDS-direct loads: bounds c and c + 1 of context (p0, p1) in the lane's table -> ops[k % SLOTS][j][lane].
+    // (s0, s1: the round's pieces; rounds of 16 have one.)
+    auto request = [&](const u32x4 s0, const u32x4 s1, u32 k) {
       uint4 *slot = &sh.ops[k % SLOTS][0][0];
 #pragma unroll
-      for (int j = 0; j < ACL_STEPS; j++) {
-        const u32 word = j < 4 ? sy.x : j < 8 ? sy.y : j < 12 ? sy.z : sy.w;
-        u32 c = (word >> (8 * (j & 3))) & 0xFFu;
+      for (int j = 0; j < STEPS; j++) {
+        if constexpr (STEPS == 32) {
+          if (j == 16) acl_wait_vm<47>();  // (the counter's limit: below)
+        }
+        const u32x4 sy = j < 16 ? s0 : s1;
+        const int q = j & 15;
+        const u32 word = q < 4 ? sy.x : q < 8 ? sy.y : q < 12 ? sy.z : sy.w;
+        u32 c = (word >> (8 * (q & 3))) & 0xFFu;
         const u32 D1 = AC_D - 1;
         c = c < D1 ? c : D1;  // symbols >= AC_D raised E_SYMBOL at ingest; stay inside the table regardless
         const u32 idx = (p0 * AC_D + p1) * (AC_D + 1) + c;
@@ -333,44 +364,52 @@ __global__ __launch_bounds__(256 * SETS) void ac_encode_lanes_k(AcEncArgs a) {
         p1 = c;
       }
     };
-    // Symbols come 128 bytes per lane at a time (8 rounds; two chunks alternate: A = rounds 0..7 of every 16, B = 8..15),
-    // each chunk requested eight rounds before its first symbol is used.  Sixteen bytes per round -- as this wave first
-    // did -- touches every 128-byte line of the block eight times, 0.75 us apart, and beside another shard's front stages
-    // the line has left the L2 in between: the stream was fetched from HBM several times over and a launch took 1.7 x
-    // as long beside the ingest stage as alone.
-    // VMEM in issue order: prologue [A B] wait [R0 .. R(AHEAD-1)], then per iteration i [R(i+AHEAD)] and, twice in 16
-    // iterations, a chunk of 8 loads behind it; R = 16 instructions.  The hardware counts at most 63 outstanding vector
-    // memory instructions per wave: three requests in flight behind the one awaited is as deep as it goes, and everything
-    // older than those -- the chunks, requested 8 rounds ahead -- has landed by then.
+    // Symbols come 128 bytes per lane at a time (RPC rounds; two chunks alternate: A = rounds 0 .. RPC - 1 of every P, B the
+    // others), each chunk requested RPC rounds -- 128 symbols -- before its first symbol is used.  Sixteen bytes per round -- as
+    // this wave first did -- touches every 128-byte line of the block eight times, 0.75 us apart, and beside another shard's
+    // front stages the line has left the L2 in between: the stream was fetched from HBM several times over and a launch
+    // took 1.7 x as long beside the ingest stage as alone.
+    // VMEM in issue order: prologue [A B] wait [R0 .. R(AHEAD-1)], then per iteration i [R(i+AHEAD)] and, twice in P
+    // iterations, a chunk of 8 loads behind it; R = STEPS instructions.  The hardware counts at most 63 outstanding vector
+    // memory instructions per wave, and everything older than the AHEAD - 1 requests behind the one awaited -- the chunks,
+    // requested RPC rounds ahead -- has landed by then.  Rounds of 16 (AHEAD = 4): three requests in flight behind the one
+    // awaited is as deep as it goes, and a request issued on top of them stalls at the limit until the oldest loads land.
+    // Rounds of 32 (AHEAD = 2): close() leaves at most 32 outstanding, so a whole request on top would be 64.  The wave
+    // waits between the halves of a request (vmcnt(47): at most one load, of the request close() waits for next anyway)
+    // and in front of a chunk (vmcnt(55)), so that the count never passes 63 and no issue depends on how the hardware
+    // behaves at the limit; the waits are for the OLDEST loads, those the next close() needs, and cost nothing extra.
     u32x4 ca[8], cb[8];
-    auto load_chunk = [&](u32x4 (&c)[8], u32 first) {
+    auto load_chunk = [&](u32x4 (&c)[8], u32 first) {  // the chunk that begins with round `first`
+      if constexpr (STEPS == 32) acl_wait_vm<55>();
 #pragma unroll
-      for (int q = 0; q < 8; q++) c[q] = acl_load16(sym_addr(first + q));
+      for (int q = 0; q < 8; q++) c[q] = acl_load16(sym_addr(first * V + q));
     };
     if (inrow) {
       load_chunk(ca, 0);
-      load_chunk(cb, 8);
+      load_chunk(cb, RPC);
 #pragma unroll
       for (int q = 0; q < 8; q++) { acl_wait_vm<0>(ca[q]); acl_wait_vm<0>(cb[q]); }
 #pragma unroll
-      for (int q = 0; q < AHEAD; q++) request(ca[q], q);
-      acl_wait_vm<(AHEAD - 1) * 16>();  // round 0 is in LDS
+      for (int q = 0; q < AHEAD; q++) request(ca[q * V], ca[q * V + V - 1], q);
+      acl_wait_vm<(AHEAD - 1) * STEPS>();  // round 0 is in LDS
       asm volatile("s_barrier" ::: "memory");
       // iteration i: request round i + AHEAD; round i + 1 is in LDS when at most the AHEAD - 1 requests behind it are outstanding
+      // (a chunk's loads, where they were issued behind the request, make the wait stricter than it has to be: never laxer)
       auto close = [&]() {
-        acl_wait_vm<(AHEAD - 1) * 16>();
+        acl_wait_vm<(AHEAD - 1) * STEPS>();
         asm volatile("s_barrier" ::: "memory");
       };
-      for (u32 i0 = 0; i0 < nr_wg; i0 += 16) {
+      for (u32 i0 = 0; i0 < nr_wg; i0 += P) {
 #pragma unroll
-        for (int j = 0; j < 16; j++) {
+        for (int j = 0; j < P; j++) {
           if (i0 + j < nr_wg) {
-            // round i0 + j + AHEAD: its symbols are element (j + AHEAD) % 16 of the chunk pair; chunk A is free for the rounds
-            // 16 .. 23 behind i0 once round i0 + 7 has been requested (j = 8 - AHEAD), chunk B eight iterations later
-            const int e = (j + AHEAD) & 15;
-            request(e < 8 ? ca[e] : cb[e - 8], i0 + j + AHEAD);
-            if (j == 8 - AHEAD) load_chunk(ca, i0 + 16);
-            if (j == 16 - AHEAD) load_chunk(cb, i0 + 24);
+            // round i0 + j + AHEAD: its symbols are round (j + AHEAD) % P of the chunk pair; chunk A is free for the rounds
+            // P .. P + RPC - 1 behind i0 once round i0 + RPC - 1 has been requested (j = RPC - AHEAD), chunk B RPC iterations later
+            const int e = (j + AHEAD) % P;
+            const int f = (e % RPC) * V;
+            request(e < RPC ? ca[f] : cb[f], e < RPC ? ca[f + V - 1] : cb[f + V - 1], i0 + j + AHEAD);
+            if (j == RPC - AHEAD) load_chunk(ca, i0 + P);
+            if (j == P - AHEAD) load_chunk(cb, i0 + P + RPC);
             close();
           }
         }
@@ -391,15 +430,15 @@ __global__ __launch_bounds__(256 * SETS) void ac_encode_lanes_k(AcEncArgs a) {
       for (u32 r = 0; r < nr_wg; r++) {
         const int slot = r % SLOTS;
         const u32 lo0 = lo, M0 = M, Q0 = Q;
-        // all 16 operand reads are issued before the first step (read at the point of use, every step waited for a full
-        // LDS round trip)
-        uint4 g[ACL_STEPS];
+        // all STEPS operand reads are issued before the first step (read at the point of use, every step waited for a full
+        // LDS round trip): 4 x STEPS registers, of a register file this wave has to itself
+        uint4 g[STEPS];
 #pragma unroll
-        for (int j = 0; j < ACL_STEPS; j++) g[j] = sh.ops[slot][j][lane];
+        for (int j = 0; j < STEPS; j++) g[j] = sh.ops[slot][j][lane];
         u32 topw = 0;  // g(c_hi) = 2^64 - 1 marks the last symbol of a context (ac_table_k); no regular high word reaches that
         u32 Bp = 0, Qp = 0;  // (the even step of a pair: two steps leave in one 16-byte record)
 #pragma unroll
-        for (int j = 0; j < ACL_STEPS; j++) {
+        for (int j = 0; j < STEPS; j++) {
           u32 B, t;
           acl_step_plain(lo, M, g[j], ones, zero, B, t);
           Q += t;
@@ -409,7 +448,7 @@ __global__ __launch_bounds__(256 * SETS) void ac_encode_lanes_k(AcEncArgs a) {
         }
         const bool live = r < nr;
         const bool poisoned = a.test_poison && r % a.test_poison == 0;
-        const bool complete = r > 0 && r * ACL_STEPS + ACL_STEPS <= n;  // not the round of the raw symbols, not a tail
+        const bool complete = r > 0 && r * STEPS + STEPS <= n;  // not the round of the raw symbols, not a tail
         const bool fast_ok = complete && topw != 0xFFFFFFFFu && M0 != 0u && M != 0u && !poisoned;
         const bool fix = live && !fast_ok;  // this lane's records of the round are rewritten by general steps (a lane whose
                                             // block has ended computes garbage nobody reads: the sink skips it)
@@ -417,11 +456,11 @@ __global__ __launch_bounds__(256 * SETS) void ac_encode_lanes_k(AcEncArgs a) {
           if (fix) {
             u32 glo = lo0 & 0x7FFFFFFFu, ghi = glo + M0 - 1u, gq = Q0;
             const u32 jstart = r == 0 ? 2u : 0u;
-            const u32 left = n - r * ACL_STEPS;
-            const u32 jend = left < (u32)ACL_STEPS ? left : (u32)ACL_STEPS;
+            const u32 left = n - r * STEPS;
+            const u32 jend = left < (u32)STEPS ? left : (u32)STEPS;
             u32 Bp = 0, Qp = 0;
 #pragma unroll 1
-            for (u32 j = 0; j < (u32)ACL_STEPS; j++) {
+            for (u32 j = 0; j < (u32)STEPS; j++) {
               const uint4 gj = sh.ops[slot][j][lane];
               u32 B = 0, t = 0;
               if (j >= jstart && j < jend) acl_step_general(glo, ghi, gj, B, t);
@@ -443,7 +482,7 @@ __global__ __launch_bounds__(256 * SETS) void ac_encode_lanes_k(AcEncArgs a) {
   } else if (role == 2) {
     // ================= sink: one bit accumulator per lane, one round behind the chain =================
     if (inrow) {
-      AclSink<LW> sk;
+      AclSink<LW, STEPS> sk;
       {
         const SCALCE_GLOBAL u8 *sp = (const SCALCE_GLOBAL u8 *)dp->sym;
         const u32 s0 = n ? (u32)sp[0] : 0u, s1 = n > 1 ? (u32)sp[1] : 0u;
@@ -454,15 +493,15 @@ __global__ __launch_bounds__(256 * SETS) void ac_encode_lanes_k(AcEncArgs a) {
       barrier_lds_only();
       auto take = [&](u32 r) {  // the records of round r
         if (r < nr && sk.room()) {  // (per lane: a block that has ended has no records)
-          uint4 v[ACL_STEPS / 2];
+          uint4 v[STEPS / 2];
 #pragma unroll
-          for (int j = 0; j < ACL_STEPS / 2; j++) v[j] = sh.rec[r & 1][j][lane];
+          for (int j = 0; j < STEPS / 2; j++) v[j] = sh.rec[r & 1][j][lane];
           const u32 s2 = sk.w2, s1 = sk.w1, s0 = sk.w0, sq = sk.Qb;
           sk.ncar = ~0u;
           // two steps, one record for the writer wave: the ring stores (an LDS instruction and its address per step) are its
           // work, not this wave's -- the sink sets the pace of a round
 #pragma unroll
-          for (int j = 0; j < ACL_STEPS / 2; j++) {
+          for (int j = 0; j < STEPS / 2; j++) {
             uint4 o;
             sk.step(v[j].y, v[j].x, o.x, o.y);
             sk.step(v[j].w, v[j].z, o.z, o.w);
@@ -472,7 +511,7 @@ __global__ __launch_bounds__(256 * SETS) void ac_encode_lanes_k(AcEncArgs a) {
             if (sk.ncar == 0u) {
               sk.w2 = s2; sk.w1 = s1; sk.w0 = s0; sk.Qb = sq;
 #pragma unroll 1
-              for (int j = 0; j < ACL_STEPS / 2; j++) {
+              for (int j = 0; j < STEPS / 2; j++) {
                 const uint4 x = sh.rec[r & 1][j][lane];
                 sk.careful(x.y, x.x);
                 sk.careful(x.w, x.z);
@@ -498,13 +537,16 @@ __global__ __launch_bounds__(256 * SETS) void ac_encode_lanes_k(AcEncArgs a) {
     }
   } else {
     // ================= writer: final words out of the staging ring =================
-    constexpr u32 RING = AclRing<LW, SETS>::WORDS;
+    constexpr u32 RING = AclRing<LW, SETS, STEPS>::WORDS;
     SCALCE_GLOBAL u32 *dst = (SCALCE_GLOBAL u32 *)dp->dst;
     const u32 wcap = dp->cap / 4;
     u32 wo = 0;  // words of this lane's block in global memory (multiple of 32 until the end)
     // In place (AC_BLOCK_IN_PLACE: dst IS the block's symbols): a line may only go where the gather wave has been for good.  In
-    // iteration i that wave is requesting round i + SLOTS - 1 out of chunks of eight rounds it loaded eight rounds earlier; what
-    // is in flight lies behind round i: lines end in front of round i - 1 (4 words per round).  A line that is ready and may
+    // iteration i that wave is requesting round i + SLOTS - 1 out of 128-symbol chunks it loaded 128 symbols earlier: every load
+    // of symbols that is in flight or still to come starts at symbol STEPS x (i + 1) or behind it (the chunk loaded in an
+    // iteration begins 128 / STEPS + SLOTS - 1 rounds behind that iteration, and has landed SLOTS - 2 iterations later).  Lines
+    // end in front of symbol STEPS x (i - 1) -- two rounds in front of anything the gather wave may still read, whatever the
+    // round's length -- which is word STEPS / 4 x (i - 1) of the block: a symbol is a byte.  A line that is ready and may
     // not go is the end of the block -- its output has caught up with its input: E_ACOVERFLOW, nothing more is written (the
     // host runs the shard again with buffers of its own).
     const bool in_place = have && (dp->flags & AC_BLOCK_IN_PLACE) != 0;
@@ -549,11 +591,11 @@ __global__ __launch_bounds__(256 * SETS) void ac_encode_lanes_k(AcEncArgs a) {
     // older round's, and putting that back would undo newer words that are not out yet.
     auto apply = [&](u32 r) {
       if (inrow && r < nr) {
-        uint4 e[ACL_STEPS / 2];
+        uint4 e[STEPS / 2];
 #pragma unroll
-        for (int j = 0; j < ACL_STEPS / 2; j++) e[j] = sh.fifo[r & 1][j][lane];
+        for (int j = 0; j < STEPS / 2; j++) e[j] = sh.fifo[r & 1][j][lane];
 #pragma unroll
-        for (int j = 0; j < ACL_STEPS / 2; j++) {
+        for (int j = 0; j < STEPS / 2; j++) {
           sh.stage[e[j].y & (RING - 1)][lane] = e[j].x;
           sh.stage[e[j].w & (RING - 1)][lane] = e[j].z;
         }
@@ -562,7 +604,7 @@ __global__ __launch_bounds__(256 * SETS) void ac_encode_lanes_k(AcEncArgs a) {
     barrier_lds_only();
     for (u32 i = 0; i < nr_wg; i++) {  // iteration i: the records of round i - 2 (the sink took it in iteration i - 1), then what it published there
       if (i > 1) apply(i - 2);
-      if (i > 0) drain(inrow ? sh.pub[(i - 1) & 1][lane] : 0u, i > 1 ? (4u * (i - 1u)) >> a.inplace_shift : 0u);
+      if (i > 0) drain(inrow ? sh.pub[(i - 1) & 1][lane] : 0u, i > 1 ? ((u32)(STEPS / 4) * (i - 1u)) >> a.inplace_shift : 0u);
       barrier_lds_only();
     }
     barrier_lds_only();  // the sink's last round is in the records

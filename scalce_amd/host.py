@@ -772,6 +772,13 @@ class Batch:
         self.L.scalce_batch_reruns.argtypes = [C.c_void_p]
         return int(self.L.scalce_batch_reruns(self.h))
 
+    @property
+    def coder_round(self):
+        """Symbols per round of the last one-block-per-lane coder launch this batch led (0: none): which kernel ran."""
+        self.L.scalce_batch_coder_round.restype = C.c_int
+        self.L.scalce_batch_coder_round.argtypes = [C.c_void_p]
+        return int(self.L.scalce_batch_coder_round(self.h))
+
     def qual_bytes(self, mate=0):
         n = C.c_uint64()
         self._check(self.L.scalce_batch_qual_bytes(self.h, mate, C.byref(n)))
