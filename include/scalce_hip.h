@@ -194,6 +194,12 @@ int scalce_batch_set_stream_scratch(scalce_batch *b, int on);
 int scalce_batch_set_code_in_place(scalce_batch *b, int on);
 uint64_t scalce_batch_reruns(const scalce_batch *b);  /* shards of this batch that had to be run again from their text */
 int scalce_batch_coder_round(const scalce_batch *b);  /* symbols per round of the last one-block-per-lane coder launch this batch led; 0: none */
+/* For tests: the path the last scalce_batch_quality call took for `mate`.  out = {source, lo, A, inside}: source = where the
+ * symbol range came from -- 0: nothing was counted (-A, no qualities, an empty piece), 1: the tile ranges the one-pass ingest
+ * left, 2: a scan of the piece's q' rows, 3: the whole alphabet (fused rows without tile ranges); lo, A = first symbol and
+ * span of the counters laid out, inside = 1 when no symbol of the piece lies outside them (all 0 when source is 0).
+ * Waits for the whole device and reads the three back. */
+int scalce_batch_quality_plan(const scalce_batch *b, int mate, uint32_t out[4]);
 /* edge[0..1] = the first two, edge[2..3] = the last two q' symbols of the rows held (input order), *nsym = how many there are,
  * *read_len (may be NULL) = symbols per row: what a rank of a sharded run tells its neighbours (qualities.cpp:179-198: prev[]
  * runs across reads, so two trigrams straddle every rank boundary).  Runs on `stream` and synchronises it. */

@@ -425,9 +425,12 @@ extern "C" int scalce_batch_set_fused_rows(scalce_batch *b, int on) {
 }
 
 // ---- stage 1: quality statistics -------------------------------------------------------------------
+// where a mate's symbol range came from (scalce_batch_quality_plan, scalce_hip.h)
+enum QualitySource : u32 { QSRC_NONE = 0, QSRC_TILES = 1, QSRC_ROWS = 2, QSRC_WHOLE = 3 };
 extern "C" int scalce_batch_quality(scalce_batch *b, void *stream) {
   if (!b) return SCALCE_ERR_ARG;
   scalce_workspace &w = *b->ws;
+  b->quality_source[0] = b->quality_source[1] = QSRC_NONE;
   if (b->nq) return SCALCE_OK;  // -Q / -f: no qualities, no statistics (compress.cpp:689,697) -- nothing is launched
   hipStream_t s = (hipStream_t)stream;
   scalce_ctx *c = b->ctx;
@@ -451,16 +454,19 @@ extern "C" int scalce_batch_quality(scalce_batch *b, void *stream) {
     if (b->mm_valid[m] && w.tile_mm_owner[m] == b) {
       const u32 nt = cdiv(b->text_bytes[m], ING_TILE);
       LAUNCH(tile_minmax_reduce_k, cdiv(nt, 256 * 16) ? cdiv(nt, 256 * 16) : 1, 256, 0, s, w.tile_mm[m].as<u16>(), nt, minmax);
+      b->quality_source[m] = QSRC_TILES;
     } else if (b->qstride[m] != (u32)b->L[m]) {
       // (fused rows and no tile ranges -- another batch of the workspace has ingested since: the whole alphabet, more passes)
       static const u32 whole[2] = {0u, 79u};
       HIP_TRY(c, hipMemcpyAsync(minmax, whole, sizeof whole, hipMemcpyHostToDevice, s));
+      b->quality_source[m] = QSRC_WHOLE;
     } else {
       LAUNCH(sym_range_k, 2048, 256, 0, s, q, n, minmax);
+      b->quality_source[m] = QSRC_ROWS;
     }
     u32 *prev = b->d_scr->prev[m];  // the two symbols in front of this piece
     LAUNCH(tri_prev_k, 1, 1, 0, s, w.q[m].as<u8>(), (u32)b->L[m], b->qstride[m], before, b->p.qprev[m][0], b->p.qprev[m][1], prev);
-    u32 *range = b->d_scr->range;  // {lo, A, all symbols inside}: span of the symbols that occur
+    u32 *range = b->d_scr->range[m];  // {lo, A, all symbols inside}: span of the symbols that occur
     LAUNCH(tri_range_k, 1, 1, 0, s, minmax, prev, range);
     unsigned long long *tiles = b->d_scr->tri_tiles;  // one tile counter per pass
     HIP_TRY(c, hipMemsetAsync(tiles, 0, sizeof b->d_scr->tri_tiles, s));
@@ -477,5 +483,19 @@ extern "C" int scalce_batch_quality(scalce_batch *b, void *stream) {
       LAUNCH(tri_check_k, 64, 256, 0, s, b->freq4[m].as<u64>(), b->tri_expected[m], &chk->acc, &chk->done, b->d_err);
     }
   }
+  return SCALCE_OK;
+}
+
+// what the last scalce_batch_quality did for `mate`: {source, lo, A, inside} -- the branch the host took and what tri_range_k
+// left in range[mate].  Waits for the device and reads back: for tests.
+extern "C" int scalce_batch_quality_plan(const scalce_batch *b, int mate, uint32_t out[4]) {
+  if (!b || !out || mate < 0 || mate >= b->nm) return SCALCE_ERR_ARG;
+  out[0] = b->quality_source[mate];
+  out[1] = out[2] = out[3] = 0;
+  if (out[0] == QSRC_NONE) return SCALCE_OK;
+  scalce_ctx *c = b->ctx;
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, hipDeviceSynchronize());
+  HIP_TRY(c, hipMemcpy(out + 1, b->d_scr->range[mate], 3 * sizeof(u32), hipMemcpyDeviceToHost));
   return SCALCE_OK;
 }

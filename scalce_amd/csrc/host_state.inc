@@ -258,7 +258,7 @@ struct BatchScratch {
   struct TriCheck { u64 acc; u32 done, pad; } tri_check[2];  // tri_check_k, per mate: cleared as one
   u32 minmax[2];         // smallest / largest symbol of the piece
   u32 prev[2][2];        // per mate: the two symbols in front of the piece
-  u32 range[3];          // {lo, A, all symbols inside}: span of the symbols that occur
+  u32 range[2][3];       // per mate: {lo, A, all symbols inside}: span of the symbols that occur (scalce_batch_quality_plan reads it back)
   // ---- tokenize
   u64 cut_carry;         // bytes in the chunk left open behind the last cut (scalce_batch_chunk_plan)
   u32 ncuts;             // ... and how many cuts
@@ -305,6 +305,7 @@ struct scalce_batch {
   bool appending = false;    // the pieces came through scalce_batch_append
   bool lean = false;         // release what a stage no longer needs (runs sized for most of HBM)
   u64 tri_expected[2] = {0, 0};  // trigrams counted so far (tri_check_k)
+  u32 quality_source[2] = {0, 0};  // where the last scalce_batch_quality took the mate's symbol range from (scalce_batch_quality_plan)
   u64 names_in_used = 0;     // bytes of the long-name store in use
   u64 S_rows = ~0ull;        // rows the record-size prefix sums in S cover (scalce_batch_chunk_plan), ~0 = stale
   u64 walk_rows = 0;         // rows [0, walk_rows) whose first tokenizer walk (tok_bucket / tok_pos) scalce_batch_chunk_plan has

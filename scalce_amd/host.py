@@ -112,6 +112,7 @@ def lib():
     L.scalce_batch_set_lean.argtypes = [vp, i32]
     L.scalce_batch_set_lean.restype = None
     L.scalce_batch_quality.argtypes = [vp, vp]
+    L.scalce_batch_quality_plan.argtypes = [vp, i32, C.POINTER(C.c_uint32)]
     L.scalce_batch_tokenize.argtypes = [vp, vp, vp]
     L.scalce_batch_order.argtypes = [vp, vp]
     L.scalce_batch_emit.argtypes = [vp, vp]
@@ -659,6 +660,13 @@ class Batch:
 
     def quality(self, stream=0):
         self._check(self.L.scalce_batch_quality(self.h, stream))
+
+    def quality_plan(self, mate=0):
+        """For tests: the path the last quality() took for `mate` (scalce_batch_quality_plan) -> (source, lo, A, inside);
+        source 0: nothing counted, 1: tile ranges of the one-pass ingest, 2: the q' rows scanned, 3: the whole alphabet."""
+        out = (C.c_uint32 * 4)()
+        self._check(self.L.scalce_batch_quality_plan(self.h, int(mate), out))
+        return tuple(int(x) for x in out)
 
     def tokenize(self, d_prior_counts=None, stream=0):
         self._check(self.L.scalce_batch_tokenize(self.h, d_prior_counts, stream))

@@ -121,8 +121,10 @@ def qmap_init(stat, lossy):
     return q.offset, np.array(list(q.values), dtype=np.int32)
 
 
-def quality_stream(quals, bases, offset, values, no_ac=False):
-    """Apply output_quality to every read in input order.  Returns (q' (N,L) uint8, freq4 u64[512000])."""
+def quality_stream(quals, bases, offset, values, no_ac=False, prev=(500, 500)):
+    """Apply output_quality to every read in input order.  Returns (q' (N,L) uint8, freq4 u64[512000]).
+    prev: the two q' symbols in front of the first read (500 = none; qualities.cpp:179).  The counters all start at 1 at the
+    mate's very first symbol (prev[1] = 500) and at 0 when symbols are carried in: the +1 was the earlier shard's."""
     quals = np.ascontiguousarray(quals, dtype=np.uint8)
     bases = np.ascontiguousarray(bases, dtype=np.uint8)
     n, L = quals.shape
@@ -132,7 +134,7 @@ def quality_stream(quals, bases, offset, values, no_ac=False):
         q.values[i] = int(values[i])
     out = np.empty((n, L), dtype=np.uint8)
     freq4 = np.zeros(512000, dtype=np.uint64)
-    state = np.array([500, 500], dtype=np.uint32)
+    state = np.array([int(prev[0]), int(prev[1])], dtype=np.uint32)
     f = lib().orc_quality
     qb, bb, ob = quals.ctypes.data, bases.ctypes.data, out.ctypes.data
     for r in range(n):
