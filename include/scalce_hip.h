@@ -486,6 +486,49 @@ typedef struct {
 int scalce_stream_decompress(scalce_ctx *ctx, const scalce_unpack_params *p, scalce_read_fn rd[2][3], void *user[2][3],
                              scalce_write_fn wr, void *wr_user, scalce_unpack_stats *stats, char *errbuf, size_t errcap);
 
+/* A RANGE of records of the archive: records first_record .. first_record + nrecords - 1 in archive order, the order a whole
+ * run writes them in (pairs for two mates: both mates take the same range, interleaved or one after the other).  The format
+ * needs no index for it: what lies in front of the range is passed over stream by stream -- bucket headers are hopped (each
+ * one is read and checked, the records behind it are not), mate 2's bare records, the raw quality rows of a -A archive and
+ * whole frames of the coded quality stream (by their size words) are skipped, names are hopped by their length bytes -- and
+ * only the frames that hold a symbol of the range are decoded: the first from its beginning, the symbols in front of the
+ * range's first record are dropped, the last one up to the range's last symbol.  Nothing behind the range is read.
+ * scalce_stream_decompress is this call with the range {0, ~0ull, no skips}; windows, buffers and wr are the same, and the
+ * first_record handed to wr -- and the index of made-up names, <library>.<index> -- stays archive-absolute.
+ * A first_record at or beyond the end gives no record and SCALCE_OK; nrecords is clamped to the end.  An archive that does
+ * not say how many records it holds (no coded qualities) ends where the streams that end a whole run end.  A stream that
+ * ends inside the part passed over, or inside the range, is the error it is for a whole run; A STREAM THAT ENDS BEHIND THE
+ * RANGE IS NOT NOTICED.
+ *   skip[m][k]   optional, per stream (0 r, 1 n, 2 q), called with the stream's `user`: passes over nbytes without delivering
+ *                them (a plain file seeks).  Returns the bytes passed over (< nbytes: the stream ended there), < 0: error.
+ *                NULL: the library reads through rd and drops the bytes (a gzip container).  The look-ahead buffer of a
+ *                stream (SCALCE_UNPACK_LOOKAHEAD_BYTES) is used up before skip is called; the name stream is always read. */
+#define SCALCE_UNPACK_LOOKAHEAD_BYTES (1u << 20)
+typedef int64_t (*scalce_skip_fn)(void *user, uint64_t nbytes);
+typedef struct {
+  uint64_t first_record;        /* zero-based, in archive order = the order -d writes; pairs for two mates */
+  uint64_t nrecords;            /* ~0ull: to the end */
+  scalce_skip_fn skip[2][3];    /* [mate][r, n, q], any of them NULL */
+} scalce_unpack_range;
+typedef struct {
+  uint64_t first_record, nrecords;          /* the range in force after clamping to the archive */
+  uint64_t total_records;                   /* ~0ull when the archive does not say (no coded qualities) */
+  uint64_t frames_decoded[2], frames_passed[2], symbols_decoded[2];   /* per mate; symbols: what the decoder was launched
+                                               for, the dropped ones in front included (the plan's out[2] + out[3]) */
+  uint64_t bytes_delivered[2][3];           /* what rd handed over, dropped bytes included */
+  uint64_t bytes_skipped[2][3];             /* what went through skip */
+} scalce_unpack_range_stats;
+int scalce_stream_decompress_range(scalce_ctx *ctx, const scalce_unpack_params *p, const scalce_unpack_range *range /* NULL: all */,
+                                   scalce_read_fn rd[2][3], void *user[2][3], scalce_write_fn wr, void *wr_user,
+                                   scalce_unpack_stats *stats, scalce_unpack_range_stats *range_stats, char *errbuf, size_t errcap);
+/* The range's arithmetic over the coded quality stream, no device call: records of read_len symbols, frames of
+ * SCALCE_AC_BLOCK symbols, total_syms in the stream; first / n are clamped to its total_syms / read_len records.
+ * out[0] = the first frame to decode (= frames passed over), out[1] = frames to decode (0 when the range is empty),
+ * out[2] = symbols of frame out[0] in front of the range's first record (decoded and dropped), out[3] = symbols of the range
+ * behind them -- n * read_len, plus the stream's trailing symbols (fewer than a record) when the range reaches the last record,
+ * as a whole run decodes them.  The decoder is launched for out[2] + out[3] symbols. */
+int scalce_range_plan_quality(int read_len, uint64_t first, uint64_t n, uint64_t total_syms, uint64_t out[4]);
+
 /* ---- runs sharded over several GPUs: one process per GPU, ONE archive -----------------------------------------
  * The reference has no distributed mode; what it carries across reads is what ranks exchange (see comm.cpp).  The
  * archive of a sharded run is byte for byte the archive of the same input on one GPU -- and of the reference at -T 1 with

@@ -70,6 +70,8 @@ struct Options {
   uint64_t bucket_set_size = 4ull << 30;  // main.cpp:68
   std::string out, library, patterns, temp = "__temp__", patterns_bin;
   uint64_t window = 0;                    // --window: bytes of FASTQ text per decompression window (0: the library's default)
+  bool has_range = false;                 // --records FIRST[:COUNT]: decompress this range of records (pairs) only
+  uint64_t range_first = 0, range_count = ~0ull;
   int gpus = 1;                           // --gpus N: one process per GPU, ONE archive (plain-text input, -c no)
   int container = 1;                      // 0 plain, 1 gzip (main.cpp:181-184 at -T 1)
   uint64_t first_file_bytes[2] = {0, 0};  // --gpus over several files written out as one: where the first file ends (the
@@ -104,6 +106,10 @@ static const char *HELP_TEXT =
     "      --window NUM[K|M|G]     decompression: bytes of FASTQ text per window (default 1G; -Q counts a record as its FASTQ).  The archive moves through the\n"
     "                              device in windows of whole records -- at least one record each --, so memory follows the\n"
     "                              window, not the archive, and -o - writes each window as it arrives\n"
+    "      --records FIRST[:COUNT] decompression: only COUNT records (pairs under -r / -i; to the end without COUNT) from record\n"
+    "                              FIRST on, counted from 0 in the order -d writes them.  What lies in front is passed over, not\n"
+    "                              decoded (plain files seek); -S parts and made-up names (-n) count from FIRST; a file that\n"
+    "                              is cut short behind the range is not noticed\n"
     "  -d, --decompress    -v, --version    -h, --help\n"
     "      --gpus N                compress on N GPUs, one process each, into ONE archive that is byte for byte the archive of\n"
     "                              one GPU (and of the reference at -T 1 with the same -B); input: one plain FASTQ file (pair), -c no\n"
@@ -1104,6 +1110,15 @@ struct ArchiveFile {
     if (k > 0) f->off += (uint64_t)k;
     return (int64_t)k;
   }
+  // scalce_skip_fn of a plain file: the offset moves, up to the file's end
+  static int64_t skip(void *user, uint64_t nbytes) {
+    ArchiveFile *f = static_cast<ArchiveFile *>(user);
+    struct stat st;
+    if (f->gz || fstat(f->fd, &st) != 0) return -1;
+    const uint64_t size = (uint64_t)st.st_size, k = std::min(nbytes, size > f->off ? size - f->off : 0);
+    f->off += k;
+    return (int64_t)k;
+  }
   ~ArchiveFile() { if (fd >= 0) ::close(fd); }
 };
 
@@ -1192,9 +1207,16 @@ static int do_decompress(const Options &o, const std::string &path, scalce_ctx *
   p.window_text_bytes = o.window;
   TextSink sink;
   sink.o = &o;
+  scalce_unpack_range rg;
+  memset(&rg, 0, sizeof rg);
+  rg.first_record = o.range_first;
+  rg.nrecords = o.range_count;
+  for (int m = 0; m < nm; m++)
+    for (int k = 0; k < 3; k++) rg.skip[m][k] = files[m][k].gz ? nullptr : ArchiveFile::skip;
   scalce_unpack_stats st;
+  scalce_unpack_range_stats rs;
   char err[1024] = "";
-  const int rc = scalce_stream_decompress(ctx, &p, rd, user, TextSink::write, &sink, &st, err, sizeof err);
+  const int rc = scalce_stream_decompress_range(ctx, &p, &rg, rd, user, TextSink::write, &sink, &st, &rs, err, sizeof err);
   if (rc) {
     // (parts already written stay where they are)
     if (st.error_wants_file && st.error_mate >= 0 && st.error_stream >= 0)
@@ -1207,6 +1229,13 @@ static int do_decompress(const Options &o, const std::string &path, scalce_ctx *
       now() - t0, st.read_wait_s, st.decode_s, st.records_s, st.write_s, nm == 2 && !o.interleave ? ", one mate after the other" : "");
   LOG("\tWindows: %llu of up to %llu bytes of text; device memory held at most %llu bytes\n", (unsigned long long)st.windows,
       (unsigned long long)st.window_text_bytes, (unsigned long long)st.peak_device_bytes);
+  if (o.has_range) {
+    char total[32] = "unknown";
+    if (rs.total_records != ~0ull) snprintf(total, sizeof total, "%llu", (unsigned long long)rs.total_records);
+    LOG("\tRange: records %llu to %llu of %s; quality frames decoded %llu, passed over %llu\n", (unsigned long long)rs.first_record,
+        (unsigned long long)(rs.first_record + rs.nrecords), total, (unsigned long long)(rs.frames_decoded[0] + rs.frames_decoded[1]),
+        (unsigned long long)(rs.frames_passed[0] + rs.frames_passed[1]));
+  }
   return 0;
 }
 
@@ -1220,7 +1249,8 @@ int main(int argc, char **argv) {
                                      {"bucket-set-size", 1, 0, 'B'}, {"paired-end", 0, 0, 'r'}, {"skip-names", 1, 0, 'n'},
                                      {"split-reads", 1, 0, 'S'}, {"fasta", 0, 0, 'f'}, {"threads", 1, 0, 'T'},
                                      {"version", 0, 0, 'v'}, {"no-arithmetic", 0, 0, 'A'}, {"patterns-bin", 1, 0, 1000},
-                                     {"gpus", 1, 0, 1001}, {"interleave", 0, 0, 'i'}, {"window", 1, 0, 1002}, {0, 0, 0, 0}};
+                                     {"gpus", 1, 0, 1001}, {"interleave", 0, 0, 'i'}, {"window", 1, 0, 1002},
+                                     {"records", 1, 0, 1003}, {0, 0, 0, 0}};
   int opt;
   while ((opt = getopt_long(argc, argv, "vhp:T:dc:o:fs:t:B:rQAn:P:S:i", long_opt, 0)) != -1) {
     switch (opt) {
@@ -1263,6 +1293,19 @@ int main(int argc, char **argv) {
         if (e == optarg || !v || (*e && (unit == 1 || e[1]))) FAIL("--window takes a positive number of bytes, optionally ended with K, M or G.\n");
         o.window = v * unit;
       } break;
+      case 1003: {
+        // FIRST[:COUNT], both plain decimal numbers (strtoull alone would take a sign, blanks and an empty string)
+        auto number = [](const char *b, const char *e, uint64_t &v) {
+          if (b == e || e - b > 19) return false;
+          v = 0;
+          for (; b != e; b++) { if (*b < '0' || *b > '9') return false; v = v * 10 + (uint64_t)(*b - '0'); }
+          return true;
+        };
+        const char *colon = strchr(optarg, ':'), *end = optarg + strlen(optarg);
+        if (!number(optarg, colon ? colon : end, o.range_first) || (colon && !number(colon + 1, end, o.range_count)))
+          FAIL("--records takes FIRST or FIRST:COUNT, two non-negative numbers of records.\n");
+        o.has_range = true;
+      } break;
       default: fputs(HELP_TEXT, stdout); return 0;
     }
   }
@@ -1271,6 +1314,7 @@ int main(int argc, char **argv) {
   if (o.interleave && o.paired) FAIL("Interleaved option (-i) cannot be used with paired-end option (-r).\n");
   if (o.out.empty()) FAIL("No output file specified.\n");
   if (!o.use_names && o.library.empty()) FAIL("No library name specified.\n");
+  if (o.has_range && !o.decompress) FAIL("--records can be only used with decompression (-d).\n");
   if (o.decompress && files.size() > 1) FAIL("Too many files specified (decompression only supports one file).\n");
   if (o.lossy < 0 || o.lossy > 100) FAIL("Percentage must be in range [0,100].\n");
   if (o.out == "-" && (o.split || o.paired)) FAIL("stdout can be only used with single-end file decompression. It cannot be used with --split-reads option!\n");

@@ -16,6 +16,15 @@
 // Every buffer is sized from the window, the read length and the core table (DESIGN.md gives the formula), none from the
 // archive; nothing is allocated or freed per window.
 //
+// A RANGE of records (scalce_stream_decompress_range; a whole run is the range from record 0 to the end) goes through the same
+// window loop.  Before the first window, pass_over() moves every stream to the range's first record without handing a byte
+// to the device: bucket headers are hopped, mate 2's records, raw quality rows and whole coded frames are skipped (the
+// caller's skip, or reads that are dropped), names are hopped by their length bytes.  The decoder starts at the frame that
+// holds the range's first symbol; the symbols of that frame in front of the record are decoded -- a frame is one chain -- and
+// left in front of the first window's; the last frame of the range is launched for the symbols up to the range's end.
+// Nothing behind the range is read: a stream that is cut short there is NOT noticed, and the check that the read streams
+// hold no more records than the others is made only where the range ends with the archive.
+//
 // Built on the public C ABI only (include/scalce_hip.h) plus the HIP runtime for pinned memory, copies and events.
 #include <hip/hip_runtime_api.h>
 
@@ -52,12 +61,17 @@ u64 align_up(u64 v, u64 a) { return (v + a - 1) / a * a; }
 // frame sizes), bulk reads straight into the caller's pinned memory for the rest
 struct Src {
   scalce_read_fn rd = nullptr;
+  scalce_skip_fn skp = nullptr;
   void *user = nullptr;
   std::vector<u8> buf;
   size_t pos = 0, end = 0;
   bool eof = false, bad = false;
   double *wait = nullptr;
-  void open(scalce_read_fn f, void *u, double *w) { rd = f; user = u; wait = w; buf.resize(1u << 20); }
+  u64 *delivered = nullptr, *skipped = nullptr;
+  void open(scalce_read_fn f, scalce_skip_fn sk, void *u, double *w, u64 *del, u64 *skd) {
+    rd = f; skp = f ? sk : nullptr; user = u; wait = w; delivered = del; skipped = skd;
+    buf.resize(SCALCE_UNPACK_LOOKAHEAD_BYTES);
+  }
   size_t avail() const { return end - pos; }
   const u8 *ptr() const { return buf.data() + pos; }
   void skip(size_t n) { pos += n; }
@@ -68,17 +82,40 @@ struct Src {
     *wait += now_s() - t0;
     if (k < 0) bad = true;
     if (k == 0) eof = true;
+    if (k > 0) *delivered += (u64)k;
     return k;
   }
-  bool need(size_t n) { return end - pos >= n ? true : fill(n); }  // false: the stream ends (or fails) before n bytes
-  bool fill(size_t n) {
+  // false: the stream ends (or fails) before n bytes.  `look`: how far a refill may read ahead of the n bytes asked for --
+  // the whole buffer for a stream that is read from end to end; less in front of bytes that are about to be passed over
+  bool need(size_t n, size_t look = ~(size_t)0) { return end - pos >= n ? true : fill(n, look); }
+  bool fill(size_t n, size_t look) {
     if (pos) { memmove(buf.data(), buf.data() + pos, end - pos); end -= pos; pos = 0; }
     if (buf.size() < n) buf.resize(n);
     while (end < n && !eof && !bad) {
-      const int64_t k = pull(buf.data() + end, buf.size() - end);
+      const int64_t k = pull(buf.data() + end, std::min(buf.size() - end, n - end + std::min(look, buf.size())));
       if (k > 0) end += (size_t)k;
     }
     return end >= n;
+  }
+  // passes over n bytes: what the look-ahead buffer holds first, then the caller's skip, or -- without one -- reads that are
+  // dropped; returns the bytes passed over (< n: the stream ends there, or has failed)
+  u64 pass(u64 n) {
+    u64 got = std::min<u64>(n, avail());
+    pos += got;
+    if (got < n && skp && !eof && !bad) {
+      const double t0 = now_s();
+      const int64_t k = skp(user, n - got);
+      *wait += now_s() - t0;
+      if (k < 0 || (u64)k > n - got) bad = true;
+      else { got += (u64)k; *skipped += (u64)k; if (got < n) eof = true; }
+      return got;
+    }
+    while (got < n && !eof && !bad) {
+      pos = end = 0;
+      const int64_t k = pull(buf.data(), std::min<u64>(buf.size(), n - got));
+      if (k > 0) got += (u64)k;
+    }
+    return got;
   }
   // n bytes into dst: what the buffer holds first, then the callback directly; returns the bytes delivered (< n: the end)
   u64 read_into(u8 *dst, u64 n) {
@@ -114,6 +151,8 @@ struct Mate {
   int64_t phred = 0;
   bool q_empty = false;
   u64 total_syms = 0, records_left = UNKNOWN, first = 0;
+  u64 range_left = UNKNOWN;  // records of the range not yet taken (UNKNOWN: the range runs to the archive's end)
+  u64 drop = 0;              // symbols of the first batch that lie in front of the range's first record
   Buckets bk;
   // the arithmetic decoder: batches of whole frames ahead of the windows
   scalce_ac_decoder *dec = nullptr;
@@ -152,6 +191,8 @@ struct Session {
   scalce_write_fn wr;
   void *wr_user;
   scalce_unpack_stats S;
+  scalce_unpack_range RG;
+  scalce_unpack_range_stats RS;
   Failure F;
   std::atomic<bool> failed{false};
   std::mutex mu;
@@ -170,9 +211,16 @@ struct Session {
   u64 live = 0;
   u64 widx = 0;
 
-  Session(scalce_ctx *c, const scalce_unpack_params *p, scalce_write_fn w, void *wu) : ctx(c), P(*p), wr(w), wr_user(wu) {
+  Session(scalce_ctx *c, const scalce_unpack_params *p, const scalce_unpack_range *rg, scalce_write_fn w, void *wu)
+      : ctx(c), P(*p), wr(w), wr_user(wu) {
     memset(&S, 0, sizeof S);
     S.error_mate = S.error_stream = -1;
+    memset(&RG, 0, sizeof RG);
+    RG.nrecords = UNKNOWN;
+    if (rg) RG = *rg;
+    memset(&RS, 0, sizeof RS);
+    RS.first_record = RG.first_record;
+    RS.total_records = UNKNOWN;
   }
 
   // ---- errors: the first one stays, nothing further is launched behind it ------------------------------------------------
@@ -211,9 +259,10 @@ struct Session {
     qual = !P.no_qualities;
     for (int m = 0; m < P.mates; m++) {
       Mate &x = M[m];
-      x.r.open(rd[m][0], user[m][0], &S.read_wait_s);
-      x.n.open(rd[m][1], user[m][1], &S.read_wait_s);
-      x.q.open(qual ? rd[m][2] : nullptr, qual ? user[m][2] : nullptr, &S.read_wait_s);
+      x.r.open(rd[m][0], RG.skip[m][0], user[m][0], &S.read_wait_s, &RS.bytes_delivered[m][0], &RS.bytes_skipped[m][0]);
+      x.n.open(rd[m][1], RG.skip[m][1], user[m][1], &S.read_wait_s, &RS.bytes_delivered[m][1], &RS.bytes_skipped[m][1]);
+      x.q.open(qual ? rd[m][2] : nullptr, RG.skip[m][2], qual ? user[m][2] : nullptr, &S.read_wait_s, &RS.bytes_delivered[m][2],
+               &RS.bytes_skipped[m][2]);
       if (!x.r.need(8) || memcmp(x.r.ptr(), "scalce2", 7)) return fail(SCALCE_ERR_FORMAT, m, 0, 1, "is not a scalce archive");
       const bool has_no_ac = x.r.ptr()[6] == '2' && x.r.ptr()[7] >= '2';
       x.r.skip(8);
@@ -257,10 +306,10 @@ struct Session {
 
   // ---- mate 1's buckets ----------------------------------------------------------------------------------------------
   // moves to the next bucket that has records; 0: there is one, 1: the stream has ended, < 0: failed
-  int next_bucket(int m) {
+  int next_bucket(int m, size_t look = ~(size_t)0) {
     Mate &x = M[m];
     while (!x.bk.left) {
-      if (!x.r.need(12)) {
+      if (!x.r.need(12, look)) {
         if (x.r.bad) { fail(SCALCE_ERR_FORMAT, m, 0, 0, "read error on the read stream"); return -1; }
         return 1;
       }
@@ -436,7 +485,9 @@ struct Session {
     }
     if (x.q.bad) return fail(SCALCE_ERR_FORMAT, m, 2, 0, "read error on the quality stream");
     const u64 nsym = std::min<u64>((u64)k * FRAME, x.syms_left);
-    const u64 carry = b ? x.have_b[par ^ 1] % (u64)x.L : 0;
+    // (the first batch of a range begins with x.drop symbols of the records in front of it: they are left where they are
+    // decoded and the windows begin behind them, so the carry counts from there)
+    const u64 carry = b ? (x.have_b[par ^ 1] - (b == 1 ? x.drop : 0)) % (u64)x.L : 0;
     if (x.rec_once[par]) SD_HIP(hipStreamWaitEvent(s_dec, x.ev_rec[par], 0));
     SD_HIP(hipMemcpyAsync(x.d_coded[par], x.h_coded, at, hipMemcpyHostToDevice, s_dec));
     SD_HIP(hipEventRecord(x.ev_coded_up, s_dec));
@@ -452,26 +503,28 @@ struct Session {
     x.syms_left -= nsym;
     x.enq = b;
     S.decode_batches[m]++;
+    RS.frames_decoded[m] += k;
+    RS.symbols_decoded[m] += nsym;
     return SCALCE_OK;
   }
   // whole records of mate m that the decoded symbols still hold; moves on to the next batch when that is none
   int records_decoded(int m, u64 &n) {
     Mate &x = M[m];
     const u64 L = (u64)x.L;
-    if (x.cur >= 0 && (x.have_b[x.cur & 1] - x.pos) / L) { n = (x.have_b[x.cur & 1] - x.pos) / L; return SCALCE_OK; }
-    if (x.cur == x.enq && !x.frames_left) { n = 0; return SCALCE_OK; }
-    if (x.enq == x.cur) SD_TRY(enqueue_batch(m));
-    x.cur++;
-    x.pos = 0;
-    SD_TRY(enqueue_batch(m));  // the batch behind it: decoded while this one's windows go through
-    const int par = (int)(x.cur & 1);
-    SD_HIP(hipEventSynchronize(x.ev_dec[par]));
-    float ms = 0;
-    SD_HIP(hipEventElapsedTime(&ms, x.t_dec0[par], x.t_dec1[par]));
-    S.decode_s += 1e-3 * ms;
-    if (x.h_bad[par]) return fail(SCALCE_ERR_FORMAT, m, 2, 0, "(ERROR) truncated quality stream");
-    n = x.have_b[par] / L;
-    return SCALCE_OK;
+    for (;;) {  // (a range's first batch may hold less than one record behind the symbols it drops: then the next one)
+      if (x.cur >= 0 && (x.have_b[x.cur & 1] - x.pos) / L) { n = (x.have_b[x.cur & 1] - x.pos) / L; return SCALCE_OK; }
+      if (x.cur == x.enq && !x.frames_left) { n = 0; return SCALCE_OK; }
+      if (x.enq == x.cur) SD_TRY(enqueue_batch(m));
+      x.cur++;
+      x.pos = x.cur ? 0 : x.drop;
+      SD_TRY(enqueue_batch(m));  // the batch behind it: decoded while this one's windows go through
+      const int par = (int)(x.cur & 1);
+      SD_HIP(hipEventSynchronize(x.ev_dec[par]));
+      float ms = 0;
+      SD_HIP(hipEventElapsedTime(&ms, x.t_dec0[par], x.t_dec1[par]));
+      S.decode_s += 1e-3 * ms;
+      if (x.h_bad[par]) return fail(SCALCE_ERR_FORMAT, m, 2, 0, "(ERROR) truncated quality stream");
+    }
   }
 
   // ---- the writer: one thread, windows in order ----------------------------------------------------------------------------
@@ -594,7 +647,93 @@ struct Session {
     return SCALCE_OK;
   }
 
-  // mates m0 .. m1 (one mate, or both under -i) from their first window to their last
+  // ---- the range: what lies in front of its first record is passed over, stream by stream -------------------------------
+  // Nothing of it reaches the device.  Where no symbol count says how many records the archive holds, the streams that end it
+  // for a whole run -- the names, else the raw quality rows, else the read stream -- end it here too: a range that begins
+  // behind them is empty.  Any other stream that ends in front of the range is truncated, as it is for a whole run.
+  int pass_over(int m0, int m1) {
+    const bool known = M[m0].records_left != UNKNOWN;
+    u64 first = RG.first_record;
+    if (known) { RS.total_records = M[m0].records_left; first = std::min(first, M[m0].records_left); }
+    constexpr size_t LOOK = 64u << 10;  // read ahead of a bucket header when the bucket behind it is skipped, not read
+    if (names)  // a length byte per name has to be read: the names go through the look-ahead buffer, not through skip
+      for (int m = m0; m <= m1; m++) {
+        Src &src = M[m].n;
+        u64 k = 0;
+        for (; k < first && src.need(1); k++) {
+          const size_t len = src.ptr()[0];
+          if (!src.need(1 + len)) return fail(SCALCE_ERR_FORMAT, m, 1, 0, src.bad ? "read error on the name stream" : "(ERROR) truncated name stream");
+          src.skip(1 + len);
+        }
+        if (src.bad) return fail(SCALCE_ERR_FORMAT, m, 1, 0, "read error on the name stream");
+        if (k < first) {
+          if (known || m != m0) return fail(SCALCE_ERR_FORMAT, m, 1, 0, "(ERROR) truncated name stream");
+          first = k;
+        }
+      }
+    for (int m = m0; m <= m1; m++) {  // -A: rows of L bytes
+      Mate &x = M[m];
+      if (!qual || !x.no_ac) continue;
+      const u64 want = first * (u64)x.L, bytes = x.q.pass(want);
+      if (x.q.bad) return fail(SCALCE_ERR_FORMAT, m, 2, 0, "read error on the quality stream");
+      if (bytes != want) {
+        if (known || names || m != m0 || bytes % (u64)x.L) return fail(SCALCE_ERR_FORMAT, m, 2, 0, "(ERROR) truncated quality stream");
+        first = bytes / (u64)x.L;
+      }
+    }
+    for (int m = m0; m <= m1; m++) {
+      Mate &x = M[m];
+      u64 got = 0;
+      if (m != 0) {
+        const u64 rb = (u64)(x.L + 3) / 4, bytes = x.r.pass(first * rb);
+        if (bytes % rb && !x.r.bad) return fail(SCALCE_ERR_FORMAT, m, 0, 0, "(ERROR) truncated read stream");
+        got = bytes / rb;
+      } else {
+        while (got < first) {  // bucket by bucket: every header is read and checked, the records behind it are not
+          if (!x.bk.left) {
+            const int e = next_bucket(m, x.r.skp ? LOOK : ~(size_t)0);
+            if (e < 0) return F.rc;
+            if (e) break;
+          }
+          const u64 t = std::min(x.bk.left, first - got), bytes = t * x.bk.rec_bytes;
+          if (x.r.pass(bytes) != bytes) return fail(SCALCE_ERR_FORMAT, m, 0, 0, x.r.bad ? "read error on the read stream" : "(ERROR) truncated read stream");
+          got += t; x.bk.left -= t;
+        }
+      }
+      if (x.r.bad) return fail(SCALCE_ERR_FORMAT, m, 0, 0, "read error on the read stream");
+      if (got != first) {
+        if (known || names || m != m0 || (qual && x.no_ac)) return fail(SCALCE_ERR_FORMAT, m, 0, 0, "(ERROR) truncated read stream");
+        first = got;
+      }
+    }
+    for (int m = m0; m <= m1; m++) {  // coded qualities: whole frames by their size words, then the symbols in front of the record
+      Mate &x = M[m];
+      if (!x.dec) continue;
+      u64 pl[4];
+      if (scalce_range_plan_quality(x.L, first, RG.nrecords, x.total_syms, pl)) return fail(SCALCE_ERR_ARG, m, 2, 0, "internal: the range's plan");
+      for (u64 f = 0; f < pl[0]; f++) {
+        if (!x.q.need(4, x.q.skp ? 0 : ~(size_t)0)) return fail(SCALCE_ERR_FORMAT, m, 2, 0, x.q.bad ? "read error on the quality stream" : "(ERROR) truncated quality stream");
+        u32 sz;
+        memcpy(&sz, x.q.ptr(), 4);
+        x.q.skip(4);
+        if (x.q.pass(sz) != sz) return fail(SCALCE_ERR_FORMAT, m, 2, 0, x.q.bad ? "read error on the quality stream" : "(ERROR) truncated quality stream");
+      }
+      RS.frames_passed[m] = pl[0];
+      x.frames_left = pl[1];
+      x.drop = pl[2];
+      x.syms_left = pl[2] + pl[3];
+    }
+    for (int m = m0; m <= m1; m++) {
+      Mate &x = M[m];
+      x.first = first;
+      x.range_left = RG.nrecords;
+      if (known) x.records_left -= first;
+    }
+    RS.first_record = first;
+    return SCALCE_OK;
+  }
+
+  // mates m0 .. m1 (one mate, or both under -i) from the range's first window to its last
   int run_pass(int m0, int m1) {
     const int nmates = m1 - m0 + 1;
     for (int m = m0; m <= m1; m++) SD_TRY(setup_decoder(m));
@@ -602,9 +741,10 @@ struct Session {
       return fail(SCALCE_ERR_FORMAT, -1, -1, 0, "(ERROR) the mates hold %llu and %llu records", (unsigned long long)M[m0].records_left,
                   (unsigned long long)M[m1].records_left);
     const bool known = M[m0].records_left != UNKNOWN;
+    SD_TRY(pass_over(m0, m1));
     for (;;) {
       if (failed) return F.rc;
-      u64 ncap = std::min(R, M[m0].records_left);
+      u64 ncap = std::min(R, std::min(M[m0].records_left, M[m0].range_left));
       for (int m = m0; m <= m1 && ncap; m++)
         if (M[m].dec) { u64 k; SD_TRY(records_decoded(m, k)); ncap = std::min(ncap, k); }
       if (!ncap) break;
@@ -706,11 +846,15 @@ struct Session {
       for (int m = m0; m <= m1; m++) {
         M[m].first += n;
         if (M[m].records_left != UNKNOWN) M[m].records_left -= n;
+        if (M[m].range_left != UNKNOWN) M[m].range_left -= n;
         S.records[m] += n;
       }
     }
-    // what is left of the read streams holds no record
-    for (int m = m0; m <= m1; m++) {
+    RS.nrecords = S.records[m0];
+    // what is left of the read streams holds no record -- where the range ends with the archive: behind a range that ends
+    // sooner nothing is read, and a stream that is cut short there is not noticed
+    const bool to_end = M[m0].range_left != 0 || M[m0].records_left == 0;
+    for (int m = m0; m <= m1 && to_end; m++) {
       Mate &x = M[m];
       bool more = false;
       if (m == 0) { const int e = x.bk.left ? 0 : next_bucket(m); if (e < 0) return F.rc; more = e == 0; }
@@ -772,13 +916,38 @@ struct Session {
 
 }  // namespace
 
+// The arithmetic of a range over the coded quality stream, without a device call: symbols [first * L, (first + n) * L) of a
+// stream of total_syms symbols in frames of SCALCE_AC_BLOCK.  first and n are clamped to the total_syms / L records the stream
+// holds; a range that reaches the last record takes the symbols behind it (fewer than one record) along, as a whole run does.
+extern "C" int scalce_range_plan_quality(int read_len, uint64_t first, uint64_t n, uint64_t total_syms, uint64_t out[4]) {
+  if (read_len <= 0 || !out) return SCALCE_ERR_ARG;
+  const u64 L = (u64)read_len, records = total_syms / L;
+  first = std::min(first, records);
+  n = std::min(n, records - first);
+  const u64 s0 = first * L, s1 = first + n == records ? total_syms : (first + n) * L;
+  out[0] = s0 / FRAME;
+  out[1] = out[2] = out[3] = 0;
+  if (!n) return SCALCE_OK;
+  out[1] = (s1 + FRAME - 1) / FRAME - out[0];
+  out[2] = s0 - out[0] * FRAME;
+  out[3] = s1 - s0;
+  return SCALCE_OK;
+}
+
 extern "C" int scalce_stream_decompress(scalce_ctx *ctx, const scalce_unpack_params *p, scalce_read_fn rd[2][3], void *user[2][3],
                                         scalce_write_fn wr, void *wr_user, scalce_unpack_stats *stats, char *errbuf, size_t errcap) {
+  return scalce_stream_decompress_range(ctx, p, nullptr, rd, user, wr, wr_user, stats, nullptr, errbuf, errcap);
+}
+
+extern "C" int scalce_stream_decompress_range(scalce_ctx *ctx, const scalce_unpack_params *p, const scalce_unpack_range *range,
+                                              scalce_read_fn rd[2][3], void *user[2][3], scalce_write_fn wr, void *wr_user,
+                                              scalce_unpack_stats *stats, scalce_unpack_range_stats *range_stats, char *errbuf,
+                                              size_t errcap) {
   if (!ctx || !p || !rd || !user || !wr || p->mates < 1 || p->mates > 2 || (p->interleave && p->mates != 2)) return SCALCE_ERR_ARG;
   for (int m = 0; m < p->mates; m++)
     if (!rd[m][0] || !rd[m][1] || (!p->no_qualities && !rd[m][2])) return SCALCE_ERR_ARG;
   if (p->ignore_names && !p->library) return SCALCE_ERR_ARG;
-  Session *s = new Session(ctx, p, wr, wr_user);
+  Session *s = new Session(ctx, p, range, wr, wr_user);
   int rc = s->run(rd, user);
   s->close();
   if (!rc && s->failed) rc = s->F.rc;
@@ -787,6 +956,7 @@ extern "C" int scalce_stream_decompress(scalce_ctx *ctx, const scalce_unpack_par
     s->S.error_mate = s->F.mate; s->S.error_stream = s->F.stream; s->S.error_wants_file = s->F.wants_file;
   }
   if (stats) *stats = s->S;
+  if (range_stats) *range_stats = s->RS;
   delete s;
   return rc;
 }

@@ -540,15 +540,42 @@ class UnpackStats(C.Structure):
 
 
 WRITE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64))
+SKIP_FN = C.CFUNCTYPE(C.c_int64, C.c_void_p, C.c_uint64)
+UNPACK_LOOKAHEAD_BYTES = 1 << 20  # SCALCE_UNPACK_LOOKAHEAD_BYTES: what a stream may be read ahead of what the session has used
+
+
+class UnpackRange(C.Structure):
+    _fields_ = [("first_record", C.c_uint64), ("nrecords", C.c_uint64), ("skip", (SKIP_FN * 3) * 2)]
+
+
+class UnpackRangeStats(C.Structure):
+    _fields_ = [("first_record", C.c_uint64), ("nrecords", C.c_uint64), ("total_records", C.c_uint64),
+                ("frames_decoded", C.c_uint64 * 2), ("frames_passed", C.c_uint64 * 2), ("symbols_decoded", C.c_uint64 * 2),
+                ("bytes_delivered", (C.c_uint64 * 3) * 2), ("bytes_skipped", (C.c_uint64 * 3) * 2)]
+
+
+def range_plan_quality(read_len, first, n, total_syms):
+    """scalce_range_plan_quality: (first frame, frames, symbols dropped in front, symbols behind them) of records
+    [first, first + n) -- n None: to the end -- over a coded quality stream of total_syms symbols."""
+    L = lib()
+    L.scalce_range_plan_quality.argtypes = [C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.scalce_range_plan_quality.restype = C.c_int
+    out = (C.c_uint64 * 4)()
+    rc = L.scalce_range_plan_quality(int(read_len), int(first), (1 << 64) - 1 if n is None else int(n), int(total_syms), out)
+    if rc:
+        raise ScalceError(f"[{rc}] scalce_range_plan_quality")
+    return tuple(int(v) for v in out)
 
 
 def stream_decompress(ctx, readers, write, mates=1, interleave=False, no_qualities=False, mate_digit=None, library=None,
-                      split=0, window_text_bytes=0):
-    """scalce_stream_decompress: an archive back to text in windows of whole records.  readers[m] = the three callables
-    (cap) -> bytes of mate m's .scalcer, .scalcen and .scalceq streams (b"" at the end; raise for a read error);
-    write(mate, first_record, nrecords, text_bytes, record_offsets or None) receives every window in order, from the
-    library's writer thread (raise to end the session).  library: print names as <library>.<index> whatever the archive
-    holds (-n).  Returns UnpackStats."""
+                      split=0, window_text_bytes=0, first_record=0, nrecords=None, skippers=None):
+    """scalce_stream_decompress_range: an archive, or a range of its records, back to text in windows of whole records.
+    readers[m] = the three callables (cap) -> bytes of mate m's .scalcer, .scalcen and .scalceq streams (b"" at the end; raise
+    for a read error); write(mate, first_record, nrecords, text_bytes, record_offsets or None) receives every window in
+    order, from the library's writer thread (raise to end the session).  library: print names as <library>.<index> whatever
+    the archive holds (-n).  first_record / nrecords (None: to the end): the range, in archive order; skippers[m] = three
+    callables (nbytes) -> bytes passed over, or None where the stream can only be read.  Returns UnpackStats; its attribute
+    `range` holds the UnpackRangeStats of the run."""
     keep = []
 
     def wrap(fn):
@@ -570,24 +597,40 @@ def stream_decompress(ctx, readers, write, mates=1, interleave=False, no_qualiti
         except Exception:  # noqa: BLE001 - reported to the library as a failed write
             return 1
         return 0
+    def wrap_skip(fn):
+        def cb(_user, nbytes):
+            try:
+                return int(fn(int(nbytes)))
+            except Exception:  # noqa: BLE001 - reported to the library as a read error
+                return -1
+        keep.append(SKIP_FN(cb))
+        return keep[-1]
+
     wfn = WRITE_FN(wcb)
     rd = ((READ_FN * 3) * 2)()
     user = ((C.c_void_p * 3) * 2)()
+    rg = UnpackRange(int(first_record), (1 << 64) - 1 if nrecords is None else int(nrecords))
     for m in range(mates):
         for k in range(3):
             if readers[m][k] is not None:
                 rd[m][k] = wrap(readers[m][k])
+            if skippers is not None and skippers[m] is not None and skippers[m][k] is not None:
+                rg.skip[m][k] = wrap_skip(skippers[m][k])
     p = UnpackParams(mates, int(interleave), int(no_qualities), int(mates == 2 if mate_digit is None else mate_digit),
                      int(library is not None), int(split), library.encode() if library is not None else None, int(window_text_bytes))
     st = UnpackStats()
+    rst = UnpackRangeStats()
     msg = C.create_string_buffer(1024)
     L = ctx.L
-    L.scalce_stream_decompress.argtypes = [C.c_void_p, C.POINTER(UnpackParams), C.c_void_p, C.c_void_p, WRITE_FN, C.c_void_p,
-                                           C.POINTER(UnpackStats), C.c_char_p, C.c_size_t]
-    L.scalce_stream_decompress.restype = C.c_int
-    rc = L.scalce_stream_decompress(ctx.h, C.byref(p), C.cast(rd, C.c_void_p), C.cast(user, C.c_void_p), wfn, None, C.byref(st), msg, len(msg))
+    L.scalce_stream_decompress_range.argtypes = [C.c_void_p, C.POINTER(UnpackParams), C.POINTER(UnpackRange), C.c_void_p, C.c_void_p,
+                                                 WRITE_FN, C.c_void_p, C.POINTER(UnpackStats), C.POINTER(UnpackRangeStats), C.c_char_p,
+                                                 C.c_size_t]
+    L.scalce_stream_decompress_range.restype = C.c_int
+    rc = L.scalce_stream_decompress_range(ctx.h, C.byref(p), C.byref(rg), C.cast(rd, C.c_void_p), C.cast(user, C.c_void_p), wfn, None,
+                                          C.byref(st), C.byref(rst), msg, len(msg))
     if rc:
         raise ScalceError(f"[{rc}] " + msg.value.decode(errors="replace"))
+    st.range = rst
     return st
 
 
