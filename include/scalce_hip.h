@@ -103,6 +103,16 @@ typedef struct {
    * Everything behind the ingest is -r's on the same pairs: the archive is byte for byte the one of the two split texts.
    * One GPU only: scalce_sharded_compress refuses such batches (SCALCE_ERR_ARG). */
   int32_t interleaved;
+  /* Reads of different lengths (--variable-length; zero = as before: a record whose length differs from read_len is an
+   * error).  Set: read_len[m] is the LONGEST read of mate m, a record may hold 0 .. read_len[m] bases, and its sequence and
+   * quality lines must be equally long.  The run is the fixed-length run of the same records padded to read_len -- 'N' behind a
+   * read's end, whose quality symbol is 0 -- made by a pad pass in front of the ingest: SCALCE_OUT_READS, _NAMES, _QUAL, _TABLE
+   * and _PERM are those of the padded text, byte for byte, and SCALCE_OUT_LENGTHS says how long each record really was.  A record
+   * longer than read_len, or one whose two lines differ, is SCALCE_ERR_FORMAT from scalce_batch_ingest / _append themselves.
+   * scalce_batch_append's consumed[] stays in bytes of the caller's pieces.  Not together with fasta, no_qualities or
+   * interleaved (scalce_batch_create: SCALCE_ERR_ARG); one GPU only: scalce_sharded_compress, scalce_batch_rewindow,
+   * scalce_batch_text_offset and scalce_pipeline_create refuse such batches (SCALCE_ERR_ARG). */
+  int32_t variable_length;
 } scalce_params;
 
 void scalce_params_default(scalce_params *p);
@@ -317,7 +327,9 @@ enum {
   SCALCE_OUT_BUCKET_COUNTS = 8, /* (buckets+1) x u64 reads per bucket, emission order, root last */
   SCALCE_OUT_QINPUT = 9,    /* N*L bytes: q' in input order, mate m                          */
   SCALCE_OUT_NAMELEN = 10,  /* N bytes: stored name length per read, input order             */
-  SCALCE_OUT_BUCKET_NAME_BYTES = 11 /* (buckets+1) x u64: bytes of each bucket's records in SCALCE_OUT_NAMES (after emit) */
+  SCALCE_OUT_BUCKET_NAME_BYTES = 11, /* (buckets+1) x u64: bytes of each bucket's records in SCALCE_OUT_NAMES (after emit) */
+  SCALCE_OUT_LENGTHS = 12   /* variable-length runs: N x u16, read_len - length of the k-th emitted record of mate m (mate 2 in
+                               mate 1's order, like its reads); valid behind scalce_batch_order; empty for other runs */
 };
 int scalce_batch_output(const scalce_batch *b, int which, int mate, const void **d_ptr, uint64_t *nbytes);
 /* Framing on the way out (replaces the copy loop of ac_write, arithmetic.cpp:318-363: the reference frames each coded
@@ -446,6 +458,25 @@ typedef struct {
 } scalce_fq_window;
 int scalce_fastq_records_window(scalce_ctx *ctx, const scalce_fq_window *w, void *stream);
 
+/* Variable-length archives: the pad behind each read's end is cut out of a window's text.  d_text / d_record_offsets are what
+ * scalce_fastq_records_window wrote (one mate's four-line records, not interleaved; nrecords + 1 offsets), d_entries the
+ * window's entries of the length stream as the .scalcel file holds them: entry_width (1 or 2) bytes each, little-endian,
+ * read_len - length.  The record's last `entry` bases and qualities go; d_out receives the text, d_out_offsets (nrecords + 1)
+ * where each record begins in it and, last, its size.  d_text and d_out 16-byte aligned; d_scan_ws: device scratch of
+ * scalce_fastq_strip_ws_bytes(nrecords) bytes.  Enqueued on `stream`; allocates nothing, waits for nothing. */
+uint64_t scalce_fastq_strip_ws_bytes(uint64_t nrecords);
+int scalce_fastq_strip_window(scalce_ctx *ctx, int read_len, uint64_t nrecords, const uint8_t *d_text, const uint64_t *d_record_offsets,
+                              const uint8_t *d_entries, int entry_width, uint8_t *d_out, uint64_t *d_out_offsets, void *d_scan_ws,
+                              void *stream);
+
+/* The read length of a variable-length run and its quality histogram, from the text read ahead for the quality sample -- no
+ * device call.  The first `sample` records r with r % stride == first are taken (sample_stats' walk; stride 1, first 0 for
+ * a text of one mate): *read_len = the longest sequence line among them, or max_length when that is > 0 (--max-length);
+ * stat (may be NULL; the caller clears it) counts the characters of their quality lines -- real ones only, there is no pad
+ * yet.  Returns the records sampled. */
+int64_t scalce_varlen_sample(const uint8_t *text, uint64_t nbytes, int64_t sample, int stride, int first, int max_length,
+                             int32_t stat[128], int32_t *read_len);
+
 /* ---- archives of any size back to text: windows of whole records through the device (stream_decode.cpp) ---------------
  * The counterpart of scalce_stream_compress.  rd[m][0..2] deliver the bytes of mate m's .scalcer, .scalcen and .scalceq
  * files, out of their containers, headers included (scalce_read_fn's contract: any number of bytes up to cap, 0 at the
@@ -457,6 +488,7 @@ int scalce_fastq_records_window(scalce_ctx *ctx, const scalce_fq_window *w, void
  *      record_offsets (nrecords + 1 entries, window-relative) only when `split` is set, else NULL; != 0 ends the session.
  * Two mates that are not interleaved go one after the other through the same buffers (mate = 0, then 1); interleaved,
  * both mates of a window form one text (mate = 0, records = pairs).  Nothing further is launched after an error. */
+typedef int64_t (*scalce_skip_fn)(void *user, uint64_t nbytes);  /* (scalce_unpack_range below says what it does) */
 typedef struct {
   int32_t mates;             /* 1, or 2 (-r, -i) */
   int32_t interleave;        /* both mates into ONE text, mate 1 then mate 2 of each pair */
@@ -466,6 +498,16 @@ typedef struct {
   int32_t split;             /* != 0: hand record_offsets to wr */
   const char *library;       /* with ignore_names: the library name to print */
   uint64_t window_text_bytes; /* 0: SCALCE_WINDOW_TEXT_DEFAULT */
+  /* The length stream of a variable-length archive (PREFIX_<m>.scalcel out of its container, header included), a fourth
+   * stream per mate; all NULL: an archive of reads of one length, as before.  Layout: the 8 magic bytes, int32 entry width
+   * (1 if L <= 255, else 2), int32 L -- it must be the read stream's --, then one little-endian entry per record in archive
+   * order: L - length.  Each window's records lose their pad on the device (scalce_fastq_strip_window) before they come down;
+   * windows are still sized by their padded text.  A stream that ends before the records do: "(ERROR) truncated length
+   * stream".  A range passes over first_record entries (len_skip, or reads that are dropped).  Not with interleave or
+   * no_qualities (SCALCE_ERR_ARG). */
+  scalce_read_fn len_rd[2];
+  void *len_user[2];
+  scalce_skip_fn len_skip[2];
 } scalce_unpack_params;
 #define SCALCE_WINDOW_TEXT_DEFAULT (1ull << 30)
 typedef int (*scalce_write_fn)(void *user, int mate, uint64_t first_record, uint64_t nrecords, const void *text,
@@ -479,7 +521,7 @@ typedef struct {
   double total_s, setup_s, read_wait_s, decode_s, records_s, write_wait_s, write_s;
                                /* read_wait: in rd; decode / records: device time of the kernels; write_wait: the session
                                   waiting for a window buffer that wr still holds; write: inside wr */
-  int32_t error_mate, error_stream;  /* on failure: which stream of which mate (0 r, 1 n, 2 q), or -1 */
+  int32_t error_mate, error_stream;  /* on failure: which stream of which mate (0 r, 1 n, 2 q, 3 l), or -1 */
   int32_t error_wants_file;    /* the message in errbuf is a predicate: put the stream's file name in front of it */
   uint64_t decode_batches[2];  /* per mate: decoder batches enqueued (runs of whole frames, one scalce_ac_decoder_launch each) */
 } scalce_unpack_stats;
@@ -504,7 +546,6 @@ int scalce_stream_decompress(scalce_ctx *ctx, const scalce_unpack_params *p, sca
  *                NULL: the library reads through rd and drops the bytes (a gzip container).  The look-ahead buffer of a
  *                stream (SCALCE_UNPACK_LOOKAHEAD_BYTES) is used up before skip is called; the name stream is always read. */
 #define SCALCE_UNPACK_LOOKAHEAD_BYTES (1u << 20)
-typedef int64_t (*scalce_skip_fn)(void *user, uint64_t nbytes);
 typedef struct {
   uint64_t first_record;        /* zero-based, in archive order = the order -d writes; pairs for two mates */
   uint64_t nrecords;            /* ~0ull: to the end */

@@ -35,6 +35,7 @@
 
 #include "../../include/scalce_hip.h"
 #include "pargz.hpp"
+#include "lenstream.hpp"
 
 
 #ifndef SCALCE_VERSION
@@ -72,6 +73,8 @@ struct Options {
   uint64_t window = 0;                    // --window: bytes of FASTQ text per decompression window (0: the library's default)
   bool has_range = false;                 // --records FIRST[:COUNT]: decompress this range of records (pairs) only
   uint64_t range_first = 0, range_count = ~0ull;
+  bool varlen = false;                    // --variable-length: reads of 0 .. L bases, padded to L on the device, lengths in PREFIX_<m>.scalcel
+  int max_length = 0;                     // --max-length NUM: L given, not taken from the sample (implies --variable-length)
   int gpus = 1;                           // --gpus N: one process per GPU, ONE archive (plain-text input, -c no)
   int container = 1;                      // 0 plain, 1 gzip (main.cpp:181-184 at -T 1)
   uint64_t first_file_bytes[2] = {0, 0};  // --gpus over several files written out as one: where the first file ends (the
@@ -94,6 +97,10 @@ static const char *HELP_TEXT =
     "  -f, --fasta                 input is FASTA (a name line and one sequence line per record): no qualities are stored\n"
     "  -Q, --no-qualities          drop the qualities of FASTQ input; decompression: write two-line records (@name, bases)\n"
     "                              of an archive made with -Q or -f (bases stored as N come back as A).  One GPU only\n"
+    "      --variable-length       reads of different lengths (trimmed FASTQ): every read is padded with N to the longest read\n"
+    "                              of the quality sample and its length kept in OUTPUT_<m>.scalcel; the other files are those\n"
+    "                              of the padded reads.  Decompression finds the .scalcel by itself.  Not with -i, -f, -Q, --gpus\n"
+    "      --max-length NUM        the longest read, when the sample may not hold it (implies --variable-length)\n"
     "  -p, --lossy-percentage INT  lossy quality transform, 0..100 (default 0)\n"
     "  -s, --sample-size INT       records sampled for the quality model (default 100000)\n"
     "  -B, --bucket-set-size NUM[M|G]  bucket storage that triggers a spill chunk (default 4G); order follows the reference\n"
@@ -193,6 +200,7 @@ static std::string mate_file(const std::string &f, int m) {  // input f's file o
 //   PREFIX_<m>.scalcer  magic, int32 no_ac (-A), int32 read length; the read stream (mate 1: buckets, each opened by
 //                       [int32 core][int64 records]; mate 2: bare records in mate 1's order)
 //   PREFIX_<m>.scalcen  magic, u8 names; the name stream, or without names (-n) int64 0 and the library name
+//   PREFIX_<m>.scalcel  --variable-length only (lenstream.hpp): magic, int32 entry width, int32 L, one entry L - length per record
 //   PREFIX_<m>.scalceq  magic, int64 Phred offset (mate 1's for both mates, compress.cpp:294,816-817); arithmetic coded:
 //                       the scaled table (QTABLE_WORDS x u32), the int64 symbol count and the coded blocks; -A: the q' rows
 static const uint8_t MAGIC[8] = {'s', 'c', 'a', 'l', 'c', 'e', '2', '2'};
@@ -504,6 +512,7 @@ static scalce_params params_from(const Options &o) {
   scalce_params_default(&p);
   p.paired = o.pairs(); p.use_names = o.use_names; p.no_ac = o.no_ac; p.bucket_set_size = o.bucket_set_size;
   p.fasta = o.fasta; p.no_qualities = o.no_qual; p.interleaved = o.interleave;
+  p.variable_length = o.varlen;
   return p;
 }
 // Mate m's quality map and read length from the first records of the first input file (get_quality_stats,
@@ -523,6 +532,10 @@ static void quality_model(const Options &o, MateSource &src, int m, scalce_param
       if (!(nl = (const uint8_t *)memchr(t, '\n', (size_t)(e - t)))) break;
     const uint8_t *nl2 = nl && nl + 1 < e ? (const uint8_t *)memchr(nl + 1, '\n', (size_t)(e - (nl + 1))) : nullptr;
     if (nl2) rl = (int)(nl2 - nl - 1);
+  } else if (o.varlen) {  // the longest sampled read (or --max-length); the histogram counts the characters that are there
+    int32_t longest = 0;
+    scalce_varlen_sample(src.peek.data(), n, o.sample, stride, first, o.max_length, qhist, &longest);
+    rl = longest;
   } else {
     sample_stats(src.peek.data(), n, o.sample, qhist, rl, stride, first);
   }
@@ -634,6 +647,19 @@ static int do_compress(const Options &o, const std::vector<std::string> &files, 
     fN.write(names_header(o));
     if (o.use_names) downs[m]->to_file(ctx, b, SCALCE_OUT_NAMES, 0, fN);  // mate 2 repeats mate 1's names (:450-454)
     fN.close();
+    if (o.varlen) {  // how long each record really was, in archive order
+      OutFile fL;
+      fL.open(archive_path(o.out, m, 'l'), gz_container(o, 'l'));
+      uint8_t head[scalce_host::LEN_HEADER_BYTES];
+      scalce_host::len_header_write(head, p.read_len[m]);
+      fL.write(head, sizeof head);
+      const std::vector<uint8_t> pad = fetch(ctx, b, SCALCE_OUT_LENGTHS, m);
+      const int width = scalce_host::len_entry_width(p.read_len[m]);
+      std::vector<uint8_t> entries(pad.size() / 2 * (size_t)width);
+      scalce_host::len_entries_write(reinterpret_cast<const uint16_t *>(pad.data()), pad.size() / 2, width, entries.data());
+      fL.write(entries);
+      fL.close();
+    }
   });
   const double t2b = now();
   SCOK(ctx, scalce_batch_finish(b, s_ent));  // the coder is through: sizes of the coded streams, device error word
@@ -656,7 +682,7 @@ static int do_compress(const Options &o, const std::vector<std::string> &files, 
   const double t2d = now();
   uint64_t new_size = 0;
   for (int m = 0; m < nm; m++)
-    for (char ext : {'r', 'q', 'n'}) {
+    for (char ext : {'r', 'q', 'n', 'l'}) {
       struct stat st;
       if (stat(archive_path(o.out, m, ext).c_str(), &st) == 0) new_size += (uint64_t)st.st_size;
     }
@@ -1185,7 +1211,17 @@ static int do_decompress(const Options &o, const std::string &path, scalce_ctx *
   const int nm = o.pairs() ? 2 : 1;
   std::string base[2] = {path, path};
   if (o.pairs() && !second_file(path, base[1])) FAIL("Cannot get file name for paired end for file %s.\n", path.c_str());
-  ArchiveFile files[2][3];
+  // a variable-length archive has a length stream next to the other three: without the file, the reads come back padded
+  bool has_lens[2] = {false, false};
+  for (int m = 0; m < nm; m++) {
+    const std::string lpath = scalce_name(base[m], 'l');
+    struct stat lst;
+    if (stat(lpath.c_str(), &lst) != 0) continue;
+    if (o.interleave) FAIL("%s: an archive of variable-length reads is decompressed mate by mate (-r), not interleaved (-i)\n", lpath.c_str());
+    if (o.fasta || o.no_qual) FAIL("%s: an archive of variable-length reads is decompressed with its qualities, not with -Q / -f\n", lpath.c_str());
+    has_lens[m] = true;
+  }
+  ArchiveFile files[2][3], lens[2];
   scalce_read_fn rd[2][3];
   void *user[2][3];
   static const char ext[3] = {'r', 'n', 'q'};
@@ -1197,6 +1233,13 @@ static int do_decompress(const Options &o, const std::string &path, scalce_ctx *
     }
   scalce_unpack_params p;
   memset(&p, 0, sizeof p);
+  for (int m = 0; m < nm; m++) {
+    if (!has_lens[m]) continue;
+    lens[m].open(scalce_name(base[m], 'l'));
+    p.len_rd[m] = ArchiveFile::read;
+    p.len_user[m] = &lens[m];
+    p.len_skip[m] = lens[m].gz ? nullptr : ArchiveFile::skip;
+  }
   p.mates = nm;
   p.interleave = o.interleave;
   p.no_qualities = o.fasta || o.no_qual;  // -d -Q / -d -f: two-line records, whatever the .scalceq holds (decompress.cpp:159-168)
@@ -1250,7 +1293,8 @@ int main(int argc, char **argv) {
                                      {"split-reads", 1, 0, 'S'}, {"fasta", 0, 0, 'f'}, {"threads", 1, 0, 'T'},
                                      {"version", 0, 0, 'v'}, {"no-arithmetic", 0, 0, 'A'}, {"patterns-bin", 1, 0, 1000},
                                      {"gpus", 1, 0, 1001}, {"interleave", 0, 0, 'i'}, {"window", 1, 0, 1002},
-                                     {"records", 1, 0, 1003}, {0, 0, 0, 0}};
+                                     {"records", 1, 0, 1003}, {"variable-length", 0, 0, 1004},
+                                     {"max-length", 1, 0, 1005}, {0, 0, 0, 0}};
   int opt;
   while ((opt = getopt_long(argc, argv, "vhp:T:dc:o:fs:t:B:rQAn:P:S:i", long_opt, 0)) != -1) {
     switch (opt) {
@@ -1306,6 +1350,12 @@ int main(int argc, char **argv) {
           FAIL("--records takes FIRST or FIRST:COUNT, two non-negative numbers of records.\n");
         o.has_range = true;
       } break;
+      case 1004: o.varlen = true; break;
+      case 1005:
+        o.max_length = atoi(optarg);
+        if (o.max_length < 1 || o.max_length > 2498) FAIL("--max-length takes the longest read's number of bases, 1 to 2498.\n");
+        o.varlen = true;
+        break;
       default: fputs(HELP_TEXT, stdout); return 0;
     }
   }
@@ -1327,6 +1377,12 @@ int main(int argc, char **argv) {
     }
   if (o.gpus > 1 && !o.decompress && (o.fasta || o.no_qual))
     FAIL("-f / -Q runs on one GPU: --gpus %d is not available without qualities\n", o.gpus);
+  if (o.varlen && !o.decompress) {  // refused before anything touches a device
+    if (o.interleave) FAIL("--variable-length is not available for interleaved input (-i): give the mates as two files (-r)\n");
+    if (o.fasta) FAIL("--variable-length is not available for FASTA input (-f)\n");
+    if (o.no_qual) FAIL("--variable-length is not available without qualities (-Q)\n");
+    if (o.gpus > 1) FAIL("--variable-length runs on one GPU: --gpus %d is not available for reads of different lengths\n", o.gpus);
+  }
   if (o.gpus > 1 && !o.decompress && o.interleave)
     FAIL("-i runs on one GPU: --gpus %d is not available for interleaved input\n", o.gpus);
   if (o.gpus > 1 && !o.decompress) {  // forks before anything touches a GPU

@@ -352,3 +352,28 @@ extern "C" int scalce_fastq_records_interleaved(scalce_ctx *c, const int read_le
   }
   return SCALCE_OK;
 }
+
+// ---- variable-length archives: the pad out of a window's text ------------------------------------------------------------
+// One scan of the stripped record sizes (it leaves the new record offsets, and the text's size behind them), one copy pass.
+extern "C" uint64_t scalce_fastq_strip_ws_bytes(uint64_t nrecords) { return sizeof(u64) * (scan_ws_elems(nrecords) + 64); }
+extern "C" int scalce_fastq_strip_window(scalce_ctx *c, int read_len, uint64_t nrecords, const uint8_t *d_text, const uint64_t *d_record_offsets,
+                                         const uint8_t *d_entries, int entry_width, uint8_t *d_out, uint64_t *d_out_offsets, void *d_scan_ws,
+                                         void *stream) {
+  if (!c || read_len <= 0 || read_len > 65535 || (entry_width != 1 && entry_width != 2) || !d_out_offsets || !d_scan_ws) return SCALCE_ERR_ARG;
+  if (nrecords && (!d_text || !d_record_offsets || !d_entries || !d_out)) return SCALCE_ERR_ARG;
+  if (((uintptr_t)d_text & 15) || ((uintptr_t)d_out & 15)) { set_err(c, "strip: the window's texts must be 16-byte aligned"); return SCALCE_ERR_ARG; }
+  hipStream_t s = (hipStream_t)stream;
+  HIP_TRY(c, hipSetDevice(c->device));
+  StripArgs a;
+  a.text = d_text; a.rec_off = reinterpret_cast<const u64 *>(d_record_offsets); a.entries = d_entries;
+  a.width = (u32)entry_width; a.L = (u32)read_len; a.nrec = nrecords;
+  a.dst_off = reinterpret_cast<u64 *>(d_out_offsets); a.dst = d_out;
+  exclusive_scan<u64>(StrippedSize{a}, nrecords, StoreTo<u64>{a.dst_off}, static_cast<u64 *>(d_scan_ws), a.dst_off + nrecords, s);
+  if (nrecords) {
+    // (the grid covers an upper bound of the text known without a read-back -- a record is '@', a name of up to 255 bytes, two
+    // lines of L and "+" with four newlines -- and the workgroups behind the text's end return at once)
+    const u64 bound = nrecords * (2ull * (u64)read_len + 6 + 256);
+    LAUNCH(strip_copy_k, cdiv(bound, VL_SPAN), 256, 0, s, a);
+  }
+  return launch_failed(c);
+}

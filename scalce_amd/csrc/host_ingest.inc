@@ -181,6 +181,50 @@ static int piece_unpack_il(scalce_batch *b, int mate, const u8 *d_text, u64 nbyt
 static int piece_unpack(scalce_batch *b, int mate, const u8 *d_text, u64 nbytes, u64 nrec, hipStream_t s) {
   return b->il ? piece_unpack_il<true>(b, mate, d_text, nbytes, nrec, s) : piece_unpack_il<false>(b, mate, d_text, nbytes, nrec, s);
 }
+// Variable-length runs: the first `nrec` records of the caller's piece (piece_count has left its tiles' line bases in tile[mate])
+// become the padded text the ingest kernels read -- every read 'N' up to L, every quality line the offset character up to L --
+// in the workspace, and L - length goes into the row array padlen[mate] at the piece's rows.  The line index of the piece,
+// one plan pass per record (lengths checked: a record beyond L or with lines that differ ends the call with SCALCE_ERR_FORMAT),
+// one exclusive scan of the padded sizes, one copy pass; the buffer is sized from the scan's total: a piece of short reads grows.
+// *used = bytes of the caller's piece those records take.  The padded text is then counted like any piece (piece_count).
+static int pad_piece(scalce_batch *b, int mate, const u8 *d_text, u64 nbytes, u64 nrec, hipStream_t s, const u8 **padded, u64 *padded_bytes,
+                     u64 *used) {
+  scalce_workspace &w = *b->ws;
+  scalce_ctx *c = b->ctx;
+  ENSURE(b, w.vl_line_end[mate], sizeof(u64) * (4 * nrec + 8));
+  ENSURE(b, w.vl_off[mate], sizeof(u64) * (nrec + 8));
+  ENSURE(b, w.scan_ws, sizeof(u64) * (scan_ws_elems(nrec) + 64));
+  PadArgs a;
+  a.text = d_text; a.nbytes = nbytes; a.nrec = nrec; a.row0 = b->base;
+  a.line_end = w.vl_line_end[mate].as<u64>();
+  a.L = (u32)b->L[mate];
+  a.qpad = (u32)b->p.qmap[mate].offset & 127u;
+  a.padlen = w.padlen[mate].as<u16>() + b->base;
+  a.dst_off = w.vl_off[mate].as<u64>();
+  a.dst = nullptr;
+  a.err = b->d_err;
+  LAUNCH(index_write_k, cdiv(nbytes, IDX_TILE), IDX_THREADS, 0, s, d_text, nbytes, w.tile[mate].as<u64>(), w.vl_line_end[mate].as<u64>(), 4 * nrec);
+  LAUNCH(pad_plan_k, cdiv(nrec, 256), 256, 0, s, a);
+  exclusive_scan<u64>(PaddedSize{a.line_end, a.padlen}, nrec, StoreTo<u64>{a.dst_off}, w.scan_ws.as<u64>(), a.dst_off + nrec, s);
+  b->vl_mate = mate;
+  { int rc = check_device_error(b, s); if (rc) return rc; }
+  u64 total = 0, last_end = 0;
+  { int rc = read_u64(b, a.dst_off + nrec, &total, 1, s); if (rc) return rc; }
+  { int rc = read_u64(b, a.line_end + 4 * nrec - 1, &last_end, 1, s); if (rc) return rc; }
+  ENSURE(b, w.vl_text[mate], (size_t)total + 256);
+  a.dst = w.vl_text[mate].as<u8>();
+  LAUNCH(pad_copy_k, cdiv(total, VL_SPAN), 256, 0, s, a);
+  u64 nlines = 0;
+  u8 last = 0;
+  { int rc = piece_count(b, mate, a.dst, total, s, &nlines, &last); if (rc) return rc; }
+  HIP_TRY(c, hipStreamSynchronize(s));
+  if (nlines != 4 * nrec || last != '\n') { set_err(c, "internal: the padded text of %llu records has %llu lines", (unsigned long long)nrec, (unsigned long long)nlines); return SCALCE_ERR_HIP; }
+  *padded = a.dst;
+  *padded_bytes = total;
+  *used = last_end + 1;
+  return SCALCE_OK;
+}
+
 // "(ERROR) ..." for a text whose line count does not make whole records (pairs, under -i)
 static int text_shape_error(scalce_batch *b, u64 nlines, u8 last) {
   const u64 lpr = (u64)b->lpr;
@@ -229,6 +273,13 @@ extern "C" int scalce_batch_ingest(scalce_batch *b, int mate, const uint8_t *d_t
   if (nrec > b->max_reads) { set_err(c, "%llu records exceed the batch capacity", (unsigned long long)nrec); return SCALCE_ERR_CAPACITY; }
   if (mate == 0) { b->N = b->NP = nrec; }
   else if (nrec != b->N) { set_err(c, "(ERROR) mates have different record counts"); return SCALCE_ERR_FORMAT; }
+  u64 used = 0;
+  if (b->vl && nrec) {  // (the ingest reads the padded text)
+    u64 padded_bytes = 0;
+    int rc = pad_piece(b, mate, d_text, nbytes, nrec, s, &d_text, &padded_bytes, &used);
+    if (rc) return rc;
+    nbytes = padded_bytes;
+  }
   { int rc = piece_unpack(b, mate, d_text, nbytes, nrec, s); if (rc) return rc; }
   b->ingested[mate] = true;
   if (b->il) b->ingested[1] = true;
@@ -265,10 +316,13 @@ static int ingest_piece(scalce_batch *b, const uint8_t *const text[2], const u64
   if (b->base + nrec >= (1ull << 32) - 64) { set_err(c, "a batch holds fewer than 2^32 reads"); return SCALCE_ERR_CAPACITY; }
   { int rc = reserve_rows(b, b->base + nrec, b->base, s); if (rc) return rc; }
   for (int m = 0; m < b->ntext; m++) {
-    int rc = piece_unpack(b, m, text[m], nbytes[m], nrec, s);
+    const u8 *t = text[m];
+    u64 tn = nbytes[m], used = 0;
+    if (b->vl && nrec) { int rc = pad_piece(b, m, t, tn, nrec, s, &t, &tn, &used); if (rc) return rc; }  // (consumed stays in the caller's bytes)
+    int rc = piece_unpack(b, m, t, tn, nrec, s);
     if (rc) return rc;
     b->ingested[m] = true;
-    consumed[m] = nrec ? b->piece_consumed[m] : 0;  // behind the newline that ends the last record taken
+    consumed[m] = nrec ? (b->vl ? used : b->piece_consumed[m]) : 0;  // behind the newline that ends the last record taken
   }
   if (b->il) b->ingested[1] = true;
   HIP_TRY(c, hipStreamSynchronize(s));
@@ -313,7 +367,7 @@ static int not_whole_records(scalce_ctx *c, const char *which) {
 // ingest starts it over.
 extern "C" int scalce_batch_rewindow(scalce_batch *b, uint64_t keep_first, uint64_t keep_rows, const uint8_t *const front[2],
                                      const uint64_t front_bytes[2], const uint8_t *const back[2], const uint64_t back_bytes[2], void *stream) {
-  if (!b || !front || !back || !front_bytes || !back_bytes || keep_first + keep_rows > b->N || b->il) return SCALCE_ERR_ARG;
+  if (!b || !front || !back || !front_bytes || !back_bytes || keep_first + keep_rows > b->N || b->il || b->vl) return SCALCE_ERR_ARG;
   scalce_ctx *c = b->ctx;
   hipStream_t s = (hipStream_t)stream;
   HIP_TRY(c, hipSetDevice(c->device));
@@ -408,7 +462,7 @@ extern "C" uint64_t scalce_batch_reruns(const scalce_batch *b) { return b ? b->r
 extern "C" int scalce_batch_coder_round(const scalce_batch *b) { return b ? b->ac_round_launched : 0; }
 extern "C" int scalce_batch_set_code_in_place(scalce_batch *b, int on) {
   if (!b) return SCALCE_ERR_ARG;
-  if (on && (b->p.no_ac || b->lean)) return SCALCE_ERR_ARG;
+  if (on && (b->p.no_ac || b->lean || b->vl)) return SCALCE_ERR_ARG;  // (variable-length: a rerun would read the caller's text, not the padded one)
   b->code_in_place = on != 0;
   return SCALCE_OK;
 }

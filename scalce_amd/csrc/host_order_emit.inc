@@ -161,6 +161,11 @@ extern "C" int scalce_batch_order(scalce_batch *b, void *stream) {
     }
   }
   b->perm = perm1;
+  // variable-length runs: L - length in output order (mate 2 follows mate 1's order, like its reads)
+  for (int m = 0; m < b->nm && b->vl; m++) {
+    ENSURE(b, b->out_lengths[m], sizeof(u16) * (N + 64));
+    LAUNCH(gather_padlen_k, cdiv(N, 256), 256, 0, s, N, b->perm, w.padlen[m].as<u16>(), b->out_lengths[m].as<u16>());
+  }
   return SCALCE_OK;
 }
 

@@ -233,6 +233,10 @@ struct scalce_workspace {
   DBuf cell_sorted;                          // name cells in output order (emit stage)
   DBuf qs_shared[2];                         // reordered q' stream of batches that only pass it on (scalce_batch_set_stream_scratch)
   DBuf alt_packed[2], alt_q[2], alt_namelen, alt_namecell, alt_name_in_off, alt_tok_bucket, alt_tok_pos;  // second set of row arrays (scalce_batch_rewindow)
+  // Variable-length runs (params variable_length): padlen[m] = L - length per row, a run-wide row array beside namelen, 16 bits
+  // per row; and the pad pass of the piece being ingested -- the line index of the caller's text, where each record begins in
+  // the padded text (vl_off, one entry more: its size) and the padded text itself, which the ingest kernels then read
+  DBuf padlen[2], vl_line_end[2], vl_off[2], vl_text[2];
   hipStream_t side = nullptr;                // the quality statistics beside the tie-break's sweeps (quality_beside): ONE more stream per workspace
   ~scalce_workspace() { if (side) hipStreamDestroy(side); }
 };
@@ -296,6 +300,8 @@ struct scalce_batch {
   // piece's newline counts and line index are mate 0's (tile[0], line_end[0]) and serve both mates; ntext = texts per piece.
   bool il = false;
   int ntext = 1;
+  bool vl = false;  // reads of different lengths (params variable_length): a pad pass in front of the ingest (pad_piece)
+  int vl_mate = 0;  // ... and the mate whose piece it padded last (which read length an error speaks of)
   u64 unit_lines() const { return (u64)lpr * (il ? 2 : 1); }  // text lines per row: a record, or a pair
   // Rows.  A batch takes its input in one piece (scalce_batch_ingest) or in several (scalce_batch_append): rows
   // [base, base + NP) are the piece being ingested / tokenized, N = base + NP is everything the batch holds.  Packed
@@ -340,6 +346,7 @@ struct scalce_batch {
   AcBlockDesc *ac_desc_host = nullptr;  // block descriptors of the last coder launch this shard led: pinned, so that the
   u32 ac_desc_cap = 0;                  // asynchronous upload never reads memory the next launch is already rewriting
   u32 *perm = nullptr;  // final permutation (points into perm_a or perm_b)
+  DBuf out_lengths[2];  // variable-length runs: L - length in output order (the order stage gathers padlen through perm)
   // host-side results
   u64 out_reads_bytes[2] = {0, 0}, out_names_bytes = 0, out_qual_bytes[2] = {0, 0};
   u32 ntie = 0, nev = 0, ntev = 0, ncand_cap = 0, jacobi_iters = 0, nchunks = 1, sweep_no = 0;
@@ -469,6 +476,8 @@ static int reserve_rows(scalce_batch *b, u64 rows, u64 used, hipStream_t s) {
     if (!b->nq && (rc = ensure_keep(b, w.q[m], (size_t)b->qstride[m] * rows + 64, (size_t)b->qstride[m] * used, s))) return rc;
   }
   if ((rc = ensure_keep(b, w.namelen, rows + 64, used, s))) return rc;
+  for (int m = 0; m < b->nm && b->vl; m++)
+    if ((rc = ensure_keep(b, w.padlen[m], sizeof(u16) * (rows + 64), sizeof(u16) * used, s))) return rc;
   if (b->p.use_names && (rc = ensure_keep(b, w.namecell, 16 * (rows + 8), 16 * used, s))) return rc;
   if (w.name_in_off.p && (rc = ensure_keep(b, w.name_in_off, sizeof(u64) * (rows + 2), sizeof(u64) * used, s))) return rc;
   if ((rc = ensure_keep(b, w.bucket, sizeof(u32) * (rows + 1), sizeof(u32) * used, s))) return rc;
@@ -511,6 +520,11 @@ static int batch_create(scalce_ctx *c, const scalce_params *p, uint64_t max_read
     return SCALCE_ERR_ARG;
   }
   if (max_reads >= (1ull << 32) - 64) { set_err(c, "a shard holds fewer than 2^32 reads"); return SCALCE_ERR_CAPACITY; }
+  if (p->variable_length && (p->fasta || p->no_qualities || p->interleaved)) {
+    set_err(c, "variable-length reads (--variable-length) are not available together with %s",
+            p->fasta ? "FASTA input (-f)" : p->no_qualities ? "dropped qualities (-Q)" : "interleaved input (-i)");
+    return SCALCE_ERR_ARG;
+  }
   HIP_TRY(c, hipSetDevice(c->device));
   scalce_workspace *w = shared;
   if (!w) { w = new scalce_workspace(); w->ctx = c; }
@@ -522,6 +536,7 @@ static int batch_create(scalce_ctx *c, const scalce_params *p, uint64_t max_read
   b->nm = p->paired ? 2 : 1;
   b->il = p->interleaved != 0;
   b->ntext = b->il ? 1 : b->nm;
+  b->vl = p->variable_length != 0;
   for (int m = 0; m < b->nm; m++) {
     b->L[m] = p->read_len[m];
     b->szr[m] = sz_read(b->L[m]);
@@ -651,8 +666,13 @@ static int check_device_error(scalce_batch *b, hipStream_t s) {
                                 "quality symbol >= 80 after mapping (arithmetic.h:47)",
                                 "arithmetic-coded block larger than the reference's 10 MiB buffer (arithmetic.cpp:101)",
                                 "mates have different record counts", "internal"};
-  set_err(b->ctx, "(ERROR) %s [record/block %llu, aux %u]", names[e.code < 8 ? e.code : 7],
-          (unsigned long long)e.where, e.aux);
+  if (b->vl && e.code == E_READLEN)
+    set_err(b->ctx, "(ERROR) record %llu holds %u bases, more than the run's read length (%d%s): give the longest read with --max-length",
+            (unsigned long long)e.where, e.aux, b->L[b->vl_mate], b->nm == 2 ? (b->vl_mate ? ", mate 2" : ", mate 1") : "");
+  else if (e.code == E_SEQQUAL)
+    set_err(b->ctx, "(ERROR) record %llu: its sequence line (%u characters) and its quality line differ in length", (unsigned long long)e.where, e.aux);
+  else
+    set_err(b->ctx, "(ERROR) %s [record/block %llu, aux %u]", names[e.code < 8 ? e.code : 7], (unsigned long long)e.where, e.aux);
   hipMemsetAsync(b->d_err, 0, sizeof(DevErr), s);
   return SCALCE_ERR_FORMAT;
 }

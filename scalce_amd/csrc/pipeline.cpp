@@ -83,6 +83,10 @@ extern "C" int scalce_pipeline_create(scalce_batch **batches, int nslots, int gr
       p->err = "records without qualities (-f / -Q) have no coder stage: the pipeline does not take them";
       return SCALCE_ERR_ARG;
     }
+    if (bp.variable_length) {  // (a shard coded in place is run again from the caller's text, which is not the padded one)
+      p->err = "variable-length reads (--variable-length) are compressed one shard at a time: the pipeline does not take them";
+      return SCALCE_ERR_ARG;
+    }
   }
   p->b.assign(batches, batches + nslots);
   p->G = group;

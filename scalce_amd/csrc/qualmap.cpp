@@ -57,3 +57,32 @@ extern "C" void scalce_qmap_init(scalce_qmap *q, const int32_t stat[128], int lo
     for (int k = left; k <= right; k++) { q->values[k] = c; taken[k] = true; }
   }
 }
+
+// The sample of a variable-length run (quality_mapping_init's read loop, qualities.cpp:64-97, on text read ahead): the
+// histogram of the quality lines as they are -- nothing is padded yet -- and the read length the run is padded to: the longest
+// sequence line among the sampled records, unless the caller names one.
+extern "C" int64_t scalce_varlen_sample(const uint8_t *t, uint64_t n, int64_t sample, int stride, int first, int max_length,
+                                        int32_t stat[128], int32_t *read_len) {
+  if (read_len) *read_len = max_length > 0 ? max_length : 0;
+  if (!t || stride < 1 || first < 0 || first >= stride) return 0;
+  uint64_t line[5] = {0, 0, 0, 0, 0};  // where a record's four lines start, and the next record
+  int64_t taken = 0;
+  int32_t longest = 0;
+  for (int64_t r = 0; taken < sample; r++, line[0] = line[4]) {
+    bool whole = true;
+    for (int k = 1; k < 5 && whole; k++) {
+      const void *nl = line[k - 1] < n ? std::memchr(t + line[k - 1], '\n', n - line[k - 1]) : nullptr;
+      if (!nl) whole = false;
+      else line[k] = (uint64_t)(static_cast<const uint8_t *>(nl) - t) + 1;
+    }
+    if (!whole) break;
+    if (r % stride != first) continue;
+    taken++;
+    if (stat)
+      for (uint64_t j = line[3]; j + 1 < line[4]; j++) stat[t[j] & 127]++;
+    const uint64_t len = line[2] - 1 - line[1];
+    if (len > (uint64_t)longest) longest = len > 0x7FFFFFFFull ? 0x7FFFFFFF : (int32_t)len;
+  }
+  if (read_len && max_length <= 0) *read_len = longest;
+  return taken;
+}

@@ -18,6 +18,7 @@
 #include "automaton.hpp"
 #include "kernels_acl.hpp"
 #include "kernels_fastq.hpp"
+#include "kernels_varlen.hpp"
 
 using namespace scalce;
 

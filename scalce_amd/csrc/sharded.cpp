@@ -700,6 +700,10 @@ extern "C" int scalce_sharded_compress(scalce_comm *comm, scalce_ctx *ctx, scalc
       scalce_set_last_error(ctx, "interleaved input (-i) is compressed on one GPU: sharded runs do not take it");
       return SCALCE_ERR_ARG;
     }
+    if (bp.variable_length) {
+      scalce_set_last_error(ctx, "variable-length reads (--variable-length) are compressed on one GPU: sharded runs do not take them");
+      return SCALCE_ERR_ARG;
+    }
   }
   const int W = scalce_comm_world(comm), rank = scalce_comm_rank(comm);
   if (W > 64) return SCALCE_ERR_ARG;

@@ -42,6 +42,7 @@
 #include <vector>
 
 #include "../../include/scalce_hip.h"
+#include "lenstream.hpp"
 
 namespace {
 
@@ -147,6 +148,10 @@ struct Buckets {
 
 struct Mate {
   Src r, n, q;
+  Src l;                     // the length stream of a variable-length archive (params len_rd), or not open
+  bool has_len = false;
+  int l_width = 0;           // bytes per entry
+  u64 l_delivered = 0, l_skipped = 0;
   int L = 0, no_ac = 0;
   int64_t phred = 0;
   bool q_empty = false;
@@ -176,6 +181,10 @@ struct Mate {
 struct Slot {
   u8 *h_in = nullptr, *d_in = nullptr, *h_text = nullptr, *d_text = nullptr;
   u64 *h_roff = nullptr, *d_roff = nullptr;
+  // variable-length archives: the window's entries of the length stream, and what strips the pad off its text
+  u8 *h_len = nullptr, *d_len = nullptr, *d_text2 = nullptr;
+  u64 *d_roff2 = nullptr;
+  void *d_scan = nullptr;
   hipEvent_t ev_up = nullptr, ev_rec = nullptr, ev_done = nullptr, t_rec0 = nullptr, t_rec1 = nullptr;
   bool busy = false;
 };
@@ -283,6 +292,18 @@ struct Session {
         if (x.q.bad) return fail(SCALCE_ERR_FORMAT, m, 2, 0, "read error on the quality stream");
       }
       if (x.n.need(8)) x.n.skip(8);
+      if (P.len_rd[m]) {  // the fourth stream: header, then one entry per record
+        x.l.open(P.len_rd[m], P.len_skip[m], P.len_user[m], &S.read_wait_s, &x.l_delivered, &x.l_skipped);
+        int hl = 0;
+        const bool whole = x.l.need(scalce_host::LEN_HEADER_BYTES);
+        if (x.l.bad) return fail(SCALCE_ERR_FORMAT, m, 3, 0, "read error on the length stream");
+        if (const char *why = scalce_host::len_header_read(x.l.ptr(), whole ? scalce_host::LEN_HEADER_BYTES : 0, &x.l_width, &hl))
+          return fail(SCALCE_ERR_FORMAT, m, 3, 0, "(ERROR) %s", why);
+        x.l.skip(scalce_host::LEN_HEADER_BYTES);
+        if (hl != x.L)
+          return fail(SCALCE_ERR_FORMAT, m, 3, 0, "(ERROR) the length stream was written for reads of up to %d bases, the read stream holds reads of %d", hl, x.L);
+        x.has_len = true;
+      }
     }
     if (P.ignore_names) {
       library = P.library ? P.library : "";
@@ -379,9 +400,15 @@ struct Session {
       SD_TRY(dmalloc(&s.d_in, cap_in));
       SD_TRY(hmalloc(&s.h_text, cap_text));
       SD_TRY(dmalloc(&s.d_text, cap_text));
-      if (P.split) {
-        SD_TRY(hmalloc(&s.h_roff, 8 * (R + 1)));
-        SD_TRY(dmalloc(&s.d_roff, 8 * (R + 1)));
+      const bool strip = M[m0].has_len;  // (never with two mates in one window: -d -i refuses a length stream)
+      if (P.split) SD_TRY(hmalloc(&s.h_roff, 8 * (R + 1)));
+      if (P.split || strip) SD_TRY(dmalloc(&s.d_roff, 8 * (R + 1)));
+      if (strip) {
+        SD_TRY(hmalloc(&s.h_len, 2 * R + 64));
+        SD_TRY(dmalloc(&s.d_len, 2 * R + 64));
+        SD_TRY(dmalloc(&s.d_text2, cap_text));
+        SD_TRY(dmalloc(&s.d_roff2, 8 * (R + 1)));
+        SD_TRY(dmalloc(&s.d_scan, scalce_fastq_strip_ws_bytes(R)));
       }
       SD_HIP(hipEventCreateWithFlags(&s.ev_up, hipEventDisableTiming));
       SD_HIP(hipEventCreateWithFlags(&s.ev_rec, hipEventDisableTiming));
@@ -397,6 +424,11 @@ struct Session {
       if (s.h_in) hipHostFree(s.h_in);
       if (s.h_text) hipHostFree(s.h_text);
       if (s.h_roff) hipHostFree(s.h_roff);
+      if (s.h_len) hipHostFree(s.h_len);
+      dfree(s.d_len, 2 * R + 64);
+      dfree(s.d_text2, cap_text);
+      dfree(s.d_roff2, 8 * (R + 1));
+      dfree(s.d_scan, scalce_fastq_strip_ws_bytes(R));
       dfree(s.d_in, cap_in);
       dfree(s.d_text, cap_text);
       dfree(s.d_roff, 8 * (R + 1));
@@ -723,6 +755,12 @@ struct Session {
       x.drop = pl[2];
       x.syms_left = pl[2] + pl[3];
     }
+    for (int m = m0; m <= m1; m++) {  // the length stream: entries of one width
+      Mate &x = M[m];
+      if (!x.has_len) continue;
+      const u64 want = first * (u64)x.l_width;
+      if (x.l.pass(want) != want) return fail(SCALCE_ERR_FORMAT, m, 3, 0, x.l.bad ? "read error on the length stream" : "(ERROR) truncated length stream");
+    }
     for (int m = m0; m <= m1; m++) {
       Mate &x = M[m];
       x.first = first;
@@ -784,6 +822,19 @@ struct Session {
         }
       }
       if (!n) break;
+      // variable-length: the window's entries; their sum says how much shorter the text comes down than it is made
+      const bool strip = M[m0].has_len;
+      u64 cut = 0;
+      if (strip) {
+        Mate &x = M[m0];
+        const u64 want = n * (u64)x.l_width;
+        if (x.l.read_into(s.h_len, want) != want)
+          return fail(SCALCE_ERR_FORMAT, m0, 3, 0, x.l.bad ? "read error on the length stream" : "(ERROR) truncated length stream");
+        const u64 sum = scalce_host::len_entries_sum(s.h_len, n, x.l_width, x.L);
+        if (sum == ~0ull) return fail(SCALCE_ERR_FORMAT, m0, 3, 0, "(ERROR) the length stream holds an entry above the read length %d", x.L);
+        cut = 2 * sum;
+        SD_HIP(hipMemcpyAsync(s.d_len, s.h_len, want, hipMemcpyHostToDevice, s_up));
+      }
       // up, records -> text, down
       u64 nbytes = 0;
       for (int m = m0; m <= m1; m++)
@@ -817,7 +868,7 @@ struct Session {
         if (names) { w.d_names = s.d_in + x.o_names; w.d_name_off = reinterpret_cast<const u64 *>(s.d_in + x.o_noff); }
         w.library = library.c_str();
         w.d_out = s.d_text;
-        w.d_record_offsets = (P.split && m == m0) ? s.d_roff : nullptr;
+        w.d_record_offsets = ((P.split || strip) && m == m0) ? s.d_roff : nullptr;
         if (nmates == 2) {
           const Mate &y = M[m == m0 ? m1 : m0];
           w.interleave = m - m0 + 1; w.pair_read_len = y.L;
@@ -830,11 +881,15 @@ struct Session {
           x.pos += n * (u64)x.L;
         }
       }
+      if (strip) {  // the pad goes: the text and its record offsets come down from the stripped copy
+        SD_TRY(lib(scalce_fastq_strip_window(ctx, M[m0].L, n, s.d_text, s.d_roff, s.d_len, M[m0].l_width, s.d_text2, s.d_roff2, s.d_scan, s_main)));
+        nbytes -= cut;
+      }
       SD_HIP(hipEventRecord(s.t_rec1, s_main));
       SD_HIP(hipEventRecord(s.ev_rec, s_main));
       SD_HIP(hipStreamWaitEvent(s_down, s.ev_rec, 0));
-      SD_HIP(hipMemcpyAsync(s.h_text, s.d_text, nbytes, hipMemcpyDeviceToHost, s_down));
-      if (P.split) SD_HIP(hipMemcpyAsync(s.h_roff, s.d_roff, 8 * (n + 1), hipMemcpyDeviceToHost, s_down));
+      SD_HIP(hipMemcpyAsync(s.h_text, strip ? s.d_text2 : s.d_text, nbytes, hipMemcpyDeviceToHost, s_down));
+      if (P.split) SD_HIP(hipMemcpyAsync(s.h_roff, strip ? s.d_roff2 : s.d_roff, 8 * (n + 1), hipMemcpyDeviceToHost, s_down));
       SD_HIP(hipEventRecord(s.ev_done, s_down));
       {
         std::lock_guard<std::mutex> lk(mu);
@@ -947,6 +1002,12 @@ extern "C" int scalce_stream_decompress_range(scalce_ctx *ctx, const scalce_unpa
   for (int m = 0; m < p->mates; m++)
     if (!rd[m][0] || !rd[m][1] || (!p->no_qualities && !rd[m][2])) return SCALCE_ERR_ARG;
   if (p->ignore_names && !p->library) return SCALCE_ERR_ARG;
+  if ((p->len_rd[0] || p->len_rd[1]) && (p->interleave || p->no_qualities || !p->len_rd[0] || (p->mates == 2 && !p->len_rd[1]))) {
+    if (errbuf && errcap)
+      snprintf(errbuf, errcap, "(ERROR) a variable-length archive (a length stream) is decompressed one mate after the other, with its qualities: "
+                               "not interleaved, not without qualities, and every mate has its length stream");
+    return SCALCE_ERR_ARG;
+  }
   Session *s = new Session(ctx, p, range, wr, wr_user);
   int rc = s->run(rd, user);
   s->close();

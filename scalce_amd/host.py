@@ -15,6 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
 
 OUT_READS, OUT_NAMES, OUT_QUAL, OUT_TABLE, OUT_FREQ4, OUT_TOKENS, OUT_PERM, OUT_QSTREAM, OUT_BUCKET_COUNTS, OUT_QINPUT, OUT_NAMELEN = range(11)
+OUT_LENGTHS = 12  # variable-length runs: N x u16, read_len - length per record in output order
 STAGES = ("ingest", "quality", "tokenize", "order", "emit", "entropy")
 ROOT_CORE = 0x3FFFFFFF
 
@@ -34,7 +35,7 @@ class QMap(C.Structure):
 class Params(C.Structure):
     _fields_ = [("read_len", C.c_int32 * 2), ("paired", C.c_int32), ("use_names", C.c_int32), ("no_ac", C.c_int32),
                 ("qmap", QMap * 2), ("bucket_set_size", C.c_uint64), ("qprev", (C.c_uint32 * 2) * 2),
-                ("fasta", C.c_int32), ("no_qualities", C.c_int32), ("interleaved", C.c_int32)]
+                ("fasta", C.c_int32), ("no_qualities", C.c_int32), ("interleaved", C.c_int32), ("variable_length", C.c_int32)]
 
 
 class ShardResult(C.Structure):
@@ -526,9 +527,14 @@ def stream_compress(ctx, params, read1, read2=None, piece_bytes=0, reads_hint=0,
     return b, st
 
 
+SKIP_FN = C.CFUNCTYPE(C.c_int64, C.c_void_p, C.c_uint64)
+
+
 class UnpackParams(C.Structure):
     _fields_ = [("mates", C.c_int32), ("interleave", C.c_int32), ("no_qualities", C.c_int32), ("mate_digit", C.c_int32),
-                ("ignore_names", C.c_int32), ("split", C.c_int32), ("library", C.c_char_p), ("window_text_bytes", C.c_uint64)]
+                ("ignore_names", C.c_int32), ("split", C.c_int32), ("library", C.c_char_p), ("window_text_bytes", C.c_uint64),
+                # the length stream of a variable-length archive, per mate (all null: reads of one length)
+                ("len_rd", READ_FN * 2), ("len_user", C.c_void_p * 2), ("len_skip", SKIP_FN * 2)]
 
 
 class UnpackStats(C.Structure):
@@ -540,7 +546,6 @@ class UnpackStats(C.Structure):
 
 
 WRITE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64))
-SKIP_FN = C.CFUNCTYPE(C.c_int64, C.c_void_p, C.c_uint64)
 UNPACK_LOOKAHEAD_BYTES = 1 << 20  # SCALCE_UNPACK_LOOKAHEAD_BYTES: what a stream may be read ahead of what the session has used
 
 
@@ -552,6 +557,38 @@ class UnpackRangeStats(C.Structure):
     _fields_ = [("first_record", C.c_uint64), ("nrecords", C.c_uint64), ("total_records", C.c_uint64),
                 ("frames_decoded", C.c_uint64 * 2), ("frames_passed", C.c_uint64 * 2), ("symbols_decoded", C.c_uint64 * 2),
                 ("bytes_delivered", (C.c_uint64 * 3) * 2), ("bytes_skipped", (C.c_uint64 * 3) * 2)]
+
+
+def varlen_sample(text, sample=100000, stride=1, first=0, max_length=0):
+    """scalce_varlen_sample (no device): (records sampled, read length, quality histogram) of the first `sample` records r of
+    `text` with r % stride == first -- the read length a variable-length run is padded to is the longest sequence line among
+    them, or max_length when that is given."""
+    L = lib()
+    L.scalce_varlen_sample.argtypes = [C.c_char_p, C.c_uint64, C.c_int64, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32),
+                                       C.POINTER(C.c_int32)]
+    L.scalce_varlen_sample.restype = C.c_int64
+    stat = (C.c_int32 * 128)()
+    rl = C.c_int32(0)
+    text = bytes(text)
+    n = L.scalce_varlen_sample(text, len(text), int(sample), int(stride), int(first), int(max_length), stat, C.byref(rl))
+    return int(n), int(rl.value), np.array(stat[:], dtype=np.int64)
+
+
+def fastq_strip_window(ctx, read_len, nrecords, d_text, d_record_offsets, d_entries, entry_width, d_out, d_out_offsets, d_scan_ws,
+                       stream=0):
+    """scalce_fastq_strip_window: the pad out of a window of a variable-length archive (device pointers; see the header)."""
+    L = ctx.L
+    L.scalce_fastq_strip_window.argtypes = [C.c_void_p, C.c_int, C.c_uint64] + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 4
+    L.scalce_fastq_strip_window.restype = C.c_int
+    ctx._check(L.scalce_fastq_strip_window(ctx.h, int(read_len), int(nrecords), d_text, d_record_offsets, d_entries, int(entry_width),
+                                           d_out, d_out_offsets, d_scan_ws, stream))
+
+
+def fastq_strip_ws_bytes(nrecords):
+    L = lib()
+    L.scalce_fastq_strip_ws_bytes.argtypes = [C.c_uint64]
+    L.scalce_fastq_strip_ws_bytes.restype = C.c_uint64
+    return int(L.scalce_fastq_strip_ws_bytes(int(nrecords)))
 
 
 def range_plan_quality(read_len, first, n, total_syms):
@@ -568,13 +605,15 @@ def range_plan_quality(read_len, first, n, total_syms):
 
 
 def stream_decompress(ctx, readers, write, mates=1, interleave=False, no_qualities=False, mate_digit=None, library=None,
-                      split=0, window_text_bytes=0, first_record=0, nrecords=None, skippers=None):
+                      split=0, window_text_bytes=0, first_record=0, nrecords=None, skippers=None, length_readers=None,
+                      length_skippers=None):
     """scalce_stream_decompress_range: an archive, or a range of its records, back to text in windows of whole records.
     readers[m] = the three callables (cap) -> bytes of mate m's .scalcer, .scalcen and .scalceq streams (b"" at the end; raise
     for a read error); write(mate, first_record, nrecords, text_bytes, record_offsets or None) receives every window in
     order, from the library's writer thread (raise to end the session).  library: print names as <library>.<index> whatever
     the archive holds (-n).  first_record / nrecords (None: to the end): the range, in archive order; skippers[m] = three
-    callables (nbytes) -> bytes passed over, or None where the stream can only be read.  Returns UnpackStats; its attribute
+    callables (nbytes) -> bytes passed over, or None where the stream can only be read.  length_readers[m] (and, optionally,
+    length_skippers[m]): the .scalcel stream of a variable-length archive, one callable per mate.  Returns UnpackStats; its attribute
     `range` holds the UnpackRangeStats of the run."""
     keep = []
 
@@ -618,6 +657,11 @@ def stream_decompress(ctx, readers, write, mates=1, interleave=False, no_qualiti
                 rg.skip[m][k] = wrap_skip(skippers[m][k])
     p = UnpackParams(mates, int(interleave), int(no_qualities), int(mates == 2 if mate_digit is None else mate_digit),
                      int(library is not None), int(split), library.encode() if library is not None else None, int(window_text_bytes))
+    for m in range(mates):
+        if length_readers is not None and length_readers[m] is not None:
+            p.len_rd[m] = wrap(length_readers[m])
+        if length_skippers is not None and length_skippers[m] is not None:
+            p.len_skip[m] = wrap_skip(length_skippers[m])
     st = UnpackStats()
     rst = UnpackRangeStats()
     msg = C.create_string_buffer(1024)
@@ -652,7 +696,8 @@ class Batch:
     """One FASTQ shard in HBM (scalce_batch)."""
 
     def __init__(self, ctx, read_len, max_reads, max_text, paired=False, use_names=True, no_ac=False, qmap=None,
-                 bucket_set_size=0, read_len2=0, qprev=None, workspace=None, fasta=False, no_qualities=False, interleaved=False):
+                 bucket_set_size=0, read_len2=0, qprev=None, workspace=None, fasta=False, no_qualities=False, interleaved=False,
+                 variable_length=False):
         self.ctx = ctx
         self.L = ctx.L
         p = Params()
@@ -663,6 +708,7 @@ class Batch:
         p.bucket_set_size = int(bucket_set_size)
         p.fasta, p.no_qualities = int(fasta), int(no_qualities)  # two-line records (-f) / qualities dropped (-Q)
         p.interleaved = int(interleaved)  # -i: one text, mate 1 and mate 2 of a pair one after the other (needs paired)
+        p.variable_length = int(variable_length)  # reads of 0 .. read_len bases, padded to read_len in front of the ingest
         if qmap is not None:  # [(offset, values)] per mate
             for m, (off, vals) in enumerate(qmap):
                 p.qmap[m].offset = int(off)
