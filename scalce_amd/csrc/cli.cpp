@@ -34,6 +34,7 @@
 #include <csignal>
 
 #include "../../include/scalce_hip.h"
+#include "hip_own.hpp"
 #include "pargz.hpp"
 #include "lenstream.hpp"
 
@@ -328,16 +329,12 @@ static std::vector<uint8_t> fetch(scalce_ctx *ctx, scalce_batch *b, int which, i
 // the copy engine, the same 0.5 s.
 struct Downloader {
   static constexpr size_t SLICE = 64u << 20;
-  uint8_t *pin[2] = {nullptr, nullptr};
-  hipStream_t s = nullptr;
-  hipEvent_t ev[2] = {nullptr, nullptr};
+  Stream s;  // (in front of the slices and events: it goes last)
+  HBuf pin[2];
+  Event ev[2];
   Downloader() {
-    HIPOK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    for (int i = 0; i < 2; i++) { HIPOK(hipHostMalloc(reinterpret_cast<void **>(&pin[i]), SLICE, hipHostMallocDefault)); HIPOK(hipEventCreateWithFlags(&ev[i], hipEventDisableTiming)); }
-  }
-  ~Downloader() {
-    for (int i = 0; i < 2; i++) { if (pin[i]) hipHostFree(pin[i]); if (ev[i]) hipEventDestroy(ev[i]); }
-    if (s) hipStreamDestroy(s);
+    HIPOK(s.create());
+    for (int i = 0; i < 2; i++) { HIPOK(pin[i].alloc(SLICE)); HIPOK(ev[i].create()); }
   }
   void to_file(scalce_ctx *ctx, scalce_batch *b, int which, int mate, OutFile &f) {
     const void *d = nullptr;
@@ -361,14 +358,14 @@ struct Downloader {
     const uint64_t nslices = (n + SLICE - 1) / SLICE;
     auto start = [&](uint64_t i) {
       const uint64_t off = i * SLICE;
-      fill(pin[i & 1], off, std::min<uint64_t>(SLICE, n - off));
+      fill(pin[i & 1].as<uint8_t>(), off, std::min<uint64_t>(SLICE, n - off));
       HIPOK(hipEventRecord(ev[i & 1], s));
     };
     if (nslices) start(0);
     for (uint64_t i = 0; i < nslices; i++) {
       HIPOK(hipEventSynchronize(ev[i & 1]));
       if (i + 1 < nslices) start(i + 1);
-      f.write(pin[i & 1], (size_t)std::min<uint64_t>(SLICE, n - i * SLICE));
+      f.write(pin[i & 1].as<uint8_t>(), (size_t)std::min<uint64_t>(SLICE, n - i * SLICE));
     }
   }
 };
@@ -623,8 +620,8 @@ static int do_compress(const Options &o, const std::vector<std::string> &files, 
   scalce_batch_stats(b, st4);
   // the arithmetic coder starts on its own stream; the read and name streams come down and are written beside it
   // (a run of up to 2048 blocks is one launch that takes as long as ONE block's serial chain, about 0.3 s)
-  hipStream_t s_ent = nullptr;
-  HIPOK(hipStreamCreateWithFlags(&s_ent, hipStreamNonBlocking));
+  Stream s_ent;
+  HIPOK(s_ent.create());
   SCOK(ctx, scalce_batch_set_frame_on_demand(b, 1));  // the coded blocks are framed on their way into the pinned slices
   SCOK(ctx, scalce_batch_entropy_begin(b, nullptr, s_ent));
 
@@ -686,7 +683,7 @@ static int do_compress(const Options &o, const std::vector<std::string> &files, 
       struct stat st;
       if (stat(archive_path(o.out, m, ext).c_str(), &st) == 0) new_size += (uint64_t)st.st_size;
     }
-  hipStreamDestroy(s_ent);
+  s_ent.release();
   const void *dc = nullptr;
   uint64_t nc = 0;
   SCOK(ctx, scalce_batch_output(b, SCALCE_OUT_BUCKET_COUNTS, 0, &dc, &nc));
@@ -834,10 +831,11 @@ static int rank_main(const Options &o, const std::vector<std::string> &files, co
   }
   if (p.read_len[0] <= 0) FAIL("Cannot determine the read length of %s\n", files[0].c_str());
   // ---- this rank's records: line-aligned byte ranges, line counts of everybody, then cuts at multiples of four lines
-  hipStream_t s = nullptr;
-  HIPOK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-  uint64_t *d_io = nullptr;
-  HIPOK(hipMalloc(reinterpret_cast<void **>(&d_io), sizeof(uint64_t) * (64 + 64 * 4)));
+  Stream s;
+  HIPOK(s.create());
+  DBuf d_io_buf;
+  HIPOK(dbuf_alloc(d_io_buf, sizeof(uint64_t) * (64 + 64 * 4)));
+  uint64_t *d_io = d_io_buf.as<uint64_t>();
   uint64_t lo[2], hi[2];
   std::vector<uint64_t> K;  // rank r starts at record K[r], in every mate
   for (int m = 0; m < nm; m++) {
@@ -870,15 +868,18 @@ static int rank_main(const Options &o, const std::vector<std::string> &files, co
     hi[m] = offset_of_line(4 * K[rank + 1]);
   }
   // ---- the piece into HBM
+  DBuf d_text_buf[2];
   uint8_t *d_text[2] = {nullptr, nullptr};
   {
     const size_t CH = 256u << 20;
+    HBuf pin_buf[2];  // (both go at the end of this block, behind the stream's synchronisation)
+    Event ev[2];
     uint8_t *pin[2];
-    hipEvent_t ev[2];
-    for (int i = 0; i < 2; i++) { HIPOK(hipHostMalloc(reinterpret_cast<void **>(&pin[i]), CH, hipHostMallocDefault)); HIPOK(hipEventCreateWithFlags(&ev[i], hipEventDisableTiming)); }
+    for (int i = 0; i < 2; i++) { HIPOK(pin_buf[i].alloc(CH)); HIPOK(ev[i].create()); pin[i] = pin_buf[i].as<uint8_t>(); }
     for (int m = 0; m < nm; m++) {
       const uint64_t n = hi[m] - lo[m];
-      HIPOK(hipMalloc(reinterpret_cast<void **>(&d_text[m]), n + 256));
+      HIPOK(dbuf_alloc(d_text_buf[m], n + 256));
+      d_text[m] = d_text_buf[m].as<uint8_t>();
       uint64_t done = 0;
       for (int i = 0; done < n; i ^= 1) {
         HIPOK(hipEventSynchronize(ev[i]));
@@ -890,7 +891,6 @@ static int rank_main(const Options &o, const std::vector<std::string> &files, co
       }
     }
     HIPOK(hipStreamSynchronize(s));
-    for (int i = 0; i < 2; i++) { hipHostFree(pin[i]); hipEventDestroy(ev[i]); }
   }
   const double t1 = now();
   // ---- the sharded run
@@ -902,7 +902,7 @@ static int rank_main(const Options &o, const std::vector<std::string> &files, co
   if (scalce_sharded_compress(comm, ctx, b, d_text[0], hi[0] - lo[0], nm == 2 ? d_text[1] : nullptr, nm == 2 ? hi[1] - lo[1] : 0, 0, s,
                               nullptr, &res))
     exit(1);
-  for (int m = 0; m < nm; m++) hipFree(d_text[m]);
+  for (int m = 0; m < nm; m++) d_text_buf[m].release();
   const double t2 = now();
   // ---- every rank writes its pieces of the archive
   const uint32_t nb1 = res.nb1;

@@ -6,20 +6,21 @@
 // takes a run of whole frames that starts at any frame of the stream.
 struct scalce_ac_decoder {
   scalce_ctx *c = nullptr;
-  u32 *d_table = nullptr, *d_cum = nullptr;  // (d_cum: ac_table_k writes the cumulative counts beside the intervals)
-  uint4 *d_tab = nullptr;
-  uint2 *d_rows = nullptr;
-  u64 device_bytes = 0;
+  DBuf d_table, d_cum;  // u32 (d_cum: ac_table_k writes the cumulative counts beside the intervals)
+  DBuf d_tab;           // uint4
+  DBuf d_rows;          // uint2
   bool cached = false, tight = false;
   int wpb_forced = -1;    // test hook SCALCE_AC_DECODE_WPB: chains per workgroup (2, 4, 8, 16); 0 = the plain decoder
   AcDecCachedArgs ca;
 };
 extern "C" void scalce_ac_decoder_destroy(scalce_ac_decoder *d) {
   if (!d) return;
-  hipFree(d->d_table); hipFree(d->d_cum); hipFree(d->d_tab); hipFree(d->d_rows);
+  (void)hipSetDevice(d->c->device);
   delete d;
 }
-extern "C" uint64_t scalce_ac_decoder_device_bytes(const scalce_ac_decoder *d) { return d ? d->device_bytes : 0; }
+extern "C" uint64_t scalce_ac_decoder_device_bytes(const scalce_ac_decoder *d) {
+  return d ? d->d_table.cap + d->d_cum.cap + d->d_tab.cap + d->d_rows.cap : 0;
+}
 extern "C" int scalce_ac_decoder_create(scalce_ctx *c, const uint32_t *table_host, void *stream, scalce_ac_decoder **out) {
   if (!c || !table_host || !out) return SCALCE_ERR_ARG;
   *out = nullptr;
@@ -28,12 +29,11 @@ extern "C" int scalce_ac_decoder_create(scalce_ctx *c, const uint32_t *table_hos
   std::unique_ptr<scalce_ac_decoder, void (*)(scalce_ac_decoder *)> d(new scalce_ac_decoder, scalce_ac_decoder_destroy);
   d->c = c;
   memset(&d->ca, 0, sizeof d->ca);
-  HIP_TRY(c, hipMalloc(&d->d_table, sizeof(u32) * 512000));
-  HIP_TRY(c, hipMalloc(&d->d_tab, sizeof(uint4) * 512000));
-  HIP_TRY(c, hipMalloc(&d->d_cum, sizeof(u32) * 6400 * 81));
-  d->device_bytes = (sizeof(u32) + sizeof(uint4)) * 512000 + sizeof(u32) * 6400 * 81;
-  HIP_TRY(c, hipMemcpyAsync(d->d_table, table_host, sizeof(u32) * 512000, hipMemcpyHostToDevice, s));
-  LAUNCH(ac_table_k, cdiv(6400, 64), 64, 0, s, d->d_table, d->d_tab, d->d_cum, (u32 *)nullptr);
+  HIP_TRY(c, dbuf_alloc(d->d_table, sizeof(u32) * 512000));
+  HIP_TRY(c, dbuf_alloc(d->d_tab, sizeof(uint4) * 512000));
+  HIP_TRY(c, dbuf_alloc(d->d_cum, sizeof(u32) * 6400 * 81));
+  HIP_TRY(c, hipMemcpyAsync(d->d_table.p, table_host, sizeof(u32) * 512000, hipMemcpyHostToDevice, s));
+  LAUNCH(ac_table_k, cdiv(6400, 64), 64, 0, s, d->d_table.as<u32>(), d->d_tab.as<uint4>(), d->d_cum.as<u32>(), (u32 *)nullptr);
   // span of the symbols that occur (scaled count > 1 in some context) and their totals: what the compact rows hold and
   // which contexts go to LDS.  (A symbol outside the span can still be coded -- one occurrence scales down to the
   // floor count 1 -- and takes the full-row path in the kernel.)
@@ -59,11 +59,10 @@ extern "C" int scalce_ac_decoder_create(scalce_ctx *c, const uint32_t *table_hos
     ca.W = W;
     memset(ca.rank, 0xFF, sizeof ca.rank);
     for (u32 r = 0; r < W; r++) { ca.hot[r] = (u8)order[r]; ca.rank[order[r]] = (u8)r; }
-    HIP_TRY(c, hipMalloc(&d->d_rows, sizeof(uint2) * (6400 * ca.S1 + 64)));  // (+ 64: a row is read with all lanes)
-    d->device_bytes += sizeof(uint2) * (6400 * (u64)ca.S1 + 64);
-    HIP_TRY(c, hipMemsetAsync(d->d_rows + 6400 * (size_t)ca.S1, 0, sizeof(uint2) * 64, s));
-    LAUNCH(ac_dec_rows_k, cdiv(6400u * ca.S1, 256), 256, 0, s, d->d_tab, smin, ca.S1, d->d_rows);
-    ca.rows = d->d_rows;
+    HIP_TRY(c, dbuf_alloc(d->d_rows, sizeof(uint2) * (6400 * ca.S1 + 64)));  // (+ 64: a row is read with all lanes)
+    HIP_TRY(c, hipMemsetAsync(d->d_rows.as<uint2>() + 6400 * (size_t)ca.S1, 0, sizeof(uint2) * 64, s));
+    LAUNCH(ac_dec_rows_k, cdiv(6400u * ca.S1, 256), 256, 0, s, d->d_tab.as<uint4>(), smin, ca.S1, d->d_rows.as<uint2>());
+    ca.rows = d->d_rows.as<uint2>();
     // ONE cached decoder (round 5; rounds 2-4 kept four): ac_decode_tight_k, the loop written by hand for the scalar unit.  It
     // needs what every table of quality strings gives -- no symbol 79 among those that occur (that symbol marks "last of its
     // context" in the rows) and no context total above 2^29 (as for the encoder's plain step); any other table takes the plain
@@ -97,7 +96,7 @@ extern "C" int scalce_ac_decoder_launch(scalce_ac_decoder *d, const uint8_t *d_f
   // the walk is serial by nature (each size says where the next one is): a small kernel follows the chain of this launch's frames
   LAUNCH(ac_frame_walk_k, 1, 1, 0, s, d_frames, (u64)nbytes, nblk, reinterpret_cast<u64 *>(d_off), d_size, d_bad);
   AcDecArgs a;
-  a.in = d_frames; a.blk_off = reinterpret_cast<const u64 *>(d_off); a.blk_size = d_size; a.nsym = nsym; a.tab = d->d_tab; a.out = d_out;
+  a.in = d_frames; a.blk_off = reinterpret_cast<const u64 *>(d_off); a.blk_size = d_size; a.nsym = nsym; a.tab = d->d_tab.as<uint4>(); a.out = d_out;
   if (d->cached && d->tight) {
     AcDecCachedArgs ca = d->ca;
     ca.d = a;
@@ -125,21 +124,19 @@ extern "C" int scalce_ac_decode(scalce_ctx *c, const uint32_t *table_host, const
   HIP_TRY(c, hipSetDevice(c->device));
   const u32 nblk = cdiv(nsym, AC_BLOCK_SYMS);
   if (!nblk) return SCALCE_OK;
-  scalce_ac_decoder *dec = nullptr;
-  if (int rc = scalce_ac_decoder_create(c, table_host, stream, &dec)) return rc;
-  u64 *d_off = nullptr;
-  u32 *d_sz = nullptr;  // nblk sizes and, behind them, the walk's verdict
-  hipError_t e = hipMalloc(&d_off, sizeof(u64) * nblk);
-  if (e == hipSuccess) e = hipMalloc(&d_sz, sizeof(u32) * ((size_t)nblk + 1));
-  int rc = SCALCE_OK;
+  scalce_ac_decoder *made = nullptr;
+  if (int rc = scalce_ac_decoder_create(c, table_host, stream, &made)) return rc;
+  std::unique_ptr<scalce_ac_decoder, void (*)(scalce_ac_decoder *)> dec(made, scalce_ac_decoder_destroy);
+  DBuf d_off, d_sz;  // u64 offsets; u32: nblk sizes and, behind them, the walk's verdict
   u32 bad = 0;
-  if (e == hipSuccess) rc = scalce_ac_decoder_launch(dec, d_blocks, nbytes, nblk, nsym, reinterpret_cast<uint64_t *>(d_off), d_sz, d_sz + nblk, d_out, stream);
-  if (e == hipSuccess && !rc) e = hipMemcpyAsync(&bad, d_sz + nblk, sizeof bad, hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess && !rc) e = hipStreamSynchronize(s);
-  hipFree(d_off); hipFree(d_sz);
-  scalce_ac_decoder_destroy(dec);
-  if (rc) return rc;
-  if (e != hipSuccess) { set_err(c, "decoding the quality stream: %s", hipGetErrorString(e)); return SCALCE_ERR_HIP; }
+  auto hip_failed = [&](hipError_t e) {
+    if (e != hipSuccess) set_err(c, "decoding the quality stream: %s", hipGetErrorString(e));
+    return e != hipSuccess;
+  };
+  if (hip_failed(dbuf_alloc(d_off, sizeof(u64) * nblk)) || hip_failed(dbuf_alloc(d_sz, sizeof(u32) * ((size_t)nblk + 1)))) return SCALCE_ERR_HIP;
+  u32 *sz = d_sz.as<u32>();
+  if (int rc = scalce_ac_decoder_launch(dec.get(), d_blocks, nbytes, nblk, nsym, d_off.as<uint64_t>(), sz, sz + nblk, d_out, stream)) return rc;
+  if (hip_failed(hipMemcpyAsync(&bad, sz + nblk, sizeof bad, hipMemcpyDeviceToHost, s)) || hip_failed(hipStreamSynchronize(s))) return SCALCE_ERR_HIP;
   if (bad) { set_err(c, "(ERROR) truncated quality stream"); return SCALCE_ERR_FORMAT; }
   return SCALCE_OK;
 }
@@ -276,41 +273,37 @@ static int fastq_records_impl(scalce_ctx *c, int read_len, int has_buckets, cons
   if (!nrecords) return SCALCE_OK;
   FqArgs a;
   memset(&a, 0, sizeof a);
-  u8 *d_reads = nullptr, *d_names = nullptr;
-  FqBucket *d_dir = nullptr;
-  u64 *d_noff = nullptr, *d_roff = nullptr, *d_pnoff = nullptr;
-  auto release = [&]() { hipFree(d_reads); hipFree(d_names); hipFree(d_dir); hipFree(d_noff); hipFree(d_roff); hipFree(d_pnoff); };
-#define FQ_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { release(); set_err(c, "%s failed: %s", #expr, hipGetErrorString(e_)); return SCALCE_ERR_HIP; } } while (0)
-  FQ_TRY(hipMalloc(&d_reads, reads_bytes + 64));
-  FQ_TRY(hipMalloc(&d_dir, sizeof(FqBucket) * dir.size()));
-  FQ_TRY(hipMemcpyAsync(d_reads, reads_host, reads_bytes, hipMemcpyHostToDevice, s));
-  FQ_TRY(hipMemcpyAsync(d_dir, dir.data(), sizeof(FqBucket) * dir.size(), hipMemcpyHostToDevice, s));
+  DBuf d_reads, d_names, d_dir, d_noff, d_roff, d_pnoff;  // (gone with the call, on every way out)
+#define FQ_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { set_err(c, "%s failed: %s", #expr, hipGetErrorString(e_)); return SCALCE_ERR_HIP; } } while (0)
+  FQ_TRY(dbuf_alloc(d_reads, reads_bytes + 64));
+  FQ_TRY(dbuf_alloc(d_dir, sizeof(FqBucket) * dir.size()));
+  FQ_TRY(hipMemcpyAsync(d_reads.p, reads_host, reads_bytes, hipMemcpyHostToDevice, s));
+  FQ_TRY(hipMemcpyAsync(d_dir.p, dir.data(), sizeof(FqBucket) * dir.size(), hipMemcpyHostToDevice, s));
   if (names_host) {
-    FQ_TRY(hipMalloc(&d_names, names_bytes + 64));
-    FQ_TRY(hipMalloc(&d_noff, sizeof(u64) * (nrecords + 1)));
-    FQ_TRY(hipMemcpyAsync(d_names, names_host, names_bytes, hipMemcpyHostToDevice, s));
-    FQ_TRY(hipMemcpyAsync(d_noff, name_off.data(), sizeof(u64) * (nrecords + 1), hipMemcpyHostToDevice, s));
+    FQ_TRY(dbuf_alloc(d_names, names_bytes + 64));
+    FQ_TRY(dbuf_alloc(d_noff, sizeof(u64) * (nrecords + 1)));
+    FQ_TRY(hipMemcpyAsync(d_names.p, names_host, names_bytes, hipMemcpyHostToDevice, s));
+    FQ_TRY(hipMemcpyAsync(d_noff.p, name_off.data(), sizeof(u64) * (nrecords + 1), hipMemcpyHostToDevice, s));
     if (pair) {
-      FQ_TRY(hipMalloc(&d_pnoff, sizeof(u64) * (nrecords + 1)));
-      FQ_TRY(hipMemcpyAsync(d_pnoff, pair->pair_noff->data(), sizeof(u64) * (nrecords + 1), hipMemcpyHostToDevice, s));
+      FQ_TRY(dbuf_alloc(d_pnoff, sizeof(u64) * (nrecords + 1)));
+      FQ_TRY(hipMemcpyAsync(d_pnoff.p, pair->pair_noff->data(), sizeof(u64) * (nrecords + 1), hipMemcpyHostToDevice, s));
     }
   } else {
     a.lib_len = (u32)std::min<size_t>(strlen(library), sizeof a.lib - 1);
-    if (strlen(library) >= sizeof a.lib) { release(); set_err(c, "library name longer than %zu characters", sizeof a.lib - 1); return SCALCE_ERR_ARG; }
+    if (strlen(library) >= sizeof a.lib) { set_err(c, "library name longer than %zu characters", sizeof a.lib - 1); return SCALCE_ERR_ARG; }
     memcpy(a.lib, library, a.lib_len);
   }
-  if (record_offsets_host) FQ_TRY(hipMalloc(&d_roff, sizeof(u64) * (nrecords + 1)));
-  a.reads = d_reads; a.dir = d_dir; a.nbuckets = (u32)dir.size(); a.nrecords = nrecords; a.L = L; a.sz_meta = sz_meta;
-  a.qual = d_qual; a.phred = (u32)phred_offset; a.names = d_names; a.name_off = d_noff;
-  a.mate_digit = (u32)mate_digit; a.out = d_out; a.rec_off = d_roff;
-  if (pair) { a.il = pair->il; a.pair_L = (u32)pair->pair_L; a.pair_name_off = d_pnoff; }
+  if (record_offsets_host) FQ_TRY(dbuf_alloc(d_roff, sizeof(u64) * (nrecords + 1)));
+  a.reads = d_reads.as<u8>(); a.dir = d_dir.as<FqBucket>(); a.nbuckets = (u32)dir.size(); a.nrecords = nrecords; a.L = L; a.sz_meta = sz_meta;
+  a.qual = d_qual; a.phred = (u32)phred_offset; a.names = d_names.as<u8>(); a.name_off = d_noff.as<u64>();
+  a.mate_digit = (u32)mate_digit; a.out = d_out; a.rec_off = d_roff.as<u64>();
+  if (pair) { a.il = pair->il; a.pair_L = (u32)pair->pair_L; a.pair_name_off = d_pnoff.as<u64>(); }
   launch_records(a, qual, s);
   if (record_offsets_host)
-    FQ_TRY(hipMemcpyAsync(record_offsets_host, d_roff, sizeof(u64) * (nrecords + 1), hipMemcpyDeviceToHost, s));
+    FQ_TRY(hipMemcpyAsync(record_offsets_host, d_roff.p, sizeof(u64) * (nrecords + 1), hipMemcpyDeviceToHost, s));
   FQ_TRY(hipStreamSynchronize(s));
   FQ_TRY(hipGetLastError());
 #undef FQ_TRY
-  release();
   return SCALCE_OK;
 }
 

@@ -1,15 +1,5 @@
 // host_state.inc -- part of scalce_hip.hip (one translation unit; included there, in this order): context, core tables on the device, grow-only buffers, the shared workspace, the batch, read-backs
-struct DBuf {  // grow-only device buffer; owns its memory (freed on the device that is current when it dies: hipSetDevice first)
-  void *p = nullptr;
-  size_t cap = 0;
-  DBuf() = default;
-  DBuf(DBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
-  DBuf &operator=(DBuf &&o) noexcept { if (this != &o) { release(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; } return *this; }
-  ~DBuf() { release(); }
-  void release() { if (p) hipFree(p); p = nullptr; cap = 0; }
-  template <typename T> T *as() const { return static_cast<T *>(p); }
-};
-static_assert(!std::is_copy_constructible<DBuf>::value && !std::is_copy_assignable<DBuf>::value, "a DBuf is handed over with std::move");
+#include "hip_own.hpp"  // DBuf: the grow-only device buffer that frees itself
 
 // the loaded table on the device (upload_tables): replaced as a whole by the next table
 struct DeviceTables {

@@ -21,15 +21,17 @@
 #include <vector>
 
 #include "../../include/scalce_hip.h"
+#include "hip_own.hpp"
 
 struct scalce_pipeline {
   std::vector<scalce_batch *> b;
   int G = 1;
   bool external = false;  // shards arrive with their coder prepared / enqueued by the caller (sharded runs)
-  hipStream_t front = nullptr;
-  std::vector<hipStream_t> coders;
-  hipEvent_t ev_front = nullptr;      // coder streams wait for the front stages through it
-  std::vector<hipEvent_t> ev;         // per slot: behind its coder launch
+  // (the streams in front of the events recorded on them: members go in reverse order)
+  Stream front;
+  std::vector<Stream> coders;
+  Event ev_front;                     // coder streams wait for the front stages through it
+  std::vector<Event> ev;              // per slot: behind its coder launch
   std::vector<char> busy;
   std::vector<int> pending;
   int next = 0;
@@ -92,27 +94,17 @@ extern "C" int scalce_pipeline_create(scalce_batch **batches, int nslots, int gr
   p->G = group;
   p->external = external_coder != 0;
   p->busy.assign(nslots, 0);
-  p->ev.assign(nslots, nullptr);
+  p->ev.resize(nslots);
   PL_HIP(p, hipGetDevice(&p->device));
-  PL_HIP(p, hipStreamCreateWithFlags(&p->front, hipStreamNonBlocking));
-  for (int i = 0; i < coder_streams; i++) {
-    hipStream_t s;
-    PL_HIP(p, hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    p->coders.push_back(s);
-  }
-  PL_HIP(p, hipEventCreateWithFlags(&p->ev_front, hipEventDisableTiming));
-  for (int i = 0; i < nslots; i++) PL_HIP(p, hipEventCreateWithFlags(&p->ev[i], hipEventDisableTiming));
+  PL_HIP(p, p->front.create());
+  p->coders.resize(coder_streams);
+  for (Stream &s : p->coders) PL_HIP(p, s.create());
+  PL_HIP(p, p->ev_front.create());
+  for (Event &e : p->ev) PL_HIP(p, e.create());
   return SCALCE_OK;
 }
 
-extern "C" void scalce_pipeline_destroy(scalce_pipeline *p) {
-  if (!p) return;
-  for (hipEvent_t e : p->ev) if (e) hipEventDestroy(e);
-  if (p->ev_front) hipEventDestroy(p->ev_front);
-  for (hipStream_t s : p->coders) if (s) hipStreamDestroy(s);
-  if (p->front) hipStreamDestroy(p->front);
-  delete p;
-}
+extern "C" void scalce_pipeline_destroy(scalce_pipeline *p) { delete p; }  // events, then coder streams, then the front stream
 
 extern "C" const char *scalce_pipeline_error(const scalce_pipeline *p) { return p ? p->err.c_str() : "no pipeline"; }
 extern "C" void *scalce_pipeline_front_stream(scalce_pipeline *p) { return p ? p->front : nullptr; }

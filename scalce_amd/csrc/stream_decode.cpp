@@ -30,106 +30,36 @@
 
 #include <algorithm>
 #include <atomic>
-#include <chrono>
 #include <condition_variable>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <deque>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
 #include <vector>
 
 #include "../../include/scalce_hip.h"
+#include "hip_own.hpp"
 #include "lenstream.hpp"
+#include "stream_src.hpp"
 
 namespace {
 
 typedef uint8_t u8;
 typedef uint32_t u32;
 typedef uint64_t u64;
+using scalce_host::now_s;
+using scalce_host::Src;
 
 constexpr u64 FRAME = SCALCE_AC_BLOCK;
 constexpr u64 TABLE_BYTES = 512000ull * 4;
 constexpr u64 SCALCE_DECODE_AHEAD = 8;  // windows' worth of symbols per decoder batch
 constexpr u64 UNKNOWN = ~0ull;
 
-double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 u64 align_up(u64 v, u64 a) { return (v + a - 1) / a * a; }
-
-// one stream of the archive behind its read callback: a look-ahead buffer for the parts the host walks (headers, names,
-// frame sizes), bulk reads straight into the caller's pinned memory for the rest
-struct Src {
-  scalce_read_fn rd = nullptr;
-  scalce_skip_fn skp = nullptr;
-  void *user = nullptr;
-  std::vector<u8> buf;
-  size_t pos = 0, end = 0;
-  bool eof = false, bad = false;
-  double *wait = nullptr;
-  u64 *delivered = nullptr, *skipped = nullptr;
-  void open(scalce_read_fn f, scalce_skip_fn sk, void *u, double *w, u64 *del, u64 *skd) {
-    rd = f; skp = f ? sk : nullptr; user = u; wait = w; delivered = del; skipped = skd;
-    buf.resize(SCALCE_UNPACK_LOOKAHEAD_BYTES);
-  }
-  size_t avail() const { return end - pos; }
-  const u8 *ptr() const { return buf.data() + pos; }
-  void skip(size_t n) { pos += n; }
-  int64_t pull(void *dst, u64 cap) {
-    if (!rd) { eof = true; return 0; }
-    const double t0 = now_s();
-    const int64_t k = rd(user, dst, cap);
-    *wait += now_s() - t0;
-    if (k < 0) bad = true;
-    if (k == 0) eof = true;
-    if (k > 0) *delivered += (u64)k;
-    return k;
-  }
-  // false: the stream ends (or fails) before n bytes.  `look`: how far a refill may read ahead of the n bytes asked for --
-  // the whole buffer for a stream that is read from end to end; less in front of bytes that are about to be passed over
-  bool need(size_t n, size_t look = ~(size_t)0) { return end - pos >= n ? true : fill(n, look); }
-  bool fill(size_t n, size_t look) {
-    if (pos) { memmove(buf.data(), buf.data() + pos, end - pos); end -= pos; pos = 0; }
-    if (buf.size() < n) buf.resize(n);
-    while (end < n && !eof && !bad) {
-      const int64_t k = pull(buf.data() + end, std::min(buf.size() - end, n - end + std::min(look, buf.size())));
-      if (k > 0) end += (size_t)k;
-    }
-    return end >= n;
-  }
-  // passes over n bytes: what the look-ahead buffer holds first, then the caller's skip, or -- without one -- reads that are
-  // dropped; returns the bytes passed over (< n: the stream ends there, or has failed)
-  u64 pass(u64 n) {
-    u64 got = std::min<u64>(n, avail());
-    pos += got;
-    if (got < n && skp && !eof && !bad) {
-      const double t0 = now_s();
-      const int64_t k = skp(user, n - got);
-      *wait += now_s() - t0;
-      if (k < 0 || (u64)k > n - got) bad = true;
-      else { got += (u64)k; *skipped += (u64)k; if (got < n) eof = true; }
-      return got;
-    }
-    while (got < n && !eof && !bad) {
-      pos = end = 0;
-      const int64_t k = pull(buf.data(), std::min<u64>(buf.size(), n - got));
-      if (k > 0) got += (u64)k;
-    }
-    return got;
-  }
-  // n bytes into dst: what the buffer holds first, then the callback directly; returns the bytes delivered (< n: the end)
-  u64 read_into(u8 *dst, u64 n) {
-    u64 got = std::min<u64>(n, avail());
-    memcpy(dst, ptr(), got);
-    pos += got;
-    while (got < n && !eof && !bad) {
-      const int64_t k = pull(dst + got, n - got);
-      if (k > 0) got += (u64)k;
-    }
-    return got;
-  }
-};
 
 struct Failure {
   int rc = SCALCE_OK;
@@ -146,6 +76,23 @@ struct Buckets {
   u8 header[12];
 };
 
+// the arithmetic decoder of one mate: batches of whole frames ahead of the windows.  Everything here is made by
+// setup_decoder() and goes with free_decoder(); the stream cursors and the window offsets are the Mate's
+struct AcDecoderDelete { void operator()(scalce_ac_decoder *d) const { scalce_ac_decoder_destroy(d); } };
+struct Decoder {
+  std::unique_ptr<scalce_ac_decoder, AcDecoderDelete> dec;
+  u64 G = 0, ycap = 0, coded_cap = 0;
+  DBuf Y[2], d_coded[2], d_off[2];
+  DBuf d_size[2];  // G sizes and the walk's verdict behind them
+  HBuf h_coded;
+  HBuf h_bad;      // one word per parity
+  Event ev_coded_up, ev_dec[2], ev_rec[2], t_dec0[2], t_dec1[2];
+  bool coded_up_once = false, rec_once[2] = {false, false};
+  u64 have_b[2] = {0, 0};     // symbols a batch buffer holds, carry included
+  int64_t enq = -1, cur = -1;  // last batch enqueued, batch being consumed
+  u64 pos = 0;                // consumed of the current batch
+};
+
 struct Mate {
   Src r, n, q;
   Src l;                     // the length stream of a variable-length archive (params len_rd), or not open
@@ -159,34 +106,32 @@ struct Mate {
   u64 range_left = UNKNOWN;  // records of the range not yet taken (UNKNOWN: the range runs to the archive's end)
   u64 drop = 0;              // symbols of the first batch that lie in front of the range's first record
   Buckets bk;
-  // the arithmetic decoder: batches of whole frames ahead of the windows
-  scalce_ac_decoder *dec = nullptr;
-  u64 frames_left = 0, syms_left = 0;
-  u64 G = 0, ycap = 0, coded_cap = 0;
-  u8 *Y[2] = {nullptr, nullptr}, *d_coded[2] = {nullptr, nullptr}, *h_coded = nullptr;
-  u64 *d_off[2] = {nullptr, nullptr};
-  u32 *d_size[2] = {nullptr, nullptr};  // G sizes and the walk's verdict behind them
-  u32 *h_bad = nullptr;                 // pinned, one word per parity
-  hipEvent_t ev_coded_up = nullptr, ev_dec[2] = {nullptr, nullptr}, ev_rec[2] = {nullptr, nullptr}, t_dec0[2] = {nullptr, nullptr},
-             t_dec1[2] = {nullptr, nullptr};
-  bool coded_up_once = false, rec_once[2] = {false, false};
-  u64 have_b[2] = {0, 0};     // symbols a batch buffer holds, carry included
-  int64_t enq = -1, cur = -1;  // last batch enqueued, batch being consumed
-  u64 pos = 0;                // consumed of the current batch
+  u64 frames_left = 0, syms_left = 0;  // of the coded quality stream, not yet handed to the decoder
+  Decoder d;
   // where this mate's parts of a window lie in the slot's input block
   u64 o_reads = 0, o_dir = 0, o_names = 0, o_noff = 0, o_qual = 0;
   u64 cap_slice = 0, cap_names = 0;
 };
 
 struct Slot {
-  u8 *h_in = nullptr, *d_in = nullptr, *h_text = nullptr, *d_text = nullptr;
-  u64 *h_roff = nullptr, *d_roff = nullptr;
+  HBuf h_in, h_text, h_roff;
+  DBuf d_in, d_text, d_roff;
   // variable-length archives: the window's entries of the length stream, and what strips the pad off its text
-  u8 *h_len = nullptr, *d_len = nullptr, *d_text2 = nullptr;
-  u64 *d_roff2 = nullptr;
-  void *d_scan = nullptr;
-  hipEvent_t ev_up = nullptr, ev_rec = nullptr, ev_done = nullptr, t_rec0 = nullptr, t_rec1 = nullptr;
+  HBuf h_len;
+  DBuf d_len, d_text2, d_roff2, d_scan;
+  Event ev_up, ev_rec, ev_done, t_rec0, t_rec1;
   bool busy = false;
+};
+
+// what the steps of one window share (run_pass)
+struct Window {
+  int si = 0;               // the slot it goes through
+  u64 n = 0, first = 0;     // records (pairs) it takes, and the index of the first
+  u64 nb[2] = {0, 0};       // per mate: bytes of names,
+  u32 ndir[2] = {0, 0};     // entries of the bucket directory
+  u64 slice[2] = {0, 0};    // and bytes of the read stream
+  u64 nbytes = 0, cut = 0;  // text that comes down; what the strip takes off it on the device
+  bool strip = false;
 };
 
 struct Job {
@@ -211,9 +156,13 @@ struct Session {
   std::thread writer;
   int device = 0;
 
+  // (the streams in front of what is used on them: close() lets everything go in the right order by hand, and should a
+  // session ever die without it, the buffers and events would still go before the streams)
+  Stream s_up, s_main, s_dec, s_down;
   Mate M[2];
   Slot slot[2];
-  hipStream_t s_up = nullptr, s_main = nullptr, s_dec = nullptr, s_down = nullptr;
+  int m0 = 0, m1 = 0;  // the mates of the pass that runs (one mate, or both under -i)
+  bool known = false;  // ... and whether a symbol count says how many records they hold
   bool names = false, qual = true;
   std::string library;
   u64 W = 0, R = 0, D = 0, cap_in = 0, cap_text = 0;
@@ -250,16 +199,24 @@ struct Session {
 #define SD_HIP(expr) do { if (int rc_ = hip((expr), #expr)) return rc_; } while (0)
 #define SD_TRY(expr) do { if (int rc_ = (expr)) return rc_; } while (0)
 
-  template <class T> int dmalloc(T **p, u64 bytes) {
-    SD_HIP(hipMalloc(reinterpret_cast<void **>(p), bytes));
-    live += bytes;
+  // a stream that ends, or fails, before what is asked of it (stream: 0 r, 1 n, 2 q, 3 l)
+  Src &src(int m, int stream) { return stream == 0 ? M[m].r : stream == 1 ? M[m].n : stream == 2 ? M[m].q : M[m].l; }
+  static const char *stream_name(int stream) { return stream == 0 ? "read" : stream == 1 ? "name" : stream == 2 ? "quality" : "length"; }
+  int read_error(int m, int stream) { return fail(SCALCE_ERR_FORMAT, m, stream, 0, "read error on the %s stream", stream_name(stream)); }
+  int truncated(int m, int stream) { return fail(SCALCE_ERR_FORMAT, m, stream, 0, "(ERROR) truncated %s stream", stream_name(stream)); }
+  int short_stream(int m, int stream) { return src(m, stream).bad ? read_error(m, stream) : truncated(m, stream); }
+
+  // device memory is counted where it comes and goes: `live` is the sum of the buffers' cap (and of the decoders' tables)
+  int dmalloc(DBuf &b, u64 bytes) {
+    SD_HIP(dbuf_alloc(b, bytes));
+    live += b.cap;
     S.peak_device_bytes = std::max(S.peak_device_bytes, live);
     return SCALCE_OK;
   }
-  template <class T> void dfree(T *&p, u64 bytes) { if (p) { hipFree(p); live -= bytes; p = nullptr; } }
-  template <class T> int hmalloc(T **p, u64 bytes) {
-    SD_HIP(hipHostMalloc(reinterpret_cast<void **>(p), bytes, hipHostMallocDefault));
-    S.pinned_host_bytes += bytes;
+  void drop(DBuf &b) { live -= b.cap; b.release(); }
+  int hmalloc(HBuf &b, u64 bytes) {
+    SD_HIP(b.alloc(bytes));
+    S.pinned_host_bytes += b.cap;
     return SCALCE_OK;
   }
 
@@ -277,26 +234,26 @@ struct Session {
       x.r.skip(8);
       int32_t v = 0;
       if (has_no_ac) {
-        if (!x.r.need(4)) return fail(SCALCE_ERR_FORMAT, m, 0, 0, "(ERROR) truncated read stream");
+        if (!x.r.need(4)) return truncated(m, 0);
         memcpy(&v, x.r.ptr(), 4); x.r.skip(4);
         x.no_ac = v;
       }
-      if (!x.r.need(4)) return fail(SCALCE_ERR_FORMAT, m, 0, 0, "(ERROR) truncated read stream");
+      if (!x.r.need(4)) return truncated(m, 0);
       memcpy(&v, x.r.ptr(), 4); x.r.skip(4);
       x.L = v;
       if (x.L <= 0) return fail(SCALCE_ERR_FORMAT, m, 0, 0, "(ERROR) read length %d in the read stream's header", x.L);
-      if (x.r.bad) return fail(SCALCE_ERR_FORMAT, m, 0, 0, "read error on the read stream");
+      if (x.r.bad) return read_error(m, 0);
       if (qual) {
         if (x.q.need(16)) { memcpy(&x.phred, x.q.ptr() + 8, 8); x.q.skip(16); } else x.q.skip(x.q.avail());
         x.q_empty = !x.q.need(1);
-        if (x.q.bad) return fail(SCALCE_ERR_FORMAT, m, 2, 0, "read error on the quality stream");
+        if (x.q.bad) return read_error(m, 2);
       }
       if (x.n.need(8)) x.n.skip(8);
       if (P.len_rd[m]) {  // the fourth stream: header, then one entry per record
         x.l.open(P.len_rd[m], P.len_skip[m], P.len_user[m], &S.read_wait_s, &x.l_delivered, &x.l_skipped);
         int hl = 0;
         const bool whole = x.l.need(scalce_host::LEN_HEADER_BYTES);
-        if (x.l.bad) return fail(SCALCE_ERR_FORMAT, m, 3, 0, "read error on the length stream");
+        if (x.l.bad) return read_error(m, 3);
         if (const char *why = scalce_host::len_header_read(x.l.ptr(), whole ? scalce_host::LEN_HEADER_BYTES : 0, &x.l_width, &hl))
           return fail(SCALCE_ERR_FORMAT, m, 3, 0, "(ERROR) %s", why);
         x.l.skip(scalce_host::LEN_HEADER_BYTES);
@@ -331,7 +288,7 @@ struct Session {
     Mate &x = M[m];
     while (!x.bk.left) {
       if (!x.r.need(12, look)) {
-        if (x.r.bad) { fail(SCALCE_ERR_FORMAT, m, 0, 0, "read error on the read stream"); return -1; }
+        if (x.r.bad) { read_error(m, 0); return -1; }
         return 1;
       }
       int32_t core;
@@ -371,7 +328,7 @@ struct Session {
   // with them every buffer -- depend on the window and the read length alone.
   u64 rec_budget(int m) const { return 2ull * (u64)M[m].L + 6; }
 
-  int setup_slots(int m0, int m1) {  // mates m0 .. m1 share a window (one mate, or both under -i)
+  int setup_slots() {  // mates m0 .. m1 share a window
     W = P.window_text_bytes ? P.window_text_bytes : SCALCE_WINDOW_TEXT_DEFAULT;
     S.window_text_bytes = W;
     u64 rec_min = 0, rec_max = 0;
@@ -379,6 +336,7 @@ struct Session {
     R = std::max<u64>(1, W / rec_min);
     D = std::min<u64>(R, (u64)scalce_patterns_count(ctx) + 2);
     cap_text = std::max(W, rec_max) + 64;
+    const u64 roff_bytes = 8 * (R + 1), len_bytes = 2 * R + 64;
     u64 o = 0;
     for (int m = m0; m <= m1; m++) {
       Mate &x = M[m];
@@ -389,50 +347,35 @@ struct Session {
       if (names) {
         x.cap_names = std::min(cap_text, R * 256);
         x.o_names = o; o = align_up(o + x.cap_names + 64, 256);
-        x.o_noff = o; o = align_up(o + 8 * (R + 1), 256);
+        x.o_noff = o; o = align_up(o + roff_bytes, 256);
       }
       if (qual && x.no_ac) { x.o_qual = o; o = align_up(o + R * (u64)x.L + 64, 256); }
     }
     cap_in = o;
     for (int i = 0; i < 2; i++) {
       Slot &s = slot[i];
-      SD_TRY(hmalloc(&s.h_in, cap_in));
-      SD_TRY(dmalloc(&s.d_in, cap_in));
-      SD_TRY(hmalloc(&s.h_text, cap_text));
-      SD_TRY(dmalloc(&s.d_text, cap_text));
+      SD_TRY(hmalloc(s.h_in, cap_in));
+      SD_TRY(dmalloc(s.d_in, cap_in));
+      SD_TRY(hmalloc(s.h_text, cap_text));
+      SD_TRY(dmalloc(s.d_text, cap_text));
       const bool strip = M[m0].has_len;  // (never with two mates in one window: -d -i refuses a length stream)
-      if (P.split) SD_TRY(hmalloc(&s.h_roff, 8 * (R + 1)));
-      if (P.split || strip) SD_TRY(dmalloc(&s.d_roff, 8 * (R + 1)));
+      if (P.split) SD_TRY(hmalloc(s.h_roff, roff_bytes));
+      if (P.split || strip) SD_TRY(dmalloc(s.d_roff, roff_bytes));
       if (strip) {
-        SD_TRY(hmalloc(&s.h_len, 2 * R + 64));
-        SD_TRY(dmalloc(&s.d_len, 2 * R + 64));
-        SD_TRY(dmalloc(&s.d_text2, cap_text));
-        SD_TRY(dmalloc(&s.d_roff2, 8 * (R + 1)));
-        SD_TRY(dmalloc(&s.d_scan, scalce_fastq_strip_ws_bytes(R)));
+        SD_TRY(hmalloc(s.h_len, len_bytes));
+        SD_TRY(dmalloc(s.d_len, len_bytes));
+        SD_TRY(dmalloc(s.d_text2, cap_text));
+        SD_TRY(dmalloc(s.d_roff2, roff_bytes));
+        SD_TRY(dmalloc(s.d_scan, scalce_fastq_strip_ws_bytes(R)));
       }
-      SD_HIP(hipEventCreateWithFlags(&s.ev_up, hipEventDisableTiming));
-      SD_HIP(hipEventCreateWithFlags(&s.ev_rec, hipEventDisableTiming));
-      SD_HIP(hipEventCreateWithFlags(&s.ev_done, hipEventDisableTiming));
-      SD_HIP(hipEventCreate(&s.t_rec0));
-      SD_HIP(hipEventCreate(&s.t_rec1));
+      for (Event *e : {&s.ev_up, &s.ev_rec, &s.ev_done}) SD_HIP(e->create());
+      for (Event *e : {&s.t_rec0, &s.t_rec1}) SD_HIP(e->create(true));  // these two are read for the kernels' time
     }
     return SCALCE_OK;
   }
   void free_slots() {
-    for (int i = 0; i < 2; i++) {
-      Slot &s = slot[i];
-      if (s.h_in) hipHostFree(s.h_in);
-      if (s.h_text) hipHostFree(s.h_text);
-      if (s.h_roff) hipHostFree(s.h_roff);
-      if (s.h_len) hipHostFree(s.h_len);
-      dfree(s.d_len, 2 * R + 64);
-      dfree(s.d_text2, cap_text);
-      dfree(s.d_roff2, 8 * (R + 1));
-      dfree(s.d_scan, scalce_fastq_strip_ws_bytes(R));
-      dfree(s.d_in, cap_in);
-      dfree(s.d_text, cap_text);
-      dfree(s.d_roff, 8 * (R + 1));
-      for (hipEvent_t e : {s.ev_up, s.ev_rec, s.ev_done, s.t_rec0, s.t_rec1}) if (e) hipEventDestroy(e);
+    for (Slot &s : slot) {
+      for (DBuf *b : {&s.d_len, &s.d_text2, &s.d_roff2, &s.d_scan, &s.d_in, &s.d_text, &s.d_roff}) drop(*b);
       s = Slot();
     }
   }
@@ -440,53 +383,45 @@ struct Session {
   // the quality stream behind its header: the table, the symbol count, then the frames -- and the decoder for them
   int setup_decoder(int m) {
     Mate &x = M[m];
+    Decoder &d = x.d;
     if (!qual || x.no_ac || x.q_empty) return SCALCE_OK;
     std::vector<u32> table(TABLE_BYTES / 4);
     if (x.q.read_into(reinterpret_cast<u8 *>(table.data()), TABLE_BYTES) != TABLE_BYTES) return fail(SCALCE_ERR_FORMAT, m, 2, 0, "(ERROR) truncated quality table");
-    if (!x.q.need(8)) return fail(SCALCE_ERR_FORMAT, m, 2, 0, "(ERROR) truncated quality stream");
+    if (!x.q.need(8)) return truncated(m, 2);
     memcpy(&x.total_syms, x.q.ptr(), 8);
     x.q.skip(8);
     x.records_left = x.total_syms / (u64)x.L;
     x.syms_left = x.total_syms;
     x.frames_left = (x.total_syms + FRAME - 1) / FRAME;
-    SD_TRY(lib(scalce_ac_decoder_create(ctx, table.data(), s_dec, &x.dec)));
-    live += scalce_ac_decoder_device_bytes(x.dec);
+    scalce_ac_decoder *dec = nullptr;
+    SD_TRY(lib(scalce_ac_decoder_create(ctx, table.data(), s_dec, &dec)));
+    d.dec.reset(dec);
+    live += scalce_ac_decoder_device_bytes(dec);
     S.peak_device_bytes = std::max(S.peak_device_bytes, live);
-    x.G = std::max<u64>(1, (SCALCE_DECODE_AHEAD * R * (u64)x.L + FRAME - 1) / FRAME);
-    x.ycap = (u64)x.L + x.G * FRAME + 256;
+    d.G = std::max<u64>(1, (SCALCE_DECODE_AHEAD * R * (u64)x.L + FRAME - 1) / FRAME);
+    d.ycap = (u64)x.L + d.G * FRAME + 256;
     // a frame of quality strings codes to a third of its symbols; a batch whose frames do not fit the staging is cut short
     // (at least one frame: a single frame larger than this is not an archive of this coder)
-    x.coded_cap = std::max<u64>(x.G * FRAME / 2, FRAME * 2) + 4096;
-    SD_TRY(hmalloc(&x.h_coded, x.coded_cap));
-    SD_TRY(hmalloc(&x.h_bad, 2 * sizeof(u32)));
-    SD_HIP(hipEventCreateWithFlags(&x.ev_coded_up, hipEventDisableTiming));
+    d.coded_cap = std::max<u64>(d.G * FRAME / 2, FRAME * 2) + 4096;
+    SD_TRY(hmalloc(d.h_coded, d.coded_cap));
+    SD_TRY(hmalloc(d.h_bad, 2 * sizeof(u32)));
+    SD_HIP(d.ev_coded_up.create());
     for (int i = 0; i < 2; i++) {
-      SD_TRY(dmalloc(&x.Y[i], x.ycap));
-      SD_TRY(dmalloc(&x.d_coded[i], x.coded_cap));
-      SD_TRY(dmalloc(&x.d_off[i], 8 * x.G));
-      SD_TRY(dmalloc(&x.d_size[i], 4 * (x.G + 1)));
-      SD_HIP(hipEventCreateWithFlags(&x.ev_dec[i], hipEventDisableTiming));
-      SD_HIP(hipEventCreateWithFlags(&x.ev_rec[i], hipEventDisableTiming));
-      SD_HIP(hipEventCreate(&x.t_dec0[i]));
-      SD_HIP(hipEventCreate(&x.t_dec1[i]));
+      SD_TRY(dmalloc(d.Y[i], d.ycap));
+      SD_TRY(dmalloc(d.d_coded[i], d.coded_cap));
+      SD_TRY(dmalloc(d.d_off[i], 8 * d.G));
+      SD_TRY(dmalloc(d.d_size[i], 4 * (d.G + 1)));
+      for (Event *e : {&d.ev_dec[i], &d.ev_rec[i]}) SD_HIP(e->create());
+      for (Event *e : {&d.t_dec0[i], &d.t_dec1[i]}) SD_HIP(e->create(true));  // (read for the decoder's time)
     }
     return SCALCE_OK;
   }
   void free_decoder(int m) {
-    Mate &x = M[m];
-    if (x.dec) { live -= scalce_ac_decoder_device_bytes(x.dec); scalce_ac_decoder_destroy(x.dec); x.dec = nullptr; }
-    if (x.h_coded) hipHostFree(x.h_coded);
-    if (x.h_bad) hipHostFree(x.h_bad);
-    x.h_coded = nullptr; x.h_bad = nullptr;
-    if (x.ev_coded_up) hipEventDestroy(x.ev_coded_up);
-    x.ev_coded_up = nullptr;
-    for (int i = 0; i < 2; i++) {
-      dfree(x.Y[i], x.ycap);
-      dfree(x.d_coded[i], x.coded_cap);
-      dfree(x.d_off[i], 8 * x.G);
-      dfree(x.d_size[i], 4 * (x.G + 1));
-      for (hipEvent_t *e : {&x.ev_dec[i], &x.ev_rec[i], &x.t_dec0[i], &x.t_dec1[i]}) { if (*e) hipEventDestroy(*e); *e = nullptr; }
-    }
+    Decoder &d = M[m].d;
+    if (d.dec) live -= scalce_ac_decoder_device_bytes(d.dec.get());
+    for (int i = 0; i < 2; i++)
+      for (DBuf *b : {&d.Y[i], &d.d_coded[i], &d.d_off[i], &d.d_size[i]}) drop(*b);
+    d = Decoder();
   }
 
   // ---- the decoder's batches ---------------------------------------------------------------------------------------------
@@ -495,45 +430,48 @@ struct Session {
   // when the windows of batch b - 2 have all been enqueued: their last records kernel is what the buffer waits for.
   int enqueue_batch(int m) {
     Mate &x = M[m];
+    Decoder &d = x.d;
     if (!x.frames_left) return SCALCE_OK;
-    const int64_t b = x.enq + 1;
+    const int64_t b = d.enq + 1;
     const int par = (int)(b & 1);
-    if (x.coded_up_once) SD_HIP(hipEventSynchronize(x.ev_coded_up));  // the staging's previous bytes have gone up
+    if (d.coded_up_once) SD_HIP(hipEventSynchronize(d.ev_coded_up));  // the staging's previous bytes have gone up
+    u8 *h_coded = d.h_coded.as<u8>(), *Y = d.Y[par].as<u8>();
+    u32 *d_size = d.d_size[par].as<u32>();
     u64 at = 0;
     u32 k = 0;
-    while (k < x.G && k < x.frames_left) {
-      if (!x.q.need(4)) return fail(SCALCE_ERR_FORMAT, m, 2, 0, "(ERROR) truncated quality stream");
+    while (k < d.G && k < x.frames_left) {
+      if (!x.q.need(4)) return truncated(m, 2);
       u32 sz;
       memcpy(&sz, x.q.ptr(), 4);
-      if (at + 4 + (u64)sz > x.coded_cap - 64) {
+      if (at + 4 + (u64)sz > d.coded_cap - 64) {
         if (k) break;
         return fail(SCALCE_ERR_FORMAT, m, 2, 0, "(ERROR) a coded block of %u bytes: not a quality stream of this coder", sz);
       }
-      memcpy(x.h_coded + at, &sz, 4);
+      memcpy(h_coded + at, &sz, 4);
       x.q.skip(4);
-      if (x.q.read_into(x.h_coded + at + 4, sz) != sz) return fail(SCALCE_ERR_FORMAT, m, 2, 0, "(ERROR) truncated quality stream");
+      if (x.q.read_into(h_coded + at + 4, sz) != sz) return truncated(m, 2);
       at += 4 + (u64)sz;
       k++;
     }
-    if (x.q.bad) return fail(SCALCE_ERR_FORMAT, m, 2, 0, "read error on the quality stream");
+    if (x.q.bad) return read_error(m, 2);
     const u64 nsym = std::min<u64>((u64)k * FRAME, x.syms_left);
     // (the first batch of a range begins with x.drop symbols of the records in front of it: they are left where they are
     // decoded and the windows begin behind them, so the carry counts from there)
-    const u64 carry = b ? (x.have_b[par ^ 1] - (b == 1 ? x.drop : 0)) % (u64)x.L : 0;
-    if (x.rec_once[par]) SD_HIP(hipStreamWaitEvent(s_dec, x.ev_rec[par], 0));
-    SD_HIP(hipMemcpyAsync(x.d_coded[par], x.h_coded, at, hipMemcpyHostToDevice, s_dec));
-    SD_HIP(hipEventRecord(x.ev_coded_up, s_dec));
-    x.coded_up_once = true;
-    if (carry) SD_HIP(hipMemcpyAsync(x.Y[par], x.Y[par ^ 1] + x.have_b[par ^ 1] - carry, carry, hipMemcpyDeviceToDevice, s_dec));
-    SD_HIP(hipEventRecord(x.t_dec0[par], s_dec));
-    SD_TRY(lib(scalce_ac_decoder_launch(x.dec, x.d_coded[par], at, k, nsym, x.d_off[par], x.d_size[par], x.d_size[par] + x.G, x.Y[par] + carry, s_dec)));
-    SD_HIP(hipEventRecord(x.t_dec1[par], s_dec));
-    SD_HIP(hipMemcpyAsync(&x.h_bad[par], x.d_size[par] + x.G, sizeof(u32), hipMemcpyDeviceToHost, s_dec));
-    SD_HIP(hipEventRecord(x.ev_dec[par], s_dec));
-    x.have_b[par] = carry + nsym;
+    const u64 carry = b ? (d.have_b[par ^ 1] - (b == 1 ? x.drop : 0)) % (u64)x.L : 0;
+    if (d.rec_once[par]) SD_HIP(hipStreamWaitEvent(s_dec, d.ev_rec[par], 0));
+    SD_HIP(hipMemcpyAsync(d.d_coded[par].p, h_coded, at, hipMemcpyHostToDevice, s_dec));
+    SD_HIP(hipEventRecord(d.ev_coded_up, s_dec));
+    d.coded_up_once = true;
+    if (carry) SD_HIP(hipMemcpyAsync(Y, d.Y[par ^ 1].as<u8>() + d.have_b[par ^ 1] - carry, carry, hipMemcpyDeviceToDevice, s_dec));
+    SD_HIP(hipEventRecord(d.t_dec0[par], s_dec));
+    SD_TRY(lib(scalce_ac_decoder_launch(d.dec.get(), d.d_coded[par].as<u8>(), at, k, nsym, d.d_off[par].as<u64>(), d_size, d_size + d.G, Y + carry, s_dec)));
+    SD_HIP(hipEventRecord(d.t_dec1[par], s_dec));
+    SD_HIP(hipMemcpyAsync(d.h_bad.as<u32>() + par, d_size + d.G, sizeof(u32), hipMemcpyDeviceToHost, s_dec));
+    SD_HIP(hipEventRecord(d.ev_dec[par], s_dec));
+    d.have_b[par] = carry + nsym;
     x.frames_left -= k;
     x.syms_left -= nsym;
-    x.enq = b;
+    d.enq = b;
     S.decode_batches[m]++;
     RS.frames_decoded[m] += k;
     RS.symbols_decoded[m] += nsym;
@@ -542,20 +480,21 @@ struct Session {
   // whole records of mate m that the decoded symbols still hold; moves on to the next batch when that is none
   int records_decoded(int m, u64 &n) {
     Mate &x = M[m];
+    Decoder &d = x.d;
     const u64 L = (u64)x.L;
     for (;;) {  // (a range's first batch may hold less than one record behind the symbols it drops: then the next one)
-      if (x.cur >= 0 && (x.have_b[x.cur & 1] - x.pos) / L) { n = (x.have_b[x.cur & 1] - x.pos) / L; return SCALCE_OK; }
-      if (x.cur == x.enq && !x.frames_left) { n = 0; return SCALCE_OK; }
-      if (x.enq == x.cur) SD_TRY(enqueue_batch(m));
-      x.cur++;
-      x.pos = x.cur ? 0 : x.drop;
+      if (d.cur >= 0 && (d.have_b[d.cur & 1] - d.pos) / L) { n = (d.have_b[d.cur & 1] - d.pos) / L; return SCALCE_OK; }
+      if (d.cur == d.enq && !x.frames_left) { n = 0; return SCALCE_OK; }
+      if (d.enq == d.cur) SD_TRY(enqueue_batch(m));
+      d.cur++;
+      d.pos = d.cur ? 0 : x.drop;
       SD_TRY(enqueue_batch(m));  // the batch behind it: decoded while this one's windows go through
-      const int par = (int)(x.cur & 1);
-      SD_HIP(hipEventSynchronize(x.ev_dec[par]));
+      const int par = (int)(d.cur & 1);
+      SD_HIP(hipEventSynchronize(d.ev_dec[par]));
       float ms = 0;
-      SD_HIP(hipEventElapsedTime(&ms, x.t_dec0[par], x.t_dec1[par]));
+      SD_HIP(hipEventElapsedTime(&ms, d.t_dec0[par], d.t_dec1[par]));
       S.decode_s += 1e-3 * ms;
-      if (x.h_bad[par]) return fail(SCALCE_ERR_FORMAT, m, 2, 0, "(ERROR) truncated quality stream");
+      if (d.h_bad.as<u32>()[par]) return truncated(m, 2);
     }
   }
 
@@ -580,7 +519,7 @@ struct Session {
         float ms = 0;
         if (hipEventElapsedTime(&ms, s.t_rec0, s.t_rec1) == hipSuccess) S.records_s += 1e-3 * ms;
         const double t0 = now_s();
-        if (wr(wr_user, j.mate, j.first, j.n, s.h_text, j.nbytes, P.split ? s.h_roff : nullptr)) fail(SCALCE_ERR_FORMAT, j.mate, -1, 0, "the write callback failed");
+        if (wr(wr_user, j.mate, j.first, j.n, s.h_text.as<u8>(), j.nbytes, P.split ? s.h_roff.as<u64>() : nullptr)) fail(SCALCE_ERR_FORMAT, j.mate, -1, 0, "the write callback failed");
         S.write_s += now_s() - t0;
         S.windows++;
       }
@@ -600,14 +539,32 @@ struct Session {
     cv.wait(lk, [&] { return (!slot[0].busy && !slot[1].busy) || failed.load(); });
   }
 
+  // ---- which stream says how many records there are ---------------------------------------------------------------------
+  // Where no symbol count says how many records the archive holds (`known`), the streams that end it for a whole run -- the
+  // names, else the raw quality rows, else the read stream, of the pass's first mate -- end it in front of a range too: a
+  // range that begins behind them is empty.  A short read on the stream that decides (0 r, 1 n, 2 q) ends the archive and is
+  // no error; any other stream that ends in front of the range, or inside a window, is truncated.
+  bool decides_count(int m, int stream) const {
+    if (known || m != m0) return false;
+    return stream == 1 || (!names && (stream == 2 || !(qual && M[m].no_ac)));
+  }
+  // does mate m's read stream hold another record (mate 2, which has no headers: another `least` bytes)?
+  int more_reads(int m, size_t least, bool &more) {
+    if (m != 0) { more = M[m].r.need(least); return SCALCE_OK; }
+    const int e = next_bucket(0);
+    more = e == 0;
+    return e < 0 ? F.rc : SCALCE_OK;
+  }
+
   // ---- one window --------------------------------------------------------------------------------------------------------
   // names of up to `ncap` records (pairs) into the slot, as many as the window's text takes; n = how many
-  int take_names(Slot &s, int m0, int m1, u64 ncap, bool known, u64 &n, u64 nb[2]) {
+  int take_names(Slot &s, u64 ncap, u64 &n, u64 nb[2]) {
     u64 text = 0;
     nb[0] = nb[1] = 0;
     n = 0;
-    u64 *noff[2] = {reinterpret_cast<u64 *>(s.h_in + M[m0].o_noff), reinterpret_cast<u64 *>(s.h_in + M[m1].o_noff)};
-    u8 *dst[2] = {s.h_in + M[m0].o_names, s.h_in + M[m1].o_names};
+    u8 *h_in = s.h_in.as<u8>();
+    u64 *noff[2] = {reinterpret_cast<u64 *>(h_in + M[m0].o_noff), reinterpret_cast<u64 *>(h_in + M[m1].o_noff)};
+    u8 *dst[2] = {h_in + M[m0].o_names, h_in + M[m1].o_names};
     const int nmates = m1 - m0 + 1;
     while (n < ncap) {
       u32 len[2] = {0, 0};
@@ -617,12 +574,12 @@ struct Session {
         Src &src = M[m0 + i].n;
         if (!src.need(1)) { ended++; continue; }
         len[i] = src.ptr()[0];
-        if (!src.need(1 + (size_t)len[i])) return fail(SCALCE_ERR_FORMAT, m0 + i, 1, 0, "(ERROR) truncated name stream");
+        if (!src.need(1 + (size_t)len[i])) return truncated(m0 + i, 1);
         rec += len[i] + rec_budget(m0 + i);
       }
       if (ended) {
-        for (int i = 0; i < nmates; i++) if (M[m0 + i].n.bad) return fail(SCALCE_ERR_FORMAT, m0 + i, 1, 0, "read error on the name stream");
-        if (known || ended != nmates) return fail(SCALCE_ERR_FORMAT, m0, 1, 0, "(ERROR) truncated name stream");
+        for (int i = 0; i < nmates; i++) if (M[m0 + i].n.bad) return read_error(m0 + i, 1);
+        if (!decides_count(m0, 1) || ended != nmates) return truncated(m0, 1);
         break;
       }
       if (n && text + rec > W) break;
@@ -645,15 +602,15 @@ struct Session {
   // n records of mate m's read stream into the slot; got < n: the stream has ended
   int take_reads(Slot &s, int m, u64 n, u64 &got, u32 &ndir, u64 &slice) {
     Mate &x = M[m];
-    u8 *dst = s.h_in + x.o_reads;
-    scalce_fq_bucket *dir = reinterpret_cast<scalce_fq_bucket *>(s.h_in + x.o_dir);
+    u8 *dst = s.h_in.as<u8>() + x.o_reads;
+    scalce_fq_bucket *dir = reinterpret_cast<scalce_fq_bucket *>(s.h_in.as<u8>() + x.o_dir);
     got = 0; ndir = 0; slice = 0;
     if (m != 0) {  // bare records in mate 1's order
       const u64 rb = (u64)(x.L + 3) / 4;
       const u64 bytes = x.r.read_into(dst, n * rb);
-      if (x.r.bad) return fail(SCALCE_ERR_FORMAT, m, 0, 0, "read error on the read stream");
+      if (x.r.bad) return read_error(m, 0);
       got = bytes / rb;
-      if (bytes % rb) return fail(SCALCE_ERR_FORMAT, m, 0, 0, "(ERROR) truncated read stream");
+      if (bytes % rb) return truncated(m, 0);
       memset(&dir[0], 0, sizeof dir[0]);
       dir[0].rec_bytes = (u32)rb;
       ndir = 1; slice = bytes;
@@ -669,7 +626,7 @@ struct Session {
       if (ndir == D) return fail(SCALCE_ERR_FORMAT, m, 0, 0, "(ERROR) the read stream opens more buckets than the core table has cores");
       const u64 t = std::min(x.bk.left, n - got), bytes = t * x.bk.rec_bytes;
       if (slice + bytes > x.cap_slice) return fail(SCALCE_ERR_FORMAT, m, 0, 0, "(ERROR) the read stream opens more buckets than the core table has cores");
-      if (x.r.read_into(dst + slice, bytes) != bytes) return fail(SCALCE_ERR_FORMAT, m, 0, 0, x.r.bad ? "read error on the read stream" : "(ERROR) truncated read stream");
+      if (x.r.read_into(dst + slice, bytes) != bytes) return short_stream(m, 0);
       scalce_fq_bucket &b = dir[ndir++];
       memset(&b, 0, sizeof b);
       b.first = got; b.off = slice; b.core_len = x.bk.core_len; b.rec_bytes = x.bk.rec_bytes;
@@ -680,11 +637,9 @@ struct Session {
   }
 
   // ---- the range: what lies in front of its first record is passed over, stream by stream -------------------------------
-  // Nothing of it reaches the device.  Where no symbol count says how many records the archive holds, the streams that end it
-  // for a whole run -- the names, else the raw quality rows, else the read stream -- end it here too: a range that begins
-  // behind them is empty.  Any other stream that ends in front of the range is truncated, as it is for a whole run.
-  int pass_over(int m0, int m1) {
-    const bool known = M[m0].records_left != UNKNOWN;
+  // Nothing of it reaches the device.  A stream that decides the record count (decides_count) may end in front of the range,
+  // which is empty then.
+  int pass_over() {
     u64 first = RG.first_record;
     if (known) { RS.total_records = M[m0].records_left; first = std::min(first, M[m0].records_left); }
     constexpr size_t LOOK = 64u << 10;  // read ahead of a bucket header when the bucket behind it is skipped, not read
@@ -694,12 +649,12 @@ struct Session {
         u64 k = 0;
         for (; k < first && src.need(1); k++) {
           const size_t len = src.ptr()[0];
-          if (!src.need(1 + len)) return fail(SCALCE_ERR_FORMAT, m, 1, 0, src.bad ? "read error on the name stream" : "(ERROR) truncated name stream");
+          if (!src.need(1 + len)) return short_stream(m, 1);
           src.skip(1 + len);
         }
-        if (src.bad) return fail(SCALCE_ERR_FORMAT, m, 1, 0, "read error on the name stream");
+        if (src.bad) return read_error(m, 1);
         if (k < first) {
-          if (known || m != m0) return fail(SCALCE_ERR_FORMAT, m, 1, 0, "(ERROR) truncated name stream");
+          if (!decides_count(m, 1)) return truncated(m, 1);
           first = k;
         }
       }
@@ -707,9 +662,9 @@ struct Session {
       Mate &x = M[m];
       if (!qual || !x.no_ac) continue;
       const u64 want = first * (u64)x.L, bytes = x.q.pass(want);
-      if (x.q.bad) return fail(SCALCE_ERR_FORMAT, m, 2, 0, "read error on the quality stream");
+      if (x.q.bad) return read_error(m, 2);
       if (bytes != want) {
-        if (known || names || m != m0 || bytes % (u64)x.L) return fail(SCALCE_ERR_FORMAT, m, 2, 0, "(ERROR) truncated quality stream");
+        if (!decides_count(m, 2) || bytes % (u64)x.L) return truncated(m, 2);
         first = bytes / (u64)x.L;
       }
     }
@@ -718,7 +673,7 @@ struct Session {
       u64 got = 0;
       if (m != 0) {
         const u64 rb = (u64)(x.L + 3) / 4, bytes = x.r.pass(first * rb);
-        if (bytes % rb && !x.r.bad) return fail(SCALCE_ERR_FORMAT, m, 0, 0, "(ERROR) truncated read stream");
+        if (bytes % rb && !x.r.bad) return truncated(m, 0);
         got = bytes / rb;
       } else {
         while (got < first) {  // bucket by bucket: every header is read and checked, the records behind it are not
@@ -728,27 +683,27 @@ struct Session {
             if (e) break;
           }
           const u64 t = std::min(x.bk.left, first - got), bytes = t * x.bk.rec_bytes;
-          if (x.r.pass(bytes) != bytes) return fail(SCALCE_ERR_FORMAT, m, 0, 0, x.r.bad ? "read error on the read stream" : "(ERROR) truncated read stream");
+          if (x.r.pass(bytes) != bytes) return short_stream(m, 0);
           got += t; x.bk.left -= t;
         }
       }
-      if (x.r.bad) return fail(SCALCE_ERR_FORMAT, m, 0, 0, "read error on the read stream");
+      if (x.r.bad) return read_error(m, 0);
       if (got != first) {
-        if (known || names || m != m0 || (qual && x.no_ac)) return fail(SCALCE_ERR_FORMAT, m, 0, 0, "(ERROR) truncated read stream");
+        if (!decides_count(m, 0)) return truncated(m, 0);
         first = got;
       }
     }
     for (int m = m0; m <= m1; m++) {  // coded qualities: whole frames by their size words, then the symbols in front of the record
       Mate &x = M[m];
-      if (!x.dec) continue;
+      if (!x.d.dec) continue;
       u64 pl[4];
       if (scalce_range_plan_quality(x.L, first, RG.nrecords, x.total_syms, pl)) return fail(SCALCE_ERR_ARG, m, 2, 0, "internal: the range's plan");
       for (u64 f = 0; f < pl[0]; f++) {
-        if (!x.q.need(4, x.q.skp ? 0 : ~(size_t)0)) return fail(SCALCE_ERR_FORMAT, m, 2, 0, x.q.bad ? "read error on the quality stream" : "(ERROR) truncated quality stream");
+        if (!x.q.need(4, x.q.skp ? 0 : ~(size_t)0)) return short_stream(m, 2);
         u32 sz;
         memcpy(&sz, x.q.ptr(), 4);
         x.q.skip(4);
-        if (x.q.pass(sz) != sz) return fail(SCALCE_ERR_FORMAT, m, 2, 0, x.q.bad ? "read error on the quality stream" : "(ERROR) truncated quality stream");
+        if (x.q.pass(sz) != sz) return short_stream(m, 2);
       }
       RS.frames_passed[m] = pl[0];
       x.frames_left = pl[1];
@@ -759,7 +714,7 @@ struct Session {
       Mate &x = M[m];
       if (!x.has_len) continue;
       const u64 want = first * (u64)x.l_width;
-      if (x.l.pass(want) != want) return fail(SCALCE_ERR_FORMAT, m, 3, 0, x.l.bad ? "read error on the length stream" : "(ERROR) truncated length stream");
+      if (x.l.pass(want) != want) return short_stream(m, 3);
     }
     for (int m = m0; m <= m1; m++) {
       Mate &x = M[m];
@@ -771,152 +726,185 @@ struct Session {
     return SCALCE_OK;
   }
 
-  // mates m0 .. m1 (one mate, or both under -i) from the range's first window to its last
-  int run_pass(int m0, int m1) {
+  // ---- the steps of a window, in the order run_pass() takes them ---------------------------------------------------------
+  // How many records: what the decoders hold, what the range and the archive leave, then what the text takes -- with names
+  // they come into the slot as they are counted, made-up names are bisected.  w.n stays 0: nothing is left
+  int window_records(Window &w) {
+    u64 ncap = std::min(R, std::min(M[m0].records_left, M[m0].range_left));
+    for (int m = m0; m <= m1 && ncap; m++)
+      if (M[m].d.dec) { u64 k; SD_TRY(records_decoded(m, k)); ncap = std::min(ncap, k); }
+    if (!ncap) return SCALCE_OK;
+    w.si = (int)(widx & 1);
+    if (!wait_slot(w.si)) return F.rc;
+    w.n = ncap;
+    w.first = M[m0].first;
+    if (names) return take_names(slot[w.si], ncap, w.n, w.nb);
+    auto text = [&](u64 k) { u64 t = 0; for (int m = m0; m <= m1; m++) t += lib_text(m, w.first, k, true); return t; };
+    if (text(w.n) > W) {
+      u64 lo = 1, hi = w.n;  // text(lo) fits (or lo = 1), text(hi) does not
+      while (hi - lo > 1) { const u64 mid = lo + (hi - lo) / 2; if (text(mid) <= W) lo = mid; else hi = mid; }
+      w.n = lo;
+    }
+    return SCALCE_OK;
+  }
+  // The pinned block from the other streams: raw quality rows, reads, length entries.  A stream that decides the record
+  // count may make the window shorter (w.n == 0: the archive ends here); then the text's size is known
+  int window_fill(Window &w) {
+    Slot &s = slot[w.si];
+    for (int m = m0; m <= m1 && w.n; m++) {  // -A: the q - offset rows as they are
+      Mate &x = M[m];
+      if (!qual || !x.no_ac) continue;
+      const u64 bytes = x.q.read_into(s.h_in.as<u8>() + x.o_qual, w.n * (u64)x.L);
+      if (x.q.bad) return read_error(m, 2);
+      if (bytes != w.n * (u64)x.L) {
+        if (!decides_count(m, 2) || bytes % (u64)x.L) return truncated(m, 2);
+        w.n = bytes / (u64)x.L;
+      }
+    }
+    for (int m = m0; m <= m1 && w.n; m++) {
+      u64 got = 0;
+      SD_TRY(take_reads(s, m, w.n, got, w.ndir[m - m0], w.slice[m - m0]));
+      if (got != w.n) {
+        if (!decides_count(m, 0)) return truncated(m, 0);
+        w.n = got;
+      }
+    }
+    if (!w.n) return SCALCE_OK;
+    // variable-length: the window's entries; their sum says how much shorter the text comes down than it is made
+    w.strip = M[m0].has_len;
+    if (w.strip) {
+      Mate &x = M[m0];
+      const u64 want = w.n * (u64)x.l_width;
+      if (x.l.read_into(s.h_len.as<u8>(), want) != want) return short_stream(m0, 3);
+      const u64 sum = scalce_host::len_entries_sum(s.h_len.as<u8>(), w.n, x.l_width, x.L);
+      if (sum == ~0ull) return fail(SCALCE_ERR_FORMAT, m0, 3, 0, "(ERROR) the length stream holds an entry above the read length %d", x.L);
+      w.cut = 2 * sum;
+    }
+    for (int m = m0; m <= m1; m++)
+      w.nbytes += names ? (qual ? scalce_fastq_text_bytes : scalce_fasta_text_bytes)(M[m].L, w.n, w.nb[m - m0], nullptr) : lib_text(m, w.first, w.n);
+    if (w.nbytes + 64 > cap_text) return fail(SCALCE_ERR_CAPACITY, -1, -1, 0, "internal: a window of %llu bytes of text", (unsigned long long)w.nbytes);
+    return SCALCE_OK;
+  }
+  int window_upload(const Window &w) {
+    Slot &s = slot[w.si];
+    u8 *h_in = s.h_in.as<u8>(), *d_in = s.d_in.as<u8>();
+    if (w.strip) SD_HIP(hipMemcpyAsync(s.d_len.p, s.h_len.p, w.n * (u64)M[m0].l_width, hipMemcpyHostToDevice, s_up));
+    for (int m = m0; m <= m1; m++) {
+      Mate &x = M[m];
+      const int i = m - m0;
+      SD_HIP(hipMemcpyAsync(d_in + x.o_reads, h_in + x.o_reads, w.slice[i], hipMemcpyHostToDevice, s_up));
+      SD_HIP(hipMemcpyAsync(d_in + x.o_dir, h_in + x.o_dir, sizeof(scalce_fq_bucket) * w.ndir[i], hipMemcpyHostToDevice, s_up));
+      if (names) {
+        SD_HIP(hipMemcpyAsync(d_in + x.o_names, h_in + x.o_names, w.nb[i], hipMemcpyHostToDevice, s_up));
+        SD_HIP(hipMemcpyAsync(d_in + x.o_noff, h_in + x.o_noff, 8 * (w.n + 1), hipMemcpyHostToDevice, s_up));
+      }
+      if (qual && x.no_ac) SD_HIP(hipMemcpyAsync(d_in + x.o_qual, h_in + x.o_qual, w.n * (u64)x.L, hipMemcpyHostToDevice, s_up));
+    }
+    SD_HIP(hipEventRecord(s.ev_up, s_up));
+    return SCALCE_OK;
+  }
+  // records -> text, mate by mate, behind the upload; then the pad goes (variable-length)
+  int window_launch(Window &w) {
+    Slot &s = slot[w.si];
+    u8 *d_in = s.d_in.as<u8>();
     const int nmates = m1 - m0 + 1;
+    SD_HIP(hipStreamWaitEvent(s_main, s.ev_up, 0));
+    SD_HIP(hipEventRecord(s.t_rec0, s_main));
+    for (int m = m0; m <= m1; m++) {
+      Mate &x = M[m];
+      Decoder &d = x.d;
+      scalce_fq_window fw;
+      memset(&fw, 0, sizeof fw);
+      fw.d_reads = d_in + x.o_reads;
+      fw.d_dir = reinterpret_cast<const scalce_fq_bucket *>(d_in + x.o_dir);
+      fw.nbuckets = w.ndir[m - m0];
+      fw.read_len = x.L; fw.has_buckets = m == 0; fw.mate_digit = P.mate_digit ? '1' + m : 0;
+      fw.nrecords = w.n; fw.first_record = w.first;
+      if (qual) fw.d_qual = x.no_ac ? d_in + x.o_qual : d.Y[d.cur & 1].as<u8>() + d.pos;
+      fw.phred_offset = x.phred;
+      if (names) { fw.d_names = d_in + x.o_names; fw.d_name_off = reinterpret_cast<const u64 *>(d_in + x.o_noff); }
+      fw.library = library.c_str();
+      fw.d_out = s.d_text.as<u8>();
+      fw.d_record_offsets = ((P.split || w.strip) && m == m0) ? s.d_roff.as<u64>() : nullptr;
+      if (nmates == 2) {
+        const Mate &y = M[m == m0 ? m1 : m0];
+        fw.interleave = m - m0 + 1; fw.pair_read_len = y.L;
+        if (names) fw.d_pair_name_off = reinterpret_cast<const u64 *>(d_in + y.o_noff);
+      }
+      SD_TRY(lib(scalce_fastq_records_window(ctx, &fw, s_main)));
+      if (d.dec) {
+        SD_HIP(hipEventRecord(d.ev_rec[d.cur & 1], s_main));
+        d.rec_once[d.cur & 1] = true;
+        d.pos += w.n * (u64)x.L;
+      }
+    }
+    if (w.strip) {  // the text and its record offsets come down from the stripped copy
+      SD_TRY(lib(scalce_fastq_strip_window(ctx, M[m0].L, w.n, s.d_text.as<u8>(), s.d_roff.as<u64>(), s.d_len.as<u8>(), M[m0].l_width,
+                                           s.d_text2.as<u8>(), s.d_roff2.as<u64>(), s.d_scan.p, s_main)));
+      w.nbytes -= w.cut;
+    }
+    SD_HIP(hipEventRecord(s.t_rec1, s_main));
+    SD_HIP(hipEventRecord(s.ev_rec, s_main));
+    return SCALCE_OK;
+  }
+  // the text comes down behind the kernels; the writer gets the window
+  int window_download(const Window &w) {
+    Slot &s = slot[w.si];
+    SD_HIP(hipStreamWaitEvent(s_down, s.ev_rec, 0));
+    SD_HIP(hipMemcpyAsync(s.h_text.p, w.strip ? s.d_text2.p : s.d_text.p, w.nbytes, hipMemcpyDeviceToHost, s_down));
+    if (P.split) SD_HIP(hipMemcpyAsync(s.h_roff.p, w.strip ? s.d_roff2.p : s.d_roff.p, 8 * (w.n + 1), hipMemcpyDeviceToHost, s_down));
+    SD_HIP(hipEventRecord(s.ev_done, s_down));
+    {
+      std::lock_guard<std::mutex> lk(mu);
+      s.busy = true;
+      jobs.push_back(Job{w.si, m1 > m0 ? 0 : m0, w.first, w.n, w.nbytes});
+    }
+    cv.notify_all();
+    return SCALCE_OK;
+  }
+  void window_advance(const Window &w) {
+    widx++;
+    for (int m = m0; m <= m1; m++) {
+      M[m].first += w.n;
+      if (M[m].records_left != UNKNOWN) M[m].records_left -= w.n;
+      if (M[m].range_left != UNKNOWN) M[m].range_left -= w.n;
+      S.records[m] += w.n;
+    }
+  }
+  // What is left of the read streams holds no record -- where the range ends with the archive: behind a range that ends
+  // sooner nothing is read, and a stream that is cut short there is not noticed
+  int check_end() {
+    if (M[m0].range_left == 0 && M[m0].records_left != 0) return SCALCE_OK;
+    for (int m = m0; m <= m1; m++) {
+      bool more = false;
+      SD_TRY(more_reads(m, (size_t)(M[m].L + 3) / 4, more));
+      if (more) return fail(SCALCE_ERR_FORMAT, m, 0, 0, "(ERROR) the read stream holds more than the %llu records of the %s stream",
+                            (unsigned long long)M[m].first, names ? "name" : "quality");
+    }
+    return SCALCE_OK;
+  }
+
+  // mates m0 .. m1 (one mate, or both under -i) from the range's first window to its last
+  int run_pass() {
     for (int m = m0; m <= m1; m++) SD_TRY(setup_decoder(m));
-    if (nmates == 2 && M[m0].records_left != M[m1].records_left)
+    if (m1 > m0 && M[m0].records_left != M[m1].records_left)
       return fail(SCALCE_ERR_FORMAT, -1, -1, 0, "(ERROR) the mates hold %llu and %llu records", (unsigned long long)M[m0].records_left,
                   (unsigned long long)M[m1].records_left);
-    const bool known = M[m0].records_left != UNKNOWN;
-    SD_TRY(pass_over(m0, m1));
+    known = M[m0].records_left != UNKNOWN;
+    SD_TRY(pass_over());
     for (;;) {
       if (failed) return F.rc;
-      u64 ncap = std::min(R, std::min(M[m0].records_left, M[m0].range_left));
-      for (int m = m0; m <= m1 && ncap; m++)
-        if (M[m].dec) { u64 k; SD_TRY(records_decoded(m, k)); ncap = std::min(ncap, k); }
-      if (!ncap) break;
-      const int si = (int)(widx & 1);
-      Slot &s = slot[si];
-      if (!wait_slot(si)) return F.rc;
-      // how many records: what the text takes, then what the streams hold
-      u64 n = ncap, nb[2] = {0, 0};
-      const u64 first = M[m0].first;
-      if (names) SD_TRY(take_names(s, m0, m1, ncap, known, n, nb));
-      else {
-        auto text = [&](u64 k) { u64 t = 0; for (int m = m0; m <= m1; m++) t += lib_text(m, first, k, true); return t; };
-        if (text(n) > W) {
-          u64 lo = 1, hi = n;  // text(lo) fits (or lo = 1), text(hi) does not
-          while (hi - lo > 1) { const u64 mid = lo + (hi - lo) / 2; if (text(mid) <= W) lo = mid; else hi = mid; }
-          n = lo;
-        }
-      }
-      for (int m = m0; m <= m1 && n; m++) {  // -A: the q - offset rows as they are
-        Mate &x = M[m];
-        if (!qual || !x.no_ac) continue;
-        const u64 bytes = x.q.read_into(s.h_in + x.o_qual, n * (u64)x.L);
-        if (x.q.bad) return fail(SCALCE_ERR_FORMAT, m, 2, 0, "read error on the quality stream");
-        if (bytes != n * (u64)x.L) {
-          if (names || m != m0 || bytes % (u64)x.L) return fail(SCALCE_ERR_FORMAT, m, 2, 0, "(ERROR) truncated quality stream");
-          n = bytes / (u64)x.L;  // made-up names: this stream says how many records there are
-        }
-      }
-      u32 ndir[2] = {0, 0};
-      u64 slice[2] = {0, 0};
-      for (int m = m0; m <= m1 && n; m++) {
-        u64 got = 0;
-        SD_TRY(take_reads(s, m, n, got, ndir[m - m0], slice[m - m0]));
-        if (got != n) {
-          if (known || names || m != m0 || (qual && M[m].no_ac)) return fail(SCALCE_ERR_FORMAT, m, 0, 0, "(ERROR) truncated read stream");
-          n = got;  // no qualities, made-up names: the read stream says how many records there are
-        }
-      }
-      if (!n) break;
-      // variable-length: the window's entries; their sum says how much shorter the text comes down than it is made
-      const bool strip = M[m0].has_len;
-      u64 cut = 0;
-      if (strip) {
-        Mate &x = M[m0];
-        const u64 want = n * (u64)x.l_width;
-        if (x.l.read_into(s.h_len, want) != want)
-          return fail(SCALCE_ERR_FORMAT, m0, 3, 0, x.l.bad ? "read error on the length stream" : "(ERROR) truncated length stream");
-        const u64 sum = scalce_host::len_entries_sum(s.h_len, n, x.l_width, x.L);
-        if (sum == ~0ull) return fail(SCALCE_ERR_FORMAT, m0, 3, 0, "(ERROR) the length stream holds an entry above the read length %d", x.L);
-        cut = 2 * sum;
-        SD_HIP(hipMemcpyAsync(s.d_len, s.h_len, want, hipMemcpyHostToDevice, s_up));
-      }
-      // up, records -> text, down
-      u64 nbytes = 0;
-      for (int m = m0; m <= m1; m++)
-        nbytes += names ? (qual ? scalce_fastq_text_bytes : scalce_fasta_text_bytes)(M[m].L, n, nb[m - m0], nullptr) : lib_text(m, first, n);
-      if (nbytes + 64 > cap_text) return fail(SCALCE_ERR_CAPACITY, -1, -1, 0, "internal: a window of %llu bytes of text", (unsigned long long)nbytes);
-      for (int m = m0; m <= m1; m++) {
-        Mate &x = M[m];
-        const int i = m - m0;
-        SD_HIP(hipMemcpyAsync(s.d_in + x.o_reads, s.h_in + x.o_reads, slice[i], hipMemcpyHostToDevice, s_up));
-        SD_HIP(hipMemcpyAsync(s.d_in + x.o_dir, s.h_in + x.o_dir, sizeof(scalce_fq_bucket) * ndir[i], hipMemcpyHostToDevice, s_up));
-        if (names) {
-          SD_HIP(hipMemcpyAsync(s.d_in + x.o_names, s.h_in + x.o_names, nb[i], hipMemcpyHostToDevice, s_up));
-          SD_HIP(hipMemcpyAsync(s.d_in + x.o_noff, s.h_in + x.o_noff, 8 * (n + 1), hipMemcpyHostToDevice, s_up));
-        }
-        if (qual && x.no_ac) SD_HIP(hipMemcpyAsync(s.d_in + x.o_qual, s.h_in + x.o_qual, n * (u64)x.L, hipMemcpyHostToDevice, s_up));
-      }
-      SD_HIP(hipEventRecord(s.ev_up, s_up));
-      SD_HIP(hipStreamWaitEvent(s_main, s.ev_up, 0));
-      SD_HIP(hipEventRecord(s.t_rec0, s_main));
-      for (int m = m0; m <= m1; m++) {
-        Mate &x = M[m];
-        scalce_fq_window w;
-        memset(&w, 0, sizeof w);
-        w.d_reads = s.d_in + x.o_reads;
-        w.d_dir = reinterpret_cast<const scalce_fq_bucket *>(s.d_in + x.o_dir);
-        w.nbuckets = ndir[m - m0];
-        w.read_len = x.L; w.has_buckets = m == 0; w.mate_digit = P.mate_digit ? '1' + m : 0;
-        w.nrecords = n; w.first_record = first;
-        if (qual) w.d_qual = x.no_ac ? s.d_in + x.o_qual : x.Y[x.cur & 1] + x.pos;
-        w.phred_offset = x.phred;
-        if (names) { w.d_names = s.d_in + x.o_names; w.d_name_off = reinterpret_cast<const u64 *>(s.d_in + x.o_noff); }
-        w.library = library.c_str();
-        w.d_out = s.d_text;
-        w.d_record_offsets = ((P.split || strip) && m == m0) ? s.d_roff : nullptr;
-        if (nmates == 2) {
-          const Mate &y = M[m == m0 ? m1 : m0];
-          w.interleave = m - m0 + 1; w.pair_read_len = y.L;
-          if (names) w.d_pair_name_off = reinterpret_cast<const u64 *>(s.d_in + y.o_noff);
-        }
-        SD_TRY(lib(scalce_fastq_records_window(ctx, &w, s_main)));
-        if (x.dec) {
-          SD_HIP(hipEventRecord(x.ev_rec[x.cur & 1], s_main));
-          x.rec_once[x.cur & 1] = true;
-          x.pos += n * (u64)x.L;
-        }
-      }
-      if (strip) {  // the pad goes: the text and its record offsets come down from the stripped copy
-        SD_TRY(lib(scalce_fastq_strip_window(ctx, M[m0].L, n, s.d_text, s.d_roff, s.d_len, M[m0].l_width, s.d_text2, s.d_roff2, s.d_scan, s_main)));
-        nbytes -= cut;
-      }
-      SD_HIP(hipEventRecord(s.t_rec1, s_main));
-      SD_HIP(hipEventRecord(s.ev_rec, s_main));
-      SD_HIP(hipStreamWaitEvent(s_down, s.ev_rec, 0));
-      SD_HIP(hipMemcpyAsync(s.h_text, strip ? s.d_text2 : s.d_text, nbytes, hipMemcpyDeviceToHost, s_down));
-      if (P.split) SD_HIP(hipMemcpyAsync(s.h_roff, strip ? s.d_roff2 : s.d_roff, 8 * (n + 1), hipMemcpyDeviceToHost, s_down));
-      SD_HIP(hipEventRecord(s.ev_done, s_down));
-      {
-        std::lock_guard<std::mutex> lk(mu);
-        s.busy = true;
-        jobs.push_back(Job{si, nmates == 2 ? 0 : m0, first, n, nbytes});
-      }
-      cv.notify_all();
-      widx++;
-      for (int m = m0; m <= m1; m++) {
-        M[m].first += n;
-        if (M[m].records_left != UNKNOWN) M[m].records_left -= n;
-        if (M[m].range_left != UNKNOWN) M[m].range_left -= n;
-        S.records[m] += n;
-      }
+      Window w;
+      SD_TRY(window_records(w));
+      if (w.n) SD_TRY(window_fill(w));
+      if (!w.n) break;
+      SD_TRY(window_upload(w));
+      SD_TRY(window_launch(w));
+      SD_TRY(window_download(w));
+      window_advance(w);
     }
     RS.nrecords = S.records[m0];
-    // what is left of the read streams holds no record -- where the range ends with the archive: behind a range that ends
-    // sooner nothing is read, and a stream that is cut short there is not noticed
-    const bool to_end = M[m0].range_left != 0 || M[m0].records_left == 0;
-    for (int m = m0; m <= m1 && to_end; m++) {
-      Mate &x = M[m];
-      bool more = false;
-      if (m == 0) { const int e = x.bk.left ? 0 : next_bucket(m); if (e < 0) return F.rc; more = e == 0; }
-      else more = x.r.need((size_t)(x.L + 3) / 4);
-      if (more) return fail(SCALCE_ERR_FORMAT, m, 0, 0, "(ERROR) the read stream holds more than the %llu records of the %s stream",
-                            (unsigned long long)x.first, names ? "name" : "quality");
-    }
+    SD_TRY(check_end());
     drain();
     if (failed) return F.rc;
     for (int m = m0; m <= m1; m++) free_decoder(m);
@@ -932,23 +920,20 @@ struct Session {
     for (int m = 0; m < P.mates && qual; m++)
       if (M[m].q_empty) {
         bool has = false;
-        if (m == 0) { const int e = next_bucket(0); if (e < 0) return F.rc; has = e == 0; }
-        else has = M[m].r.need(1);
+        SD_TRY(more_reads(m, 1, has));
         if (has) return fail(SCALCE_ERR_FORMAT, m, 2, 1, "holds no qualities: the archive was made with -Q or -f; decompress it with -Q");
         M[m].records_left = 0;
       }
-    SD_HIP(hipStreamCreateWithFlags(&s_up, hipStreamNonBlocking));
-    SD_HIP(hipStreamCreateWithFlags(&s_main, hipStreamNonBlocking));
-    SD_HIP(hipStreamCreateWithFlags(&s_dec, hipStreamNonBlocking));
-    SD_HIP(hipStreamCreateWithFlags(&s_down, hipStreamNonBlocking));
+    for (Stream *s : {&s_up, &s_main, &s_dec, &s_down}) SD_HIP(s->create());
     writer = std::thread([this] { writer_main(); });
     const bool together = P.mates == 2 && P.interleave;
     for (int m = 0; m < P.mates; m += together ? 2 : 1) {
-      const int m1 = together ? 1 : m;
+      m0 = m;
+      m1 = together ? 1 : m;
       const double ts = now_s();
-      int rc = setup_slots(m, m1);
+      int rc = setup_slots();
       S.setup_s += now_s() - ts;
-      if (!rc) rc = run_pass(m, m1);
+      if (!rc) rc = run_pass();
       if (rc) return rc;
       drain();
       free_slots();
@@ -957,15 +942,17 @@ struct Session {
     return SCALCE_OK;
   }
 
+  // The order in which everything goes: the writer is joined (it waits on the slots' events and reads their pinned text), then
+  // every stream is synchronised (whatever is still on its way ends before the buffers go), then the buffers and events, and
+  // the streams last.
   void close() {
     { std::lock_guard<std::mutex> lk(mu); closing = true; }
     cv.notify_all();
     if (writer.joinable()) writer.join();
-    // whatever is still on its way ends before the buffers go
-    for (hipStream_t s : {s_up, s_main, s_dec, s_down}) if (s) (void)hipStreamSynchronize(s);
+    for (Stream *s : {&s_up, &s_main, &s_dec, &s_down}) if (s->s) (void)hipStreamSynchronize(*s);
     for (int m = 0; m < 2; m++) free_decoder(m);
     free_slots();
-    for (hipStream_t s : {s_up, s_main, s_dec, s_down}) if (s) hipStreamDestroy(s);
+    for (Stream *s : {&s_up, &s_main, &s_dec, &s_down}) s->release();
   }
 };
 

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../include/scalce_hip.h"
+#include "hip_own.hpp"
 
 namespace {
 
@@ -95,31 +96,161 @@ void reader_main(ChunkRing *ring, scalce_read_fn rd, void *user, uint64_t piece)
 struct Mate {
   ChunkRing ring;
   std::thread reader;
-  std::vector<uint8_t *> pinned;
+  std::vector<HBuf> pinned;  // (the ring's chunks: they go only after the reader has been joined)
   // the piece handed to the batch: [tail of the previous piece][new chunks]; two buffers, so that the tail moves to the
   // front of the OTHER one (no overlapping copy)
-  uint8_t *d_text[2] = {nullptr, nullptr};
+  DBuf d_text[2];
   int cur = 0;
   uint64_t have = 0;              // bytes of d_text[cur] in use
   // chunks on their way up: a queue of at most two, slot = index & 1
-  uint8_t *d_raw[2] = {nullptr, nullptr};
+  DBuf d_raw[2];
   uint64_t raw_n[2] = {0, 0};
-  hipEvent_t up_ev[2] = {nullptr, nullptr};    // the chunk has arrived in d_raw[slot]
-  hipEvent_t land_ev[2] = {nullptr, nullptr};  // ... and has been copied behind the tail: the slot may be overwritten
+  Event up_ev[2];    // the chunk has arrived in d_raw[slot]
+  Event land_ev[2];  // ... and has been copied behind the tail: the slot may be overwritten
   bool landed_once[2] = {false, false};
   ChunkRing::Chunk raw_chunk[2];
   uint64_t head = 0, tail = 0;    // queue of chunks in d_raw: [head, tail)
   bool eof = false;               // the stream's last chunk has been taken from the ring
   bool all_landed() const { return eof && head == tail; }
+  uint8_t *text() const { return d_text[cur].as<uint8_t>(); }
 };
 
-}  // namespace
-
-#define ST_HIP(expr)                                                                              \
-  do {                                                                                            \
-    hipError_t e_ = (expr);                                                                       \
-    if (e_ != hipSuccess) { err = std::string(#expr) + ": " + hipGetErrorString(e_); goto fail; } \
+#define ST_HIP(expr)                                                                                              \
+  do {                                                                                                            \
+    hipError_t e_ = (expr);                                                                                       \
+    if (e_ != hipSuccess) { err = std::string(#expr) + ": " + hipGetErrorString(e_); return SCALCE_ERR_HIP; }     \
   } while (0)
+
+// The run itself.  Whatever it returns, the caller joins the readers, lets the buffers, events and streams go and, on an
+// error, puts `err` into errbuf and destroys the batch: nothing is cleaned up in here.
+int stream_run(scalce_ctx *ctx, const scalce_params *p, scalce_read_fn rd[2], void *user[2], int nm, uint64_t piece, uint64_t reads_hint,
+               int flags, Stream &s_copy, Stream &s_main, Mate M[2], scalce_batch *&b, scalce_stream_stats &S, std::string &err) {
+  const int NPIN = 3;
+  const uint64_t cap = 2 * piece;  // of a piece: the tail of the previous one plus one chunk
+  int rc = SCALCE_OK;
+  ST_HIP(s_copy.create());
+  ST_HIP(s_main.create());
+  for (int m = 0; m < nm; m++) {
+    for (int i = 0; i < NPIN; i++) {
+      M[m].pinned.emplace_back();
+      ST_HIP(M[m].pinned.back().alloc(piece));
+      ChunkRing::Chunk c;
+      c.p = M[m].pinned.back().as<uint8_t>();
+      M[m].ring.free_.push_back(c);
+    }
+    for (int i = 0; i < 2; i++) {
+      ST_HIP(dbuf_alloc(M[m].d_text[i], cap + 256));
+      ST_HIP(dbuf_alloc(M[m].d_raw[i], piece + 256));
+      ST_HIP(M[m].up_ev[i].create());
+      ST_HIP(M[m].land_ev[i].create());
+    }
+  }
+  {
+    const uint64_t rec_min = p->fasta ? (uint64_t)p->read_len[0] + 4 : 2 * (uint64_t)p->read_len[0] + 7;  // (">x", bases, two newlines)
+    const uint64_t rows0 = reads_hint ? reads_hint + 16 : piece / rec_min + 16;
+    rc = scalce_batch_create(ctx, p, rows0, cap + 256, &b);
+    if (rc) { err = scalce_last_error(ctx); return rc; }
+    scalce_batch_set_lean(b, (flags & SCALCE_STREAM_LEAN) ? 1 : 0);
+  }
+  for (int m = 0; m < nm; m++) M[m].reader = std::thread(reader_main, &M[m].ring, rd[m], user[m], piece);
+
+  // one more chunk of every mate that has input left and a free slot starts its way up
+  auto upload = [&]() -> int {
+    for (int m = 0; m < nm; m++) {
+      Mate &x = M[m];
+      if (x.eof || x.tail - x.head >= 2) continue;
+      const int sl = (int)(x.tail & 1);
+      ChunkRing::Chunk c;
+      const double t0 = now_s();
+      if (!x.ring.take_full(c)) { err = x.ring.error; return SCALCE_ERR_FORMAT; }
+      S.read_wait_s += now_s() - t0;
+      if (c.last) x.eof = true;
+      x.raw_chunk[sl] = c;
+      x.raw_n[sl] = c.n;
+      // the slot's previous chunk must have left for d_text before this one lands on it
+      if (x.landed_once[sl] && hipStreamWaitEvent(s_copy, x.land_ev[sl], 0) != hipSuccess) { err = "hipStreamWaitEvent failed"; return SCALCE_ERR_HIP; }
+      if (c.n && hipMemcpyAsync(x.d_raw[sl].p, c.p, c.n, hipMemcpyHostToDevice, s_copy) != hipSuccess) { err = "hipMemcpyAsync (chunk upload) failed"; return SCALCE_ERR_HIP; }
+      if (hipEventRecord(x.up_ev[sl], s_copy) != hipSuccess) { err = "hipEventRecord failed"; return SCALCE_ERR_HIP; }
+      x.tail++;
+      S.bytes[m] += c.n;
+    }
+    return SCALCE_OK;
+  };
+  // chunks that have arrived go behind the tail in d_text while the piece is short of `piece` bytes and they fit;
+  // their pinned buffers return to the reader
+  int landed = 0;
+  auto land = [&]() -> int {
+    landed = 0;
+    for (int m = 0; m < nm; m++) {
+      Mate &x = M[m];
+      while (x.head < x.tail && x.have < piece && x.have + x.raw_n[x.head & 1] <= cap) {
+        const int sl = (int)(x.head & 1);
+        const double t0 = now_s();
+        if (hipEventSynchronize(x.up_ev[sl]) != hipSuccess) { err = "chunk upload failed"; return SCALCE_ERR_HIP; }
+        S.h2d_wait_s += now_s() - t0;
+        if (x.raw_n[sl] && hipMemcpyAsync(x.text() + x.have, x.d_raw[sl].p, x.raw_n[sl], hipMemcpyDeviceToDevice, s_main) != hipSuccess) {
+          err = "hipMemcpyAsync (piece assembly) failed";
+          return SCALCE_ERR_HIP;
+        }
+        if (hipEventRecord(x.land_ev[sl], s_main) != hipSuccess) { err = "hipEventRecord failed"; return SCALCE_ERR_HIP; }
+        x.landed_once[sl] = true;
+        x.have += x.raw_n[sl];
+        x.ring.put_free(x.raw_chunk[sl]);
+        x.head++;
+        landed++;
+      }
+    }
+    return SCALCE_OK;
+  };
+
+  if ((rc = upload())) return rc;
+  for (;;) {
+    if ((rc = land())) return rc;
+    if ((rc = upload())) return rc;  // travels while this piece is worked on
+    bool final_piece = true;
+    for (int m = 0; m < nm; m++) final_piece = final_piece && M[m].all_landed();
+    uint64_t used[2] = {0, 0};
+    const double t0 = now_s();
+    rc = scalce_batch_append(b, M[0].text(), M[0].have, nm == 2 ? M[1].text() : nullptr, nm == 2 ? M[1].have : 0, final_piece ? 1 : 0, used, s_main);
+    S.front_s += now_s() - t0;
+    if (rc) { err = scalce_last_error(ctx); return rc; }
+    S.rounds++;
+    bool progress = landed > 0;
+    for (int m = 0; m < nm; m++) {
+      Mate &x = M[m];
+      if (used[m] > x.have) { err = "internal: consumed more than the piece"; return SCALCE_ERR_ARG; }
+      progress = progress || used[m] > 0;
+      const uint64_t rest = x.have - used[m];
+      if (rest && used[m]) {  // the unconsumed tail opens the next piece
+        ST_HIP(hipMemcpyAsync(x.d_text[x.cur ^ 1].p, x.text() + used[m], rest, hipMemcpyDeviceToDevice, s_main));
+        x.cur ^= 1;
+      }
+      x.have = rest;
+    }
+    if (final_piece) break;
+    if (!progress) {
+      err = "(ERROR) a record does not fit one piece of the stream, or the mates have different record counts";
+      return SCALCE_ERR_FORMAT;
+    }
+  }
+  double t0 = now_s();
+  if ((rc = scalce_batch_order(b, s_main)) || (rc = scalce_batch_finish(b, s_main))) { err = scalce_last_error(ctx); return rc; }
+  S.order_s = now_s() - t0;
+  // the staging buffers are dead: give them back before the emit stage allocates the streams
+  for (int m = 0; m < nm; m++)
+    for (int i = 0; i < 2; i++) { M[m].d_text[i].release(); M[m].d_raw[i].release(); }
+  t0 = now_s();
+  if ((rc = scalce_batch_emit(b, s_main)) || (rc = scalce_batch_finish(b, s_main))) { err = scalce_last_error(ctx); return rc; }
+  S.emit_s = now_s() - t0;
+  if (!(flags & SCALCE_STREAM_DEFER_ENTROPY)) {
+    t0 = now_s();
+    if ((rc = scalce_batch_entropy(b, nullptr, s_main)) || (rc = scalce_batch_finish(b, s_main))) { err = scalce_last_error(ctx); return rc; }
+    S.entropy_s = now_s() - t0;
+  }
+  return SCALCE_OK;
+}
+
+}  // namespace
 
 extern "C" int scalce_stream_compress(scalce_ctx *ctx, const scalce_params *p, scalce_read_fn rd1, void *user1, scalce_read_fn rd2,
                                       void *user2, uint64_t piece_bytes, uint64_t reads_hint, int flags, scalce_batch **out,
@@ -129,177 +260,30 @@ extern "C" int scalce_stream_compress(scalce_ctx *ctx, const scalce_params *p, s
   // piece's tail that goes on into the next piece always begins at a pair)
   const int nm = p->paired && !p->interleaved ? 2 : 1;
   const uint64_t piece = ((piece_bytes ? piece_bytes : (1ull << 30)) + 4095) & ~4095ull;
-  const int NPIN = 3;
-  const uint64_t cap = 2 * piece;  // of a piece: the tail of the previous one plus one chunk
   scalce_read_fn rd[2] = {rd1, rd2};
   void *user[2] = {user1, user2};
+  Stream s_copy, s_main;  // (in front of the mates: the streams go after the buffers and events used on them)
   Mate M[2];
   scalce_batch *b = nullptr;
-  hipStream_t s_copy = nullptr, s_main = nullptr;
   std::string err;
-  int rc = SCALCE_OK;
   scalce_stream_stats S;
   memset(&S, 0, sizeof S);
   const double t_start = now_s();
-  bool started = false;
-
-  ST_HIP(hipStreamCreateWithFlags(&s_copy, hipStreamNonBlocking));
-  ST_HIP(hipStreamCreateWithFlags(&s_main, hipStreamNonBlocking));
-  for (int m = 0; m < nm; m++) {
-    for (int i = 0; i < NPIN; i++) {
-      void *hp = nullptr;
-      ST_HIP(hipHostMalloc(&hp, piece, hipHostMallocDefault));
-      M[m].pinned.push_back(static_cast<uint8_t *>(hp));
-      ChunkRing::Chunk c;
-      c.p = static_cast<uint8_t *>(hp);
-      M[m].ring.free_.push_back(c);
-    }
-    for (int i = 0; i < 2; i++) {
-      ST_HIP(hipMalloc(reinterpret_cast<void **>(&M[m].d_text[i]), cap + 256));
-      ST_HIP(hipMalloc(reinterpret_cast<void **>(&M[m].d_raw[i]), piece + 256));
-      ST_HIP(hipEventCreateWithFlags(&M[m].up_ev[i], hipEventDisableTiming));
-      ST_HIP(hipEventCreateWithFlags(&M[m].land_ev[i], hipEventDisableTiming));
-    }
+  const int rc = stream_run(ctx, p, rd, user, nm, piece, reads_hint, flags, s_copy, s_main, M, b, S, err);
+  if (rc) {
+    if (errbuf && errcap) snprintf(errbuf, errcap, "%s", err.c_str());
+    if (b) scalce_batch_destroy(b);
+    b = nullptr;
+  } else {
+    S.total_s = now_s() - t_start;
+    S.reads = scalce_batch_reads(b);
   }
-  {
-    const uint64_t rec_min = p->fasta ? (uint64_t)p->read_len[0] + 4 : 2 * (uint64_t)p->read_len[0] + 7;  // (">x", bases, two newlines)
-    const uint64_t rows0 = reads_hint ? reads_hint + 16 : piece / rec_min + 16;
-    rc = scalce_batch_create(ctx, p, rows0, cap + 256, &b);
-    if (rc) { err = scalce_last_error(ctx); goto fail_rc; }
-    scalce_batch_set_lean(b, (flags & SCALCE_STREAM_LEAN) ? 1 : 0);
-  }
-  for (int m = 0; m < nm; m++) M[m].reader = std::thread(reader_main, &M[m].ring, rd[m], user[m], piece);
-  started = true;
-
-  {
-    // one more chunk of every mate that has input left and a free slot starts its way up
-    auto upload = [&]() -> int {
-      for (int m = 0; m < nm; m++) {
-        Mate &x = M[m];
-        if (x.eof || x.tail - x.head >= 2) continue;
-        const int sl = (int)(x.tail & 1);
-        ChunkRing::Chunk c;
-        const double t0 = now_s();
-        if (!x.ring.take_full(c)) { err = x.ring.error; return SCALCE_ERR_FORMAT; }
-        S.read_wait_s += now_s() - t0;
-        if (c.last) x.eof = true;
-        x.raw_chunk[sl] = c;
-        x.raw_n[sl] = c.n;
-        // the slot's previous chunk must have left for d_text before this one lands on it
-        if (x.landed_once[sl] && hipStreamWaitEvent(s_copy, x.land_ev[sl], 0) != hipSuccess) { err = "hipStreamWaitEvent failed"; return SCALCE_ERR_HIP; }
-        if (c.n && hipMemcpyAsync(x.d_raw[sl], c.p, c.n, hipMemcpyHostToDevice, s_copy) != hipSuccess) { err = "hipMemcpyAsync (chunk upload) failed"; return SCALCE_ERR_HIP; }
-        if (hipEventRecord(x.up_ev[sl], s_copy) != hipSuccess) { err = "hipEventRecord failed"; return SCALCE_ERR_HIP; }
-        x.tail++;
-        S.bytes[m] += c.n;
-      }
-      return SCALCE_OK;
-    };
-    // chunks that have arrived go behind the tail in d_text while the piece is short of `piece` bytes and they fit;
-    // their pinned buffers return to the reader
-    int landed = 0;
-    auto land = [&]() -> int {
-      landed = 0;
-      for (int m = 0; m < nm; m++) {
-        Mate &x = M[m];
-        while (x.head < x.tail && x.have < piece && x.have + x.raw_n[x.head & 1] <= cap) {
-          const int sl = (int)(x.head & 1);
-          const double t0 = now_s();
-          if (hipEventSynchronize(x.up_ev[sl]) != hipSuccess) { err = "chunk upload failed"; return SCALCE_ERR_HIP; }
-          S.h2d_wait_s += now_s() - t0;
-          if (x.raw_n[sl] && hipMemcpyAsync(x.d_text[x.cur] + x.have, x.d_raw[sl], x.raw_n[sl], hipMemcpyDeviceToDevice, s_main) != hipSuccess) {
-            err = "hipMemcpyAsync (piece assembly) failed";
-            return SCALCE_ERR_HIP;
-          }
-          if (hipEventRecord(x.land_ev[sl], s_main) != hipSuccess) { err = "hipEventRecord failed"; return SCALCE_ERR_HIP; }
-          x.landed_once[sl] = true;
-          x.have += x.raw_n[sl];
-          x.ring.put_free(x.raw_chunk[sl]);
-          x.head++;
-          landed++;
-        }
-      }
-      return SCALCE_OK;
-    };
-
-    if ((rc = upload())) goto fail_rc;
-    for (;;) {
-      if ((rc = land())) goto fail_rc;
-      if ((rc = upload())) goto fail_rc;  // travels while this piece is worked on
-      bool final_piece = true;
-      for (int m = 0; m < nm; m++) final_piece = final_piece && M[m].all_landed();
-      uint64_t used[2] = {0, 0};
-      const double t0 = now_s();
-      rc = scalce_batch_append(b, M[0].d_text[M[0].cur], M[0].have, nm == 2 ? M[1].d_text[M[1].cur] : nullptr, nm == 2 ? M[1].have : 0,
-                               final_piece ? 1 : 0, used, s_main);
-      S.front_s += now_s() - t0;
-      if (rc) { err = scalce_last_error(ctx); goto fail_rc; }
-      S.rounds++;
-      bool progress = landed > 0;
-      for (int m = 0; m < nm; m++) {
-        Mate &x = M[m];
-        if (used[m] > x.have) { err = "internal: consumed more than the piece"; rc = SCALCE_ERR_ARG; goto fail_rc; }
-        progress = progress || used[m] > 0;
-        const uint64_t rest = x.have - used[m];
-        if (rest && used[m]) {  // the unconsumed tail opens the next piece
-          ST_HIP(hipMemcpyAsync(x.d_text[x.cur ^ 1], x.d_text[x.cur] + used[m], rest, hipMemcpyDeviceToDevice, s_main));
-          x.cur ^= 1;
-        }
-        x.have = rest;
-      }
-      if (final_piece) break;
-      if (!progress) {
-        err = "(ERROR) a record does not fit one piece of the stream, or the mates have different record counts";
-        rc = SCALCE_ERR_FORMAT;
-        goto fail_rc;
-      }
-    }
-  }
-  {
-    double t0 = now_s();
-    if ((rc = scalce_batch_order(b, s_main)) || (rc = scalce_batch_finish(b, s_main))) { err = scalce_last_error(ctx); goto fail_rc; }
-    S.order_s = now_s() - t0;
-    // the staging buffers are dead: give them back before the emit stage allocates the streams
-    for (int m = 0; m < nm; m++)
-      for (int i = 0; i < 2; i++) {
-        hipFree(M[m].d_text[i]); M[m].d_text[i] = nullptr;
-        hipFree(M[m].d_raw[i]); M[m].d_raw[i] = nullptr;
-      }
-    t0 = now_s();
-    if ((rc = scalce_batch_emit(b, s_main)) || (rc = scalce_batch_finish(b, s_main))) { err = scalce_last_error(ctx); goto fail_rc; }
-    S.emit_s = now_s() - t0;
-    if (!(flags & SCALCE_STREAM_DEFER_ENTROPY)) {
-      t0 = now_s();
-      if ((rc = scalce_batch_entropy(b, nullptr, s_main)) || (rc = scalce_batch_finish(b, s_main))) { err = scalce_last_error(ctx); goto fail_rc; }
-      S.entropy_s = now_s() - t0;
-    }
-  }
-  S.total_s = now_s() - t_start;
-  S.reads = scalce_batch_reads(b);
-  goto cleanup;
-
-fail:
-  rc = SCALCE_ERR_HIP;
-fail_rc:
-  if (errbuf && errcap) snprintf(errbuf, errcap, "%s", err.c_str());
-  if (b) scalce_batch_destroy(b);
-  b = nullptr;
-cleanup:
+  // a reader blocked in rd() ends with its stream; one waiting for a free chunk is woken here.  Every reader is joined
+  // before its pinned chunks go with the mates
   for (int m = 0; m < nm; m++) {
     M[m].ring.shutdown();
-    if (started && M[m].reader.joinable()) {
-      // a reader blocked in rd() ends with its stream; one waiting for a free chunk has just been woken
-      M[m].reader.join();
-    }
-    for (int i = 0; i < 2; i++) {
-      if (M[m].d_text[i]) hipFree(M[m].d_text[i]);
-      if (M[m].d_raw[i]) hipFree(M[m].d_raw[i]);
-      if (M[m].up_ev[i]) hipEventDestroy(M[m].up_ev[i]);
-      if (M[m].land_ev[i]) hipEventDestroy(M[m].land_ev[i]);
-    }
-    for (uint8_t *hp : M[m].pinned) hipHostFree(hp);
+    if (M[m].reader.joinable()) M[m].reader.join();
   }
-  if (s_copy) hipStreamDestroy(s_copy);
-  if (s_main) hipStreamDestroy(s_main);
   if (st) *st = S;
   *out = b;
   return rc;
