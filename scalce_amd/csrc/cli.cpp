@@ -9,59 +9,31 @@
 // combine_and_compress_with_split (compress.cpp:289-343) and, for -d, the record loop of
 // decompress.cpp:259-369.  Every byte of the hot path is produced by the HIP kernels; there is no CPU
 // fallback -- without a GPU the tool stops with an error.
+//
+// What needs HIP or the library is here: the downloads, the archive headers, the quality model, the three runs and main().
+// The host logic between them has headers of its own, which compile without HIP (tools/cli_host_check.cpp drives them):
+//   cli_io.hpp      messages, thread counts, Fd, parallel reads, line counting, OutFile
+//   cli_input.hpp   MateSource (a mate's files joined), sample_stats
+//   cli_shares.hpp  --gpus: a rank's record range (LineRanges), its share of every bucket (Shares, place_share)
+//   cli_sink.hpp    -d: ArchiveFile behind the read callbacks, TextSink behind the write callback
 #include <getopt.h>
 #include <hip/hip_runtime_api.h>
-#include <fcntl.h>
-#include <sys/stat.h>
 #include <sys/wait.h>
-#include <unistd.h>
-#include <sys/time.h>
-#include <zlib.h>
-#include <atomic>
-#include <memory>
-#include <thread>
-#include <algorithm>
-
-#include <cstdarg>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
 
 #include <cerrno>
 #include <csignal>
 
 #include "../../include/scalce_hip.h"
 #include "hip_own.hpp"
-#include "pargz.hpp"
 #include "lenstream.hpp"
-
+#include "cli_io.hpp"
+#include "cli_input.hpp"
+#include "cli_shares.hpp"
+#include "cli_sink.hpp"
 
 #ifndef SCALCE_VERSION
 #define SCALCE_VERSION "2.8-mi355x"
 #endif
-
-static void LOG(const char *fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vfprintf(stderr, fmt, ap);
-  va_end(ap);
-}
-[[noreturn]] static void FAIL(const char *fmt, ...) {  // ERROR(), const.h:77-81
-  va_list ap;
-  va_start(ap, fmt);
-  fprintf(stderr, "(ERROR) ");
-  vfprintf(stderr, fmt, ap);
-  va_end(ap);
-  exit(1);
-}
-static double now() {
-  struct timeval t;
-  gettimeofday(&t, 0);
-  return t.tv_sec + 1e-6 * t.tv_usec;
-}
 
 struct Options {
   int lossy = 0, sample = 100000, threads = 0, split = 0;
@@ -123,80 +95,6 @@ static const char *HELP_TEXT =
     "                              one GPU (and of the reference at -T 1 with the same -B); input: one plain FASTQ file (pair), -c no\n"
     "core table: --patterns-bin FILE or $SCALCE_PATTERNS or patterns.bin next to the executable\n";
 
-// ---- small I/O helpers ------------------------------------------------------------------------------
-// Host threads: -T, else the cores shared by `procs` processes (a process alone leaves one to its main thread), at most
-// 64.  Plain files are read by up to 8 of them, gzip members inflated by up to 32, the gz containers deflated by all.
-static int g_threads = 1;
-static void set_threads(const Options &o, int procs) {
-  const int hw = (int)std::thread::hardware_concurrency();
-  g_threads = o.threads > 0 ? o.threads : std::max(1, std::min(64, procs > 1 ? hw / procs : hw - 1));
-}
-static int g_threads_io() { return std::max(1, std::min(g_threads, 8)); }
-static int g_threads_gz() { return std::max(1, std::min(g_threads, 32)); }
-
-static bool is_gzip(const std::string &path) {  // the gzip magic (the reference's readers sniff it too, decompress.cpp:99-113)
-  const int fd = ::open(path.c_str(), O_RDONLY);
-  uint8_t mg[2] = {0, 0};
-  const bool gz = fd >= 0 && ::pread(fd, mg, 2, 0) == 2 && mg[0] == 0x1F && mg[1] == 0x8B;
-  if (fd >= 0) ::close(fd);
-  return gz;
-}
-// fn(a, b) on the slices [a, b) of [0, n), `slice` bytes each, taken in turn by up to `threads` threads (the caller's included)
-template <class Fn> static void for_slices(uint64_t n, uint64_t slice, int threads, Fn fn) {
-  std::atomic<uint64_t> next{0};
-  auto work = [&]() { for (uint64_t a; (a = next.fetch_add(slice)) < n;) fn(a, std::min(n, a + slice)); };
-  const int nt = (int)std::min<uint64_t>((uint64_t)std::max(1, threads), (n + slice - 1) / slice);
-  std::vector<std::thread> pool;
-  for (int t = 1; t < nt; t++) pool.emplace_back(work);
-  work();
-  for (auto &t : pool) t.join();
-}
-// n bytes of fd from offset off, read in slices by several threads (one thread copying out of the page cache delivers about
-// 5 GB/s, a tenth of what an upload behind it can take)
-static bool pread_parallel(int fd, uint8_t *dst, uint64_t n, uint64_t off, uint64_t slice, int threads) {
-  std::atomic<bool> bad{false};
-  for_slices(n, slice, threads, [&](uint64_t a, uint64_t b) {
-    for (uint64_t done = a; done < b && !bad;) {
-      const ssize_t k = ::pread(fd, dst + done, (size_t)(b - done), (off_t)(off + done));
-      if (k <= 0) bad = true; else done += (uint64_t)k;
-    }
-  });
-  return !bad;
-}
-// A whole file: plain by parallel pread, gzip (the IO_GZIP reader, compress.cpp:756) with its members inflated by several
-// threads (our own -c gz containers are 4 MiB members)
-static std::vector<uint8_t> read_whole(const std::string &path) {
-  std::vector<uint8_t> out;
-  if (is_gzip(path)) {
-    scalce_host::ParGz z;
-    if (!z.open(path, g_threads_gz())) FAIL("Cannot read file %s\n", path.c_str());
-    std::vector<uint8_t> chunk(64u << 20);
-    for (int64_t k; (k = z.read(chunk.data(), chunk.size())) != 0;) {
-      if (k < 0) FAIL("Read error on %s\n", path.c_str());
-      out.insert(out.end(), chunk.begin(), chunk.begin() + k);
-    }
-    return out;
-  }
-  const int fd = ::open(path.c_str(), O_RDONLY);
-  struct stat st;
-  if (fd < 0 || fstat(fd, &st) != 0) FAIL("Cannot read file %s\n", path.c_str());
-  out.resize((size_t)st.st_size);
-  if (!pread_parallel(fd, out.data(), out.size(), 0, 64u << 20, g_threads_io())) FAIL("Read error on %s\n", path.c_str());
-  ::close(fd);
-  return out;
-}
-static bool second_file(const std::string &p, std::string &out) {  // get_second_file, const.cpp:51-64
-  out = p;
-  for (int i = (int)out.size() - 1; i >= 0; i--)
-    if (out[i] == '1') { out[i] = '2'; return true; }
-  return false;
-}
-static std::string mate_file(const std::string &f, int m) {  // input f's file of mate m
-  std::string out = f;
-  if (m && !second_file(f, out)) FAIL("Cannot get file name for paired end for file %s. File should contain character 1.\n", f.c_str());
-  return out;
-}
-
 // ---- the archive: the file headers of combine_and_compress_with_split (compress.cpp:263-343) ---------------------------
 //   PREFIX_<m>.scalcer  magic, int32 no_ac (-A), int32 read length; the read stream (mate 1: buckets, each opened by
 //                       [int32 core][int64 records]; mate 2: bare records in mate 1's order)
@@ -207,6 +105,11 @@ static std::string mate_file(const std::string &f, int m) {  // input f's file o
 static const uint8_t MAGIC[8] = {'s', 'c', 'a', 'l', 'c', 'e', '2', '2'};
 static constexpr size_t QTABLE_WORDS = 512000;
 static std::string archive_path(const std::string &out, int m, char ext) { return out + "_" + std::to_string(m + 1) + ".scalce" + ext; }
+// fn(extension, path) on every mate's files with the extensions `exts` ("rnq": .scalcer, .scalcen, .scalceq)
+template <class Fn> static void for_each_archive_file(const Options &o, const char *exts, Fn fn) {
+  for (int m = 0; m < (o.pairs() ? 2 : 1); m++)
+    for (const char *e = exts; *e; e++) fn(*e, archive_path(o.out, m, *e));
+}
 // -c gz holds every file in a gzip container but an arithmetic-coded .scalceq (compress.cpp:249)
 static bool gz_container(const Options &o, char ext) { return o.container == 1 && (ext != 'q' || o.no_ac); }
 static std::vector<uint8_t> with_magic(const void *fields, size_t n) {
@@ -223,92 +126,6 @@ static std::vector<uint8_t> names_header(const Options &o) {  // without names: 
 }
 static std::vector<uint8_t> qual_header(int64_t phred) { return with_magic(&phred, 8); }
 
-// Output file.  Plain: stdio.  gzip container (-c gz / pigz): the reference hands the stream to a pigz child or to
-// zlib's gzwrite (buffio.cpp:148-188, 190-260); here the bytes are collected and deflated at close() by g_threads
-// host threads, 4 MiB per independent gzip member -- concatenated members are one valid gzip file, which the
-// reference's reader (gzread, decompress.cpp:99-113) and ours accept alike (once the hot path is on
-// the GPU, single-threaded deflate of .scalcer/.scalcen is what the wall clock of a run is made of).
-struct OutFile {
-  bool gz = false;
-  FILE *f = nullptr;
-  std::vector<uint8_t> pending;  // gz only: bytes not deflated yet
-  uint64_t written = 0;
-  static constexpr size_t MEMBER = 4u << 20;
-  void open(const std::string &path, bool gz_) {
-    gz = gz_;
-    f = path == "-" ? stdout : fopen(path.c_str(), "wb");
-    if (!f) FAIL("Cannot create %s\n", path.c_str());
-  }
-  void raw(const uint8_t *b, size_t n) {
-    written += n;
-    while (n) {
-      size_t k = n > (1u << 30) ? (1u << 30) : n;
-      if (fwrite(b, 1, k, f) != k) FAIL("write failed\n");
-      b += k; n -= k;
-    }
-  }
-  void write(const void *p, size_t n) {
-    const uint8_t *b = static_cast<const uint8_t *>(p);
-    if (!gz) { raw(b, n); return; }
-    pending.insert(pending.end(), b, b + n);
-    // enough for every thread: deflate what is there, member by member (the stream never has to sit in memory whole)
-    if (pending.size() >= MEMBER * (size_t)std::max(1, g_threads) * 2) flush_members(false);
-  }
-  void write(const std::vector<uint8_t> &v) { write(v.data(), v.size()); }
-  // The reference writes its containers at zlib's default level (buffio.cpp: gzopen(path, "wb")), and so does this writer for
-  // what deflate shrinks (names: to a third).  The read stream is 2-bit packed bases, as good as incompressible (the
-  // reference's own gz gains 2.5 % on it) and the slowest thing zlib can be fed: ~20 MB/s per core at level 6 -- 3.6 of the
-  // 5.8 s of a 50 M-read run with -c gz.  A member none of whose sample windows (eight of 16 KiB, spread over the member)
-  // shrinks by a tenth at level 1 is therefore Huffman-coded only (Z_HUFFMAN_ONLY: no match search, ~15 x the speed, within
-  // a percent of the size).  SCALCE_GZ_LEVEL=<n> turns that off and deflates every member at level n.
-  static bool hardly_compressible(const uint8_t *src, size_t n) {
-    static const bool off = getenv("SCALCE_GZ_LEVEL") != nullptr;   // (a level asked for by hand is applied to every member)
-    if (off || n < 4096) return false;
-    const size_t win = std::min<size_t>(n, 16u << 10), nwin = n >= 8 * win ? 8 : 1;
-    std::vector<uint8_t> tmp(compressBound((uLong)win));
-    for (size_t i = 0; i < nwin; i++) {
-      const size_t at = nwin == 1 ? 0 : (n - win) / (nwin - 1) * i;
-      uLongf got = (uLongf)tmp.size();
-      if (compress2(tmp.data(), &got, src + at, (uLong)win, 1) != Z_OK) return false;
-      if (got * 10 < win * 9) return false;   // this part does shrink: the member goes through deflate proper
-    }
-    return true;
-  }
-  static void deflate_member(const uint8_t *src, size_t n, std::vector<uint8_t> &out) {
-    z_stream z;
-    memset(&z, 0, sizeof z);
-    const bool fast = n && hardly_compressible(src, n);
-    // (what does shrink -- names -- goes at zlib's default level, the reference's: level 3 is 2.4 x the speed for a tenth more
-    //  bytes of that stream; SCALCE_GZ_LEVEL=3 asks for it)
-    static const int level = getenv("SCALCE_GZ_LEVEL") ? atoi(getenv("SCALCE_GZ_LEVEL")) : Z_DEFAULT_COMPRESSION;
-    if (deflateInit2(&z, fast ? 1 : level, Z_DEFLATED, 15 + 16, 8, fast ? Z_HUFFMAN_ONLY : Z_DEFAULT_STRATEGY) != Z_OK) FAIL("deflateInit2 failed\n");
-    out.resize(deflateBound(&z, (uLong)n) + 64);
-    z.next_in = const_cast<Bytef *>(src); z.avail_in = (uInt)n;
-    z.next_out = out.data(); z.avail_out = (uInt)out.size();
-    if (deflate(&z, Z_FINISH) != Z_STREAM_END) FAIL("deflate failed\n");
-    out.resize(z.total_out);
-    deflateEnd(&z);
-  }
-  void flush_members(bool all) {
-    const size_t whole = pending.size() / MEMBER, nchunks = all ? (pending.empty() ? 0 : (pending.size() + MEMBER - 1) / MEMBER) : whole;
-    if (!nchunks) return;
-    std::vector<std::vector<uint8_t>> members(nchunks);
-    const size_t done = std::min(pending.size(), nchunks * MEMBER);
-    for_slices(done, MEMBER, g_threads, [&](uint64_t a, uint64_t b) { deflate_member(pending.data() + a, b - a, members[a / MEMBER]); });
-    for (auto &m : members) raw(m.data(), m.size());
-    pending.erase(pending.begin(), pending.begin() + done);
-  }
-  void close() {
-    if (gz && f) {
-      const bool nothing = written == 0 && pending.empty();
-      flush_members(true);
-      if (nothing) { std::vector<uint8_t> m; deflate_member(nullptr, 0, m); raw(m.data(), m.size()); }  // an empty gzip file
-      pending.clear(); pending.shrink_to_fit();
-    }
-    if (f && f != stdout) fclose(f);
-    f = nullptr;
-  }
-};
 #define HIPOK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) FAIL("%s: %s\n", #x, hipGetErrorString(e_)); } while (0)
 #define SCOK(ctx, x) do { int rc_ = (x); if (rc_) { fprintf(stderr, "%s\n", scalce_last_error(ctx)); exit(1); } } while (0)
 
@@ -370,139 +187,6 @@ struct Downloader {
   }
 };
 
-// One mate's input: the files of the command line one after the other (compress.cpp:756-797 runs them through the same
-// trie; the record stream is their concatenation), each plain or gzip (the reference opens everything through zlib,
-// :767-779).  Plain files are read by parallel pread straight into the pinned chunk the streaming host hands in.
-struct MateSource {
-  std::vector<std::string> files;
-  size_t cur = 0;
-  int fd = -1;
-  scalce_host::ParGz pgz;     // gzip input: members inflated on several threads (pargz.hpp)
-  bool gz = false;
-  std::vector<uint8_t> peek;  // bytes read ahead for the quality sample, served first
-  size_t peek_pos = 0;
-  bool open_next() {
-    if (cur >= files.size()) return false;
-    const std::string &path = files[cur++];
-    if (is_gzip(path)) {
-      if (!pgz.open(path, std::max(1, g_threads))) FAIL("Cannot read file %s\n", path.c_str());
-      gz = true;
-      return true;
-    }
-    fd = ::open(path.c_str(), O_RDONLY);
-    if (fd < 0) FAIL("Cannot read file %s\n", path.c_str());
-#ifdef POSIX_FADV_SEQUENTIAL
-    posix_fadvise(fd, 0, 0, POSIX_FADV_SEQUENTIAL);
-#endif
-    return true;
-  }
-  uint64_t fpos = 0;  // plain files: where the next read starts
-  bool hold_at_file_end = false;  // fill_peek: the sample never runs into the next file
-  // The reference reads every file on its own, line by line (compress.cpp:756-811, gzgets): a file whose last line has no
-  // newline still ends there.  Concatenated byte-wise that line would run into the next file's '@name', so a file that
-  // does not end in a newline is given one.
-  uint8_t last_byte = '\n';
-  bool pending_newline = false;
-  // -i: every file must hold whole pairs (concatenated, a file with an odd record count would pair the next file's records
-  // the wrong way round).  pair_lines = lines of a pair; the newlines of the current file are counted on their way through.
-  uint64_t pair_lines = 0, file_lines = 0;
-  std::string error;  // why read_raw returned -1, when it was the input's shape
-  int64_t read_raw(void *dst, uint64_t cap) {
-    for (;;) {
-      if (pending_newline && cap) { pending_newline = false; last_byte = '\n'; *static_cast<uint8_t *>(dst) = '\n'; return 1; }
-      if (fd < 0 && !gz) {
-        if (hold_at_file_end && cur >= 1) return 0;
-        if (!open_next()) return 0;
-        fpos = 0;
-        file_lines = 0;
-      }
-      const int64_t k = gz ? pgz.read(dst, cap) : read_plain(static_cast<uint8_t *>(dst), cap);
-      if (k < 0) return -1;
-      if (k > 0) {
-        const uint8_t *p = static_cast<const uint8_t *>(dst), *e = p + k;
-        if (pair_lines)
-          while ((p = static_cast<const uint8_t *>(memchr(p, '\n', (size_t)(e - p))))) { file_lines++; p++; }
-        last_byte = static_cast<uint8_t *>(dst)[k - 1];
-        return k;
-      }
-      if (gz) { pgz.close(); gz = false; } else { ::close(fd); fd = -1; }
-      if (last_byte != '\n') pending_newline = true;
-      const uint64_t lines = file_lines + (pending_newline ? 1 : 0), lpr = pair_lines / 2;
-      if (pair_lines && lines % pair_lines && lines % lpr == 0) {
-        char msg[4352];
-        snprintf(msg, sizeof msg, "(ERROR) %s holds an odd number of records (%llu): -i needs mate 1 and mate 2 of every pair\n",
-                 files[cur - 1].c_str(), (unsigned long long)(lines / lpr));
-        error = msg;
-        return -1;
-      }
-    }
-  }
-  // a big request on a plain file is read by several threads at once
-  int64_t read_plain(uint8_t *dst, uint64_t cap) {
-    struct stat st;
-    if (fstat(fd, &st) != 0) return -1;
-    const uint64_t want = std::min(cap, (uint64_t)st.st_size > fpos ? (uint64_t)st.st_size - fpos : 0);
-    if (!pread_parallel(fd, dst, want, fpos, 16u << 20, g_threads_io())) return -1;
-    fpos += want;
-    return (int64_t)want;
-  }
-  int64_t read(void *dst, uint64_t cap) {
-    if (peek_pos < peek.size()) {
-      const size_t k = (size_t)std::min<uint64_t>(cap, peek.size() - peek_pos);
-      memcpy(dst, peek.data() + peek_pos, k);
-      peek_pos += k;
-      if (peek_pos == peek.size()) { std::vector<uint8_t>().swap(peek); peek_pos = 0; }
-      return (int64_t)k;
-    }
-    return read_raw(dst, cap);
-  }
-  // read ahead until the text holds `records` records or the FIRST file ends: quality_mapping_init's sample is taken
-  // from files[0] alone (get_quality_stats, compress.cpp:761; the loop of qualities.cpp:66-78 stops at its end)
-  void fill_peek(int records, int lines_per_record) {
-    hold_at_file_end = true;
-    const size_t want = (size_t)lines_per_record * (size_t)records;
-    size_t lines = 0, scanned = 0;
-    for (int64_t got = 1; got;) {
-      const uint8_t *p = peek.data();
-      while (scanned < peek.size() && lines < want) {
-        const void *nl = memchr(p + scanned, '\n', peek.size() - scanned);
-        if (!nl) { scanned = peek.size(); break; }
-        scanned = (size_t)((const uint8_t *)nl - p) + 1;
-        lines++;
-      }
-      if (lines >= want) break;
-      const size_t old = peek.size(), step = 16u << 20;
-      peek.resize(old + step);
-      for (got = 0; (size_t)got < step;) {
-        const int64_t k = read_raw(peek.data() + old + got, step - (size_t)got);
-        if (k < 0) FAIL("%s", error.empty() ? "Read error\n" : error.c_str());
-        if (k == 0) break;
-        got += k;
-      }
-      peek.resize(old + (size_t)got);
-    }
-    hold_at_file_end = false;
-  }
-  static int64_t read_cb(void *user, void *dst, uint64_t cap) { return static_cast<MateSource *>(user)->read(dst, cap); }
-};
-
-// sampling loop of quality_mapping_init (qualities.cpp:64-97) on the text read ahead: the first `sample` records r with
-// r % stride == first (-i: stride 2, `first` = the mate -- the _interleave == 10 / 20 skips of qualities.cpp:67-90)
-static void sample_stats(const uint8_t *t, size_t n, int sample, int32_t stat[128], int &read_length, int stride = 1, int first = 0) {
-  size_t line[5] = {0};  // where a record's four lines start, and the next record
-  for (long r = 0, taken = 0; taken < sample; r++, line[0] = line[4]) {
-    for (int k = 1; k < 5; k++) {
-      const void *nl = line[k - 1] < n ? memchr(t + line[k - 1], '\n', n - line[k - 1]) : nullptr;
-      if (!nl) return;
-      line[k] = (size_t)((const uint8_t *)nl - t) + 1;
-    }
-    if (r % stride != first) continue;
-    taken++;
-    for (size_t j = line[3]; j + 1 < line[4]; j++) stat[t[j] & 127]++;
-    read_length = (int)(line[4] - 1 - line[3]);
-  }
-}
-
 // ---- run setup --------------------------------------------------------------------------------------------
 static scalce_params params_from(const Options &o) {
   scalce_params p;
@@ -511,6 +195,36 @@ static scalce_params params_from(const Options &o) {
   p.fasta = o.fasta; p.no_qualities = o.no_qual; p.interleaved = o.interleave;
   p.variable_length = o.varlen;
   return p;
+}
+// the same for -d; lens[m]: mate m's length stream, open where has_lens[m] says the archive has one
+static scalce_unpack_params unpack_params_from(const Options &o, int nm, ArchiveFile lens[2], const bool has_lens[2]) {
+  scalce_unpack_params p;
+  memset(&p, 0, sizeof p);
+  for (int m = 0; m < nm; m++) {
+    if (!has_lens[m]) continue;
+    p.len_rd[m] = ArchiveFile::read;
+    p.len_user[m] = &lens[m];
+    p.len_skip[m] = lens[m].gz ? nullptr : ArchiveFile::skip;
+  }
+  p.mates = nm;
+  p.interleave = o.interleave;
+  p.no_qualities = o.fasta || o.no_qual;  // -d -Q / -d -f: two-line records, whatever the .scalceq holds (decompress.cpp:159-168)
+  p.mate_digit = o.pairs();
+  p.ignore_names = !o.use_names;          // decompress.cpp:219-237
+  p.library = o.library.c_str();
+  p.split = o.split;
+  p.window_text_bytes = o.window;
+  return p;
+}
+// --records (the whole archive without it); a plain file of the archive can be passed over by seeking
+static scalce_unpack_range unpack_range_from(const Options &o, int nm, ArchiveFile files[2][3]) {
+  scalce_unpack_range rg;
+  memset(&rg, 0, sizeof rg);
+  rg.first_record = o.range_first;
+  rg.nrecords = o.range_count;
+  for (int m = 0; m < nm; m++)
+    for (int k = 0; k < 3; k++) rg.skip[m][k] = files[m][k].gz ? nullptr : ArchiveFile::skip;
+  return rg;
 }
 // Mate m's quality map and read length from the first records of the first input file (get_quality_stats,
 // compress.cpp:761).  fill_peek holds at the end of that file; under --gpus, where several files were written out as one,
@@ -574,42 +288,101 @@ static void log_statistics(const Options &o, const scalce_params &p, uint64_t N,
 }
 
 // ---- compress -----------------------------------------------------------------------------------------
+// A mate's files of the archive, out of the batch of a finished run.  One thread per mate calls these.
+struct MateFiles {
+  const Options &o;
+  const scalce_params &p;
+  scalce_ctx *ctx;
+  scalce_batch *b;
+  void write_reads_and_names(int m, Downloader &down) const {
+    OutFile fR, fN;
+    fR.open(archive_path(o.out, m, 'r'), gz_container(o, 'r'));
+    fR.write(reads_header(o, p.read_len[m]));
+    down.to_file(ctx, b, SCALCE_OUT_READS, m, fR);
+    fR.close();
+    fN.open(archive_path(o.out, m, 'n'), gz_container(o, 'n'));
+    fN.write(names_header(o));
+    if (o.use_names) down.to_file(ctx, b, SCALCE_OUT_NAMES, 0, fN);  // mate 2 repeats mate 1's names (:450-454)
+    fN.close();
+  }
+  void write_lengths(int m) const {  // --variable-length: how long each record really was, in archive order
+    OutFile fL;
+    fL.open(archive_path(o.out, m, 'l'), gz_container(o, 'l'));
+    uint8_t head[scalce_host::LEN_HEADER_BYTES];
+    scalce_host::len_header_write(head, p.read_len[m]);
+    fL.write(head, sizeof head);
+    const std::vector<uint8_t> pad = fetch(ctx, b, SCALCE_OUT_LENGTHS, m);
+    const int width = scalce_host::len_entry_width(p.read_len[m]);
+    std::vector<uint8_t> entries(pad.size() / 2 * (size_t)width);
+    scalce_host::len_entries_write(reinterpret_cast<const uint16_t *>(pad.data()), pad.size() / 2, width, entries.data());
+    fL.write(entries);
+    fL.close();
+  }
+  void write_qualities(int m, Downloader &down, uint64_t N) const {  // once the coder is through; N: records of the run
+    OutFile fQ;
+    fQ.open(archive_path(o.out, m, 'q'), gz_container(o, 'q'));
+    fQ.write(qual_header(p.qmap[0].offset));
+    if (!(o.fasta || o.no_qual)) {  // (-Q / -f: the header and nothing else -- no table (:296), no coder blocks (ac_write of nothing))
+      if (!o.no_ac) {
+        fQ.write(fetch(ctx, b, SCALCE_OUT_TABLE, m));
+        const uint64_t total = N * (uint64_t)p.read_len[m];
+        fQ.write(&total, 8);
+      }
+      down.qual_to_file(ctx, b, m, fQ);
+    }
+    fQ.close();
+  }
+};
+
+// The input of a one-GPU run: a source per input stream (-i reads both mates from one), with the quality model sampled.
+struct CompressInput {
+  int nsrc;
+  MateSource src[2];
+  uint64_t original = 0, bytes1 = 0;  // input bytes: every mate's, mate 1's
+  bool plain1 = true;                 // no gzip among mate 1's files
+  CompressInput(const Options &o, const std::vector<std::string> &files, scalce_params &p) : nsrc(o.paired ? 2 : 1) {
+    if (o.interleave) src[0].pair_lines = 2 * (o.fasta ? 2 : 4);
+    for (int m = 0; m < nsrc; m++) {
+      for (const std::string &f : files) {
+        const std::string path = mate_file(f, m);
+        struct stat st;
+        const uint64_t size = stat(path.c_str(), &st) == 0 ? (uint64_t)st.st_size : 0;
+        original += size;
+        if (m == 0) { bytes1 += size; plain1 = plain1 && !is_gzip(path); }
+        src[m].files.push_back(path);
+      }
+      quality_model(o, src[m], m, p, true);
+    }
+    if (o.interleave) quality_model(o, src[0], 1, p, true);
+    if (p.read_len[0] <= 0) FAIL("Cannot determine the read length of %s\n", files[0].c_str());
+  }
+  // rows to expect: exact enough for plain text (a record is 2 L + 6 bytes plus its name), unknown behind gzip
+  uint64_t rows_hint(const Options &o, const scalce_params &p) const {
+    return plain1 ? bytes1 / ((o.fasta ? 1 : 2) * (uint64_t)p.read_len[0] + (o.fasta ? 4 : 8)) / (o.interleave ? 2 : 1) + 64 : 0;
+  }
+  uint64_t piece_bytes(uint64_t hint) const {
+    uint64_t piece = 256ull << 20;  // per chunk; three of them are pinned per mate
+    if (const char *e = getenv("SCALCE_PIECE_BYTES")) piece = strtoull(e, nullptr, 10);
+    if (hint && bytes1 + (1u << 20) < piece) piece = bytes1 + (1u << 20);  // small inputs: no point in pinning gigabytes
+    return piece;
+  }
+};
+
 static int do_compress(const Options &o, const std::vector<std::string> &files, scalce_ctx *ctx) {
   const double t0 = now();
   const int nm = o.pairs() ? 2 : 1;
-  const int nsrc = o.interleave ? 1 : nm;  // input streams: -i reads both mates from one
-  uint64_t original = 0, bytes1 = 0;  // input bytes: every mate's, mate 1's
-  bool plain1 = true;                 // no gzip among mate 1's files
   scalce_params p = params_from(o);
-  const bool no_qual = o.fasta || o.no_qual;
   LOG("Preprocessing FASTQ files ...\n");
-  MateSource src[2];
-  if (o.interleave) src[0].pair_lines = 2 * (o.fasta ? 2 : 4);
-  for (int m = 0; m < nsrc; m++) {
-    for (const std::string &f : files) {
-      const std::string path = mate_file(f, m);
-      struct stat st;
-      const uint64_t size = stat(path.c_str(), &st) == 0 ? (uint64_t)st.st_size : 0;
-      original += size;
-      if (m == 0) { bytes1 += size; plain1 = plain1 && !is_gzip(path); }
-      src[m].files.push_back(path);
-    }
-    quality_model(o, src[m], m, p, true);
-  }
-  if (o.interleave) quality_model(o, src[0], 1, p, true);
-  if (p.read_len[0] <= 0) FAIL("Cannot determine the read length of %s\n", files[0].c_str());
-  // rows to expect: exact enough for plain text (a record is 2 L + 6 bytes plus its name), unknown behind gzip
-  const uint64_t hint = plain1 ? bytes1 / ((o.fasta ? 1 : 2) * (uint64_t)p.read_len[0] + (o.fasta ? 4 : 8)) / (o.interleave ? 2 : 1) + 64 : 0;
-  uint64_t piece = 256ull << 20;  // per chunk; three of them are pinned per mate
-  if (const char *e = getenv("SCALCE_PIECE_BYTES")) piece = strtoull(e, nullptr, 10);
-  if (hint && bytes1 + (1u << 20) < piece) piece = bytes1 + (1u << 20);  // small inputs: no point in pinning gigabytes
+  CompressInput in(o, files, p);
+  const int nsrc = in.nsrc;
+  const uint64_t hint = in.rows_hint(o, p), piece = in.piece_bytes(hint);
   scalce_batch *b = nullptr;
   scalce_stream_stats ss;
   char emsg[512] = "";
   const double t1 = now();
-  if (scalce_stream_compress(ctx, &p, MateSource::read_cb, &src[0], nsrc == 2 ? MateSource::read_cb : nullptr, nsrc == 2 ? &src[1] : nullptr, piece,
-                             hint, SCALCE_STREAM_LEAN | SCALCE_STREAM_DEFER_ENTROPY, &b, &ss, emsg, sizeof emsg)) {
-    if (!src[0].error.empty()) fputs(src[0].error.c_str(), stderr);  // (-i: a file of odd record count; the stream only saw a read error)
+  if (scalce_stream_compress(ctx, &p, MateSource::read_cb, &in.src[0], nsrc == 2 ? MateSource::read_cb : nullptr, nsrc == 2 ? &in.src[1] : nullptr,
+                             piece, hint, SCALCE_STREAM_LEAN | SCALCE_STREAM_DEFER_ENTROPY, &b, &ss, emsg, sizeof emsg)) {
+    if (!in.src[0].error.empty()) fputs(in.src[0].error.c_str(), stderr);  // (-i: a file of odd record count; the stream only saw a read error)
     else fprintf(stderr, "%s\n", emsg[0] ? emsg : scalce_last_error(ctx));
     exit(1);
   }
@@ -633,56 +406,25 @@ static int do_compress(const Options &o, const std::vector<std::string> &files, 
     for (auto &t : ts) t.join();
   };
   std::unique_ptr<Downloader> downs[2];  // (a mate's pinned slices serve both of its passes)
+  const MateFiles w{o, p, ctx, b};
   per_mate([&](int m) {
     downs[m].reset(new Downloader);
-    OutFile fR, fN;
-    fR.open(archive_path(o.out, m, 'r'), gz_container(o, 'r'));
-    fR.write(reads_header(o, p.read_len[m]));
-    downs[m]->to_file(ctx, b, SCALCE_OUT_READS, m, fR);
-    fR.close();
-    fN.open(archive_path(o.out, m, 'n'), gz_container(o, 'n'));
-    fN.write(names_header(o));
-    if (o.use_names) downs[m]->to_file(ctx, b, SCALCE_OUT_NAMES, 0, fN);  // mate 2 repeats mate 1's names (:450-454)
-    fN.close();
-    if (o.varlen) {  // how long each record really was, in archive order
-      OutFile fL;
-      fL.open(archive_path(o.out, m, 'l'), gz_container(o, 'l'));
-      uint8_t head[scalce_host::LEN_HEADER_BYTES];
-      scalce_host::len_header_write(head, p.read_len[m]);
-      fL.write(head, sizeof head);
-      const std::vector<uint8_t> pad = fetch(ctx, b, SCALCE_OUT_LENGTHS, m);
-      const int width = scalce_host::len_entry_width(p.read_len[m]);
-      std::vector<uint8_t> entries(pad.size() / 2 * (size_t)width);
-      scalce_host::len_entries_write(reinterpret_cast<const uint16_t *>(pad.data()), pad.size() / 2, width, entries.data());
-      fL.write(entries);
-      fL.close();
-    }
+    w.write_reads_and_names(m, *downs[m]);
+    if (o.varlen) w.write_lengths(m);
   });
   const double t2b = now();
   SCOK(ctx, scalce_batch_finish(b, s_ent));  // the coder is through: sizes of the coded streams, device error word
   const double t2c = now();
   per_mate([&](int m) {
-    OutFile fQ;
-    fQ.open(archive_path(o.out, m, 'q'), gz_container(o, 'q'));
-    fQ.write(qual_header(p.qmap[0].offset));
-    if (!no_qual) {  // (-Q / -f: the header and nothing else -- no table (:296), no coder blocks (ac_write of nothing))
-      if (!o.no_ac) {
-        fQ.write(fetch(ctx, b, SCALCE_OUT_TABLE, m));
-        const uint64_t total = N * (uint64_t)p.read_len[m];
-        fQ.write(&total, 8);
-      }
-      downs[m]->qual_to_file(ctx, b, m, fQ);
-    }
-    fQ.close();
+    w.write_qualities(m, *downs[m], N);
     downs[m].reset();
   });
   const double t2d = now();
   uint64_t new_size = 0;
-  for (int m = 0; m < nm; m++)
-    for (char ext : {'r', 'q', 'n', 'l'}) {
-      struct stat st;
-      if (stat(archive_path(o.out, m, ext).c_str(), &st) == 0) new_size += (uint64_t)st.st_size;
-    }
+  for_each_archive_file(o, "rnql", [&](char, const std::string &fn) {
+    struct stat st;
+    if (stat(fn.c_str(), &st) == 0) new_size += (uint64_t)st.st_size;
+  });
   s_ent.release();
   const void *dc = nullptr;
   uint64_t nc = 0;
@@ -697,8 +439,8 @@ static int do_compress(const Options &o, const std::vector<std::string> &files, 
       "order %.2f, emit %.2f; reads+names down and written beside the coder %.2f, waiting for the coder %.2f, qualities down and written %.2f, device buffers released %.2f)\n",
       t3 - t0, t1 - t0, ss.total_s - ss.order_s - ss.emit_s, ss.read_wait_s, ss.h2d_wait_s, ss.front_s, ss.order_s, ss.emit_s,
       t2b - t2, t2c - t2b, t2d - t2c, t3 - t2d);
-  LOG("\tOriginal size: %.2lfM, new size: %.2lfM, compression factor: %.2lf\n", original / (1024.0 * 1024.0),
-      new_size / (1024.0 * 1024.0), new_size ? (double)original / (double)new_size : 0.0);
+  LOG("\tOriginal size: %.2lfM, new size: %.2lfM, compression factor: %.2lf\n", in.original / (1024.0 * 1024.0),
+      new_size / (1024.0 * 1024.0), new_size ? (double)in.original / (double)new_size : 0.0);
   return 0;
 }
 
@@ -706,82 +448,182 @@ static int do_compress(const Options &o, const std::vector<std::string> &files, 
 // One process per GPU (forked before anything touches a GPU), rank r takes the r-th part of the input file, the ranks talk
 // RCCL (scalce_sharded_compress) and every rank writes its pieces of the ONE archive with pwrite at the offsets the
 // run-wide bucket counts give.  SCALCE_COMM=shm makes all ranks share GPU 0 over the shared-memory rehearsal transport.
-static uint64_t count_newlines(int fd, uint64_t a, uint64_t b, int threads) {
-  std::atomic<uint64_t> total{0};
-  const uint64_t step = 64u << 20;
-  std::atomic<uint64_t> next{a};
-  auto work = [&]() {
-    std::vector<char> buf(8u << 20);
-    for (uint64_t at; (at = next.fetch_add(step)) < b;) {
-      const uint64_t end = std::min(b, at + step);
-      uint64_t n = 0;
-      for (uint64_t p = at; p < end;) {
-        const ssize_t k = ::pread(fd, buf.data(), (size_t)std::min<uint64_t>(buf.size(), end - p), (off_t)p);
-        if (k <= 0) FAIL("Read error\n");
-        const char *q = buf.data(), *e = q + k;
-        while ((q = static_cast<const char *>(memchr(q, '\n', (size_t)(e - q))))) { n++; q++; }
-        p += (uint64_t)k;
-      }
-      total += n;
+// A rank's steps, in the order rank_main() takes them.
+
+// 1. The communicator: the shared-memory transport, or RCCL with the id rank 0 publishes in a file next to the output.
+static scalce_comm *open_comm(const Options &o, bool shm, int device, int world, int rank, const std::string &tag) {
+  scalce_comm *comm = nullptr;
+  if (shm) {
+    if (scalce_comm_create_shm(device, world, rank, ("/scalce_cli_" + tag).c_str(), 1ull << 30, &comm)) FAIL("%s\n", scalce_comm_error(comm));
+    return comm;
+  }
+  const std::string idfile = o.out + ".rcclid." + tag;
+  uint8_t id[SCALCE_COMM_ID_BYTES];
+  if (rank == 0) {
+    if (scalce_comm_unique_id(id)) FAIL("RCCL is not available\n");
+    FILE *f = fopen((idfile + ".tmp").c_str(), "wb");
+    if (!f || fwrite(id, 1, sizeof id, f) != sizeof id) FAIL("Cannot write %s\n", idfile.c_str());
+    fclose(f);
+    rename((idfile + ".tmp").c_str(), idfile.c_str());
+  } else {
+    FILE *f = nullptr;
+    for (int tries = 0; tries < 60000 && !(f = fopen(idfile.c_str(), "rb")); tries++) usleep(1000);
+    if (!f || fread(id, 1, sizeof id, f) != sizeof id) FAIL("rank 0 did not publish the RCCL id\n");
+    fclose(f);
+  }
+  if (scalce_comm_create_rccl(device, world, rank, id, &comm)) FAIL("%s\n", scalce_comm_error(comm));
+  scalce_comm_barrier(comm, nullptr);
+  if (rank == 0) unlink(idfile.c_str());
+  return comm;
+}
+
+// one mate's input file as a rank holds it, and the bytes [lo, hi) of it that are the rank's records
+struct RankInput {
+  std::string path;
+  Fd fd;
+  uint64_t size = 0, lo = 0, hi = 0;
+};
+// 2. The quality model: the first records of the FILE, the same on every rank (get_quality_stats, compress.cpp:761).
+static void open_rank_inputs(const Options &o, const std::vector<std::string> &files, int nm, bool log, scalce_params &p, RankInput in[2]) {
+  in[0].path = files[0];
+  in[1].path = mate_file(files[0], o.paired ? 1 : 0);
+  for (int m = 0; m < nm; m++) {
+    if (is_gzip(in[m].path)) FAIL("--gpus needs plain (not gzip) input: the file is split by byte ranges\n");
+    MateSource src;
+    src.files.push_back(in[m].path);
+    quality_model(o, src, m, p, log);
+    struct stat st;
+    if (!in[m].fd.open(in[m].path, O_RDONLY) || fstat(in[m].fd.get(), &st) != 0) FAIL("Cannot read file %s\n", in[m].path.c_str());
+    in[m].size = (uint64_t)st.st_size;
+  }
+  if (p.read_len[0] <= 0) FAIL("Cannot determine the read length of %s\n", files[0].c_str());
+}
+// 3. This rank's records of mate m: a line-aligned byte range, the line counts of everybody (one all-gather through the
+// 64 + 64 * 4 words of d_io), then cuts at multiples of four lines (cli_shares.hpp).  K: where every rank's records begin,
+// made from mate 1 and kept for mate 2.
+static void record_range(scalce_comm *comm, hipStream_t s, uint64_t *d_io, int rank, int world, int m, RankInput &in, std::vector<uint64_t> &K) {
+  const int fd = in.fd.get();
+  const uint64_t a = line_start(fd, in.size, world, rank), b = line_start(fd, in.size, world, rank + 1);
+  uint64_t mine[2] = {count_newlines(fd, a, b, std::max(1, std::min(g_threads, 16))), a};
+  std::vector<uint64_t> all((size_t)world * 2);
+  HIPOK(hipMemcpy(d_io, mine, sizeof mine, hipMemcpyHostToDevice));
+  if (scalce_comm_all_gather(comm, d_io, d_io + 64, sizeof mine, s)) FAIL("%s\n", scalce_comm_error(comm));
+  HIPOK(hipStreamSynchronize(s));
+  HIPOK(hipMemcpy(all.data(), d_io + 64, all.size() * 8, hipMemcpyDeviceToHost));
+  const LineRanges ranges(world, all.data());
+  switch (ranges.refusal(m ? &K : nullptr)) {
+    case LineRanges::NOT_WHOLE_RECORDS: FAIL("%s has %llu lines: not a multiple of 4\n", in.path.c_str(), (unsigned long long)ranges.lines());
+    case LineRanges::MATES_DIFFER: FAIL("mates have different record counts\n");
+    case LineRanges::OK: break;
+  }
+  if (m == 0) K = ranges.first_records();
+  in.lo = ranges.offset_of_line(fd, in.size, 4 * K[rank]);
+  in.hi = ranges.offset_of_line(fd, in.size, 4 * K[rank + 1]);
+}
+// 4. The piece into HBM, through two pinned chunks in turn.
+static void upload_piece(RankInput in[2], int nm, hipStream_t s, DBuf d_text[2]) {
+  const size_t CH = 256u << 20;
+  HBuf pin_buf[2];  // (both go at the end of this function, behind the stream's synchronisation)
+  Event ev[2];
+  uint8_t *pin[2];
+  for (int i = 0; i < 2; i++) { HIPOK(pin_buf[i].alloc(CH)); HIPOK(ev[i].create()); pin[i] = pin_buf[i].as<uint8_t>(); }
+  for (int m = 0; m < nm; m++) {
+    const uint64_t n = in[m].hi - in[m].lo;
+    HIPOK(dbuf_alloc(d_text[m], n + 256));
+    uint64_t done = 0;
+    for (int i = 0; done < n; i ^= 1) {
+      HIPOK(hipEventSynchronize(ev[i]));
+      const uint64_t k = std::min<uint64_t>(CH, n - done);
+      if (!pread_parallel(in[m].fd.get(), pin[i], k, in[m].lo + done, 16u << 20, g_threads_io())) FAIL("Read error\n");
+      HIPOK(hipMemcpyAsync(d_text[m].as<uint8_t>() + done, pin[i], k, hipMemcpyHostToDevice, s));
+      HIPOK(hipEventRecord(ev[i], s));
+      done += k;
     }
-  };
-  std::vector<std::thread> pool;
-  for (int t = 1; t < threads; t++) pool.emplace_back(work);
-  work();
-  for (auto &t : pool) t.join();
-  return total;
-}
-// byte offset behind the `skip`-th newline at or after `from`
-static uint64_t skip_lines(int fd, uint64_t from, uint64_t size, uint64_t skip) {
-  std::vector<char> buf(8u << 20);
-  uint64_t p = from;
-  while (skip && p < size) {
-    const ssize_t k = ::pread(fd, buf.data(), (size_t)std::min<uint64_t>(buf.size(), size - p), (off_t)p);
-    if (k <= 0) FAIL("Read error\n");
-    const char *q = buf.data(), *e = q + k;
-    while (skip && (q = static_cast<const char *>(memchr(q, '\n', (size_t)(e - q))))) { skip--; q++; }
-    if (!skip) return p + (uint64_t)(q - buf.data());
-    p += (uint64_t)k;
   }
-  return p;
+  HIPOK(hipStreamSynchronize(s));
 }
-static void pwrite_all(int fd, const void *src, size_t n, uint64_t off) {
-  const uint8_t *p = static_cast<const uint8_t *>(src);
-  while (n) {
-    const ssize_t k = ::pwrite(fd, p, n, (off_t)off);
-    if (k <= 0) FAIL("write failed\n");
-    p += k; n -= (size_t)k; off += (uint64_t)k;
+// 5. The sharded run over the uploaded pieces; the batch holds this rank's streams, res the run-wide counts.
+static scalce_batch *run_sharded(scalce_comm *comm, scalce_ctx *ctx, const scalce_params &p, const RankInput in[2], int nm, DBuf d_text[2],
+                                 hipStream_t s, scalce_shard_result &res) {
+  scalce_batch *b = nullptr;
+  const uint64_t n0 = in[0].hi - in[0].lo, n1 = nm == 2 ? in[1].hi - in[1].lo : 0;
+  const uint64_t rows = n0 / (2 * (uint64_t)p.read_len[0] + 7) + 64;
+  SCOK(ctx, scalce_batch_create(ctx, &p, rows + rows / 3, std::max(n0, n1) + 256, &b));
+  memset(&res, 0, sizeof res);
+  if (scalce_sharded_compress(comm, ctx, b, d_text[0].as<uint8_t>(), n0, nm == 2 ? d_text[1].as<uint8_t>() : nullptr, n1, 0, s, nullptr, &res))
+    exit(1);
+  for (int m = 0; m < nm; m++) d_text[m].release();
+  return b;
+}
+// 6. Every rank writes its pieces of the archive: per file, rank 0 (`lead`) creates it and writes the header, everybody
+// opens it behind a barrier and places its share.
+struct ShareWriter {
+  const Options &o;
+  const scalce_params &p;
+  scalce_ctx *ctx;
+  scalce_batch *b;
+  scalce_comm *comm;
+  hipStream_t s;
+  const int rank;
+  const bool lead;
+  const scalce_shard_result &res;
+  const Shares reads, names;  // records and name bytes per mate-1 bucket
+  std::vector<int32_t> bucket_pattern;
+  std::vector<uint64_t> recsz;  // bytes of a mate-1 record per bucket: the bases its core does not give, and the metadata
+  ShareWriter(const Options &o_, const scalce_params &p_, scalce_ctx *ctx_, scalce_batch *b_, scalce_comm *comm_, hipStream_t s_, int rank_, int world,
+              const scalce_shard_result &res_, const std::vector<uint8_t> &table, bool is_text)
+      : o(o_), p(p_), ctx(ctx_), b(b_), comm(comm_), s(s_), rank(rank_), lead(rank_ == 0), res(res_), reads(res_.counts, res_.nb1, world, rank_),
+        names(res_.name_bytes, res_.nb1, world, rank_), bucket_pattern(res_.nb1), recsz(res_.nb1) {
+    int32_t nst = 0, nbk = 0;
+    scalce_patterns_describe_host(table.data(), table.size(), is_text ? 1 : 0, bucket_pattern.data(), res.nb1, &nst, &nbk);
+    const int L0 = p.read_len[0], sz_meta = L0 > 255 ? 2 : 1;
+    for (uint32_t k = 0; k < res.nb1; k++) {
+      const int lv = bucket_pattern[k] == SCALCE_ROOT_CORE ? 0 : scalce_pattern_length(ctx, bucket_pattern[k]);
+      recsz[k] = (uint64_t)((L0 - lv + 3) / 4 + sz_meta);
+    }
   }
-}
-// Bucket k of a stream holds the units of every rank in rank order: amount[r * nb + k] of rank r.  Per bucket: this rank's
-// amount, the amount of the ranks before it, and the run's.
-struct Shares {
-  std::vector<uint64_t> mine, before, all;
-  Shares(const uint64_t *amount, uint32_t nb, int world, int rank) : mine(nb, 0), before(nb, 0), all(nb, 0) {
-    for (int r = 0; r < world; r++)
-      for (uint32_t k = 0; k < nb; k++) {
-        const uint64_t a = amount[(size_t)r * nb + k];
-        if (r < rank) before[k] += a;
-        if (r == rank) mine[k] = a;
-        all[k] += a;
+  Fd open_out(int m, char ext, const std::vector<uint8_t> &header) const {
+    const std::string fn = archive_path(o.out, m, ext);
+    Fd f;
+    if (lead && !f.open(fn, O_CREAT | O_TRUNC | O_WRONLY, 0644)) FAIL("Cannot create %s\n", fn.c_str());
+    f.release();
+    scalce_comm_barrier(comm, s);
+    if (!f.open(fn, O_WRONLY)) FAIL("Cannot open %s\n", fn.c_str());
+    if (lead) pwrite_all(f.get(), header.data(), header.size(), 0);
+    return f;
+  }
+  void write_reads(int m) const {  // .scalcer: mate 1 in buckets, mate 2 bare rows in mate 1's order
+    const uint64_t w = ((uint64_t)p.read_len[m] + 3) / 4;
+    const std::vector<uint8_t> h = reads_header(o, p.read_len[m]), mine = fetch(ctx, b, SCALCE_OUT_READS, m);
+    const Fd f = open_out(m, 'r', h);
+    if (m == 0) place_share(f.get(), h.size(), mine.data(), reads, [&](size_t k) { return recsz[k]; }, bucket_pattern.data(), lead);
+    else place_share(f.get(), h.size(), mine.data(), reads, [w](size_t) { return w; });
+  }
+  void write_names(int m) const {  // .scalcen (mate 2 repeats mate 1's names, compress.cpp:450-454)
+    const std::vector<uint8_t> h = names_header(o);
+    const Fd f = open_out(m, 'n', h);
+    if (o.use_names) place_share(f.get(), h.size(), fetch(ctx, b, SCALCE_OUT_NAMES, 0).data(), names, [](size_t) { return (uint64_t)1; });
+  }
+  void write_qualities(int m) const {  // .scalceq
+    const uint64_t L = (uint64_t)p.read_len[m];
+    const std::vector<uint8_t> h = qual_header(p.qmap[0].offset);
+    const Fd f = open_out(m, 'q', h);
+    if (!o.no_ac) {  // the table and the symbol count, then the coded blocks of every rank in rank order
+      if (lead) {
+        const std::vector<uint8_t> tb = fetch(ctx, b, SCALCE_OUT_TABLE, m);
+        pwrite_all(f.get(), tb.data(), tb.size(), h.size());
+        const uint64_t total = res.reads_total * L;
+        pwrite_all(f.get(), &total, 8, h.size() + tb.size());
       }
+      uint64_t before = 0;
+      for (int r = 0; r < rank; r++) before += res.coded_bytes[m][r];
+      const std::vector<uint8_t> mine = fetch(ctx, b, SCALCE_OUT_QUAL, m);
+      pwrite_all(f.get(), mine.data(), mine.size(), h.size() + QTABLE_WORDS * 4 + 8 + before);
+    } else {  // -A: the raw q' rows, bucket by bucket in rank order (compress.cpp:389-390)
+      place_share(f.get(), h.size(), fetch(ctx, b, SCALCE_OUT_QSTREAM, m).data(), reads, [L](size_t) { return L; });
+    }
   }
 };
-// This rank's share of a stream that starts at byte `base` of the file, pwritten bucket by bucket at its run-wide place;
-// a unit of bucket k is unit(k) bytes.  With `cores` (mate-1 reads) a bucket with units in the run opens with the 12-byte
-// header [int32 core][int64 units]: rank 0 (`lead`) writes it, and the rank's own bytes carry one per bucket it has units in.
-template <class Unit>
-static void place_share(int fd, uint64_t base, const uint8_t *mine, const Shares &sh, Unit unit, const int32_t *cores = nullptr,
-                        bool lead = false) {
-  const uint64_t h = cores ? 12 : 0;
-  for (size_t k = 0; k < sh.all.size(); k++) {
-    if (cores && !sh.all[k]) continue;
-    if (cores && lead) { uint8_t hd[12]; memcpy(hd, &cores[k], 4); memcpy(hd + 4, &sh.all[k], 8); pwrite_all(fd, hd, 12, base); }
-    const uint64_t u = unit(k);
-    if (sh.mine[k]) { pwrite_all(fd, mine + h, sh.mine[k] * u, base + h + sh.before[k] * u); mine += h + sh.mine[k] * u; }
-    base += h + sh.all[k] * u;
-  }
-}
 
 static int rank_main(const Options &o, const std::vector<std::string> &files, const char *argv0, int rank, int world, const std::string &tag) {
   const bool shm = getenv("SCALCE_COMM") && !strcmp(getenv("SCALCE_COMM"), "shm");
@@ -791,186 +633,33 @@ static int rank_main(const Options &o, const std::vector<std::string> &files, co
   std::vector<uint8_t> table;
   bool is_text = false;
   scalce_ctx *ctx = open_device(o, argv0, device, table, is_text);
-  // communicator
-  scalce_comm *comm = nullptr;
-  if (shm) {
-    if (scalce_comm_create_shm(device, world, rank, ("/scalce_cli_" + tag).c_str(), 1ull << 30, &comm)) FAIL("%s\n", scalce_comm_error(comm));
-  } else {
-    const std::string idfile = o.out + ".rcclid." + tag;
-    uint8_t id[SCALCE_COMM_ID_BYTES];
-    if (rank == 0) {
-      if (scalce_comm_unique_id(id)) FAIL("RCCL is not available\n");
-      FILE *f = fopen((idfile + ".tmp").c_str(), "wb");
-      if (!f || fwrite(id, 1, sizeof id, f) != sizeof id) FAIL("Cannot write %s\n", idfile.c_str());
-      fclose(f);
-      rename((idfile + ".tmp").c_str(), idfile.c_str());
-    } else {
-      FILE *f = nullptr;
-      for (int tries = 0; tries < 60000 && !(f = fopen(idfile.c_str(), "rb")); tries++) usleep(1000);
-      if (!f || fread(id, 1, sizeof id, f) != sizeof id) FAIL("rank 0 did not publish the RCCL id\n");
-      fclose(f);
-    }
-    if (scalce_comm_create_rccl(device, world, rank, id, &comm)) FAIL("%s\n", scalce_comm_error(comm));
-    scalce_comm_barrier(comm, nullptr);
-    if (rank == 0) unlink(idfile.c_str());
-  }
-  // quality model: the first records of the FILE, the same on every rank (get_quality_stats, compress.cpp:761)
+  scalce_comm *comm = open_comm(o, shm, device, world, rank, tag);
   scalce_params p = params_from(o);
-  const std::string path[2] = {files[0], mate_file(files[0], o.paired ? 1 : 0)};
-  int fd[2] = {-1, -1};
-  uint64_t fsize[2] = {0, 0};
-  for (int m = 0; m < nm; m++) {
-    if (is_gzip(path[m])) FAIL("--gpus needs plain (not gzip) input: the file is split by byte ranges\n");
-    MateSource src;
-    src.files.push_back(path[m]);
-    quality_model(o, src, m, p, rank == 0);
-    fd[m] = ::open(path[m].c_str(), O_RDONLY);
-    struct stat st;
-    if (fd[m] < 0 || fstat(fd[m], &st) != 0) FAIL("Cannot read file %s\n", path[m].c_str());
-    fsize[m] = (uint64_t)st.st_size;
-  }
-  if (p.read_len[0] <= 0) FAIL("Cannot determine the read length of %s\n", files[0].c_str());
-  // ---- this rank's records: line-aligned byte ranges, line counts of everybody, then cuts at multiples of four lines
+  RankInput in[2];
+  open_rank_inputs(o, files, nm, rank == 0, p, in);
   Stream s;
   HIPOK(s.create());
-  DBuf d_io_buf;
-  HIPOK(dbuf_alloc(d_io_buf, sizeof(uint64_t) * (64 + 64 * 4)));
-  uint64_t *d_io = d_io_buf.as<uint64_t>();
-  uint64_t lo[2], hi[2];
+  DBuf d_io;
+  HIPOK(dbuf_alloc(d_io, sizeof(uint64_t) * (64 + 64 * 4)));
   std::vector<uint64_t> K;  // rank r starts at record K[r], in every mate
-  for (int m = 0; m < nm; m++) {
-    auto line_start = [&](int r) -> uint64_t {  // first line start at or behind the r-th N-th of the file
-      if (r <= 0) return 0;
-      if (r >= world) return fsize[m];
-      const uint64_t at = fsize[m] / (uint64_t)world * (uint64_t)r;
-      return at ? skip_lines(fd[m], at - 1, fsize[m], 1) : 0;
-    };
-    const uint64_t a = line_start(rank), b = line_start(rank + 1);
-    uint64_t mine[2] = {count_newlines(fd[m], a, b, std::max(1, std::min(g_threads, 16))), a};
-    std::vector<uint64_t> all((size_t)world * 2);
-    HIPOK(hipMemcpy(d_io, mine, sizeof mine, hipMemcpyHostToDevice));
-    if (scalce_comm_all_gather(comm, d_io, d_io + 64, sizeof mine, s)) FAIL("%s\n", scalce_comm_error(comm));
-    HIPOK(hipStreamSynchronize(s));
-    HIPOK(hipMemcpy(all.data(), d_io + 64, all.size() * 8, hipMemcpyDeviceToHost));
-    std::vector<uint64_t> first_line(world + 1, 0);  // run-wide line number at which every tentative range begins
-    for (int r = 0; r < world; r++) first_line[r + 1] = first_line[r] + all[2 * r];
-    if (first_line[world] % 4) FAIL("%s has %llu lines: not a multiple of 4\n", path[m].c_str(), (unsigned long long)first_line[world]);
-    if (m == 1 && first_line[world] != 4 * K[world]) FAIL("mates have different record counts\n");
-    // rank r starts at record K_r = ceil(first line of mate 1's r-th range / 4): the same record in every mate
-    if (m == 0) { K.assign(world + 1, 0); for (int r = 0; r <= world; r++) K[r] = (first_line[r] + 3) / 4; }
-    auto offset_of_line = [&](uint64_t line) -> uint64_t {
-      if (line >= first_line[world]) return fsize[m];
-      int r = 0;
-      while (r + 1 < world && first_line[r + 1] <= line) r++;
-      return skip_lines(fd[m], all[2 * r + 1], fsize[m], line - first_line[r]);
-    };
-    lo[m] = offset_of_line(4 * K[rank]);
-    hi[m] = offset_of_line(4 * K[rank + 1]);
-  }
-  // ---- the piece into HBM
-  DBuf d_text_buf[2];
-  uint8_t *d_text[2] = {nullptr, nullptr};
-  {
-    const size_t CH = 256u << 20;
-    HBuf pin_buf[2];  // (both go at the end of this block, behind the stream's synchronisation)
-    Event ev[2];
-    uint8_t *pin[2];
-    for (int i = 0; i < 2; i++) { HIPOK(pin_buf[i].alloc(CH)); HIPOK(ev[i].create()); pin[i] = pin_buf[i].as<uint8_t>(); }
-    for (int m = 0; m < nm; m++) {
-      const uint64_t n = hi[m] - lo[m];
-      HIPOK(dbuf_alloc(d_text_buf[m], n + 256));
-      d_text[m] = d_text_buf[m].as<uint8_t>();
-      uint64_t done = 0;
-      for (int i = 0; done < n; i ^= 1) {
-        HIPOK(hipEventSynchronize(ev[i]));
-        const uint64_t k = std::min<uint64_t>(CH, n - done);
-        if (!pread_parallel(fd[m], pin[i], k, lo[m] + done, 16u << 20, g_threads_io())) FAIL("Read error\n");
-        HIPOK(hipMemcpyAsync(d_text[m] + done, pin[i], k, hipMemcpyHostToDevice, s));
-        HIPOK(hipEventRecord(ev[i], s));
-        done += k;
-      }
-    }
-    HIPOK(hipStreamSynchronize(s));
-  }
+  for (int m = 0; m < nm; m++) record_range(comm, s, d_io.as<uint64_t>(), rank, world, m, in[m], K);
+  DBuf d_text[2];
+  upload_piece(in, nm, s, d_text);
   const double t1 = now();
-  // ---- the sharded run
-  scalce_batch *b = nullptr;
-  const uint64_t rows = (hi[0] - lo[0]) / (2 * (uint64_t)p.read_len[0] + 7) + 64;
-  SCOK(ctx, scalce_batch_create(ctx, &p, rows + rows / 3, std::max(hi[0] - lo[0], nm == 2 ? hi[1] - lo[1] : 0) + 256, &b));
   scalce_shard_result res;
-  memset(&res, 0, sizeof res);
-  if (scalce_sharded_compress(comm, ctx, b, d_text[0], hi[0] - lo[0], nm == 2 ? d_text[1] : nullptr, nm == 2 ? hi[1] - lo[1] : 0, 0, s,
-                              nullptr, &res))
-    exit(1);
-  for (int m = 0; m < nm; m++) d_text_buf[m].release();
+  scalce_batch *b = run_sharded(comm, ctx, p, in, nm, d_text, s, res);
   const double t2 = now();
-  // ---- every rank writes its pieces of the archive
-  const uint32_t nb1 = res.nb1;
-  std::vector<int32_t> bucket_pattern(nb1);
-  int32_t nst = 0, nbk = 0;
-  scalce_patterns_describe_host(table.data(), table.size(), is_text ? 1 : 0, bucket_pattern.data(), nb1, &nst, &nbk);
-  const Shares reads(res.counts, nb1, world, rank), names(res.name_bytes, nb1, world, rank);
-  std::vector<uint64_t> recsz(nb1);
-  const int L0 = p.read_len[0], sz_meta = L0 > 255 ? 2 : 1;
-  for (uint32_t k = 0; k < nb1; k++) {
-    const int lv = bucket_pattern[k] == SCALCE_ROOT_CORE ? 0 : scalce_pattern_length(ctx, bucket_pattern[k]);
-    recsz[k] = (uint64_t)((L0 - lv + 3) / 4 + sz_meta);
-  }
-  const uint64_t N = res.reads_total;
-  const bool lead = rank == 0;  // rank 0 writes the file headers
-  auto open_out = [&](int m, char ext, const std::vector<uint8_t> &header) {
-    const std::string fn = archive_path(o.out, m, ext);
-    if (lead) {
-      const int f = ::open(fn.c_str(), O_CREAT | O_TRUNC | O_WRONLY, 0644);
-      if (f < 0) FAIL("Cannot create %s\n", fn.c_str());
-      ::close(f);
-    }
-    scalce_comm_barrier(comm, s);
-    const int f = ::open(fn.c_str(), O_WRONLY);
-    if (f < 0) FAIL("Cannot open %s\n", fn.c_str());
-    if (lead) pwrite_all(f, header.data(), header.size(), 0);
-    return f;
-  };
+  const ShareWriter w(o, p, ctx, b, comm, s, rank, world, res, table, is_text);
   for (int m = 0; m < nm; m++) {
-    const uint64_t L = (uint64_t)p.read_len[m], w = (L + 3) / 4;
-    {  // .scalcer: mate 1 in buckets, mate 2 bare rows in mate 1's order
-      const std::vector<uint8_t> h = reads_header(o, p.read_len[m]), mine = fetch(ctx, b, SCALCE_OUT_READS, m);
-      const int f = open_out(m, 'r', h);
-      if (m == 0) place_share(f, h.size(), mine.data(), reads, [&](size_t k) { return recsz[k]; }, bucket_pattern.data(), lead);
-      else place_share(f, h.size(), mine.data(), reads, [w](size_t) { return w; });
-      ::close(f);
-    }
-    {  // .scalcen (mate 2 repeats mate 1's names, compress.cpp:450-454)
-      const std::vector<uint8_t> h = names_header(o);
-      const int f = open_out(m, 'n', h);
-      if (o.use_names) place_share(f, h.size(), fetch(ctx, b, SCALCE_OUT_NAMES, 0).data(), names, [](size_t) { return (uint64_t)1; });
-      ::close(f);
-    }
-    {  // .scalceq
-      const std::vector<uint8_t> h = qual_header(p.qmap[0].offset);
-      const int f = open_out(m, 'q', h);
-      if (!o.no_ac) {  // the table and the symbol count, then the coded blocks of every rank in rank order
-        if (lead) {
-          const std::vector<uint8_t> tb = fetch(ctx, b, SCALCE_OUT_TABLE, m);
-          pwrite_all(f, tb.data(), tb.size(), h.size());
-          const uint64_t total = N * L;
-          pwrite_all(f, &total, 8, h.size() + tb.size());
-        }
-        uint64_t before = 0;
-        for (int r = 0; r < rank; r++) before += res.coded_bytes[m][r];
-        const std::vector<uint8_t> mine = fetch(ctx, b, SCALCE_OUT_QUAL, m);
-        pwrite_all(f, mine.data(), mine.size(), h.size() + QTABLE_WORDS * 4 + 8 + before);
-      } else {  // -A: the raw q' rows, bucket by bucket in rank order (compress.cpp:389-390)
-        place_share(f, h.size(), fetch(ctx, b, SCALCE_OUT_QSTREAM, m).data(), reads, [L](size_t) { return L; });
-      }
-      ::close(f);
-    }
+    w.write_reads(m);
+    w.write_names(m);
+    w.write_qualities(m);
   }
   scalce_comm_barrier(comm, s);
   const double t3 = now();
-  if (lead) {
-    LOG("\tDone with file %s, %llu reads found\n", files[0].c_str(), (unsigned long long)N);
-    log_statistics(o, p, N, reads.all[nb1 - 1]);
+  if (w.lead) {
+    LOG("\tDone with file %s, %llu reads found\n", files[0].c_str(), (unsigned long long)res.reads_total);
+    log_statistics(o, p, res.reads_total, w.reads.all[res.nb1 - 1]);
     LOG("\tGPUs: %d, spill chunks: %u, tie-break rounds: %u\n", world, res.chunks_total, res.rounds);
     LOG("\tTime elapsed: %.2f s (split + read + upload %.2f, sharded hot path %.2f, download + write %.2f)\n", t3 - t0, t1 - t0, t2 - t1, t3 - t2);
   }
@@ -1036,18 +725,18 @@ static std::string materialize_inputs(Options &o, const std::vector<std::string>
 // -c gz behind --gpus: the ranks write the plain archive at computed offsets; the streams the reference would have sent
 // through its gzip writer are then rewritten as gzip members by this process's threads
 static void gzip_in_place(const std::string &path) {
-  const int fd = ::open(path.c_str(), O_RDONLY);
-  if (fd < 0) FAIL("Cannot read %s\n", path.c_str());
+  Fd in;
+  if (!in.open(path, O_RDONLY)) FAIL("Cannot read %s\n", path.c_str());
   OutFile out;
   out.open(path + ".gz.tmp", true);
   std::vector<uint8_t> buf(256u << 20);
   for (;;) {
-    const ssize_t k = ::read(fd, buf.data(), buf.size());
+    const ssize_t k = ::read(in.get(), buf.data(), buf.size());
     if (k < 0) FAIL("Read error on %s\n", path.c_str());
     if (k == 0) break;
     out.write(buf.data(), (size_t)k);
   }
-  ::close(fd);
+  in.release();
   out.close();
   if (rename((path + ".gz.tmp").c_str(), path.c_str()) != 0) FAIL("Cannot replace %s\n", path.c_str());
 }
@@ -1056,7 +745,7 @@ static int multi_gpu_compress(const Options &o_in, const std::vector<std::string
   if (o_in.gpus > 64) FAIL("--gpus: at most 64\n");
   LOG("Preprocessing FASTQ files ...\n");
   const std::string tag = std::to_string(getpid()) + "_" + std::to_string((long)time(nullptr));
-  set_threads(o_in, 1);
+  set_threads(o_in.threads, 1);
   Options o = o_in;
   o.container = 0;  // the ranks write plain; -c gz is applied to the finished files below
   std::vector<std::string> files = files_in;
@@ -1065,7 +754,7 @@ static int multi_gpu_compress(const Options &o_in, const std::vector<std::string
     files.assign(1, materialize_inputs(o, files_in, tag));
     LOG("\t%zu input file(s) per mate written out as one plain file under %s (%.2f s)\n", files_in.size(), o.temp.c_str(), now() - t0);
   }
-  set_threads(o, o.gpus);  // (the ranks share the host)
+  set_threads(o.threads, o.gpus);  // (the ranks share the host)
   std::vector<pid_t> kids;
   for (int r = 0; r < o.gpus; r++) {
     const pid_t pid = fork();
@@ -1092,17 +781,14 @@ static int multi_gpu_compress(const Options &o_in, const std::vector<std::string
     }
   }
   if (bad) {  // what the ranks had written so far is not an archive: nothing stays behind under the output name
-    for (int m = 0; m < (o.paired ? 2 : 1); m++)
-      for (char ext : {'r', 'n', 'q'}) unlink(archive_path(o.out, m, ext).c_str());
+    for_each_archive_file(o, "rnq", [](char, const std::string &fn) { unlink(fn.c_str()); });
     fprintf(stderr, "(ERROR) a rank failed\n");
     return 1;
   }
   if (o_in.container != 0) {
-    set_threads(o_in, 1);
+    set_threads(o_in.threads, 1);
     const double t0 = now();
-    for (int m = 0; m < (o.paired ? 2 : 1); m++)
-      for (char ext : {'r', 'n', 'q'})
-        if (gz_container(o_in, ext)) gzip_in_place(archive_path(o.out, m, ext));
+    for_each_archive_file(o, "rnq", [&](char ext, const std::string &fn) { if (gz_container(o_in, ext)) gzip_in_place(fn); });
     LOG("\tgzip containers written by %d host threads: %.2f s\n", g_threads, now() - t0);
   }
   LOG("Done!\n");
@@ -1115,155 +801,55 @@ static std::string scalce_name(std::string path, char c) {  // get_file_name, de
   if (p != std::string::npos && p + 7 < path.size()) path[p + 7] = c;
   return path;
 }
-// one file of the archive behind scalce_read_fn: a gzip container through the parallel reader, which streams (no seek), or
-// a plain file through pread
-struct ArchiveFile {
-  std::string path;
-  bool gz = false;
-  scalce_host::ParGz z;
-  int fd = -1;
-  uint64_t off = 0;
-  void open(const std::string &p) {
-    path = p;
-    gz = is_gzip(p);  // container sniffing (decompress.cpp:99-113)
-    if (gz) { if (!z.open(p, g_threads_gz())) FAIL("Cannot read file %s\n", p.c_str()); }
-    else if ((fd = ::open(p.c_str(), O_RDONLY)) < 0) FAIL("Cannot read file %s\n", p.c_str());
-  }
-  static int64_t read(void *user, void *dst, uint64_t cap) {
-    ArchiveFile *f = static_cast<ArchiveFile *>(user);
-    if (f->gz) return f->z.read(dst, cap);
-    const ssize_t k = ::pread(f->fd, dst, (size_t)std::min<uint64_t>(cap, 1u << 30), (off_t)f->off);
-    if (k > 0) f->off += (uint64_t)k;
-    return (int64_t)k;
-  }
-  // scalce_skip_fn of a plain file: the offset moves, up to the file's end
-  static int64_t skip(void *user, uint64_t nbytes) {
-    ArchiveFile *f = static_cast<ArchiveFile *>(user);
-    struct stat st;
-    if (f->gz || fstat(f->fd, &st) != 0) return -1;
-    const uint64_t size = (uint64_t)st.st_size, k = std::min(nbytes, size > f->off ? size - f->off : 0);
-    f->off += k;
-    return (int64_t)k;
-  }
-  ~ArchiveFile() { if (fd >= 0) ::close(fd); }
-};
-
-// the text of the windows, as they arrive, into OUT_<m>.fastq -- or, with -S n, into a new part every n records (pairs
-// under -i; decompress.cpp:276-287), cut at the window's record offsets, across window boundaries
-struct TextSink {
-  const Options *o = nullptr;
-  struct PerMate {
-    OutFile f;
-    bool open = false;
-    int part = 0;
-    uint64_t in_part = 0, files = 0;
-    char fn[4096];
-  } pm[2];
-  void open_next(int m) {
-    PerMate &x = pm[m];
-    x.part++;
-    if (o->out == "-") snprintf(x.fn, sizeof x.fn, "-");
-    else if (o->split) snprintf(x.fn, sizeof x.fn, "%s.%d_%d.fastq", o->out.c_str(), x.part, m + 1);
-    else snprintf(x.fn, sizeof x.fn, "%s_%d.fastq", o->out.c_str(), m + 1);
-    x.f.open(x.fn, false);
-    x.open = true;
-    x.in_part = 0;
-    x.files++;
-  }
-  void close_part(int m) {
-    PerMate &x = pm[m];
-    if (x.f.f == stdout) fflush(stdout);
-    x.f.close();
-    x.open = false;
-    LOG("Created %s with %lld %s\n", x.fn, (long long)x.in_part, o->interleave ? "pairs" : "reads");
-  }
-  static int write(void *user, int m, uint64_t, uint64_t nrec, const void *text, uint64_t nbytes, const uint64_t *roff) {
-    TextSink *t = static_cast<TextSink *>(user);
-    PerMate &x = t->pm[m];
-    const uint8_t *b = static_cast<const uint8_t *>(text);
-    if (!t->o->split) {
-      if (!x.open) t->open_next(m);
-      x.f.write(b, nbytes);
-      x.in_part += nrec;
-      if (x.f.f == stdout) fflush(stdout);  // -o -: a window is out when it has arrived
-      return 0;
+// The archive named by its .scalcen: every mate's three files open behind the read callbacks, and the length streams of a
+// variable-length archive.
+struct Archive {
+  std::string base[2];
+  bool has_lens[2] = {false, false};
+  ArchiveFile files[2][3], lens[2];
+  scalce_read_fn rd[2][3];
+  void *user[2][3];
+  Archive(const Options &o, const std::string &path, int nm) {
+    base[0] = base[1] = path;
+    if (o.pairs() && !second_file(path, base[1])) FAIL("Cannot get file name for paired end for file %s.\n", path.c_str());
+    // a variable-length archive has a length stream next to the other three: without the file, the reads come back padded
+    for (int m = 0; m < nm; m++) {
+      const std::string lpath = scalce_name(base[m], 'l');
+      struct stat lst;
+      if (stat(lpath.c_str(), &lst) != 0) continue;
+      if (o.interleave) FAIL("%s: an archive of variable-length reads is decompressed mate by mate (-r), not interleaved (-i)\n", lpath.c_str());
+      if (o.fasta || o.no_qual) FAIL("%s: an archive of variable-length reads is decompressed with its qualities, not with -Q / -f\n", lpath.c_str());
+      has_lens[m] = true;
     }
-    for (uint64_t k = 0; k < nrec;) {
-      if (!x.open) t->open_next(m);
-      const uint64_t take = std::min<uint64_t>((uint64_t)t->o->split - x.in_part, nrec - k);
-      x.f.write(b + roff[k], roff[k + take] - roff[k]);
-      x.in_part += take;
-      k += take;
-      if (x.in_part == (uint64_t)t->o->split) t->close_part(m);
-    }
-    return 0;
-  }
-  void finish(int m) {  // (an archive without records still gives its one empty file)
-    if (!pm[m].open && !pm[m].files) open_next(m);
-    if (pm[m].open) close_part(m);
+    static const char ext[3] = {'r', 'n', 'q'};
+    for (int m = 0; m < 2; m++)
+      for (int k = 0; k < 3; k++) {
+        rd[m][k] = m < nm ? ArchiveFile::read : nullptr;
+        user[m][k] = &files[m][k];
+        if (m < nm) files[m][k].open(scalce_name(base[m], ext[k]));
+      }
+    for (int m = 0; m < nm; m++)
+      if (has_lens[m]) lens[m].open(scalce_name(base[m], 'l'));
   }
 };
-
 // One path for every archive: scalce_stream_decompress moves it through the device in windows of whole records.  The read
 // callbacks hand out the files as they are read, the write callback writes each window's text as it arrives.
 static int do_decompress(const Options &o, const std::string &path, scalce_ctx *ctx) {
   const double t0 = now();
   const int nm = o.pairs() ? 2 : 1;
-  std::string base[2] = {path, path};
-  if (o.pairs() && !second_file(path, base[1])) FAIL("Cannot get file name for paired end for file %s.\n", path.c_str());
-  // a variable-length archive has a length stream next to the other three: without the file, the reads come back padded
-  bool has_lens[2] = {false, false};
-  for (int m = 0; m < nm; m++) {
-    const std::string lpath = scalce_name(base[m], 'l');
-    struct stat lst;
-    if (stat(lpath.c_str(), &lst) != 0) continue;
-    if (o.interleave) FAIL("%s: an archive of variable-length reads is decompressed mate by mate (-r), not interleaved (-i)\n", lpath.c_str());
-    if (o.fasta || o.no_qual) FAIL("%s: an archive of variable-length reads is decompressed with its qualities, not with -Q / -f\n", lpath.c_str());
-    has_lens[m] = true;
-  }
-  ArchiveFile files[2][3], lens[2];
-  scalce_read_fn rd[2][3];
-  void *user[2][3];
-  static const char ext[3] = {'r', 'n', 'q'};
-  for (int m = 0; m < 2; m++)
-    for (int k = 0; k < 3; k++) {
-      rd[m][k] = m < nm ? ArchiveFile::read : nullptr;
-      user[m][k] = &files[m][k];
-      if (m < nm) files[m][k].open(scalce_name(base[m], ext[k]));
-    }
-  scalce_unpack_params p;
-  memset(&p, 0, sizeof p);
-  for (int m = 0; m < nm; m++) {
-    if (!has_lens[m]) continue;
-    lens[m].open(scalce_name(base[m], 'l'));
-    p.len_rd[m] = ArchiveFile::read;
-    p.len_user[m] = &lens[m];
-    p.len_skip[m] = lens[m].gz ? nullptr : ArchiveFile::skip;
-  }
-  p.mates = nm;
-  p.interleave = o.interleave;
-  p.no_qualities = o.fasta || o.no_qual;  // -d -Q / -d -f: two-line records, whatever the .scalceq holds (decompress.cpp:159-168)
-  p.mate_digit = o.pairs();
-  p.ignore_names = !o.use_names;          // decompress.cpp:219-237
-  p.library = o.library.c_str();
-  p.split = o.split;
-  p.window_text_bytes = o.window;
+  Archive ar(o, path, nm);
+  const scalce_unpack_params p = unpack_params_from(o, nm, ar.lens, ar.has_lens);
+  const scalce_unpack_range rg = unpack_range_from(o, nm, ar.files);
   TextSink sink;
-  sink.o = &o;
-  scalce_unpack_range rg;
-  memset(&rg, 0, sizeof rg);
-  rg.first_record = o.range_first;
-  rg.nrecords = o.range_count;
-  for (int m = 0; m < nm; m++)
-    for (int k = 0; k < 3; k++) rg.skip[m][k] = files[m][k].gz ? nullptr : ArchiveFile::skip;
+  sink.out = o.out; sink.split = o.split; sink.interleave = o.interleave;
   scalce_unpack_stats st;
   scalce_unpack_range_stats rs;
   char err[1024] = "";
-  const int rc = scalce_stream_decompress_range(ctx, &p, &rg, rd, user, TextSink::write, &sink, &st, &rs, err, sizeof err);
+  const int rc = scalce_stream_decompress_range(ctx, &p, &rg, ar.rd, ar.user, TextSink::write, &sink, &st, &rs, err, sizeof err);
   if (rc) {
     // (parts already written stay where they are)
     if (st.error_wants_file && st.error_mate >= 0 && st.error_stream >= 0)
-      FAIL("%s %s\n", st.error_stream == 0 ? base[st.error_mate].c_str() : files[st.error_mate][st.error_stream].path.c_str(), err);
+      FAIL("%s %s\n", st.error_stream == 0 ? ar.base[st.error_mate].c_str() : ar.files[st.error_mate][st.error_stream].path.c_str(), err);
     fprintf(stderr, "%s%s\n", strncmp(err, "(ERROR)", 7) ? "(ERROR) " : "", err);
     exit(1);
   }
@@ -1282,10 +868,38 @@ static int do_decompress(const Options &o, const std::string &path, scalce_ctx *
   return 0;
 }
 
-int main(int argc, char **argv) {
-  const double t_main = now();
-  Options o;
-  LOG("SCALCE %s [MI355X / HIP]\n", SCALCE_VERSION);
+// ---- the command line ------------------------------------------------------------------------------------------
+// The three numbers with a form of their own.  Each accepts what it always did, so they stay three.
+static uint64_t bucket_set_size_arg(const char *arg) {  // -B NUM[M|G]
+  std::string s = arg;
+  const char al = s.empty() ? 0 : s.back();
+  uint64_t unit = 1024 * 1024ull;
+  if (al == 'G') unit *= 1024; else if (al != 'M') FAIL("Size parameter must be ended with G or M.\n");
+  s.pop_back();
+  return unit * (uint64_t)atoi(s.c_str());
+}
+static uint64_t window_arg(const char *arg) {  // --window NUM[K|M|G]
+  char *e = nullptr;
+  const unsigned long long v = strtoull(arg, &e, 10);
+  const uint64_t unit = *e == 'K' ? 1ull << 10 : *e == 'M' ? 1ull << 20 : *e == 'G' ? 1ull << 30 : 1;
+  if (e == arg || !v || (*e && (unit == 1 || e[1]))) FAIL("--window takes a positive number of bytes, optionally ended with K, M or G.\n");
+  return v * unit;
+}
+static void records_arg(const char *arg, Options &o) {  // --records FIRST[:COUNT]
+  // both plain decimal numbers (strtoull alone would take a sign, blanks and an empty string)
+  auto number = [](const char *b, const char *e, uint64_t &v) {
+    if (b == e || e - b > 19) return false;
+    v = 0;
+    for (; b != e; b++) { if (*b < '0' || *b > '9') return false; v = v * 10 + (uint64_t)(*b - '0'); }
+    return true;
+  };
+  const char *colon = strchr(arg, ':'), *end = arg + strlen(arg);
+  if (!number(arg, colon ? colon : end, o.range_first) || (colon && !number(colon + 1, end, o.range_count)))
+    FAIL("--records takes FIRST or FIRST:COUNT, two non-negative numbers of records.\n");
+  o.has_range = true;
+}
+// false: the run ends here with status 0 (-v, -h, an unknown option)
+static bool parse_options(int argc, char **argv, Options &o) {
   static struct option long_opt[] = {{"help", 0, 0, 'h'}, {"lossy-percentage", 1, 0, 'p'}, {"decompress", 0, 0, 'd'},
                                      {"compression", 1, 0, 'c'}, {"output", 1, 0, 'o'}, {"sample-size", 1, 0, 's'},
                                      {"no-qualities", 0, 0, 'Q'}, {"patterns", 1, 0, 'P'}, {"temp-directory", 1, 0, 't'},
@@ -1298,8 +912,8 @@ int main(int argc, char **argv) {
   int opt;
   while ((opt = getopt_long(argc, argv, "vhp:T:dc:o:fs:t:B:rQAn:P:S:i", long_opt, 0)) != -1) {
     switch (opt) {
-      case 'v': return 0;
-      case 'h': fputs(HELP_TEXT, stdout); return 0;
+      case 'v': return false;
+      case 'h': fputs(HELP_TEXT, stdout); return false;
       case 'A': o.no_ac = true; break;
       case 'f': o.fasta = true; break;
       case 'Q': o.no_qual = true; break;
@@ -1309,14 +923,7 @@ int main(int argc, char **argv) {
         else if (!strcmp(optarg, "bz")) FAIL("bzip2 containers are outside this build's scope (SURVEY.md section 2, #18: host-side container code); use gz or no\n");
         else FAIL("Unknown compression mode. See help for details.\n");
         break;
-      case 'B': {
-        std::string s = optarg;
-        const char al = s.empty() ? 0 : s.back();
-        uint64_t unit = 1024 * 1024ull;
-        if (al == 'G') unit *= 1024; else if (al != 'M') FAIL("Size parameter must be ended with G or M.\n");
-        s.pop_back();
-        o.bucket_set_size = unit * (uint64_t)atoi(s.c_str());
-      } break;
+      case 'B': o.bucket_set_size = bucket_set_size_arg(optarg); break;
       case 'p': o.lossy = atoi(optarg); break;
       case 'T': o.threads = atoi(optarg); break;
       case 'S': o.split = atoi(optarg); break;
@@ -1330,37 +937,21 @@ int main(int argc, char **argv) {
       case 'n': o.use_names = false; o.library = optarg; break;
       case 1000: o.patterns_bin = optarg; break;
       case 1001: o.gpus = atoi(optarg); break;
-      case 1002: {
-        char *e = nullptr;
-        const unsigned long long v = strtoull(optarg, &e, 10);
-        const uint64_t unit = *e == 'K' ? 1ull << 10 : *e == 'M' ? 1ull << 20 : *e == 'G' ? 1ull << 30 : 1;
-        if (e == optarg || !v || (*e && (unit == 1 || e[1]))) FAIL("--window takes a positive number of bytes, optionally ended with K, M or G.\n");
-        o.window = v * unit;
-      } break;
-      case 1003: {
-        // FIRST[:COUNT], both plain decimal numbers (strtoull alone would take a sign, blanks and an empty string)
-        auto number = [](const char *b, const char *e, uint64_t &v) {
-          if (b == e || e - b > 19) return false;
-          v = 0;
-          for (; b != e; b++) { if (*b < '0' || *b > '9') return false; v = v * 10 + (uint64_t)(*b - '0'); }
-          return true;
-        };
-        const char *colon = strchr(optarg, ':'), *end = optarg + strlen(optarg);
-        if (!number(optarg, colon ? colon : end, o.range_first) || (colon && !number(colon + 1, end, o.range_count)))
-          FAIL("--records takes FIRST or FIRST:COUNT, two non-negative numbers of records.\n");
-        o.has_range = true;
-      } break;
+      case 1002: o.window = window_arg(optarg); break;
+      case 1003: records_arg(optarg, o); break;
       case 1004: o.varlen = true; break;
       case 1005:
         o.max_length = atoi(optarg);
         if (o.max_length < 1 || o.max_length > 2498) FAIL("--max-length takes the longest read's number of bases, 1 to 2498.\n");
         o.varlen = true;
         break;
-      default: fputs(HELP_TEXT, stdout); return 0;
+      default: fputs(HELP_TEXT, stdout); return false;
     }
   }
-  std::vector<std::string> files(argv + optind, argv + argc);
-  // check_arguments, main.cpp:120-164
+  return true;
+}
+// check_arguments, main.cpp:120-164, and what this build refuses; all of it before anything touches a device
+static void check_arguments(const Options &o, const std::vector<std::string> &files) {
   if (o.interleave && o.paired) FAIL("Interleaved option (-i) cannot be used with paired-end option (-r).\n");
   if (o.out.empty()) FAIL("No output file specified.\n");
   if (!o.use_names && o.library.empty()) FAIL("No library name specified.\n");
@@ -1385,6 +976,15 @@ int main(int argc, char **argv) {
   }
   if (o.gpus > 1 && !o.decompress && o.interleave)
     FAIL("-i runs on one GPU: --gpus %d is not available for interleaved input\n", o.gpus);
+}
+
+int main(int argc, char **argv) {
+  const double t_main = now();
+  Options o;
+  LOG("SCALCE %s [MI355X / HIP]\n", SCALCE_VERSION);
+  if (!parse_options(argc, argv, o)) return 0;
+  const std::vector<std::string> files(argv + optind, argv + argc);
+  check_arguments(o, files);
   if (o.gpus > 1 && !o.decompress) {  // forks before anything touches a GPU
     // (a run that -B does not cut anywhere is one chunk: scalce_sharded_compress sends all its rows to rank 0)
     return multi_gpu_compress(o, files, argv[0]);
@@ -1392,7 +992,7 @@ int main(int argc, char **argv) {
   std::vector<uint8_t> table;
   bool is_text = false;
   scalce_ctx *ctx = open_device(o, argv[0], 0, table, is_text);
-  set_threads(o, 1);
+  set_threads(o.threads, 1);
   const double t_ready = now();
   const int rc = o.decompress ? do_decompress(o, files[0], ctx) : do_compress(o, files, ctx);
   scalce_ctx_destroy(ctx);
