@@ -170,6 +170,7 @@ int scalce_batch_reset(scalce_batch *b);
  * read and name streams while the coder works.  errbuf receives the message on failure. */
 #define SCALCE_STREAM_LEAN 1
 #define SCALCE_STREAM_DEFER_ENTROPY 2
+#define SCALCE_STREAM_KEEP_ORDER 4  /* scalce_batch_set_keep_order on the run's batch: SCALCE_OUT_PERM outlives the lean releases */
 typedef int64_t (*scalce_read_fn)(void *user, void *dst, uint64_t cap);
 typedef struct {
   double total_s, read_wait_s, h2d_wait_s, front_s, order_s, emit_s, entropy_s;
@@ -182,6 +183,9 @@ int scalce_stream_compress(scalce_ctx *ctx, const scalce_params *p, scalce_read_
  * exists, rows and sort scratch once the records are emitted): outputs 5, 6, 9 become unavailable, runs sized for most
  * of HBM fit. */
 void scalce_batch_set_lean(scalce_batch *b, int lean);
+/* on = 1: the permutation is an output of the run (the order stream of --keep-order): SCALCE_OUT_PERM stays valid behind
+ * scalce_batch_emit and scalce_batch_finish whether the batch is lean or not.  Nothing else changes. */
+int scalce_batch_set_keep_order(scalce_batch *b, int on);
 /* Row layout of the batch.  A single-end batch with names keeps ONE row per read -- q' | name cell | packed bases, what the
  * reference keeps per read in its bucket blob (reads.h:52-58, compress.cpp:675-706) -- so that the emit stage reaches
  * everything it reorders through one random access.  on = 0 (before anything is ingested) goes back to separate arrays whose
@@ -569,6 +573,68 @@ int scalce_stream_decompress_range(scalce_ctx *ctx, const scalce_unpack_params *
  * behind them -- n * read_len, plus the stream's trailing symbols (fewer than a record) when the range reaches the last record,
  * as a whole run decodes them.  The decoder is launched for out[2] + out[3] symbols. */
 int scalce_range_plan_quality(int read_len, uint64_t first, uint64_t n, uint64_t total_syms, uint64_t out[4]);
+
+/* ---- the input order back (archives made with --keep-order; kernels_restore.hpp, stream_decode.cpp) ---------------------
+ * The order stream (PREFIX_1.scalceo out of its container): the 8 magic bytes, int32 4 (entry width), int32 0, int64 N, then
+ * N little-endian u32 -- entry k is the input index of the k-th record (pair) of the archive, SCALCE_OUT_PERM.  On the way
+ * back the records of a window belong at places spread over the whole output, so the output is cut into S STRIPES of R
+ * consecutive input indices and the text travels twice: each window's records are grouped by stripe on the device and
+ * appended to a spill; then, stripe by stripe, every window's share is read back, put in its places on the device and handed
+ * to wr.  Memory follows the window; the text is written twice and read once.
+ *
+ * The device building blocks only enqueue on `stream`, allocate nothing and wait for nothing.
+ *
+ * scalce_records_permute: output record r is input record d_source[r] (an entry >= nrecords gives an empty record);
+ *   d_out_offsets (nrecords + 1) is the scan of the permuted lengths.  d_text: any byte address; text_bytes: the bytes of
+ *   d_text that hold the records (d_record_offsets[nrecords] <= text_bytes); d_out 16-byte aligned, nothing is stored at or
+ *   past out_cap nor past the text's end; d_ws: scalce_records_permute_ws_bytes(nrecords) bytes.
+ * scalce_order_group: d_source lists the window's records 0 .. nrecords - 1 grouped by stripe d_index[i] / stripe_records,
+ *   stable within a stripe; d_stripe_counts[s] (nstripes entries, nstripes <= 65536) how many fell into stripe s; *d_bad is
+ *   cleared, then set when an index is >= total_records (such a record is counted in the last stripe).  d_ws:
+ *   scalce_order_group_ws_bytes(nrecords, nstripes) bytes.
+ * scalce_order_place: d_source[d_index[i] - base] = i for the m records of a stripe (d_source: expect entries; a place that
+ *   stays empty holds ~0); *d_bad is cleared, then set when an index lies outside [base, base + expect), when two records
+ *   claim one place, or when a place stays empty.
+ * scalce_order_gather: d_out[k] = d_in[d_source[k]], the order entries of the grouped records.
+ * scalce_order_plan (no device call): out = {R, S}; R = max(1, window_text_bytes / max_record_bytes), raised where needed so
+ *   that S = ceil(total_records / R) <= 65536. */
+uint64_t scalce_records_permute_ws_bytes(uint64_t nrecords);
+int scalce_records_permute(scalce_ctx *ctx, const uint8_t *d_text, const uint64_t *d_record_offsets, uint64_t nrecords,
+                           uint64_t text_bytes, const uint32_t *d_source, uint8_t *d_out, uint64_t out_cap,
+                           uint64_t *d_out_offsets, void *d_ws, void *stream);
+uint64_t scalce_order_group_ws_bytes(uint64_t nrecords, uint64_t nstripes);
+int scalce_order_group(scalce_ctx *ctx, const uint32_t *d_index, uint64_t nrecords, uint64_t stripe_records, uint64_t total_records,
+                       uint64_t nstripes, uint32_t *d_source, uint32_t *d_stripe_counts, uint32_t *d_bad, void *d_ws, void *stream);
+int scalce_order_place(scalce_ctx *ctx, const uint32_t *d_index, uint64_t m, uint64_t base, uint64_t expect, uint32_t *d_source,
+                       uint32_t *d_bad, void *stream);
+int scalce_order_gather(scalce_ctx *ctx, const uint32_t *d_in, const uint32_t *d_source, uint64_t n, uint32_t *d_out, void *stream);
+int scalce_order_plan(uint64_t total_records, uint64_t window_text_bytes, uint64_t max_record_bytes, uint64_t out[2]);
+
+/* scalce_stream_decompress with the input order restored.  order_rd[m] delivers the order stream, header included, once per
+ * mate pass: two mates that are not interleaved go one after the other and each reads it from the start; interleaved, only
+ * [0] is used and an entry counts pairs.  wr receives the text in INPUT order: first_record is the input index of the first
+ * record handed over, a call holds one stripe.  spill_dir: where the two spill files are made (and unlinked at once).
+ * Errors, besides those of scalce_stream_decompress: "(ERROR) truncated order stream", "(ERROR) is not a scalce order
+ * stream", "(ERROR) order stream holds <n> entries, the archive <m> records", "(ERROR) order stream is not a permutation of
+ * the records", and a spill file that cannot be made or written (error_stream 4 names the order stream). */
+typedef struct {
+  scalce_read_fn order_rd[2];
+  void *order_user[2];
+  const char *spill_dir;
+} scalce_restore_params;
+typedef struct {
+  uint64_t records;         /* restored (per mate pass: the archive's records or pairs) */
+  uint64_t stripes;         /* S */
+  uint64_t stripe_records;  /* R */
+  uint64_t spilled_bytes;   /* text and record words written to the spill, all mate passes */
+  double group_pass_s;      /* wall time of the window loop (decode, group, spill) */
+  double stripe_pass_s;     /* wall time of the stripe loop (read back, place, write) */
+  double spill_write_s, spill_read_s;  /* inside write(2) / pread(2) on the spill files */
+  double place_wait_s;      /* the stripe loop waiting for the device (upload, place, permute, download) */
+} scalce_restore_stats;
+int scalce_stream_decompress_restore(scalce_ctx *ctx, const scalce_unpack_params *p, const scalce_restore_params *rp,
+                                     scalce_read_fn rd[2][3], void *user[2][3], scalce_write_fn wr, void *wr_user,
+                                     scalce_unpack_stats *stats, scalce_restore_stats *restore_stats, char *errbuf, size_t errcap);
 
 /* ---- runs sharded over several GPUs: one process per GPU, ONE archive -----------------------------------------
  * The reference has no distributed mode; what it carries across reads is what ranks exchange (see comm.cpp).  The

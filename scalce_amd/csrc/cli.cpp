@@ -26,6 +26,7 @@
 #include "../../include/scalce_hip.h"
 #include "hip_own.hpp"
 #include "lenstream.hpp"
+#include "orderstream.hpp"
 #include "cli_io.hpp"
 #include "cli_input.hpp"
 #include "cli_shares.hpp"
@@ -48,6 +49,9 @@ struct Options {
   uint64_t range_first = 0, range_count = ~0ull;
   bool varlen = false;                    // --variable-length: reads of 0 .. L bases, padded to L on the device, lengths in PREFIX_<m>.scalcel
   int max_length = 0;                     // --max-length NUM: L given, not taken from the sample (implies --variable-length)
+  bool keep_order = false;                // --keep-order: the input index of every record of the archive, in PREFIX_1.scalceo
+  bool archive_order = false;             // -d --archive-order: a .scalceo next to the archive is ignored
+  bool temp_given = false;                // -t was given (the default of `temp` is the reference's)
   int gpus = 1;                           // --gpus N: one process per GPU, ONE archive (plain-text input, -c no)
   int container = 1;                      // 0 plain, 1 gzip (main.cpp:181-184 at -T 1)
   uint64_t first_file_bytes[2] = {0, 0};  // --gpus over several files written out as one: where the first file ends (the
@@ -74,6 +78,10 @@ static const char *HELP_TEXT =
     "                              of the quality sample and its length kept in OUTPUT_<m>.scalcel; the other files are those\n"
     "                              of the padded reads.  Decompression finds the .scalcel by itself.  Not with -i, -f, -Q, --gpus\n"
     "      --max-length NUM        the longest read, when the sample may not hold it (implies --variable-length)\n"
+    "      --keep-order            keep the order of the input: the input index of every record (pair) of the archive goes into\n"
+    "                              OUTPUT_1.scalceo, every other file is the one the run without the option writes.  Decompression\n"
+    "                              finds the .scalceo by itself and writes the records in the order they came in.  Not with --gpus\n"
+    "      --archive-order         decompression: ignore the .scalceo, write the records in the archive's order\n"
     "  -p, --lossy-percentage INT  lossy quality transform, 0..100 (default 0)\n"
     "  -s, --sample-size INT       records sampled for the quality model (default 100000)\n"
     "  -B, --bucket-set-size NUM[M|G]  bucket storage that triggers a spill chunk (default 4G); order follows the reference\n"
@@ -81,7 +89,8 @@ static const char *HELP_TEXT =
     "  -T, --threads INT           host threads that read plain input and deflate the gz containers (default: cores - 1,\n"
     "                              at most 64);\n"
     "                              the hot path itself runs on the GPU\n"
-    "  -t, --temp-directory STR    accepted for compatibility (nothing is spilled)\n"
+    "  -t, --temp-directory STR    where decompression spills while it restores the input order (two unnamed files; default:\n"
+    "                              the directory of OUTPUT, or $TMPDIR for -o -) and where --gpus writes joined input files\n"
     "  -S, --split-reads INT       decompression: reads per output part\n"
     "      --window NUM[K|M|G]     decompression: bytes of FASTQ text per window (default 1G; -Q counts a record as its FASTQ).  The archive moves through the\n"
     "                              device in windows of whole records -- at least one record each --, so memory follows the\n"
@@ -89,7 +98,8 @@ static const char *HELP_TEXT =
     "      --records FIRST[:COUNT] decompression: only COUNT records (pairs under -r / -i; to the end without COUNT) from record\n"
     "                              FIRST on, counted from 0 in the order -d writes them.  What lies in front is passed over, not\n"
     "                              decoded (plain files seek); -S parts and made-up names (-n) count from FIRST; a file that\n"
-    "                              is cut short behind the range is not noticed\n"
+    "                              is cut short behind the range is not noticed.  Counts in the archive's order: with a .scalceo\n"
+    "                              next to the archive it needs --archive-order\n"
     "  -d, --decompress    -v, --version    -h, --help\n"
     "      --gpus N                compress on N GPUs, one process each, into ONE archive that is byte for byte the archive of\n"
     "                              one GPU (and of the reference at -T 1 with the same -B); input: one plain FASTQ file (pair), -c no\n"
@@ -100,6 +110,8 @@ static const char *HELP_TEXT =
 //                       [int32 core][int64 records]; mate 2: bare records in mate 1's order)
 //   PREFIX_<m>.scalcen  magic, u8 names; the name stream, or without names (-n) int64 0 and the library name
 //   PREFIX_<m>.scalcel  --variable-length only (lenstream.hpp): magic, int32 entry width, int32 L, one entry L - length per record
+//   PREFIX_1.scalceo    --keep-order only (orderstream.hpp): magic, int32 4, int32 0, int64 N, N x u32: the input index of the
+//                       k-th record (pair) of the archive; one file for both mates
 //   PREFIX_<m>.scalceq  magic, int64 Phred offset (mate 1's for both mates, compress.cpp:294,816-817); arithmetic coded:
 //                       the scaled table (QTABLE_WORDS x u32), the int64 symbol count and the coded blocks; -A: the q' rows
 static const uint8_t MAGIC[8] = {'s', 'c', 'a', 'l', 'c', 'e', '2', '2'};
@@ -318,6 +330,16 @@ struct MateFiles {
     fL.write(entries);
     fL.close();
   }
+  void write_order() const {  // --keep-order: the input index of every record (pair), in archive order
+    OutFile fO;
+    fO.open(archive_path(o.out, 0, 'o'), gz_container(o, 'o'));
+    const std::vector<uint8_t> perm = fetch(ctx, b, SCALCE_OUT_PERM, 0);
+    uint8_t head[scalce_host::ORDER_HEADER_BYTES];
+    scalce_host::order_header_write(head, perm.size() / 4);
+    fO.write(head, sizeof head);
+    fO.write(perm);
+    fO.close();
+  }
   void write_qualities(int m, Downloader &down, uint64_t N) const {  // once the coder is through; N: records of the run
     OutFile fQ;
     fQ.open(archive_path(o.out, m, 'q'), gz_container(o, 'q'));
@@ -381,7 +403,7 @@ static int do_compress(const Options &o, const std::vector<std::string> &files, 
   char emsg[512] = "";
   const double t1 = now();
   if (scalce_stream_compress(ctx, &p, MateSource::read_cb, &in.src[0], nsrc == 2 ? MateSource::read_cb : nullptr, nsrc == 2 ? &in.src[1] : nullptr,
-                             piece, hint, SCALCE_STREAM_LEAN | SCALCE_STREAM_DEFER_ENTROPY, &b, &ss, emsg, sizeof emsg)) {
+                             piece, hint, SCALCE_STREAM_LEAN | SCALCE_STREAM_DEFER_ENTROPY | (o.keep_order ? SCALCE_STREAM_KEEP_ORDER : 0), &b, &ss, emsg, sizeof emsg)) {
     if (!in.src[0].error.empty()) fputs(in.src[0].error.c_str(), stderr);  // (-i: a file of odd record count; the stream only saw a read error)
     else fprintf(stderr, "%s\n", emsg[0] ? emsg : scalce_last_error(ctx));
     exit(1);
@@ -411,7 +433,10 @@ static int do_compress(const Options &o, const std::vector<std::string> &files, 
     downs[m].reset(new Downloader);
     w.write_reads_and_names(m, *downs[m]);
     if (o.varlen) w.write_lengths(m);
+    if (o.keep_order && m == 0) w.write_order();
   });
+  // (an order stream left under this prefix by an earlier run does not belong to this archive)
+  if (!o.keep_order) unlink(archive_path(o.out, 0, 'o').c_str());
   const double t2b = now();
   SCOK(ctx, scalce_batch_finish(b, s_ent));  // the coder is through: sizes of the coded streams, device error word
   const double t2c = now();
@@ -421,7 +446,7 @@ static int do_compress(const Options &o, const std::vector<std::string> &files, 
   });
   const double t2d = now();
   uint64_t new_size = 0;
-  for_each_archive_file(o, "rnql", [&](char, const std::string &fn) {
+  for_each_archive_file(o, o.keep_order ? "rnqlo" : "rnql", [&](char, const std::string &fn) {
     struct stat st;
     if (stat(fn.c_str(), &st) == 0) new_size += (uint64_t)st.st_size;
   });
@@ -806,7 +831,8 @@ static std::string scalce_name(std::string path, char c) {  // get_file_name, de
 struct Archive {
   std::string base[2];
   bool has_lens[2] = {false, false};
-  ArchiveFile files[2][3], lens[2];
+  bool has_order = false;  // a PREFIX_1.scalceo lies next to the .scalcen (and --archive-order does not set it aside)
+  ArchiveFile files[2][3], lens[2], order[2];  // (a mate pass reads the order stream from its start: one handle each)
   scalce_read_fn rd[2][3];
   void *user[2][3];
   Archive(const Options &o, const std::string &path, int nm) {
@@ -830,6 +856,11 @@ struct Archive {
       }
     for (int m = 0; m < nm; m++)
       if (has_lens[m]) lens[m].open(scalce_name(base[m], 'l'));
+    struct stat ost;
+    has_order = !o.archive_order && stat(scalce_name(base[0], 'o').c_str(), &ost) == 0;
+    if (has_order && o.has_range)
+      FAIL("--records counts in the archive's order and %s holds the input's: give --archive-order with --records\n", scalce_name(base[0], 'o').c_str());
+    for (int m = 0; m < (o.interleave ? 1 : nm) && has_order; m++) order[m].open(scalce_name(base[0], 'o'));
   }
 };
 // One path for every archive: scalce_stream_decompress moves it through the device in windows of whole records.  The read
@@ -844,11 +875,32 @@ static int do_decompress(const Options &o, const std::string &path, scalce_ctx *
   sink.out = o.out; sink.split = o.split; sink.interleave = o.interleave;
   scalce_unpack_stats st;
   scalce_unpack_range_stats rs;
+  scalce_restore_stats os;
   char err[1024] = "";
-  const int rc = scalce_stream_decompress_range(ctx, &p, &rg, ar.rd, ar.user, TextSink::write, &sink, &st, &rs, err, sizeof err);
+  std::string spill_dir;
+  int rc;
+  if (ar.has_order) {  // the input order back: two passes through a spill under -t, next to the output, or in $TMPDIR
+    scalce_restore_params rp;
+    memset(&rp, 0, sizeof rp);
+    for (int m = 0; m < (o.interleave ? 1 : nm); m++) { rp.order_rd[m] = ArchiveFile::read; rp.order_user[m] = &ar.order[m]; }
+    if (o.temp_given) {
+      spill_dir = o.temp;
+      struct stat tst;
+      if (stat(spill_dir.c_str(), &tst) != 0 && mkdir(spill_dir.c_str(), 0777) != 0) FAIL("Cannot create temporary directory %s (-t)\n", spill_dir.c_str());
+    } else if (o.out == "-") {
+      spill_dir = getenv("TMPDIR") && getenv("TMPDIR")[0] ? getenv("TMPDIR") : "/tmp";
+    } else {
+      const size_t sl = o.out.rfind('/');
+      spill_dir = sl == std::string::npos ? "." : sl == 0 ? "/" : o.out.substr(0, sl);
+    }
+    rp.spill_dir = spill_dir.c_str();
+    memset(&rs, 0, sizeof rs);
+    rc = scalce_stream_decompress_restore(ctx, &p, &rp, ar.rd, ar.user, TextSink::write, &sink, &st, &os, err, sizeof err);
+  } else
+    rc = scalce_stream_decompress_range(ctx, &p, &rg, ar.rd, ar.user, TextSink::write, &sink, &st, &rs, err, sizeof err);
   if (rc) {
     // (parts already written stay where they are)
-    if (st.error_wants_file && st.error_mate >= 0 && st.error_stream >= 0)
+    if (st.error_wants_file && st.error_mate >= 0 && st.error_stream >= 0 && st.error_stream < 3)
       FAIL("%s %s\n", st.error_stream == 0 ? ar.base[st.error_mate].c_str() : ar.files[st.error_mate][st.error_stream].path.c_str(), err);
     fprintf(stderr, "%s%s\n", strncmp(err, "(ERROR)", 7) ? "(ERROR) " : "", err);
     exit(1);
@@ -858,6 +910,12 @@ static int do_decompress(const Options &o, const std::string &path, scalce_ctx *
       now() - t0, st.read_wait_s, st.decode_s, st.records_s, st.write_s, nm == 2 && !o.interleave ? ", one mate after the other" : "");
   LOG("\tWindows: %llu of up to %llu bytes of text; device memory held at most %llu bytes\n", (unsigned long long)st.windows,
       (unsigned long long)st.window_text_bytes, (unsigned long long)st.peak_device_bytes);
+  if (ar.has_order) {
+    LOG("\tOrder: %llu records restored through %llu stripes of up to %llu records; %llu bytes spilled in %s\n", (unsigned long long)os.records,
+        (unsigned long long)os.stripes, (unsigned long long)os.stripe_records, (unsigned long long)os.spilled_bytes, spill_dir.c_str());
+    LOG("\tOrder: window loop %.2f s (spill written %.2f), stripe loop %.2f s (spill read %.2f, waiting for place + permute %.2f)\n", os.group_pass_s,
+        os.spill_write_s, os.stripe_pass_s, os.spill_read_s, os.place_wait_s);
+  }
   if (o.has_range) {
     char total[32] = "unknown";
     if (rs.total_records != ~0ull) snprintf(total, sizeof total, "%llu", (unsigned long long)rs.total_records);
@@ -908,7 +966,8 @@ static bool parse_options(int argc, char **argv, Options &o) {
                                      {"version", 0, 0, 'v'}, {"no-arithmetic", 0, 0, 'A'}, {"patterns-bin", 1, 0, 1000},
                                      {"gpus", 1, 0, 1001}, {"interleave", 0, 0, 'i'}, {"window", 1, 0, 1002},
                                      {"records", 1, 0, 1003}, {"variable-length", 0, 0, 1004},
-                                     {"max-length", 1, 0, 1005}, {0, 0, 0, 0}};
+                                     {"max-length", 1, 0, 1005}, {"keep-order", 0, 0, 1006},
+                                     {"archive-order", 0, 0, 1007}, {0, 0, 0, 0}};
   int opt;
   while ((opt = getopt_long(argc, argv, "vhp:T:dc:o:fs:t:B:rQAn:P:S:i", long_opt, 0)) != -1) {
     switch (opt) {
@@ -932,7 +991,7 @@ static bool parse_options(int argc, char **argv, Options &o) {
       case 's': o.sample = atoi(optarg); break;
       case 'd': o.decompress = true; break;
       case 'P': o.patterns = optarg; break;
-      case 't': o.temp = optarg; break;
+      case 't': o.temp = optarg; o.temp_given = true; break;
       case 'o': o.out = optarg; break;
       case 'n': o.use_names = false; o.library = optarg; break;
       case 1000: o.patterns_bin = optarg; break;
@@ -945,6 +1004,8 @@ static bool parse_options(int argc, char **argv, Options &o) {
         if (o.max_length < 1 || o.max_length > 2498) FAIL("--max-length takes the longest read's number of bases, 1 to 2498.\n");
         o.varlen = true;
         break;
+      case 1006: o.keep_order = true; break;
+      case 1007: o.archive_order = true; break;
       default: fputs(HELP_TEXT, stdout); return false;
     }
   }
@@ -956,6 +1017,9 @@ static void check_arguments(const Options &o, const std::vector<std::string> &fi
   if (o.out.empty()) FAIL("No output file specified.\n");
   if (!o.use_names && o.library.empty()) FAIL("No library name specified.\n");
   if (o.has_range && !o.decompress) FAIL("--records can be only used with decompression (-d).\n");
+  if (o.keep_order && o.decompress) FAIL("--keep-order is an option of compression: -d restores the order by itself when the archive has a .scalceo\n");
+  if (o.archive_order && !o.decompress) FAIL("--archive-order can be only used with decompression (-d).\n");
+  if (o.keep_order && o.gpus > 1) FAIL("--keep-order runs on one GPU: with --gpus %d the permutation lies spread over the ranks\n", o.gpus);
   if (o.decompress && files.size() > 1) FAIL("Too many files specified (decompression only supports one file).\n");
   if (o.lossy < 0 || o.lossy > 100) FAIL("Percentage must be in range [0,100].\n");
   if (o.out == "-" && (o.split || o.paired)) FAIL("stdout can be only used with single-end file decompression. It cannot be used with --split-reads option!\n");

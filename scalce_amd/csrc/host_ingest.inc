@@ -458,6 +458,11 @@ extern "C" void scalce_batch_set_lean(scalce_batch *b, int lean) {
   b->lean = lean != 0;
   if (b->lean) unfuse(b);
 }
+extern "C" int scalce_batch_set_keep_order(scalce_batch *b, int on) {
+  if (!b) return SCALCE_ERR_ARG;
+  b->keep_order = on != 0;
+  return SCALCE_OK;
+}
 extern "C" uint64_t scalce_batch_reruns(const scalce_batch *b) { return b ? b->reruns : 0; }
 extern "C" int scalce_batch_coder_round(const scalce_batch *b) { return b ? b->ac_round_launched : 0; }
 extern "C" int scalce_batch_set_code_in_place(scalce_batch *b, int on) {

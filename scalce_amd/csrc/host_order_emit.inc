@@ -277,9 +277,13 @@ extern "C" int scalce_batch_emit(scalce_batch *b, void *stream) {
                     &w.ev_sorted, &w.ev_tmp, &w.ev_place, &w.chosen, &w.G, &w.cand_place,
                     &w.bucket, &w.endv, &w.tokens, &w.chunk, &w.chunk_start, &w.perm_a, &w.perm_b, &w.key_a, &w.key_b, &w.hist, &w.S,
                     &w.run_head, &w.run_hcount, &w.run_rank, &w.runid, &w.run_items_a, &w.run_items_b, &w.run_pos};
-    for (DBuf *d : dead)
+    // (keep_order: the permutation is an output of the run -- the half of the pair it lies in stays, and so does the pointer)
+    const bool keep_perm = b->keep_order && b->perm;
+    for (DBuf *d : dead) {
+      if (keep_perm && d->p && (u8 *)b->perm >= d->as<u8>() && (u8 *)b->perm < d->as<u8>() + d->cap) continue;
       if (d->cap >= (256u << 20)) d->release();  // (the big ones; releasing dozens of small buffers only costs time)
-    b->perm = nullptr;
+    }
+    if (!keep_perm) b->perm = nullptr;
     b->sorted_keys = nullptr;
     w.row_cap = 0;
   }

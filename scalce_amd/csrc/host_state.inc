@@ -300,6 +300,7 @@ struct scalce_batch {
   u64 tok_done = 0, tok_base = 0, tok_n = 0;  // rows tokenized so far / the rows of the tokenization in progress
   bool appending = false;    // the pieces came through scalce_batch_append
   bool lean = false;         // release what a stage no longer needs (runs sized for most of HBM)
+  bool keep_order = false;   // SCALCE_OUT_PERM is an output of the run: a lean batch keeps it (scalce_batch_set_keep_order)
   u64 tri_expected[2] = {0, 0};  // trigrams counted so far (tri_check_k)
   u32 quality_source[2] = {0, 0};  // where the last scalce_batch_quality took the mate's symbol range from (scalce_batch_quality_plan)
   u64 names_in_used = 0;     // bytes of the long-name store in use

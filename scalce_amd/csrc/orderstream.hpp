@@ -1,0 +1,116 @@
+// orderstream.hpp -- the order stream of an archive made with --keep-order (PREFIX_1.scalceo), host side only: no device call,
+// no HIP header.  Layout: the 8 magic bytes, int32 entry width (4), int32 0, int64 N, then N little-endian u32: entry k is the
+// input index of the k-th record (pair) of the archive.  The writer (cli.cpp) and the reader (stream_decode.cpp) share it, and
+// the table that says where each window's share of each stripe lies in the spill of the restore.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <vector>
+
+namespace scalce_host {
+
+constexpr size_t ORDER_HEADER_BYTES = 24;
+constexpr int ORDER_ENTRY_WIDTH = 4;
+constexpr uint64_t ORDER_MAX_STRIPES = 65536;
+static const uint8_t ORDER_MAGIC[8] = {'s', 'c', 'a', 'l', 'c', 'e', '2', '2'};
+
+inline void order_header_write(uint8_t out[ORDER_HEADER_BYTES], uint64_t n) {
+  const int32_t f[2] = {ORDER_ENTRY_WIDTH, 0};
+  memcpy(out, ORDER_MAGIC, 8);
+  memcpy(out + 8, f, 8);
+  memcpy(out + 16, &n, 8);
+}
+// nullptr: a header this build reads (*n filled in); else what is wrong with it
+inline const char *order_header_read(const uint8_t *h, size_t have, uint64_t *n) {
+  if (have < ORDER_HEADER_BYTES) return "truncated order stream";
+  if (memcmp(h, ORDER_MAGIC, 7)) return "is not a scalce order stream";
+  int32_t f[2];
+  memcpy(f, h + 8, 8);
+  if (f[0] != ORDER_ENTRY_WIDTH || f[1] != 0) return "is not a scalce order stream";
+  int64_t v;
+  memcpy(&v, h + 16, 8);
+  if (v < 0 || v > 0xFFFFFFFFll) return "is not a scalce order stream";
+  *n = (uint64_t)v;
+  return nullptr;
+}
+// the other messages of the stream; `entries` against the `records` the archive holds
+inline const char *order_not_permutation() { return "order stream is not a permutation of the records"; }
+inline int order_count_message(char *out, size_t cap, uint64_t entries, uint64_t records) {
+  return snprintf(out, cap, "order stream holds %llu entries, the archive %llu records", (unsigned long long)entries,
+                  (unsigned long long)records);
+}
+// host-side check of n entries: false when one of them is >= total (the device checks the same; this one serves callers
+// that hold the entries anyway)
+inline bool order_entries_in_range(const uint32_t *e, size_t n, uint64_t total) {
+  for (size_t i = 0; i < n; i++)
+    if ((uint64_t)e[i] >= total) return false;
+  return true;
+}
+
+// R records per stripe and S stripes for N records, from the window and the bound of a record's text: R = window /
+// max_record_bytes (at least 1), raised where needed so that S = ceil(N / R) <= ORDER_MAX_STRIPES
+inline void order_plan(uint64_t total, uint64_t window, uint64_t max_record_bytes, uint64_t out[2]) {
+  uint64_t R = max_record_bytes ? window / max_record_bytes : window;
+  if (R < 1) R = 1;
+  uint64_t S = (total + R - 1) / R;
+  if (S > ORDER_MAX_STRIPES) {
+    R = (total + ORDER_MAX_STRIPES - 1) / ORDER_MAX_STRIPES;
+    S = (total + R - 1) / R;
+  }
+  out[0] = R;
+  out[1] = S;
+}
+
+// Where each window's share of each stripe lies in the spill.  A window's records are appended grouped by stripe, so its
+// share of stripe s follows its share of stripe s - 1: the table keeps, per window, where its records begin in the text and
+// in the record words, and its non-empty shares; stripes are then taken in rising order and every window keeps a cursor.
+struct StripeTable {
+  struct Share { uint32_t stripe, records; uint64_t bytes; };
+  struct Piece { uint64_t text_at, bytes, record_at, records; };  // one pread of text, one of record words
+  struct Win { uint64_t text_at, record_at; size_t first, n, cur; };
+  uint64_t S = 0, next_stripe = 0;
+  uint64_t text_bytes = 0, records = 0;  // appended so far
+  std::vector<Share> shares;
+  std::vector<Win> wins;
+  void reset(uint64_t stripes) { *this = StripeTable(); S = stripes; }
+  // a window of n records: counts[s] of them in stripe s (S entries), off[k] where the k-th of them begins in the window's
+  // grouped text (n + 1 entries).  false: the counts do not add up to n
+  bool add_window(const uint32_t *counts, const uint64_t *off, uint64_t n) {
+    Win w{text_bytes, records, shares.size(), 0, 0};
+    uint64_t at = 0;
+    for (uint64_t s = 0; s < S; s++) {
+      const uint64_t c = counts[s];
+      if (!c) continue;
+      if (at + c > n) { shares.resize(w.first); return false; }
+      shares.push_back(Share{(uint32_t)s, (uint32_t)c, off[at + c] - off[at]});
+      at += c;
+    }
+    if (at != n) { shares.resize(w.first); return false; }
+    w.n = shares.size() - w.first;
+    wins.push_back(w);
+    text_bytes += off[n] - off[0];
+    records += n;
+    return true;
+  }
+  // the pieces of the next stripe, in window order (stripes are asked for in order 0, 1, ..); returns its records
+  uint64_t take_stripe(std::vector<Piece> &out, uint64_t *bytes) {
+    out.clear();
+    uint64_t rec = 0, by = 0;
+    const uint64_t s = next_stripe++;
+    for (Win &w : wins) {
+      if (w.cur == w.n || shares[w.first + w.cur].stripe != s) continue;
+      const Share &sh = shares[w.first + w.cur++];
+      out.push_back(Piece{w.text_at, sh.bytes, w.record_at, sh.records});
+      w.text_at += sh.bytes;
+      w.record_at += sh.records;
+      rec += sh.records;
+      by += sh.bytes;
+    }
+    if (bytes) *bytes = by;
+    return rec;
+  }
+};
+
+}  // namespace scalce_host

@@ -31,3 +31,4 @@ using namespace scalce;
 #include "host_entropy.inc"
 #include "host_api.inc"
 #include "host_decode.inc"
+#include "kernels_restore.hpp"

@@ -27,8 +27,11 @@
 //
 // Built on the public C ABI only (include/scalce_hip.h) plus the HIP runtime for pinned memory, copies and events.
 #include <hip/hip_runtime_api.h>
+#include <fcntl.h>
+#include <unistd.h>
 
 #include <algorithm>
+#include <cerrno>
 #include <atomic>
 #include <condition_variable>
 #include <cstdarg>
@@ -44,6 +47,7 @@
 #include "../../include/scalce_hip.h"
 #include "hip_own.hpp"
 #include "lenstream.hpp"
+#include "orderstream.hpp"
 #include "stream_src.hpp"
 
 namespace {
@@ -137,6 +141,30 @@ struct Window {
 struct Job {
   int slot, mate;
   u64 first, n, nbytes;
+  int kind = 0;  // 0: a window for wr; 1: a window for the spill; 2: a stripe for wr (the last two: the order restore)
+};
+
+// The order restore (scalce_stream_decompress_restore).  Pass B is the window loop: a window's records are grouped by stripe
+// on the device and its text, entries and record sizes appended to the spill by the writer thread.  Pass C reads the spill
+// back stripe by stripe, puts the records in their places on the device and hands each stripe to wr.
+struct RestoreSlot {
+  HBuf h_ord, h_gidx, h_groff, h_counts, h_bad;
+  DBuf d_ord, d_sidx, d_gidx, d_gtext, d_groff, d_counts, d_bad, d_ws;
+};
+struct Restore {
+  scalce_restore_params P;
+  scalce_restore_stats S;
+  Src o;                       // the order stream of the pass that runs
+  u64 delivered = 0, skipped = 0;
+  u64 N = 0, taken = 0;        // entries its header promises; entries the windows have taken
+  u64 R = 0, NS = 0;           // records per stripe, stripes (scalce_order_plan)
+  u64 rcap = 0;                // records a buffer of record words holds: a window's or a stripe's, whichever is more
+  std::string dir;
+  int fd_text = -1, fd_rec = -1;
+  scalce_host::StripeTable table;
+  std::vector<u64> words;      // a window's / a stripe's record words: entry | size << 32
+  RestoreSlot rs[2];
+  ~Restore() { if (fd_text >= 0) ::close(fd_text); if (fd_rec >= 0) ::close(fd_rec); }
 };
 
 struct Session {
@@ -155,6 +183,7 @@ struct Session {
   bool closing = false;
   std::thread writer;
   int device = 0;
+  std::unique_ptr<Restore> X;  // set: the input order is restored
 
   // (the streams in front of what is used on them: close() lets everything go in the right order by hand, and should a
   // session ever die without it, the buffers and events would still go before the streams)
@@ -200,8 +229,10 @@ struct Session {
 #define SD_TRY(expr) do { if (int rc_ = (expr)) return rc_; } while (0)
 
   // a stream that ends, or fails, before what is asked of it (stream: 0 r, 1 n, 2 q, 3 l)
-  Src &src(int m, int stream) { return stream == 0 ? M[m].r : stream == 1 ? M[m].n : stream == 2 ? M[m].q : M[m].l; }
-  static const char *stream_name(int stream) { return stream == 0 ? "read" : stream == 1 ? "name" : stream == 2 ? "quality" : "length"; }
+  Src &src(int m, int stream) { return stream == 0 ? M[m].r : stream == 1 ? M[m].n : stream == 2 ? M[m].q : stream == 3 ? M[m].l : X->o; }
+  static const char *stream_name(int stream) {
+    return stream == 0 ? "read" : stream == 1 ? "name" : stream == 2 ? "quality" : stream == 3 ? "length" : "order";
+  }
   int read_error(int m, int stream) { return fail(SCALCE_ERR_FORMAT, m, stream, 0, "read error on the %s stream", stream_name(stream)); }
   int truncated(int m, int stream) { return fail(SCALCE_ERR_FORMAT, m, stream, 0, "(ERROR) truncated %s stream", stream_name(stream)); }
   int short_stream(int m, int stream) { return src(m, stream).bad ? read_error(m, stream) : truncated(m, stream); }
@@ -336,7 +367,17 @@ struct Session {
     R = std::max<u64>(1, W / rec_min);
     D = std::min<u64>(R, (u64)scalce_patterns_count(ctx) + 2);
     cap_text = std::max(W, rec_max) + 64;
-    const u64 roff_bytes = 8 * (R + 1), len_bytes = 2 * R + 64;
+    u64 rcap = R;
+    if (X) {  // a stripe's text fits the window's bound, unless the cap on the stripes raised R
+      u64 pl[2];
+      scalce_host::order_plan(X->N, W, rec_max, pl);
+      X->R = pl[0]; X->NS = pl[1];
+      X->S.stripe_records = pl[0]; X->S.stripes = pl[1];
+      X->table.reset(X->NS);
+      cap_text = std::max(cap_text, X->R * rec_max + 64);
+      rcap = X->rcap = std::max(R, X->R);
+    }
+    const u64 roff_bytes = 8 * (rcap + 1), len_bytes = 2 * R + 64;
     u64 o = 0;
     for (int m = m0; m <= m1; m++) {
       Mate &x = M[m];
@@ -360,7 +401,21 @@ struct Session {
       SD_TRY(dmalloc(s.d_text, cap_text));
       const bool strip = M[m0].has_len;  // (never with two mates in one window: -d -i refuses a length stream)
       if (P.split) SD_TRY(hmalloc(s.h_roff, roff_bytes));
-      if (P.split || strip) SD_TRY(dmalloc(s.d_roff, roff_bytes));
+      if (P.split || strip || X) SD_TRY(dmalloc(s.d_roff, roff_bytes));
+      if (X) {
+        RestoreSlot &q = X->rs[i];
+        const u64 words = 4 * rcap + 64, ws = std::max(scalce_order_group_ws_bytes(rcap, X->NS), scalce_records_permute_ws_bytes(rcap));
+        for (HBuf *b : {&q.h_ord, &q.h_gidx}) SD_TRY(hmalloc(*b, words));
+        SD_TRY(hmalloc(q.h_groff, roff_bytes));
+        SD_TRY(hmalloc(q.h_counts, 4 * X->NS + 64));
+        SD_TRY(hmalloc(q.h_bad, 64));
+        for (DBuf *b : {&q.d_ord, &q.d_sidx, &q.d_gidx}) SD_TRY(dmalloc(*b, words));
+        SD_TRY(dmalloc(q.d_gtext, cap_text));
+        SD_TRY(dmalloc(q.d_groff, roff_bytes));
+        SD_TRY(dmalloc(q.d_counts, 4 * X->NS + 64));
+        SD_TRY(dmalloc(q.d_bad, 64));
+        SD_TRY(dmalloc(q.d_ws, ws));
+      }
       if (strip) {
         SD_TRY(hmalloc(s.h_len, len_bytes));
         SD_TRY(dmalloc(s.d_len, len_bytes));
@@ -378,6 +433,11 @@ struct Session {
       for (DBuf *b : {&s.d_len, &s.d_text2, &s.d_roff2, &s.d_scan, &s.d_in, &s.d_text, &s.d_roff}) drop(*b);
       s = Slot();
     }
+    if (X)
+      for (RestoreSlot &q : X->rs) {
+        for (DBuf *b : {&q.d_ord, &q.d_sidx, &q.d_gidx, &q.d_gtext, &q.d_groff, &q.d_counts, &q.d_bad, &q.d_ws}) drop(*b);
+        q = RestoreSlot();
+      }
   }
 
   // the quality stream behind its header: the table, the symbol count, then the frames -- and the decoder for them
@@ -512,16 +572,25 @@ struct Session {
       }
       Slot &s = slot[j.slot];
       if (!failed) {
+        const double t0 = now_s();
         const hipError_t e = hipEventSynchronize(s.ev_done);
         if (e != hipSuccess) hip(e, "a window's text did not come down");
+        if (j.kind == 2) X->S.place_wait_s += now_s() - t0;
       }
-      if (!failed) {
+      if (!failed && j.kind && X->rs[j.slot].h_bad.as<u32>()[0])
+        fail(SCALCE_ERR_FORMAT, m0, 4, 0, "(ERROR) %s", scalce_host::order_not_permutation());
+      if (!failed && j.kind == 1) {
         float ms = 0;
         if (hipEventElapsedTime(&ms, s.t_rec0, s.t_rec1) == hipSuccess) S.records_s += 1e-3 * ms;
+        spill_window(j);
+        S.windows++;
+      } else if (!failed) {
+        float ms = 0;
+        if (!j.kind && hipEventElapsedTime(&ms, s.t_rec0, s.t_rec1) == hipSuccess) S.records_s += 1e-3 * ms;
         const double t0 = now_s();
         if (wr(wr_user, j.mate, j.first, j.n, s.h_text.as<u8>(), j.nbytes, P.split ? s.h_roff.as<u64>() : nullptr)) fail(SCALCE_ERR_FORMAT, j.mate, -1, 0, "the write callback failed");
         S.write_s += now_s() - t0;
-        S.windows++;
+        if (!j.kind) S.windows++;
       }
       { std::lock_guard<std::mutex> lk(mu); s.busy = false; }
       cv.notify_all();
@@ -537,6 +606,130 @@ struct Session {
   void drain() {
     std::unique_lock<std::mutex> lk(mu);
     cv.wait(lk, [&] { return (!slot[0].busy && !slot[1].busy) || failed.load(); });
+  }
+
+  // ---- the order restore --------------------------------------------------------------------------------------------------
+  int order_count(u64 records) {
+    char b[200];
+    scalce_host::order_count_message(b, sizeof b, X->N, records);
+    return fail(SCALCE_ERR_FORMAT, m0, 4, 0, "(ERROR) %s", b);
+  }
+  int spill_error(const char *what) {
+    return fail(SCALCE_ERR_FORMAT, -1, -1, 0, "(ERROR) cannot %s a spill file in %s: %s", what, X->dir.c_str(), strerror(errno));
+  }
+  // a mate pass begins: the order stream from its start, its header, empty spill files
+  int restore_open(int m) {
+    Restore &x = *X;
+    x.o = Src();
+    x.o.open(x.P.order_rd[m], nullptr, x.P.order_user[m], &S.read_wait_s, &x.delivered, &x.skipped);
+    const bool whole = x.o.need(scalce_host::ORDER_HEADER_BYTES);
+    if (x.o.bad) return read_error(m, 4);
+    if (const char *why = scalce_host::order_header_read(x.o.ptr(), whole ? scalce_host::ORDER_HEADER_BYTES : 0, &x.N))
+      return fail(SCALCE_ERR_FORMAT, m, 4, 0, "(ERROR) %s", why);
+    x.o.skip(scalce_host::ORDER_HEADER_BYTES);
+    x.taken = 0;
+    for (int *fd : {&x.fd_text, &x.fd_rec}) {
+      if (*fd < 0) {  // made once, unlinked at once: nothing stays behind whatever happens
+        std::string path = x.dir + "/scalce_order_XXXXXX";
+        *fd = mkstemp(&path[0]);
+        if (*fd < 0) return spill_error("make");
+        unlink(path.c_str());
+      } else if (ftruncate(*fd, 0) != 0) return spill_error("empty");
+    }
+    return SCALCE_OK;
+  }
+  bool spill_write(int fd, const void *p, u64 n, u64 at) {
+    const u8 *b = static_cast<const u8 *>(p);
+    const double t0 = now_s();
+    while (n) {
+      const ssize_t k = ::pwrite(fd, b, (size_t)std::min<u64>(n, 1u << 30), (off_t)at);
+      if (k < 0 && errno == EINTR) continue;
+      if (k <= 0) { if (!k) errno = ENOSPC; X->S.spill_write_s += now_s() - t0; return false; }
+      b += k; n -= (u64)k; at += (u64)k;
+    }
+    X->S.spill_write_s += now_s() - t0;
+    return true;
+  }
+  bool spill_read(int fd, void *p, u64 n, u64 at) {
+    u8 *b = static_cast<u8 *>(p);
+    const double t0 = now_s();
+    while (n) {
+      const ssize_t k = ::pread(fd, b, (size_t)std::min<u64>(n, 1u << 30), (off_t)at);
+      if (k < 0 && errno == EINTR) continue;
+      if (k <= 0) { if (!k) errno = EIO; X->S.spill_read_s += now_s() - t0; return false; }
+      b += k; n -= (u64)k; at += (u64)k;
+    }
+    X->S.spill_read_s += now_s() - t0;
+    return true;
+  }
+  // (the writer thread) a window's grouped records behind the spill's end; the table learns where its shares lie
+  void spill_window(const Job &j) {
+    Restore &x = *X;
+    const RestoreSlot &q = x.rs[j.slot];
+    const u64 *off = q.h_groff.as<u64>();
+    const u32 *idx = q.h_gidx.as<u32>();
+    const u64 text_at = x.table.text_bytes, rec_at = x.table.records;
+    if (off[j.n] - off[0] != j.nbytes || !x.table.add_window(q.h_counts.as<u32>(), off, j.n)) {
+      fail(SCALCE_ERR_FORMAT, m0, 4, 0, "internal: a window's stripes do not add up");
+      return;
+    }
+    x.words.resize(j.n);
+    for (u64 k = 0; k < j.n; k++) x.words[k] = (u64)idx[k] | ((off[k + 1] - off[k]) << 32);
+    if (!spill_write(x.fd_text, slot[j.slot].h_text.p, j.nbytes, text_at) || !spill_write(x.fd_rec, x.words.data(), 8 * j.n, 8 * rec_at)) {
+      spill_error("write");
+      return;
+    }
+    x.S.spilled_bytes += j.nbytes + 8 * j.n;
+  }
+  // Pass C: stripe s holds the records of input index [s R, s R + expect).  Every window's share comes back from the spill,
+  // goes up, the records find their places and the stripe goes to wr through the writer thread, slot by slot in turn.
+  int restore_stripes() {
+    Restore &x = *X;
+    const int mate = m1 > m0 ? 0 : m0;
+    std::vector<scalce_host::StripeTable::Piece> pieces;
+    for (u64 s = 0; s < x.NS; s++) {
+      if (failed) return F.rc;
+      const u64 base = s * x.R, expect = std::min(x.R, x.N - base);
+      u64 bytes = 0;
+      const u64 m = x.table.take_stripe(pieces, &bytes);
+      if (m != expect) return fail(SCALCE_ERR_FORMAT, m0, 4, 0, "(ERROR) %s", scalce_host::order_not_permutation());
+      if (bytes + 64 > cap_text || m > x.rcap) return fail(SCALCE_ERR_CAPACITY, -1, -1, 0, "internal: a stripe of %llu bytes of text", (unsigned long long)bytes);
+      const int si = (int)(s & 1);
+      if (!wait_slot(si)) return F.rc;
+      Slot &sl = slot[si];
+      RestoreSlot &q = x.rs[si];
+      x.words.resize(m);
+      u64 tb = 0, tr = 0;
+      for (const auto &pc : pieces) {
+        if (!spill_read(x.fd_text, sl.h_text.as<u8>() + tb, pc.bytes, pc.text_at) || !spill_read(x.fd_rec, x.words.data() + tr, 8 * pc.records, 8 * pc.record_at))
+          return spill_error("read");
+        tb += pc.bytes; tr += pc.records;
+      }
+      u64 *off = q.h_groff.as<u64>();
+      u32 *idx = q.h_ord.as<u32>();
+      off[0] = 0;
+      for (u64 k = 0; k < m; k++) { idx[k] = (u32)x.words[k]; off[k + 1] = off[k] + (x.words[k] >> 32); }
+      if (off[m] != bytes) return fail(SCALCE_ERR_FORMAT, m0, 4, 0, "internal: a stripe's record sizes do not add up");
+      SD_HIP(hipMemcpyAsync(sl.d_text.p, sl.h_text.p, bytes, hipMemcpyHostToDevice, s_main));
+      SD_HIP(hipMemcpyAsync(sl.d_roff.p, off, 8 * (m + 1), hipMemcpyHostToDevice, s_main));
+      SD_HIP(hipMemcpyAsync(q.d_ord.p, idx, 4 * m, hipMemcpyHostToDevice, s_main));
+      SD_TRY(lib(scalce_order_place(ctx, q.d_ord.as<u32>(), m, base, expect, q.d_sidx.as<u32>(), q.d_bad.as<u32>(), s_main)));
+      SD_TRY(lib(scalce_records_permute(ctx, sl.d_text.as<u8>(), sl.d_roff.as<u64>(), m, bytes, q.d_sidx.as<u32>(), q.d_gtext.as<u8>(), cap_text,
+                                        q.d_groff.as<u64>(), q.d_ws.p, s_main)));
+      SD_HIP(hipMemcpyAsync(sl.h_text.p, q.d_gtext.p, bytes, hipMemcpyDeviceToHost, s_main));
+      if (P.split) SD_HIP(hipMemcpyAsync(sl.h_roff.p, q.d_groff.p, 8 * (m + 1), hipMemcpyDeviceToHost, s_main));
+      SD_HIP(hipMemcpyAsync(q.h_bad.p, q.d_bad.p, 4, hipMemcpyDeviceToHost, s_main));
+      SD_HIP(hipEventRecord(sl.ev_done, s_main));
+      {
+        std::lock_guard<std::mutex> lk(mu);
+        sl.busy = true;
+        jobs.push_back(Job{si, mate, base, expect, bytes, 2});
+      }
+      cv.notify_all();
+    }
+    drain();
+    x.S.records = x.N;
+    return failed ? F.rc : SCALCE_OK;
   }
 
   // ---- which stream says how many records there are ---------------------------------------------------------------------
@@ -733,6 +926,7 @@ struct Session {
     u64 ncap = std::min(R, std::min(M[m0].records_left, M[m0].range_left));
     for (int m = m0; m <= m1 && ncap; m++)
       if (M[m].d.dec) { u64 k; SD_TRY(records_decoded(m, k)); ncap = std::min(ncap, k); }
+    if (X) ncap = std::min(ncap, X->N - X->taken);  // (records behind the last entry: check_end reports them)
     if (!ncap) return SCALCE_OK;
     w.si = (int)(widx & 1);
     if (!wait_slot(w.si)) return F.rc;
@@ -780,6 +974,11 @@ struct Session {
       if (sum == ~0ull) return fail(SCALCE_ERR_FORMAT, m0, 3, 0, "(ERROR) the length stream holds an entry above the read length %d", x.L);
       w.cut = 2 * sum;
     }
+    if (X) {  // the window's entries of the order stream
+      const u64 want = 4 * w.n;
+      if (X->o.read_into(X->rs[w.si].h_ord.as<u8>(), want) != want) return short_stream(m0, 4);
+      X->taken += w.n;
+    }
     for (int m = m0; m <= m1; m++)
       w.nbytes += names ? (qual ? scalce_fastq_text_bytes : scalce_fasta_text_bytes)(M[m].L, w.n, w.nb[m - m0], nullptr) : lib_text(m, w.first, w.n);
     if (w.nbytes + 64 > cap_text) return fail(SCALCE_ERR_CAPACITY, -1, -1, 0, "internal: a window of %llu bytes of text", (unsigned long long)w.nbytes);
@@ -789,6 +988,7 @@ struct Session {
     Slot &s = slot[w.si];
     u8 *h_in = s.h_in.as<u8>(), *d_in = s.d_in.as<u8>();
     if (w.strip) SD_HIP(hipMemcpyAsync(s.d_len.p, s.h_len.p, w.n * (u64)M[m0].l_width, hipMemcpyHostToDevice, s_up));
+    if (X) SD_HIP(hipMemcpyAsync(X->rs[w.si].d_ord.p, X->rs[w.si].h_ord.p, 4 * w.n, hipMemcpyHostToDevice, s_up));
     for (int m = m0; m <= m1; m++) {
       Mate &x = M[m];
       const int i = m - m0;
@@ -825,7 +1025,7 @@ struct Session {
       if (names) { fw.d_names = d_in + x.o_names; fw.d_name_off = reinterpret_cast<const u64 *>(d_in + x.o_noff); }
       fw.library = library.c_str();
       fw.d_out = s.d_text.as<u8>();
-      fw.d_record_offsets = ((P.split || w.strip) && m == m0) ? s.d_roff.as<u64>() : nullptr;
+      fw.d_record_offsets = ((P.split || w.strip || X) && m == m0) ? s.d_roff.as<u64>() : nullptr;
       if (nmates == 2) {
         const Mate &y = M[m == m0 ? m1 : m0];
         fw.interleave = m - m0 + 1; fw.pair_read_len = y.L;
@@ -843,6 +1043,14 @@ struct Session {
                                            s.d_text2.as<u8>(), s.d_roff2.as<u64>(), s.d_scan.p, s_main)));
       w.nbytes -= w.cut;
     }
+    if (X) {  // the window's records grouped by the stripe of the output they belong to, and their entries with them
+      RestoreSlot &q = X->rs[w.si];
+      SD_TRY(lib(scalce_order_group(ctx, q.d_ord.as<u32>(), w.n, X->R, X->N, X->NS, q.d_sidx.as<u32>(), q.d_counts.as<u32>(), q.d_bad.as<u32>(),
+                                    q.d_ws.p, s_main)));
+      SD_TRY(lib(scalce_records_permute(ctx, (w.strip ? s.d_text2 : s.d_text).as<u8>(), (w.strip ? s.d_roff2 : s.d_roff).as<u64>(), w.n, w.nbytes,
+                                        q.d_sidx.as<u32>(), q.d_gtext.as<u8>(), cap_text, q.d_groff.as<u64>(), q.d_ws.p, s_main)));
+      SD_TRY(lib(scalce_order_gather(ctx, q.d_ord.as<u32>(), q.d_sidx.as<u32>(), w.n, q.d_gidx.as<u32>(), s_main)));
+    }
     SD_HIP(hipEventRecord(s.t_rec1, s_main));
     SD_HIP(hipEventRecord(s.ev_rec, s_main));
     return SCALCE_OK;
@@ -851,13 +1059,29 @@ struct Session {
   int window_download(const Window &w) {
     Slot &s = slot[w.si];
     SD_HIP(hipStreamWaitEvent(s_down, s.ev_rec, 0));
+    if (X) {  // the grouped text, where its records begin, their entries, the stripes' counts and the verdict
+      RestoreSlot &q = X->rs[w.si];
+      SD_HIP(hipMemcpyAsync(s.h_text.p, q.d_gtext.p, w.nbytes, hipMemcpyDeviceToHost, s_down));
+      SD_HIP(hipMemcpyAsync(q.h_groff.p, q.d_groff.p, 8 * (w.n + 1), hipMemcpyDeviceToHost, s_down));
+      SD_HIP(hipMemcpyAsync(q.h_gidx.p, q.d_gidx.p, 4 * w.n, hipMemcpyDeviceToHost, s_down));
+      SD_HIP(hipMemcpyAsync(q.h_counts.p, q.d_counts.p, 4 * X->NS, hipMemcpyDeviceToHost, s_down));
+      SD_HIP(hipMemcpyAsync(q.h_bad.p, q.d_bad.p, 4, hipMemcpyDeviceToHost, s_down));
+      SD_HIP(hipEventRecord(s.ev_done, s_down));
+      {
+        std::lock_guard<std::mutex> lk(mu);
+        s.busy = true;
+        jobs.push_back(Job{w.si, m1 > m0 ? 0 : m0, w.first, w.n, w.nbytes, 1});
+      }
+      cv.notify_all();
+      return SCALCE_OK;
+    }
     SD_HIP(hipMemcpyAsync(s.h_text.p, w.strip ? s.d_text2.p : s.d_text.p, w.nbytes, hipMemcpyDeviceToHost, s_down));
     if (P.split) SD_HIP(hipMemcpyAsync(s.h_roff.p, w.strip ? s.d_roff2.p : s.d_roff.p, 8 * (w.n + 1), hipMemcpyDeviceToHost, s_down));
     SD_HIP(hipEventRecord(s.ev_done, s_down));
     {
       std::lock_guard<std::mutex> lk(mu);
       s.busy = true;
-      jobs.push_back(Job{w.si, m1 > m0 ? 0 : m0, w.first, w.n, w.nbytes});
+      jobs.push_back(Job{w.si, m1 > m0 ? 0 : m0, w.first, w.n, w.nbytes, 0});
     }
     cv.notify_all();
     return SCALCE_OK;
@@ -878,6 +1102,8 @@ struct Session {
     for (int m = m0; m <= m1; m++) {
       bool more = false;
       SD_TRY(more_reads(m, (size_t)(M[m].L + 3) / 4, more));
+      if (more && X && X->taken == X->N)
+        return fail(SCALCE_ERR_FORMAT, m0, 4, 0, "(ERROR) order stream holds %llu entries, the archive more records", (unsigned long long)X->N);
       if (more) return fail(SCALCE_ERR_FORMAT, m, 0, 0, "(ERROR) the read stream holds more than the %llu records of the %s stream",
                             (unsigned long long)M[m].first, names ? "name" : "quality");
     }
@@ -886,11 +1112,13 @@ struct Session {
 
   // mates m0 .. m1 (one mate, or both under -i) from the range's first window to its last
   int run_pass() {
+    const double t_pass = now_s();
     for (int m = m0; m <= m1; m++) SD_TRY(setup_decoder(m));
     if (m1 > m0 && M[m0].records_left != M[m1].records_left)
       return fail(SCALCE_ERR_FORMAT, -1, -1, 0, "(ERROR) the mates hold %llu and %llu records", (unsigned long long)M[m0].records_left,
                   (unsigned long long)M[m1].records_left);
     known = M[m0].records_left != UNKNOWN;
+    if (X && known && X->N != M[m0].records_left) return order_count(M[m0].records_left);
     SD_TRY(pass_over());
     for (;;) {
       if (failed) return F.rc;
@@ -908,6 +1136,13 @@ struct Session {
     drain();
     if (failed) return F.rc;
     for (int m = m0; m <= m1; m++) free_decoder(m);
+    if (X) {
+      if (X->taken != X->N) return order_count(X->taken);
+      X->S.group_pass_s += now_s() - t_pass;
+      const double tc = now_s();
+      SD_TRY(restore_stripes());
+      X->S.stripe_pass_s += now_s() - tc;
+    }
     return SCALCE_OK;
   }
 
@@ -931,7 +1166,8 @@ struct Session {
       m0 = m;
       m1 = together ? 1 : m;
       const double ts = now_s();
-      int rc = setup_slots();
+      int rc = X ? restore_open(m) : SCALCE_OK;
+      if (!rc) rc = setup_slots();
       S.setup_s += now_s() - ts;
       if (!rc) rc = run_pass();
       if (rc) return rc;
@@ -976,15 +1212,20 @@ extern "C" int scalce_range_plan_quality(int read_len, uint64_t first, uint64_t 
   return SCALCE_OK;
 }
 
+extern "C" int scalce_order_plan(uint64_t total_records, uint64_t window_text_bytes, uint64_t max_record_bytes, uint64_t out[2]) {
+  if (!out || !max_record_bytes || total_records > 0xFFFFFFFFull) return SCALCE_ERR_ARG;
+  scalce_host::order_plan(total_records, window_text_bytes, max_record_bytes, out);
+  return SCALCE_OK;
+}
+
 extern "C" int scalce_stream_decompress(scalce_ctx *ctx, const scalce_unpack_params *p, scalce_read_fn rd[2][3], void *user[2][3],
                                         scalce_write_fn wr, void *wr_user, scalce_unpack_stats *stats, char *errbuf, size_t errcap) {
   return scalce_stream_decompress_range(ctx, p, nullptr, rd, user, wr, wr_user, stats, nullptr, errbuf, errcap);
 }
 
-extern "C" int scalce_stream_decompress_range(scalce_ctx *ctx, const scalce_unpack_params *p, const scalce_unpack_range *range,
-                                              scalce_read_fn rd[2][3], void *user[2][3], scalce_write_fn wr, void *wr_user,
-                                              scalce_unpack_stats *stats, scalce_unpack_range_stats *range_stats, char *errbuf,
-                                              size_t errcap) {
+// what every entry point asks of its arguments; the session that runs, reports and goes
+static int unpack_args(scalce_ctx *ctx, const scalce_unpack_params *p, scalce_read_fn rd[2][3], void *user[2][3], scalce_write_fn wr, char *errbuf,
+                       size_t errcap) {
   if (!ctx || !p || !rd || !user || !wr || p->mates < 1 || p->mates > 2 || (p->interleave && p->mates != 2)) return SCALCE_ERR_ARG;
   for (int m = 0; m < p->mates; m++)
     if (!rd[m][0] || !rd[m][1] || (!p->no_qualities && !rd[m][2])) return SCALCE_ERR_ARG;
@@ -995,7 +1236,10 @@ extern "C" int scalce_stream_decompress_range(scalce_ctx *ctx, const scalce_unpa
                                "not interleaved, not without qualities, and every mate has its length stream");
     return SCALCE_ERR_ARG;
   }
-  Session *s = new Session(ctx, p, range, wr, wr_user);
+  return SCALCE_OK;
+}
+static int session_run(Session *s, scalce_read_fn rd[2][3], void *user[2][3], scalce_unpack_stats *stats, scalce_unpack_range_stats *range_stats,
+                       char *errbuf, size_t errcap) {
   int rc = s->run(rd, user);
   s->close();
   if (!rc && s->failed) rc = s->F.rc;
@@ -1005,6 +1249,32 @@ extern "C" int scalce_stream_decompress_range(scalce_ctx *ctx, const scalce_unpa
   }
   if (stats) *stats = s->S;
   if (range_stats) *range_stats = s->RS;
+  return rc;
+}
+
+extern "C" int scalce_stream_decompress_range(scalce_ctx *ctx, const scalce_unpack_params *p, const scalce_unpack_range *range,
+                                              scalce_read_fn rd[2][3], void *user[2][3], scalce_write_fn wr, void *wr_user,
+                                              scalce_unpack_stats *stats, scalce_unpack_range_stats *range_stats, char *errbuf,
+                                              size_t errcap) {
+  if (const int rc = unpack_args(ctx, p, rd, user, wr, errbuf, errcap)) return rc;
+  Session *s = new Session(ctx, p, range, wr, wr_user);
+  const int rc = session_run(s, rd, user, stats, range_stats, errbuf, errcap);
+  delete s;
+  return rc;
+}
+
+extern "C" int scalce_stream_decompress_restore(scalce_ctx *ctx, const scalce_unpack_params *p, const scalce_restore_params *rp,
+                                                scalce_read_fn rd[2][3], void *user[2][3], scalce_write_fn wr, void *wr_user,
+                                                scalce_unpack_stats *stats, scalce_restore_stats *restore_stats, char *errbuf, size_t errcap) {
+  if (const int rc = unpack_args(ctx, p, rd, user, wr, errbuf, errcap)) return rc;
+  if (!rp || !rp->order_rd[0] || (p->mates == 2 && !p->interleave && !rp->order_rd[1])) return SCALCE_ERR_ARG;
+  Session *s = new Session(ctx, p, nullptr, wr, wr_user);
+  s->X.reset(new Restore);
+  s->X->P = *rp;
+  memset(&s->X->S, 0, sizeof s->X->S);
+  s->X->dir = rp->spill_dir && rp->spill_dir[0] ? rp->spill_dir : ".";
+  const int rc = session_run(s, rd, user, stats, nullptr, errbuf, errcap);
+  if (restore_stats) *restore_stats = s->X->S;
   delete s;
   return rc;
 }

@@ -8,6 +8,7 @@ module takes raw device pointers.
 """
 import ctypes as C
 import os
+import struct
 
 import numpy as np
 
@@ -678,6 +679,163 @@ def stream_decompress(ctx, readers, write, mates=1, interleave=False, no_qualiti
     return st
 
 
+# ---- the input order back (archives made with --keep-order) -----------------------------------------------------------------
+ORDER_HEADER_BYTES = 24  # the 8 magic bytes, int32 4 (entry width), int32 0, int64 N; then N x u32
+ORDER_MAX_STRIPES = 65536
+STREAM_KEEP_ORDER = 4    # SCALCE_STREAM_KEEP_ORDER
+
+
+def pack_order(perm):
+    """The bytes of a .scalceo stream: header, then the input index of the k-th record of the archive."""
+    perm = np.asarray(perm, dtype=np.int64)
+    if perm.size and (perm.min() < 0 or perm.max() > 0xFFFFFFFF):
+        raise ValueError("an entry of an order stream is an unsigned 32-bit index")
+    return b"scalce22" + struct.pack("<iiq", 4, 0, perm.size) + perm.astype("<u4").tobytes()
+
+
+def unpack_order(data):
+    """The entries of the bytes of a .scalceo stream (out of its container); ValueError with the library's message."""
+    if len(data) < ORDER_HEADER_BYTES:
+        raise ValueError("truncated order stream")
+    width, zero, n = struct.unpack("<iiq", data[8:24])
+    if data[:7] != b"scalce2" or width != 4 or zero != 0 or n < 0 or n > 0xFFFFFFFF:
+        raise ValueError("is not a scalce order stream")
+    if len(data) < ORDER_HEADER_BYTES + 4 * n:
+        raise ValueError("truncated order stream")
+    if len(data) != ORDER_HEADER_BYTES + 4 * n:
+        raise ValueError(f"order stream holds {(len(data) - ORDER_HEADER_BYTES) // 4} entries, its header says {n}")
+    return np.frombuffer(data, dtype="<u4", offset=ORDER_HEADER_BYTES).astype(np.int64)
+
+
+def order_plan(total_records, window_text_bytes, max_record_bytes):
+    """scalce_order_plan (no device): (R, S) -- records per stripe and stripes of the order restore."""
+    L = lib()
+    L.scalce_order_plan.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.scalce_order_plan.restype = C.c_int
+    out = (C.c_uint64 * 2)()
+    rc = L.scalce_order_plan(int(total_records), int(window_text_bytes), int(max_record_bytes), out)
+    if rc:
+        raise ScalceError(f"[{rc}] scalce_order_plan")
+    return int(out[0]), int(out[1])
+
+
+def records_permute_ws_bytes(nrecords):
+    L = lib()
+    L.scalce_records_permute_ws_bytes.argtypes = [C.c_uint64]
+    L.scalce_records_permute_ws_bytes.restype = C.c_uint64
+    return int(L.scalce_records_permute_ws_bytes(int(nrecords)))
+
+
+def records_permute(ctx, d_text, d_record_offsets, nrecords, text_bytes, d_source, d_out, out_cap, d_out_offsets, d_ws, stream=0):
+    """scalce_records_permute: output record r is input record d_source[r] (device pointers; see the header)."""
+    L = ctx.L
+    L.scalce_records_permute.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64,
+                                         C.c_void_p, C.c_void_p, C.c_void_p]
+    L.scalce_records_permute.restype = C.c_int
+    ctx._check(L.scalce_records_permute(ctx.h, d_text, d_record_offsets, int(nrecords), int(text_bytes), d_source, d_out, int(out_cap),
+                                        d_out_offsets, d_ws, stream))
+
+
+def order_group_ws_bytes(nrecords, nstripes):
+    L = lib()
+    L.scalce_order_group_ws_bytes.argtypes = [C.c_uint64, C.c_uint64]
+    L.scalce_order_group_ws_bytes.restype = C.c_uint64
+    return int(L.scalce_order_group_ws_bytes(int(nrecords), int(nstripes)))
+
+
+def order_group(ctx, d_index, nrecords, stripe_records, total_records, nstripes, d_source, d_stripe_counts, d_bad, d_ws, stream=0):
+    """scalce_order_group: a window's records grouped by the stripe of their entry, stable (device pointers)."""
+    L = ctx.L
+    L.scalce_order_group.argtypes = [C.c_void_p, C.c_void_p] + [C.c_uint64] * 4 + [C.c_void_p] * 5
+    L.scalce_order_group.restype = C.c_int
+    ctx._check(L.scalce_order_group(ctx.h, d_index, int(nrecords), int(stripe_records), int(total_records), int(nstripes), d_source,
+                                    d_stripe_counts, d_bad, d_ws, stream))
+
+
+def order_place(ctx, d_index, m, base, expect, d_source, d_bad, stream=0):
+    """scalce_order_place: d_source[d_index[i] - base] = i, checked by scatter and verify (device pointers)."""
+    L = ctx.L
+    L.scalce_order_place.argtypes = [C.c_void_p, C.c_void_p] + [C.c_uint64] * 3 + [C.c_void_p] * 3
+    L.scalce_order_place.restype = C.c_int
+    ctx._check(L.scalce_order_place(ctx.h, d_index, int(m), int(base), int(expect), d_source, d_bad, stream))
+
+
+def order_gather(ctx, d_in, d_source, n, d_out, stream=0):
+    L = ctx.L
+    L.scalce_order_gather.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+    L.scalce_order_gather.restype = C.c_int
+    ctx._check(L.scalce_order_gather(ctx.h, d_in, d_source, int(n), d_out, stream))
+
+
+class RestoreParams(C.Structure):
+    _fields_ = [("order_rd", READ_FN * 2), ("order_user", C.c_void_p * 2), ("spill_dir", C.c_char_p)]
+
+
+class RestoreStats(C.Structure):
+    _fields_ = [("records", C.c_uint64), ("stripes", C.c_uint64), ("stripe_records", C.c_uint64), ("spilled_bytes", C.c_uint64),
+                ("group_pass_s", C.c_double), ("stripe_pass_s", C.c_double), ("spill_write_s", C.c_double),
+                ("spill_read_s", C.c_double), ("place_wait_s", C.c_double)]
+
+
+def stream_decompress_restore(ctx, readers, order_readers, write, spill_dir, mates=1, interleave=False, no_qualities=False,
+                              mate_digit=None, library=None, split=0, window_text_bytes=0, length_readers=None):
+    """scalce_stream_decompress_restore: stream_decompress with the input order restored.  order_readers[m]: the callable
+    (cap) -> bytes of the .scalceo stream, read from its start once per mate pass (interleaved: only [0]); write receives
+    the text in input order, one stripe per call, first_record = the input index of its first record.  Returns
+    UnpackStats; its attribute `restore` holds the RestoreStats."""
+    keep = []
+
+    def wrap(fn):
+        def cb(_user, dst, cap):
+            try:
+                data = fn(int(cap))
+            except Exception:  # noqa: BLE001 - reported to the library as a read error
+                return -1
+            if data:
+                C.memmove(dst, data, len(data))
+            return len(data)
+        keep.append(READ_FN(cb))
+        return keep[-1]
+
+    def wcb(_user, mate, first, nrec, text, nbytes, roff):
+        try:
+            offs = [roff[i] for i in range(nrec + 1)] if roff else None
+            write(int(mate), int(first), int(nrec), C.string_at(text, nbytes), offs)
+        except Exception:  # noqa: BLE001 - reported to the library as a failed write
+            return 1
+        return 0
+
+    wfn = WRITE_FN(wcb)
+    rd = ((READ_FN * 3) * 2)()
+    user = ((C.c_void_p * 3) * 2)()
+    for m in range(mates):
+        for k in range(3):
+            if readers[m][k] is not None:
+                rd[m][k] = wrap(readers[m][k])
+    p = UnpackParams(mates, int(interleave), int(no_qualities), int(mates == 2 if mate_digit is None else mate_digit),
+                     int(library is not None), int(split), library.encode() if library is not None else None, int(window_text_bytes))
+    rp = RestoreParams()
+    rp.spill_dir = os.fsencode(spill_dir)
+    for m in range(1 if interleave else mates):
+        rp.order_rd[m] = wrap(order_readers[m])
+        if length_readers is not None and length_readers[m] is not None:
+            p.len_rd[m] = wrap(length_readers[m])
+    st = UnpackStats()
+    rst = RestoreStats()
+    msg = C.create_string_buffer(1024)
+    L = ctx.L
+    L.scalce_stream_decompress_restore.argtypes = [C.c_void_p, C.POINTER(UnpackParams), C.POINTER(RestoreParams), C.c_void_p, C.c_void_p,
+                                                   WRITE_FN, C.c_void_p, C.POINTER(UnpackStats), C.POINTER(RestoreStats), C.c_char_p,
+                                                   C.c_size_t]
+    L.scalce_stream_decompress_restore.restype = C.c_int
+    rc = L.scalce_stream_decompress_restore(ctx.h, C.byref(p), C.byref(rp), C.cast(rd, C.c_void_p), C.cast(user, C.c_void_p), wfn, None,
+                                            C.byref(st), C.byref(rst), msg, len(msg))
+    if rc:
+        raise ScalceError(f"[{rc}] " + msg.value.decode(errors="replace"))
+    st.restore = rst
+    return st
+
+
 class Workspace:
     """Front-stage device buffers shared by several batches (scalce_workspace): see include/scalce_hip.h."""
 
@@ -746,6 +904,11 @@ class Batch:
 
     def set_lean(self, lean=True):
         self.L.scalce_batch_set_lean(self.h, int(lean))
+
+    def set_keep_order(self, on=True):
+        """OUT_PERM stays valid behind emit() and finish(), lean or not (scalce_batch_set_keep_order)."""
+        self.L.scalce_batch_set_keep_order.argtypes = [C.c_void_p, C.c_int]
+        self._check(self.L.scalce_batch_set_keep_order(self.h, int(on)))
 
     def quality(self, stream=0):
         self._check(self.L.scalce_batch_quality(self.h, stream))
