@@ -214,6 +214,16 @@ int scalce_batch_coder_round(const scalce_batch *b);  /* symbols per round of th
  * span of the counters laid out, inside = 1 when no symbol of the piece lies outside them (all 0 when source is 0).
  * Waits for the whole device and reads the three back. */
 int scalce_batch_quality_plan(const scalce_batch *b, int mate, uint32_t out[4]);
+/* For tests: what the ingest of the last piece (scalce_batch_ingest, _append, _front, _compress) did for `mate`.
+ * out[0] = the kernel that wrote the mate's rows -- 0: nothing ingested yet, or an empty piece, 1: the one-pass tile kernel
+ * (read lengths 16 .. 160), 2: the indexed kernel that works out of LDS tiles (read lengths up to 160), 3: the indexed kernel
+ * that reads every record straight from memory (longer reads); out[1] = 1 when the one-pass kernel ran first, met a record that
+ * does not end inside its tile's overlap (or a tile with more than 2048 lines) and the piece was done again by an indexed
+ * kernel; out[2] = 1 when the line index of the piece was built on the way (the indexed kernels and names longer than 15
+ * characters need it); out[3] = the bytes the piece added to the store of names longer than 15 characters (mate 0; 0 for
+ * mate 1 of two texts).  Interleaved batches ingest both mates from one text: mate 1 reports mate 0's out[1..3], and in out[0]
+ * the kernel that wrote its own rows.  Host bookkeeping only: nothing is launched, waited for or read back. */
+int scalce_batch_ingest_plan(const scalce_batch *b, int mate, uint32_t out[4]);
 /* edge[0..1] = the first two, edge[2..3] = the last two q' symbols of the rows held (input order), *nsym = how many there are,
  * *read_len (may be NULL) = symbols per row: what a rank of a sharded run tells its neighbours (qualities.cpp:179-198: prev[]
  * runs across reads, so two trigrams straddle every rank boundary).  Runs on `stream` and synchronises it. */
@@ -332,8 +342,10 @@ enum {
   SCALCE_OUT_QINPUT = 9,    /* N*L bytes: q' in input order, mate m                          */
   SCALCE_OUT_NAMELEN = 10,  /* N bytes: stored name length per read, input order             */
   SCALCE_OUT_BUCKET_NAME_BYTES = 11, /* (buckets+1) x u64: bytes of each bucket's records in SCALCE_OUT_NAMES (after emit) */
-  SCALCE_OUT_LENGTHS = 12   /* variable-length runs: N x u16, read_len - length of the k-th emitted record of mate m (mate 2 in
+  SCALCE_OUT_LENGTHS = 12,  /* variable-length runs: N x u16, read_len - length of the k-th emitted record of mate m (mate 2 in
                                mate 1's order, like its reads); valid behind scalce_batch_order; empty for other runs */
+  SCALCE_OUT_NAMECELLS = 13 /* for tests: N x 16 bytes, input order: [stored length][the name's first 15 characters, zero behind a
+                               shorter name] as the ingest left them; empty with names off, gone once a lean batch has emitted */
 };
 int scalce_batch_output(const scalce_batch *b, int which, int mate, const void **d_ptr, uint64_t *nbytes);
 /* Framing on the way out (replaces the copy loop of ac_write, arithmetic.cpp:318-363: the reference frames each coded

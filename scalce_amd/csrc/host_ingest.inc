@@ -41,6 +41,8 @@ static int ensure_line_index(scalce_batch *b, int mate, hipStream_t s) {
 // the first `nrec` records of the text -> rows [base, base + nrec): 2-bit bases, q', names
 // (A one-pass variant -- no count pass, the tiles' line bases by decoupled look-back between the workgroups -- was byte-exact
 // and slower: 9.2 ms against 1.7 + 6.2 at 50 M x 100 bp, rounds 3-4; removed in round 5.)
+// which kernel wrote a mate's rows (scalce_batch_ingest_plan, scalce_hip.h)
+enum IngestKernel : u32 { INGK_NONE = 0, INGK_ONE_PASS = 1, INGK_TILED = 2, INGK_DIRECT = 3 };
 // LPR = lines per record, QOUT = q' rows written, IL = interleaved pairs: the record variants of the kernels (unpack_record_at).
 // IL: called for mate 0 with the one text, which it ingests for both mates -- nrec pairs, one count, one line index.
 template <int LPR, bool QOUT, bool IL>
@@ -58,6 +60,7 @@ static int piece_unpack_t(scalce_batch *b, int mate, const u8 *d_text, u64 nbyte
     b->text_bytes[m] = nbytes;
     b->line_index_ok[m] = false;
     b->piece_consumed[m] = 0;
+    for (int i = 0; i < 4; i++) b->ingest_plan[m][i] = 0;
   }
   if (!nrec) return SCALCE_OK;
   // the arguments of the launches that write mate m's rows
@@ -120,9 +123,10 @@ static int piece_unpack_t(scalce_batch *b, int mate, const u8 *d_text, u64 nbyte
         w.tile_mm_owner[m] = b;
       }
     { int rc = read_words(b, d_flags, &flags, sizeof flags / 4, s); if (rc) return rc; }
+    for (int m = mate; m < mate + NMATE; m++) b->ingest_plan[m][0] = INGK_ONE_PASS;
     if (flags.slow) {  // a record longer than the overlap: redo the piece the indexed way
       fused = false;
-      for (int m = mate; m < mate + NMATE; m++) b->mm_valid[m] = false;
+      for (int m = mate; m < mate + NMATE; m++) { b->mm_valid[m] = false; b->ingest_plan[m][1] = 1; }
     }
   }
   if (!fused) {
@@ -139,8 +143,9 @@ static int piece_unpack_t(scalce_batch *b, int mate, const u8 *d_text, u64 nbyte
     for (int m = mate; m < mate + NMATE; m++) {  // (IL: mate 2 from the same text and line index)
       UnpackArgs am = a;
       if (m != mate) { am = args_of(m); am.line_end = a.line_end; }
-      if ((size_t)UNP_RPB * am.L <= (size_t)UNP_Q_CAP)
-        LAUNCH(k_unpack_tiled, cdiv(nrec, UNP_RPB), 2 * UNP_RPB, unp_text_cap(am.L) + 32 + (QOUT ? unp_q_cap(am.L) : 0u), s, am);
+      const bool tiled = (size_t)UNP_RPB * am.L <= (size_t)UNP_Q_CAP;
+      b->ingest_plan[m][0] = tiled ? INGK_TILED : INGK_DIRECT;
+      if (tiled) LAUNCH(k_unpack_tiled, cdiv(nrec, UNP_RPB), 2 * UNP_RPB, unp_text_cap(am.L) + 32 + (QOUT ? unp_q_cap(am.L) : 0u), s, am);
       else LAUNCH(k_unpack, cdiv(nrec, 256), 256, 0, s, am);
     }
     if (fused_rows)
@@ -167,8 +172,12 @@ static int piece_unpack_t(scalce_batch *b, int mate, const u8 *d_text, u64 nbyte
       { int rc = ensure_keep(b, w.names_in, b->names_in_used + total + 64, b->names_in_used, s); if (rc) return rc; }
       LAUNCH(k_long_names, cdiv(nrec, 256), 256, 0, s, nrec, d_text, w.line_end[mate].as<u64>(), a.namelen, off, b->names_in_used, w.names_in.as<u8>());
       b->names_in_used += total;
+      b->ingest_plan[mate][3] = (u32)total;
     }
   }
+  b->ingest_plan[mate][2] = b->line_index_ok[mate] ? 1u : 0u;
+  if (IL)  // (one text, one line index, mate 1's names: mate 2 reports what mate 1 does, and the kernel that wrote its own rows)
+    for (int i = 1; i < 4; i++) b->ingest_plan[mate + 1][i] = b->ingest_plan[mate][i];
   return SCALCE_OK;
 }
 template <bool IL>
@@ -246,6 +255,8 @@ static void batch_restart(scalce_batch *b) {
   b->names_in_used = 0;
   b->tri_expected[0] = b->tri_expected[1] = 0;
   b->ingested[0] = b->ingested[1] = false;
+  for (int m = 0; m < 2; m++)
+    for (int i = 0; i < 4; i++) b->ingest_plan[m][i] = 0;
   // (frames laid out but not copied belong to the shard that is being replaced: scalce_batch_qual_window must not serve them)
   for (int m = 0; m < 2; m++) { b->frame_virtual[m] = 0; b->frame_off_host[m].clear(); }
 }
@@ -484,6 +495,14 @@ extern "C" int scalce_batch_set_fused_rows(scalce_batch *b, int on) {
 }
 
 // ---- stage 1: quality statistics -------------------------------------------------------------------
+// what the last piece_unpack_t did for `mate`: {kernel, slow, line index built, long-name bytes} -- the host's own branches,
+// nothing is read back
+extern "C" int scalce_batch_ingest_plan(const scalce_batch *b, int mate, uint32_t out[4]) {
+  if (!b || !out || mate < 0 || mate >= b->nm) return SCALCE_ERR_ARG;
+  for (int i = 0; i < 4; i++) out[i] = b->ingest_plan[mate][i];
+  return SCALCE_OK;
+}
+
 // where a mate's symbol range came from (scalce_batch_quality_plan, scalce_hip.h)
 enum QualitySource : u32 { QSRC_NONE = 0, QSRC_TILES = 1, QSRC_ROWS = 2, QSRC_WHOLE = 3 };
 extern "C" int scalce_batch_quality(scalce_batch *b, void *stream) {

@@ -303,6 +303,7 @@ struct scalce_batch {
   bool keep_order = false;   // SCALCE_OUT_PERM is an output of the run: a lean batch keeps it (scalce_batch_set_keep_order)
   u64 tri_expected[2] = {0, 0};  // trigrams counted so far (tri_check_k)
   u32 quality_source[2] = {0, 0};  // where the last scalce_batch_quality took the mate's symbol range from (scalce_batch_quality_plan)
+  u32 ingest_plan[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};  // what the last piece_unpack_t did for the mate (scalce_batch_ingest_plan)
   u64 names_in_used = 0;     // bytes of the long-name store in use
   u64 S_rows = ~0ull;        // rows the record-size prefix sums in S cover (scalce_batch_chunk_plan), ~0 = stale
   u64 walk_rows = 0;         // rows [0, walk_rows) whose first tokenizer walk (tok_bucket / tok_pos) scalce_batch_chunk_plan has

@@ -467,13 +467,14 @@ __global__ __launch_bounds__(ING_THREADS) void ingest_tiles2_k(Ingest2Args g, In
   __shared__ u32 sm[ING_THREADS / 64];
   __shared__ u32 s_count[2];
   __shared__ u32 s_mm[2 * (ING_THREADS / 64)];
+  __shared__ u32 s_unwritten[2];                                   // per mate: a rejected record left its q' row unwritten
   const int tid = threadIdx.x;
   const u32 ti = blockIdx.x;                                       // the tile
   const u64 t0 = (u64)ti * ING_TILE;                               // text offset of the tile
   const u64 avail = a.u.nbytes - t0;
   const u32 len = (u32)(avail < ING_TILE + ING_OVER ? avail : ING_TILE + ING_OVER);
   if (QOUT && tid < 128 * (int)NMATE) lut[tid] = tid < 128 ? a.u.qlut[tid] : g2.i.u.qlut[tid - 128];
-  if (tid == 0) s_count[1] = 0;
+  if (tid == 0) { s_count[1] = 0; s_unwritten[0] = s_unwritten[1] = 0; }
   for (u32 i = (u32)tid * 16; i < len + 8; i += ING_THREADS * 16) {
     uint4 v;
     if (t0 + i + 16 <= a.u.nbytes) v = *reinterpret_cast<const uint4 *>(a.u.text + t0 + i);
@@ -536,15 +537,18 @@ __global__ __launch_bounds__(ING_THREADS) void ingest_tiles2_k(Ingest2Args g, In
   const u64 rid0 = (G0 + j0) / RL;
   const u32 nloc = j0 < count ? (count - j0 + RL - 1) / RL : 0u;  // name lines that END in tile + overlap (<= RECMAX)
   // one thread per record (pair): is it this tile's (it STARTS here and is whole), are its lines as long as they must be, its name
-  for (u32 k = (u32)tid; k < nloc; k += ING_THREADS) {
+  // (k = nloc: the record behind them, whose name line may begin in this tile and end behind the overlap -- it is this tile's too)
+  for (u32 k = (u32)tid; k <= nloc; k += ING_THREADS) {
     const u32 j = j0 + RL * k;
     const u64 rid = rid0 + k;
     bool take = rid < a.u.nrec;
     u32 ns = 0;
     if (take) {
-      ns = j ? (u32)nl[j - 1] + 1 : 0u;
-      if (j && j - 1 >= count) take = false;
-      else if (ns >= ING_TILE) take = false;                        // starts in the next tile: that workgroup's record
+      if (j && j - 1 >= count) take = false;                        // (where it starts is not in sight: not in this tile)
+      else {
+        ns = j ? (u32)nl[j - 1] + 1 : 0u;
+        if (ns >= ING_TILE || ns >= len) take = false;              // starts in the next tile: that workgroup's record (or not at all)
+      }
     }
     if (take && j + RL - 1 >= count) {                              // all its lines must end inside tile + overlap
       take = false;
@@ -563,7 +567,10 @@ __global__ __launch_bounds__(ING_THREADS) void ingest_tiles2_k(Ingest2Args g, In
       if (p1 - p0 - 1 != (u32)L || (LPR == 4 && p3 - p2 - 1 != (u32)L)) {
         dev_fail(u.err, E_READLEN, rid, p1 - p0 - 1);
         rec_sb[slot] = 0xFFFFu;                                       // nothing of it is unpacked
-        if (QOUT) rec_sq[slot] = 0xFFFFu;
+        if (QOUT) {
+          rec_sq[slot] = 0xFFFFu;
+          s_unwritten[m] = 1u;  // its q' row holds whatever the memory held: the tile reports the widest range (see below)
+        }
         if (u.mate == 0) {  // the run ends with an error; until the host sees it, later stages must find a well-formed row
           u.namelen[rid] = 0;
           if (u.namecell) { u32x4a z; z.x = z.y = z.z = z.w = 0; *reinterpret_cast<u32x4a *>(u.namecell + (u64)u.cellstride * rid) = z; }
@@ -729,7 +736,9 @@ __global__ __launch_bounds__(ING_THREADS) void ingest_tiles2_k(Ingest2Args g, In
     if (lane_id() == 0) { s_mm[2 * wave_id()] = lo; s_mm[2 * wave_id() + 1] = hi; }
     __syncthreads();  // (also: the q' rows of the tile are written)
     for (int w = 0; w < ING_THREADS / 64; w++) { lo = min(lo, s_mm[2 * w]); hi = max(hi, s_mm[2 * w + 1]); }
-    if (tid == 0 && gm.tile_minmax) gm.tile_minmax[ti] = (u16)(lo | (hi << 8));
+    // (a rejected record's row was not written, and the statistics stage runs before the host sees the error: 0 .. 255 tells it
+    // that symbols of the piece lie outside the counters it lays out, so that its counting loop tests every one of them)
+    if (tid == 0 && gm.tile_minmax) gm.tile_minmax[ti] = s_unwritten[m] ? (u16)0xFF00u : (u16)(lo | (hi << 8));
     if (hi >= 80 && !um.no_ac) {  // a symbol the coder's tables have no row for (arithmetic.h:47): which record was it?
       for (u32 k = (u32)tid; k < ntake; k += ING_THREADS) {
         if (sbm[k] == 0xFFFFu) continue;

@@ -17,6 +17,7 @@ _LIB = None
 
 OUT_READS, OUT_NAMES, OUT_QUAL, OUT_TABLE, OUT_FREQ4, OUT_TOKENS, OUT_PERM, OUT_QSTREAM, OUT_BUCKET_COUNTS, OUT_QINPUT, OUT_NAMELEN = range(11)
 OUT_LENGTHS = 12  # variable-length runs: N x u16, read_len - length per record in output order
+OUT_NAMECELLS = 13  # for tests: N x 16 bytes, [stored length][first 15 characters, zero behind a shorter name], input order
 STAGES = ("ingest", "quality", "tokenize", "order", "emit", "entropy")
 ROOT_CORE = 0x3FFFFFFF
 
@@ -115,6 +116,7 @@ def lib():
     L.scalce_batch_set_lean.restype = None
     L.scalce_batch_quality.argtypes = [vp, vp]
     L.scalce_batch_quality_plan.argtypes = [vp, i32, C.POINTER(C.c_uint32)]
+    L.scalce_batch_ingest_plan.argtypes = [vp, i32, C.POINTER(C.c_uint32)]
     L.scalce_batch_tokenize.argtypes = [vp, vp, vp]
     L.scalce_batch_order.argtypes = [vp, vp]
     L.scalce_batch_emit.argtypes = [vp, vp]
@@ -918,6 +920,13 @@ class Batch:
         source 0: nothing counted, 1: tile ranges of the one-pass ingest, 2: the q' rows scanned, 3: the whole alphabet."""
         out = (C.c_uint32 * 4)()
         self._check(self.L.scalce_batch_quality_plan(self.h, int(mate), out))
+        return tuple(int(x) for x in out)
+
+    def ingest_plan(self, mate=0):
+        """For tests: what the ingest of the last piece did for `mate` (scalce_batch_ingest_plan) -> (kernel, slow, line index
+        built, long-name bytes); kernel 0: nothing ingested, 1: one-pass, 2: indexed out of LDS tiles, 3: indexed, direct."""
+        out = (C.c_uint32 * 4)()
+        self._check(self.L.scalce_batch_ingest_plan(self.h, int(mate), out))
         return tuple(int(x) for x in out)
 
     def tokenize(self, d_prior_counts=None, stream=0):
