@@ -1,12 +1,19 @@
 // orderstream.hpp -- the order stream of an archive made with --keep-order (PREFIX_1.scalceo), host side only: no device call,
 // no HIP header.  Layout: the 8 magic bytes, int32 entry width (4), int32 0, int64 N, then N little-endian u32: entry k is the
 // input index of the k-th record (pair) of the archive.  The writer (cli.cpp) and the reader (stream_decode.cpp) share it, and
-// the table that says where each window's share of each stripe lies in the spill of the restore.
+// the table that says where each window's share of each stripe lies in the spill of the restore, with the spill's record word
+// and the spill file itself.
 #pragma once
+#include <fcntl.h>
+#include <unistd.h>
+
+#include <algorithm>
+#include <cerrno>
 #include <cstddef>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <string>
 #include <vector>
 
 namespace scalce_host {
@@ -63,6 +70,11 @@ inline void order_plan(uint64_t total, uint64_t window, uint64_t max_record_byte
   out[1] = S;
 }
 
+// what the spill keeps per record beside its text: the record's entry of the order stream and the bytes of its text
+inline uint64_t record_word(uint32_t entry, uint64_t size) { return (uint64_t)entry | size << 32; }
+inline uint32_t record_entry(uint64_t word) { return (uint32_t)word; }
+inline uint64_t record_size(uint64_t word) { return word >> 32; }
+
 // Where each window's share of each stripe lies in the spill.  A window's records are appended grouped by stripe, so its
 // share of stripe s follows its share of stripe s - 1: the table keeps, per window, where its records begin in the text and
 // in the record words, and its non-empty shares; stripes are then taken in rising order and every window keeps a cursor.
@@ -110,6 +122,39 @@ struct StripeTable {
     }
     if (bytes) *bytes = by;
     return rec;
+  }
+};
+
+// One file of the spill: made once with mkstemp and unlinked at once -- nothing stays behind whatever happens --, emptied
+// when a further mate pass begins, closed when it goes.  A false return leaves errno for the caller's message.
+struct SpillFile {
+  int fd = -1;
+  uint64_t piece = 1u << 30;  // the most one call moves (tools/orderstream_check.cpp lowers it)
+  SpillFile() = default;
+  SpillFile(const SpillFile &) = delete;
+  SpillFile &operator=(const SpillFile &) = delete;
+  ~SpillFile() { if (fd >= 0) ::close(fd); }
+  // *what: the verb of the step that failed ("make", "empty")
+  bool reset(const std::string &dir, const char **what) {
+    if (fd >= 0) { *what = "empty"; return ftruncate(fd, 0) == 0; }
+    *what = "make";
+    std::string path = dir + "/scalce_order_XXXXXX";
+    fd = mkstemp(&path[0]);
+    if (fd >= 0) unlink(path.c_str());
+    return fd >= 0;
+  }
+  // n bytes at `at`, written from p or read into it: interrupted calls are repeated, a write that takes nothing is a full
+  // disk (ENOSPC), a read that gives nothing lies behind the file's end (EIO)
+  bool transfer(bool write, void *p, uint64_t n, uint64_t at) {
+    uint8_t *b = static_cast<uint8_t *>(p);
+    while (n) {
+      const size_t want = (size_t)std::min(n, piece);
+      const ssize_t k = write ? ::pwrite(fd, b, want, (off_t)at) : ::pread(fd, b, want, (off_t)at);
+      if (k < 0 && errno == EINTR) continue;
+      if (k <= 0) { if (!k) errno = write ? ENOSPC : EIO; return false; }
+      b += k; n -= (uint64_t)k; at += (uint64_t)k;
+    }
+    return true;
   }
 };
 

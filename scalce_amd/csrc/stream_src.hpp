@@ -1,4 +1,4 @@
-// stream_src.hpp -- one stream of an archive behind its read callback, as the decompress host (stream_decode.cpp) walks it.
+// stream_src.hpp -- one stream of an archive behind its read callback, as the decompress host (archive_walk.hpp) walks it.
 // Host side only: callbacks and a std::vector, no device call, no HIP header, so that its arithmetic can be run on its own
 // (tools/src_check.cpp).
 #pragma once
@@ -53,6 +53,14 @@ struct Src {
       if (k > 0) end += (size_t)k;
     }
     return end >= n;
+  }
+  // the next little-endian T (a header field, a size word; the hosts are little-endian), or false: the stream ends, or
+  // fails, before it -- nothing is taken then
+  template <typename T> bool get(T &v, size_t look = ~(size_t)0) {
+    if (!need(sizeof(T), look)) return false;
+    memcpy(&v, ptr(), sizeof(T));
+    skip(sizeof(T));
+    return true;
   }
   // passes over n bytes: what the look-ahead buffer holds first, then the caller's skip, or -- without one -- reads that are
   // dropped; returns the bytes passed over (< n: the stream ends there, or has failed)

@@ -607,6 +607,52 @@ def range_plan_quality(read_len, first, n, total_syms):
     return tuple(int(v) for v in out)
 
 
+# what stream_decompress and stream_decompress_restore share: their callbacks over Python callables (`keep` holds them
+# alive for the call), their UnpackParams and their error
+def _unpack_read_fn(keep, fn):
+    def cb(_user, dst, cap):
+        try:
+            data = fn(int(cap))
+        except Exception:  # noqa: BLE001 - reported to the library as a read error
+            return -1
+        if data:
+            C.memmove(dst, data, len(data))
+        return len(data)
+    keep.append(READ_FN(cb))
+    return keep[-1]
+
+
+def _unpack_skip_fn(keep, fn):
+    def cb(_user, nbytes):
+        try:
+            return int(fn(int(nbytes)))
+        except Exception:  # noqa: BLE001 - reported to the library as a read error
+            return -1
+    keep.append(SKIP_FN(cb))
+    return keep[-1]
+
+
+def _unpack_write_fn(write):
+    def wcb(_user, mate, first, nrec, text, nbytes, roff):
+        try:
+            offs = [roff[i] for i in range(nrec + 1)] if roff else None
+            write(int(mate), int(first), int(nrec), C.string_at(text, nbytes), offs)
+        except Exception:  # noqa: BLE001 - reported to the library as a failed write
+            return 1
+        return 0
+    return WRITE_FN(wcb)
+
+
+def _unpack_params(mates, interleave, no_qualities, mate_digit, library, split, window_text_bytes):
+    return UnpackParams(mates, int(interleave), int(no_qualities), int(mates == 2 if mate_digit is None else mate_digit),
+                        int(library is not None), int(split), library.encode() if library is not None else None, int(window_text_bytes))
+
+
+def _unpack_check(rc, msg):
+    if rc:
+        raise ScalceError(f"[{rc}] " + msg.value.decode(errors="replace"))
+
+
 def stream_decompress(ctx, readers, write, mates=1, interleave=False, no_qualities=False, mate_digit=None, library=None,
                       split=0, window_text_bytes=0, first_record=0, nrecords=None, skippers=None, length_readers=None,
                       length_skippers=None):
@@ -619,52 +665,22 @@ def stream_decompress(ctx, readers, write, mates=1, interleave=False, no_qualiti
     length_skippers[m]): the .scalcel stream of a variable-length archive, one callable per mate.  Returns UnpackStats; its attribute
     `range` holds the UnpackRangeStats of the run."""
     keep = []
-
-    def wrap(fn):
-        def cb(_user, dst, cap):
-            try:
-                data = fn(int(cap))
-            except Exception:  # noqa: BLE001 - reported to the library as a read error
-                return -1
-            if data:
-                C.memmove(dst, data, len(data))
-            return len(data)
-        keep.append(READ_FN(cb))
-        return keep[-1]
-
-    def wcb(_user, mate, first, nrec, text, nbytes, roff):
-        try:
-            offs = [roff[i] for i in range(nrec + 1)] if roff else None
-            write(int(mate), int(first), int(nrec), C.string_at(text, nbytes), offs)
-        except Exception:  # noqa: BLE001 - reported to the library as a failed write
-            return 1
-        return 0
-    def wrap_skip(fn):
-        def cb(_user, nbytes):
-            try:
-                return int(fn(int(nbytes)))
-            except Exception:  # noqa: BLE001 - reported to the library as a read error
-                return -1
-        keep.append(SKIP_FN(cb))
-        return keep[-1]
-
-    wfn = WRITE_FN(wcb)
+    wfn = _unpack_write_fn(write)
     rd = ((READ_FN * 3) * 2)()
     user = ((C.c_void_p * 3) * 2)()
     rg = UnpackRange(int(first_record), (1 << 64) - 1 if nrecords is None else int(nrecords))
     for m in range(mates):
         for k in range(3):
             if readers[m][k] is not None:
-                rd[m][k] = wrap(readers[m][k])
+                rd[m][k] = _unpack_read_fn(keep, readers[m][k])
             if skippers is not None and skippers[m] is not None and skippers[m][k] is not None:
-                rg.skip[m][k] = wrap_skip(skippers[m][k])
-    p = UnpackParams(mates, int(interleave), int(no_qualities), int(mates == 2 if mate_digit is None else mate_digit),
-                     int(library is not None), int(split), library.encode() if library is not None else None, int(window_text_bytes))
+                rg.skip[m][k] = _unpack_skip_fn(keep, skippers[m][k])
+    p = _unpack_params(mates, interleave, no_qualities, mate_digit, library, split, window_text_bytes)
     for m in range(mates):
         if length_readers is not None and length_readers[m] is not None:
-            p.len_rd[m] = wrap(length_readers[m])
+            p.len_rd[m] = _unpack_read_fn(keep, length_readers[m])
         if length_skippers is not None and length_skippers[m] is not None:
-            p.len_skip[m] = wrap_skip(length_skippers[m])
+            p.len_skip[m] = _unpack_skip_fn(keep, length_skippers[m])
     st = UnpackStats()
     rst = UnpackRangeStats()
     msg = C.create_string_buffer(1024)
@@ -675,8 +691,7 @@ def stream_decompress(ctx, readers, write, mates=1, interleave=False, no_qualiti
     L.scalce_stream_decompress_range.restype = C.c_int
     rc = L.scalce_stream_decompress_range(ctx.h, C.byref(p), C.byref(rg), C.cast(rd, C.c_void_p), C.cast(user, C.c_void_p), wfn, None,
                                           C.byref(st), C.byref(rst), msg, len(msg))
-    if rc:
-        raise ScalceError(f"[{rc}] " + msg.value.decode(errors="replace"))
+    _unpack_check(rc, msg)
     st.range = rst
     return st
 
@@ -786,42 +801,20 @@ def stream_decompress_restore(ctx, readers, order_readers, write, spill_dir, mat
     the text in input order, one stripe per call, first_record = the input index of its first record.  Returns
     UnpackStats; its attribute `restore` holds the RestoreStats."""
     keep = []
-
-    def wrap(fn):
-        def cb(_user, dst, cap):
-            try:
-                data = fn(int(cap))
-            except Exception:  # noqa: BLE001 - reported to the library as a read error
-                return -1
-            if data:
-                C.memmove(dst, data, len(data))
-            return len(data)
-        keep.append(READ_FN(cb))
-        return keep[-1]
-
-    def wcb(_user, mate, first, nrec, text, nbytes, roff):
-        try:
-            offs = [roff[i] for i in range(nrec + 1)] if roff else None
-            write(int(mate), int(first), int(nrec), C.string_at(text, nbytes), offs)
-        except Exception:  # noqa: BLE001 - reported to the library as a failed write
-            return 1
-        return 0
-
-    wfn = WRITE_FN(wcb)
+    wfn = _unpack_write_fn(write)
     rd = ((READ_FN * 3) * 2)()
     user = ((C.c_void_p * 3) * 2)()
     for m in range(mates):
         for k in range(3):
             if readers[m][k] is not None:
-                rd[m][k] = wrap(readers[m][k])
-    p = UnpackParams(mates, int(interleave), int(no_qualities), int(mates == 2 if mate_digit is None else mate_digit),
-                     int(library is not None), int(split), library.encode() if library is not None else None, int(window_text_bytes))
+                rd[m][k] = _unpack_read_fn(keep, readers[m][k])
+    p = _unpack_params(mates, interleave, no_qualities, mate_digit, library, split, window_text_bytes)
     rp = RestoreParams()
     rp.spill_dir = os.fsencode(spill_dir)
     for m in range(1 if interleave else mates):
-        rp.order_rd[m] = wrap(order_readers[m])
+        rp.order_rd[m] = _unpack_read_fn(keep, order_readers[m])
         if length_readers is not None and length_readers[m] is not None:
-            p.len_rd[m] = wrap(length_readers[m])
+            p.len_rd[m] = _unpack_read_fn(keep, length_readers[m])
     st = UnpackStats()
     rst = RestoreStats()
     msg = C.create_string_buffer(1024)
@@ -832,8 +825,7 @@ def stream_decompress_restore(ctx, readers, order_readers, write, spill_dir, mat
     L.scalce_stream_decompress_restore.restype = C.c_int
     rc = L.scalce_stream_decompress_restore(ctx.h, C.byref(p), C.byref(rp), C.cast(rd, C.c_void_p), C.cast(user, C.c_void_p), wfn, None,
                                             C.byref(st), C.byref(rst), msg, len(msg))
-    if rc:
-        raise ScalceError(f"[{rc}] " + msg.value.decode(errors="replace"))
+    _unpack_check(rc, msg)
     st.restore = rst
     return st
 

@@ -1,5 +1,5 @@
 // orderstream_check.cpp -- the host side of the order stream (scalce_amd/csrc/orderstream.hpp: header, error strings, entry
-// checks, the stripe plan and the table of the spill's shares) on its own: a program for AddressSanitizer, no device, no HIP.
+// checks, the stripe plan, the table of the spill's shares, its record word and its file) on its own: a program for AddressSanitizer, no device, no HIP.
 //   g++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all tools/orderstream_check.cpp -o /tmp/oc && /tmp/oc
 // Every array handed to the code under test is a heap block of exactly the size it may touch.
 #include <cstdio>
@@ -148,6 +148,33 @@ static void table_refuses() {
   CHECK(t.add_window(counts.get(), off.get(), 3) && t.records == 3 && t.text_bytes == 30);
 }
 
+// the record word, and the spill file: write and read across a piece boundary, emptied between passes, a read past the end
+static void spill_file() {
+  CHECK(record_word(0xFFFFFFFFu, 5) == 0x5FFFFFFFFull && record_entry(0x5FFFFFFFFull) == 0xFFFFFFFFu && record_size(0x5FFFFFFFFull) == 5);
+  CHECK(record_word(7, 0xFFFFFFFFull) == 0xFFFFFFFF00000007ull && record_size(0xFFFFFFFF00000007ull) == 0xFFFFFFFFull);
+  const char *tmp = getenv("TMPDIR");
+  const std::string dir = tmp && tmp[0] ? tmp : "/tmp";
+  const char *what = nullptr;
+  SpillFile none;
+  CHECK(!none.reset(dir + "/no_such_directory_of_the_check", &what) && !strcmp(what, "make") && errno == ENOENT && none.fd < 0);
+  SpillFile f;
+  CHECK(f.reset(dir, &what) && f.fd >= 0);
+  f.piece = 7;  // pieces of 7 bytes: 20 bytes go in three calls
+  std::unique_ptr<uint8_t[]> out(new uint8_t[20]), back(new uint8_t[20]), part(new uint8_t[9]);
+  for (int i = 0; i < 20; i++) out[i] = (uint8_t)(100 + i);
+  CHECK(f.transfer(true, out.get(), 20, 3) && lseek(f.fd, 0, SEEK_END) == 23);
+  CHECK(f.transfer(false, back.get(), 20, 3) && !memcmp(back.get(), out.get(), 20));
+  CHECK(f.transfer(false, part.get(), 9, 3 + 6) && !memcmp(part.get(), out.get() + 6, 9));  // (across the boundary between two pieces)
+  CHECK(f.transfer(false, part.get(), 0, 1000));                                            // nothing asked, nothing read
+  errno = 0;
+  CHECK(!f.transfer(false, back.get(), 20, 4) && errno == EIO);  // one byte past the end
+  const int fd = f.fd;
+  CHECK(f.reset(dir, &what) && f.fd == fd && lseek(f.fd, 0, SEEK_END) == 0);  // the next pass: the same file, empty
+  errno = 0;
+  CHECK(!f.transfer(false, back.get(), 1, 0) && errno == EIO);
+  CHECK(f.transfer(true, out.get(), 5, 0) && f.transfer(false, back.get(), 5, 0) && !memcmp(back.get(), out.get(), 5));
+}
+
 int main() {
   header_round_trip();
   header_errors();
@@ -160,6 +187,7 @@ int main() {
   table_case(2, 65536, 40, true);
   table_case(1, 1, 0, false);
   table_refuses();
+  spill_file();
   puts("orderstream_check: ok");
   return 0;
 }
