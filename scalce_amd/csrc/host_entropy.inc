@@ -86,8 +86,8 @@ static int ac_prepare(AcJob &j, hipStream_t s, bool framed_output = true, bool f
 //   clamp(ceil(blocks / CUs), 8, 64), the others 32.
 //
 //   symbols per round (64 only): rows of up to 48 lanes 32, or SCALCE_AC_ROUND (16 | 32) if set; wider rows 16 (their arrays
-//   do not fit into the LDS at 32).  ac_launch runs rows of up to 48 lanes as <true, 1, 48, 3, 32> or <true, 1, 48, 5, 16> --
-//   either way the gather wave is 64 symbols ahead of the chain -- and wider ones as <true, 1, 64, 5, 16>.
+//   do not fit into the LDS at 32).  ac_launch runs rows of up to 48 lanes as <48, 3, 32> or <48, 5, 16> --
+//   either way the gather wave is 64 symbols ahead of the chain -- and wider ones as <64, 5, 16>.
 //
 // One block per workgroup has the lowest latency of a block; four take 0.57 x the SIMD time per block at 1.2 x the
 // latency.  Paired reads: both mates' streams in ONE launch instead of two launches of the one-block kernel behind each
@@ -116,7 +116,7 @@ static int ac_blocks_override() {
 // workgroup's blocks go through ONE CU's vector memory pipeline (1024 scattered 16-byte reads per 0.75 us round at 64), and
 // beside another shard's streaming front stages -- when an L2 miss takes three times as long -- that pipeline, not the coder,
 // set the pace of a launch: 908 ms beside the ingest stage and 1299 ms beside the order stage at 64 blocks per workgroup
-// against 575 / 694 ms at 32 and 560 / 559 ms at 16 (543 ms alone; tools/coder_beside.py).  Fewer blocks per workgroup
+// against 575 / 694 ms at 32 and 560 / 559 ms at 16 (543 ms alone; DESIGN_HISTORY.md).  Fewer blocks per workgroup
 // are more CUs held per launch, CUs the front stages of the next shards do not get: in round 3's mix 48 was the best
 // trade (ms per shard at 32 / 40 / 48 / 56 / 64 blocks: 107.0 / 106.6 / 102.4 / 108.0 / 115.5; DESIGN.md section 7).
 // Round 4 (twelve slots, block buffers of their own): 79.9 / 80.0 / 81.1 / 81.7 / 82.2 / 85.6 ms per shard at 32 / 36 / 40 /
@@ -271,9 +271,9 @@ static int ac_launch(AcJob *jobs, int njobs, AcLaunchKind kind, hipStream_t s, h
       //  CU-seconds and 35 % more latency per launch: 98 against 75 ms per shard with fifteen slots, round 5; waves on shared CUs at
       //  raised priority: +5 %, round 3.  Both removed.)
       lead->ac_round_launched = shape.round;  // (scalce_batch_coder_round: tests)
-      if (a.lanes_used <= 48 && shape.round == 32) LAUNCH((ac_encode_lanes_k<true, 1, 48, 3, 32>), cdiv(total, a.lanes_used), 256, 0, s, a);
-      else if (a.lanes_used <= 48) LAUNCH((ac_encode_lanes_k<true, 1, 48, 5, 16>), cdiv(total, a.lanes_used), 256, 0, s, a);  // (rows of 48: LDS for a longer staging ring)
-      else LAUNCH((ac_encode_lanes_k<true, 1, 64, 5, 16>), cdiv(total, a.lanes_used), 256, 0, s, a);
+      if (a.lanes_used <= 48 && shape.round == 32) LAUNCH((ac_encode_lanes_k<48, 3, 32>), cdiv(total, a.lanes_used), 256, 0, s, a);
+      else if (a.lanes_used <= 48) LAUNCH((ac_encode_lanes_k<48, 5, 16>), cdiv(total, a.lanes_used), 256, 0, s, a);  // (rows of 48: LDS for a longer staging ring)
+      else LAUNCH((ac_encode_lanes_k<64, 5, 16>), cdiv(total, a.lanes_used), 256, 0, s, a);
     } else if (shape.blocks_per_wg == 8) {
       if (general) LAUNCH((ac_encode_rows_k<true, 8>), cdiv(total, 8), 320, 0, s, a);
       else LAUNCH((ac_encode_rows_k<false, 8>), cdiv(total, 8), 320, 0, s, a);

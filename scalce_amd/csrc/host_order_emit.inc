@@ -70,7 +70,7 @@ extern "C" int scalce_batch_order(scalce_batch *b, void *stream) {
   // phase 1 on (key, read) pairs when bucket | chunk | 32 prefix bits fit 64 bits (always, short of a million cores
   // together with more than 4096 chunks): every pass then reads and writes sequentially.  The index-only passes below
   // gather a digit through the index in every pass: 8 GB of sector fetches per pass at 50 M reads, and the scattered
-  // accesses are what slows a coder launch running beside the order stage most (tools/coder_beside.py).
+  // accesses are what slows a coder launch running beside the order stage most (DESIGN_HISTORY.md).
   const bool by_pairs = two_phase && PREFIX_BITS + cbits + bits <= 64;
   u64 *sorted_keys = nullptr;
   const u32 end_bits = (16 + PREFIX_BITS + cbits + bits <= 64) ? 16u : 0u;

@@ -108,7 +108,8 @@ struct AcEncArgs {
   u32 chain_prio;      // s_setprio of the chain waves (ac_encode_rows_k)
   u32 helper_prio;     // s_setprio of the helper waves (ac_encode_rows_k)
   u32 lanes_used;      // ac_encode_lanes_k: blocks per workgroup (0 = 64)
-  u32 pairing;         // ac_encode_lanes_k with two sets: which roles share a SIMD (experiments)
+  u32 pairing;         // read by no kernel any more (the two-set experiment of ac_encode_lanes_k, DESIGN_HISTORY.md section 0b); it
+                       // and the two priorities are constants (ac_launch), kept because ac_encode_rows_k measured slower without them
   u32 test_poison;     // test hook: every test_poison-th super-round pretends a step hit the full-range exit (0 = off)
   u32 inplace_shift;   // test hook (SCALCE_AC_INPLACE_TEST): blocks coded in place may only use 2^-shift of what they have consumed
 };
@@ -1345,8 +1346,8 @@ __global__ __launch_bounds__(256) void ac_dec_rows_k(const uint4 *tab, u32 smin,
 
 
 
-// ---- decoder, the loop written for the scalar unit (round 4): ac_decode_lean_k in ~45 instructions per symbol --------
-// ac_decode_lean_k's loop is ~80 instructions as the compiler emits it (230 ns per symbol: a lone wavefront issues one
+// ---- decoder, the loop written for the scalar unit (round 4): ac_decode_tight_k, ~45 instructions per symbol --------
+// The loop of its predecessor ac_decode_lean_k (gone from the tree: DESIGN_HISTORY.md) is ~80 instructions as the compiler emits it (230 ns per symbol: a lone wavefront issues one
 // instruction in four to five cycles, and the chain of a block is nothing but issue slots): a dozen s_cselect / s_cmp to
 // materialise conditions, renorm_count on the vector unit and back (v_mov, v_bfe, s_nop, v_readfirstlane), two scalar
 // multiplications for the address of the next row, v_cmp + v_cndmask for the output lane, eleven register moves where the

@@ -115,8 +115,8 @@ __device__ __forceinline__ void acl_step_plain(u32 &lo, u32 &M, const uint4 g, u
 // holds it -- 128 words for rounds of 32 (97).  Rounds of 16 keep their 64 words: a step drops fewer than 32 bits while
 // every symbol keeps an interval of two values (the host's condition for this kernel), so two rounds of 16 complete at
 // most 31 words, 31 + 31 + 2.  Do not shrink either.
-template <int LW, int SETS, int STEPS> struct AclRing { static constexpr int WORDS = STEPS <= 16 ? 64 : 128; };
-template <int LW, int STEPS>
+template <int STEPS> constexpr int ACL_RING_WORDS = STEPS <= 16 ? 64 : 128;
+template <int STEPS>
 struct AclSink {
   SCALCE_GLOBAL u32 *dst;
   u32 wcap;      // words the block may write
@@ -228,15 +228,15 @@ struct AclSink {
   }
 };
 
-// LW = lanes (blocks) of a set of four waves, SLOTS = operand ring: the gather wave runs SLOTS - 1 rounds ahead of the chain
+// LW = lanes (blocks) of a workgroup of four waves, SLOTS = operand ring: the gather wave runs SLOTS - 1 rounds ahead of the chain
 // STEPS = symbols per block and round.  LW = 48, SLOTS = 3, STEPS = 32: ops 73 728 + rec 24 576 + fifo 24 576 + ring (128 words)
 // 24 576 + pub / final_lo 576 = 148 032 bytes of the CU's 160 KiB; a fourth slot or rows of 64 lanes do not fit at 32.
-template <int LW, int SLOTS, int STEPS, int RINGW>
+template <int LW, int SLOTS, int STEPS>
 struct AclShared {
   uint4 ops[SLOTS][STEPS][LW];          // gather -> chain: operands of a round (slot = round % SLOTS), written by LDS-direct loads
   uint4 rec[2][STEPS / 2][LW];          // chain -> sink: (Q, B) of two steps of a round per entry
   uint4 fifo[2][STEPS / 2][LW];         // sink -> writer: (val, wq) of two steps per entry (AclSink::step)
-  u32 stage[RINGW][LW];                 // writer: coded words on their way out -- word k of the block in slot (k + 1) & (WORDS - 1)
+  u32 stage[ACL_RING_WORDS<STEPS>][LW]; // writer: coded words on their way out -- word k of the block in slot (k + 1) & (WORDS - 1)
   u32 pub[2][LW];                       // sink -> writer: words below this index are final
   u32 final_lo[LW];
 };
@@ -260,28 +260,14 @@ __device__ __forceinline__ void acl_wait_vm() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
-// SETS = 1: one set of four waves per workgroup, a wave per SIMD (round 3).  SETS = 2 (round 4): TWO sets in a workgroup of
-// eight waves over 2 x LW blocks, two waves per SIMD -- a chain or sink wave spends half of a step waiting for its DS
-// instructions, slots that a light wave (gather, writer) of the OTHER set takes: wave w of a workgroup
-// goes to SIMD w % 4, so
-//     SIMD 0: chain A + gather B    SIMD 1: chain B + gather A    SIMD 2: sink A + writer B    SIMD 3: sink B + writer A
-// A CU then codes 2 x LW blocks at (nearly) the pace of LW.  Each wave claims 256 registers: two per SIMD, nothing else.
-// LDS holds both sets (LW = 48, SLOTS = 3: 2 x 73 KB).  One barrier per round for all eight waves.
-template <bool EXCLUSIVE, int SETS, int LW, int SLOTS, int STEPS>
-__global__ __launch_bounds__(256 * SETS) void ac_encode_lanes_k(AcEncArgs a) {
-  static_assert(SLOTS >= 3 && SLOTS <= 9 && LW <= 64 && (SETS == 1 || SETS == 2) && (STEPS == 16 || STEPS == 32), "");
-  using Shared = AclShared<LW, SLOTS, STEPS, AclRing<LW, SETS, STEPS>::WORDS>;
-  static_assert(sizeof(Shared) * SETS <= 160 * 1024, "the workgroup's arrays must fit into the LDS of a CU");
-  __shared__ Shared shs[SETS];
+template <int LW, int SLOTS, int STEPS>
+__global__ __launch_bounds__(256) void ac_encode_lanes_k(AcEncArgs a) {
+  static_assert(SLOTS >= 3 && SLOTS <= 9 && LW <= 64 && (STEPS == 16 || STEPS == 32), "");
+  using Shared = AclShared<LW, SLOTS, STEPS>;
+  static_assert(sizeof(Shared) <= 160 * 1024, "the workgroup's arrays must fit into the LDS of a CU");
+  __shared__ Shared sh;
   const int lane = lane_id();
-  const int w = wave_id();
-  // SETS == 1: 0 chain, 1 gather, 2 sink, 3 writer: the four SIMDs of the CU.  SETS == 2: see above.
-  // (a.pairing, experiments: 1 = chain + writer / sink + gather, 2 = chain + sink / gather + writer on a SIMD)
-  const u32 rtab = a.pairing == 1 ? 0x11332200u : a.pairing == 2 ? 0x33221100u : 0x33112200u;  // role of wave w: nibble w
-  const u32 stab = a.pairing == 1 ? 0x01011010u : a.pairing == 2 ? 0x01011010u : 0x01011010u;  // set of wave w
-  const int role = SETS == 1 ? w : (int)((rtab >> (4 * w)) & 15u);
-  const int set = SETS == 1 ? 0 : (int)((stab >> (4 * w)) & 15u);
-  Shared &sh = shs[set];
+  const int role = wave_id();  // 0 chain, 1 gather, 2 sink, 3 writer: the four SIMDs of the CU
   // Workgroups are dealt to the 8 XCDs in turn (b and b + 8 share one: MI355X_MICROARCH.md, Workgroup dispatch), and
   // every XCD has an L2 of its own.  A launch holds the blocks of several streams back to back, each stream with its own
   // 4 MB table: the workgroups of an XCD take CONSECUTIVE groups of blocks, so that an L2 serves one or two tables
@@ -289,44 +275,33 @@ __global__ __launch_bounds__(256 * SETS) void ac_encode_lanes_k(AcEncArgs a) {
   // only: any placement gives the same bytes.
   const u32 nwg = gridDim.x, xq = nwg >> 3, xr = nwg & 7u, xcd = blockIdx.x & 7u;
   const u32 wg = (xcd < xr ? xcd * (xq + 1u) : xr * (xq + 1u) + (xcd - xr) * xq) + (blockIdx.x >> 3);
-  const u32 bpw = a.lanes_used && a.lanes_used < (u32)LW ? a.lanes_used : (u32)LW;  // blocks per set (lanes in use)
-  const u32 blk = (wg * SETS + (u32)set) * bpw + (u32)lane;
+  const u32 bpw = a.lanes_used && a.lanes_used < (u32)LW ? a.lanes_used : (u32)LW;  // blocks per workgroup (lanes in use)
+  const u32 blk = wg * bpw + (u32)lane;
   const bool have = blk < a.nblocks && (u32)lane < bpw;
   const SCALCE_GLOBAL AcBlockDesc *dp = (const SCALCE_GLOBAL AcBlockDesc *)a.desc + (have ? blk : 0u);
   const u32 n = have ? dp->n : 0u;
   const u32 nr = (n + STEPS - 1) / STEPS;  // rounds of this lane's block
   u32 nr_wg = nr;                                    // rounds of the workgroup = those of its longest block
-  if (SETS == 2) {                                   // (the other set's blocks as well: one barrier serves both)
-    const u32 oblk = (wg * SETS + (u32)(set ^ 1)) * bpw + (u32)lane;
-    const u32 on = oblk < a.nblocks && (u32)lane < bpw ? ((const SCALCE_GLOBAL AcBlockDesc *)a.desc + oblk)->n : 0u;
-    const u32 onr = (on + STEPS - 1) / STEPS;
-    nr_wg = onr > nr_wg ? onr : nr_wg;
-  }
 #pragma unroll
   for (int d = 32; d; d >>= 1) { const u32 o = __shfl_xor(nr_wg, d, 64); nr_wg = o > nr_wg ? o : nr_wg; }
   nr_wg = __builtin_amdgcn_readfirstlane(nr_wg);
   if (!nr_wg) return;
   // Front stages of other shards run beside this kernel.  Their waves on a coder wave's SIMD take issue slots from it
   // (every one of the four waves is on the round's critical path, the one-instruction-per-four-cycles kind), and their
-  // memory traffic queues in front of the gather wave's table rows in the CU's own memory pipeline.  EXCLUSIVE makes each
-  // coder wave claim its SIMD's whole register file (256 VGPRs + 256 AGPRs: an empty asm statement that names the last
-  // of each; half of it with two sets), so that the dispatcher places nothing else on the CU; otherwise all only run at
-  // raised priority.
-  if (EXCLUSIVE) {
-    if (SETS == 1) asm volatile("" ::: "v255", "a255");
-    else asm volatile("" ::: "v255");
-  }
-  if (SETS == 2 && (role & 1)) {  // the light waves take what the chain / sink on their SIMD leaves
-    if (a.helper_prio == 0) __builtin_amdgcn_s_setprio(0);
-    else if (a.helper_prio == 1) __builtin_amdgcn_s_setprio(1);
-    else if (a.helper_prio == 3) __builtin_amdgcn_s_setprio(3);
-    else __builtin_amdgcn_s_setprio(2);
-  } else __builtin_amdgcn_s_setprio(3);
-  // lanes beyond LW (SETS == 2) hold no block and must not touch the arrays, whose rows are LW wide
+  // memory traffic queues in front of the gather wave's table rows in the CU's own memory pipeline.  So each coder wave
+  // claims its SIMD's whole register file (256 VGPRs + 256 AGPRs: an empty asm statement that names the last of each),
+  // and the dispatcher places nothing else on the CU.
+  asm volatile("" ::: "v255", "a255");
+  __builtin_amdgcn_s_setprio(3);
+  // lanes beyond LW hold no block and must not touch the arrays, whose rows are LW wide
   const bool inrow = LW == 64 || lane < LW;
 
+  // Every wave passes the same nr_wg + 3 barriers: one before round 0, one at the end of every round, two at the end
+  // (the sink's last round, the writer's last words).
   if (role == 1) {
     // ================= gather: table rows straight into LDS, SLOTS - 1 rounds ahead =================
+    // Writes ops[k % SLOTS] for round k (LDS-direct loads), reads no array.  The barrier of iteration i says that round
+    // i + 1's operands have landed.
     constexpr int AHEAD = SLOTS - 1;
     const SCALCE_GLOBAL u8 *sp = (const SCALCE_GLOBAL u8 *)dp->sym;
     const SCALCE_GLOBAL u64 *tab = (const SCALCE_GLOBAL u64 *)dp->tab;  // compact: [6400][81] bounds (ac_table_k)
@@ -420,6 +395,8 @@ __global__ __launch_bounds__(256 * SETS) void ac_encode_lanes_k(AcEncArgs a) {
     }
   } else if (role == 0) {
     // ================= chain: one coder state per lane =================
+    // Round r: reads ops[r % SLOTS]; writes rec[r & 1] (again where the general step redoes the round) and, in the
+    // block's last round, final_lo.
     u32 ones, zero;
     asm("v_mov_b32 %0, -1" : "=v"(ones));
     asm("v_mov_b32 %0, 0" : "=v"(zero));
@@ -481,8 +458,10 @@ __global__ __launch_bounds__(256 * SETS) void ac_encode_lanes_k(AcEncArgs a) {
     }
   } else if (role == 2) {
     // ================= sink: one bit accumulator per lane, one round behind the chain =================
+    // Iteration i takes round i - 1: reads rec[(i - 1) & 1], writes fifo[(i - 1) & 1] and pub[i & 1]; the last round
+    // follows the loop, and final_lo is read behind the last barrier.
     if (inrow) {
-      AclSink<LW, STEPS> sk;
+      AclSink<STEPS> sk;
       {
         const SCALCE_GLOBAL u8 *sp = (const SCALCE_GLOBAL u8 *)dp->sym;
         const u32 s0 = n ? (u32)sp[0] : 0u, s1 = n > 1 ? (u32)sp[1] : 0u;
@@ -537,7 +516,9 @@ __global__ __launch_bounds__(256 * SETS) void ac_encode_lanes_k(AcEncArgs a) {
     }
   } else {
     // ================= writer: final words out of the staging ring =================
-    constexpr u32 RING = AclRing<LW, SETS, STEPS>::WORDS;
+    // Iteration i: reads fifo[i & 1] (round i - 2) and pub[(i - 1) & 1]; stage is this wave's alone.  All 64 lanes pass
+    // every barrier, in a row of 48 as well: a store pairs the lines of two blocks.
+    constexpr u32 RING = ACL_RING_WORDS<STEPS>;
     SCALCE_GLOBAL u32 *dst = (SCALCE_GLOBAL u32 *)dp->dst;
     const u32 wcap = dp->cap / 4;
     u32 wo = 0;  // words of this lane's block in global memory (multiple of 32 until the end)

@@ -764,9 +764,8 @@ def test_coder_long_underflow_runs_and_carries(blocks_per_wave, ctx, monkeypatch
 
 @pytest.mark.gpu
 def test_lanes_coder_shapes_write_the_same_bytes(ctx, monkeypatch):
-    """ac_encode_lanes_k in every shape of its workgroup -- one set of four waves over rows of 48 or 64 lanes, two sets over
-    rows of 48, 40 and 32 (eight waves, two per SIMD; kernels_acl.hpp) -- and with every seventh round forced through the
-    redo path: 130 blocks (more than one workgroup in every shape, a last workgroup that is partly empty, a last block that
+    """ac_encode_lanes_k in every shape of its workgroup -- four waves over rows of 48 or 64 lanes (kernels_acl.hpp) -- and
+    with every seventh round forced through the redo path: 130 blocks (more than one workgroup in every shape, a last workgroup that is partly empty, a last block that
     is short), crafted carries at the start of two of them.  All shapes against the first, and the first block of the
     stream -- which holds the crafted symbols -- against the oracle's bytes."""
     import hashlib
@@ -791,8 +790,7 @@ def test_lanes_coder_shapes_write_the_same_bytes(ctx, monkeypatch):
     want0 = O.AcStat(table).encode_stream(first)
     ref = None
     # (8 .. 28: what a launch that has the chip to itself may pick -- as few blocks per workgroup as all CUs allow)
-    for sets, lanes, poison in (("1", "48", "0"), ("1", "64", "0"), ("1", "32", "0"), ("1", "32", "7"), ("1", "40", "7"), ("1", "8", "0"),
-                                ("1", "11", "7"), ("1", "28", "0")):
+    for lanes, poison in (("48", "0"), ("64", "0"), ("32", "0"), ("32", "7"), ("40", "7"), ("8", "0"), ("11", "7"), ("28", "0")):
         monkeypatch.setenv("SCALCE_AC_LANES_USED", lanes)
         monkeypatch.setenv("SCALCE_AC_TEST_POISON", poison)
         b = host.Batch(ctx, 100, max_reads=1024, max_text=1 << 20)
@@ -803,7 +801,7 @@ def test_lanes_coder_shapes_write_the_same_bytes(ctx, monkeypatch):
             assert (enc[:len(want0)] == want0).all(), "the first block differs from the oracle's"
             ref = (len(enc), hashlib.sha256(enc.tobytes()).hexdigest())
         else:
-            assert (len(enc), hashlib.sha256(enc.tobytes()).hexdigest()) == ref, f"sets {sets}, rows of {lanes} lanes: other bytes"
+            assert (len(enc), hashlib.sha256(enc.tobytes()).hexdigest()) == ref, f"rows of {lanes} lanes: other bytes"
         b.close()
 
 
