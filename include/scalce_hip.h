@@ -171,6 +171,7 @@ int scalce_batch_reset(scalce_batch *b);
 #define SCALCE_STREAM_LEAN 1
 #define SCALCE_STREAM_DEFER_ENTROPY 2
 #define SCALCE_STREAM_KEEP_ORDER 4  /* scalce_batch_set_keep_order on the run's batch: SCALCE_OUT_PERM outlives the lean releases */
+#define SCALCE_STREAM_KEEP_COMMENTS 8  /* scalce_batch_set_keep_comments on the run's batch: SCALCE_OUT_COMMENTS holds what follows the names */
 typedef int64_t (*scalce_read_fn)(void *user, void *dst, uint64_t cap);
 typedef struct {
   double total_s, read_wait_s, h2d_wait_s, front_s, order_s, emit_s, entropy_s;
@@ -186,6 +187,21 @@ void scalce_batch_set_lean(scalce_batch *b, int lean);
 /* on = 1: the permutation is an output of the run (the order stream of --keep-order): SCALCE_OUT_PERM stays valid behind
  * scalce_batch_emit and scalce_batch_finish whether the batch is lean or not.  Nothing else changes. */
 int scalce_batch_set_keep_order(scalce_batch *b, int on);
+/* on = 1: what follows the name on every record's header line is an output of the run (the comment stream of --keep-comments).
+ * The name slicer ends a name at the first space (output_name, names.cpp:55-57); a record's ENTRY is the rest of the line, from
+ * that space inclusive to the newline exclusive -- empty for a line without a space, " " for "@name ".  Every piece's entries go,
+ * each with a newline behind it, into a byte store per mate in input order (mate 2's header line has an entry of its own,
+ * although its name is not stored; interleaved text: record 2k + m goes to mate m's store), and the emit stage gathers them
+ * through the permutation: SCALCE_OUT_COMMENTS.  Every other output is what it is without the option, byte for byte.  An entry
+ * longer than 65535 bytes is SCALCE_ERR_FORMAT from the ingest itself ("(ERROR) record <n>: what follows the name is longer than
+ * 65535 bytes").  To be called before the first ingest or append of a run.  SCALCE_ERR_ARG for a batch with use_names == 0;
+ * one GPU only: scalce_sharded_compress, scalce_batch_rewindow, scalce_batch_text_offset and scalce_pipeline_create refuse such
+ * batches (SCALCE_ERR_ARG).  Off (the default): no kernel of it is launched and no buffer of it allocated. */
+int scalce_batch_set_keep_comments(scalce_batch *b, int on);
+/* *nbytes = the size of SCALCE_OUT_COMMENTS of `mate` (entries and their newlines), *longest = its longest entry in bytes without
+ * the newline (the C of the .scalcec header); either may be NULL.  Valid behind the ingest of the run's last piece; zero without
+ * the option. */
+int scalce_batch_comments_info(const scalce_batch *b, int mate, uint64_t *nbytes, uint32_t *longest);
 /* Row layout of the batch.  A single-end batch with names keeps ONE row per read -- q' | name cell | packed bases, what the
  * reference keeps per read in its bucket blob (reads.h:52-58, compress.cpp:675-706) -- so that the emit stage reaches
  * everything it reorders through one random access.  on = 0 (before anything is ingested) goes back to separate arrays whose
@@ -344,8 +360,11 @@ enum {
   SCALCE_OUT_BUCKET_NAME_BYTES = 11, /* (buckets+1) x u64: bytes of each bucket's records in SCALCE_OUT_NAMES (after emit) */
   SCALCE_OUT_LENGTHS = 12,  /* variable-length runs: N x u16, read_len - length of the k-th emitted record of mate m (mate 2 in
                                mate 1's order, like its reads); valid behind scalce_batch_order; empty for other runs */
-  SCALCE_OUT_NAMECELLS = 13 /* for tests: N x 16 bytes, input order: [stored length][the name's first 15 characters, zero behind a
+  SCALCE_OUT_NAMECELLS = 13,/* for tests: N x 16 bytes, input order: [stored length][the name's first 15 characters, zero behind a
                                shorter name] as the ingest left them; empty with names off, gone once a lean batch has emitted */
+  SCALCE_OUT_COMMENTS = 14  /* scalce_batch_set_keep_comments: what follows the name of the k-th emitted record of mate m, each entry
+                               followed by a newline (mate 2 in mate 1's order); valid behind scalce_batch_emit, lean or not; empty
+                               without the option */
 };
 int scalce_batch_output(const scalce_batch *b, int which, int mate, const void **d_ptr, uint64_t *nbytes);
 /* Framing on the way out (replaces the copy loop of ac_write, arithmetic.cpp:318-363: the reference frames each coded
@@ -485,6 +504,31 @@ int scalce_fastq_strip_window(scalce_ctx *ctx, int read_len, uint64_t nrecords, 
                               const uint8_t *d_entries, int entry_width, uint8_t *d_out, uint64_t *d_out_offsets, void *d_scan_ws,
                               void *stream);
 
+/* Archives made with --keep-comments: the entries of the comment stream go back between each name and its newline.  d_text /
+ * d_record_offsets are what scalce_fastq_records_window wrote (one mate's records, not interleaved; nrecords + 1 offsets; records
+ * of read_len bases, has_qualities = 0 for two-line records: the header line's newline lies 2 read_len + 5, or read_len + 2,
+ * bytes in front of the record's end), d_entries the window's entry_bytes bytes of the stream as the .scalcec file holds them
+ * behind its header: nrecords entries, each followed by a newline.  Where each entry lies is found on the device by a newline
+ * index.  d_out receives the text (room for the window's text plus entry_bytes), d_out_offsets (nrecords + 1) where each record
+ * begins in it and, last, its size.  *d_bad is set when the entries do not hold exactly nrecords newlines, the last one at their
+ * end (records whose entry is missing then get none).  To be run BEFORE scalce_fastq_strip_window, which measures from the
+ * record's end.  d_text, d_entries and d_out 16-byte aligned; d_ws: device scratch of scalce_fastq_comment_ws_bytes(nrecords,
+ * entry_bytes) bytes.  Enqueued on `stream`; allocates nothing, waits for nothing. */
+uint64_t scalce_fastq_comment_ws_bytes(uint64_t nrecords, uint64_t entry_bytes);
+int scalce_fastq_comment_window(scalce_ctx *ctx, int read_len, int has_qualities, uint64_t nrecords, const uint8_t *d_text,
+                                const uint64_t *d_record_offsets, const uint8_t *d_entries, uint64_t entry_bytes, uint8_t *d_out,
+                                uint64_t *d_out_offsets, uint32_t *d_bad, void *d_ws, void *stream);
+/* The same for an interleaved window (scalce_fastq_records_window with interleave): npairs pairs, mate 1 then mate 2 of each, of
+ * read_len[0] / read_len[1] bases; d_pair_offsets (npairs + 1) where each pair begins, d_name_off2 mate 2's name offsets as
+ * scalce_fastq_records_window took them (npairs + 1: a name record is a length byte and the name, which is how long mate 2's
+ * header line is); d_entries: 2 npairs entries, mate 1's then mate 2's of each pair.  d_out_pair_offsets (npairs + 1): where each
+ * pair begins in d_out.  d_ws: scalce_fastq_comment_pairs_ws_bytes(npairs, entry_bytes) bytes. */
+uint64_t scalce_fastq_comment_pairs_ws_bytes(uint64_t npairs, uint64_t entry_bytes);
+int scalce_fastq_comment_window_pairs(scalce_ctx *ctx, const int read_len[2], int has_qualities, uint64_t npairs, const uint8_t *d_text,
+                                      const uint64_t *d_pair_offsets, const uint64_t *d_name_off2, const uint8_t *d_entries,
+                                      uint64_t entry_bytes, uint8_t *d_out, uint64_t *d_out_pair_offsets, uint32_t *d_bad, void *d_ws,
+                                      void *stream);
+
 /* The read length of a variable-length run and its quality histogram, from the text read ahead for the quality sample -- no
  * device call.  The first `sample` records r with r % stride == first are taken (sample_stats' walk; stride 1, first 0 for
  * a text of one mate): *read_len = the longest sequence line among them, or max_length when that is > 0 (--max-length);
@@ -537,7 +581,7 @@ typedef struct {
   double total_s, setup_s, read_wait_s, decode_s, records_s, write_wait_s, write_s;
                                /* read_wait: in rd; decode / records: device time of the kernels; write_wait: the session
                                   waiting for a window buffer that wr still holds; write: inside wr */
-  int32_t error_mate, error_stream;  /* on failure: which stream of which mate (0 r, 1 n, 2 q, 3 l), or -1 */
+  int32_t error_mate, error_stream;  /* on failure: which stream of which mate (0 r, 1 n, 2 q, 3 l, 4 o, 5 c), or -1 */
   int32_t error_wants_file;    /* the message in errbuf is a predicate: put the stream's file name in front of it */
   uint64_t decode_batches[2];  /* per mate: decoder batches enqueued (runs of whole frames, one scalce_ac_decoder_launch each) */
 } scalce_unpack_stats;
@@ -647,6 +691,30 @@ typedef struct {
 int scalce_stream_decompress_restore(scalce_ctx *ctx, const scalce_unpack_params *p, const scalce_restore_params *rp,
                                      scalce_read_fn rd[2][3], void *user[2][3], scalce_write_fn wr, void *wr_user,
                                      scalce_unpack_stats *stats, scalce_restore_stats *restore_stats, char *errbuf, size_t errcap);
+
+/* ---- what follows the names, back on the way out (archives made with --keep-comments; commentstream.hpp, kernels_comments.hpp) ---
+ * The comment stream (PREFIX_<m>.scalcec out of its container), one per mate: the 8 magic bytes, int32 0 (entry width 0: text
+ * entries), int32 C (the longest entry in bytes, without its terminator), int64 N, then N entries in archive order, each followed
+ * by a newline: SCALCE_OUT_COMMENTS.  com_rd[m] delivers mate m's, header included; both NULL: no comments.  Every record's entry
+ * is taken with its name and counts in the window's budget: a window holds at most window_text_bytes of text WITH its entries,
+ * and device and pinned memory follow the window (a record's bound grows by C), never C x records.  Each window's entries go
+ * back on the device (scalce_fastq_comment_window) before the pad goes (variable-length archives) and before the order restore
+ * groups the window.  A range passes over first_record entries by their newlines; the stream is always read.
+ * scalce_stream_decompress_comments covers the three shapes of decompression: range and rp NULL is scalce_stream_decompress,
+ * range set scalce_stream_decompress_range, rp set scalce_stream_decompress_restore (both: SCALCE_ERR_ARG); comments NULL is the
+ * existing call of that shape.  Every mate has its stream (else SCALCE_ERR_ARG); interleaved, both mates' entries of a window go
+ * into its one text (scalce_fastq_comment_window_pairs).  Not for an archive without stored names.  Errors besides theirs: "(ERROR) truncated comment stream" (it ends inside an entry or before the
+ * records do), "(ERROR) is not a scalce comment stream", "(ERROR) comment stream holds <n> entries, the archive <m> records",
+ * "(ERROR) comment stream: an entry is longer than its header says"; error_stream 5 names the comment stream. */
+typedef struct {
+  scalce_read_fn com_rd[2];
+  void *com_user[2];
+} scalce_unpack_comments;
+int scalce_stream_decompress_comments(scalce_ctx *ctx, const scalce_unpack_params *p, const scalce_unpack_comments *comments,
+                                      const scalce_unpack_range *range /* NULL: all */, const scalce_restore_params *rp /* NULL: archive order */,
+                                      scalce_read_fn rd[2][3], void *user[2][3], scalce_write_fn wr, void *wr_user,
+                                      scalce_unpack_stats *stats, scalce_unpack_range_stats *range_stats,
+                                      scalce_restore_stats *restore_stats, char *errbuf, size_t errcap);
 
 /* ---- runs sharded over several GPUs: one process per GPU, ONE archive -----------------------------------------
  * The reference has no distributed mode; what it carries across reads is what ranks exchange (see comm.cpp).  The

@@ -10,6 +10,7 @@
 #include <string>
 
 #include "../../include/scalce_hip.h"
+#include "commentstream.hpp"
 #include "lenstream.hpp"
 #include "stream_src.hpp"
 
@@ -32,9 +33,9 @@ __attribute__((format(printf, 6, 7))) inline int failure(Failure &f, int rc, int
   f.rc = rc; f.msg = b; f.mate = mate; f.stream = stream; f.wants_file = wants_file;
   return rc;
 }
-// a stream that ends, or fails, before what is asked of it (stream: 0 r, 1 n, 2 q, 3 l, 4 o)
+// a stream that ends, or fails, before what is asked of it (stream: 0 r, 1 n, 2 q, 3 l, 4 o, 5 c)
 inline const char *stream_name(int stream) {
-  return stream == 0 ? "read" : stream == 1 ? "name" : stream == 2 ? "quality" : stream == 3 ? "length" : "order";
+  return stream == 0 ? "read" : stream == 1 ? "name" : stream == 2 ? "quality" : stream == 3 ? "length" : stream == 5 ? "comment" : "order";
 }
 inline int read_error(Failure &f, int m, int stream) { return failure(f, SCALCE_ERR_FORMAT, m, stream, 0, "read error on the %s stream", stream_name(stream)); }
 inline int truncated(Failure &f, int m, int stream) { return failure(f, SCALCE_ERR_FORMAT, m, stream, 0, "(ERROR) truncated %s stream", stream_name(stream)); }
@@ -64,6 +65,11 @@ struct ArcMate {
   bool has_len = false;
   int l_width = 0;           // bytes per entry
   u64 l_delivered = 0, l_skipped = 0;
+  Src c;                     // the comment stream of an archive made with --keep-comments (scalce_unpack_comments), or not open
+  bool has_com = false;
+  u32 c_longest = 0;         // its header's C: the longest entry, without the newline
+  u64 c_total = 0, c_taken = 0;  // its header's N; entries taken or passed over so far
+  u64 c_delivered = 0, c_skipped = 0;
   int L = 0, no_ac = 0;
   int64_t phred = 0;
   bool q_empty = false;
@@ -82,6 +88,8 @@ struct ReadsDst {
 };
 // ... and a mate's names: the name records as they are, and where each begins (one entry more than there are names)
 struct NamesDst { u8 *bytes; u64 *off; u64 cap; };
+// ... and its entries of the comment stream, each with its newline, as the stream holds them
+struct CommentsDst { u8 *bytes; u64 cap; u64 nbytes = 0; };
 
 // The arithmetic of a range over the coded quality stream, without a device call: symbols [first * L, (first + n) * L) of a
 // stream of total_syms symbols in frames of SCALCE_AC_BLOCK.  first and n are clamped to the total_syms / L records the stream
@@ -293,8 +301,65 @@ struct Walk {
     }
     return src.bad ? read_error(f, m, 1) : SCALCE_OK;
   }
-  // names of up to `ncap` records (pairs) of the pass's mates into to[], as many as W bytes of text take; n = how many
-  int take_names(NamesDst to[2], u64 ncap, u64 W, u64 &n, u64 nb[2], Failure &f) {
+  // ---- the comment stream (commentstream.hpp): a fifth cursor of the mate ----------------------------------------------------
+  int comments_open(int m, scalce_read_fn rd, void *user, double *wait, Failure &f) {
+    ArcMate &x = *M[m];
+    x.c.open(rd, nullptr, user, wait, &x.c_delivered, &x.c_skipped);
+    const bool whole = x.c.need(COMMENT_HEADER_BYTES);
+    if (x.c.bad) return read_error(f, m, 5);
+    if (const char *why = comment_header_read(x.c.ptr(), whole ? COMMENT_HEADER_BYTES : 0, &x.c_longest, &x.c_total))
+      return failure(f, SCALCE_ERR_FORMAT, m, 5, 0, "(ERROR) %s", why);
+    x.c.skip(COMMENT_HEADER_BYTES);
+    x.has_com = true;
+    x.c_taken = 0;
+    return SCALCE_OK;
+  }
+  // the next entry where it lies in the look-ahead buffer: len = its bytes with the newline.  0: there it is; 1: the stream
+  // ends here, between two entries; else the failure -- it ends inside an entry, an entry outgrows the header's C, a read failed
+  int next_comment(int m, size_t &len, Failure &f) {
+    ArcMate &x = *M[m];
+    Src &c = x.c;
+    size_t seen = 0;
+    for (;;) {
+      const size_t have = c.avail();
+      if (have > seen) {
+        const void *nl = memchr(c.ptr() + seen, '\n', have - seen);
+        if (nl) {
+          len = (size_t)((const u8 *)nl - c.ptr()) + 1;
+          if (len - 1 > x.c_longest) return failure(f, SCALCE_ERR_FORMAT, m, 5, 0, "(ERROR) %s", comment_entry_too_long());
+          return 0;
+        }
+        seen = have;
+      }
+      if (seen > x.c_longest) return failure(f, SCALCE_ERR_FORMAT, m, 5, 0, "(ERROR) %s", comment_entry_too_long());
+      if (!c.need(seen + 1)) {
+        if (c.bad) return read_error(f, m, 5);
+        return seen ? truncated(f, m, 5) : 1;
+      }
+    }
+  }
+  // entries in front of a range: passed over on the host by their newlines (the stream is always read, as the names are)
+  int pass_comments(int m, u64 n, u64 &got, Failure &f) {
+    for (got = 0; got < n; got++) {
+      size_t len = 0;
+      const int e = next_comment(m, len, f);
+      if (e == 1) break;
+      if (e) return e;
+      M[m]->c.skip(len);
+      M[m]->c_taken++;
+    }
+    return SCALCE_OK;
+  }
+  int comment_count(int m, u64 entries, u64 records, Failure &f) const {
+    char b[200];
+    comment_count_message(b, sizeof b, entries, records);
+    return failure(f, SCALCE_ERR_FORMAT, m, 5, 0, "(ERROR) %s", b);
+  }
+
+  // names of up to `ncap` records (pairs) of the pass's mates into to[], as many as W bytes of text take; n = how many.
+  // com: each record's entry of the comment stream is taken in the same step and counts in the budget (two mates in one window:
+  // mate 1's entry, then mate 2's, pair by pair -- the order of the records in the interleaved text)
+  int take_names(NamesDst to[2], u64 ncap, u64 W, u64 &n, u64 nb[2], Failure &f, CommentsDst *com = nullptr) {
     u64 text = 0;
     nb[0] = nb[1] = 0;
     n = 0;
@@ -310,6 +375,13 @@ struct Walk {
         if (!src.need(1 + (size_t)len[i])) return truncated(f, m0 + i, 1);
         rec += len[i] + rec_budget(m0 + i);
       }
+      size_t clen[2] = {0, 0};  // the records' entries with their newlines
+      for (int i = 0; i < nmates && com && !ended; i++) {
+        const int e = next_comment(m0 + i, clen[i], f);
+        if (e == 1) return truncated(f, m0 + i, 5);
+        if (e) return e;
+        rec += clen[i] - 1;
+      }
       if (ended) {
         for (int i = 0; i < nmates; i++) if (M[m0 + i]->n.bad) return read_error(f, m0 + i, 1);
         if (!decides_count(m0, 1) || ended != nmates) return truncated(f, m0, 1);
@@ -318,7 +390,14 @@ struct Walk {
       if (n && text + rec > W) break;
       bool fits = true;
       for (int i = 0; i < nmates; i++) fits = fits && nb[i] + 1 + len[i] <= to[i].cap;
+      if (com) fits = fits && com->nbytes + clen[0] + clen[1] <= com->cap;
       if (!fits) break;
+      for (int i = 0; i < nmates && com; i++) {
+        memcpy(com->bytes + com->nbytes, M[m0 + i]->c.ptr(), clen[i]);
+        M[m0 + i]->c.skip(clen[i]);
+        M[m0 + i]->c_taken++;
+        com->nbytes += clen[i];
+      }
       for (int i = 0; i < nmates; i++) {
         Src &src = M[m0 + i]->n;
         to[i].off[n] = nb[i];

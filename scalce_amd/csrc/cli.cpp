@@ -31,6 +31,7 @@
 #include "cli_input.hpp"
 #include "cli_shares.hpp"
 #include "cli_sink.hpp"
+#include "cli_comments.hpp"
 
 #ifndef SCALCE_VERSION
 #define SCALCE_VERSION "2.8-mi355x"
@@ -51,6 +52,8 @@ struct Options {
   int max_length = 0;                     // --max-length NUM: L given, not taken from the sample (implies --variable-length)
   bool keep_order = false;                // --keep-order: the input index of every record of the archive, in PREFIX_1.scalceo
   bool archive_order = false;             // -d --archive-order: a .scalceo next to the archive is ignored
+  bool keep_comments = false;             // --keep-comments: what follows every record's name, in PREFIX_<m>.scalcec
+  bool no_comments = false;               // -d --no-comments: a .scalcec next to the archive is ignored
   bool temp_given = false;                // -t was given (the default of `temp` is the reference's)
   int gpus = 1;                           // --gpus N: one process per GPU, ONE archive (plain-text input, -c no)
   int container = 1;                      // 0 plain, 1 gzip (main.cpp:181-184 at -T 1)
@@ -82,6 +85,11 @@ static const char *HELP_TEXT =
     "                              OUTPUT_1.scalceo, every other file is the one the run without the option writes.  Decompression\n"
     "                              finds the .scalceo by itself and writes the records in the order they came in.  Not with --gpus\n"
     "      --archive-order         decompression: ignore the .scalceo, write the records in the archive's order\n"
+    "      --keep-comments         keep what follows the name on every record's header line (from the first space on: mate number,\n"
+    "                              barcode, length=...): it goes into OUTPUT_<m>.scalcec, every other file is the one the run\n"
+    "                              without the option writes.  Decompression finds the .scalcec by itself and puts the comments\n"
+    "                              back; the '+' line stays a bare '+'.  Not with -n, --gpus\n"
+    "      --no-comments           decompression: ignore the .scalcec, write the names alone\n"
     "  -p, --lossy-percentage INT  lossy quality transform, 0..100 (default 0)\n"
     "  -s, --sample-size INT       records sampled for the quality model (default 100000)\n"
     "  -B, --bucket-set-size NUM[M|G]  bucket storage that triggers a spill chunk (default 4G); order follows the reference\n"
@@ -112,6 +120,8 @@ static const char *HELP_TEXT =
 //   PREFIX_<m>.scalcel  --variable-length only (lenstream.hpp): magic, int32 entry width, int32 L, one entry L - length per record
 //   PREFIX_1.scalceo    --keep-order only (orderstream.hpp): magic, int32 4, int32 0, int64 N, N x u32: the input index of the
 //                       k-th record (pair) of the archive; one file for both mates
+//   PREFIX_<m>.scalcec  --keep-comments only (commentstream.hpp): magic, int32 0, int32 C (longest entry), int64 N, then what follows
+//                       the name of each record of the archive, from the first space on, each entry followed by a newline
 //   PREFIX_<m>.scalceq  magic, int64 Phred offset (mate 1's for both mates, compress.cpp:294,816-817); arithmetic coded:
 //                       the scaled table (QTABLE_WORDS x u32), the int64 symbol count and the coded blocks; -A: the q' rows
 static const uint8_t MAGIC[8] = {'s', 'c', 'a', 'l', 'c', 'e', '2', '2'};
@@ -340,6 +350,16 @@ struct MateFiles {
     fO.write(perm);
     fO.close();
   }
+  void write_comments(int m, Downloader &down, uint64_t N) const {  // --keep-comments: what follows each name, in archive order
+    OutFile fC;
+    fC.open(archive_path(o.out, m, 'c'), gz_container(o, 'c'));
+    uint64_t nbytes = 0;
+    uint32_t longest = 0;
+    SCOK(ctx, scalce_batch_comments_info(b, m, &nbytes, &longest));
+    comment_file_header(fC, longest, N);
+    down.to_file(ctx, b, SCALCE_OUT_COMMENTS, m, fC);
+    fC.close();
+  }
   void write_qualities(int m, Downloader &down, uint64_t N) const {  // once the coder is through; N: records of the run
     OutFile fQ;
     fQ.open(archive_path(o.out, m, 'q'), gz_container(o, 'q'));
@@ -403,7 +423,8 @@ static int do_compress(const Options &o, const std::vector<std::string> &files, 
   char emsg[512] = "";
   const double t1 = now();
   if (scalce_stream_compress(ctx, &p, MateSource::read_cb, &in.src[0], nsrc == 2 ? MateSource::read_cb : nullptr, nsrc == 2 ? &in.src[1] : nullptr,
-                             piece, hint, SCALCE_STREAM_LEAN | SCALCE_STREAM_DEFER_ENTROPY | (o.keep_order ? SCALCE_STREAM_KEEP_ORDER : 0), &b, &ss, emsg, sizeof emsg)) {
+                             piece, hint, SCALCE_STREAM_LEAN | SCALCE_STREAM_DEFER_ENTROPY | (o.keep_order ? SCALCE_STREAM_KEEP_ORDER : 0) |
+                                 (o.keep_comments ? SCALCE_STREAM_KEEP_COMMENTS : 0), &b, &ss, emsg, sizeof emsg)) {
     if (!in.src[0].error.empty()) fputs(in.src[0].error.c_str(), stderr);  // (-i: a file of odd record count; the stream only saw a read error)
     else fprintf(stderr, "%s\n", emsg[0] ? emsg : scalce_last_error(ctx));
     exit(1);
@@ -434,9 +455,11 @@ static int do_compress(const Options &o, const std::vector<std::string> &files, 
     w.write_reads_and_names(m, *downs[m]);
     if (o.varlen) w.write_lengths(m);
     if (o.keep_order && m == 0) w.write_order();
+    if (o.keep_comments) w.write_comments(m, *downs[m], N);
   });
-  // (an order stream left under this prefix by an earlier run does not belong to this archive)
+  // (an order stream left under this prefix by an earlier run does not belong to this archive, nor do comment streams)
   if (!o.keep_order) unlink(archive_path(o.out, 0, 'o').c_str());
+  if (!o.keep_comments) for_each_archive_file(o, "c", [](char, const std::string &fn) { unlink(fn.c_str()); });
   const double t2b = now();
   SCOK(ctx, scalce_batch_finish(b, s_ent));  // the coder is through: sizes of the coded streams, device error word
   const double t2c = now();
@@ -446,7 +469,8 @@ static int do_compress(const Options &o, const std::vector<std::string> &files, 
   });
   const double t2d = now();
   uint64_t new_size = 0;
-  for_each_archive_file(o, o.keep_order ? "rnqlo" : "rnql", [&](char, const std::string &fn) {
+  const std::string exts = std::string("rnql") + (o.keep_order ? "o" : "") + (o.keep_comments ? "c" : "");
+  for_each_archive_file(o, exts.c_str(), [&](char, const std::string &fn) {
     struct stat st;
     if (stat(fn.c_str(), &st) == 0) new_size += (uint64_t)st.st_size;
   });
@@ -456,9 +480,13 @@ static int do_compress(const Options &o, const std::vector<std::string> &files, 
   SCOK(ctx, scalce_batch_output(b, SCALCE_OUT_BUCKET_COUNTS, 0, &dc, &nc));
   uint64_t unbucketed = 0;
   if (nc >= 8) SCOK(ctx, scalce_memcpy_d2h(ctx, &unbucketed, (const uint8_t *)dc + nc - 8, 8));
+  uint64_t com_bytes[2] = {0, 0};
+  uint32_t com_longest[2] = {0, 0};
+  for (int m = 0; m < nm && o.keep_comments; m++) SCOK(ctx, scalce_batch_comments_info(b, m, &com_bytes[m], &com_longest[m]));
   scalce_batch_destroy(b);
   const double t3 = now();
   log_statistics(o, p, N, unbucketed);
+  for (int m = 0; m < nm && o.keep_comments; m++) comment_log(N, com_bytes[m], com_longest[m]);
   LOG("\tSpill chunks: %u, pieces streamed: %llu\n", st4[3], (unsigned long long)ss.rounds);
   LOG("\tTime elapsed: %.2f s (sample %.2f; stream %.2f = waiting for the reader %.2f + for uploads %.2f + ingest/count/tokenize %.2f; "
       "order %.2f, emit %.2f; reads+names down and written beside the coder %.2f, waiting for the coder %.2f, qualities down and written %.2f, device buffers released %.2f)\n",
@@ -832,6 +860,8 @@ struct Archive {
   std::string base[2];
   bool has_lens[2] = {false, false};
   bool has_order = false;  // a PREFIX_1.scalceo lies next to the .scalcen (and --archive-order does not set it aside)
+  bool has_comments = false;  // every mate has a PREFIX_<m>.scalcec next to its .scalcen (and neither --no-comments nor -n sets them aside)
+  ArchiveFile comments[2];
   ArchiveFile files[2][3], lens[2], order[2];  // (a mate pass reads the order stream from its start: one handle each)
   scalce_read_fn rd[2][3];
   void *user[2][3];
@@ -861,6 +891,10 @@ struct Archive {
     if (has_order && o.has_range)
       FAIL("--records counts in the archive's order and %s holds the input's: give --archive-order with --records\n", scalce_name(base[0], 'o').c_str());
     for (int m = 0; m < (o.interleave ? 1 : nm) && has_order; m++) order[m].open(scalce_name(base[0], 'o'));
+    // what follows the names: put back when every mate has its stream, names are printed and nothing sets the streams aside
+    has_comments = !o.no_comments && o.use_names;
+    for (int m = 0; m < nm && has_comments; m++) has_comments = comment_file_present(scalce_name(base[m], 'c'));
+    for (int m = 0; m < nm && has_comments; m++) comments[m].open(scalce_name(base[m], 'c'));
   }
 };
 // One path for every archive: scalce_stream_decompress moves it through the device in windows of whole records.  The read
@@ -879,6 +913,9 @@ static int do_decompress(const Options &o, const std::string &path, scalce_ctx *
   char err[1024] = "";
   std::string spill_dir;
   int rc;
+  scalce_unpack_comments cm;
+  memset(&cm, 0, sizeof cm);
+  for (int m = 0; m < nm && ar.has_comments; m++) { cm.com_rd[m] = ArchiveFile::read; cm.com_user[m] = &ar.comments[m]; }
   if (ar.has_order) {  // the input order back: two passes through a spill under -t, next to the output, or in $TMPDIR
     scalce_restore_params rp;
     memset(&rp, 0, sizeof rp);
@@ -895,11 +932,16 @@ static int do_decompress(const Options &o, const std::string &path, scalce_ctx *
     }
     rp.spill_dir = spill_dir.c_str();
     memset(&rs, 0, sizeof rs);
-    rc = scalce_stream_decompress_restore(ctx, &p, &rp, ar.rd, ar.user, TextSink::write, &sink, &st, &os, err, sizeof err);
-  } else
+    rc = ar.has_comments ? scalce_stream_decompress_comments(ctx, &p, &cm, nullptr, &rp, ar.rd, ar.user, TextSink::write, &sink, &st, nullptr, &os, err, sizeof err)
+                         : scalce_stream_decompress_restore(ctx, &p, &rp, ar.rd, ar.user, TextSink::write, &sink, &st, &os, err, sizeof err);
+  } else if (ar.has_comments)
+    rc = scalce_stream_decompress_comments(ctx, &p, &cm, &rg, nullptr, ar.rd, ar.user, TextSink::write, &sink, &st, &rs, nullptr, err, sizeof err);
+  else
     rc = scalce_stream_decompress_range(ctx, &p, &rg, ar.rd, ar.user, TextSink::write, &sink, &st, &rs, err, sizeof err);
   if (rc) {
     // (parts already written stay where they are)
+    if (st.error_stream == 5 && st.error_mate >= 0 && !strncmp(err, "(ERROR) is not", 14))  // (a predicate about the comment stream's file)
+      FAIL("%s %s\n", ar.comments[st.error_mate].path.c_str(), err + 8);
     if (st.error_wants_file && st.error_mate >= 0 && st.error_stream >= 0 && st.error_stream < 3)
       FAIL("%s %s\n", st.error_stream == 0 ? ar.base[st.error_mate].c_str() : ar.files[st.error_mate][st.error_stream].path.c_str(), err);
     fprintf(stderr, "%s%s\n", strncmp(err, "(ERROR)", 7) ? "(ERROR) " : "", err);
@@ -967,7 +1009,8 @@ static bool parse_options(int argc, char **argv, Options &o) {
                                      {"gpus", 1, 0, 1001}, {"interleave", 0, 0, 'i'}, {"window", 1, 0, 1002},
                                      {"records", 1, 0, 1003}, {"variable-length", 0, 0, 1004},
                                      {"max-length", 1, 0, 1005}, {"keep-order", 0, 0, 1006},
-                                     {"archive-order", 0, 0, 1007}, {0, 0, 0, 0}};
+                                     {"archive-order", 0, 0, 1007}, {"keep-comments", 0, 0, 1008},
+                                     {"no-comments", 0, 0, 1009}, {0, 0, 0, 0}};
   int opt;
   while ((opt = getopt_long(argc, argv, "vhp:T:dc:o:fs:t:B:rQAn:P:S:i", long_opt, 0)) != -1) {
     switch (opt) {
@@ -1006,6 +1049,8 @@ static bool parse_options(int argc, char **argv, Options &o) {
         break;
       case 1006: o.keep_order = true; break;
       case 1007: o.archive_order = true; break;
+      case 1008: o.keep_comments = true; break;
+      case 1009: o.no_comments = true; break;
       default: fputs(HELP_TEXT, stdout); return false;
     }
   }
@@ -1020,6 +1065,10 @@ static void check_arguments(const Options &o, const std::vector<std::string> &fi
   if (o.keep_order && o.decompress) FAIL("--keep-order is an option of compression: -d restores the order by itself when the archive has a .scalceo\n");
   if (o.archive_order && !o.decompress) FAIL("--archive-order can be only used with decompression (-d).\n");
   if (o.keep_order && o.gpus > 1) FAIL("--keep-order runs on one GPU: with --gpus %d the permutation lies spread over the ranks\n", o.gpus);
+  if (o.keep_comments && o.decompress) FAIL("--keep-comments is an option of compression: -d puts the comments back by itself when the archive has a .scalcec\n");
+  if (o.no_comments && !o.decompress) FAIL("--no-comments can be only used with decompression (-d).\n");
+  if (o.keep_comments && !o.use_names) FAIL("--keep-comments with -n: nothing is kept for what follows a name that is not kept\n");
+  if (o.keep_comments && o.gpus > 1) FAIL("--keep-comments runs on one GPU: with --gpus %d the comments lie spread over the ranks\n", o.gpus);
   if (o.decompress && files.size() > 1) FAIL("Too many files specified (decompression only supports one file).\n");
   if (o.lossy < 0 || o.lossy > 100) FAIL("Percentage must be in range [0,100].\n");
   if (o.out == "-" && (o.split || o.paired)) FAIL("stdout can be only used with single-end file decompression. It cannot be used with --split-reads option!\n");

@@ -181,6 +181,10 @@ extern "C" int scalce_batch_output(const scalce_batch *b, int which, int mate, c
     case SCALCE_OUT_NAMELEN: *d_ptr = w.namelen.p; *nbytes = b->N; break;
     case SCALCE_OUT_LENGTHS: *d_ptr = b->out_lengths[mate].p; *nbytes = b->vl && b->out_lengths[mate].p ? sizeof(u16) * b->N : 0; break;
     case SCALCE_OUT_BUCKET_NAME_BYTES: *d_ptr = b->bucket_name_bytes.p; *nbytes = b->bucket_name_bytes.p ? sizeof(u64) * nb1 : 0; break;
+    case SCALCE_OUT_COMMENTS:
+      *d_ptr = b->keep_comments ? b->out_comments[mate].p : nullptr;
+      *nbytes = b->keep_comments && b->out_comments[mate].p ? b->out_comments_bytes[mate] : 0;
+      break;
     case SCALCE_OUT_NAMECELLS: *d_ptr = w.namecell.p; *nbytes = b->p.use_names && w.namecell.p ? 16 * b->N : 0; break;
     default: return SCALCE_ERR_ARG;
   }

@@ -370,3 +370,88 @@ extern "C" int scalce_fastq_strip_window(scalce_ctx *c, int read_len, uint64_t n
   }
   return launch_failed(c);
 }
+
+// ---- what follows the names, back in a window's text (archives made with --keep-comments; kernels_comments.hpp) -------------
+// scratch of scalce_fastq_comment_window, in 64-bit words: the newline counts of the entries' tiles, the tiles of the two scans,
+// the count itself, the newline index (one entry per record)
+static u64 comment_ws_tiles(u64 entry_bytes) { return (entry_bytes + IDX_TILE - 1) / IDX_TILE + 8; }
+static u64 comment_ws_scan(u64 nrecords, u64 entry_bytes) { return scan_ws_elems(std::max<u64>(nrecords, comment_ws_tiles(entry_bytes))) + 64; }
+extern "C" uint64_t scalce_fastq_comment_ws_bytes(uint64_t nrecords, uint64_t entry_bytes) {
+  return sizeof(u64) * (comment_ws_tiles(entry_bytes) + comment_ws_scan(nrecords, entry_bytes) + 8 + nrecords + 8);
+}
+// the insert pass over nrecords records of `d_text` that begin at d_record_offsets: a record's tail is tail[r & par]
+static int comment_window(scalce_ctx *c, const u64 tail[2], u32 par, uint64_t nrecords, const uint8_t *d_text, const uint64_t *d_record_offsets,
+                          const uint8_t *d_entries, uint64_t entry_bytes, uint8_t *d_out, uint64_t *d_out_offsets, uint32_t *d_bad, void *d_ws,
+                          u64 text_bound, hipStream_t s) {
+  u64 *tile = static_cast<u64 *>(d_ws), *scan = tile + comment_ws_tiles(entry_bytes), *nlines = scan + comment_ws_scan(nrecords, entry_bytes);
+  u64 *ent_end = nlines + 8;
+  // the newline index of the entries: entry r ends at its r-th newline (an index that stays short leaves empty entries, and *d_bad)
+  HIP_TRY(c, hipMemsetAsync(nlines, 0, sizeof(u64) * (8 + nrecords), s));
+  const u32 ntiles = cdiv(entry_bytes, IDX_TILE);
+  if (ntiles) {
+    LAUNCH(index_count_k, ntiles, IDX_THREADS, 0, s, d_entries, entry_bytes, tile);
+    exclusive_scan<u64>(LoadAs<u64, u64>{tile}, ntiles, StoreTo<u64>{tile}, scan, nlines, s);
+    LAUNCH(index_write_k, ntiles, IDX_THREADS, 0, s, d_entries, entry_bytes, tile, ent_end, nrecords);
+  }
+  LAUNCH(insert_check_k, 1, 1, 0, s, nlines, d_entries, entry_bytes, nrecords, d_bad);
+  InsertArgs a;
+  a.text = d_text; a.rec_off = reinterpret_cast<const u64 *>(d_record_offsets); a.entries = d_entries; a.entry_bytes = entry_bytes;
+  a.ent_end = ent_end; a.tail[0] = tail[0]; a.tail[1] = tail[1]; a.par = par; a.nrec = nrecords;
+  a.dst_off = reinterpret_cast<u64 *>(d_out_offsets); a.dst = d_out;
+  exclusive_scan<u64>(InsertedSize{a}, nrecords, StoreTo<u64>{a.dst_off}, scan, a.dst_off + nrecords, s);
+  // (the grid covers an upper bound of the text known without a read-back; the workgroups behind the text's end return at once)
+  if (nrecords) LAUNCH(insert_copy_k, cdiv(text_bound + entry_bytes, VL_SPAN), 256, 0, s, a);
+  return launch_failed(c);
+}
+static u64 comment_tail(int read_len, int has_qualities) { return has_qualities ? 2ull * (u64)read_len + 5 : (u64)read_len + 2; }
+extern "C" int scalce_fastq_comment_window(scalce_ctx *c, int read_len, int has_qualities, uint64_t nrecords, const uint8_t *d_text,
+                                           const uint64_t *d_record_offsets, const uint8_t *d_entries, uint64_t entry_bytes, uint8_t *d_out,
+                                           uint64_t *d_out_offsets, uint32_t *d_bad, void *d_ws, void *stream) {
+  if (!c || read_len <= 0 || read_len > 65535 || !d_out_offsets || !d_bad || !d_ws || nrecords > 0xFFFFFFFFull) return SCALCE_ERR_ARG;
+  if (nrecords && (!d_text || !d_record_offsets || !d_out)) return SCALCE_ERR_ARG;
+  if (entry_bytes && !d_entries) return SCALCE_ERR_ARG;
+  if (((uintptr_t)d_text & 15) || ((uintptr_t)d_out & 15) || ((uintptr_t)d_entries & 15)) {
+    set_err(c, "comments: the window's texts and its entries must be 16-byte aligned");
+    return SCALCE_ERR_ARG;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  HIP_TRY(c, hipSetDevice(c->device));
+  // (the records' own bound of the text -- scalce_fastq_strip_window's -- a record is '@', a name of up to 255 bytes, the lines and their newlines)
+  const u64 tail[2] = {comment_tail(read_len, has_qualities), 0};
+  return comment_window(c, tail, 0, nrecords, d_text, d_record_offsets, d_entries, entry_bytes, d_out, d_out_offsets, d_bad, d_ws,
+                        nrecords * (2ull * (u64)read_len + 6 + 256), s);
+}
+
+// The same for an interleaved window (scalce_fastq_records_window with interleave): 2 npairs records, mate 1's the even ones, and
+// their entries in that order.  The records' own offsets are made from the pairs' and mate 2's name offsets, and the pairs' new
+// offsets taken from the records' new ones.
+static u64 comment_pairs_words(u64 npairs) { return 2 * npairs + 8; }
+extern "C" uint64_t scalce_fastq_comment_pairs_ws_bytes(uint64_t npairs, uint64_t entry_bytes) {
+  return scalce_fastq_comment_ws_bytes(2 * npairs, entry_bytes) + sizeof(u64) * 2 * comment_pairs_words(npairs);
+}
+extern "C" int scalce_fastq_comment_window_pairs(scalce_ctx *c, const int read_len[2], int has_qualities, uint64_t npairs, const uint8_t *d_text,
+                                                 const uint64_t *d_pair_offsets, const uint64_t *d_name_off2, const uint8_t *d_entries,
+                                                 uint64_t entry_bytes, uint8_t *d_out, uint64_t *d_out_pair_offsets, uint32_t *d_bad, void *d_ws,
+                                                 void *stream) {
+  if (!c || !read_len || !d_out_pair_offsets || !d_bad || !d_ws || npairs > 0x7FFFFFFFull) return SCALCE_ERR_ARG;
+  for (int m = 0; m < 2; m++) if (read_len[m] <= 0 || read_len[m] > 65535) return SCALCE_ERR_ARG;
+  if (npairs && (!d_text || !d_pair_offsets || !d_name_off2 || !d_out)) return SCALCE_ERR_ARG;
+  if (entry_bytes && !d_entries) return SCALCE_ERR_ARG;
+  if (((uintptr_t)d_text & 15) || ((uintptr_t)d_out & 15) || ((uintptr_t)d_entries & 15)) {
+    set_err(c, "comments: the window's texts and its entries must be 16-byte aligned");
+    return SCALCE_ERR_ARG;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  HIP_TRY(c, hipSetDevice(c->device));
+  const u64 tail[2] = {comment_tail(read_len[0], has_qualities), comment_tail(read_len[1], has_qualities)};
+  u64 *rec_off = reinterpret_cast<u64 *>(static_cast<u8 *>(d_ws) + scalce_fastq_comment_ws_bytes(2 * npairs, entry_bytes));
+  u64 *new_off = rec_off + comment_pairs_words(npairs);
+  LAUNCH(pair_split_k, cdiv(npairs + 1, 256), 256, 0, s, npairs, reinterpret_cast<const u64 *>(d_pair_offsets), reinterpret_cast<const u64 *>(d_name_off2),
+         tail[1], rec_off);
+  const int rc = comment_window(c, tail, 1, 2 * npairs, d_text, reinterpret_cast<const uint64_t *>(rec_off), d_entries, entry_bytes, d_out,
+                                reinterpret_cast<uint64_t *>(new_off), d_bad, d_ws,
+                                npairs * (2ull * ((u64)read_len[0] + (u64)read_len[1]) + 12 + 512), s);
+  if (rc) return rc;
+  LAUNCH(pair_offsets_k, cdiv(npairs + 1, 256), 256, 0, s, npairs, new_off, reinterpret_cast<u64 *>(d_out_pair_offsets));
+  return launch_failed(c);
+}

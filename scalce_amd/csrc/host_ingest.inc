@@ -38,6 +38,44 @@ static int ensure_line_index(scalce_batch *b, int mate, hipStream_t s) {
   return SCALCE_OK;
 }
 
+// --keep-comments: what follows the name on the header lines of the piece's first `nrec` rows goes behind mate m's entries of
+// earlier pieces (com_in[m], input order), each entry with its newline; comlen[m] keeps the lengths per row.  Runs behind the
+// rows' own ingest (mate 0's lengths come from namelen), from the piece's line index: a plan pass, one exclusive scan, one
+// copy pass.  The text is not needed again.  `mate`: the text's; an interleaved text (mate 0's) serves both mates.
+static int piece_comments(scalce_batch *b, int mate, const u8 *d_text, u64 nbytes, u64 nrec, hipStream_t s) {
+  scalce_workspace &w = *b->ws;
+  scalce_ctx *c = b->ctx;
+  { int rc = ensure_line_index(b, mate, s); if (rc) return rc; }
+  ENSURE(b, b->com_piece_off, sizeof(u64) * (nrec + 8));
+  ENSURE(b, w.scan_ws, sizeof(u64) * (scan_ws_elems(nrec) + 64));
+  for (int m = mate; m < (b->il ? 2 : mate + 1); m++) {
+    const u64 rows = std::max<u64>(w.row_cap, b->base + nrec);
+    { int rc = ensure_keep(b, b->comlen[m], sizeof(u16) * (rows + 64), sizeof(u16) * b->base, s); if (rc) return rc; }
+    if (b->base == 0) HIP_TRY(c, hipMemsetAsync(&b->d_scr->comment_longest[m], 0, sizeof(u32), s));
+    CommentArgs a;
+    a.text = d_text; a.nbytes = nbytes; a.line_end = w.line_end[mate].as<u64>();
+    a.unit_lines = (u32)b->unit_lines(); a.line0 = m == mate ? 0u : (u32)b->lpr;
+    a.nrec = nrec; a.row0 = b->base;
+    a.namelen = m == 0 ? w.namelen.as<u8>() + b->base : nullptr;
+    a.comlen = b->comlen[m].as<u16>() + b->base;
+    a.off = b->com_piece_off.as<u64>();
+    a.dst = nullptr;
+    a.longest = &b->d_scr->comment_longest[m];
+    a.err = b->d_err;
+    LAUNCH(comment_plan_k, cdiv(nrec, 256), 256, 0, s, a);
+    exclusive_scan<u64>(CommentSize{a.comlen}, nrec, StoreTo<u64>{a.off}, w.scan_ws.as<u64>(), a.off + nrec, s);
+    { int rc = check_device_error(b, s); if (rc) return rc; }
+    u64 total = 0;
+    { int rc = read_u64(b, a.off + nrec, &total, 1, s); if (rc) return rc; }
+    { int rc = read_u32(b, &b->d_scr->comment_longest[m], &b->com_longest[m], 1, s); if (rc) return rc; }
+    { int rc = ensure_keep(b, b->com_in[m], b->com_used[m] + total + 64, b->com_used[m], s); if (rc) return rc; }
+    a.dst = b->com_in[m].as<u8>() + b->com_used[m];
+    LAUNCH(comment_copy_k, cdiv(total, COM_SPAN), 256, 0, s, a);
+    b->com_used[m] += total;
+  }
+  return SCALCE_OK;
+}
+
 // the first `nrec` records of the text -> rows [base, base + nrec): 2-bit bases, q', names
 // (A one-pass variant -- no count pass, the tiles' line bases by decoupled look-back between the workgroups -- was byte-exact
 // and slower: 9.2 ms against 1.7 + 6.2 at 50 M x 100 bp, rounds 3-4; removed in round 5.)
@@ -175,6 +213,7 @@ static int piece_unpack_t(scalce_batch *b, int mate, const u8 *d_text, u64 nbyte
       b->ingest_plan[mate][3] = (u32)total;
     }
   }
+  if (b->keep_comments) { int rc = piece_comments(b, mate, d_text, nbytes, nrec, s); if (rc) return rc; }
   b->ingest_plan[mate][2] = b->line_index_ok[mate] ? 1u : 0u;
   if (IL)  // (one text, one line index, mate 1's names: mate 2 reports what mate 1 does, and the kernel that wrote its own rows)
     for (int i = 1; i < 4; i++) b->ingest_plan[mate + 1][i] = b->ingest_plan[mate][i];
@@ -253,6 +292,7 @@ static void batch_restart(scalce_batch *b) {
   b->tok_done = b->tok_base = b->tok_n = 0;
   b->appending = false;
   b->names_in_used = 0;
+  for (int m = 0; m < 2; m++) b->com_used[m] = b->out_comments_bytes[m] = b->com_longest[m] = 0;
   b->tri_expected[0] = b->tri_expected[1] = 0;
   b->ingested[0] = b->ingested[1] = false;
   for (int m = 0; m < 2; m++)
@@ -378,7 +418,7 @@ static int not_whole_records(scalce_ctx *c, const char *which) {
 // ingest starts it over.
 extern "C" int scalce_batch_rewindow(scalce_batch *b, uint64_t keep_first, uint64_t keep_rows, const uint8_t *const front[2],
                                      const uint64_t front_bytes[2], const uint8_t *const back[2], const uint64_t back_bytes[2], void *stream) {
-  if (!b || !front || !back || !front_bytes || !back_bytes || keep_first + keep_rows > b->N || b->il || b->vl) return SCALCE_ERR_ARG;
+  if (!b || !front || !back || !front_bytes || !back_bytes || keep_first + keep_rows > b->N || b->il || b->vl || b->keep_comments) return SCALCE_ERR_ARG;
   scalce_ctx *c = b->ctx;
   hipStream_t s = (hipStream_t)stream;
   HIP_TRY(c, hipSetDevice(c->device));
@@ -472,6 +512,21 @@ extern "C" void scalce_batch_set_lean(scalce_batch *b, int lean) {
 extern "C" int scalce_batch_set_keep_order(scalce_batch *b, int on) {
   if (!b) return SCALCE_ERR_ARG;
   b->keep_order = on != 0;
+  return SCALCE_OK;
+}
+// what follows the names becomes an output of the run (SCALCE_OUT_COMMENTS): before the first ingest or append of the run
+extern "C" int scalce_batch_set_keep_comments(scalce_batch *b, int on) {
+  if (!b) return SCALCE_ERR_ARG;
+  if (on && !b->p.use_names) { set_err(b->ctx, "nothing is kept for what follows a name that is not kept"); return SCALCE_ERR_ARG; }
+  b->keep_comments = on != 0;
+  return SCALCE_OK;
+}
+// (for the other translation units of the library: sharded.cpp, pipeline.cpp)
+bool scalce_batch_keeps_comments(const scalce_batch *b) { return b && b->keep_comments; }
+extern "C" int scalce_batch_comments_info(const scalce_batch *b, int mate, uint64_t *nbytes, uint32_t *longest) {
+  if (!b || mate < 0 || mate >= b->nm) return SCALCE_ERR_ARG;
+  if (nbytes) *nbytes = b->keep_comments ? b->com_used[mate] : 0;
+  if (longest) *longest = b->keep_comments ? b->com_longest[mate] : 0;
   return SCALCE_OK;
 }
 extern "C" uint64_t scalce_batch_reruns(const scalce_batch *b) { return b ? b->reruns : 0; }

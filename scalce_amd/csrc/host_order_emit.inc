@@ -269,6 +269,27 @@ extern "C" int scalce_batch_emit(scalce_batch *b, void *stream) {
              b->out_reads[1].as<u8>());
     }
   } else if (b->nm == 2) b->out_reads_bytes[1] = 0;
+  // what follows the names, in archive order: output record k is input record perm[k] of the mate's store -- the permute of the
+  // order restore (scalce_records_permute), with the scan of the rows' entry sizes for the store's offsets
+  for (int m = 0; m < b->nm && b->keep_comments; m++) {
+    b->out_comments_bytes[m] = N ? b->com_used[m] : 0;
+    if (!N) continue;
+    ENSURE(b, b->com_off, sizeof(u64) * (N + 8));
+    ENSURE(b, b->com_out_off, sizeof(u64) * (N + 8));
+    ENSURE(b, b->com_ws, (size_t)scalce_records_permute_ws_bytes(N));
+    ENSURE(b, b->out_comments[m], (size_t)b->com_used[m] + 64);
+    u64 *off = b->com_off.as<u64>();
+    exclusive_scan<u64>(CommentSize{b->comlen[m].as<u16>()}, N, StoreTo<u64>{off}, b->com_ws.as<u64>(), off + N, s);
+    int rc = scalce_records_permute(c, b->com_in[m].as<u8>(), b->com_off.as<uint64_t>(), N, b->com_used[m], b->perm, b->out_comments[m].as<u8>(), b->com_used[m],
+                                    b->com_out_off.as<uint64_t>(), b->com_ws.p, s);
+    if (rc) return rc;
+    if (b->lean) {  // the input-order store is dead once the gathered stream exists
+      HIP_TRY(c, hipStreamSynchronize(s));
+      b->com_in[m].release();
+      b->comlen[m].release();
+    }
+  }
+  if (b->lean && b->keep_comments) { b->com_off.release(); b->com_out_off.release(); b->com_ws.release(); b->com_piece_off.release(); }
   if (b->lean) {  // nothing behind this stage reads the rows, the tokens or the sort scratch
     HIP_TRY(c, hipStreamSynchronize(s));
     DBuf *dead[] = {&w.packed[0], &w.packed[1], &w.namecell, &w.names_in, &w.name_in_off, &w.name_off, &w.outlen, &w.cell_sorted,

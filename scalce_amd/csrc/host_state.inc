@@ -242,6 +242,7 @@ struct BatchScratch {
   u64 consumed[2];       // per mate: text offset behind the last record taken (piece_unpack_t)
   u64 long_names_bytes;  // what the piece adds to the long-name store
   u64 text_offset;       // scalce_batch_text_offset
+  u32 comment_longest[2];  // per mate: the run's longest entry (comment_plan_k; cleared when a run starts)
   struct IngestFlags {   // cleared and read back as one
     u32 max_namelen;     // longest name of the piece
     u32 slow;            // a record did not fit the tile overlap: the piece is redone the indexed way
@@ -339,6 +340,14 @@ struct scalce_batch {
   u32 ac_desc_cap = 0;                  // asynchronous upload never reads memory the next launch is already rewriting
   u32 *perm = nullptr;  // final permutation (points into perm_a or perm_b)
   DBuf out_lengths[2];  // variable-length runs: L - length in output order (the order stage gathers padlen through perm)
+  // What follows the names (scalce_batch_set_keep_comments): per mate comlen = the entry's length per row (u16, run-wide, input
+  // order) and com_in = the entries, each with its newline, in input order (com_used bytes of it, like the long-name store);
+  // the emit stage gathers them through the permutation into out_comments (SCALCE_OUT_COMMENTS).  com_off / com_out_off /
+  // com_piece_off: the offsets of the gather and of a piece's extract pass.  Nothing of it exists without the option.
+  bool keep_comments = false;
+  DBuf comlen[2], com_in[2], out_comments[2], com_off, com_out_off, com_piece_off, com_ws;
+  u64 com_used[2] = {0, 0}, out_comments_bytes[2] = {0, 0};
+  u32 com_longest[2] = {0, 0};
   // host-side results
   u64 out_reads_bytes[2] = {0, 0}, out_names_bytes = 0, out_qual_bytes[2] = {0, 0};
   u32 ntie = 0, nev = 0, ntev = 0, ncand_cap = 0, jacobi_iters = 0, nchunks = 1, sweep_no = 0;
@@ -661,6 +670,8 @@ static int check_device_error(scalce_batch *b, hipStream_t s) {
   if (b->vl && e.code == E_READLEN)
     set_err(b->ctx, "(ERROR) record %llu holds %u bases, more than the run's read length (%d%s): give the longest read with --max-length",
             (unsigned long long)e.where, e.aux, b->L[b->vl_mate], b->nm == 2 ? (b->vl_mate ? ", mate 2" : ", mate 1") : "");
+  else if (e.code == E_COMMENT)
+    set_err(b->ctx, "(ERROR) record %llu: what follows the name is longer than 65535 bytes", (unsigned long long)e.where);
   else if (e.code == E_SEQQUAL)
     set_err(b->ctx, "(ERROR) record %llu: its sequence line (%u characters) and its quality line differ in length", (unsigned long long)e.where, e.aux);
   else

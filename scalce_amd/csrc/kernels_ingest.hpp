@@ -19,7 +19,8 @@ enum DevErrCode : u32 {
   E_ACOVERFLOW = 5, // a coded block outgrew the reference's 10 MiB output buffer (arithmetic.cpp:101)
   E_PAIRS = 6,      // mates have different record counts
   E_INTERNAL = 7,
-  E_SEQQUAL = 8     // variable-length runs: a record whose sequence and quality lines differ in length (pad_plan_k)
+  E_SEQQUAL = 8,    // variable-length runs: a record whose sequence and quality lines differ in length (pad_plan_k)
+  E_COMMENT = 9     // --keep-comments: what follows a record's name is longer than 65535 bytes (comment_plan_k)
 };
 struct DevErr {
   u32 code;

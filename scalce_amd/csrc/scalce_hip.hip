@@ -19,6 +19,7 @@
 #include "kernels_acl.hpp"
 #include "kernels_fastq.hpp"
 #include "kernels_varlen.hpp"
+#include "kernels_comments.hpp"
 
 using namespace scalce;
 

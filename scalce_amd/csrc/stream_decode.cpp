@@ -94,6 +94,9 @@ struct Slot {
   // variable-length archives: the window's entries of the length stream, and what strips the pad off its text
   HBuf h_len;
   DBuf d_len, d_text2, d_roff2, d_scan;
+  // archives with a comment stream: the window's entries, the text with them put back and what the insert pass works in
+  HBuf h_com, h_cbad;
+  DBuf d_com, d_textc, d_roffc, d_cws, d_cbad;
   Event ev_up, ev_rec, ev_done, t_rec0, t_rec1;
   bool busy = false;
 };
@@ -107,6 +110,8 @@ struct Window {
   u64 slice[2] = {0, 0};    // and bytes of the read stream
   u64 nbytes = 0, cut = 0;  // text that comes down; what the strip takes off it on the device
   bool strip = false;
+  bool com = false;         // the window's entries of the comment stream go back into its text
+  u64 cbytes = 0;           // ... their bytes, newlines included
 };
 
 struct Job {
@@ -163,6 +168,8 @@ struct Session {
   std::thread writer;
   int device = 0;
   std::unique_ptr<Restore> X;  // set: the input order is restored
+  scalce_unpack_comments CM;   // the comment streams (scalce_stream_decompress_comments), or none
+  u64 cap_com = 0;             // bytes of entries a slot takes
 
   // (the streams in front of what is used on them: close() lets everything go in the right order by hand, and should a
   // session ever die without it, the buffers and events would still go before the streams)
@@ -182,6 +189,7 @@ struct Session {
     RG.nrecords = UNKNOWN;
     if (rg) RG = *rg;
     memset(&RS, 0, sizeof RS);
+    memset(&CM, 0, sizeof CM);
     RS.first_record = RG.first_record;
     RS.total_records = UNKNOWN;
     A.M[0] = &M[0];
@@ -243,7 +251,12 @@ struct Session {
     W = P.window_text_bytes ? P.window_text_bytes : SCALCE_WINDOW_TEXT_DEFAULT;
     S.window_text_bytes = W;
     u64 rec_min = 0, rec_max = 0;
-    for (int m = A.m0; m <= A.m1; m++) { rec_min += A.rec_budget(m); rec_max += rec_fixed(m) + 255 + 32; }
+    // (comment streams: the bound of a record's text grows by the mate's longest entry)
+    const bool com = M[A.m0].has_com;
+    const u64 nmates = (u64)(A.m1 - A.m0 + 1);
+    u64 C = 0;
+    for (int m = A.m0; m <= A.m1 && com; m++) C = std::max<u64>(C, M[m].c_longest);
+    for (int m = A.m0; m <= A.m1; m++) { rec_min += A.rec_budget(m); rec_max += rec_fixed(m) + 255 + 32 + (com ? M[m].c_longest : 0); }
     R = std::max<u64>(1, W / rec_min);
     D = std::min<u64>(R, (u64)scalce_patterns_count(ctx) + 2);
     cap_text = std::max(W, rec_max) + 64;
@@ -281,7 +294,18 @@ struct Session {
       SD_TRY(dmalloc(s.d_text, cap_text));
       const bool strip = M[A.m0].has_len;  // (never with two mates in one window: -d -i refuses a length stream)
       if (P.split) SD_TRY(hmalloc(s.h_roff, roff_bytes));
-      if (P.split || strip || X) SD_TRY(dmalloc(s.d_roff, roff_bytes));
+      if (P.split || strip || X || com) SD_TRY(dmalloc(s.d_roff, roff_bytes));
+      if (com) {  // a window's entries: no more than its text, nor than its records' times the longest
+        cap_com = std::min(std::max(W, nmates * (C + 1)), R * nmates * (C + 1)) + 64;
+        SD_TRY(hmalloc(s.h_com, cap_com));
+        SD_TRY(hmalloc(s.h_cbad, 64));
+        memset(s.h_cbad.p, 0, 64);
+        SD_TRY(dmalloc(s.d_com, cap_com));
+        SD_TRY(dmalloc(s.d_textc, cap_text));
+        SD_TRY(dmalloc(s.d_roffc, roff_bytes));
+        SD_TRY(dmalloc(s.d_cws, nmates == 2 ? scalce_fastq_comment_pairs_ws_bytes(R, cap_com) : scalce_fastq_comment_ws_bytes(R, cap_com)));
+        SD_TRY(dmalloc(s.d_cbad, 64));
+      }
       if (X) SD_TRY(X->setup_slot(*this, i, roff_bytes));
       if (strip) {
         SD_TRY(hmalloc(s.h_len, len_bytes));
@@ -297,7 +321,7 @@ struct Session {
   }
   void free_slots() {
     for (Slot &s : slot) {
-      for (DBuf *b : {&s.d_len, &s.d_text2, &s.d_roff2, &s.d_scan, &s.d_in, &s.d_text, &s.d_roff}) drop(*b);
+      for (DBuf *b : {&s.d_len, &s.d_text2, &s.d_roff2, &s.d_scan, &s.d_com, &s.d_textc, &s.d_roffc, &s.d_cws, &s.d_cbad, &s.d_in, &s.d_text, &s.d_roff}) drop(*b);
       s = Slot();
     }
     if (X) X->free_slots(*this);
@@ -428,6 +452,8 @@ struct Session {
     if (j.kind == Job::STRIPE) X->S.place_wait_s += now_s() - t0;
     if (!failed && j.kind != Job::WINDOW && X->rs[j.slot].h_bad.as<u32>()[0])
       fail(SCALCE_ERR_FORMAT, A.m0, 4, 0, "(ERROR) %s", order_not_permutation());
+    if (!failed && j.kind != Job::STRIPE && slot[j.slot].h_cbad.p && slot[j.slot].h_cbad.as<u32>()[0])
+      fail(SCALCE_ERR_FORMAT, A.m0, 5, 0, "internal: a window's entries of the comment stream do not fit its records");
     return !failed;
   }
   void records_time(const Slot &s) {
@@ -602,6 +628,8 @@ struct Session {
     }
     for (int m = m0; m <= m1; m++)  // the length stream: entries of one width
       if (M[m].has_len) SD_TRY(took(A.lengths(m, first, nullptr, got, WF), m, 3, got, first));
+    for (int m = m0; m <= m1; m++)  // the comment stream: entries by their newlines
+      if (M[m].has_com) SD_TRY(took(A.pass_comments(m, first, got, WF), m, 5, got, first));
     for (int m = m0; m <= m1; m++) {
       Mate &x = M[m];
       x.first = first;
@@ -630,7 +658,11 @@ struct Session {
       u8 *h_in = slot[w.si].h_in.as<u8>();
       NamesDst to[2] = {{h_in + M[m0].o_names, reinterpret_cast<u64 *>(h_in + M[m0].o_noff), M[m0].cap_names},
                                      {h_in + M[m1].o_names, reinterpret_cast<u64 *>(h_in + M[m1].o_noff), M[m1].cap_names}};
-      return walk(A.take_names(to, ncap, W, w.n, w.nb, WF));
+      CommentsDst cd{slot[w.si].h_com.as<u8>(), cap_com};
+      w.com = M[m0].has_com;
+      const int rc = A.take_names(to, ncap, W, w.n, w.nb, WF, w.com ? &cd : nullptr);
+      w.cbytes = cd.nbytes;
+      return walk(rc);
     }
     auto text = [&](u64 k) { u64 t = 0; for (int m = m0; m <= m1; m++) t += lib_text(m, w.first, k, true); return t; };
     if (text(w.n) > W) {
@@ -672,6 +704,7 @@ struct Session {
     }
     for (int m = m0; m <= m1; m++)
       w.nbytes += A.names ? (A.qual ? scalce_fastq_text_bytes : scalce_fasta_text_bytes)(M[m].L, w.n, w.nb[m - m0], nullptr) : lib_text(m, w.first, w.n);
+    if (w.com) w.nbytes += w.cbytes - w.n * (u64)(m1 - m0 + 1);  // (the entries without their newlines)
     if (w.nbytes + 64 > cap_text) return fail(SCALCE_ERR_CAPACITY, -1, -1, 0, "internal: a window of %llu bytes of text", (unsigned long long)w.nbytes);
     return SCALCE_OK;
   }
@@ -679,6 +712,7 @@ struct Session {
     Slot &s = slot[w.si];
     u8 *h_in = s.h_in.as<u8>(), *d_in = s.d_in.as<u8>();
     if (w.strip) SD_HIP(hipMemcpyAsync(s.d_len.p, s.h_len.p, w.n * (u64)M[A.m0].l_width, hipMemcpyHostToDevice, s_up));
+    if (w.com) SD_HIP(hipMemcpyAsync(s.d_com.p, s.h_com.p, w.cbytes, hipMemcpyHostToDevice, s_up));
     if (X) SD_TRY(X->upload(*this, w));
     for (int m = A.m0; m <= A.m1; m++) {
       Mate &x = M[m];
@@ -694,7 +728,10 @@ struct Session {
     SD_HIP(hipEventRecord(s.ev_up, s_up));
     return SCALCE_OK;
   }
-  // records -> text, mate by mate, behind the upload; then the pad goes (variable-length)
+  // where a window's finished text and record offsets lie: behind the strip, else behind the insert, else as the records kernel left them
+  DBuf &window_text(const Window &w) { Slot &s = slot[w.si]; return w.strip ? s.d_text2 : w.com ? s.d_textc : s.d_text; }
+  DBuf &window_roff(const Window &w) { Slot &s = slot[w.si]; return w.strip ? s.d_roff2 : w.com ? s.d_roffc : s.d_roff; }
+  // records -> text, mate by mate, behind the upload; then the entries come back (comments) and the pad goes (variable-length)
   int window_launch(Window &w) {
     const int m0 = A.m0, m1 = A.m1;
     Slot &s = slot[w.si];
@@ -717,7 +754,7 @@ struct Session {
       if (A.names) { fw.d_names = d_in + x.o_names; fw.d_name_off = reinterpret_cast<const u64 *>(d_in + x.o_noff); }
       fw.library = A.library.c_str();
       fw.d_out = s.d_text.as<u8>();
-      fw.d_record_offsets = ((P.split || w.strip || X) && m == m0) ? s.d_roff.as<u64>() : nullptr;
+      fw.d_record_offsets = ((P.split || w.strip || X || w.com) && m == m0) ? s.d_roff.as<u64>() : nullptr;
       if (nmates == 2) {
         const Mate &y = M[m == m0 ? m1 : m0];
         fw.interleave = m - m0 + 1; fw.pair_read_len = y.L;
@@ -730,12 +767,22 @@ struct Session {
         d.pos += w.n * (u64)x.L;
       }
     }
+    // the entries go back in BEFORE the strip (which measures from the record's end) and before the order restore groups the
+    // window (its records are self-contained text)
+    if (w.com && nmates == 2) {  // (one interleaved text: both mates' entries, pair by pair)
+      const int rl[2] = {M[m0].L, M[m1].L};
+      SD_TRY(lib(scalce_fastq_comment_window_pairs(ctx, rl, A.qual ? 1 : 0, w.n, s.d_text.as<u8>(), s.d_roff.as<u64>(),
+                                                   reinterpret_cast<const u64 *>(d_in + M[m1].o_noff), s.d_com.as<u8>(), w.cbytes, s.d_textc.as<u8>(),
+                                                   s.d_roffc.as<u64>(), s.d_cbad.as<u32>(), s.d_cws.p, s_main)));
+    } else if (w.com)
+      SD_TRY(lib(scalce_fastq_comment_window(ctx, M[m0].L, A.qual ? 1 : 0, w.n, s.d_text.as<u8>(), s.d_roff.as<u64>(), s.d_com.as<u8>(), w.cbytes,
+                                             s.d_textc.as<u8>(), s.d_roffc.as<u64>(), s.d_cbad.as<u32>(), s.d_cws.p, s_main)));
     if (w.strip) {  // the text and its record offsets come down from the stripped copy
-      SD_TRY(lib(scalce_fastq_strip_window(ctx, M[m0].L, w.n, s.d_text.as<u8>(), s.d_roff.as<u64>(), s.d_len.as<u8>(), M[m0].l_width,
-                                           s.d_text2.as<u8>(), s.d_roff2.as<u64>(), s.d_scan.p, s_main)));
+      SD_TRY(lib(scalce_fastq_strip_window(ctx, M[m0].L, w.n, (w.com ? s.d_textc : s.d_text).as<u8>(), (w.com ? s.d_roffc : s.d_roff).as<u64>(),
+                                           s.d_len.as<u8>(), M[m0].l_width, s.d_text2.as<u8>(), s.d_roff2.as<u64>(), s.d_scan.p, s_main)));
       w.nbytes -= w.cut;
     }
-    if (X) SD_TRY(X->group(*this, w, (w.strip ? s.d_text2 : s.d_text).as<u8>(), (w.strip ? s.d_roff2 : s.d_roff).as<u64>()));
+    if (X) SD_TRY(X->group(*this, w, window_text(w).as<u8>(), window_roff(w).as<u64>()));
     SD_HIP(hipEventRecord(s.t_rec1, s_main));
     SD_HIP(hipEventRecord(s.ev_rec, s_main));
     return SCALCE_OK;
@@ -747,9 +794,10 @@ struct Session {
     if (X) {
       SD_TRY(X->download(*this, w));
     } else {
-      SD_HIP(hipMemcpyAsync(s.h_text.p, w.strip ? s.d_text2.p : s.d_text.p, w.nbytes, hipMemcpyDeviceToHost, s_down));
-      if (P.split) SD_HIP(hipMemcpyAsync(s.h_roff.p, w.strip ? s.d_roff2.p : s.d_roff.p, 8 * (w.n + 1), hipMemcpyDeviceToHost, s_down));
+      SD_HIP(hipMemcpyAsync(s.h_text.p, window_text(w).p, w.nbytes, hipMemcpyDeviceToHost, s_down));
+      if (P.split) SD_HIP(hipMemcpyAsync(s.h_roff.p, window_roff(w).p, 8 * (w.n + 1), hipMemcpyDeviceToHost, s_down));
     }
+    if (w.com) SD_HIP(hipMemcpyAsync(s.h_cbad.p, s.d_cbad.p, 4, hipMemcpyDeviceToHost, s_down));
     SD_HIP(hipEventRecord(s.ev_done, s_down));
     to_writer(w.si, w.first, w.n, w.nbytes, X ? Job::SPILL : Job::WINDOW);
     return SCALCE_OK;
@@ -783,6 +831,8 @@ struct Session {
                   (unsigned long long)M[m1].records_left);
     A.known = M[m0].records_left != UNKNOWN;
     if (X && A.known && X->N != M[m0].records_left) return order_count(M[m0].records_left);
+    for (int m = m0; m <= m1; m++)
+      if (M[m].has_com && A.known && M[m].c_total != M[m0].records_left) return walk(A.comment_count(m, M[m].c_total, M[m0].records_left, WF));
     SD_TRY(pass_over());
     for (;;) {
       if (failed) return F.rc;
@@ -797,6 +847,9 @@ struct Session {
     }
     RS.nrecords = S.records[m0];
     SD_TRY(check_end());
+    // (an archive that does not say how many records it holds, read to its end: the stream must have ended with it)
+    for (int m = m0; m <= m1; m++)
+      if (M[m].has_com && M[m0].range_left == UNKNOWN && M[m].c_taken != M[m].c_total) return walk(A.comment_count(m, M[m].c_total, M[m].c_taken, WF));
     drain();
     if (failed) return F.rc;
     for (int m = m0; m <= m1; m++) free_decoder(m);
@@ -823,6 +876,11 @@ struct Session {
         if (has) return fail(SCALCE_ERR_FORMAT, m, 2, 1, "holds no qualities: the archive was made with -Q or -f; decompress it with -Q");
         M[m].records_left = 0;
       }
+    for (int m = 0; m < P.mates; m++) {  // the comment streams: header, then one entry per record
+      if (!CM.com_rd[m]) continue;
+      if (!A.names) return fail(SCALCE_ERR_ARG, m, 5, 0, "(ERROR) a comment stream goes with stored names: the archive holds none (or -n sets them aside)");
+      SD_TRY(walk(A.comments_open(m, CM.com_rd[m], CM.com_user[m], &S.read_wait_s, WF)));
+    }
     for (Stream *s : {&s_up, &s_main, &s_dec, &s_down}) SD_HIP(s->create());
     writer = std::thread([this] { writer_main(); });
     const bool together = P.mates == 2 && P.interleave;
@@ -956,6 +1014,39 @@ extern "C" int scalce_stream_decompress_range(scalce_ctx *ctx, const scalce_unpa
   const int rc = session_run(s, rd, user, stats, range_stats, errbuf, errcap);
   delete s;
   return rc;
+}
+
+// the three shapes of decompression behind one call, with or without comment streams (the entry points below and above are this)
+static int decompress_any(scalce_ctx *ctx, const scalce_unpack_params *p, const scalce_unpack_comments *cm, const scalce_unpack_range *range,
+                          const scalce_restore_params *rp, scalce_read_fn rd[2][3], void *user[2][3], scalce_write_fn wr, void *wr_user,
+                          scalce_unpack_stats *stats, scalce_unpack_range_stats *range_stats, scalce_restore_stats *restore_stats, char *errbuf,
+                          size_t errcap) {
+  if (const int rc = unpack_args(ctx, p, rd, user, wr, errbuf, errcap)) return rc;
+  if (rp && (range || !rp->order_rd[0] || (p->mates == 2 && !p->interleave && !rp->order_rd[1]))) return SCALCE_ERR_ARG;
+  const bool com = cm && (cm->com_rd[0] || cm->com_rd[1]);
+  if (com && (!cm->com_rd[0] || (p->mates == 2 && !cm->com_rd[1]))) {
+    if (errbuf && errcap) snprintf(errbuf, errcap, "(ERROR) an archive with comment streams: every mate has its stream");
+    return SCALCE_ERR_ARG;
+  }
+  Session *s = new Session(ctx, p, range, wr, wr_user);
+  if (com) s->CM = *cm;
+  if (rp) {
+    s->X.reset(new Restore);
+    s->X->P = *rp;
+    memset(&s->X->S, 0, sizeof s->X->S);
+    s->X->dir = rp->spill_dir && rp->spill_dir[0] ? rp->spill_dir : ".";
+  }
+  const int rc = session_run(s, rd, user, stats, rp ? nullptr : range_stats, errbuf, errcap);
+  if (rp && restore_stats) *restore_stats = s->X->S;
+  delete s;
+  return rc;
+}
+extern "C" int scalce_stream_decompress_comments(scalce_ctx *ctx, const scalce_unpack_params *p, const scalce_unpack_comments *comments,
+                                                 const scalce_unpack_range *range, const scalce_restore_params *rp, scalce_read_fn rd[2][3],
+                                                 void *user[2][3], scalce_write_fn wr, void *wr_user, scalce_unpack_stats *stats,
+                                                 scalce_unpack_range_stats *range_stats, scalce_restore_stats *restore_stats, char *errbuf,
+                                                 size_t errcap) {
+  return decompress_any(ctx, p, comments, range, rp, rd, user, wr, wr_user, stats, range_stats, restore_stats, errbuf, errcap);
 }
 
 extern "C" int scalce_stream_decompress_restore(scalce_ctx *ctx, const scalce_unpack_params *p, const scalce_restore_params *rp,

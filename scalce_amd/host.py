@@ -18,6 +18,7 @@ _LIB = None
 OUT_READS, OUT_NAMES, OUT_QUAL, OUT_TABLE, OUT_FREQ4, OUT_TOKENS, OUT_PERM, OUT_QSTREAM, OUT_BUCKET_COUNTS, OUT_QINPUT, OUT_NAMELEN = range(11)
 OUT_LENGTHS = 12  # variable-length runs: N x u16, read_len - length per record in output order
 OUT_NAMECELLS = 13  # for tests: N x 16 bytes, [stored length][first 15 characters, zero behind a shorter name], input order
+OUT_COMMENTS = 14  # keep_comments: what follows the name of every record in output order, each entry followed by a newline
 STAGES = ("ingest", "quality", "tokenize", "order", "emit", "entropy")
 ROOT_CORE = 0x3FFFFFFF
 
@@ -653,9 +654,37 @@ def _unpack_check(rc, msg):
         raise ScalceError(f"[{rc}] " + msg.value.decode(errors="replace"))
 
 
+class UnpackComments(C.Structure):
+    """scalce_unpack_comments: the comment streams of an archive made with --keep-comments, one per mate"""
+    _fields_ = [("com_rd", READ_FN * 2), ("com_user", C.c_void_p * 2)]
+
+
+def _unpack_comments(keep, mates, comment_readers):
+    cm = UnpackComments()
+    for m in range(mates):
+        if comment_readers[m] is not None:
+            cm.com_rd[m] = _unpack_read_fn(keep, comment_readers[m])
+    return cm
+
+
+def _decompress_comments(ctx, p, cm, rg, rp, rd, user, wfn, st, rst, ost, msg):
+    """scalce_stream_decompress_comments: the one entry point behind the three shapes, with comment streams"""
+    L = ctx.L
+    L.scalce_stream_decompress_comments.argtypes = [C.c_void_p, C.POINTER(UnpackParams), C.POINTER(UnpackComments), C.POINTER(UnpackRange),
+                                                    C.POINTER(RestoreParams), C.c_void_p, C.c_void_p, WRITE_FN, C.c_void_p,
+                                                    C.POINTER(UnpackStats), C.POINTER(UnpackRangeStats), C.POINTER(RestoreStats),
+                                                    C.c_char_p, C.c_size_t]
+    L.scalce_stream_decompress_comments.restype = C.c_int
+    return L.scalce_stream_decompress_comments(ctx.h, C.byref(p), C.byref(cm) if cm is not None else None,
+                                               C.byref(rg) if rg is not None else None, C.byref(rp) if rp is not None else None,
+                                               C.cast(rd, C.c_void_p), C.cast(user, C.c_void_p), wfn, None, C.byref(st),
+                                               C.byref(rst) if rst is not None else None, C.byref(ost) if ost is not None else None,
+                                               msg, len(msg))
+
+
 def stream_decompress(ctx, readers, write, mates=1, interleave=False, no_qualities=False, mate_digit=None, library=None,
                       split=0, window_text_bytes=0, first_record=0, nrecords=None, skippers=None, length_readers=None,
-                      length_skippers=None):
+                      length_skippers=None, comment_readers=None):
     """scalce_stream_decompress_range: an archive, or a range of its records, back to text in windows of whole records.
     readers[m] = the three callables (cap) -> bytes of mate m's .scalcer, .scalcen and .scalceq streams (b"" at the end; raise
     for a read error); write(mate, first_record, nrecords, text_bytes, record_offsets or None) receives every window in
@@ -663,7 +692,8 @@ def stream_decompress(ctx, readers, write, mates=1, interleave=False, no_qualiti
     the archive holds (-n).  first_record / nrecords (None: to the end): the range, in archive order; skippers[m] = three
     callables (nbytes) -> bytes passed over, or None where the stream can only be read.  length_readers[m] (and, optionally,
     length_skippers[m]): the .scalcel stream of a variable-length archive, one callable per mate.  Returns UnpackStats; its attribute
-    `range` holds the UnpackRangeStats of the run."""
+    `range` holds the UnpackRangeStats of the run.  comment_readers[m]: the .scalcec stream of an archive made with
+    --keep-comments, one callable per mate -- the call then goes through scalce_stream_decompress_comments."""
     keep = []
     wfn = _unpack_write_fn(write)
     rd = ((READ_FN * 3) * 2)()
@@ -689,8 +719,11 @@ def stream_decompress(ctx, readers, write, mates=1, interleave=False, no_qualiti
                                                  WRITE_FN, C.c_void_p, C.POINTER(UnpackStats), C.POINTER(UnpackRangeStats), C.c_char_p,
                                                  C.c_size_t]
     L.scalce_stream_decompress_range.restype = C.c_int
-    rc = L.scalce_stream_decompress_range(ctx.h, C.byref(p), C.byref(rg), C.cast(rd, C.c_void_p), C.cast(user, C.c_void_p), wfn, None,
-                                          C.byref(st), C.byref(rst), msg, len(msg))
+    if comment_readers is not None:
+        rc = _decompress_comments(ctx, p, _unpack_comments(keep, mates, comment_readers), rg, None, rd, user, wfn, st, rst, None, msg)
+    else:
+        rc = L.scalce_stream_decompress_range(ctx.h, C.byref(p), C.byref(rg), C.cast(rd, C.c_void_p), C.cast(user, C.c_void_p), wfn, None,
+                                              C.byref(st), C.byref(rst), msg, len(msg))
     _unpack_check(rc, msg)
     st.range = rst
     return st
@@ -784,6 +817,78 @@ def order_gather(ctx, d_in, d_source, n, d_out, stream=0):
     ctx._check(L.scalce_order_gather(ctx.h, d_in, d_source, int(n), d_out, stream))
 
 
+# ---- what follows the names (archives made with --keep-comments) ------------------------------------------------------------
+COMMENT_HEADER_BYTES = 24  # the 8 magic bytes, int32 0 (text entries), int32 C (longest entry), int64 N; then N entries + newline
+COMMENT_MAX_ENTRY = 65535
+STREAM_KEEP_COMMENTS = 8   # SCALCE_STREAM_KEEP_COMMENTS
+
+
+def pack_comments(entries):
+    """The bytes of a .scalcec stream: header, then every entry (bytes, no newline inside) followed by a newline."""
+    entries = [bytes(e) for e in entries]
+    for e in entries:
+        if b"\n" in e:
+            raise ValueError("an entry of a comment stream holds no newline")
+        if len(e) > COMMENT_MAX_ENTRY:
+            raise ValueError("an entry of a comment stream is at most 65535 bytes long")
+    longest = max((len(e) for e in entries), default=0)
+    return b"scalce22" + struct.pack("<iiq", 0, longest, len(entries)) + b"".join(e + b"\n" for e in entries)
+
+
+def unpack_comments(data):
+    """The entries of the bytes of a .scalcec stream (out of its container); ValueError with the library's message."""
+    data = bytes(data)
+    if len(data) < COMMENT_HEADER_BYTES:
+        raise ValueError("truncated comment stream")
+    width, longest, n = struct.unpack("<iiq", data[8:24])
+    if data[:7] != b"scalce2" or width != 0 or longest < 0 or longest > COMMENT_MAX_ENTRY or n < 0 or n > 0xFFFFFFFF:
+        raise ValueError("is not a scalce comment stream")
+    body = data[COMMENT_HEADER_BYTES:]
+    entries = body.split(b"\n")
+    if entries.pop() != b"" or len(entries) < n:  # (the stream ends inside an entry, or before N entries)
+        raise ValueError("truncated comment stream")
+    if len(entries) != n:
+        raise ValueError(f"comment stream holds {len(entries)} entries, its header says {n}")
+    if any(len(e) > longest for e in entries):
+        raise ValueError("comment stream: an entry is longer than its header says")
+    return entries
+
+
+def fastq_comment_ws_bytes(nrecords, entry_bytes):
+    L = lib()
+    L.scalce_fastq_comment_ws_bytes.argtypes = [C.c_uint64, C.c_uint64]
+    L.scalce_fastq_comment_ws_bytes.restype = C.c_uint64
+    return int(L.scalce_fastq_comment_ws_bytes(int(nrecords), int(entry_bytes)))
+
+
+def fastq_comment_window(ctx, read_len, has_qualities, nrecords, d_text, d_record_offsets, d_entries, entry_bytes, d_out,
+                         d_out_offsets, d_bad, d_ws, stream=0):
+    """scalce_fastq_comment_window: a window's entries back between each name and its newline (device pointers; see the header)."""
+    L = ctx.L
+    L.scalce_fastq_comment_window.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint64] + [C.c_void_p] * 3 + [C.c_uint64] + [C.c_void_p] * 5
+    L.scalce_fastq_comment_window.restype = C.c_int
+    ctx._check(L.scalce_fastq_comment_window(ctx.h, int(read_len), int(bool(has_qualities)), int(nrecords), d_text, d_record_offsets,
+                                             d_entries, int(entry_bytes), d_out, d_out_offsets, d_bad, d_ws, stream))
+
+
+def fastq_comment_pairs_ws_bytes(npairs, entry_bytes):
+    L = lib()
+    L.scalce_fastq_comment_pairs_ws_bytes.argtypes = [C.c_uint64, C.c_uint64]
+    L.scalce_fastq_comment_pairs_ws_bytes.restype = C.c_uint64
+    return int(L.scalce_fastq_comment_pairs_ws_bytes(int(npairs), int(entry_bytes)))
+
+
+def fastq_comment_window_pairs(ctx, read_lens, has_qualities, npairs, d_text, d_pair_offsets, d_name_off2, d_entries, entry_bytes, d_out,
+                               d_out_pair_offsets, d_bad, d_ws, stream=0):
+    """scalce_fastq_comment_window_pairs: the same for an interleaved window, both mates' entries pair by pair (device pointers)."""
+    L = ctx.L
+    L.scalce_fastq_comment_window_pairs.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_uint64] + [C.c_void_p] * 4 + [C.c_uint64] + [C.c_void_p] * 5
+    L.scalce_fastq_comment_window_pairs.restype = C.c_int
+    rl = (C.c_int * 2)(int(read_lens[0]), int(read_lens[1]))
+    ctx._check(L.scalce_fastq_comment_window_pairs(ctx.h, rl, int(bool(has_qualities)), int(npairs), d_text, d_pair_offsets, d_name_off2,
+                                                   d_entries, int(entry_bytes), d_out, d_out_pair_offsets, d_bad, d_ws, stream))
+
+
 class RestoreParams(C.Structure):
     _fields_ = [("order_rd", READ_FN * 2), ("order_user", C.c_void_p * 2), ("spill_dir", C.c_char_p)]
 
@@ -795,7 +900,7 @@ class RestoreStats(C.Structure):
 
 
 def stream_decompress_restore(ctx, readers, order_readers, write, spill_dir, mates=1, interleave=False, no_qualities=False,
-                              mate_digit=None, library=None, split=0, window_text_bytes=0, length_readers=None):
+                              mate_digit=None, library=None, split=0, window_text_bytes=0, length_readers=None, comment_readers=None):
     """scalce_stream_decompress_restore: stream_decompress with the input order restored.  order_readers[m]: the callable
     (cap) -> bytes of the .scalceo stream, read from its start once per mate pass (interleaved: only [0]); write receives
     the text in input order, one stripe per call, first_record = the input index of its first record.  Returns
@@ -823,8 +928,11 @@ def stream_decompress_restore(ctx, readers, order_readers, write, spill_dir, mat
                                                    WRITE_FN, C.c_void_p, C.POINTER(UnpackStats), C.POINTER(RestoreStats), C.c_char_p,
                                                    C.c_size_t]
     L.scalce_stream_decompress_restore.restype = C.c_int
-    rc = L.scalce_stream_decompress_restore(ctx.h, C.byref(p), C.byref(rp), C.cast(rd, C.c_void_p), C.cast(user, C.c_void_p), wfn, None,
-                                            C.byref(st), C.byref(rst), msg, len(msg))
+    if comment_readers is not None:
+        rc = _decompress_comments(ctx, p, _unpack_comments(keep, mates, comment_readers), None, rp, rd, user, wfn, st, None, rst, msg)
+    else:
+        rc = L.scalce_stream_decompress_restore(ctx.h, C.byref(p), C.byref(rp), C.cast(rd, C.c_void_p), C.cast(user, C.c_void_p), wfn, None,
+                                                C.byref(st), C.byref(rst), msg, len(msg))
     _unpack_check(rc, msg)
     st.restore = rst
     return st
@@ -849,7 +957,7 @@ class Batch:
 
     def __init__(self, ctx, read_len, max_reads, max_text, paired=False, use_names=True, no_ac=False, qmap=None,
                  bucket_set_size=0, read_len2=0, qprev=None, workspace=None, fasta=False, no_qualities=False, interleaved=False,
-                 variable_length=False):
+                 variable_length=False, keep_comments=False):
         self.ctx = ctx
         self.L = ctx.L
         p = Params()
@@ -879,6 +987,8 @@ class Batch:
             rc = self.L.scalce_batch_create(ctx.h, C.byref(p), int(max_reads), int(max_text), C.byref(self.h))
         if rc:
             raise ScalceError(f"[{rc}] " + self.L.scalce_last_error(ctx.h).decode())
+        if keep_comments:
+            self.set_keep_comments(True)
 
     def _check(self, rc):
         self.ctx._check(rc)
@@ -903,6 +1013,20 @@ class Batch:
         """OUT_PERM stays valid behind emit() and finish(), lean or not (scalce_batch_set_keep_order)."""
         self.L.scalce_batch_set_keep_order.argtypes = [C.c_void_p, C.c_int]
         self._check(self.L.scalce_batch_set_keep_order(self.h, int(on)))
+
+    def set_keep_comments(self, on=True):
+        """What follows the names becomes OUT_COMMENTS (scalce_batch_set_keep_comments): before the run's first ingest or append."""
+        self.L.scalce_batch_set_keep_comments.argtypes = [C.c_void_p, C.c_int]
+        self.L.scalce_batch_set_keep_comments.restype = C.c_int
+        self._check(self.L.scalce_batch_set_keep_comments(self.h, int(on)))
+
+    def comments_info(self, mate=0):
+        """scalce_batch_comments_info: (bytes of OUT_COMMENTS, longest entry) of `mate`."""
+        self.L.scalce_batch_comments_info.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
+        self.L.scalce_batch_comments_info.restype = C.c_int
+        n, c = C.c_uint64(0), C.c_uint32(0)
+        self._check(self.L.scalce_batch_comments_info(self.h, int(mate), C.byref(n), C.byref(c)))
+        return int(n.value), int(c.value)
 
     def quality(self, stream=0):
         self._check(self.L.scalce_batch_quality(self.h, stream))
