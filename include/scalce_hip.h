@@ -172,6 +172,7 @@ int scalce_batch_reset(scalce_batch *b);
 #define SCALCE_STREAM_DEFER_ENTROPY 2
 #define SCALCE_STREAM_KEEP_ORDER 4  /* scalce_batch_set_keep_order on the run's batch: SCALCE_OUT_PERM outlives the lean releases */
 #define SCALCE_STREAM_KEEP_COMMENTS 8  /* scalce_batch_set_keep_comments on the run's batch: SCALCE_OUT_COMMENTS holds what follows the names */
+#define SCALCE_STREAM_KEEP_BASES 16  /* scalce_batch_set_keep_bases on the run's batch: SCALCE_OUT_EXCEPTIONS holds what the archive does not keep of the bases */
 typedef int64_t (*scalce_read_fn)(void *user, void *dst, uint64_t cap);
 typedef struct {
   double total_s, read_wait_s, h2d_wait_s, front_s, order_s, emit_s, entropy_s;
@@ -202,6 +203,26 @@ int scalce_batch_set_keep_comments(scalce_batch *b, int on);
  * the newline (the C of the .scalcec header); either may be NULL.  Valid behind the ingest of the run's last piece; zero without
  * the option. */
 int scalce_batch_comments_info(const scalce_batch *b, int mate, uint64_t *nbytes, uint32_t *longest);
+/* on = 1: every base letter and the quality under an N become an output of the run (the exception stream of --keep-bases).  The
+ * archive stores a base in two bits: a c g t as A C G T, every other letter as A (getval, const.h:127, const.cpp:47-49); an
+ * upper-case N survives only by forcing quality symbol 0 (qualities.cpp:183), and every symbol 0 comes back as N
+ * (decompress.cpp:350-351).  With the input's letter b and quality character q at a position, values[] / offset the run's
+ * quality map: the stored symbol is s = 0 if b == 'N', else values[q] - offset (runs with qualities only); the letter that comes
+ * back is 'N' if the run has qualities and s == 0, else "ACGT"[getval(b)]; the quality that comes back is offset + s.  The
+ * position is an EXCEPTION when that letter is not b, or when the run has qualities, b == 'N' and values[q] != offset.  (An N with
+ * the offset quality is none.)  Its ENTRY is a u64: bits 0-7 b, bits 8-15 values[q] (0 without qualities), bits 16-27 the
+ * position, bits 28-63 the record's index in archive order (pairs: the pair's; each mate has its own entries).  Every piece's
+ * entries go into a store per mate in input order (a count pass over the text the ingest read, a scan, a write pass), and the
+ * emit stage gathers them through the permutation: SCALCE_OUT_EXCEPTIONS, strictly ascending.  Every other output is what it is
+ * without the option, byte for byte.  Read lengths up to 4095.  To be called before the first ingest or append of a run
+ * (SCALCE_ERR_ARG behind it); one GPU only: scalce_sharded_compress, scalce_batch_rewindow, scalce_batch_text_offset and
+ * scalce_pipeline_create refuse such batches (SCALCE_ERR_ARG).  Off (the default): no kernel of it is launched and no buffer of
+ * it allocated. */
+int scalce_batch_set_keep_bases(scalce_batch *b, int on);
+/* *entries = the u64 entries of SCALCE_OUT_EXCEPTIONS of `mate` (the X of the .scalcex header), *records_with_one = how many of
+ * the mate's records hold at least one; either may be NULL.  Valid behind the ingest of the run's last piece; zero without the
+ * option. */
+int scalce_batch_exceptions_info(const scalce_batch *b, int mate, uint64_t *entries, uint64_t *records_with_one);
 /* Row layout of the batch.  A single-end batch with names keeps ONE row per read -- q' | name cell | packed bases, what the
  * reference keeps per read in its bucket blob (reads.h:52-58, compress.cpp:675-706) -- so that the emit stage reaches
  * everything it reorders through one random access.  on = 0 (before anything is ingested) goes back to separate arrays whose
@@ -362,8 +383,11 @@ enum {
                                mate 1's order, like its reads); valid behind scalce_batch_order; empty for other runs */
   SCALCE_OUT_NAMECELLS = 13,/* for tests: N x 16 bytes, input order: [stored length][the name's first 15 characters, zero behind a
                                shorter name] as the ingest left them; empty with names off, gone once a lean batch has emitted */
-  SCALCE_OUT_COMMENTS = 14  /* scalce_batch_set_keep_comments: what follows the name of the k-th emitted record of mate m, each entry
+  SCALCE_OUT_COMMENTS = 14, /* scalce_batch_set_keep_comments: what follows the name of the k-th emitted record of mate m, each entry
                                followed by a newline (mate 2 in mate 1's order); valid behind scalce_batch_emit, lean or not; empty
+                               without the option */
+  SCALCE_OUT_EXCEPTIONS = 15 /* scalce_batch_set_keep_bases: the u64 entries of mate m in archive order, strictly ascending (letter |
+                               values[q] << 8 | position << 16 | record << 28); valid behind scalce_batch_emit, lean or not; empty
                                without the option */
 };
 int scalce_batch_output(const scalce_batch *b, int which, int mate, const void **d_ptr, uint64_t *nbytes);
@@ -529,6 +553,30 @@ int scalce_fastq_comment_window_pairs(scalce_ctx *ctx, const int read_len[2], in
                                       uint64_t entry_bytes, uint8_t *d_out, uint64_t *d_out_pair_offsets, uint32_t *d_bad, void *d_ws,
                                       void *stream);
 
+/* Archives made with --keep-bases: the entries of the exception stream go back into a window's text, in place (what
+ * decompress.cpp:331-351 cannot give back: lower case, IUPAC letters, the quality under an N, the base under symbol 0).  d_text /
+ * d_record_offsets are what scalce_fastq_records_window wrote (one mate's records; nrecords + 1 offsets; records of read_len
+ * bases, has_qualities = 0 for two-line records), the window holds the archive's records [first_record, first_record + nrecords),
+ * d_entries the nentries u64 entries of those records as the .scalcex file holds them (device memory).  One thread per entry
+ * writes the letter into the sequence line and, with qualities, the quality character into the quality line; both lines are found
+ * from the record's end, so names of any length need nothing.  *d_bad is cleared, then set by an entry whose record lies outside
+ * the window or whose position is not below read_len: such an entry stores nothing.  To be run BEFORE the comments go back, the
+ * pad goes and the order is restored (all three keep the lines' contents).  Enqueued on `stream`; allocates nothing, waits for
+ * nothing. */
+int scalce_fastq_exception_window(scalce_ctx *ctx, int read_len, int has_qualities, uint64_t first_record, uint64_t nrecords,
+                                  uint8_t *d_text, const uint64_t *d_record_offsets, const uint64_t *d_entries, uint64_t nentries,
+                                  uint32_t *d_bad, void *stream);
+/* The same for an interleaved window: npairs pairs from pair first_pair on, mate 1 then mate 2 of each, of read_len[0] /
+ * read_len[1] bases; d_pair_offsets (npairs + 1), d_name_off2 mate 2's name offsets as scalce_fastq_records_window took them, or
+ * NULL for made-up names ("<library>.<index>": library_len = the library name's length, else ignored);
+ * d_entries[m] / nentries[m]: mate m's entries (their record index counts pairs).  d_ws: device scratch of
+ * scalce_fastq_exception_pairs_ws_bytes(npairs) bytes. */
+uint64_t scalce_fastq_exception_pairs_ws_bytes(uint64_t npairs);
+int scalce_fastq_exception_window_pairs(scalce_ctx *ctx, const int read_len[2], int has_qualities, uint64_t first_pair, uint64_t npairs,
+                                        uint8_t *d_text, const uint64_t *d_pair_offsets, const uint64_t *d_name_off2, uint64_t library_len,
+                                        const uint64_t *const d_entries[2], const uint64_t nentries[2], uint32_t *d_bad, void *d_ws,
+                                        void *stream);
+
 /* The read length of a variable-length run and its quality histogram, from the text read ahead for the quality sample -- no
  * device call.  The first `sample` records r with r % stride == first are taken (sample_stats' walk; stride 1, first 0 for
  * a text of one mate): *read_len = the longest sequence line among them, or max_length when that is > 0 (--max-length);
@@ -581,7 +629,7 @@ typedef struct {
   double total_s, setup_s, read_wait_s, decode_s, records_s, write_wait_s, write_s;
                                /* read_wait: in rd; decode / records: device time of the kernels; write_wait: the session
                                   waiting for a window buffer that wr still holds; write: inside wr */
-  int32_t error_mate, error_stream;  /* on failure: which stream of which mate (0 r, 1 n, 2 q, 3 l, 4 o, 5 c), or -1 */
+  int32_t error_mate, error_stream;  /* on failure: which stream of which mate (0 r, 1 n, 2 q, 3 l, 4 o, 5 c, 6 x), or -1 */
   int32_t error_wants_file;    /* the message in errbuf is a predicate: put the stream's file name in front of it */
   uint64_t decode_batches[2];  /* per mate: decoder batches enqueued (runs of whole frames, one scalce_ac_decoder_launch each) */
 } scalce_unpack_stats;
@@ -715,6 +763,32 @@ int scalce_stream_decompress_comments(scalce_ctx *ctx, const scalce_unpack_param
                                       scalce_read_fn rd[2][3], void *user[2][3], scalce_write_fn wr, void *wr_user,
                                       scalce_unpack_stats *stats, scalce_unpack_range_stats *range_stats,
                                       scalce_restore_stats *restore_stats, char *errbuf, size_t errcap);
+
+/* ---- the letters and qualities the archive does not keep, back on the way out (archives made with --keep-bases; exceptionstream.hpp,
+ * kernels_exceptions.hpp) -----
+ * The exception stream (PREFIX_<m>.scalcex out of its container), one per mate: the 8 magic bytes, int32 8 (entry width), int32 L,
+ * int64 N (records), int64 X (entries), then X little-endian u64 in strictly ascending order: SCALCE_OUT_EXCEPTIONS (bits 0-7 the
+ * letter, 8-15 the quality character, 16-27 the position, 28-63 the record's index in archive order; pairs: the pair's index, each
+ * mate in its own stream with its own L).  What it undoes: getval stores a c g t as A C G T and every other letter as A (const.h:127,
+ * const.cpp:47-49), an N forces quality symbol 0 (qualities.cpp:183) and every symbol 0 comes back as N (decompress.cpp:350-351).
+ * exc_rd[m] delivers mate m's, header included; both NULL: no exceptions.  Each window takes the entries of its records over the
+ * callback -- a range passes over those in front of it and reads none behind it, memory follows the window's entries -- and they go
+ * back on the device (scalce_fastq_exception_window) directly behind the records kernel: before the comments go back, the pad goes
+ * and the order restore groups the window.  Without qualities on the way out (-Q) only the letters are written.
+ * scalce_stream_decompress_exceptions is scalce_stream_decompress_comments with the exception streams beside the comment streams;
+ * either may be NULL, range and rp as there.  Every mate has its stream (else SCALCE_ERR_ARG).  Errors besides theirs: "(ERROR)
+ * truncated exception stream", "(ERROR) is not a scalce exception stream", "(ERROR) exception stream holds <n> records, the archive
+ * <m>", "(ERROR) exception stream is for reads of <l> bases, the archive's have <L>", "(ERROR) exception stream: entries are not in
+ * ascending order", "(ERROR) exception stream: an entry lies outside its record"; error_stream 6 names the exception stream. */
+typedef struct {
+  scalce_read_fn exc_rd[2];
+  void *exc_user[2];
+} scalce_unpack_exceptions;
+int scalce_stream_decompress_exceptions(scalce_ctx *ctx, const scalce_unpack_params *p, const scalce_unpack_comments *comments /* NULL: none */,
+                                        const scalce_unpack_exceptions *exceptions /* NULL: none */, const scalce_unpack_range *range /* NULL: all */,
+                                        const scalce_restore_params *rp /* NULL: archive order */, scalce_read_fn rd[2][3], void *user[2][3],
+                                        scalce_write_fn wr, void *wr_user, scalce_unpack_stats *stats, scalce_unpack_range_stats *range_stats,
+                                        scalce_restore_stats *restore_stats, char *errbuf, size_t errcap);
 
 /* ---- runs sharded over several GPUs: one process per GPU, ONE archive -----------------------------------------
  * The reference has no distributed mode; what it carries across reads is what ranks exchange (see comm.cpp).  The

@@ -33,9 +33,9 @@ __attribute__((format(printf, 6, 7))) inline int failure(Failure &f, int rc, int
   f.rc = rc; f.msg = b; f.mate = mate; f.stream = stream; f.wants_file = wants_file;
   return rc;
 }
-// a stream that ends, or fails, before what is asked of it (stream: 0 r, 1 n, 2 q, 3 l, 4 o, 5 c)
+// a stream that ends, or fails, before what is asked of it (stream: 0 r, 1 n, 2 q, 3 l, 4 o, 5 c, 6 x)
 inline const char *stream_name(int stream) {
-  return stream == 0 ? "read" : stream == 1 ? "name" : stream == 2 ? "quality" : stream == 3 ? "length" : stream == 5 ? "comment" : "order";
+  return stream == 0 ? "read" : stream == 1 ? "name" : stream == 2 ? "quality" : stream == 3 ? "length" : stream == 5 ? "comment" : stream == 6 ? "exception" : "order";
 }
 inline int read_error(Failure &f, int m, int stream) { return failure(f, SCALCE_ERR_FORMAT, m, stream, 0, "read error on the %s stream", stream_name(stream)); }
 inline int truncated(Failure &f, int m, int stream) { return failure(f, SCALCE_ERR_FORMAT, m, stream, 0, "(ERROR) truncated %s stream", stream_name(stream)); }

@@ -32,6 +32,7 @@
 #include "cli_shares.hpp"
 #include "cli_sink.hpp"
 #include "cli_comments.hpp"
+#include "cli_exceptions.hpp"
 
 #ifndef SCALCE_VERSION
 #define SCALCE_VERSION "2.8-mi355x"
@@ -54,6 +55,8 @@ struct Options {
   bool archive_order = false;             // -d --archive-order: a .scalceo next to the archive is ignored
   bool keep_comments = false;             // --keep-comments: what follows every record's name, in PREFIX_<m>.scalcec
   bool no_comments = false;               // -d --no-comments: a .scalcec next to the archive is ignored
+  bool keep_bases = false;                // --keep-bases: every letter and quality the archive does not keep, in PREFIX_<m>.scalcex
+  bool stored_bases = false;              // -d --stored-bases: a .scalcex next to the archive is ignored
   bool temp_given = false;                // -t was given (the default of `temp` is the reference's)
   int gpus = 1;                           // --gpus N: one process per GPU, ONE archive (plain-text input, -c no)
   int container = 1;                      // 0 plain, 1 gzip (main.cpp:181-184 at -T 1)
@@ -90,6 +93,12 @@ static const char *HELP_TEXT =
     "                              without the option writes.  Decompression finds the .scalcec by itself and puts the comments\n"
     "                              back; the '+' line stays a bare '+'.  Not with -n, --gpus\n"
     "      --no-comments           decompression: ignore the .scalcec, write the names alone\n"
+    "      --keep-bases            keep every base letter and the quality under an N: the archive stores a c g t as A C G T, every\n"
+    "                              other letter as A, an N only through its quality, and returns a base whose quality maps to the\n"
+    "                              lowest as N.  What it changes goes into OUTPUT_<m>.scalcex, every other file is the one the\n"
+    "                              run without the option writes.  Decompression finds the .scalcex by itself and puts the letters\n"
+    "                              and qualities back.  Not with --gpus\n"
+    "      --stored-bases          decompression: ignore the .scalcex, write the bases as the archive stores them\n"
     "  -p, --lossy-percentage INT  lossy quality transform, 0..100 (default 0)\n"
     "  -s, --sample-size INT       records sampled for the quality model (default 100000)\n"
     "  -B, --bucket-set-size NUM[M|G]  bucket storage that triggers a spill chunk (default 4G); order follows the reference\n"
@@ -122,6 +131,8 @@ static const char *HELP_TEXT =
 //                       k-th record (pair) of the archive; one file for both mates
 //   PREFIX_<m>.scalcec  --keep-comments only (commentstream.hpp): magic, int32 0, int32 C (longest entry), int64 N, then what follows
 //                       the name of each record of the archive, from the first space on, each entry followed by a newline
+//   PREFIX_<m>.scalcex  --keep-bases only (exceptionstream.hpp): magic, int32 8, int32 L, int64 N, int64 X, then X x u64 in ascending
+//                       order: letter | quality character << 8 | position << 16 | record of the archive << 28
 //   PREFIX_<m>.scalceq  magic, int64 Phred offset (mate 1's for both mates, compress.cpp:294,816-817); arithmetic coded:
 //                       the scaled table (QTABLE_WORDS x u32), the int64 symbol count and the coded blocks; -A: the q' rows
 static const uint8_t MAGIC[8] = {'s', 'c', 'a', 'l', 'c', 'e', '2', '2'};
@@ -360,6 +371,15 @@ struct MateFiles {
     down.to_file(ctx, b, SCALCE_OUT_COMMENTS, m, fC);
     fC.close();
   }
+  void write_exceptions(int m, Downloader &down, uint64_t N) const {  // --keep-bases: what the archive does not keep, in archive order
+    OutFile fX;
+    fX.open(archive_path(o.out, m, 'x'), gz_container(o, 'x'));
+    uint64_t entries = 0;
+    SCOK(ctx, scalce_batch_exceptions_info(b, m, &entries, nullptr));
+    exception_file_header(fX, (uint32_t)p.read_len[m], N, entries);
+    down.to_file(ctx, b, SCALCE_OUT_EXCEPTIONS, m, fX);
+    fX.close();
+  }
   void write_qualities(int m, Downloader &down, uint64_t N) const {  // once the coder is through; N: records of the run
     OutFile fQ;
     fQ.open(archive_path(o.out, m, 'q'), gz_container(o, 'q'));
@@ -424,7 +444,7 @@ static int do_compress(const Options &o, const std::vector<std::string> &files, 
   const double t1 = now();
   if (scalce_stream_compress(ctx, &p, MateSource::read_cb, &in.src[0], nsrc == 2 ? MateSource::read_cb : nullptr, nsrc == 2 ? &in.src[1] : nullptr,
                              piece, hint, SCALCE_STREAM_LEAN | SCALCE_STREAM_DEFER_ENTROPY | (o.keep_order ? SCALCE_STREAM_KEEP_ORDER : 0) |
-                                 (o.keep_comments ? SCALCE_STREAM_KEEP_COMMENTS : 0), &b, &ss, emsg, sizeof emsg)) {
+                                 (o.keep_comments ? SCALCE_STREAM_KEEP_COMMENTS : 0) | (o.keep_bases ? SCALCE_STREAM_KEEP_BASES : 0), &b, &ss, emsg, sizeof emsg)) {
     if (!in.src[0].error.empty()) fputs(in.src[0].error.c_str(), stderr);  // (-i: a file of odd record count; the stream only saw a read error)
     else fprintf(stderr, "%s\n", emsg[0] ? emsg : scalce_last_error(ctx));
     exit(1);
@@ -456,10 +476,12 @@ static int do_compress(const Options &o, const std::vector<std::string> &files, 
     if (o.varlen) w.write_lengths(m);
     if (o.keep_order && m == 0) w.write_order();
     if (o.keep_comments) w.write_comments(m, *downs[m], N);
+    if (o.keep_bases) w.write_exceptions(m, *downs[m], N);
   });
   // (an order stream left under this prefix by an earlier run does not belong to this archive, nor do comment streams)
   if (!o.keep_order) unlink(archive_path(o.out, 0, 'o').c_str());
   if (!o.keep_comments) for_each_archive_file(o, "c", [](char, const std::string &fn) { unlink(fn.c_str()); });
+  if (!o.keep_bases) for_each_archive_file(o, "x", [](char, const std::string &fn) { unlink(fn.c_str()); });
   const double t2b = now();
   SCOK(ctx, scalce_batch_finish(b, s_ent));  // the coder is through: sizes of the coded streams, device error word
   const double t2c = now();
@@ -469,7 +491,7 @@ static int do_compress(const Options &o, const std::vector<std::string> &files, 
   });
   const double t2d = now();
   uint64_t new_size = 0;
-  const std::string exts = std::string("rnql") + (o.keep_order ? "o" : "") + (o.keep_comments ? "c" : "");
+  const std::string exts = std::string("rnql") + (o.keep_order ? "o" : "") + (o.keep_comments ? "c" : "") + (o.keep_bases ? "x" : "");
   for_each_archive_file(o, exts.c_str(), [&](char, const std::string &fn) {
     struct stat st;
     if (stat(fn.c_str(), &st) == 0) new_size += (uint64_t)st.st_size;
@@ -483,9 +505,12 @@ static int do_compress(const Options &o, const std::vector<std::string> &files, 
   uint64_t com_bytes[2] = {0, 0};
   uint32_t com_longest[2] = {0, 0};
   for (int m = 0; m < nm && o.keep_comments; m++) SCOK(ctx, scalce_batch_comments_info(b, m, &com_bytes[m], &com_longest[m]));
+  uint64_t exc_entries[2] = {0, 0}, exc_rows[2] = {0, 0};
+  for (int m = 0; m < nm && o.keep_bases; m++) SCOK(ctx, scalce_batch_exceptions_info(b, m, &exc_entries[m], &exc_rows[m]));
   scalce_batch_destroy(b);
   const double t3 = now();
   log_statistics(o, p, N, unbucketed);
+  for (int m = 0; m < nm && o.keep_bases; m++) exception_log(N, exc_entries[m], exc_rows[m]);
   for (int m = 0; m < nm && o.keep_comments; m++) comment_log(N, com_bytes[m], com_longest[m]);
   LOG("\tSpill chunks: %u, pieces streamed: %llu\n", st4[3], (unsigned long long)ss.rounds);
   LOG("\tTime elapsed: %.2f s (sample %.2f; stream %.2f = waiting for the reader %.2f + for uploads %.2f + ingest/count/tokenize %.2f; "
@@ -862,6 +887,8 @@ struct Archive {
   bool has_order = false;  // a PREFIX_1.scalceo lies next to the .scalcen (and --archive-order does not set it aside)
   bool has_comments = false;  // every mate has a PREFIX_<m>.scalcec next to its .scalcen (and neither --no-comments nor -n sets them aside)
   ArchiveFile comments[2];
+  bool has_exceptions = false;  // every mate has a PREFIX_<m>.scalcex next to its .scalcen (and --stored-bases does not set them aside)
+  ArchiveFile exceptions[2];
   ArchiveFile files[2][3], lens[2], order[2];  // (a mate pass reads the order stream from its start: one handle each)
   scalce_read_fn rd[2][3];
   void *user[2][3];
@@ -895,6 +922,10 @@ struct Archive {
     has_comments = !o.no_comments && o.use_names;
     for (int m = 0; m < nm && has_comments; m++) has_comments = comment_file_present(scalce_name(base[m], 'c'));
     for (int m = 0; m < nm && has_comments; m++) comments[m].open(scalce_name(base[m], 'c'));
+    // what the archive does not keep of the bases: put back when every mate has its stream
+    has_exceptions = !o.stored_bases;
+    for (int m = 0; m < nm && has_exceptions; m++) has_exceptions = exception_file_present(scalce_name(base[m], 'x'));
+    for (int m = 0; m < nm && has_exceptions; m++) exceptions[m].open(scalce_name(base[m], 'x'));
   }
 };
 // One path for every archive: scalce_stream_decompress moves it through the device in windows of whole records.  The read
@@ -916,6 +947,12 @@ static int do_decompress(const Options &o, const std::string &path, scalce_ctx *
   scalce_unpack_comments cm;
   memset(&cm, 0, sizeof cm);
   for (int m = 0; m < nm && ar.has_comments; m++) { cm.com_rd[m] = ArchiveFile::read; cm.com_user[m] = &ar.comments[m]; }
+  scalce_unpack_exceptions ex;
+  memset(&ex, 0, sizeof ex);
+  for (int m = 0; m < nm && ar.has_exceptions; m++) { ex.exc_rd[m] = ArchiveFile::read; ex.exc_user[m] = &ar.exceptions[m]; }
+  const scalce_unpack_comments *cmp = ar.has_comments ? &cm : nullptr;
+  const scalce_unpack_exceptions *exp = ar.has_exceptions ? &ex : nullptr;
+  const bool side = ar.has_comments || ar.has_exceptions;
   if (ar.has_order) {  // the input order back: two passes through a spill under -t, next to the output, or in $TMPDIR
     scalce_restore_params rp;
     memset(&rp, 0, sizeof rp);
@@ -932,16 +969,18 @@ static int do_decompress(const Options &o, const std::string &path, scalce_ctx *
     }
     rp.spill_dir = spill_dir.c_str();
     memset(&rs, 0, sizeof rs);
-    rc = ar.has_comments ? scalce_stream_decompress_comments(ctx, &p, &cm, nullptr, &rp, ar.rd, ar.user, TextSink::write, &sink, &st, nullptr, &os, err, sizeof err)
-                         : scalce_stream_decompress_restore(ctx, &p, &rp, ar.rd, ar.user, TextSink::write, &sink, &st, &os, err, sizeof err);
-  } else if (ar.has_comments)
-    rc = scalce_stream_decompress_comments(ctx, &p, &cm, &rg, nullptr, ar.rd, ar.user, TextSink::write, &sink, &st, &rs, nullptr, err, sizeof err);
-  else
-    rc = scalce_stream_decompress_range(ctx, &p, &rg, ar.rd, ar.user, TextSink::write, &sink, &st, &rs, err, sizeof err);
+    // (side streams: the one entry point that takes comments and exceptions, either or both; else the call as it always was)
+    rc = side ? scalce_stream_decompress_exceptions(ctx, &p, cmp, exp, nullptr, &rp, ar.rd, ar.user, TextSink::write, &sink, &st, nullptr, &os, err, sizeof err)
+              : scalce_stream_decompress_restore(ctx, &p, &rp, ar.rd, ar.user, TextSink::write, &sink, &st, &os, err, sizeof err);
+  } else
+    rc = side ? scalce_stream_decompress_exceptions(ctx, &p, cmp, exp, &rg, nullptr, ar.rd, ar.user, TextSink::write, &sink, &st, &rs, nullptr, err, sizeof err)
+              : scalce_stream_decompress_range(ctx, &p, &rg, ar.rd, ar.user, TextSink::write, &sink, &st, &rs, err, sizeof err);
   if (rc) {
     // (parts already written stay where they are)
     if (st.error_stream == 5 && st.error_mate >= 0 && !strncmp(err, "(ERROR) is not", 14))  // (a predicate about the comment stream's file)
       FAIL("%s %s\n", ar.comments[st.error_mate].path.c_str(), err + 8);
+    if (st.error_stream == 6 && st.error_mate >= 0 && !strncmp(err, "(ERROR) is not", 14))  // (... about the exception stream's)
+      FAIL("%s %s\n", ar.exceptions[st.error_mate].path.c_str(), err + 8);
     if (st.error_wants_file && st.error_mate >= 0 && st.error_stream >= 0 && st.error_stream < 3)
       FAIL("%s %s\n", st.error_stream == 0 ? ar.base[st.error_mate].c_str() : ar.files[st.error_mate][st.error_stream].path.c_str(), err);
     fprintf(stderr, "%s%s\n", strncmp(err, "(ERROR)", 7) ? "(ERROR) " : "", err);
@@ -1010,7 +1049,8 @@ static bool parse_options(int argc, char **argv, Options &o) {
                                      {"records", 1, 0, 1003}, {"variable-length", 0, 0, 1004},
                                      {"max-length", 1, 0, 1005}, {"keep-order", 0, 0, 1006},
                                      {"archive-order", 0, 0, 1007}, {"keep-comments", 0, 0, 1008},
-                                     {"no-comments", 0, 0, 1009}, {0, 0, 0, 0}};
+                                     {"no-comments", 0, 0, 1009}, {"keep-bases", 0, 0, 1010},
+                                     {"stored-bases", 0, 0, 1011}, {0, 0, 0, 0}};
   int opt;
   while ((opt = getopt_long(argc, argv, "vhp:T:dc:o:fs:t:B:rQAn:P:S:i", long_opt, 0)) != -1) {
     switch (opt) {
@@ -1051,6 +1091,8 @@ static bool parse_options(int argc, char **argv, Options &o) {
       case 1007: o.archive_order = true; break;
       case 1008: o.keep_comments = true; break;
       case 1009: o.no_comments = true; break;
+      case 1010: o.keep_bases = true; break;
+      case 1011: o.stored_bases = true; break;
       default: fputs(HELP_TEXT, stdout); return false;
     }
   }
@@ -1069,6 +1111,9 @@ static void check_arguments(const Options &o, const std::vector<std::string> &fi
   if (o.no_comments && !o.decompress) FAIL("--no-comments can be only used with decompression (-d).\n");
   if (o.keep_comments && !o.use_names) FAIL("--keep-comments with -n: nothing is kept for what follows a name that is not kept\n");
   if (o.keep_comments && o.gpus > 1) FAIL("--keep-comments runs on one GPU: with --gpus %d the comments lie spread over the ranks\n", o.gpus);
+  if (o.keep_bases && o.decompress) FAIL("--keep-bases is an option of compression: -d puts the bases back by itself when the archive has a .scalcex\n");
+  if (o.stored_bases && !o.decompress) FAIL("--stored-bases can be only used with decompression (-d).\n");
+  if (o.keep_bases && o.gpus > 1) FAIL("--keep-bases runs on one GPU: with --gpus %d the exceptions lie spread over the ranks\n", o.gpus);
   if (o.decompress && files.size() > 1) FAIL("Too many files specified (decompression only supports one file).\n");
   if (o.lossy < 0 || o.lossy > 100) FAIL("Percentage must be in range [0,100].\n");
   if (o.out == "-" && (o.split || o.paired)) FAIL("stdout can be only used with single-end file decompression. It cannot be used with --split-reads option!\n");

@@ -455,3 +455,57 @@ extern "C" int scalce_fastq_comment_window_pairs(scalce_ctx *c, const int read_l
   LAUNCH(pair_offsets_k, cdiv(npairs + 1, 256), 256, 0, s, npairs, new_off, reinterpret_cast<u64 *>(d_out_pair_offsets));
   return launch_failed(c);
 }
+
+// ---- the letters and qualities the archive does not keep, back in a window's text (archives made with --keep-bases) ---------
+static int exception_apply(scalce_ctx *c, u8 *d_text, const u64 *rec_off, u32 stride, u32 which, u64 first, u64 nunits, int read_len,
+                           int has_qualities, const uint64_t *d_entries, uint64_t nentries, uint32_t *d_bad, hipStream_t s) {
+  if (!nentries) return SCALCE_OK;
+  ExcApplyArgs a;
+  a.text = d_text; a.rec_off = rec_off; a.stride = stride; a.which = which; a.first = first; a.nunits = nunits;
+  a.entries = reinterpret_cast<const u64 *>(d_entries); a.nent = nentries;
+  a.L = (u32)read_len; a.has_q = has_qualities ? 1u : 0u; a.bad = d_bad;
+  LAUNCH(exc_apply_k, cdiv(nentries, 256), 256, 0, s, a);
+  return SCALCE_OK;
+}
+static bool exception_args_ok(int read_len, uint64_t n, uint64_t nentries, const void *d_text, const void *d_off, const void *d_entries) {
+  return read_len > 0 && read_len < (1 << EXC_POS_BITS) && n <= 0xFFFFFFFFull && (!nentries || (d_text && d_off && d_entries && n));
+}
+extern "C" int scalce_fastq_exception_window(scalce_ctx *c, int read_len, int has_qualities, uint64_t first_record, uint64_t nrecords,
+                                             uint8_t *d_text, const uint64_t *d_record_offsets, const uint64_t *d_entries, uint64_t nentries,
+                                             uint32_t *d_bad, void *stream) {
+  if (!c || !d_bad || !exception_args_ok(read_len, nrecords, nentries, d_text, d_record_offsets, d_entries)) return SCALCE_ERR_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, hipMemsetAsync(d_bad, 0, sizeof(u32), s));
+  { int rc = exception_apply(c, d_text, reinterpret_cast<const u64 *>(d_record_offsets), 1, 0, first_record, nrecords, read_len, has_qualities,
+                             d_entries, nentries, d_bad, s); if (rc) return rc; }
+  return launch_failed(c);
+}
+// The same for an interleaved window: npairs pairs, mate 1 then mate 2 of each; mate m's entries count pairs.  The records'
+// own offsets are made from the pairs' and mate 2's name offsets (pair_split_k), then each mate's entries go to its records.
+extern "C" uint64_t scalce_fastq_exception_pairs_ws_bytes(uint64_t npairs) { return sizeof(u64) * (2 * npairs + 8); }
+extern "C" int scalce_fastq_exception_window_pairs(scalce_ctx *c, const int read_len[2], int has_qualities, uint64_t first_pair, uint64_t npairs,
+                                                   uint8_t *d_text, const uint64_t *d_pair_offsets, const uint64_t *d_name_off2, uint64_t library_len,
+                                                   const uint64_t *const d_entries[2], const uint64_t nentries[2], uint32_t *d_bad, void *d_ws,
+                                                   void *stream) {
+  if (!c || !d_bad || !read_len || !d_entries || !nentries || !d_ws || npairs > 0x7FFFFFFFull) return SCALCE_ERR_ARG;
+  for (int m = 0; m < 2; m++)
+    if (!exception_args_ok(read_len[m], npairs, nentries[m], d_text, d_pair_offsets, d_entries[m])) return SCALCE_ERR_ARG;
+  if (!d_name_off2 && library_len > 255) { set_err(c, "exceptions: a library name is at most 255 characters long"); return SCALCE_ERR_ARG; }
+  hipStream_t s = (hipStream_t)stream;
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, hipMemsetAsync(d_bad, 0, sizeof(u32), s));
+  if (!npairs) return SCALCE_OK;
+  u64 *rec_off = static_cast<u64 *>(d_ws);
+  if (d_name_off2)
+    LAUNCH(pair_split_k, cdiv(npairs + 1, 256), 256, 0, s, npairs, reinterpret_cast<const u64 *>(d_pair_offsets), reinterpret_cast<const u64 *>(d_name_off2),
+           comment_tail(read_len[1], has_qualities), rec_off);
+  else  // made-up names: "<library>.<index>"
+    LAUNCH(pair_split_lib_k, cdiv(npairs + 1, 256), 256, 0, s, npairs, reinterpret_cast<const u64 *>(d_pair_offsets), first_pair, (u32)library_len,
+           comment_tail(read_len[1], has_qualities), rec_off);
+  for (u32 m = 0; m < 2; m++) {
+    int rc = exception_apply(c, d_text, rec_off, 2, m, first_pair, npairs, read_len[m], has_qualities, d_entries[m], nentries[m], d_bad, s);
+    if (rc) return rc;
+  }
+  return launch_failed(c);
+}

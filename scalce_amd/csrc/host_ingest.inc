@@ -76,6 +76,54 @@ static int piece_comments(scalce_batch *b, int mate, const u8 *d_text, u64 nbyte
   return SCALCE_OK;
 }
 
+// --keep-bases: the exceptions of the piece's first `nrec` rows (kernels_exceptions.hpp) go behind mate m's entries of earlier
+// pieces (exc_in[m], input order); exc_cnt[m] keeps the count per row.  Runs behind the rows' own ingest, from the piece's line
+// index and over the text the ingest read: a count pass, one exclusive scan and, when the piece has any, a write pass.
+// `mate`: the text's; an interleaved text (mate 0's) serves both mates.
+static int piece_exceptions(scalce_batch *b, int mate, const u8 *d_text, u64 nbytes, u64 nrec, hipStream_t s) {
+  scalce_workspace &w = *b->ws;
+  { int rc = ensure_line_index(b, mate, s); if (rc) return rc; }
+  const u32 nblocks = cdiv(nrec, EXC_ROWS);
+  ENSURE(b, b->exc_piece_off, sizeof(u64) * (nrec + 8) + sizeof(u32) * ((size_t)nblocks + 8));  // (offsets, total, rows; the workgroups' rows)
+  ENSURE(b, w.scan_ws, sizeof(u64) * (scan_ws_elems(nrec) + 64));
+  for (int m = mate; m < (b->il ? 2 : mate + 1); m++) {
+    const u64 rows = std::max<u64>(w.row_cap, b->base + nrec);
+    { int rc = ensure_keep(b, b->exc_cnt[m], sizeof(u16) * (rows + 64), sizeof(u16) * b->base, s); if (rc) return rc; }
+    ExcArgs a;
+    a.text = d_text; a.nbytes = nbytes; a.line_end = w.line_end[mate].as<u64>();
+    a.lpr = (u32)b->lpr; a.unit_recs = b->il ? 2u : 1u; a.rec0 = m == mate ? 0u : 1u;
+    a.L = (u32)b->L[m];
+    a.has_q = b->nq ? 0u : 1u;
+    a.q_affine = b->nq ? -1 : b->q_affine[m];
+    a.qzero[0] = a.qzero[1] = 0;
+    a.qzero_end = 0;
+    for (int i = 0; i < 128 && !b->nq; i++)
+      if (b->p.qmap[m].values[i] == b->p.qmap[m].offset) { a.qzero[i >> 6] |= 1ull << (i & 63); a.qzero_end = (u32)i + 1; }
+    a.qlut = b->nq ? nullptr : b->d_qlut[m];
+    a.qoffset = b->nq ? 0u : (u32)b->p.qmap[m].offset & 255u;
+    a.padlen = b->vl ? w.padlen[m].as<u16>() + b->base : nullptr;
+    a.nrec = nrec;
+    a.count = b->exc_cnt[m].as<u16>() + b->base;
+    a.off = b->exc_piece_off.as<u64>();
+    a.dst = nullptr;
+    a.rows_with = reinterpret_cast<u32 *>(b->exc_piece_off.as<u64>() + nrec + 8);
+    LAUNCH(exc_count_k, nblocks, 256, 0, s, a);
+    exclusive_scan<u64>(ExcCount{a.count}, nrec, StoreTo<u64>{b->exc_piece_off.as<u64>()}, w.scan_ws.as<u64>(), b->exc_piece_off.as<u64>() + nrec, s);
+    // (the rows that hold one: the sum of the workgroups' counts, into the word behind the total -- read back with it)
+    exclusive_scan<u64>(LoadAs<u32, u64>{a.rows_with}, nblocks, ExcNoStore{}, w.scan_ws.as<u64>(), b->exc_piece_off.as<u64>() + nrec + 1, s);
+    u64 back[2] = {0, 0};  // the piece's entries, its rows that hold one
+    { int rc = read_u64(b, a.off + nrec, back, 2, s); if (rc) return rc; }
+    const u64 total = back[0];
+    b->exc_rows[m] += back[1];
+    if (!total) continue;
+    { int rc = ensure_keep(b, b->exc_in[m], sizeof(u64) * (b->exc_used[m] + total + 8), sizeof(u64) * b->exc_used[m], s); if (rc) return rc; }
+    a.dst = b->exc_in[m].as<u64>() + b->exc_used[m];
+    LAUNCH(exc_write_k, cdiv(nrec, EXC_ROWS), 256, 0, s, a);
+    b->exc_used[m] += total;
+  }
+  return SCALCE_OK;
+}
+
 // the first `nrec` records of the text -> rows [base, base + nrec): 2-bit bases, q', names
 // (A one-pass variant -- no count pass, the tiles' line bases by decoupled look-back between the workgroups -- was byte-exact
 // and slower: 9.2 ms against 1.7 + 6.2 at 50 M x 100 bp, rounds 3-4; removed in round 5.)
@@ -214,6 +262,7 @@ static int piece_unpack_t(scalce_batch *b, int mate, const u8 *d_text, u64 nbyte
     }
   }
   if (b->keep_comments) { int rc = piece_comments(b, mate, d_text, nbytes, nrec, s); if (rc) return rc; }
+  if (b->keep_bases) { int rc = piece_exceptions(b, mate, d_text, nbytes, nrec, s); if (rc) return rc; }
   b->ingest_plan[mate][2] = b->line_index_ok[mate] ? 1u : 0u;
   if (IL)  // (one text, one line index, mate 1's names: mate 2 reports what mate 1 does, and the kernel that wrote its own rows)
     for (int i = 1; i < 4; i++) b->ingest_plan[mate + 1][i] = b->ingest_plan[mate][i];
@@ -293,6 +342,7 @@ static void batch_restart(scalce_batch *b) {
   b->appending = false;
   b->names_in_used = 0;
   for (int m = 0; m < 2; m++) b->com_used[m] = b->out_comments_bytes[m] = b->com_longest[m] = 0;
+  for (int m = 0; m < 2; m++) b->exc_used[m] = b->exc_rows[m] = b->out_exc_entries[m] = 0;
   b->tri_expected[0] = b->tri_expected[1] = 0;
   b->ingested[0] = b->ingested[1] = false;
   for (int m = 0; m < 2; m++)
@@ -418,7 +468,7 @@ static int not_whole_records(scalce_ctx *c, const char *which) {
 // ingest starts it over.
 extern "C" int scalce_batch_rewindow(scalce_batch *b, uint64_t keep_first, uint64_t keep_rows, const uint8_t *const front[2],
                                      const uint64_t front_bytes[2], const uint8_t *const back[2], const uint64_t back_bytes[2], void *stream) {
-  if (!b || !front || !back || !front_bytes || !back_bytes || keep_first + keep_rows > b->N || b->il || b->vl || b->keep_comments) return SCALCE_ERR_ARG;
+  if (!b || !front || !back || !front_bytes || !back_bytes || keep_first + keep_rows > b->N || b->il || b->vl || b->keep_comments || b->keep_bases) return SCALCE_ERR_ARG;
   scalce_ctx *c = b->ctx;
   hipStream_t s = (hipStream_t)stream;
   HIP_TRY(c, hipSetDevice(c->device));
@@ -527,6 +577,22 @@ extern "C" int scalce_batch_comments_info(const scalce_batch *b, int mate, uint6
   if (!b || mate < 0 || mate >= b->nm) return SCALCE_ERR_ARG;
   if (nbytes) *nbytes = b->keep_comments ? b->com_used[mate] : 0;
   if (longest) *longest = b->keep_comments ? b->com_longest[mate] : 0;
+  return SCALCE_OK;
+}
+// the letters and qualities the archive does not keep become an output of the run (SCALCE_OUT_EXCEPTIONS): before the first
+// ingest or append of the run
+extern "C" int scalce_batch_set_keep_bases(scalce_batch *b, int on) {
+  if (!b) return SCALCE_ERR_ARG;
+  if (b->N || b->appending || b->ingested[0]) { set_err(b->ctx, "keep-bases is set before the first ingest or append of a run"); return SCALCE_ERR_ARG; }
+  b->keep_bases = on != 0;
+  return SCALCE_OK;
+}
+// (for the other translation units of the library: sharded.cpp, pipeline.cpp)
+bool scalce_batch_keeps_bases(const scalce_batch *b) { return b && b->keep_bases; }
+extern "C" int scalce_batch_exceptions_info(const scalce_batch *b, int mate, uint64_t *entries, uint64_t *records_with_one) {
+  if (!b || mate < 0 || mate >= b->nm) return SCALCE_ERR_ARG;
+  if (entries) *entries = b->keep_bases ? b->exc_used[mate] : 0;
+  if (records_with_one) *records_with_one = b->keep_bases ? b->exc_rows[mate] : 0;
   return SCALCE_OK;
 }
 extern "C" uint64_t scalce_batch_reruns(const scalce_batch *b) { return b ? b->reruns : 0; }

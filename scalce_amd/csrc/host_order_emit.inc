@@ -289,6 +289,37 @@ extern "C" int scalce_batch_emit(scalce_batch *b, void *stream) {
       b->comlen[m].release();
     }
   }
+  // the exceptions, in archive order: the entries of output record k are those of input record perm[k], with k stamped in --
+  // two scans of the rows' counts (input order for the store's offsets, permuted for the stream's) and one gather
+  if (b->keep_bases && N >= EXC_MAX_RECORDS) {  // (36 bits of an entry name its record)
+    set_err(c, "(ERROR) --keep-bases: %llu records are more than the 2^36 - 1 an exception stream can name", (unsigned long long)N);
+    return SCALCE_ERR_CAPACITY;
+  }
+  for (int m = 0; m < b->nm && b->keep_bases; m++) {
+    b->out_exc_entries[m] = N ? b->exc_used[m] : 0;
+    if (!N || !b->exc_used[m]) {
+      if (b->lean) { HIP_TRY(c, hipStreamSynchronize(s)); b->exc_in[m].release(); }  // (a store an earlier run of the batch left)
+      continue;
+    }
+    ENSURE(b, b->exc_off, sizeof(u64) * (N + 8));
+    ENSURE(b, b->exc_out_off, sizeof(u64) * (N + 8));
+    ENSURE(b, b->exc_ws, sizeof(u64) * (scan_ws_elems(N) + 64));
+    ENSURE(b, b->out_exc[m], sizeof(u64) * (b->exc_used[m] + 8));
+    const u16 *cnt = b->exc_cnt[m].as<u16>();
+    u64 *off = b->exc_off.as<u64>(), *out_off = b->exc_out_off.as<u64>();
+    exclusive_scan<u64>(ExcCount{cnt}, N, StoreTo<u64>{off}, b->exc_ws.as<u64>(), off + N, s);
+    exclusive_scan<u64>(ExcCountPermuted{cnt, b->perm}, N, StoreTo<u64>{out_off}, b->exc_ws.as<u64>(), out_off + N, s);
+    LAUNCH(exc_gather_k, cdiv(N, 256), 256, 0, s, N, b->perm, cnt, off, b->exc_in[m].as<u64>(), out_off, b->out_exc[m].as<u64>());
+    if (b->lean) {  // the input-order store is dead once the gathered stream exists
+      HIP_TRY(c, hipStreamSynchronize(s));
+      b->exc_in[m].release();
+    }
+  }
+  if (b->lean && b->keep_bases) {
+    HIP_TRY(c, hipStreamSynchronize(s));
+    for (int m = 0; m < b->nm; m++) b->exc_cnt[m].release();
+    b->exc_off.release(); b->exc_out_off.release(); b->exc_ws.release(); b->exc_piece_off.release();
+  }
   if (b->lean && b->keep_comments) { b->com_off.release(); b->com_out_off.release(); b->com_ws.release(); b->com_piece_off.release(); }
   if (b->lean) {  // nothing behind this stage reads the rows, the tokens or the sort scratch
     HIP_TRY(c, hipStreamSynchronize(s));

@@ -348,6 +348,13 @@ struct scalce_batch {
   DBuf comlen[2], com_in[2], out_comments[2], com_off, com_out_off, com_piece_off, com_ws;
   u64 com_used[2] = {0, 0}, out_comments_bytes[2] = {0, 0};
   u32 com_longest[2] = {0, 0};
+  // The letters and qualities the archive does not keep (scalce_batch_set_keep_bases): per mate exc_cnt = the exceptions per
+  // row (u16, run-wide, input order) and exc_in = their entries in input order (exc_used of them); the emit stage gathers
+  // them through the permutation into out_exc (SCALCE_OUT_EXCEPTIONS) with the archive index stamped in.  exc_piece_off /
+  // exc_off / exc_out_off: the offsets of a piece's write pass and of the gather.  Nothing of it exists without the option.
+  bool keep_bases = false;
+  DBuf exc_cnt[2], exc_in[2], out_exc[2], exc_piece_off, exc_off, exc_out_off, exc_ws;
+  u64 exc_used[2] = {0, 0}, exc_rows[2] = {0, 0}, out_exc_entries[2] = {0, 0};
   // host-side results
   u64 out_reads_bytes[2] = {0, 0}, out_names_bytes = 0, out_qual_bytes[2] = {0, 0};
   u32 ntie = 0, nev = 0, ntev = 0, ncand_cap = 0, jacobi_iters = 0, nchunks = 1, sweep_no = 0;

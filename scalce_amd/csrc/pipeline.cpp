@@ -24,6 +24,7 @@
 #include "hip_own.hpp"
 
 bool scalce_batch_keeps_comments(const scalce_batch *b);  // (host_ingest.inc: scalce_batch_set_keep_comments is on)
+bool scalce_batch_keeps_bases(const scalce_batch *b);     // (host_ingest.inc: scalce_batch_set_keep_bases is on)
 
 struct scalce_pipeline {
   std::vector<scalce_batch *> b;
@@ -93,6 +94,10 @@ extern "C" int scalce_pipeline_create(scalce_batch **batches, int nslots, int gr
     }
     if (scalce_batch_keeps_comments(batches[i])) {  // (a shard coded in place is run again from its text: the store would take its entries twice)
       p->err = "comments (--keep-comments) are kept one shard at a time: the pipeline does not take such a batch";
+      return SCALCE_ERR_ARG;
+    }
+    if (scalce_batch_keeps_bases(batches[i])) {  // (for the same reason: the store would take a shard's entries twice)
+      p->err = "exceptions (--keep-bases) are kept one shard at a time: the pipeline does not take such a batch";
       return SCALCE_ERR_ARG;
     }
   }

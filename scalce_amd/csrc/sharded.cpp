@@ -30,6 +30,7 @@
 
 void scalce_set_last_error(scalce_ctx *c, const char *msg);  // (host_state.inc: the message scalce_last_error returns)
 bool scalce_batch_keeps_comments(const scalce_batch *b);      // (host_ingest.inc: scalce_batch_set_keep_comments is on)
+bool scalce_batch_keeps_bases(const scalce_batch *b);         // (host_ingest.inc: scalce_batch_set_keep_bases is on)
 
 namespace {
 
@@ -707,6 +708,10 @@ extern "C" int scalce_sharded_compress(scalce_comm *comm, scalce_ctx *ctx, scalc
     }
     if (scalce_batch_keeps_comments(b)) {  // (the stores lie spread over the ranks, as the permutation does)
       scalce_set_last_error(ctx, "comments (--keep-comments) are kept on one GPU: sharded runs do not take such a batch");
+      return SCALCE_ERR_ARG;
+    }
+    if (scalce_batch_keeps_bases(b)) {  // (the stores lie spread over the ranks, as the permutation does)
+      scalce_set_last_error(ctx, "exceptions (--keep-bases) are kept on one GPU: sharded runs do not take such a batch");
       return SCALCE_ERR_ARG;
     }
   }

@@ -52,6 +52,7 @@
 #include "../../include/scalce_hip.h"
 #include "archive_walk.hpp"
 #include "hip_own.hpp"
+#include "exceptionstream.hpp"
 #include "orderstream.hpp"
 
 namespace {
@@ -97,6 +98,9 @@ struct Slot {
   // archives with a comment stream: the window's entries, the text with them put back and what the insert pass works in
   HBuf h_com, h_cbad;
   DBuf d_com, d_textc, d_roffc, d_cws, d_cbad;
+  // archives with an exception stream: the window's entries per mate (they grow with the windows), the verdict, the pairs' scratch
+  HBuf h_exc[2], h_xbad;
+  DBuf d_exc[2], d_xbad, d_xws;
   Event ev_up, ev_rec, ev_done, t_rec0, t_rec1;
   bool busy = false;
 };
@@ -112,6 +116,8 @@ struct Window {
   bool strip = false;
   bool com = false;         // the window's entries of the comment stream go back into its text
   u64 cbytes = 0;           // ... their bytes, newlines included
+  bool exc = false;         // the window's entries of the exception stream go back into its text
+  u64 nexc[2] = {0, 0};     // ... how many, per mate
 };
 
 struct Job {
@@ -170,6 +176,10 @@ struct Session {
   std::unique_ptr<Restore> X;  // set: the input order is restored
   scalce_unpack_comments CM;   // the comment streams (scalce_stream_decompress_comments), or none
   u64 cap_com = 0;             // bytes of entries a slot takes
+  scalce_unpack_exceptions EX; // the exception streams (scalce_stream_decompress_exceptions), or none
+  ExceptionCursor xc[2];       // ... where each mate's stands
+  bool has_exc[2] = {false, false};
+  std::vector<u64> xents;      // a window's entries of one mate, on their way into the slot
 
   // (the streams in front of what is used on them: close() lets everything go in the right order by hand, and should a
   // session ever die without it, the buffers and events would still go before the streams)
@@ -190,6 +200,7 @@ struct Session {
     if (rg) RG = *rg;
     memset(&RS, 0, sizeof RS);
     memset(&CM, 0, sizeof CM);
+    memset(&EX, 0, sizeof EX);
     RS.first_record = RG.first_record;
     RS.total_records = UNKNOWN;
     A.M[0] = &M[0];
@@ -294,7 +305,14 @@ struct Session {
       SD_TRY(dmalloc(s.d_text, cap_text));
       const bool strip = M[A.m0].has_len;  // (never with two mates in one window: -d -i refuses a length stream)
       if (P.split) SD_TRY(hmalloc(s.h_roff, roff_bytes));
-      if (P.split || strip || X || com) SD_TRY(dmalloc(s.d_roff, roff_bytes));
+      const bool exc = has_exc[A.m0];
+      if (P.split || strip || X || com || exc) SD_TRY(dmalloc(s.d_roff, roff_bytes));
+      if (exc) {
+        SD_TRY(hmalloc(s.h_xbad, 64));
+        memset(s.h_xbad.p, 0, 64);
+        SD_TRY(dmalloc(s.d_xbad, 64));
+        if (nmates == 2) SD_TRY(dmalloc(s.d_xws, scalce_fastq_exception_pairs_ws_bytes(R)));
+      }
       if (com) {  // a window's entries: no more than its text, nor than its records' times the longest
         cap_com = std::min(std::max(W, nmates * (C + 1)), R * nmates * (C + 1)) + 64;
         SD_TRY(hmalloc(s.h_com, cap_com));
@@ -321,7 +339,9 @@ struct Session {
   }
   void free_slots() {
     for (Slot &s : slot) {
-      for (DBuf *b : {&s.d_len, &s.d_text2, &s.d_roff2, &s.d_scan, &s.d_com, &s.d_textc, &s.d_roffc, &s.d_cws, &s.d_cbad, &s.d_in, &s.d_text, &s.d_roff}) drop(*b);
+      for (DBuf *b : {&s.d_len, &s.d_text2, &s.d_roff2, &s.d_scan, &s.d_com, &s.d_textc, &s.d_roffc, &s.d_cws, &s.d_cbad, &s.d_exc[0], &s.d_exc[1], &s.d_xbad, &s.d_xws,
+                      &s.d_in, &s.d_text, &s.d_roff})
+        drop(*b);
       s = Slot();
     }
     if (X) X->free_slots(*this);
@@ -454,6 +474,8 @@ struct Session {
       fail(SCALCE_ERR_FORMAT, A.m0, 4, 0, "(ERROR) %s", order_not_permutation());
     if (!failed && j.kind != Job::STRIPE && slot[j.slot].h_cbad.p && slot[j.slot].h_cbad.as<u32>()[0])
       fail(SCALCE_ERR_FORMAT, A.m0, 5, 0, "internal: a window's entries of the comment stream do not fit its records");
+    if (!failed && j.kind != Job::STRIPE && slot[j.slot].h_xbad.p && slot[j.slot].h_xbad.as<u32>()[0])
+      fail(SCALCE_ERR_FORMAT, A.m0, 6, 0, "(ERROR) %s", exception_outside());
     return !failed;
   }
   void records_time(const Slot &s) {
@@ -702,6 +724,22 @@ struct Session {
       if (X->o.read_into(X->rs[w.si].h_ord.as<u8>(), want) != want) return walk(short_stream(WF, m0, 4, X->o));
       X->taken += w.n;
     }
+    // the exception stream: the entries of the window's records, per mate (the cursor passes over what lies in front of them)
+    w.exc = has_exc[m0];
+    for (int m = m0; m <= m1 && w.exc; m++) {
+      xents.clear();
+      if (const char *why = xc[m].take(w.first, w.first + w.n, &xents)) return fail(SCALCE_ERR_FORMAT, m, 6, 0, "(ERROR) %s", why);
+      const int i = m - m0;
+      w.nexc[i] = xents.size();
+      if (8 * w.nexc[i] + 64 > s.h_exc[i].cap) {  // (the slot is idle: its last window is written)
+        const u64 want = std::max<u64>(2 * s.h_exc[i].cap, 8 * w.nexc[i] + 4096);
+        S.pinned_host_bytes -= s.h_exc[i].cap;
+        SD_TRY(hmalloc(s.h_exc[i], want));
+        drop(s.d_exc[i]);
+        SD_TRY(dmalloc(s.d_exc[i], want));
+      }
+      if (w.nexc[i]) memcpy(s.h_exc[i].p, xents.data(), 8 * w.nexc[i]);
+    }
     for (int m = m0; m <= m1; m++)
       w.nbytes += A.names ? (A.qual ? scalce_fastq_text_bytes : scalce_fasta_text_bytes)(M[m].L, w.n, w.nb[m - m0], nullptr) : lib_text(m, w.first, w.n);
     if (w.com) w.nbytes += w.cbytes - w.n * (u64)(m1 - m0 + 1);  // (the entries without their newlines)
@@ -713,6 +751,8 @@ struct Session {
     u8 *h_in = s.h_in.as<u8>(), *d_in = s.d_in.as<u8>();
     if (w.strip) SD_HIP(hipMemcpyAsync(s.d_len.p, s.h_len.p, w.n * (u64)M[A.m0].l_width, hipMemcpyHostToDevice, s_up));
     if (w.com) SD_HIP(hipMemcpyAsync(s.d_com.p, s.h_com.p, w.cbytes, hipMemcpyHostToDevice, s_up));
+    for (int i = 0; i < 2 && w.exc; i++)
+      if (w.nexc[i]) SD_HIP(hipMemcpyAsync(s.d_exc[i].p, s.h_exc[i].p, 8 * w.nexc[i], hipMemcpyHostToDevice, s_up));
     if (X) SD_TRY(X->upload(*this, w));
     for (int m = A.m0; m <= A.m1; m++) {
       Mate &x = M[m];
@@ -754,7 +794,7 @@ struct Session {
       if (A.names) { fw.d_names = d_in + x.o_names; fw.d_name_off = reinterpret_cast<const u64 *>(d_in + x.o_noff); }
       fw.library = A.library.c_str();
       fw.d_out = s.d_text.as<u8>();
-      fw.d_record_offsets = ((P.split || w.strip || X || w.com) && m == m0) ? s.d_roff.as<u64>() : nullptr;
+      fw.d_record_offsets = ((P.split || w.strip || X || w.com || w.exc) && m == m0) ? s.d_roff.as<u64>() : nullptr;
       if (nmates == 2) {
         const Mate &y = M[m == m0 ? m1 : m0];
         fw.interleave = m - m0 + 1; fw.pair_read_len = y.L;
@@ -767,6 +807,16 @@ struct Session {
         d.pos += w.n * (u64)x.L;
       }
     }
+    // the exceptions first, in place: the comment insert, the strip and the order restore all keep what the lines hold
+    if (w.exc && nmates == 2) {
+      const int rl[2] = {M[m0].L, M[m1].L};
+      const uint64_t *ents[2] = {s.d_exc[0].as<uint64_t>(), s.d_exc[1].as<uint64_t>()};
+      SD_TRY(lib(scalce_fastq_exception_window_pairs(ctx, rl, A.qual ? 1 : 0, w.first, w.n, s.d_text.as<u8>(), s.d_roff.as<u64>(),
+                                                     A.names ? reinterpret_cast<const u64 *>(d_in + M[m1].o_noff) : nullptr, A.library.size(), ents,
+                                                     w.nexc, s.d_xbad.as<u32>(), s.d_xws.p, s_main)));
+    } else if (w.exc)
+      SD_TRY(lib(scalce_fastq_exception_window(ctx, M[m0].L, A.qual ? 1 : 0, w.first, w.n, s.d_text.as<u8>(), s.d_roff.as<u64>(),
+                                               s.d_exc[0].as<uint64_t>(), w.nexc[0], s.d_xbad.as<u32>(), s_main)));
     // the entries go back in BEFORE the strip (which measures from the record's end) and before the order restore groups the
     // window (its records are self-contained text)
     if (w.com && nmates == 2) {  // (one interleaved text: both mates' entries, pair by pair)
@@ -798,6 +848,7 @@ struct Session {
       if (P.split) SD_HIP(hipMemcpyAsync(s.h_roff.p, window_roff(w).p, 8 * (w.n + 1), hipMemcpyDeviceToHost, s_down));
     }
     if (w.com) SD_HIP(hipMemcpyAsync(s.h_cbad.p, s.d_cbad.p, 4, hipMemcpyDeviceToHost, s_down));
+    if (w.exc) SD_HIP(hipMemcpyAsync(s.h_xbad.p, s.d_xbad.p, 4, hipMemcpyDeviceToHost, s_down));
     SD_HIP(hipEventRecord(s.ev_done, s_down));
     to_writer(w.si, w.first, w.n, w.nbytes, X ? Job::SPILL : Job::WINDOW);
     return SCALCE_OK;
@@ -833,6 +884,18 @@ struct Session {
     if (X && A.known && X->N != M[m0].records_left) return order_count(M[m0].records_left);
     for (int m = m0; m <= m1; m++)
       if (M[m].has_com && A.known && M[m].c_total != M[m0].records_left) return walk(A.comment_count(m, M[m].c_total, M[m0].records_left, WF));
+    for (int m = m0; m <= m1; m++) {
+      if (!has_exc[m]) continue;
+      char b[200];
+      if (A.known && xc[m].records != M[m0].records_left) {
+        exception_count_message(b, sizeof b, xc[m].records, M[m0].records_left);
+        return fail(SCALCE_ERR_FORMAT, m, 6, 0, "(ERROR) %s", b);
+      }
+      if (xc[m].read_len != (uint32_t)M[m].L) {
+        exception_length_message(b, sizeof b, xc[m].read_len, (uint32_t)M[m].L);
+        return fail(SCALCE_ERR_FORMAT, m, 6, 0, "(ERROR) %s", b);
+      }
+    }
     SD_TRY(pass_over());
     for (;;) {
       if (failed) return F.rc;
@@ -880,6 +943,12 @@ struct Session {
       if (!CM.com_rd[m]) continue;
       if (!A.names) return fail(SCALCE_ERR_ARG, m, 5, 0, "(ERROR) a comment stream goes with stored names: the archive holds none (or -n sets them aside)");
       SD_TRY(walk(A.comments_open(m, CM.com_rd[m], CM.com_user[m], &S.read_wait_s, WF)));
+    }
+    for (int m = 0; m < P.mates; m++) {  // the exception streams: header, then the entries in ascending order
+      if (!EX.exc_rd[m]) continue;
+      xc[m].start(EX.exc_rd[m], EX.exc_user[m]);
+      if (const char *why = xc[m].read_header()) return fail(SCALCE_ERR_FORMAT, m, 6, 0, "(ERROR) %s", why);
+      has_exc[m] = true;
     }
     for (Stream *s : {&s_up, &s_main, &s_dec, &s_down}) SD_HIP(s->create());
     writer = std::thread([this] { writer_main(); });
@@ -1017,8 +1086,8 @@ extern "C" int scalce_stream_decompress_range(scalce_ctx *ctx, const scalce_unpa
 }
 
 // the three shapes of decompression behind one call, with or without comment streams (the entry points below and above are this)
-static int decompress_any(scalce_ctx *ctx, const scalce_unpack_params *p, const scalce_unpack_comments *cm, const scalce_unpack_range *range,
-                          const scalce_restore_params *rp, scalce_read_fn rd[2][3], void *user[2][3], scalce_write_fn wr, void *wr_user,
+static int decompress_any(scalce_ctx *ctx, const scalce_unpack_params *p, const scalce_unpack_comments *cm, const scalce_unpack_exceptions *ex,
+                          const scalce_unpack_range *range, const scalce_restore_params *rp, scalce_read_fn rd[2][3], void *user[2][3], scalce_write_fn wr, void *wr_user,
                           scalce_unpack_stats *stats, scalce_unpack_range_stats *range_stats, scalce_restore_stats *restore_stats, char *errbuf,
                           size_t errcap) {
   if (const int rc = unpack_args(ctx, p, rd, user, wr, errbuf, errcap)) return rc;
@@ -1028,8 +1097,14 @@ static int decompress_any(scalce_ctx *ctx, const scalce_unpack_params *p, const 
     if (errbuf && errcap) snprintf(errbuf, errcap, "(ERROR) an archive with comment streams: every mate has its stream");
     return SCALCE_ERR_ARG;
   }
+  const bool exc = ex && (ex->exc_rd[0] || ex->exc_rd[1]);
+  if (exc && (!ex->exc_rd[0] || (p->mates == 2 && !ex->exc_rd[1]))) {
+    if (errbuf && errcap) snprintf(errbuf, errcap, "(ERROR) an archive with exception streams: every mate has its stream");
+    return SCALCE_ERR_ARG;
+  }
   Session *s = new Session(ctx, p, range, wr, wr_user);
   if (com) s->CM = *cm;
+  if (exc) s->EX = *ex;
   if (rp) {
     s->X.reset(new Restore);
     s->X->P = *rp;
@@ -1046,7 +1121,14 @@ extern "C" int scalce_stream_decompress_comments(scalce_ctx *ctx, const scalce_u
                                                  void *user[2][3], scalce_write_fn wr, void *wr_user, scalce_unpack_stats *stats,
                                                  scalce_unpack_range_stats *range_stats, scalce_restore_stats *restore_stats, char *errbuf,
                                                  size_t errcap) {
-  return decompress_any(ctx, p, comments, range, rp, rd, user, wr, wr_user, stats, range_stats, restore_stats, errbuf, errcap);
+  return decompress_any(ctx, p, comments, nullptr, range, rp, rd, user, wr, wr_user, stats, range_stats, restore_stats, errbuf, errcap);
+}
+extern "C" int scalce_stream_decompress_exceptions(scalce_ctx *ctx, const scalce_unpack_params *p, const scalce_unpack_comments *comments,
+                                                   const scalce_unpack_exceptions *exceptions, const scalce_unpack_range *range,
+                                                   const scalce_restore_params *rp, scalce_read_fn rd[2][3], void *user[2][3], scalce_write_fn wr,
+                                                   void *wr_user, scalce_unpack_stats *stats, scalce_unpack_range_stats *range_stats,
+                                                   scalce_restore_stats *restore_stats, char *errbuf, size_t errcap) {
+  return decompress_any(ctx, p, comments, exceptions, range, rp, rd, user, wr, wr_user, stats, range_stats, restore_stats, errbuf, errcap);
 }
 
 extern "C" int scalce_stream_decompress_restore(scalce_ctx *ctx, const scalce_unpack_params *p, const scalce_restore_params *rp,

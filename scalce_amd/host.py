@@ -19,6 +19,7 @@ OUT_READS, OUT_NAMES, OUT_QUAL, OUT_TABLE, OUT_FREQ4, OUT_TOKENS, OUT_PERM, OUT_
 OUT_LENGTHS = 12  # variable-length runs: N x u16, read_len - length per record in output order
 OUT_NAMECELLS = 13  # for tests: N x 16 bytes, [stored length][first 15 characters, zero behind a shorter name], input order
 OUT_COMMENTS = 14  # keep_comments: what follows the name of every record in output order, each entry followed by a newline
+OUT_EXCEPTIONS = 15  # keep_bases: u64 entries in output order: letter | values[q] << 8 | position << 16 | record << 28
 STAGES = ("ingest", "quality", "tokenize", "order", "emit", "entropy")
 ROOT_CORE = 0x3FFFFFFF
 
@@ -667,9 +668,34 @@ def _unpack_comments(keep, mates, comment_readers):
     return cm
 
 
-def _decompress_comments(ctx, p, cm, rg, rp, rd, user, wfn, st, rst, ost, msg):
-    """scalce_stream_decompress_comments: the one entry point behind the three shapes, with comment streams"""
+class UnpackExceptions(C.Structure):
+    """scalce_unpack_exceptions: the exception streams of an archive made with --keep-bases, one per mate"""
+    _fields_ = [("exc_rd", READ_FN * 2), ("exc_user", C.c_void_p * 2)]
+
+
+def _unpack_exceptions(keep, mates, exception_readers):
+    ex = UnpackExceptions()
+    for m in range(mates):
+        if exception_readers[m] is not None:
+            ex.exc_rd[m] = _unpack_read_fn(keep, exception_readers[m])
+    return ex
+
+
+def _decompress_streams(ctx, p, cm, rg, rp, rd, user, wfn, st, rst, ost, msg, ex=None):
+    """The one entry point behind the three shapes of decompression for archives with side streams: cm the comment streams
+    (scalce_stream_decompress_comments), ex the exception streams beside them or alone (scalce_stream_decompress_exceptions)"""
     L = ctx.L
+    if ex is not None:
+        L.scalce_stream_decompress_exceptions.argtypes = [C.c_void_p, C.POINTER(UnpackParams), C.POINTER(UnpackComments), C.POINTER(UnpackExceptions),
+                                                          C.POINTER(UnpackRange), C.POINTER(RestoreParams), C.c_void_p, C.c_void_p, WRITE_FN,
+                                                          C.c_void_p, C.POINTER(UnpackStats), C.POINTER(UnpackRangeStats), C.POINTER(RestoreStats),
+                                                          C.c_char_p, C.c_size_t]
+        L.scalce_stream_decompress_exceptions.restype = C.c_int
+        return L.scalce_stream_decompress_exceptions(ctx.h, C.byref(p), C.byref(cm) if cm is not None else None, C.byref(ex),
+                                                     C.byref(rg) if rg is not None else None, C.byref(rp) if rp is not None else None,
+                                                     C.cast(rd, C.c_void_p), C.cast(user, C.c_void_p), wfn, None, C.byref(st),
+                                                     C.byref(rst) if rst is not None else None, C.byref(ost) if ost is not None else None,
+                                                     msg, len(msg))
     L.scalce_stream_decompress_comments.argtypes = [C.c_void_p, C.POINTER(UnpackParams), C.POINTER(UnpackComments), C.POINTER(UnpackRange),
                                                     C.POINTER(RestoreParams), C.c_void_p, C.c_void_p, WRITE_FN, C.c_void_p,
                                                     C.POINTER(UnpackStats), C.POINTER(UnpackRangeStats), C.POINTER(RestoreStats),
@@ -684,7 +710,7 @@ def _decompress_comments(ctx, p, cm, rg, rp, rd, user, wfn, st, rst, ost, msg):
 
 def stream_decompress(ctx, readers, write, mates=1, interleave=False, no_qualities=False, mate_digit=None, library=None,
                       split=0, window_text_bytes=0, first_record=0, nrecords=None, skippers=None, length_readers=None,
-                      length_skippers=None, comment_readers=None):
+                      length_skippers=None, comment_readers=None, exception_readers=None):
     """scalce_stream_decompress_range: an archive, or a range of its records, back to text in windows of whole records.
     readers[m] = the three callables (cap) -> bytes of mate m's .scalcer, .scalcen and .scalceq streams (b"" at the end; raise
     for a read error); write(mate, first_record, nrecords, text_bytes, record_offsets or None) receives every window in
@@ -693,7 +719,8 @@ def stream_decompress(ctx, readers, write, mates=1, interleave=False, no_qualiti
     callables (nbytes) -> bytes passed over, or None where the stream can only be read.  length_readers[m] (and, optionally,
     length_skippers[m]): the .scalcel stream of a variable-length archive, one callable per mate.  Returns UnpackStats; its attribute
     `range` holds the UnpackRangeStats of the run.  comment_readers[m]: the .scalcec stream of an archive made with
-    --keep-comments, one callable per mate -- the call then goes through scalce_stream_decompress_comments."""
+    --keep-comments, one callable per mate -- the call then goes through scalce_stream_decompress_comments.  exception_readers[m]:
+    the .scalcex stream of an archive made with --keep-bases -- through scalce_stream_decompress_exceptions."""
     keep = []
     wfn = _unpack_write_fn(write)
     rd = ((READ_FN * 3) * 2)()
@@ -719,8 +746,11 @@ def stream_decompress(ctx, readers, write, mates=1, interleave=False, no_qualiti
                                                  WRITE_FN, C.c_void_p, C.POINTER(UnpackStats), C.POINTER(UnpackRangeStats), C.c_char_p,
                                                  C.c_size_t]
     L.scalce_stream_decompress_range.restype = C.c_int
-    if comment_readers is not None:
-        rc = _decompress_comments(ctx, p, _unpack_comments(keep, mates, comment_readers), rg, None, rd, user, wfn, st, rst, None, msg)
+    if exception_readers is not None:
+        cm = _unpack_comments(keep, mates, comment_readers) if comment_readers is not None else None
+        rc = _decompress_streams(ctx, p, cm, rg, None, rd, user, wfn, st, rst, None, msg, ex=_unpack_exceptions(keep, mates, exception_readers))
+    elif comment_readers is not None:
+        rc = _decompress_streams(ctx, p, _unpack_comments(keep, mates, comment_readers), rg, None, rd, user, wfn, st, rst, None, msg)
     else:
         rc = L.scalce_stream_decompress_range(ctx.h, C.byref(p), C.byref(rg), C.cast(rd, C.c_void_p), C.cast(user, C.c_void_p), wfn, None,
                                               C.byref(st), C.byref(rst), msg, len(msg))
@@ -889,6 +919,76 @@ def fastq_comment_window_pairs(ctx, read_lens, has_qualities, npairs, d_text, d_
                                                    d_entries, int(entry_bytes), d_out, d_out_pair_offsets, d_bad, d_ws, stream))
 
 
+# ---- the letters and qualities the archive does not keep (archives made with --keep-bases) ------------------------------------
+EXCEPTION_HEADER_BYTES = 32  # the 8 magic bytes, int32 8 (entry width), int32 L, int64 N (records), int64 X (entries); then X x u64
+EXCEPTION_MAX_RECORDS = 1 << 36
+STREAM_KEEP_BASES = 16       # SCALCE_STREAM_KEEP_BASES
+
+
+def exception_entry(record, position, letter, quality=0):
+    """One u64 of a .scalcex stream: bits 0-7 the letter, 8-15 the quality character, 16-27 the position, 28-63 the record."""
+    return int(letter) | int(quality) << 8 | int(position) << 16 | int(record) << 28
+
+
+def pack_exceptions(entries, read_len, nrecords):
+    """The bytes of a .scalcex stream: header, then the entries (u64, strictly ascending) little-endian."""
+    e = np.ascontiguousarray(entries, dtype="<u8").reshape(-1)
+    if len(e) > 1 and not ((e[1:] >> np.uint64(16)) > (e[:-1] >> np.uint64(16))).all():   # (by record and position: one entry per place)
+        raise ValueError("exception stream: entries are not in ascending order")
+    return b"scalce22" + struct.pack("<iiqq", 8, int(read_len), int(nrecords), len(e)) + e.tobytes()
+
+
+def unpack_exceptions(data):
+    """(read_len, nrecords, entries as a u64 array) of the bytes of a .scalcex stream (out of its container); ValueError with
+    the library's message."""
+    data = bytes(data)
+    if len(data) < EXCEPTION_HEADER_BYTES:
+        raise ValueError("truncated exception stream")
+    width, L, n, x = struct.unpack("<iiqq", data[8:32])
+    if data[:7] != b"scalce2" or width != 8 or L <= 0 or L >= 4096 or n < 0 or n >= EXCEPTION_MAX_RECORDS or x < 0:
+        raise ValueError("is not a scalce exception stream")
+    if len(data) - EXCEPTION_HEADER_BYTES < 8 * x:
+        raise ValueError("truncated exception stream")
+    e = np.frombuffer(data, dtype="<u8", count=x, offset=EXCEPTION_HEADER_BYTES).astype(np.uint64)
+    if len(e) > 1 and not ((e[1:] >> np.uint64(16)) > (e[:-1] >> np.uint64(16))).all():
+        raise ValueError("exception stream: entries are not in ascending order")
+    if len(e) and (((e >> np.uint64(28)) >= np.uint64(n)).any() or (((e >> np.uint64(16)) & np.uint64(0xFFF)) >= np.uint64(L)).any()):
+        raise ValueError("exception stream: an entry lies outside its record")
+    return L, n, e
+
+
+def fastq_exception_window(ctx, read_len, has_qualities, first_record, nrecords, d_text, d_record_offsets, d_entries, nentries, d_bad,
+                           stream=0):
+    """scalce_fastq_exception_window: a window's entries of the exception stream back into its text, in place (device pointers)."""
+    L = ctx.L
+    L.scalce_fastq_exception_window.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_uint64] + [C.c_void_p] * 3 + [C.c_uint64] + [C.c_void_p] * 2
+    L.scalce_fastq_exception_window.restype = C.c_int
+    ctx._check(L.scalce_fastq_exception_window(ctx.h, int(read_len), int(bool(has_qualities)), int(first_record), int(nrecords), d_text,
+                                               d_record_offsets, d_entries, int(nentries), d_bad, stream))
+
+
+def fastq_exception_pairs_ws_bytes(npairs):
+    L = lib()
+    L.scalce_fastq_exception_pairs_ws_bytes.argtypes = [C.c_uint64]
+    L.scalce_fastq_exception_pairs_ws_bytes.restype = C.c_uint64
+    return int(L.scalce_fastq_exception_pairs_ws_bytes(int(npairs)))
+
+
+def fastq_exception_window_pairs(ctx, read_lens, has_qualities, first_pair, npairs, d_text, d_pair_offsets, d_name_off2, d_entries, nentries,
+                                 d_bad, d_ws, stream=0, library_len=0):
+    """scalce_fastq_exception_window_pairs: the same for an interleaved window; d_entries / nentries: one per mate;
+    d_name_off2 None: made-up names of a library name of library_len characters."""
+    L = ctx.L
+    L.scalce_fastq_exception_window_pairs.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_uint64, C.c_uint64] + [C.c_void_p] * 3 + [
+        C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)] + [C.c_void_p] * 3
+    L.scalce_fastq_exception_window_pairs.restype = C.c_int
+    rl = (C.c_int * 2)(int(read_lens[0]), int(read_lens[1]))
+    de = (C.c_void_p * 2)(d_entries[0], d_entries[1])
+    ne = (C.c_uint64 * 2)(int(nentries[0]), int(nentries[1]))
+    ctx._check(L.scalce_fastq_exception_window_pairs(ctx.h, rl, int(bool(has_qualities)), int(first_pair), int(npairs), d_text, d_pair_offsets,
+                                                     d_name_off2, int(library_len), de, ne, d_bad, d_ws, stream))
+
+
 class RestoreParams(C.Structure):
     _fields_ = [("order_rd", READ_FN * 2), ("order_user", C.c_void_p * 2), ("spill_dir", C.c_char_p)]
 
@@ -900,7 +1000,8 @@ class RestoreStats(C.Structure):
 
 
 def stream_decompress_restore(ctx, readers, order_readers, write, spill_dir, mates=1, interleave=False, no_qualities=False,
-                              mate_digit=None, library=None, split=0, window_text_bytes=0, length_readers=None, comment_readers=None):
+                              mate_digit=None, library=None, split=0, window_text_bytes=0, length_readers=None, comment_readers=None,
+                              exception_readers=None):
     """scalce_stream_decompress_restore: stream_decompress with the input order restored.  order_readers[m]: the callable
     (cap) -> bytes of the .scalceo stream, read from its start once per mate pass (interleaved: only [0]); write receives
     the text in input order, one stripe per call, first_record = the input index of its first record.  Returns
@@ -928,8 +1029,11 @@ def stream_decompress_restore(ctx, readers, order_readers, write, spill_dir, mat
                                                    WRITE_FN, C.c_void_p, C.POINTER(UnpackStats), C.POINTER(RestoreStats), C.c_char_p,
                                                    C.c_size_t]
     L.scalce_stream_decompress_restore.restype = C.c_int
-    if comment_readers is not None:
-        rc = _decompress_comments(ctx, p, _unpack_comments(keep, mates, comment_readers), None, rp, rd, user, wfn, st, None, rst, msg)
+    if exception_readers is not None:
+        cm = _unpack_comments(keep, mates, comment_readers) if comment_readers is not None else None
+        rc = _decompress_streams(ctx, p, cm, None, rp, rd, user, wfn, st, None, rst, msg, ex=_unpack_exceptions(keep, mates, exception_readers))
+    elif comment_readers is not None:
+        rc = _decompress_streams(ctx, p, _unpack_comments(keep, mates, comment_readers), None, rp, rd, user, wfn, st, None, rst, msg)
     else:
         rc = L.scalce_stream_decompress_restore(ctx.h, C.byref(p), C.byref(rp), C.cast(rd, C.c_void_p), C.cast(user, C.c_void_p), wfn, None,
                                                 C.byref(st), C.byref(rst), msg, len(msg))
@@ -957,7 +1061,7 @@ class Batch:
 
     def __init__(self, ctx, read_len, max_reads, max_text, paired=False, use_names=True, no_ac=False, qmap=None,
                  bucket_set_size=0, read_len2=0, qprev=None, workspace=None, fasta=False, no_qualities=False, interleaved=False,
-                 variable_length=False, keep_comments=False):
+                 variable_length=False, keep_comments=False, keep_bases=False):
         self.ctx = ctx
         self.L = ctx.L
         p = Params()
@@ -989,6 +1093,8 @@ class Batch:
             raise ScalceError(f"[{rc}] " + self.L.scalce_last_error(ctx.h).decode())
         if keep_comments:
             self.set_keep_comments(True)
+        if keep_bases:
+            self.set_keep_bases(True)
 
     def _check(self, rc):
         self.ctx._check(rc)
@@ -1027,6 +1133,21 @@ class Batch:
         n, c = C.c_uint64(0), C.c_uint32(0)
         self._check(self.L.scalce_batch_comments_info(self.h, int(mate), C.byref(n), C.byref(c)))
         return int(n.value), int(c.value)
+
+    def set_keep_bases(self, on=True):
+        """The letters and qualities the archive does not keep become OUT_EXCEPTIONS (scalce_batch_set_keep_bases): before the
+        run's first ingest or append."""
+        self.L.scalce_batch_set_keep_bases.argtypes = [C.c_void_p, C.c_int]
+        self.L.scalce_batch_set_keep_bases.restype = C.c_int
+        self._check(self.L.scalce_batch_set_keep_bases(self.h, int(on)))
+
+    def exceptions_info(self, mate=0):
+        """scalce_batch_exceptions_info: (entries of OUT_EXCEPTIONS, records that hold at least one) of `mate`."""
+        self.L.scalce_batch_exceptions_info.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        self.L.scalce_batch_exceptions_info.restype = C.c_int
+        x, n = C.c_uint64(0), C.c_uint64(0)
+        self._check(self.L.scalce_batch_exceptions_info(self.h, int(mate), C.byref(x), C.byref(n)))
+        return int(x.value), int(n.value)
 
     def quality(self, stream=0):
         self._check(self.L.scalce_batch_quality(self.h, stream))
