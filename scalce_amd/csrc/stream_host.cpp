@@ -232,7 +232,9 @@ int stream_run(scalce_ctx *ctx, const scalce_params *p, scalce_read_fn rd[2], vo
     }
     if (final_piece) break;
     if (!progress) {
-      err = "(ERROR) a record does not fit one piece of the stream, or the mates have different record counts";
+      err = "(ERROR) a record does not fit one piece of the stream (" + std::to_string(piece) + " bytes; a record of " +
+            std::to_string(p->read_len[0]) + " bases is " + std::to_string(2 * (uint64_t)p->read_len[0] + 6) +
+            " bytes and its name line), or the mates have different record counts";
       return SCALCE_ERR_FORMAT;
     }
   }
@@ -262,7 +264,12 @@ extern "C" int scalce_stream_compress(scalce_ctx *ctx, const scalce_params *p, s
   // streams read: one per mate, or ONE under -i (both mates in one text; scalce_batch_append takes whole pairs of it, so a
   // piece's tail that goes on into the next piece always begins at a pair)
   const int nm = p->paired && !p->interleaved ? 2 : 1;
-  const uint64_t piece = ((piece_bytes ? piece_bytes : (1ull << 30)) + 4095) & ~4095ull;
+  // a piece holds at least one record (-i: one pair) at its bound -- the fixed part, a name of up to 255 bytes, 32 to spare --,
+  // or the tail of a piece could never grow into a whole record: reads of 2498 bases are 5 KB of text each
+  uint64_t unit = 0;
+  for (int m = 0; m < (p->paired ? 2 : 1); m++) unit += 2 * (uint64_t)(p->read_len[m] > 0 ? p->read_len[m] : 0) + 6 + 255 + 32;
+  const uint64_t asked = piece_bytes ? piece_bytes : (1ull << 30);
+  const uint64_t piece = ((asked > unit ? asked : unit) + 4095) & ~4095ull;
   scalce_read_fn rd[2] = {rd1, rd2};
   void *user[2] = {user1, user2};
   Stream s_copy, s_main;  // (in front of the mates: the streams go after the buffers and events used on them)

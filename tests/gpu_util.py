@@ -35,6 +35,37 @@ def oracle_streams(trie, bases, quals, qoff=33, qvals=None, chunk=None, no_ac=Fa
     return dict(pat=pat, end=end, perm=perm, qp=qp, f4=f4)
 
 
+def check_against_oracle(ctx, trie, bases, quals, qoff=33, qvals=None, label=""):
+    n, L = bases.shape
+    fq = synth.fastq_bytes_fast(bases, quals)
+    qm = None if qvals is None else [(qoff, qvals), (qoff, qvals)]
+    b = hip_compress(ctx, fq, L, qmap=qm)
+    ref = oracle_streams(trie, bases, quals, qoff, qvals)
+    st = b.stats()
+    tok = b.output(host.OUT_TOKENS, 0, np.int32).reshape(-1, 2)
+    bad = np.flatnonzero((tok[:, 0] != ref["pat"]) | (tok[:, 1] != ref["end"]))
+    assert len(bad) == 0, f"{label}: {len(bad)} token mismatches, first at read {bad[:5]}: hip {tok[bad[:5]]} " \
+                          f"oracle {ref['pat'][bad[:5]]},{ref['end'][bad[:5]]} stats {st}"
+    perm = b.output(host.OUT_PERM, 0, np.uint32)
+    badp = np.flatnonzero(perm != ref["perm"])
+    assert len(badp) == 0, f"{label}: permutation differs at {len(badp)} of {n} positions, first {badp[:5]}"
+    qin = b.output(host.OUT_QINPUT, 0).reshape(n, L)
+    assert (qin == ref["qp"]).all(), f"{label}: q' mismatch"
+    f4 = b.output(host.OUT_FREQ4, 0, np.uint64)
+    assert (f4 + 1 == ref["f4"]).all(), f"{label}: trigram table mismatch at {np.flatnonzero(f4 + 1 != ref['f4'])[:5]}"
+    table = b.output(host.OUT_TABLE, 0, np.uint32)
+    assert (table == O.ac_scale(ref["f4"], 1)).all(), f"{label}: scaled table mismatch"
+    qs = b.output(host.OUT_QSTREAM, 0)
+    want_qs = ref["qp"][ref["perm"]].reshape(-1)
+    assert (qs == want_qs).all(), f"{label}: reordered quality stream mismatch"
+    enc = b.output(host.OUT_QUAL, 0)
+    want = O.AcStat(table).encode_stream(want_qs)
+    assert len(enc) == len(want), f"{label}: AC length {len(enc)} vs {len(want)}"
+    neq = np.flatnonzero(enc != want)
+    assert len(neq) == 0, f"{label}: AC bytes differ first at {neq[:5]} of {len(want)}"
+    return b, ref, st
+
+
 def craft_straddle(n, cum, total, rng, first2=(9, 12)):
     """n symbols for a context-free table (cum[0..80] cumulative counts) chosen while following the reference coder's
     state (arithmetic.cpp:122-152): runs of 1..40 symbols whose interval holds the midpoint -- each adds pending

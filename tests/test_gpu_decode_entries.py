@@ -230,7 +230,7 @@ CORES = [b"A", b"C", b"G", b"T", CORE12, CORE32]
 CORE_TEXT = b"\n".join(CORES) + b"\n"
 SIZES = (20, 12, 1, 17, 20)  # buckets change at records 19 -> 20, 31 -> 32, 32 -> 33 and 49 -> 50; bucket 2 is one record
 NREC = sum(SIZES)
-LENGTHS = list(range(1, 41)) + [63, 64, 65, 100, 255, 256, 257, 300]
+LENGTHS = list(range(1, 41)) + [63, 64, 65, 100, 255, 256, 257, 300, 1000, 2498]
 
 
 def record_set(L, seed=0):

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import oraclelib as O
+from gpu_util import check_against_oracle
 from scalce_amd import format as fmt
 from scalce_amd import host, synth
 
@@ -25,38 +26,6 @@ def ctx(patterns_blob):
 
 def sha(a):
     return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
-
-
-def check_against_oracle(ctx, trie, bases, quals, qoff=33, qvals=None, label=""):
-    from gpu_util import hip_compress, oracle_streams
-    n, L = bases.shape
-    fq = synth.fastq_bytes_fast(bases, quals)
-    qm = None if qvals is None else [(qoff, qvals), (qoff, qvals)]
-    b = hip_compress(ctx, fq, L, qmap=qm)
-    ref = oracle_streams(trie, bases, quals, qoff, qvals)
-    st = b.stats()
-    tok = b.output(host.OUT_TOKENS, 0, np.int32).reshape(-1, 2)
-    bad = np.flatnonzero((tok[:, 0] != ref["pat"]) | (tok[:, 1] != ref["end"]))
-    assert len(bad) == 0, f"{label}: {len(bad)} token mismatches, first at read {bad[:5]}: hip {tok[bad[:5]]} " \
-                          f"oracle {ref['pat'][bad[:5]]},{ref['end'][bad[:5]]} stats {st}"
-    perm = b.output(host.OUT_PERM, 0, np.uint32)
-    badp = np.flatnonzero(perm != ref["perm"])
-    assert len(badp) == 0, f"{label}: permutation differs at {len(badp)} of {n} positions, first {badp[:5]}"
-    qin = b.output(host.OUT_QINPUT, 0).reshape(n, L)
-    assert (qin == ref["qp"]).all(), f"{label}: q' mismatch"
-    f4 = b.output(host.OUT_FREQ4, 0, np.uint64)
-    assert (f4 + 1 == ref["f4"]).all(), f"{label}: trigram table mismatch at {np.flatnonzero(f4 + 1 != ref['f4'])[:5]}"
-    table = b.output(host.OUT_TABLE, 0, np.uint32)
-    assert (table == O.ac_scale(ref["f4"], 1)).all(), f"{label}: scaled table mismatch"
-    qs = b.output(host.OUT_QSTREAM, 0)
-    want_qs = ref["qp"][ref["perm"]].reshape(-1)
-    assert (qs == want_qs).all(), f"{label}: reordered quality stream mismatch"
-    enc = b.output(host.OUT_QUAL, 0)
-    want = O.AcStat(table).encode_stream(want_qs)
-    assert len(enc) == len(want), f"{label}: AC length {len(enc)} vs {len(want)}"
-    neq = np.flatnonzero(enc != want)
-    assert len(neq) == 0, f"{label}: AC bytes differ first at {neq[:5]} of {len(want)}"
-    return b, ref, st
 
 
 @pytest.mark.parametrize("name", ["se100", "se100_lossy", "se150_text", "se36_ties"])

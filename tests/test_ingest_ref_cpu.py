@@ -20,7 +20,7 @@ def sha(a):
 
 
 # ---- the 2-bit rows ---------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("L", [1, 2, 3, 4, 5, 15, 16, 17, 19, 100, 161])
+@pytest.mark.parametrize("L", [1, 2, 3, 4, 5, 15, 16, 17, 19, 100, 161, 1000, 2498])
 def test_rows_are_pack_read(L):
     rng = np.random.default_rng(L)
     bases = np.frombuffer(b"ACGTNacgtn", dtype=np.uint8)[rng.integers(0, 10, size=(40, L))]

@@ -65,6 +65,24 @@ def test_plan_cap_on_the_stripes():
         host.order_plan(10, 1 << 30, 0)
 
 
+def test_plan_records_of_the_longest_pair():
+    """a pair of 2498-base reads is 10 590 bytes of text at the bound: windows below one record, of one, of three, of the archive"""
+    rec = rec_max(2498, mates=2)
+    assert rec == 2 * (2 * 2498 + 6 + 255 + 32)
+    assert host.order_plan(400, 1, rec) == (1, 400)
+    assert host.order_plan(400, 3000, rec) == (1, 400)            # less than one record: a record per stripe all the same
+    assert host.order_plan(400, rec - 1, rec) == (1, 400)
+    assert host.order_plan(400, rec, rec) == (1, 400)
+    assert host.order_plan(400, 3 * rec, rec) == (3, 134)
+    assert host.order_plan(400, 3 * rec + rec - 1, rec) == (3, 134)
+    assert host.order_plan(400, 400 * rec, rec) == (400, 1)
+    assert host.order_plan(400, 1 << 30, rec) == ((1 << 30) // rec, 1)
+    R, S = host.order_plan(70_000, 3000, rec)                     # more records than stripes under a window below one record
+    assert (R, S) == (2, 35_000)
+    single = rec_max(2498)
+    assert host.order_plan(400, 3000, single) == (1, 400) and host.order_plan(400, 2 * single, single) == (2, 200)
+
+
 def test_plan_stripe_text_fits_the_window_unless_the_cap_raised_r():
     rng = np.random.default_rng(5)
     for _ in range(3000):

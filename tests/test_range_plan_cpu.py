@@ -7,7 +7,7 @@ import pytest
 from scalce_amd import host
 
 FRAME = 10 * 1024 * 1024
-LENGTHS = [1, 36, 64, 100, 150, 301]
+LENGTHS = [1, 36, 64, 100, 150, 301, 1000, 2498]
 
 
 def plan(L, first, n, total):
