@@ -173,6 +173,7 @@ int scalce_batch_reset(scalce_batch *b);
 #define SCALCE_STREAM_KEEP_ORDER 4  /* scalce_batch_set_keep_order on the run's batch: SCALCE_OUT_PERM outlives the lean releases */
 #define SCALCE_STREAM_KEEP_COMMENTS 8  /* scalce_batch_set_keep_comments on the run's batch: SCALCE_OUT_COMMENTS holds what follows the names */
 #define SCALCE_STREAM_KEEP_BASES 16  /* scalce_batch_set_keep_bases on the run's batch: SCALCE_OUT_EXCEPTIONS holds what the archive does not keep of the bases */
+#define SCALCE_STREAM_KEEP_PLUS 32  /* scalce_batch_set_keep_plus on the run's batch: SCALCE_OUT_PLUS holds the records' '+' lines as entries */
 typedef int64_t (*scalce_read_fn)(void *user, void *dst, uint64_t cap);
 typedef struct {
   double total_s, read_wait_s, h2d_wait_s, front_s, order_s, emit_s, entropy_s;
@@ -203,6 +204,24 @@ int scalce_batch_set_keep_comments(scalce_batch *b, int on);
  * the newline (the C of the .scalcec header); either may be NULL.  Valid behind the ingest of the run's last piece; zero without
  * the option. */
 int scalce_batch_comments_info(const scalce_batch *b, int mate, uint64_t *nbytes, uint32_t *longest);
+/* on = 1: every record's third line becomes an output of the run (the plus-line stream of --keep-plus).  It mirrors
+ * scalce_batch_set_keep_comments.  The reference writes the line back as a bare '+' (decompress.cpp prints "+\n"); a record's
+ * ENTRY says what stood there: empty for a bare '+'; the byte '=' when the line behind its '+' equals the header line behind
+ * its '@' (the whole line, name and what follows it); else '\'' followed by the line's bytes behind the '+'.  Every piece's
+ * entries go, each with a newline behind it, into a byte store per mate in input order (interleaved text: record 2k + m goes to
+ * mate m's store; pieces cut anywhere), and the emit stage gathers them through the permutation: SCALCE_OUT_PLUS.  Every other
+ * output is what it is without the option, byte for byte.  SCALCE_ERR_FORMAT from the ingest itself for a third line that is
+ * empty or begins with another character ("(ERROR) record <n>: the third line does not begin with '+'") and for a stored entry
+ * above 65535 bytes ("(ERROR) record <n>: the '+' line is longer than 65535 bytes").  To be called before the first ingest or
+ * append of a run.  SCALCE_ERR_ARG for a batch made with fasta or no_qualities (no such line) or coded in place; one GPU only:
+ * scalce_sharded_compress, scalce_batch_rewindow, scalce_batch_text_offset, scalce_batch_set_code_in_place and
+ * scalce_pipeline_create refuse such batches (SCALCE_ERR_ARG).  Off (the default): no kernel of it is launched and no buffer of
+ * it allocated. */
+int scalce_batch_set_keep_plus(scalce_batch *b, int on);
+/* Mirrors scalce_batch_comments_info.  *nbytes = the size of SCALCE_OUT_PLUS of `mate` (entries and their newlines), *longest =
+ * its longest stored entry in bytes, class byte included, newline not (the P of the .scalcep header; 0: every line was bare),
+ * *repeats / *literals = how many entries are '=' / begin with '\'' (valid behind scalce_batch_emit).  Any may be NULL. */
+int scalce_batch_plus_info(const scalce_batch *b, int mate, uint64_t *nbytes, uint32_t *longest, uint64_t *repeats, uint64_t *literals);
 /* on = 1: every base letter and the quality under an N become an output of the run (the exception stream of --keep-bases).  The
  * archive stores a base in two bits: a c g t as A C G T, every other letter as A (getval, const.h:127, const.cpp:47-49); an
  * upper-case N survives only by forcing quality symbol 0 (qualities.cpp:183), and every symbol 0 comes back as N
@@ -386,9 +405,11 @@ enum {
   SCALCE_OUT_COMMENTS = 14, /* scalce_batch_set_keep_comments: what follows the name of the k-th emitted record of mate m, each entry
                                followed by a newline (mate 2 in mate 1's order); valid behind scalce_batch_emit, lean or not; empty
                                without the option */
-  SCALCE_OUT_EXCEPTIONS = 15 /* scalce_batch_set_keep_bases: the u64 entries of mate m in archive order, strictly ascending (letter |
+  SCALCE_OUT_EXCEPTIONS = 15,/* scalce_batch_set_keep_bases: the u64 entries of mate m in archive order, strictly ascending (letter |
                                values[q] << 8 | position << 16 | record << 28); valid behind scalce_batch_emit, lean or not; empty
                                without the option */
+  SCALCE_OUT_PLUS = 16       /* scalce_batch_set_keep_plus: the '+'-line entry of the k-th emitted record of mate m, each followed by a
+                                newline (mate 2 in mate 1's order); valid behind scalce_batch_emit, lean or not; empty without the option */
 };
 int scalce_batch_output(const scalce_batch *b, int which, int mate, const void **d_ptr, uint64_t *nbytes);
 /* Framing on the way out (replaces the copy loop of ac_write, arithmetic.cpp:318-363: the reference frames each coded
@@ -629,7 +650,7 @@ typedef struct {
   double total_s, setup_s, read_wait_s, decode_s, records_s, write_wait_s, write_s;
                                /* read_wait: in rd; decode / records: device time of the kernels; write_wait: the session
                                   waiting for a window buffer that wr still holds; write: inside wr */
-  int32_t error_mate, error_stream;  /* on failure: which stream of which mate (0 r, 1 n, 2 q, 3 l, 4 o, 5 c, 6 x), or -1 */
+  int32_t error_mate, error_stream;  /* on failure: which stream of which mate (0 r, 1 n, 2 q, 3 l, 4 o, 5 c, 6 x, 7 p), or -1 */
   int32_t error_wants_file;    /* the message in errbuf is a predicate: put the stream's file name in front of it */
   uint64_t decode_batches[2];  /* per mate: decoder batches enqueued (runs of whole frames, one scalce_ac_decoder_launch each) */
 } scalce_unpack_stats;
@@ -789,6 +810,50 @@ int scalce_stream_decompress_exceptions(scalce_ctx *ctx, const scalce_unpack_par
                                         const scalce_restore_params *rp /* NULL: archive order */, scalce_read_fn rd[2][3], void *user[2][3],
                                         scalce_write_fn wr, void *wr_user, scalce_unpack_stats *stats, scalce_unpack_range_stats *range_stats,
                                         scalce_restore_stats *restore_stats, char *errbuf, size_t errcap);
+
+/* ---- the '+' lines, back on the way out (archives made with --keep-plus; plusstream.hpp, kernels_plus.hpp) -----------------
+ * The plus-line stream (PREFIX_<m>.scalcep out of its container), one per mate: the 8 magic bytes, int32 0 (text entries, as in
+ * .scalcec), int32 P (the longest stored entry in bytes), int64 N, then N entries in archive order, each followed by a newline:
+ * SCALCE_OUT_PLUS.  P = 0: no entries follow, every record's line is bare.  plus_rd[m] delivers mate m's, header included; both
+ * NULL: no such streams.
+ *
+ * scalce_fastq_plus_window mirrors scalce_fastq_comment_window and runs BEHIND it and behind scalce_fastq_strip_window (both
+ * measure from the record's end and assume "\n+\n" between bases and qualities): d_text / d_record_offsets are a window's
+ * records of any header and read length (nrecords + 1 offsets; records with qualities), d_entries its entry_bytes bytes of the
+ * stream: nrecords entries, each followed by a newline, found on the device by a newline index.  A repeat grows its record by
+ * the header line as the text holds it (comments included when they were put back), a literal by its bytes.  d_out (out_cap
+ * bytes of room) receives the text, d_out_offsets (nrecords + 1) where each record begins in it and, last, its size.  *d_bad is
+ * set when the entries do not hold exactly nrecords newlines, when an entry's first byte is neither '=' nor '\'' or a '=' has
+ * bytes behind it (such records get a bare '+'), or when the text would outgrow out_cap (nothing is written then).  d_text,
+ * d_entries and d_out 16-byte aligned; d_ws: scalce_fastq_plus_ws_bytes(nrecords, entry_bytes) bytes.  Enqueued on `stream`;
+ * allocates nothing, waits for nothing.  _pairs mirrors scalce_fastq_comment_window_pairs: an interleaved window of npairs
+ * pairs of read_len[0] / read_len[1] bases; d_entries: 2 npairs entries, mate 1's then mate 2's of each pair.
+ *
+ * scalce_stream_decompress_plus is scalce_stream_decompress_exceptions with the plus-line streams beside the others; each may be
+ * NULL, range and rp as there.  Every mate has its stream (else SCALCE_ERR_ARG).  A record's entry is taken with the record and
+ * counts in the window's budget with what it adds to the text: the bound of a record's text grows by max(P - 1, the bound of
+ * its header line), device and pinned memory follow the window.  A range passes over the entries in front of it and reads none
+ * behind it.  Not with params no_qualities (two-line records have no such line: SCALCE_ERR_ARG).  Errors besides theirs:
+ * "(ERROR) truncated plus-line stream", "(ERROR) is not a scalce plus-line stream", "(ERROR) plus-line stream holds <n> entries,
+ * the archive <m> records", "(ERROR) plus-line stream: an entry is longer than its header says", "(ERROR) plus-line stream:
+ * malformed entry"; error_stream 7 names the plus-line stream. */
+uint64_t scalce_fastq_plus_ws_bytes(uint64_t nrecords, uint64_t entry_bytes);
+int scalce_fastq_plus_window(scalce_ctx *ctx, uint64_t nrecords, const uint8_t *d_text, const uint64_t *d_record_offsets,
+                             const uint8_t *d_entries, uint64_t entry_bytes, uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_offsets,
+                             uint32_t *d_bad, void *d_ws, void *stream);
+uint64_t scalce_fastq_plus_pairs_ws_bytes(uint64_t npairs, uint64_t entry_bytes);
+int scalce_fastq_plus_window_pairs(scalce_ctx *ctx, const int read_len[2], uint64_t npairs, const uint8_t *d_text,
+                                   const uint64_t *d_pair_offsets, const uint8_t *d_entries, uint64_t entry_bytes, uint8_t *d_out,
+                                   uint64_t out_cap, uint64_t *d_out_pair_offsets, uint32_t *d_bad, void *d_ws, void *stream);
+typedef struct {
+  scalce_read_fn plus_rd[2];
+  void *plus_user[2];
+} scalce_unpack_plus;
+int scalce_stream_decompress_plus(scalce_ctx *ctx, const scalce_unpack_params *p, const scalce_unpack_comments *comments /* NULL: none */,
+                                  const scalce_unpack_exceptions *exceptions /* NULL: none */, const scalce_unpack_plus *plus /* NULL: none */,
+                                  const scalce_unpack_range *range /* NULL: all */, const scalce_restore_params *rp /* NULL: archive order */,
+                                  scalce_read_fn rd[2][3], void *user[2][3], scalce_write_fn wr, void *wr_user, scalce_unpack_stats *stats,
+                                  scalce_unpack_range_stats *range_stats, scalce_restore_stats *restore_stats, char *errbuf, size_t errcap);
 
 /* ---- runs sharded over several GPUs: one process per GPU, ONE archive -----------------------------------------
  * The reference has no distributed mode; what it carries across reads is what ranks exchange (see comm.cpp).  The

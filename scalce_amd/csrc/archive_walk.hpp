@@ -12,6 +12,7 @@
 #include "../../include/scalce_hip.h"
 #include "commentstream.hpp"
 #include "lenstream.hpp"
+#include "plusstream.hpp"
 #include "stream_src.hpp"
 
 namespace scalce_host {
@@ -33,9 +34,9 @@ __attribute__((format(printf, 6, 7))) inline int failure(Failure &f, int rc, int
   f.rc = rc; f.msg = b; f.mate = mate; f.stream = stream; f.wants_file = wants_file;
   return rc;
 }
-// a stream that ends, or fails, before what is asked of it (stream: 0 r, 1 n, 2 q, 3 l, 4 o, 5 c, 6 x)
+// a stream that ends, or fails, before what is asked of it (stream: 0 r, 1 n, 2 q, 3 l, 4 o, 5 c, 6 x, 7 p)
 inline const char *stream_name(int stream) {
-  return stream == 0 ? "read" : stream == 1 ? "name" : stream == 2 ? "quality" : stream == 3 ? "length" : stream == 5 ? "comment" : stream == 6 ? "exception" : "order";
+  return stream == 0 ? "read" : stream == 1 ? "name" : stream == 2 ? "quality" : stream == 3 ? "length" : stream == 5 ? "comment" : stream == 6 ? "exception" : stream == 7 ? "plus-line" : "order";
 }
 inline int read_error(Failure &f, int m, int stream) { return failure(f, SCALCE_ERR_FORMAT, m, stream, 0, "read error on the %s stream", stream_name(stream)); }
 inline int truncated(Failure &f, int m, int stream) { return failure(f, SCALCE_ERR_FORMAT, m, stream, 0, "(ERROR) truncated %s stream", stream_name(stream)); }
@@ -70,6 +71,11 @@ struct ArcMate {
   u32 c_longest = 0;         // its header's C: the longest entry, without the newline
   u64 c_total = 0, c_taken = 0;  // its header's N; entries taken or passed over so far
   u64 c_delivered = 0, c_skipped = 0;
+  Src p;                     // the plus-line stream of an archive made with --keep-plus (scalce_unpack_plus), or not open
+  bool has_plus = false;
+  u32 p_longest = 0;         // its header's P: the longest stored entry, without the newline (0: no entries follow)
+  u64 p_total = 0, p_taken = 0;  // its header's N; entries taken or passed over so far
+  u64 p_delivered = 0, p_skipped = 0;
   int L = 0, no_ac = 0;
   int64_t phred = 0;
   bool q_empty = false;
@@ -90,6 +96,8 @@ struct ReadsDst {
 struct NamesDst { u8 *bytes; u64 *off; u64 cap; };
 // ... and its entries of the comment stream, each with its newline, as the stream holds them
 struct CommentsDst { u8 *bytes; u64 cap; u64 nbytes = 0; };
+// ... and of the plus-line stream, the same; grow = what they add to the window's text
+struct PlusDst { u8 *bytes; u64 cap; u64 nbytes = 0; u64 grow = 0; };
 
 // The arithmetic of a range over the coded quality stream, without a device call: symbols [first * L, (first + n) * L) of a
 // stream of total_syms symbols in frames of SCALCE_AC_BLOCK.  first and n are clamped to the total_syms / L records the stream
@@ -356,10 +364,105 @@ struct Walk {
     return failure(f, SCALCE_ERR_FORMAT, m, 5, 0, "(ERROR) %s", b);
   }
 
+  // ---- the plus-line stream (plusstream.hpp): a sixth cursor of the mate, walked like the comment stream ---------------------
+  int plus_open(int m, scalce_read_fn rd, void *user, double *wait, Failure &f) {
+    ArcMate &x = *M[m];
+    x.p.open(rd, nullptr, user, wait, &x.p_delivered, &x.p_skipped);
+    const bool whole = x.p.need(PLUS_HEADER_BYTES);
+    if (x.p.bad) return read_error(f, m, 7);
+    if (const char *why = plus_header_read(x.p.ptr(), whole ? PLUS_HEADER_BYTES : 0, &x.p_longest, &x.p_total))
+      return failure(f, SCALCE_ERR_FORMAT, m, 7, 0, "(ERROR) %s", why);
+    x.p.skip(PLUS_HEADER_BYTES);
+    x.has_plus = true;
+    x.p_taken = 0;
+    return SCALCE_OK;
+  }
+  // the next entry where it lies in the look-ahead buffer: at = its bytes, len = how many with the newline, cls = what it is.
+  // 0: there it is; 1: the stream ends here, between two entries; else the failure.  A stream with P = 0 holds no entries:
+  // every record's is the empty one.
+  int next_plus(int m, const u8 *&at, size_t &len, PlusClass &cls, Failure &f) {
+    static const u8 bare[1] = {'\n'};
+    ArcMate &x = *M[m];
+    if (!x.p_longest) {
+      if (x.p_taken >= x.p_total) return 1;
+      at = bare; len = 1; cls = PLUS_BARE;
+      return 0;
+    }
+    Src &c = x.p;
+    size_t seen = 0;
+    for (;;) {
+      const size_t have = c.avail();
+      if (have > seen) {
+        const void *nl = memchr(c.ptr() + seen, '\n', have - seen);
+        if (nl) {
+          len = (size_t)((const u8 *)nl - c.ptr()) + 1;
+          if (len - 1 > x.p_longest) return failure(f, SCALCE_ERR_FORMAT, m, 7, 0, "(ERROR) %s", plus_entry_too_long());
+          at = c.ptr();
+          cls = plus_class(at, len - 1);
+          if (cls == PLUS_MALFORMED) return failure(f, SCALCE_ERR_FORMAT, m, 7, 0, "(ERROR) %s", plus_malformed());
+          return 0;
+        }
+        seen = have;
+      }
+      if (seen > x.p_longest) return failure(f, SCALCE_ERR_FORMAT, m, 7, 0, "(ERROR) %s", plus_entry_too_long());
+      if (!c.need(seen + 1)) {
+        if (c.bad) return read_error(f, m, 7);
+        return seen ? truncated(f, m, 7) : 1;
+      }
+    }
+  }
+  void plus_taken(int m, size_t len) {
+    ArcMate &x = *M[m];
+    if (x.p_longest) x.p.skip(len);
+    x.p_taken++;
+  }
+  // entries in front of a range: passed over on the host by their newlines; none behind the range is read
+  int pass_plus(int m, u64 n, u64 &got, Failure &f) {
+    for (got = 0; got < n; got++) {
+      const u8 *at;
+      size_t len = 0;
+      PlusClass cls;
+      const int e = next_plus(m, at, len, cls, f);
+      if (e == 1) break;
+      if (e) return e;
+      plus_taken(m, len);
+    }
+    return SCALCE_OK;
+  }
+  int plus_count(int m, u64 entries, u64 records, Failure &f) const {
+    char b[200];
+    plus_count_message(b, sizeof b, entries, records);
+    return failure(f, SCALCE_ERR_FORMAT, m, 7, 0, "(ERROR) %s", b);
+  }
+  // One record's (pair's) entries into `to`, if they and what they add fit: header[i] = the bytes of mate i's header line behind
+  // its '@' as this run writes it, which is what a repeat adds.  grow = what the entries add to the text.  0: peeked (nothing is
+  // consumed before plus_commit); 1: mate 1's stream ends here, between two entries; else the failure.
+  struct PlusPeek { const u8 *at[2]; size_t len[2] = {0, 0}; PlusClass cls[2] = {PLUS_BARE, PLUS_BARE}; u64 grow = 0; };
+  int plus_peek(const u64 header[2], PlusPeek &k, Failure &f) {
+    k.grow = 0;
+    for (int i = 0; i <= m1 - m0; i++) {
+      const int e = next_plus(m0 + i, k.at[i], k.len[i], k.cls[i], f);
+      if (e == 1 && i) return truncated(f, m0 + i, 7);
+      if (e) return e;
+      k.grow += plus_growth(k.cls[i], k.len[i] - 1, header[i]);
+    }
+    return SCALCE_OK;
+  }
+  bool plus_fits(const PlusDst &to, const PlusPeek &k) const { return to.nbytes + k.len[0] + k.len[1] <= to.cap; }
+  void plus_commit(PlusDst &to, const PlusPeek &k) {
+    for (int i = 0; i <= m1 - m0; i++) {
+      memcpy(to.bytes + to.nbytes, k.at[i], k.len[i]);
+      to.nbytes += k.len[i];
+      plus_taken(m0 + i, k.len[i]);
+    }
+    to.grow += k.grow;
+  }
+
   // names of up to `ncap` records (pairs) of the pass's mates into to[], as many as W bytes of text take; n = how many.
   // com: each record's entry of the comment stream is taken in the same step and counts in the budget (two mates in one window:
   // mate 1's entry, then mate 2's, pair by pair -- the order of the records in the interleaved text)
-  int take_names(NamesDst to[2], u64 ncap, u64 W, u64 &n, u64 nb[2], Failure &f, CommentsDst *com = nullptr) {
+  // plus: the same for each record's entry of the plus-line stream, with what it adds to the record's text
+  int take_names(NamesDst to[2], u64 ncap, u64 W, u64 &n, u64 nb[2], Failure &f, CommentsDst *com = nullptr, PlusDst *plus = nullptr) {
     u64 text = 0;
     nb[0] = nb[1] = 0;
     n = 0;
@@ -382,6 +485,12 @@ struct Walk {
         if (e) return e;
         rec += clen[i] - 1;
       }
+      PlusPeek pk;
+      if (plus && !ended) {
+        const u64 header[2] = {len[0] + (clen[0] ? clen[0] - 1 : 0), len[1] + (clen[1] ? clen[1] - 1 : 0)};
+        if (const int e = plus_peek(header, pk, f)) return e == 1 ? truncated(f, m0, 7) : e;
+        rec += pk.grow;
+      }
       if (ended) {
         for (int i = 0; i < nmates; i++) if (M[m0 + i]->n.bad) return read_error(f, m0 + i, 1);
         if (!decides_count(m0, 1) || ended != nmates) return truncated(f, m0, 1);
@@ -391,7 +500,9 @@ struct Walk {
       bool fits = true;
       for (int i = 0; i < nmates; i++) fits = fits && nb[i] + 1 + len[i] <= to[i].cap;
       if (com) fits = fits && com->nbytes + clen[0] + clen[1] <= com->cap;
+      if (plus) fits = fits && plus_fits(*plus, pk);
       if (!fits) break;
+      if (plus) plus_commit(*plus, pk);
       for (int i = 0; i < nmates && com; i++) {
         memcpy(com->bytes + com->nbytes, M[m0 + i]->c.ptr(), clen[i]);
         M[m0 + i]->c.skip(clen[i]);

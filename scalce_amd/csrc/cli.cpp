@@ -32,6 +32,7 @@
 #include "cli_shares.hpp"
 #include "cli_sink.hpp"
 #include "cli_comments.hpp"
+#include "cli_plus.hpp"
 #include "cli_exceptions.hpp"
 
 #ifndef SCALCE_VERSION
@@ -55,6 +56,9 @@ struct Options {
   bool archive_order = false;             // -d --archive-order: a .scalceo next to the archive is ignored
   bool keep_comments = false;             // --keep-comments: what follows every record's name, in PREFIX_<m>.scalcec
   bool no_comments = false;               // -d --no-comments: a .scalcec next to the archive is ignored
+  bool keep_plus = false;                 // --keep-plus: what stood on every record's '+' line, in PREFIX_<m>.scalcep
+  bool bare_plus = false;                 // -d --bare-plus: a .scalcep next to the archive is ignored
+  bool lossless = false;                  // --lossless: --keep-order --keep-comments --keep-bases --keep-plus (-f: without the last)
   bool keep_bases = false;                // --keep-bases: every letter and quality the archive does not keep, in PREFIX_<m>.scalcex
   bool stored_bases = false;              // -d --stored-bases: a .scalcex next to the archive is ignored
   bool temp_given = false;                // -t was given (the default of `temp` is the reference's)
@@ -93,6 +97,12 @@ static const char *HELP_TEXT =
     "                              without the option writes.  Decompression finds the .scalcec by itself and puts the comments\n"
     "                              back; the '+' line stays a bare '+'.  Not with -n, --gpus\n"
     "      --no-comments           decompression: ignore the .scalcec, write the names alone\n"
+    "      --keep-plus             keep every record's third line: a bare '+', a repeat of the header line, or a line of its own goes\n"
+    "                              into OUTPUT_<m>.scalcep, every other file is the one the run without the option writes.\n"
+    "                              Decompression finds the .scalcep by itself and puts the lines back.  Not with -f, -Q, --gpus\n"
+    "      --bare-plus             decompression: ignore the .scalcep, write a bare '+'\n"
+    "      --lossless              --keep-order --keep-comments --keep-bases --keep-plus: scalce -d returns the input byte for\n"
+    "                              byte.  Not with -p above 0, -n, -Q, --gpus\n"
     "      --keep-bases            keep every base letter and the quality under an N: the archive stores a c g t as A C G T, every\n"
     "                              other letter as A, an N only through its quality, and returns a base whose quality maps to the\n"
     "                              lowest as N.  What it changes goes into OUTPUT_<m>.scalcex, every other file is the one the\n"
@@ -133,6 +143,9 @@ static const char *HELP_TEXT =
 //                       the name of each record of the archive, from the first space on, each entry followed by a newline
 //   PREFIX_<m>.scalcex  --keep-bases only (exceptionstream.hpp): magic, int32 8, int32 L, int64 N, int64 X, then X x u64 in ascending
 //                       order: letter | quality character << 8 | position << 16 | record of the archive << 28
+//   PREFIX_<m>.scalcep  --keep-plus only (plusstream.hpp): magic, int32 0, int32 P (longest stored entry), int64 N, then the '+' line
+//                       of each record of the archive as an entry (empty: bare, '=': the header line again, '\'' + the line's
+//                       bytes), each followed by a newline; P = 0: no entries
 //   PREFIX_<m>.scalceq  magic, int64 Phred offset (mate 1's for both mates, compress.cpp:294,816-817); arithmetic coded:
 //                       the scaled table (QTABLE_WORDS x u32), the int64 symbol count and the coded blocks; -A: the q' rows
 static const uint8_t MAGIC[8] = {'s', 'c', 'a', 'l', 'c', 'e', '2', '2'};
@@ -371,6 +384,15 @@ struct MateFiles {
     down.to_file(ctx, b, SCALCE_OUT_COMMENTS, m, fC);
     fC.close();
   }
+  void write_plus(int m, Downloader &down, uint64_t N) const {  // --keep-plus: the '+' lines as entries, in archive order
+    OutFile fP;
+    fP.open(archive_path(o.out, m, 'p'), gz_container(o, 'p'));
+    uint32_t longest = 0;
+    SCOK(ctx, scalce_batch_plus_info(b, m, nullptr, &longest, nullptr, nullptr));
+    plus_file_header(fP, longest, N);
+    if (longest) down.to_file(ctx, b, SCALCE_OUT_PLUS, m, fP);  // (P = 0: every line was bare, the file is its header)
+    fP.close();
+  }
   void write_exceptions(int m, Downloader &down, uint64_t N) const {  // --keep-bases: what the archive does not keep, in archive order
     OutFile fX;
     fX.open(archive_path(o.out, m, 'x'), gz_container(o, 'x'));
@@ -444,7 +466,8 @@ static int do_compress(const Options &o, const std::vector<std::string> &files, 
   const double t1 = now();
   if (scalce_stream_compress(ctx, &p, MateSource::read_cb, &in.src[0], nsrc == 2 ? MateSource::read_cb : nullptr, nsrc == 2 ? &in.src[1] : nullptr,
                              piece, hint, SCALCE_STREAM_LEAN | SCALCE_STREAM_DEFER_ENTROPY | (o.keep_order ? SCALCE_STREAM_KEEP_ORDER : 0) |
-                                 (o.keep_comments ? SCALCE_STREAM_KEEP_COMMENTS : 0) | (o.keep_bases ? SCALCE_STREAM_KEEP_BASES : 0), &b, &ss, emsg, sizeof emsg)) {
+                                 (o.keep_comments ? SCALCE_STREAM_KEEP_COMMENTS : 0) | (o.keep_bases ? SCALCE_STREAM_KEEP_BASES : 0) |
+                                 (o.keep_plus ? SCALCE_STREAM_KEEP_PLUS : 0), &b, &ss, emsg, sizeof emsg)) {
     if (!in.src[0].error.empty()) fputs(in.src[0].error.c_str(), stderr);  // (-i: a file of odd record count; the stream only saw a read error)
     else fprintf(stderr, "%s\n", emsg[0] ? emsg : scalce_last_error(ctx));
     exit(1);
@@ -477,11 +500,13 @@ static int do_compress(const Options &o, const std::vector<std::string> &files, 
     if (o.keep_order && m == 0) w.write_order();
     if (o.keep_comments) w.write_comments(m, *downs[m], N);
     if (o.keep_bases) w.write_exceptions(m, *downs[m], N);
+    if (o.keep_plus) w.write_plus(m, *downs[m], N);
   });
   // (an order stream left under this prefix by an earlier run does not belong to this archive, nor do comment streams)
   if (!o.keep_order) unlink(archive_path(o.out, 0, 'o').c_str());
   if (!o.keep_comments) for_each_archive_file(o, "c", [](char, const std::string &fn) { unlink(fn.c_str()); });
   if (!o.keep_bases) for_each_archive_file(o, "x", [](char, const std::string &fn) { unlink(fn.c_str()); });
+  if (!o.keep_plus) for_each_archive_file(o, "p", [](char, const std::string &fn) { unlink(fn.c_str()); });
   const double t2b = now();
   SCOK(ctx, scalce_batch_finish(b, s_ent));  // the coder is through: sizes of the coded streams, device error word
   const double t2c = now();
@@ -491,7 +516,7 @@ static int do_compress(const Options &o, const std::vector<std::string> &files, 
   });
   const double t2d = now();
   uint64_t new_size = 0;
-  const std::string exts = std::string("rnql") + (o.keep_order ? "o" : "") + (o.keep_comments ? "c" : "") + (o.keep_bases ? "x" : "");
+  const std::string exts = std::string("rnql") + (o.keep_order ? "o" : "") + (o.keep_comments ? "c" : "") + (o.keep_bases ? "x" : "") + (o.keep_plus ? "p" : "");
   for_each_archive_file(o, exts.c_str(), [&](char, const std::string &fn) {
     struct stat st;
     if (stat(fn.c_str(), &st) == 0) new_size += (uint64_t)st.st_size;
@@ -507,11 +532,15 @@ static int do_compress(const Options &o, const std::vector<std::string> &files, 
   for (int m = 0; m < nm && o.keep_comments; m++) SCOK(ctx, scalce_batch_comments_info(b, m, &com_bytes[m], &com_longest[m]));
   uint64_t exc_entries[2] = {0, 0}, exc_rows[2] = {0, 0};
   for (int m = 0; m < nm && o.keep_bases; m++) SCOK(ctx, scalce_batch_exceptions_info(b, m, &exc_entries[m], &exc_rows[m]));
+  uint32_t plus_longest[2] = {0, 0};
+  uint64_t plus_rep[2] = {0, 0}, plus_lit[2] = {0, 0};
+  for (int m = 0; m < nm && o.keep_plus; m++) SCOK(ctx, scalce_batch_plus_info(b, m, nullptr, &plus_longest[m], &plus_rep[m], &plus_lit[m]));
   scalce_batch_destroy(b);
   const double t3 = now();
   log_statistics(o, p, N, unbucketed);
   for (int m = 0; m < nm && o.keep_bases; m++) exception_log(N, exc_entries[m], exc_rows[m]);
   for (int m = 0; m < nm && o.keep_comments; m++) comment_log(N, com_bytes[m], com_longest[m]);
+  for (int m = 0; m < nm && o.keep_plus; m++) plus_log(N, plus_rep[m], plus_lit[m], plus_longest[m]);
   LOG("\tSpill chunks: %u, pieces streamed: %llu\n", st4[3], (unsigned long long)ss.rounds);
   LOG("\tTime elapsed: %.2f s (sample %.2f; stream %.2f = waiting for the reader %.2f + for uploads %.2f + ingest/count/tokenize %.2f; "
       "order %.2f, emit %.2f; reads+names down and written beside the coder %.2f, waiting for the coder %.2f, qualities down and written %.2f, device buffers released %.2f)\n",
@@ -889,6 +918,8 @@ struct Archive {
   ArchiveFile comments[2];
   bool has_exceptions = false;  // every mate has a PREFIX_<m>.scalcex next to its .scalcen (and --stored-bases does not set them aside)
   ArchiveFile exceptions[2];
+  bool has_plus = false;  // every mate has a PREFIX_<m>.scalcep next to its .scalcen (and neither --bare-plus nor -Q / -f sets them aside)
+  ArchiveFile plus[2];
   ArchiveFile files[2][3], lens[2], order[2];  // (a mate pass reads the order stream from its start: one handle each)
   scalce_read_fn rd[2][3];
   void *user[2][3];
@@ -926,6 +957,10 @@ struct Archive {
     has_exceptions = !o.stored_bases;
     for (int m = 0; m < nm && has_exceptions; m++) has_exceptions = exception_file_present(scalce_name(base[m], 'x'));
     for (int m = 0; m < nm && has_exceptions; m++) exceptions[m].open(scalce_name(base[m], 'x'));
+    // the '+' lines: put back when every mate has its stream and the records that go out have such a line
+    has_plus = !o.bare_plus && !o.no_qual && !o.fasta;
+    for (int m = 0; m < nm && has_plus; m++) has_plus = plus_file_present(scalce_name(base[m], 'p'));
+    for (int m = 0; m < nm && has_plus; m++) plus[m].open(scalce_name(base[m], 'p'));
   }
 };
 // One path for every archive: scalce_stream_decompress moves it through the device in windows of whole records.  The read
@@ -952,7 +987,11 @@ static int do_decompress(const Options &o, const std::string &path, scalce_ctx *
   for (int m = 0; m < nm && ar.has_exceptions; m++) { ex.exc_rd[m] = ArchiveFile::read; ex.exc_user[m] = &ar.exceptions[m]; }
   const scalce_unpack_comments *cmp = ar.has_comments ? &cm : nullptr;
   const scalce_unpack_exceptions *exp = ar.has_exceptions ? &ex : nullptr;
-  const bool side = ar.has_comments || ar.has_exceptions;
+  scalce_unpack_plus pl;
+  memset(&pl, 0, sizeof pl);
+  for (int m = 0; m < nm && ar.has_plus; m++) { pl.plus_rd[m] = ArchiveFile::read; pl.plus_user[m] = &ar.plus[m]; }
+  const scalce_unpack_plus *plp = ar.has_plus ? &pl : nullptr;
+  const bool side = ar.has_comments || ar.has_exceptions || ar.has_plus;
   if (ar.has_order) {  // the input order back: two passes through a spill under -t, next to the output, or in $TMPDIR
     scalce_restore_params rp;
     memset(&rp, 0, sizeof rp);
@@ -969,11 +1008,11 @@ static int do_decompress(const Options &o, const std::string &path, scalce_ctx *
     }
     rp.spill_dir = spill_dir.c_str();
     memset(&rs, 0, sizeof rs);
-    // (side streams: the one entry point that takes comments and exceptions, either or both; else the call as it always was)
-    rc = side ? scalce_stream_decompress_exceptions(ctx, &p, cmp, exp, nullptr, &rp, ar.rd, ar.user, TextSink::write, &sink, &st, nullptr, &os, err, sizeof err)
+    // (side streams: the one entry point that takes comments, exceptions and '+' lines, any of them; else the call as it always was)
+    rc = side ? scalce_stream_decompress_plus(ctx, &p, cmp, exp, plp, nullptr, &rp, ar.rd, ar.user, TextSink::write, &sink, &st, nullptr, &os, err, sizeof err)
               : scalce_stream_decompress_restore(ctx, &p, &rp, ar.rd, ar.user, TextSink::write, &sink, &st, &os, err, sizeof err);
   } else
-    rc = side ? scalce_stream_decompress_exceptions(ctx, &p, cmp, exp, &rg, nullptr, ar.rd, ar.user, TextSink::write, &sink, &st, &rs, nullptr, err, sizeof err)
+    rc = side ? scalce_stream_decompress_plus(ctx, &p, cmp, exp, plp, &rg, nullptr, ar.rd, ar.user, TextSink::write, &sink, &st, &rs, nullptr, err, sizeof err)
               : scalce_stream_decompress_range(ctx, &p, &rg, ar.rd, ar.user, TextSink::write, &sink, &st, &rs, err, sizeof err);
   if (rc) {
     // (parts already written stay where they are)
@@ -981,6 +1020,8 @@ static int do_decompress(const Options &o, const std::string &path, scalce_ctx *
       FAIL("%s %s\n", ar.comments[st.error_mate].path.c_str(), err + 8);
     if (st.error_stream == 6 && st.error_mate >= 0 && !strncmp(err, "(ERROR) is not", 14))  // (... about the exception stream's)
       FAIL("%s %s\n", ar.exceptions[st.error_mate].path.c_str(), err + 8);
+    if (st.error_stream == 7 && st.error_mate >= 0 && !strncmp(err, "(ERROR) is not", 14))  // (... about the plus-line stream's)
+      FAIL("%s %s\n", ar.plus[st.error_mate].path.c_str(), err + 8);
     if (st.error_wants_file && st.error_mate >= 0 && st.error_stream >= 0 && st.error_stream < 3)
       FAIL("%s %s\n", st.error_stream == 0 ? ar.base[st.error_mate].c_str() : ar.files[st.error_mate][st.error_stream].path.c_str(), err);
     fprintf(stderr, "%s%s\n", strncmp(err, "(ERROR)", 7) ? "(ERROR) " : "", err);
@@ -1050,7 +1091,8 @@ static bool parse_options(int argc, char **argv, Options &o) {
                                      {"max-length", 1, 0, 1005}, {"keep-order", 0, 0, 1006},
                                      {"archive-order", 0, 0, 1007}, {"keep-comments", 0, 0, 1008},
                                      {"no-comments", 0, 0, 1009}, {"keep-bases", 0, 0, 1010},
-                                     {"stored-bases", 0, 0, 1011}, {0, 0, 0, 0}};
+                                     {"stored-bases", 0, 0, 1011}, {"keep-plus", 0, 0, 1012},
+                                     {"bare-plus", 0, 0, 1013}, {"lossless", 0, 0, 1014}, {0, 0, 0, 0}};
   int opt;
   while ((opt = getopt_long(argc, argv, "vhp:T:dc:o:fs:t:B:rQAn:P:S:i", long_opt, 0)) != -1) {
     switch (opt) {
@@ -1093,8 +1135,15 @@ static bool parse_options(int argc, char **argv, Options &o) {
       case 1009: o.no_comments = true; break;
       case 1010: o.keep_bases = true; break;
       case 1011: o.stored_bases = true; break;
+      case 1012: o.keep_plus = true; break;
+      case 1013: o.bare_plus = true; break;
+      case 1014: o.lossless = true; break;
       default: fputs(HELP_TEXT, stdout); return false;
     }
+  }
+  if (o.lossless) {  // (FASTA has no '+' line: there the three are the input)
+    o.keep_order = o.keep_comments = o.keep_bases = true;
+    if (!o.fasta) o.keep_plus = true;
   }
   return true;
 }
@@ -1104,6 +1153,18 @@ static void check_arguments(const Options &o, const std::vector<std::string> &fi
   if (o.out.empty()) FAIL("No output file specified.\n");
   if (!o.use_names && o.library.empty()) FAIL("No library name specified.\n");
   if (o.has_range && !o.decompress) FAIL("--records can be only used with decompression (-d).\n");
+  if (o.lossless) {  // (in front of the single options' refusals: each of these says why the promise cannot be kept)
+    if (o.decompress) FAIL("--lossless is an option of compression: -d puts everything back by itself when the archive has the streams\n");
+    if (o.lossy != 0) FAIL("--lossless with -p %d: the lossy quality transform changes qualities, the input would not come back\n", o.lossy);
+    if (!o.use_names) FAIL("--lossless with -n: names that are not kept cannot come back\n");
+    if (o.no_qual) FAIL("--lossless with -Q: qualities that are not kept cannot come back\n");
+    if (o.gpus > 1) FAIL("--lossless runs on one GPU: with --gpus %d the order, comments, exceptions and '+' lines lie spread over the ranks\n", o.gpus);
+  }
+  if (o.keep_plus && o.decompress) FAIL("--keep-plus is an option of compression: -d puts the '+' lines back by itself when the archive has a .scalcep\n");
+  if (o.bare_plus && !o.decompress) FAIL("--bare-plus can be only used with decompression (-d).\n");
+  if (o.keep_plus && o.fasta) FAIL("--keep-plus with -f: FASTA records have no '+' line to keep\n");
+  if (o.keep_plus && o.no_qual) FAIL("--keep-plus with -Q: the records are kept as two lines, there is no '+' line to keep\n");
+  if (o.keep_plus && o.gpus > 1) FAIL("--keep-plus runs on one GPU: with --gpus %d the '+' lines lie spread over the ranks\n", o.gpus);
   if (o.keep_order && o.decompress) FAIL("--keep-order is an option of compression: -d restores the order by itself when the archive has a .scalceo\n");
   if (o.archive_order && !o.decompress) FAIL("--archive-order can be only used with decompression (-d).\n");
   if (o.keep_order && o.gpus > 1) FAIL("--keep-order runs on one GPU: with --gpus %d the permutation lies spread over the ranks\n", o.gpus);

@@ -189,6 +189,10 @@ extern "C" int scalce_batch_output(const scalce_batch *b, int which, int mate, c
       *d_ptr = b->keep_bases ? b->out_exc[mate].p : nullptr;
       *nbytes = b->keep_bases && b->out_exc[mate].p ? sizeof(u64) * b->out_exc_entries[mate] : 0;
       break;
+    case SCALCE_OUT_PLUS:
+      *d_ptr = b->keep_plus ? b->out_plus[mate].p : nullptr;
+      *nbytes = b->keep_plus && b->out_plus[mate].p ? b->out_plus_bytes[mate] : 0;
+      break;
     case SCALCE_OUT_NAMECELLS: *d_ptr = w.namecell.p; *nbytes = b->p.use_names && w.namecell.p ? 16 * b->N : 0; break;
     default: return SCALCE_ERR_ARG;
   }

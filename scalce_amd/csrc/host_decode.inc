@@ -509,3 +509,75 @@ extern "C" int scalce_fastq_exception_window_pairs(scalce_ctx *c, const int read
   }
   return launch_failed(c);
 }
+
+// ---- the '+' lines, back in a window's text (archives made with --keep-plus; kernels_plus.hpp) --------------------------------
+// scratch of scalce_fastq_plus_window, in 64-bit words: what the comment insert takes (tiles, scans, the count, the newline
+// index) and one more word per record: where its '+' lies
+extern "C" uint64_t scalce_fastq_plus_ws_bytes(uint64_t nrecords, uint64_t entry_bytes) {
+  return scalce_fastq_comment_ws_bytes(nrecords, entry_bytes) + sizeof(u64) * (nrecords + 8);
+}
+static int plus_window(scalce_ctx *c, uint64_t nrecords, const uint8_t *d_text, const uint64_t *d_record_offsets, const uint8_t *d_entries,
+                       uint64_t entry_bytes, uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_offsets, uint32_t *d_bad, void *d_ws, hipStream_t s) {
+  u64 *tile = static_cast<u64 *>(d_ws), *scan = tile + comment_ws_tiles(entry_bytes), *nlines = scan + comment_ws_scan(nrecords, entry_bytes);
+  u64 *ent_end = nlines + 8, *plus_at = ent_end + nrecords + 8;
+  // the newline index of the entries, and the verdict on their count, as the comment insert makes them
+  HIP_TRY(c, hipMemsetAsync(nlines, 0, sizeof(u64) * (8 + nrecords), s));
+  const u32 ntiles = cdiv(entry_bytes, IDX_TILE);
+  if (ntiles) {
+    LAUNCH(index_count_k, ntiles, IDX_THREADS, 0, s, d_entries, entry_bytes, tile);
+    exclusive_scan<u64>(LoadAs<u64, u64>{tile}, ntiles, StoreTo<u64>{tile}, scan, nlines, s);
+    LAUNCH(index_write_k, ntiles, IDX_THREADS, 0, s, d_entries, entry_bytes, tile, ent_end, nrecords);
+  }
+  LAUNCH(insert_check_k, 1, 1, 0, s, nlines, d_entries, entry_bytes, nrecords, d_bad);
+  PlusArgs a;
+  a.text = d_text; a.rec_off = reinterpret_cast<const u64 *>(d_record_offsets); a.entries = d_entries; a.entry_bytes = entry_bytes;
+  a.ent_end = ent_end; a.nrec = nrecords; a.plus_at = plus_at; a.dst_off = reinterpret_cast<u64 *>(d_out_offsets); a.dst = d_out;
+  a.dst_cap = out_cap; a.bad = d_bad;
+  if (nrecords) LAUNCH(plus_insert_plan_k, cdiv(nrecords, 256), 256, 0, s, a);
+  exclusive_scan<u64>(LoadAs<u64, u64>{a.dst_off}, nrecords, StoreTo<u64>{a.dst_off}, scan, a.dst_off + nrecords, s);
+  // (the grid covers the room the caller gave; the workgroups behind the text's end return at once)
+  if (nrecords && out_cap) LAUNCH(plus_insert_copy_k, cdiv(out_cap, VL_SPAN), 256, 0, s, a);
+  return launch_failed(c);
+}
+static int plus_window_args(scalce_ctx *c, uint64_t n, const uint8_t *d_text, const uint64_t *d_off, const uint8_t *d_entries, uint64_t entry_bytes,
+                            uint8_t *d_out, uint64_t *d_out_off, uint32_t *d_bad, void *d_ws) {
+  if (!c || !d_out_off || !d_bad || !d_ws || n > 0x7FFFFFFFull) return SCALCE_ERR_ARG;
+  if (n && (!d_text || !d_off || !d_out)) return SCALCE_ERR_ARG;
+  if (entry_bytes && !d_entries) return SCALCE_ERR_ARG;
+  if (((uintptr_t)d_text & 15) || ((uintptr_t)d_out & 15) || ((uintptr_t)d_entries & 15)) {
+    set_err(c, "plus lines: the window's texts and its entries must be 16-byte aligned");
+    return SCALCE_ERR_ARG;
+  }
+  return SCALCE_OK;
+}
+extern "C" int scalce_fastq_plus_window(scalce_ctx *c, uint64_t nrecords, const uint8_t *d_text, const uint64_t *d_record_offsets,
+                                        const uint8_t *d_entries, uint64_t entry_bytes, uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_offsets,
+                                        uint32_t *d_bad, void *d_ws, void *stream) {
+  if (int rc = plus_window_args(c, nrecords, d_text, d_record_offsets, d_entries, entry_bytes, d_out, d_out_offsets, d_bad, d_ws)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  HIP_TRY(c, hipSetDevice(c->device));
+  return plus_window(c, nrecords, d_text, d_record_offsets, d_entries, entry_bytes, d_out, out_cap, d_out_offsets, d_bad, d_ws, s);
+}
+// The same for an interleaved window: 2 npairs records, mate 1's the even ones, and their entries in that order.  The records'
+// own offsets are made from the pairs' (mate 1's record is its header line and 2 read_len[0] + 5 bytes), and the pairs' new
+// offsets taken from the records' new ones.
+extern "C" uint64_t scalce_fastq_plus_pairs_ws_bytes(uint64_t npairs, uint64_t entry_bytes) {
+  return scalce_fastq_plus_ws_bytes(2 * npairs, entry_bytes) + sizeof(u64) * 2 * comment_pairs_words(npairs);
+}
+extern "C" int scalce_fastq_plus_window_pairs(scalce_ctx *c, const int read_len[2], uint64_t npairs, const uint8_t *d_text,
+                                              const uint64_t *d_pair_offsets, const uint8_t *d_entries, uint64_t entry_bytes, uint8_t *d_out,
+                                              uint64_t out_cap, uint64_t *d_out_pair_offsets, uint32_t *d_bad, void *d_ws, void *stream) {
+  if (!read_len || npairs > 0x3FFFFFFFull) return SCALCE_ERR_ARG;
+  for (int m = 0; m < 2; m++) if (read_len[m] <= 0 || read_len[m] > 65535) return SCALCE_ERR_ARG;
+  if (int rc = plus_window_args(c, npairs, d_text, d_pair_offsets, d_entries, entry_bytes, d_out, d_out_pair_offsets, d_bad, d_ws)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  HIP_TRY(c, hipSetDevice(c->device));
+  u64 *rec_off = reinterpret_cast<u64 *>(static_cast<u8 *>(d_ws) + scalce_fastq_plus_ws_bytes(2 * npairs, entry_bytes));
+  u64 *new_off = rec_off + comment_pairs_words(npairs);
+  LAUNCH(plus_pair_split_k, cdiv(npairs + 1, 256), 256, 0, s, npairs, d_text, reinterpret_cast<const u64 *>(d_pair_offsets), (u64)read_len[0], rec_off);
+  const int rc = plus_window(c, 2 * npairs, d_text, reinterpret_cast<const uint64_t *>(rec_off), d_entries, entry_bytes, d_out, out_cap,
+                             reinterpret_cast<uint64_t *>(new_off), d_bad, d_ws, s);
+  if (rc) return rc;
+  LAUNCH(pair_offsets_k, cdiv(npairs + 1, 256), 256, 0, s, npairs, new_off, reinterpret_cast<u64 *>(d_out_pair_offsets));
+  return launch_failed(c);
+}

@@ -76,6 +76,43 @@ static int piece_comments(scalce_batch *b, int mate, const u8 *d_text, u64 nbyte
   return SCALCE_OK;
 }
 
+// --keep-plus: the third lines of the piece's first `nrec` rows, as entries (kernels_plus.hpp), go behind mate m's entries of
+// earlier pieces (plus_in[m], input order); pluslen[m] keeps the stored lengths per row.  The shape of piece_comments: a plan
+// pass (class and length; the two errors of the option), one exclusive scan of length + 1, one extract pass.
+static int piece_plus(scalce_batch *b, int mate, const u8 *d_text, u64 nbytes, u64 nrec, hipStream_t s) {
+  scalce_workspace &w = *b->ws;
+  scalce_ctx *c = b->ctx;
+  { int rc = ensure_line_index(b, mate, s); if (rc) return rc; }
+  ENSURE(b, b->com_piece_off, sizeof(u64) * (nrec + 8));
+  ENSURE(b, w.scan_ws, sizeof(u64) * (scan_ws_elems(nrec) + 64));
+  for (int m = mate; m < (b->il ? 2 : mate + 1); m++) {
+    const u64 rows = std::max<u64>(w.row_cap, b->base + nrec);
+    { int rc = ensure_keep(b, b->pluslen[m], sizeof(u16) * (rows + 64), sizeof(u16) * b->base, s); if (rc) return rc; }
+    if (b->base == 0) HIP_TRY(c, hipMemsetAsync(&b->d_scr->plus_longest[m], 0, sizeof(u32), s));
+    CommentArgs a;
+    a.text = d_text; a.nbytes = nbytes; a.line_end = w.line_end[mate].as<u64>();
+    a.unit_lines = (u32)b->unit_lines(); a.line0 = m == mate ? 0u : (u32)b->lpr;
+    a.nrec = nrec; a.row0 = b->base;
+    a.namelen = nullptr;
+    a.comlen = b->pluslen[m].as<u16>() + b->base;
+    a.off = b->com_piece_off.as<u64>();
+    a.dst = nullptr;
+    a.longest = &b->d_scr->plus_longest[m];
+    a.err = b->d_err;
+    LAUNCH(plus_plan_k, cdiv(nrec, 256), 256, 0, s, a);
+    exclusive_scan<u64>(CommentSize{a.comlen}, nrec, StoreTo<u64>{a.off}, w.scan_ws.as<u64>(), a.off + nrec, s);
+    { int rc = check_device_error(b, s); if (rc) return rc; }
+    u64 total = 0;
+    { int rc = read_u64(b, a.off + nrec, &total, 1, s); if (rc) return rc; }
+    { int rc = read_u32(b, &b->d_scr->plus_longest[m], &b->plus_longest[m], 1, s); if (rc) return rc; }
+    { int rc = ensure_keep(b, b->plus_in[m], b->plus_used[m] + total + 64, b->plus_used[m], s); if (rc) return rc; }
+    a.dst = b->plus_in[m].as<u8>() + b->plus_used[m];
+    LAUNCH(plus_copy_k, cdiv(total, COM_SPAN), 256, 0, s, a);
+    b->plus_used[m] += total;
+  }
+  return SCALCE_OK;
+}
+
 // --keep-bases: the exceptions of the piece's first `nrec` rows (kernels_exceptions.hpp) go behind mate m's entries of earlier
 // pieces (exc_in[m], input order); exc_cnt[m] keeps the count per row.  Runs behind the rows' own ingest, from the piece's line
 // index and over the text the ingest read: a count pass, one exclusive scan and, when the piece has any, a write pass.
@@ -263,6 +300,7 @@ static int piece_unpack_t(scalce_batch *b, int mate, const u8 *d_text, u64 nbyte
   }
   if (b->keep_comments) { int rc = piece_comments(b, mate, d_text, nbytes, nrec, s); if (rc) return rc; }
   if (b->keep_bases) { int rc = piece_exceptions(b, mate, d_text, nbytes, nrec, s); if (rc) return rc; }
+  if (b->keep_plus) { int rc = piece_plus(b, mate, d_text, nbytes, nrec, s); if (rc) return rc; }
   b->ingest_plan[mate][2] = b->line_index_ok[mate] ? 1u : 0u;
   if (IL)  // (one text, one line index, mate 1's names: mate 2 reports what mate 1 does, and the kernel that wrote its own rows)
     for (int i = 1; i < 4; i++) b->ingest_plan[mate + 1][i] = b->ingest_plan[mate][i];
@@ -343,6 +381,7 @@ static void batch_restart(scalce_batch *b) {
   b->names_in_used = 0;
   for (int m = 0; m < 2; m++) b->com_used[m] = b->out_comments_bytes[m] = b->com_longest[m] = 0;
   for (int m = 0; m < 2; m++) b->exc_used[m] = b->exc_rows[m] = b->out_exc_entries[m] = 0;
+  for (int m = 0; m < 2; m++) { b->plus_used[m] = b->out_plus_bytes[m] = 0; b->plus_longest[m] = b->plus_repeats[m] = b->plus_literals[m] = 0; }
   b->tri_expected[0] = b->tri_expected[1] = 0;
   b->ingested[0] = b->ingested[1] = false;
   for (int m = 0; m < 2; m++)
@@ -468,7 +507,7 @@ static int not_whole_records(scalce_ctx *c, const char *which) {
 // ingest starts it over.
 extern "C" int scalce_batch_rewindow(scalce_batch *b, uint64_t keep_first, uint64_t keep_rows, const uint8_t *const front[2],
                                      const uint64_t front_bytes[2], const uint8_t *const back[2], const uint64_t back_bytes[2], void *stream) {
-  if (!b || !front || !back || !front_bytes || !back_bytes || keep_first + keep_rows > b->N || b->il || b->vl || b->keep_comments || b->keep_bases) return SCALCE_ERR_ARG;
+  if (!b || !front || !back || !front_bytes || !back_bytes || keep_first + keep_rows > b->N || b->il || b->vl || b->keep_comments || b->keep_bases || b->keep_plus) return SCALCE_ERR_ARG;
   scalce_ctx *c = b->ctx;
   hipStream_t s = (hipStream_t)stream;
   HIP_TRY(c, hipSetDevice(c->device));
@@ -579,6 +618,25 @@ extern "C" int scalce_batch_comments_info(const scalce_batch *b, int mate, uint6
   if (longest) *longest = b->keep_comments ? b->com_longest[mate] : 0;
   return SCALCE_OK;
 }
+// the '+' lines become an output of the run (SCALCE_OUT_PLUS): before the first ingest or append of the run
+extern "C" int scalce_batch_set_keep_plus(scalce_batch *b, int on) {
+  if (!b) return SCALCE_ERR_ARG;
+  if (on && (b->lpr != 4 || b->nq)) { set_err(b->ctx, "records without a '+' line (fasta, no_qualities) have none to keep"); return SCALCE_ERR_ARG; }
+  if (on && b->code_in_place) { set_err(b->ctx, "a batch coded in place is run again from its text: the store would take its '+' lines twice"); return SCALCE_ERR_ARG; }
+  if (b->N || b->appending || b->ingested[0]) { set_err(b->ctx, "keep-plus is set before the first ingest or append of a run"); return SCALCE_ERR_ARG; }
+  b->keep_plus = on != 0;
+  return SCALCE_OK;
+}
+// (for the other translation units of the library: sharded.cpp, pipeline.cpp)
+bool scalce_batch_keeps_plus(const scalce_batch *b) { return b && b->keep_plus; }
+extern "C" int scalce_batch_plus_info(const scalce_batch *b, int mate, uint64_t *nbytes, uint32_t *longest, uint64_t *repeats, uint64_t *literals) {
+  if (!b || mate < 0 || mate >= b->nm) return SCALCE_ERR_ARG;
+  if (nbytes) *nbytes = b->keep_plus ? b->plus_used[mate] : 0;
+  if (longest) *longest = b->keep_plus ? b->plus_longest[mate] : 0;
+  if (repeats) *repeats = b->keep_plus ? b->plus_repeats[mate] : 0;
+  if (literals) *literals = b->keep_plus ? b->plus_literals[mate] : 0;
+  return SCALCE_OK;
+}
 // the letters and qualities the archive does not keep become an output of the run (SCALCE_OUT_EXCEPTIONS): before the first
 // ingest or append of the run
 extern "C" int scalce_batch_set_keep_bases(scalce_batch *b, int on) {
@@ -600,6 +658,7 @@ extern "C" int scalce_batch_coder_round(const scalce_batch *b) { return b ? b->a
 extern "C" int scalce_batch_set_code_in_place(scalce_batch *b, int on) {
   if (!b) return SCALCE_ERR_ARG;
   if (on && (b->p.no_ac || b->lean || b->vl)) return SCALCE_ERR_ARG;  // (variable-length: a rerun would read the caller's text, not the padded one)
+  if (on && b->keep_plus) return SCALCE_ERR_ARG;                       // (the rerun would append the text's '+' lines to the store again)
   b->code_in_place = on != 0;
   return SCALCE_OK;
 }

@@ -289,6 +289,31 @@ extern "C" int scalce_batch_emit(scalce_batch *b, void *stream) {
       b->comlen[m].release();
     }
   }
+  // the '+' lines, in archive order: the same gather over the plus store; the classes are counted for the log on the way
+  for (int m = 0; m < b->nm && b->keep_plus; m++) {
+    b->out_plus_bytes[m] = N ? b->plus_used[m] : 0;
+    if (!N) continue;
+    ENSURE(b, b->com_off, sizeof(u64) * (N + 8));
+    ENSURE(b, b->com_out_off, sizeof(u64) * (N + 8));
+    ENSURE(b, b->com_ws, (size_t)scalce_records_permute_ws_bytes(N));
+    ENSURE(b, b->out_plus[m], (size_t)b->plus_used[m] + 64);
+    u64 *off = b->com_off.as<u64>();
+    const u16 *len = b->pluslen[m].as<u16>();
+    HIP_TRY(c, hipMemsetAsync(b->d_scr->plus_classes[m], 0, 2 * sizeof(u32), s));
+    LAUNCH(plus_count_k, cdiv(N, 256), 256, 0, s, N, len, b->d_scr->plus_classes[m]);
+    exclusive_scan<u64>(CommentSize{len}, N, StoreTo<u64>{off}, b->com_ws.as<u64>(), off + N, s);
+    int rc = scalce_records_permute(c, b->plus_in[m].as<u8>(), b->com_off.as<uint64_t>(), N, b->plus_used[m], b->perm, b->out_plus[m].as<u8>(), b->plus_used[m],
+                                    b->com_out_off.as<uint64_t>(), b->com_ws.p, s);
+    if (rc) return rc;
+    u32 cls[2] = {0, 0};
+    { int rc2 = read_u32(b, b->d_scr->plus_classes[m], cls, 2, s); if (rc2) return rc2; }
+    b->plus_repeats[m] = cls[0]; b->plus_literals[m] = cls[1];
+    if (b->lean) {  // the input-order store is dead once the gathered stream exists
+      HIP_TRY(c, hipStreamSynchronize(s));
+      b->plus_in[m].release();
+      b->pluslen[m].release();
+    }
+  }
   // the exceptions, in archive order: the entries of output record k are those of input record perm[k], with k stamped in --
   // two scans of the rows' counts (input order for the store's offsets, permuted for the stream's) and one gather
   if (b->keep_bases && N >= EXC_MAX_RECORDS) {  // (36 bits of an entry name its record)
@@ -320,7 +345,7 @@ extern "C" int scalce_batch_emit(scalce_batch *b, void *stream) {
     for (int m = 0; m < b->nm; m++) b->exc_cnt[m].release();
     b->exc_off.release(); b->exc_out_off.release(); b->exc_ws.release(); b->exc_piece_off.release();
   }
-  if (b->lean && b->keep_comments) { b->com_off.release(); b->com_out_off.release(); b->com_ws.release(); b->com_piece_off.release(); }
+  if (b->lean && (b->keep_comments || b->keep_plus)) { b->com_off.release(); b->com_out_off.release(); b->com_ws.release(); b->com_piece_off.release(); }
   if (b->lean) {  // nothing behind this stage reads the rows, the tokens or the sort scratch
     HIP_TRY(c, hipStreamSynchronize(s));
     DBuf *dead[] = {&w.packed[0], &w.packed[1], &w.namecell, &w.names_in, &w.name_in_off, &w.name_off, &w.outlen, &w.cell_sorted,

@@ -243,6 +243,8 @@ struct BatchScratch {
   u64 long_names_bytes;  // what the piece adds to the long-name store
   u64 text_offset;       // scalce_batch_text_offset
   u32 comment_longest[2];  // per mate: the run's longest entry (comment_plan_k; cleared when a run starts)
+  u32 plus_longest[2];     // per mate: the run's longest stored '+'-line entry (plus_plan_k; cleared when a run starts)
+  u32 plus_classes[2][2];  // per mate: repeated and literal entries of the run (plus_count_k at the emit stage)
   struct IngestFlags {   // cleared and read back as one
     u32 max_namelen;     // longest name of the piece
     u32 slow;            // a record did not fit the tile overlap: the piece is redone the indexed way
@@ -348,6 +350,14 @@ struct scalce_batch {
   DBuf comlen[2], com_in[2], out_comments[2], com_off, com_out_off, com_piece_off, com_ws;
   u64 com_used[2] = {0, 0}, out_comments_bytes[2] = {0, 0};
   u32 com_longest[2] = {0, 0};
+  // The '+' lines (scalce_batch_set_keep_plus): the same shape once more -- pluslen = the stored entry's length per row (0 bare,
+  // 1 repeat, 1 + bytes literal), plus_in the entries with class byte and newline in input order, out_plus what the emit stage
+  // gathers (SCALCE_OUT_PLUS).  The offsets and the scratch of the gather are the comments' when both are on, since the
+  // gathers run one behind the other.  Nothing of it exists without the option.
+  bool keep_plus = false;
+  DBuf pluslen[2], plus_in[2], out_plus[2];
+  u64 plus_used[2] = {0, 0}, out_plus_bytes[2] = {0, 0};
+  u32 plus_longest[2] = {0, 0}, plus_repeats[2] = {0, 0}, plus_literals[2] = {0, 0};
   // The letters and qualities the archive does not keep (scalce_batch_set_keep_bases): per mate exc_cnt = the exceptions per
   // row (u16, run-wide, input order) and exc_in = their entries in input order (exc_used of them); the emit stage gathers
   // them through the permutation into out_exc (SCALCE_OUT_EXCEPTIONS) with the archive index stamped in.  exc_piece_off /
@@ -679,6 +689,10 @@ static int check_device_error(scalce_batch *b, hipStream_t s) {
             (unsigned long long)e.where, e.aux, b->L[b->vl_mate], b->nm == 2 ? (b->vl_mate ? ", mate 2" : ", mate 1") : "");
   else if (e.code == E_COMMENT)
     set_err(b->ctx, "(ERROR) record %llu: what follows the name is longer than 65535 bytes", (unsigned long long)e.where);
+  else if (e.code == E_PLUSLINE)
+    set_err(b->ctx, "(ERROR) record %llu: the third line does not begin with '+'", (unsigned long long)e.where);
+  else if (e.code == E_PLUSLONG)
+    set_err(b->ctx, "(ERROR) record %llu: the '+' line is longer than 65535 bytes", (unsigned long long)e.where);
   else if (e.code == E_SEQQUAL)
     set_err(b->ctx, "(ERROR) record %llu: its sequence line (%u characters) and its quality line differ in length", (unsigned long long)e.where, e.aux);
   else

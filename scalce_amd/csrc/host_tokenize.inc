@@ -516,6 +516,7 @@ extern "C" int scalce_batch_text_offset(scalce_batch *b, int mate, uint64_t row,
   if (b->vl) { set_err(b->ctx, "variable-length runs ingest a padded copy of the piece: its offsets are not the caller's"); return SCALCE_ERR_ARG; }
   if (b->keep_comments) { set_err(b->ctx, "a batch that keeps comments is compressed on one GPU: no caller moves its rows"); return SCALCE_ERR_ARG; }
   if (b->keep_bases) { set_err(b->ctx, "a batch that keeps bases is compressed on one GPU: no caller moves its rows"); return SCALCE_ERR_ARG; }
+  if (b->keep_plus) { set_err(b->ctx, "a batch that keeps '+' lines is compressed on one GPU: no caller moves its rows"); return SCALCE_ERR_ARG; }
   *offset = 0;
   const u64 line = b->il ? (u64)b->lpr * (2 * row + (u64)mate) : (u64)b->lpr * row;
   if (!line) return SCALCE_OK;  // (-i: mate 2 of row 0 is the text's second record, not its first byte)

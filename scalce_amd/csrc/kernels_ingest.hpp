@@ -20,7 +20,9 @@ enum DevErrCode : u32 {
   E_PAIRS = 6,      // mates have different record counts
   E_INTERNAL = 7,
   E_SEQQUAL = 8,    // variable-length runs: a record whose sequence and quality lines differ in length (pad_plan_k)
-  E_COMMENT = 9     // --keep-comments: what follows a record's name is longer than 65535 bytes (comment_plan_k)
+  E_COMMENT = 9,    // --keep-comments: what follows a record's name is longer than 65535 bytes (comment_plan_k)
+  E_PLUSLINE = 10,  // --keep-plus: a record's third line is empty or does not begin with '+' (plus_plan_k)
+  E_PLUSLONG = 11   // --keep-plus: a record's '+' line is longer than 65535 bytes (plus_plan_k)
 };
 struct DevErr {
   u32 code;

@@ -23,6 +23,7 @@
 #include "../../include/scalce_hip.h"
 #include "hip_own.hpp"
 
+bool scalce_batch_keeps_plus(const scalce_batch *b);      // (host_ingest.inc: scalce_batch_set_keep_plus is on)
 bool scalce_batch_keeps_comments(const scalce_batch *b);  // (host_ingest.inc: scalce_batch_set_keep_comments is on)
 bool scalce_batch_keeps_bases(const scalce_batch *b);     // (host_ingest.inc: scalce_batch_set_keep_bases is on)
 
@@ -90,6 +91,10 @@ extern "C" int scalce_pipeline_create(scalce_batch **batches, int nslots, int gr
     }
     if (bp.variable_length) {  // (a shard coded in place is run again from the caller's text, which is not the padded one)
       p->err = "variable-length reads (--variable-length) are compressed one shard at a time: the pipeline does not take them";
+      return SCALCE_ERR_ARG;
+    }
+    if (scalce_batch_keeps_plus(batches[i])) {  // (the same rerun would take the '+' lines twice)
+      p->err = "'+' lines (--keep-plus) are kept one shard at a time: the pipeline does not take such a batch";
       return SCALCE_ERR_ARG;
     }
     if (scalce_batch_keeps_comments(batches[i])) {  // (a shard coded in place is run again from its text: the store would take its entries twice)

@@ -20,6 +20,7 @@
 #include "kernels_fastq.hpp"
 #include "kernels_varlen.hpp"
 #include "kernels_comments.hpp"
+#include "kernels_plus.hpp"
 #include "kernels_exceptions.hpp"
 
 using namespace scalce;

@@ -29,6 +29,7 @@
 #include "../../include/scalce_hip.h"
 
 void scalce_set_last_error(scalce_ctx *c, const char *msg);  // (host_state.inc: the message scalce_last_error returns)
+bool scalce_batch_keeps_plus(const scalce_batch *b);          // (host_ingest.inc: scalce_batch_set_keep_plus is on)
 bool scalce_batch_keeps_comments(const scalce_batch *b);      // (host_ingest.inc: scalce_batch_set_keep_comments is on)
 bool scalce_batch_keeps_bases(const scalce_batch *b);         // (host_ingest.inc: scalce_batch_set_keep_bases is on)
 
@@ -704,6 +705,10 @@ extern "C" int scalce_sharded_compress(scalce_comm *comm, scalce_ctx *ctx, scalc
     }
     if (bp.variable_length) {
       scalce_set_last_error(ctx, "variable-length reads (--variable-length) are compressed on one GPU: sharded runs do not take them");
+      return SCALCE_ERR_ARG;
+    }
+    if (scalce_batch_keeps_plus(b)) {  // (the stores lie spread over the ranks)
+      scalce_set_last_error(ctx, "'+' lines (--keep-plus) are kept on one GPU: sharded runs do not take such a batch");
       return SCALCE_ERR_ARG;
     }
     if (scalce_batch_keeps_comments(b)) {  // (the stores lie spread over the ranks, as the permutation does)

@@ -98,6 +98,9 @@ struct Slot {
   // archives with a comment stream: the window's entries, the text with them put back and what the insert pass works in
   HBuf h_com, h_cbad;
   DBuf d_com, d_textc, d_roffc, d_cws, d_cbad;
+  // archives with a plus-line stream: the window's entries, the text with the lines put back and what that pass works in
+  HBuf h_plus, h_pbad;
+  DBuf d_plus, d_textp, d_roffp, d_pws, d_pbad;
   // archives with an exception stream: the window's entries per mate (they grow with the windows), the verdict, the pairs' scratch
   HBuf h_exc[2], h_xbad;
   DBuf d_exc[2], d_xbad, d_xws;
@@ -116,6 +119,8 @@ struct Window {
   bool strip = false;
   bool com = false;         // the window's entries of the comment stream go back into its text
   u64 cbytes = 0;           // ... their bytes, newlines included
+  bool plus = false;        // the window's entries of the plus-line stream go back into its text
+  u64 pbytes = 0, pgrow = 0;  // ... their bytes, newlines included, and what they add to the text
   bool exc = false;         // the window's entries of the exception stream go back into its text
   u64 nexc[2] = {0, 0};     // ... how many, per mate
 };
@@ -176,6 +181,8 @@ struct Session {
   std::unique_ptr<Restore> X;  // set: the input order is restored
   scalce_unpack_comments CM;   // the comment streams (scalce_stream_decompress_comments), or none
   u64 cap_com = 0;             // bytes of entries a slot takes
+  scalce_unpack_plus PL;       // the plus-line streams (scalce_stream_decompress_plus), or none
+  u64 cap_plus = 0;            // bytes of entries a slot takes
   scalce_unpack_exceptions EX; // the exception streams (scalce_stream_decompress_exceptions), or none
   ExceptionCursor xc[2];       // ... where each mate's stands
   bool has_exc[2] = {false, false};
@@ -201,6 +208,7 @@ struct Session {
     memset(&RS, 0, sizeof RS);
     memset(&CM, 0, sizeof CM);
     memset(&EX, 0, sizeof EX);
+    memset(&PL, 0, sizeof PL);
     RS.first_record = RG.first_record;
     RS.total_records = UNKNOWN;
     A.M[0] = &M[0];
@@ -267,7 +275,15 @@ struct Session {
     const u64 nmates = (u64)(A.m1 - A.m0 + 1);
     u64 C = 0;
     for (int m = A.m0; m <= A.m1 && com; m++) C = std::max<u64>(C, M[m].c_longest);
-    for (int m = A.m0; m <= A.m1; m++) { rec_min += A.rec_budget(m); rec_max += rec_fixed(m) + 255 + 32 + (com ? M[m].c_longest : 0); }
+    // (plus-line streams: ... and by the longest a '+' line can become: a literal of P - 1 bytes, or the header line's own bound)
+    const bool plus = wants_plus();
+    u64 PE = 0;
+    for (int m = A.m0; m <= A.m1 && plus; m++) PE = std::max<u64>(PE, M[m].p_longest);
+    for (int m = A.m0; m <= A.m1; m++) {
+      const u64 header = 255 + 32 + (com ? M[m].c_longest : 0);
+      rec_min += A.rec_budget(m);
+      rec_max += rec_fixed(m) + header + (plus ? std::max<u64>(M[m].p_longest ? M[m].p_longest - 1 : 0, header) : 0);
+    }
     R = std::max<u64>(1, W / rec_min);
     D = std::min<u64>(R, (u64)scalce_patterns_count(ctx) + 2);
     cap_text = std::max(W, rec_max) + 64;
@@ -306,7 +322,18 @@ struct Session {
       const bool strip = M[A.m0].has_len;  // (never with two mates in one window: -d -i refuses a length stream)
       if (P.split) SD_TRY(hmalloc(s.h_roff, roff_bytes));
       const bool exc = has_exc[A.m0];
-      if (P.split || strip || X || com || exc) SD_TRY(dmalloc(s.d_roff, roff_bytes));
+      if (P.split || strip || X || com || exc || plus) SD_TRY(dmalloc(s.d_roff, roff_bytes));
+      if (plus) {  // a window's entries: a repeat or a bare line takes two bytes at most, a literal two more than it adds to the text
+        cap_plus = std::min(W + 2 * R * nmates, R * nmates * (PE + 1)) + nmates * (PE + 1) + 64;
+        SD_TRY(hmalloc(s.h_plus, cap_plus));
+        SD_TRY(hmalloc(s.h_pbad, 64));
+        memset(s.h_pbad.p, 0, 64);
+        SD_TRY(dmalloc(s.d_plus, cap_plus));
+        SD_TRY(dmalloc(s.d_textp, cap_text));
+        SD_TRY(dmalloc(s.d_roffp, roff_bytes));
+        SD_TRY(dmalloc(s.d_pws, nmates == 2 ? scalce_fastq_plus_pairs_ws_bytes(R, cap_plus) : scalce_fastq_plus_ws_bytes(R, cap_plus)));
+        SD_TRY(dmalloc(s.d_pbad, 64));
+      }
       if (exc) {
         SD_TRY(hmalloc(s.h_xbad, 64));
         memset(s.h_xbad.p, 0, 64);
@@ -340,6 +367,7 @@ struct Session {
   void free_slots() {
     for (Slot &s : slot) {
       for (DBuf *b : {&s.d_len, &s.d_text2, &s.d_roff2, &s.d_scan, &s.d_com, &s.d_textc, &s.d_roffc, &s.d_cws, &s.d_cbad, &s.d_exc[0], &s.d_exc[1], &s.d_xbad, &s.d_xws,
+                      &s.d_plus, &s.d_textp, &s.d_roffp, &s.d_pws, &s.d_pbad,
                       &s.d_in, &s.d_text, &s.d_roff})
         drop(*b);
       s = Slot();
@@ -474,6 +502,8 @@ struct Session {
       fail(SCALCE_ERR_FORMAT, A.m0, 4, 0, "(ERROR) %s", order_not_permutation());
     if (!failed && j.kind != Job::STRIPE && slot[j.slot].h_cbad.p && slot[j.slot].h_cbad.as<u32>()[0])
       fail(SCALCE_ERR_FORMAT, A.m0, 5, 0, "internal: a window's entries of the comment stream do not fit its records");
+    if (!failed && j.kind != Job::STRIPE && slot[j.slot].h_pbad.p && slot[j.slot].h_pbad.as<u32>()[0])
+      fail(SCALCE_ERR_FORMAT, A.m0, 7, 0, "(ERROR) %s", plus_malformed());
     if (!failed && j.kind != Job::STRIPE && slot[j.slot].h_xbad.p && slot[j.slot].h_xbad.as<u32>()[0])
       fail(SCALCE_ERR_FORMAT, A.m0, 6, 0, "(ERROR) %s", exception_outside());
     return !failed;
@@ -652,6 +682,8 @@ struct Session {
       if (M[m].has_len) SD_TRY(took(A.lengths(m, first, nullptr, got, WF), m, 3, got, first));
     for (int m = m0; m <= m1; m++)  // the comment stream: entries by their newlines
       if (M[m].has_com) SD_TRY(took(A.pass_comments(m, first, got, WF), m, 5, got, first));
+    for (int m = m0; m <= m1; m++)  // the plus-line stream: the same
+      if (M[m].has_plus) SD_TRY(took(A.pass_plus(m, first, got, WF), m, 7, got, first));
     for (int m = m0; m <= m1; m++) {
       Mate &x = M[m];
       x.first = first;
@@ -682,8 +714,11 @@ struct Session {
                                      {h_in + M[m1].o_names, reinterpret_cast<u64 *>(h_in + M[m1].o_noff), M[m1].cap_names}};
       CommentsDst cd{slot[w.si].h_com.as<u8>(), cap_com};
       w.com = M[m0].has_com;
-      const int rc = A.take_names(to, ncap, W, w.n, w.nb, WF, w.com ? &cd : nullptr);
+      PlusDst pd{slot[w.si].h_plus.as<u8>(), cap_plus};
+      w.plus = wants_plus();
+      const int rc = A.take_names(to, ncap, W, w.n, w.nb, WF, w.com ? &cd : nullptr, w.plus ? &pd : nullptr);
       w.cbytes = cd.nbytes;
+      w.pbytes = pd.nbytes; w.pgrow = pd.grow;
       return walk(rc);
     }
     auto text = [&](u64 k) { u64 t = 0; for (int m = m0; m <= m1; m++) t += lib_text(m, w.first, k, true); return t; };
@@ -691,6 +726,28 @@ struct Session {
       u64 lo = 1, hi = w.n;  // text(lo) fits (or lo = 1), text(hi) does not
       while (hi - lo > 1) { const u64 mid = lo + (hi - lo) / 2; if (text(mid) <= W) lo = mid; else hi = mid; }
       w.n = lo;
+    }
+    w.plus = wants_plus();
+    if (w.plus) {  // made-up names: each record's entries are taken with what they add, and the window ends where its budget does
+      PlusDst pd{slot[w.si].h_plus.as<u8>(), cap_plus};
+      u64 n = 0, t = 0;
+      for (; n < w.n; n++) {
+        u64 header[2] = {0, 0}, rec = 0;
+        for (int m = m0; m <= m1; m++) {
+          const u64 one = lib_text(m, w.first + n, 1, true);
+          header[m - m0] = one - (2ull * (u64)M[m].L + 6);  // (the record is '@', the name, two lines of L, '+' and four newlines)
+          rec += one;
+        }
+        Walk::PlusPeek pk;
+        const int e = A.plus_peek(header, pk, WF);
+        if (e == 1 && !A.known) break;  // (the stream ends with the archive, whose other streams say where that is)
+        if (e) return walk(e == 1 ? truncated(WF, m0, 7) : e);
+        if (n && (t + rec + pk.grow > W || !A.plus_fits(pd, pk))) break;
+        A.plus_commit(pd, pk);
+        t += rec + pk.grow;
+      }
+      w.n = n;
+      w.pbytes = pd.nbytes; w.pgrow = pd.grow;
     }
     return SCALCE_OK;
   }
@@ -743,6 +800,7 @@ struct Session {
     for (int m = m0; m <= m1; m++)
       w.nbytes += A.names ? (A.qual ? scalce_fastq_text_bytes : scalce_fasta_text_bytes)(M[m].L, w.n, w.nb[m - m0], nullptr) : lib_text(m, w.first, w.n);
     if (w.com) w.nbytes += w.cbytes - w.n * (u64)(m1 - m0 + 1);  // (the entries without their newlines)
+    if (w.plus) w.nbytes += w.pgrow;
     if (w.nbytes + 64 > cap_text) return fail(SCALCE_ERR_CAPACITY, -1, -1, 0, "internal: a window of %llu bytes of text", (unsigned long long)w.nbytes);
     return SCALCE_OK;
   }
@@ -751,6 +809,7 @@ struct Session {
     u8 *h_in = s.h_in.as<u8>(), *d_in = s.d_in.as<u8>();
     if (w.strip) SD_HIP(hipMemcpyAsync(s.d_len.p, s.h_len.p, w.n * (u64)M[A.m0].l_width, hipMemcpyHostToDevice, s_up));
     if (w.com) SD_HIP(hipMemcpyAsync(s.d_com.p, s.h_com.p, w.cbytes, hipMemcpyHostToDevice, s_up));
+    if (w.plus && w.pbytes) SD_HIP(hipMemcpyAsync(s.d_plus.p, s.h_plus.p, w.pbytes, hipMemcpyHostToDevice, s_up));
     for (int i = 0; i < 2 && w.exc; i++)
       if (w.nexc[i]) SD_HIP(hipMemcpyAsync(s.d_exc[i].p, s.h_exc[i].p, 8 * w.nexc[i], hipMemcpyHostToDevice, s_up));
     if (X) SD_TRY(X->upload(*this, w));
@@ -769,8 +828,14 @@ struct Session {
     return SCALCE_OK;
   }
   // where a window's finished text and record offsets lie: behind the strip, else behind the insert, else as the records kernel left them
-  DBuf &window_text(const Window &w) { Slot &s = slot[w.si]; return w.strip ? s.d_text2 : w.com ? s.d_textc : s.d_text; }
-  DBuf &window_roff(const Window &w) { Slot &s = slot[w.si]; return w.strip ? s.d_roff2 : w.com ? s.d_roffc : s.d_roff; }
+  DBuf &window_text(const Window &w) { Slot &s = slot[w.si]; return w.plus ? s.d_textp : w.strip ? s.d_text2 : w.com ? s.d_textc : s.d_text; }
+  DBuf &window_roff(const Window &w) { Slot &s = slot[w.si]; return w.plus ? s.d_roffp : w.strip ? s.d_roff2 : w.com ? s.d_roffc : s.d_roff; }
+  // the plus-line streams are put back: there are some, the records that go out have a third line, and not every line was bare
+  bool wants_plus() const {
+    bool any = false;
+    for (int m = A.m0; m <= A.m1; m++) any = any || (M[m].has_plus && M[m].p_longest);
+    return A.qual && any;
+  }
   // records -> text, mate by mate, behind the upload; then the entries come back (comments) and the pad goes (variable-length)
   int window_launch(Window &w) {
     const int m0 = A.m0, m1 = A.m1;
@@ -794,7 +859,7 @@ struct Session {
       if (A.names) { fw.d_names = d_in + x.o_names; fw.d_name_off = reinterpret_cast<const u64 *>(d_in + x.o_noff); }
       fw.library = A.library.c_str();
       fw.d_out = s.d_text.as<u8>();
-      fw.d_record_offsets = ((P.split || w.strip || X || w.com || w.exc) && m == m0) ? s.d_roff.as<u64>() : nullptr;
+      fw.d_record_offsets = ((P.split || w.strip || X || w.com || w.exc || w.plus) && m == m0) ? s.d_roff.as<u64>() : nullptr;
       if (nmates == 2) {
         const Mate &y = M[m == m0 ? m1 : m0];
         fw.interleave = m - m0 + 1; fw.pair_read_len = y.L;
@@ -832,6 +897,17 @@ struct Session {
                                            s.d_len.as<u8>(), M[m0].l_width, s.d_text2.as<u8>(), s.d_roff2.as<u64>(), s.d_scan.p, s_main)));
       w.nbytes -= w.cut;
     }
+    // the '+' lines go back BEHIND the comment insert and the strip: both measure from the record's end and assume "\n+\n"
+    if (w.plus) {
+      DBuf &src = w.strip ? s.d_text2 : w.com ? s.d_textc : s.d_text, &src_off = w.strip ? s.d_roff2 : w.com ? s.d_roffc : s.d_roff;
+      if (nmates == 2) {
+        const int rl[2] = {M[m0].L, M[m1].L};
+        SD_TRY(lib(scalce_fastq_plus_window_pairs(ctx, rl, w.n, src.as<u8>(), src_off.as<u64>(), s.d_plus.as<u8>(), w.pbytes, s.d_textp.as<u8>(),
+                                                  cap_text, s.d_roffp.as<u64>(), s.d_pbad.as<u32>(), s.d_pws.p, s_main)));
+      } else
+        SD_TRY(lib(scalce_fastq_plus_window(ctx, w.n, src.as<u8>(), src_off.as<u64>(), s.d_plus.as<u8>(), w.pbytes, s.d_textp.as<u8>(), cap_text,
+                                            s.d_roffp.as<u64>(), s.d_pbad.as<u32>(), s.d_pws.p, s_main)));
+    }
     if (X) SD_TRY(X->group(*this, w, window_text(w).as<u8>(), window_roff(w).as<u64>()));
     SD_HIP(hipEventRecord(s.t_rec1, s_main));
     SD_HIP(hipEventRecord(s.ev_rec, s_main));
@@ -849,6 +925,7 @@ struct Session {
     }
     if (w.com) SD_HIP(hipMemcpyAsync(s.h_cbad.p, s.d_cbad.p, 4, hipMemcpyDeviceToHost, s_down));
     if (w.exc) SD_HIP(hipMemcpyAsync(s.h_xbad.p, s.d_xbad.p, 4, hipMemcpyDeviceToHost, s_down));
+    if (w.plus) SD_HIP(hipMemcpyAsync(s.h_pbad.p, s.d_pbad.p, 4, hipMemcpyDeviceToHost, s_down));
     SD_HIP(hipEventRecord(s.ev_done, s_down));
     to_writer(w.si, w.first, w.n, w.nbytes, X ? Job::SPILL : Job::WINDOW);
     return SCALCE_OK;
@@ -884,6 +961,8 @@ struct Session {
     if (X && A.known && X->N != M[m0].records_left) return order_count(M[m0].records_left);
     for (int m = m0; m <= m1; m++)
       if (M[m].has_com && A.known && M[m].c_total != M[m0].records_left) return walk(A.comment_count(m, M[m].c_total, M[m0].records_left, WF));
+    for (int m = m0; m <= m1; m++)
+      if (M[m].has_plus && A.known && M[m].p_total != M[m0].records_left) return walk(A.plus_count(m, M[m].p_total, M[m0].records_left, WF));
     for (int m = m0; m <= m1; m++) {
       if (!has_exc[m]) continue;
       char b[200];
@@ -913,6 +992,8 @@ struct Session {
     // (an archive that does not say how many records it holds, read to its end: the stream must have ended with it)
     for (int m = m0; m <= m1; m++)
       if (M[m].has_com && M[m0].range_left == UNKNOWN && M[m].c_taken != M[m].c_total) return walk(A.comment_count(m, M[m].c_total, M[m].c_taken, WF));
+    for (int m = m0; m <= m1; m++)
+      if (M[m].has_plus && M[m].p_longest && M[m0].range_left == UNKNOWN && M[m].p_taken != M[m].p_total) return walk(A.plus_count(m, M[m].p_total, M[m].p_taken, WF));
     drain();
     if (failed) return F.rc;
     for (int m = m0; m <= m1; m++) free_decoder(m);
@@ -943,6 +1024,11 @@ struct Session {
       if (!CM.com_rd[m]) continue;
       if (!A.names) return fail(SCALCE_ERR_ARG, m, 5, 0, "(ERROR) a comment stream goes with stored names: the archive holds none (or -n sets them aside)");
       SD_TRY(walk(A.comments_open(m, CM.com_rd[m], CM.com_user[m], &S.read_wait_s, WF)));
+    }
+    for (int m = 0; m < P.mates; m++) {  // the plus-line streams: header, then one entry per record (none when P = 0)
+      if (!PL.plus_rd[m]) continue;
+      if (!A.qual) return fail(SCALCE_ERR_ARG, m, 7, 0, "(ERROR) a plus-line stream goes with four-line records: -Q writes two");
+      SD_TRY(walk(A.plus_open(m, PL.plus_rd[m], PL.plus_user[m], &S.read_wait_s, WF)));
     }
     for (int m = 0; m < P.mates; m++) {  // the exception streams: header, then the entries in ascending order
       if (!EX.exc_rd[m]) continue;
@@ -1087,6 +1173,7 @@ extern "C" int scalce_stream_decompress_range(scalce_ctx *ctx, const scalce_unpa
 
 // the three shapes of decompression behind one call, with or without comment streams (the entry points below and above are this)
 static int decompress_any(scalce_ctx *ctx, const scalce_unpack_params *p, const scalce_unpack_comments *cm, const scalce_unpack_exceptions *ex,
+                          const scalce_unpack_plus *pl,
                           const scalce_unpack_range *range, const scalce_restore_params *rp, scalce_read_fn rd[2][3], void *user[2][3], scalce_write_fn wr, void *wr_user,
                           scalce_unpack_stats *stats, scalce_unpack_range_stats *range_stats, scalce_restore_stats *restore_stats, char *errbuf,
                           size_t errcap) {
@@ -1102,7 +1189,13 @@ static int decompress_any(scalce_ctx *ctx, const scalce_unpack_params *p, const 
     if (errbuf && errcap) snprintf(errbuf, errcap, "(ERROR) an archive with exception streams: every mate has its stream");
     return SCALCE_ERR_ARG;
   }
+  const bool plus = pl && (pl->plus_rd[0] || pl->plus_rd[1]);
+  if (plus && (!pl->plus_rd[0] || (p->mates == 2 && !pl->plus_rd[1]))) {
+    if (errbuf && errcap) snprintf(errbuf, errcap, "(ERROR) an archive with plus-line streams: every mate has its stream");
+    return SCALCE_ERR_ARG;
+  }
   Session *s = new Session(ctx, p, range, wr, wr_user);
+  if (plus) s->PL = *pl;
   if (com) s->CM = *cm;
   if (exc) s->EX = *ex;
   if (rp) {
@@ -1121,14 +1214,22 @@ extern "C" int scalce_stream_decompress_comments(scalce_ctx *ctx, const scalce_u
                                                  void *user[2][3], scalce_write_fn wr, void *wr_user, scalce_unpack_stats *stats,
                                                  scalce_unpack_range_stats *range_stats, scalce_restore_stats *restore_stats, char *errbuf,
                                                  size_t errcap) {
-  return decompress_any(ctx, p, comments, nullptr, range, rp, rd, user, wr, wr_user, stats, range_stats, restore_stats, errbuf, errcap);
+  return decompress_any(ctx, p, comments, nullptr, nullptr, range, rp, rd, user, wr, wr_user, stats, range_stats, restore_stats, errbuf, errcap);
 }
 extern "C" int scalce_stream_decompress_exceptions(scalce_ctx *ctx, const scalce_unpack_params *p, const scalce_unpack_comments *comments,
                                                    const scalce_unpack_exceptions *exceptions, const scalce_unpack_range *range,
                                                    const scalce_restore_params *rp, scalce_read_fn rd[2][3], void *user[2][3], scalce_write_fn wr,
                                                    void *wr_user, scalce_unpack_stats *stats, scalce_unpack_range_stats *range_stats,
                                                    scalce_restore_stats *restore_stats, char *errbuf, size_t errcap) {
-  return decompress_any(ctx, p, comments, exceptions, range, rp, rd, user, wr, wr_user, stats, range_stats, restore_stats, errbuf, errcap);
+  return decompress_any(ctx, p, comments, exceptions, nullptr, range, rp, rd, user, wr, wr_user, stats, range_stats, restore_stats, errbuf, errcap);
+}
+extern "C" int scalce_stream_decompress_plus(scalce_ctx *ctx, const scalce_unpack_params *p, const scalce_unpack_comments *comments,
+                                             const scalce_unpack_exceptions *exceptions, const scalce_unpack_plus *plus,
+                                             const scalce_unpack_range *range, const scalce_restore_params *rp, scalce_read_fn rd[2][3],
+                                             void *user[2][3], scalce_write_fn wr, void *wr_user, scalce_unpack_stats *stats,
+                                             scalce_unpack_range_stats *range_stats, scalce_restore_stats *restore_stats, char *errbuf,
+                                             size_t errcap) {
+  return decompress_any(ctx, p, comments, exceptions, plus, range, rp, rd, user, wr, wr_user, stats, range_stats, restore_stats, errbuf, errcap);
 }
 
 extern "C" int scalce_stream_decompress_restore(scalce_ctx *ctx, const scalce_unpack_params *p, const scalce_restore_params *rp,

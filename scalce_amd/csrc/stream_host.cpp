@@ -152,6 +152,7 @@ int stream_run(scalce_ctx *ctx, const scalce_params *p, scalce_read_fn rd[2], vo
     if (rc) { err = scalce_last_error(ctx); return rc; }
     scalce_batch_set_lean(b, (flags & SCALCE_STREAM_LEAN) ? 1 : 0);
     scalce_batch_set_keep_order(b, (flags & SCALCE_STREAM_KEEP_ORDER) ? 1 : 0);
+    if ((flags & SCALCE_STREAM_KEEP_PLUS) && (rc = scalce_batch_set_keep_plus(b, 1))) { err = scalce_last_error(ctx); return rc; }
     if ((flags & SCALCE_STREAM_KEEP_COMMENTS) && (rc = scalce_batch_set_keep_comments(b, 1))) { err = scalce_last_error(ctx); return rc; }
     if ((flags & SCALCE_STREAM_KEEP_BASES) && (rc = scalce_batch_set_keep_bases(b, 1))) { err = scalce_last_error(ctx); return rc; }
   }

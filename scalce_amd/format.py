@@ -8,6 +8,11 @@ symbol count; .scalcen adds the names flag byte and, under -n, int64 0 plus the 
 A variable-length run (params.variable_length) has a fourth file per mate, ours alone: .scalcel = magic, int32 entry width
 (1 if L <= 255, else 2), int32 L, then one little-endian entry per record in archive order holding L - length.  The other
 three files are those of the same reads padded with N to L.
+
+A run that keeps the '+' lines (--keep-plus) has a .scalcep per mate, ours alone: magic, int32 0 (text entries), int32 P (the
+longest stored entry in bytes), int64 N, then N entries in archive order, each followed by a newline.  An entry is empty (a
+bare '+'), b"=" (the line repeats the header line behind its '@') or b"'" followed by the line's bytes behind the '+'.
+P = 0: no entries follow, every line was bare.
 """
 import gzip
 import struct
@@ -78,6 +83,46 @@ def unpack_lengths(data):
     if pad.size and pad.max() > read_len:
         raise ValueError("length stream: an entry above the read length")
     return read_len, pad
+
+
+PLUS_HEADER_BYTES = 24
+PLUS_MAX_ENTRY = 65535
+
+
+def pack_plus(entries):
+    """The bytes of a .scalcep stream: header, then every entry followed by a newline -- or the header alone when all are empty."""
+    entries = [bytes(e) for e in entries]
+    for e in entries:
+        if b"\n" in e:
+            raise ValueError("an entry of a plus-line stream holds no newline")
+        if len(e) > PLUS_MAX_ENTRY:
+            raise ValueError("an entry of a plus-line stream is at most 65535 bytes long")
+        if e and e != b"=" and not (e[:1] == b"'" and len(e) > 1):
+            raise ValueError("plus-line stream: malformed entry")
+    longest = max((len(e) for e in entries), default=0)
+    return MAGIC + struct.pack("<iiq", 0, longest, len(entries)) + (b"".join(e + b"\n" for e in entries) if longest else b"")
+
+
+def unpack_plus(data):
+    """The entries of the bytes of a .scalcep stream (out of its container); ValueError with the library's message."""
+    data = bytes(data)
+    if len(data) < PLUS_HEADER_BYTES:
+        raise ValueError("truncated plus-line stream")
+    width, longest, n = struct.unpack("<iiq", data[8:24])
+    if data[:7] != MAGIC[:7] or width != 0 or longest < 0 or longest > PLUS_MAX_ENTRY or n < 0 or n > 0xFFFFFFFF:
+        raise ValueError("is not a scalce plus-line stream")
+    if longest == 0:
+        return [b""] * n
+    entries = data[PLUS_HEADER_BYTES:].split(b"\n")
+    if entries.pop() != b"" or len(entries) < n:  # (the stream ends inside an entry, or before N entries)
+        raise ValueError("truncated plus-line stream")
+    if len(entries) != n:
+        raise ValueError(f"plus-line stream holds {len(entries)} entries, its header says {n}")
+    if any(len(e) > longest for e in entries):
+        raise ValueError("plus-line stream: an entry is longer than its header says")
+    if any(e and e != b"=" and not (e[:1] == b"'" and len(e) > 1) for e in entries):
+        raise ValueError("plus-line stream: malformed entry")
+    return entries
 
 
 def sample_qmap(fastq_bytes, sample=100000, lossy=0):

@@ -19,6 +19,7 @@ OUT_READS, OUT_NAMES, OUT_QUAL, OUT_TABLE, OUT_FREQ4, OUT_TOKENS, OUT_PERM, OUT_
 OUT_LENGTHS = 12  # variable-length runs: N x u16, read_len - length per record in output order
 OUT_NAMECELLS = 13  # for tests: N x 16 bytes, [stored length][first 15 characters, zero behind a shorter name], input order
 OUT_COMMENTS = 14  # keep_comments: what follows the name of every record in output order, each entry followed by a newline
+OUT_PLUS = 16  # keep_plus: the '+'-line entry of every record in output order, each followed by a newline
 OUT_EXCEPTIONS = 15  # keep_bases: u64 entries in output order: letter | values[q] << 8 | position << 16 | record << 28
 STAGES = ("ingest", "quality", "tokenize", "order", "emit", "entropy")
 ROOT_CORE = 0x3FFFFFFF
@@ -681,10 +682,36 @@ def _unpack_exceptions(keep, mates, exception_readers):
     return ex
 
 
-def _decompress_streams(ctx, p, cm, rg, rp, rd, user, wfn, st, rst, ost, msg, ex=None):
+class UnpackPlus(C.Structure):
+    """scalce_unpack_plus: the plus-line streams of an archive made with --keep-plus, one per mate"""
+    _fields_ = [("plus_rd", READ_FN * 2), ("plus_user", C.c_void_p * 2)]
+
+
+def _unpack_plus(keep, mates, plus_readers):
+    pl = UnpackPlus()
+    for m in range(mates):
+        if plus_readers[m] is not None:
+            pl.plus_rd[m] = _unpack_read_fn(keep, plus_readers[m])
+    return pl
+
+
+def _decompress_streams(ctx, p, cm, rg, rp, rd, user, wfn, st, rst, ost, msg, ex=None, pl=None):
     """The one entry point behind the three shapes of decompression for archives with side streams: cm the comment streams
-    (scalce_stream_decompress_comments), ex the exception streams beside them or alone (scalce_stream_decompress_exceptions)"""
+    (scalce_stream_decompress_comments), ex the exception streams beside them or alone (scalce_stream_decompress_exceptions),
+    pl the plus-line streams beside either or alone (scalce_stream_decompress_plus)"""
     L = ctx.L
+    if pl is not None:
+        L.scalce_stream_decompress_plus.argtypes = [C.c_void_p, C.POINTER(UnpackParams), C.POINTER(UnpackComments), C.POINTER(UnpackExceptions),
+                                                    C.POINTER(UnpackPlus), C.POINTER(UnpackRange), C.POINTER(RestoreParams), C.c_void_p,
+                                                    C.c_void_p, WRITE_FN, C.c_void_p, C.POINTER(UnpackStats), C.POINTER(UnpackRangeStats),
+                                                    C.POINTER(RestoreStats), C.c_char_p, C.c_size_t]
+        L.scalce_stream_decompress_plus.restype = C.c_int
+        return L.scalce_stream_decompress_plus(ctx.h, C.byref(p), C.byref(cm) if cm is not None else None,
+                                               C.byref(ex) if ex is not None else None, C.byref(pl),
+                                               C.byref(rg) if rg is not None else None, C.byref(rp) if rp is not None else None,
+                                               C.cast(rd, C.c_void_p), C.cast(user, C.c_void_p), wfn, None, C.byref(st),
+                                               C.byref(rst) if rst is not None else None, C.byref(ost) if ost is not None else None,
+                                               msg, len(msg))
     if ex is not None:
         L.scalce_stream_decompress_exceptions.argtypes = [C.c_void_p, C.POINTER(UnpackParams), C.POINTER(UnpackComments), C.POINTER(UnpackExceptions),
                                                           C.POINTER(UnpackRange), C.POINTER(RestoreParams), C.c_void_p, C.c_void_p, WRITE_FN,
@@ -710,7 +737,7 @@ def _decompress_streams(ctx, p, cm, rg, rp, rd, user, wfn, st, rst, ost, msg, ex
 
 def stream_decompress(ctx, readers, write, mates=1, interleave=False, no_qualities=False, mate_digit=None, library=None,
                       split=0, window_text_bytes=0, first_record=0, nrecords=None, skippers=None, length_readers=None,
-                      length_skippers=None, comment_readers=None, exception_readers=None):
+                      length_skippers=None, comment_readers=None, exception_readers=None, plus_readers=None):
     """scalce_stream_decompress_range: an archive, or a range of its records, back to text in windows of whole records.
     readers[m] = the three callables (cap) -> bytes of mate m's .scalcer, .scalcen and .scalceq streams (b"" at the end; raise
     for a read error); write(mate, first_record, nrecords, text_bytes, record_offsets or None) receives every window in
@@ -720,7 +747,8 @@ def stream_decompress(ctx, readers, write, mates=1, interleave=False, no_qualiti
     length_skippers[m]): the .scalcel stream of a variable-length archive, one callable per mate.  Returns UnpackStats; its attribute
     `range` holds the UnpackRangeStats of the run.  comment_readers[m]: the .scalcec stream of an archive made with
     --keep-comments, one callable per mate -- the call then goes through scalce_stream_decompress_comments.  exception_readers[m]:
-    the .scalcex stream of an archive made with --keep-bases -- through scalce_stream_decompress_exceptions."""
+    the .scalcex stream of an archive made with --keep-bases -- through scalce_stream_decompress_exceptions.  plus_readers[m]:
+    the .scalcep stream of an archive made with --keep-plus -- through scalce_stream_decompress_plus."""
     keep = []
     wfn = _unpack_write_fn(write)
     rd = ((READ_FN * 3) * 2)()
@@ -746,7 +774,11 @@ def stream_decompress(ctx, readers, write, mates=1, interleave=False, no_qualiti
                                                  WRITE_FN, C.c_void_p, C.POINTER(UnpackStats), C.POINTER(UnpackRangeStats), C.c_char_p,
                                                  C.c_size_t]
     L.scalce_stream_decompress_range.restype = C.c_int
-    if exception_readers is not None:
+    if plus_readers is not None:
+        cm = _unpack_comments(keep, mates, comment_readers) if comment_readers is not None else None
+        ex = _unpack_exceptions(keep, mates, exception_readers) if exception_readers is not None else None
+        rc = _decompress_streams(ctx, p, cm, rg, None, rd, user, wfn, st, rst, None, msg, ex=ex, pl=_unpack_plus(keep, mates, plus_readers))
+    elif exception_readers is not None:
         cm = _unpack_comments(keep, mates, comment_readers) if comment_readers is not None else None
         rc = _decompress_streams(ctx, p, cm, rg, None, rd, user, wfn, st, rst, None, msg, ex=_unpack_exceptions(keep, mates, exception_readers))
     elif comment_readers is not None:
@@ -989,6 +1021,45 @@ def fastq_exception_window_pairs(ctx, read_lens, has_qualities, first_pair, npai
                                                      d_name_off2, int(library_len), de, ne, d_bad, d_ws, stream))
 
 
+# ---- the '+' lines (archives made with --keep-plus; format.pack_plus / unpack_plus hold the stream's layout) ------------------
+STREAM_KEEP_PLUS = 32  # SCALCE_STREAM_KEEP_PLUS
+
+
+def fastq_plus_ws_bytes(nrecords, entry_bytes):
+    L = lib()
+    L.scalce_fastq_plus_ws_bytes.argtypes = [C.c_uint64, C.c_uint64]
+    L.scalce_fastq_plus_ws_bytes.restype = C.c_uint64
+    return int(L.scalce_fastq_plus_ws_bytes(int(nrecords), int(entry_bytes)))
+
+
+def fastq_plus_window(ctx, nrecords, d_text, d_record_offsets, d_entries, entry_bytes, d_out, out_cap, d_out_offsets, d_bad, d_ws, stream=0):
+    """scalce_fastq_plus_window: a window's '+' lines back behind each '+' (device pointers; see the header)."""
+    L = ctx.L
+    L.scalce_fastq_plus_window.argtypes = [C.c_void_p, C.c_uint64] + [C.c_void_p] * 3 + [C.c_uint64, C.c_void_p, C.c_uint64] + [C.c_void_p] * 4
+    L.scalce_fastq_plus_window.restype = C.c_int
+    ctx._check(L.scalce_fastq_plus_window(ctx.h, int(nrecords), d_text, d_record_offsets, d_entries, int(entry_bytes), d_out, int(out_cap),
+                                          d_out_offsets, d_bad, d_ws, stream))
+
+
+def fastq_plus_pairs_ws_bytes(npairs, entry_bytes):
+    L = lib()
+    L.scalce_fastq_plus_pairs_ws_bytes.argtypes = [C.c_uint64, C.c_uint64]
+    L.scalce_fastq_plus_pairs_ws_bytes.restype = C.c_uint64
+    return int(L.scalce_fastq_plus_pairs_ws_bytes(int(npairs), int(entry_bytes)))
+
+
+def fastq_plus_window_pairs(ctx, read_lens, npairs, d_text, d_pair_offsets, d_entries, entry_bytes, d_out, out_cap, d_out_pair_offsets, d_bad,
+                            d_ws, stream=0):
+    """scalce_fastq_plus_window_pairs: the same for an interleaved window, both mates' entries pair by pair (device pointers)."""
+    L = ctx.L
+    L.scalce_fastq_plus_window_pairs.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_uint64] + [C.c_void_p] * 3 + [
+        C.c_uint64, C.c_void_p, C.c_uint64] + [C.c_void_p] * 4
+    L.scalce_fastq_plus_window_pairs.restype = C.c_int
+    rl = (C.c_int * 2)(int(read_lens[0]), int(read_lens[1]))
+    ctx._check(L.scalce_fastq_plus_window_pairs(ctx.h, rl, int(npairs), d_text, d_pair_offsets, d_entries, int(entry_bytes), d_out,
+                                                int(out_cap), d_out_pair_offsets, d_bad, d_ws, stream))
+
+
 class RestoreParams(C.Structure):
     _fields_ = [("order_rd", READ_FN * 2), ("order_user", C.c_void_p * 2), ("spill_dir", C.c_char_p)]
 
@@ -1001,7 +1072,7 @@ class RestoreStats(C.Structure):
 
 def stream_decompress_restore(ctx, readers, order_readers, write, spill_dir, mates=1, interleave=False, no_qualities=False,
                               mate_digit=None, library=None, split=0, window_text_bytes=0, length_readers=None, comment_readers=None,
-                              exception_readers=None):
+                              exception_readers=None, plus_readers=None):
     """scalce_stream_decompress_restore: stream_decompress with the input order restored.  order_readers[m]: the callable
     (cap) -> bytes of the .scalceo stream, read from its start once per mate pass (interleaved: only [0]); write receives
     the text in input order, one stripe per call, first_record = the input index of its first record.  Returns
@@ -1029,7 +1100,11 @@ def stream_decompress_restore(ctx, readers, order_readers, write, spill_dir, mat
                                                    WRITE_FN, C.c_void_p, C.POINTER(UnpackStats), C.POINTER(RestoreStats), C.c_char_p,
                                                    C.c_size_t]
     L.scalce_stream_decompress_restore.restype = C.c_int
-    if exception_readers is not None:
+    if plus_readers is not None:
+        cm = _unpack_comments(keep, mates, comment_readers) if comment_readers is not None else None
+        ex = _unpack_exceptions(keep, mates, exception_readers) if exception_readers is not None else None
+        rc = _decompress_streams(ctx, p, cm, None, rp, rd, user, wfn, st, None, rst, msg, ex=ex, pl=_unpack_plus(keep, mates, plus_readers))
+    elif exception_readers is not None:
         cm = _unpack_comments(keep, mates, comment_readers) if comment_readers is not None else None
         rc = _decompress_streams(ctx, p, cm, None, rp, rd, user, wfn, st, None, rst, msg, ex=_unpack_exceptions(keep, mates, exception_readers))
     elif comment_readers is not None:
@@ -1061,7 +1136,7 @@ class Batch:
 
     def __init__(self, ctx, read_len, max_reads, max_text, paired=False, use_names=True, no_ac=False, qmap=None,
                  bucket_set_size=0, read_len2=0, qprev=None, workspace=None, fasta=False, no_qualities=False, interleaved=False,
-                 variable_length=False, keep_comments=False, keep_bases=False):
+                 variable_length=False, keep_comments=False, keep_bases=False, keep_plus=False):
         self.ctx = ctx
         self.L = ctx.L
         p = Params()
@@ -1095,6 +1170,8 @@ class Batch:
             self.set_keep_comments(True)
         if keep_bases:
             self.set_keep_bases(True)
+        if keep_plus:
+            self.set_keep_plus(True)
 
     def _check(self, rc):
         self.ctx._check(rc)
@@ -1133,6 +1210,21 @@ class Batch:
         n, c = C.c_uint64(0), C.c_uint32(0)
         self._check(self.L.scalce_batch_comments_info(self.h, int(mate), C.byref(n), C.byref(c)))
         return int(n.value), int(c.value)
+
+    def set_keep_plus(self, on=True):
+        """Every record's '+' line becomes OUT_PLUS (scalce_batch_set_keep_plus): before the run's first ingest or append."""
+        self.L.scalce_batch_set_keep_plus.argtypes = [C.c_void_p, C.c_int]
+        self.L.scalce_batch_set_keep_plus.restype = C.c_int
+        self._check(self.L.scalce_batch_set_keep_plus(self.h, int(on)))
+
+    def plus_info(self, mate=0):
+        """scalce_batch_plus_info: (bytes of OUT_PLUS, longest stored entry, repeats, literals) of `mate`."""
+        self.L.scalce_batch_plus_info.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
+                                                  C.POINTER(C.c_uint64)]
+        self.L.scalce_batch_plus_info.restype = C.c_int
+        n, p, r, l = C.c_uint64(0), C.c_uint32(0), C.c_uint64(0), C.c_uint64(0)
+        self._check(self.L.scalce_batch_plus_info(self.h, int(mate), C.byref(n), C.byref(p), C.byref(r), C.byref(l)))
+        return int(n.value), int(p.value), int(r.value), int(l.value)
 
     def set_keep_bases(self, on=True):
         """The letters and qualities the archive does not keep become OUT_EXCEPTIONS (scalce_batch_set_keep_bases): before the
