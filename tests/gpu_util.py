@@ -2,6 +2,7 @@
 import numpy as np
 
 import oraclelib as O
+from coder_totals import craft_straddle  # noqa: F401  (on the coder step restated there; its callers import it from here)
 from scalce_amd import host, synth
 
 
@@ -66,47 +67,42 @@ def check_against_oracle(ctx, trie, bases, quals, qoff=33, qvals=None, label="")
     return b, ref, st
 
 
-def craft_straddle(n, cum, total, rng, first2=(9, 12)):
-    """n symbols for a context-free table (cum[0..80] cumulative counts) chosen while following the reference coder's
-    state (arithmetic.cpp:122-152): runs of 1..40 symbols whose interval holds the midpoint -- each adds pending
-    underflow bits -- between stretches of random symbols.  Returns (symbols, longest pending run in bits)."""
-    out = [first2[0], first2[1]]
-    lo, hi = 0, 0xFFFFFFFF
-    used = [s for s in range(80) if cum[s + 1] > cum[s] + 1]
-    run_left, free, pend, maxpend = 0, 0, 0, 0
-    while len(out) < n:
-        if run_left == 0 and free == 0:
-            run_left, free = int(rng.integers(1, 41)), int(rng.integers(1, 12))
-        width = ((hi - lo) & 0xFFFFFFFF) + 1
-        pick = None
-        if free == 0:
-            for s in used:
-                nl = lo + width * int(cum[s]) // total
-                nh = lo + width * int(cum[s + 1]) // total - 1
-                if 0x40000000 <= nl < 0x80000000 <= nh < 0xC0000000:
-                    pick = s
-                    break
-            run_left -= 1
-        if pick is None:
-            pick = int(rng.choice(used))
-            free = max(0, free - 1)
-        nh = (lo + width * int(cum[pick + 1]) // total - 1) & 0xFFFFFFFF
-        nl = (lo + width * int(cum[pick]) // total) & 0xFFFFFFFF
-        while True:
-            if (nh & 0x80000000) == (nl & 0x80000000):
-                pend = 0
-            elif not (nh & 0x40000000) and (nl & 0x40000000):
-                nl &= 0x3FFFFFFF
-                nh |= 0x40000000
-                pend += 1
-                maxpend = max(maxpend, pend)
-            else:
-                break
-            nl = (nl << 1) & 0xFFFFFFFF
-            nh = ((nh << 1) | 1) & 0xFFFFFFFF
-        lo, hi = nl, nh
-        out.append(pick)
-    return np.array(out[:n], dtype=np.uint8), maxpend
+# ---- device buffers between guard bytes (test_gpu_decode_entries, test_gpu_coder_totals) -------------------------------------
+GUARD = 1024
+SENT = 0xA5  # no symbol (< 80), no character of a text (< 0x90 with the phred offsets used)
+DEV = "cuda:0"
+
+
+class Out:
+    """nbytes of output at `offset` from a 256-byte aligned address, sentinel everywhere, GUARD bytes on both sides"""
+
+    def __init__(self, nbytes, offset=0):
+        import torch
+        self.t = torch.full((256 + GUARD + 64 + nbytes + GUARD,), SENT, dtype=torch.uint8, device=DEV)
+        self.start = (-self.t.data_ptr()) % 256 + GUARD + offset
+        self.nbytes = nbytes
+        self.ptr = self.t.data_ptr() + self.start
+
+    def region(self, what="", sentinel_free=True):
+        h = self.t.cpu().numpy()
+        assert (h[:self.start] == SENT).all(), f"{what}: bytes in front of the output were written"
+        assert (h[self.start + self.nbytes:] == SENT).all(), f"{what}: bytes behind the output were written"
+        got = h[self.start:self.start + self.nbytes]
+        assert not sentinel_free or not (got == SENT).any(), f"{what}: output bytes were left unwritten"
+        return got
+
+
+class In:
+    """data at `offset` from a 256-byte aligned address; the tensor ends `slack` bytes behind it (the slack is not zero)"""
+
+    def __init__(self, data, offset=0, slack=64):
+        import torch
+        a = np.frombuffer(bytes(data), dtype=np.uint8)
+        raw = torch.full((offset + len(a) + slack,), 0xEE, dtype=torch.uint8, device=DEV)
+        assert raw.data_ptr() % 256 == 0  # (the allocator hands out blocks aligned to 512 bytes)
+        if len(a):
+            raw[offset:offset + len(a)] = torch.from_numpy(a.copy()).to(DEV)
+        self.t, self.ptr, self.nbytes = raw, raw.data_ptr() + offset, len(a)
 
 
 # ---- what the order stage sorts by, restated in numpy from the oracle's tokens (test_gpu_order_emit, test_gpu_scale) ----

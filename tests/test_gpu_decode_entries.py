@@ -11,13 +11,11 @@ import pytest
 
 import decode_ref as R
 import oraclelib as O
+from gpu_util import DEV, GUARD, SENT, In, Out  # noqa: F401
 from scalce_amd import host
 
 pytestmark = pytest.mark.gpu
 FRAME = R.FRAME
-GUARD = 1024
-SENT = 0xA5  # no symbol (< 80), no character of a text (< 0x90 with the phred offsets used)
-DEV = "cuda:0"
 
 
 @pytest.fixture(scope="module")
@@ -25,39 +23,7 @@ def ctx():
     return host.Context(0, patterns_text=CORE_TEXT)
 
 
-# ---- device buffers ---------------------------------------------------------------------------------------------------------
-class Out:
-    """nbytes of output at `offset` from a 256-byte aligned address, sentinel everywhere, GUARD bytes on both sides"""
-
-    def __init__(self, nbytes, offset=0):
-        import torch
-        self.t = torch.full((256 + GUARD + 64 + nbytes + GUARD,), SENT, dtype=torch.uint8, device=DEV)
-        self.start = (-self.t.data_ptr()) % 256 + GUARD + offset
-        self.nbytes = nbytes
-        self.ptr = self.t.data_ptr() + self.start
-
-    def region(self, what="", sentinel_free=True):
-        h = self.t.cpu().numpy()
-        assert (h[:self.start] == SENT).all(), f"{what}: bytes in front of the output were written"
-        assert (h[self.start + self.nbytes:] == SENT).all(), f"{what}: bytes behind the output were written"
-        got = h[self.start:self.start + self.nbytes]
-        assert not sentinel_free or not (got == SENT).any(), f"{what}: output bytes were left unwritten"
-        return got
-
-
-class In:
-    """data at `offset` from a 256-byte aligned address; the tensor ends `slack` bytes behind it (the slack is not zero)"""
-
-    def __init__(self, data, offset=0, slack=64):
-        import torch
-        a = np.frombuffer(bytes(data), dtype=np.uint8)
-        raw = torch.full((offset + len(a) + slack,), 0xEE, dtype=torch.uint8, device=DEV)
-        assert raw.data_ptr() % 256 == 0  # (the allocator hands out blocks aligned to 512 bytes)
-        if len(a):
-            raw[offset:offset + len(a)] = torch.from_numpy(a.copy()).to(DEV)
-        self.t, self.ptr, self.nbytes = raw, raw.data_ptr() + offset, len(a)
-
-
+# ---- device buffers: Out and In, between guard bytes (gpu_util) -----------------------------------------------------------
 def dev_u64(values):
     import torch
     return torch.tensor([int(v) - (1 << 64) if int(v) >= 1 << 63 else int(v) for v in values], dtype=torch.int64, device=DEV)
