@@ -444,6 +444,15 @@ int scalce_memcpy_d2d(scalce_ctx *ctx, void *dst_dev, const void *src_dev, uint6
  * sort phase's `any_large` as read back: != 0 when a run of more than 32 records with bases behind the 16-base prefix sent
  * every run through the radix passes, 0 when the runs were sorted where they stood or the phase did not run */
 int scalce_batch_stats(const scalce_batch *b, uint32_t out[7]);
+/* For tests: the path the last tie-break (scalce_batch_tokenize, _tokenize_settle) took.  out[0] = 0: the piece had no tie
+ * reads, 1: windows of tie reads with one launch per sweep, 2: windows with two launches per sweep (a window whose words do
+ * not fit a workgroup's LDS, or SCALCE_TIE_WINDOW=<reads>:two_launches), 3: the global sweeps (SCALCE_TIE_WINDOW=0); out[1] =
+ * the tie reads per window actually used, after the clamp to 2^30 and the cap of 64 Mi cells (windows x (buckets + 1)),
+ * out[2] = the number of windows (both 0 without windows); out[3] = where tie_sequential_k kept its counters when the sweeps
+ * gave up (scalce_batch_stats out[5]) -- 1: LDS inside the default limit (up to 48 KB of counters), 2: LDS with the limit raised (up to 100 KB), 3: global memory,
+ * 0: it did not run.
+ * Host bookkeeping only: nothing is launched, waited for or read back. */
+int scalce_batch_tie_plan(const scalce_batch *b, uint32_t out[4]);
 
 /* Device self-test of the arithmetic coder's closed-form step (multiply-high by reciprocal fractions, merged
  * renormalisation shift) against the literal loop of arithmetic.cpp:122-152 on `ncases` random and crafted

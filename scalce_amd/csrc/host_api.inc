@@ -263,6 +263,11 @@ extern "C" int scalce_batch_stats(const scalce_batch *b, uint32_t out[7]) {
   out[6] = b->order_radix_fallback;
   return SCALCE_OK;
 }
+extern "C" int scalce_batch_tie_plan(const scalce_batch *b, uint32_t out[4]) {
+  if (!b || !out) return SCALCE_ERR_ARG;
+  for (int i = 0; i < 4; i++) out[i] = b->tie_plan[i];
+  return SCALCE_OK;
+}
 
 extern "C" int scalce_selftest_ac(scalce_ctx *c, uint64_t ncases, uint32_t seed, int general, uint32_t out[6]) {
   if (!c || !out) return SCALCE_ERR_ARG;

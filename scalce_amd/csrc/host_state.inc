@@ -369,6 +369,7 @@ struct scalce_batch {
   u64 out_reads_bytes[2] = {0, 0}, out_names_bytes = 0, out_qual_bytes[2] = {0, 0};
   u32 ntie = 0, nev = 0, ntev = 0, ncand_cap = 0, jacobi_iters = 0, nchunks = 1, sweep_no = 0;
   bool tie_fallback = false;  // the last tie-break ended in tie_sequential_k
+  u32 tie_plan[4] = {0, 0, 0, 0};  // path, tie reads per window, windows, counters of tie_sequential_k (scalce_batch_tie_plan)
   bool tok_open = false;
   int dirty_cur = 0;
   std::vector<uint64_t> explicit_chunks;  // spill-chunk starts given by the caller (sharded runs), else -B rule

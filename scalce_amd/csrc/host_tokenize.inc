@@ -64,6 +64,7 @@ extern "C" int scalce_batch_tokenize_begin(scalce_batch *b, void *stream) {
   const u64 N = b->tok_n;
   b->jacobi_iters = 0;
   b->tie_fallback = false;
+  for (u32 &v : b->tie_plan) v = 0;
   b->sweep_no = 0;
   b->tok_open = true;
   const u32 nb1 = (u32)c->A.n_buckets + 1;  // buckets incl. root
@@ -249,6 +250,7 @@ static int tokenize_sequential(scalce_batch *b, const uint64_t *d_prior, hipStre
   const size_t lds = (size_t)nb1 * 4;
   a.lds_counters = lds <= 100 * 1024 ? 1u : 0u;
   if (!a.lds_counters) HIP_TRY(c, hipMemsetAsync(a.tiecount, 0, sizeof(u32) * nb1, s));
+  b->tie_plan[3] = !a.lds_counters ? 3u : lds > 48 * 1024 ? 2u : 1u;
   if (a.lds_counters && lds > 48 * 1024)
     HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(tie_sequential_k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   LAUNCH(tie_sequential_k, 1, 64, a.lds_counters ? lds : 0, s, a);
@@ -328,6 +330,7 @@ static int tokenize_windows(scalce_batch *b, const uint64_t *d_prior, bool *sett
   const u64 max_cells = 64ull << 20;  // (a million-core table: fewer, larger windows)
   if ((u64)cdiv(ntie, W) * nb1 > max_cells) W = (u32)cdiv(ntie, max_cells / nb1 ? max_cells / nb1 : 1);
   const u32 nwin = cdiv(ntie, W);
+  b->tie_plan[0] = 2; b->tie_plan[1] = W; b->tie_plan[2] = nwin;  // (two launches per sweep unless the fused kernel takes it below)
   const u64 ncells = (u64)nwin * nb1;
   const u64 nwords = ((u64)ntev >> 6) + 4;
   ENSURE(b, w.tw_cells, sizeof(u32) * (3 * ncells + 8));
@@ -372,6 +375,7 @@ static int tokenize_windows(scalce_batch *b, const uint64_t *d_prior, bool *sett
     { int rc = read_u32(b, maxw_d, &maxw, 1, s); if (rc) return rc; }
     const size_t lds = (size_t)(maxw + 2) * 12;
     if (lds <= 140 * 1024) {
+      b->tie_plan[0] = 1;
       if (lds > 48 * 1024)
         HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(tie_window_fused_k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
       static const u32 one = 1;
@@ -448,6 +452,7 @@ extern "C" int scalce_batch_tokenize_settle(scalce_batch *b, const uint64_t *d_p
   // Sweeps go out four at a time and the host looks at their flags once per batch: a sweep after the fixed point changes
   // nothing (and costs next to nothing), while a round trip per sweep left the stream idle 47 times per shard.
   hipStream_t s = (hipStream_t)stream;
+  if (b->tok_n && b->ntie) b->tie_plan[0] = 3;
   for (bool done = !(b->tok_n && b->ntie); !done;) {
     StageTimer tm(b, ST_TOKENIZE, s);
     u32 *flags = b->d_scr->sweep_moved;

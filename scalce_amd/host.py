@@ -143,6 +143,7 @@ def lib():
     L.scalce_batch_stage_reset.argtypes = [vp, i32]
     L.scalce_batch_stage_reset.restype = None
     L.scalce_batch_stats.argtypes = [vp, C.POINTER(C.c_uint32)]
+    L.scalce_batch_tie_plan.argtypes = [vp, C.POINTER(C.c_uint32)]
     L.scalce_batch_kernel_timing.argtypes = [vp, i32]
     L.scalce_batch_kernel_timing.restype = None
     L.scalce_batch_kernel_ms.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(i32), C.POINTER(u64), C.POINTER(u64)]
@@ -1391,6 +1392,15 @@ class Batch:
         self._check(self.L.scalce_batch_stats(self.h, a))
         return dict(tie_reads=a[0], events=a[1], jacobi_iters=a[2], chunks=a[3], order_run_members=a[4], tie_fallback=a[5],
                     order_radix_fallback=a[6])
+
+    def tie_plan(self):
+        """For tests: the path the last tie-break took (scalce_batch_tie_plan).  path 0: no tie reads, 1: windows with one
+        launch per sweep, 2: windows with two launches, 3: global sweeps; window = tie reads per window as used, windows = how
+        many; sequential = the counters of tie_sequential_k, 0: it did not run, 1: LDS, 2: LDS with the limit raised, 3: global
+        memory."""
+        a = (C.c_uint32 * 4)()
+        self._check(self.L.scalce_batch_tie_plan(self.h, a))
+        return dict(path=a[0], window=a[1], windows=a[2], sequential=a[3])
 
     def stage_reset(self, enable=True):
         self.L.scalce_batch_stage_reset(self.h, int(enable))

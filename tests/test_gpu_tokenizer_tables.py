@@ -119,6 +119,9 @@ def test_tie_reads(name, mode, monkeypatch):
     b = run(ctx, bases)
     check_against_oracle(b, trie, bases, f"{name} ties {mode}")
     assert b.stats()["tie_reads"] > 10_000
+    if mode != "sweeps8":   # the hook selected the path the case is named after
+        plan = b.tie_plan()
+        assert plan["path"] == {"0": 3, "700": 1, "700:two_launches": 2}[mode] and plan["window"] == (0 if mode == "0" else 700)
 
 
 @pytest.mark.parametrize("name", TIE_SHAPES)
