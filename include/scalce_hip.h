@@ -174,10 +174,17 @@ int scalce_batch_reset(scalce_batch *b);
 #define SCALCE_STREAM_KEEP_COMMENTS 8  /* scalce_batch_set_keep_comments on the run's batch: SCALCE_OUT_COMMENTS holds what follows the names */
 #define SCALCE_STREAM_KEEP_BASES 16  /* scalce_batch_set_keep_bases on the run's batch: SCALCE_OUT_EXCEPTIONS holds what the archive does not keep of the bases */
 #define SCALCE_STREAM_KEEP_PLUS 32  /* scalce_batch_set_keep_plus on the run's batch: SCALCE_OUT_PLUS holds the records' '+' lines as entries */
+/* The text's digest (--digest): every chunk of every mate stream, as it has arrived on the device and before anything is put in
+ * front of it or padded, gets one scalce_crc32_device launch on the stream that orders its way into the piece; the words collect
+ * in a small device array, come down behind the launches without a wait of their own and are joined on the host in input order
+ * (scalce_crc32_combine): stats->crc[m] = zlib's crc32 of the stats->bytes[m] bytes rd delivered for mate stream m (-i: one text,
+ * crc[0]).  Without the flag nothing of it is launched or allocated and crc[] is 0. */
+#define SCALCE_STREAM_DIGEST 64
 typedef int64_t (*scalce_read_fn)(void *user, void *dst, uint64_t cap);
 typedef struct {
   double total_s, read_wait_s, h2d_wait_s, front_s, order_s, emit_s, entropy_s;
   uint64_t rounds, reads, bytes[2];
+  uint32_t crc[2];           /* SCALCE_STREAM_DIGEST */
 } scalce_stream_stats;
 int scalce_stream_compress(scalce_ctx *ctx, const scalce_params *p, scalce_read_fn rd1, void *user1, scalce_read_fn rd2,
                            void *user2, uint64_t piece_bytes, uint64_t reads_hint, int flags, scalce_batch **out,
@@ -461,6 +468,22 @@ int scalce_batch_tie_plan(const scalce_batch *b, uint32_t out[4]);
  * its fall-back, as the encoder's inner loop runs it.  out[0] = mismatches, out[1..5] = lo, hi, c_lo, c_hi, total of the first one. */
 int scalce_selftest_ac(scalce_ctx *ctx, uint64_t ncases, uint32_t seed, int general, uint32_t out[6]);
 
+/* ---- zlib's CRC-32 of a text on the device (kernels_crc.hpp; --digest and the check on -d) -----------------------------
+ * Polynomial 0xEDB88320 reflected, initial value and final xor 0xFFFFFFFF: the number gzip keeps in a member's trailer.
+ * scalce_crc32_device enqueues two launches on `stream` (spans of the range, each by one workgroup; then the join of the
+ * workgroups' words) and nothing else: behind them *d_crc holds crc32(0, data, nbytes).  d_data: any byte address, nothing
+ * outside [d_data, d_data + nbytes) is read; nbytes 0 .. 2^40 (0: *d_crc = 0).  ws: device scratch of
+ * scalce_crc32_ws_bytes(nbytes) bytes, 4-byte aligned, the launch's own until it has run.
+ * scalce_crc32_plan (no device call) says how a range that begins on a 16-byte boundary is cut: out = {bytes per lane per
+ * step, bytes per workgroup step (tile), bytes per workgroup (span: whole tiles), workgroups launched}.  A range that begins
+ * h bytes behind such a boundary is cut like one of h + nbytes bytes.
+ * scalce_crc32_combine (host only): crc32(A || B) from crc32(A), crc32(B) and B's length -- zlib's crc32_combine64 --, what
+ * joins the results of chunks, windows and stripes in order. */
+int scalce_crc32_device(scalce_ctx *ctx, const uint8_t *d_data, uint64_t nbytes, uint32_t *d_crc, void *ws, void *stream);
+uint64_t scalce_crc32_ws_bytes(uint64_t nbytes);
+int scalce_crc32_plan(uint64_t nbytes, uint32_t out[4]);
+uint32_t scalce_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b);
+
 /* ---- decode side (next row of SURVEY 8f-1): ac_read / ac_decoder (arithmetic.cpp:173-268,
  *      365-400).  d_blocks = [u32 size][bytes]... as written by scalce_batch_entropy. ---------- */
 int scalce_ac_decode(scalce_ctx *ctx, const uint32_t *table_host, const uint8_t *d_blocks, uint64_t nbytes,
@@ -646,6 +669,12 @@ typedef struct {
   scalce_read_fn len_rd[2];
   void *len_user[2];
   scalce_skip_fn len_skip[2];
+  /* != 0: the text handed to wr is hashed on the device on its way out.  Each window's final text -- behind the records kernel,
+   * exceptions, comments, pad strip and '+' lines -- or, with the order restore, each stripe's gathered text gets one
+   * scalce_crc32_device launch on the buffer its download reads; the words come down beside the window's error words and are
+   * joined in the order wr is called: stats->crc[m] / text_bytes[m] = zlib's crc32 and the size of everything wr received for
+   * mate m (mates one after the other: [0], [1]; an interleaved text: [0]).  0: nothing of it is launched. */
+  int32_t digest;
 } scalce_unpack_params;
 #define SCALCE_WINDOW_TEXT_DEFAULT (1ull << 30)
 typedef int (*scalce_write_fn)(void *user, int mate, uint64_t first_record, uint64_t nrecords, const void *text,
@@ -659,9 +688,11 @@ typedef struct {
   double total_s, setup_s, read_wait_s, decode_s, records_s, write_wait_s, write_s;
                                /* read_wait: in rd; decode / records: device time of the kernels; write_wait: the session
                                   waiting for a window buffer that wr still holds; write: inside wr */
-  int32_t error_mate, error_stream;  /* on failure: which stream of which mate (0 r, 1 n, 2 q, 3 l, 4 o, 5 c, 6 x, 7 p), or -1 */
+  int32_t error_mate, error_stream;  /* on failure: which stream of which mate (0 r, 1 n, 2 q, 3 l, 4 o, 5 c, 6 x, 7 p, 8 d), or -1 */
   int32_t error_wants_file;    /* the message in errbuf is a predicate: put the stream's file name in front of it */
   uint64_t decode_batches[2];  /* per mate: decoder batches enqueued (runs of whole frames, one scalce_ac_decoder_launch each) */
+  uint32_t crc[2];             /* params->digest: see there */
+  uint64_t text_bytes[2];
 } scalce_unpack_stats;
 int scalce_stream_decompress(scalce_ctx *ctx, const scalce_unpack_params *p, scalce_read_fn rd[2][3], void *user[2][3],
                              scalce_write_fn wr, void *wr_user, scalce_unpack_stats *stats, char *errbuf, size_t errcap);

@@ -27,6 +27,7 @@
 #include "hip_own.hpp"
 #include "lenstream.hpp"
 #include "orderstream.hpp"
+#include "digeststream.hpp"
 #include "cli_io.hpp"
 #include "cli_input.hpp"
 #include "cli_shares.hpp"
@@ -61,6 +62,8 @@ struct Options {
   bool lossless = false;                  // --lossless: --keep-order --keep-comments --keep-bases --keep-plus (-f: without the last)
   bool keep_bases = false;                // --keep-bases: every letter and quality the archive does not keep, in PREFIX_<m>.scalcex
   bool stored_bases = false;              // -d --stored-bases: a .scalcex next to the archive is ignored
+  bool digest = false;                    // --digest (with --lossless): bytes and CRC-32 of every input text, in PREFIX_1.scalced
+  bool test = false;                      // -d --test: decode everything, check the digest, write nothing
   bool temp_given = false;                // -t was given (the default of `temp` is the reference's)
   int gpus = 1;                           // --gpus N: one process per GPU, ONE archive (plain-text input, -c no)
   int container = 1;                      // 0 plain, 1 gzip (main.cpp:181-184 at -T 1)
@@ -103,6 +106,16 @@ static const char *HELP_TEXT =
     "      --bare-plus             decompression: ignore the .scalcep, write a bare '+'\n"
     "      --lossless              --keep-order --keep-comments --keep-bases --keep-plus: scalce -d returns the input byte for\n"
     "                              byte.  Not with -p above 0, -n, -Q, --gpus\n"
+    "      --digest                with --lossless: the size and zlib's CRC-32 of every input text (one per mate stream: several\n"
+    "                              files are their concatenation, gzip input is its decompressed text) go into OUTPUT_1.scalced,\n"
+    "                              taken on the device as the text comes up; every other file is the one the run without the\n"
+    "                              option writes.  For one single-member .fastq.gz the number is the one gzip -lv prints.\n"
+    "                              Decompression finds the .scalced by itself, takes the same number of the text it writes and\n"
+    "                              ends with status 1 when they differ (the output stays); it is not checked when another text\n"
+    "                              than the input's was asked for (--archive-order, --no-comments, --stored-bases, --bare-plus,\n"
+    "                              -n, -Q, --records, -i for -r's archive or -r for -i's, a stream of --lossless missing)\n"
+    "      --test                  decompression: decode everything and check the digest, write nothing (-o is not needed);\n"
+    "                              status 0: every stream read to its end without error and, with a .scalced, the text matches\n"
     "      --keep-bases            keep every base letter and the quality under an N: the archive stores a c g t as A C G T, every\n"
     "                              other letter as A, an N only through its quality, and returns a base whose quality maps to the\n"
     "                              lowest as N.  What it changes goes into OUTPUT_<m>.scalcex, every other file is the one the\n"
@@ -146,6 +159,8 @@ static const char *HELP_TEXT =
 //   PREFIX_<m>.scalcep  --keep-plus only (plusstream.hpp): magic, int32 0, int32 P (longest stored entry), int64 N, then the '+' line
 //                       of each record of the archive as an entry (empty: bare, '=': the header line again, '\'' + the line's
 //                       bytes), each followed by a newline; P = 0: no entries
+//   PREFIX_1.scalced    --digest only (digeststream.hpp): magic, int32 16, int32 kind (0 one text, 1 paired files, 2 interleaved; + 4
+//                       two-line records), int64 T, then T x {u64 bytes, u32 crc32, u32 0}: each input text's size and zlib CRC-32
 //   PREFIX_<m>.scalceq  magic, int64 Phred offset (mate 1's for both mates, compress.cpp:294,816-817); arithmetic coded:
 //                       the scaled table (QTABLE_WORDS x u32), the int64 symbol count and the coded blocks; -A: the q' rows
 static const uint8_t MAGIC[8] = {'s', 'c', 'a', 'l', 'c', 'e', '2', '2'};
@@ -467,7 +482,7 @@ static int do_compress(const Options &o, const std::vector<std::string> &files, 
   if (scalce_stream_compress(ctx, &p, MateSource::read_cb, &in.src[0], nsrc == 2 ? MateSource::read_cb : nullptr, nsrc == 2 ? &in.src[1] : nullptr,
                              piece, hint, SCALCE_STREAM_LEAN | SCALCE_STREAM_DEFER_ENTROPY | (o.keep_order ? SCALCE_STREAM_KEEP_ORDER : 0) |
                                  (o.keep_comments ? SCALCE_STREAM_KEEP_COMMENTS : 0) | (o.keep_bases ? SCALCE_STREAM_KEEP_BASES : 0) |
-                                 (o.keep_plus ? SCALCE_STREAM_KEEP_PLUS : 0), &b, &ss, emsg, sizeof emsg)) {
+                                 (o.keep_plus ? SCALCE_STREAM_KEEP_PLUS : 0) | (o.digest ? SCALCE_STREAM_DIGEST : 0), &b, &ss, emsg, sizeof emsg)) {
     if (!in.src[0].error.empty()) fputs(in.src[0].error.c_str(), stderr);  // (-i: a file of odd record count; the stream only saw a read error)
     else fprintf(stderr, "%s\n", emsg[0] ? emsg : scalce_last_error(ctx));
     exit(1);
@@ -507,6 +522,22 @@ static int do_compress(const Options &o, const std::vector<std::string> &files, 
   if (!o.keep_comments) for_each_archive_file(o, "c", [](char, const std::string &fn) { unlink(fn.c_str()); });
   if (!o.keep_bases) for_each_archive_file(o, "x", [](char, const std::string &fn) { unlink(fn.c_str()); });
   if (!o.keep_plus) for_each_archive_file(o, "p", [](char, const std::string &fn) { unlink(fn.c_str()); });
+  // --digest: what the run read, one entry per mate stream (a digest stream left by an earlier run goes like the others)
+  scalce_host::Digest dg;
+  if (o.digest) {
+    dg.kind = (o.paired ? scalce_host::DIGEST_KIND_PAIRED : o.interleave ? scalce_host::DIGEST_KIND_INTERLEAVED : scalce_host::DIGEST_KIND_SINGLE) |
+              (o.fasta ? scalce_host::DIGEST_KIND_FASTA : 0);
+    dg.texts = nsrc;
+    for (int m = 0; m < nsrc; m++) { dg.text[m].bytes = ss.bytes[m]; dg.text[m].crc = ss.crc[m]; }
+    uint8_t raw[scalce_host::DIGEST_MAX_BYTES];
+    const size_t n = scalce_host::digest_write(raw, dg);
+    OutFile fD;
+    fD.open(archive_path(o.out, 0, 'd'), gz_container(o, 'd'));
+    fD.write(raw, n);
+    fD.close();
+  } else {
+    unlink(archive_path(o.out, 0, 'd').c_str());
+  }
   const double t2b = now();
   SCOK(ctx, scalce_batch_finish(b, s_ent));  // the coder is through: sizes of the coded streams, device error word
   const double t2c = now();
@@ -541,6 +572,7 @@ static int do_compress(const Options &o, const std::vector<std::string> &files, 
   for (int m = 0; m < nm && o.keep_bases; m++) exception_log(N, exc_entries[m], exc_rows[m]);
   for (int m = 0; m < nm && o.keep_comments; m++) comment_log(N, com_bytes[m], com_longest[m]);
   for (int m = 0; m < nm && o.keep_plus; m++) plus_log(N, plus_rep[m], plus_lit[m], plus_longest[m]);
+  for (int m = 0; m < dg.texts; m++) LOG("\tDigest: %llu bytes, crc32 %08x\n", (unsigned long long)dg.text[m].bytes, dg.text[m].crc);
   LOG("\tSpill chunks: %u, pieces streamed: %llu\n", st4[3], (unsigned long long)ss.rounds);
   LOG("\tTime elapsed: %.2f s (sample %.2f; stream %.2f = waiting for the reader %.2f + for uploads %.2f + ingest/count/tokenize %.2f; "
       "order %.2f, emit %.2f; reads+names down and written beside the coder %.2f, waiting for the coder %.2f, qualities down and written %.2f, device buffers released %.2f)\n",
@@ -971,8 +1003,43 @@ static int do_decompress(const Options &o, const std::string &path, scalce_ctx *
   Archive ar(o, path, nm);
   const scalce_unpack_params p = unpack_params_from(o, nm, ar.lens, ar.has_lens);
   const scalce_unpack_range rg = unpack_range_from(o, nm, ar.files);
+  // the digest stream, when the archive has one: what the input was, and whether the text asked for is the input's
+  scalce_host::Digest dg;
+  const std::string dpath = scalce_name(ar.base[0], 'd');
+  struct stat dst;
+  const bool has_digest = stat(dpath.c_str(), &dst) == 0;
+  const char *unchecked = nullptr;
+  if (has_digest) {
+    ArchiveFile fd;
+    fd.open(dpath);
+    uint8_t raw[scalce_host::DIGEST_MAX_BYTES + 8];
+    size_t have = 0;
+    for (int64_t k; have < sizeof raw && (k = ArchiveFile::read(&fd, raw + have, sizeof raw - have)) != 0; have += (size_t)k)
+      if (k < 0) FAIL("Read error on %s\n", dpath.c_str());
+    if (const char *why = scalce_host::digest_read(raw, have, &dg)) {
+      if (!strncmp(why, "is not", 6)) FAIL("%s %s\n", dpath.c_str(), why);
+      FAIL("%s\n", why);
+    }
+    const int kind = dg.kind & 3, archive_texts = scalce_host::digest_kind_texts(dg.kind);
+    if (dg.texts != archive_texts) {
+      char msg[128];
+      scalce_host::digest_count_message(msg, sizeof msg, (uint64_t)dg.texts, (uint64_t)archive_texts);
+      FAIL("%s\n", msg);
+    }
+    const bool two_line = (dg.kind & scalce_host::DIGEST_KIND_FASTA) != 0;
+    unchecked = o.has_range ? "--records" : o.archive_order ? "--archive-order" : o.no_comments ? "--no-comments" : o.stored_bases ? "--stored-bases" :
+                o.bare_plus ? "--bare-plus" : !o.use_names ? "-n" : o.no_qual ? "-Q" :
+                kind == scalce_host::DIGEST_KIND_PAIRED && !o.paired ? (o.interleave ? "-i: the input was two files" : "the input was two files: give -r") :
+                kind == scalce_host::DIGEST_KIND_INTERLEAVED && !o.interleave ? (o.paired ? "-r: the input was one interleaved file" : "the input was interleaved: give -i") :
+                kind == scalce_host::DIGEST_KIND_SINGLE && o.pairs() ? "the input was one single-end text" :
+                two_line != o.fasta ? (two_line ? "the input was FASTA: give -f" : "-f: the input was FASTQ") :
+                !ar.has_order ? "no .scalceo" : !ar.has_comments ? "no .scalcec" : !ar.has_exceptions ? "no .scalcex" : !two_line && !ar.has_plus ? "no .scalcep" : nullptr;
+    if (unchecked && o.test) FAIL("--test: the text cannot be checked against the digest (%s)\n", unchecked);
+  }
+  scalce_unpack_params pd = p;
+  pd.digest = has_digest && !unchecked;
   TextSink sink;
-  sink.out = o.out; sink.split = o.split; sink.interleave = o.interleave;
+  sink.out = o.out; sink.split = o.split; sink.interleave = o.interleave; sink.discard = o.test;
   scalce_unpack_stats st;
   scalce_unpack_range_stats rs;
   scalce_restore_stats os;
@@ -1000,7 +1067,7 @@ static int do_decompress(const Options &o, const std::string &path, scalce_ctx *
       spill_dir = o.temp;
       struct stat tst;
       if (stat(spill_dir.c_str(), &tst) != 0 && mkdir(spill_dir.c_str(), 0777) != 0) FAIL("Cannot create temporary directory %s (-t)\n", spill_dir.c_str());
-    } else if (o.out == "-") {
+    } else if (o.out == "-" || o.out.empty()) {
       spill_dir = getenv("TMPDIR") && getenv("TMPDIR")[0] ? getenv("TMPDIR") : "/tmp";
     } else {
       const size_t sl = o.out.rfind('/');
@@ -1009,11 +1076,11 @@ static int do_decompress(const Options &o, const std::string &path, scalce_ctx *
     rp.spill_dir = spill_dir.c_str();
     memset(&rs, 0, sizeof rs);
     // (side streams: the one entry point that takes comments, exceptions and '+' lines, any of them; else the call as it always was)
-    rc = side ? scalce_stream_decompress_plus(ctx, &p, cmp, exp, plp, nullptr, &rp, ar.rd, ar.user, TextSink::write, &sink, &st, nullptr, &os, err, sizeof err)
-              : scalce_stream_decompress_restore(ctx, &p, &rp, ar.rd, ar.user, TextSink::write, &sink, &st, &os, err, sizeof err);
+    rc = side ? scalce_stream_decompress_plus(ctx, &pd, cmp, exp, plp, nullptr, &rp, ar.rd, ar.user, TextSink::write, &sink, &st, nullptr, &os, err, sizeof err)
+              : scalce_stream_decompress_restore(ctx, &pd, &rp, ar.rd, ar.user, TextSink::write, &sink, &st, &os, err, sizeof err);
   } else
-    rc = side ? scalce_stream_decompress_plus(ctx, &p, cmp, exp, plp, &rg, nullptr, ar.rd, ar.user, TextSink::write, &sink, &st, &rs, nullptr, err, sizeof err)
-              : scalce_stream_decompress_range(ctx, &p, &rg, ar.rd, ar.user, TextSink::write, &sink, &st, &rs, err, sizeof err);
+    rc = side ? scalce_stream_decompress_plus(ctx, &pd, cmp, exp, plp, &rg, nullptr, ar.rd, ar.user, TextSink::write, &sink, &st, &rs, nullptr, err, sizeof err)
+              : scalce_stream_decompress_range(ctx, &pd, &rg, ar.rd, ar.user, TextSink::write, &sink, &st, &rs, err, sizeof err);
   if (rc) {
     // (parts already written stay where they are)
     if (st.error_stream == 5 && st.error_mate >= 0 && !strncmp(err, "(ERROR) is not", 14))  // (a predicate about the comment stream's file)
@@ -1045,7 +1112,27 @@ static int do_decompress(const Options &o, const std::string &path, scalce_ctx *
         (unsigned long long)(rs.first_record + rs.nrecords), total, (unsigned long long)(rs.frames_decoded[0] + rs.frames_decoded[1]),
         (unsigned long long)(rs.frames_passed[0] + rs.frames_passed[1]));
   }
-  return 0;
+  // the digest: what was written (or, under --test, only decoded) against what the input was, text by text
+  if (!has_digest) {
+    if (o.test) LOG("\tDigest: none recorded; streams decode to their end\n");
+    return 0;
+  }
+  if (unchecked) { LOG("\tDigest: not checked (%s)\n", unchecked); return 0; }
+  int bad = 0;
+  for (int m = 0; m < dg.texts; m++) {
+    scalce_host::DigestText got;
+    got.bytes = st.text_bytes[m];
+    got.crc = st.crc[m];
+    if (got.bytes == dg.text[m].bytes && got.crc == dg.text[m].crc) {
+      LOG("\tDigest: %llu bytes, crc32 %08x: the input's\n", (unsigned long long)got.bytes, got.crc);
+      continue;
+    }
+    char msg[256];
+    scalce_host::digest_mismatch_message(msg, sizeof msg, m + 1, dg.text[m], got);
+    fprintf(stderr, "(ERROR) %s\n", msg);
+    bad = 1;
+  }
+  return bad;
 }
 
 // ---- the command line ------------------------------------------------------------------------------------------
@@ -1092,7 +1179,8 @@ static bool parse_options(int argc, char **argv, Options &o) {
                                      {"archive-order", 0, 0, 1007}, {"keep-comments", 0, 0, 1008},
                                      {"no-comments", 0, 0, 1009}, {"keep-bases", 0, 0, 1010},
                                      {"stored-bases", 0, 0, 1011}, {"keep-plus", 0, 0, 1012},
-                                     {"bare-plus", 0, 0, 1013}, {"lossless", 0, 0, 1014}, {0, 0, 0, 0}};
+                                     {"bare-plus", 0, 0, 1013}, {"lossless", 0, 0, 1014},
+                                     {"digest", 0, 0, 1015}, {"test", 0, 0, 1016}, {0, 0, 0, 0}};
   int opt;
   while ((opt = getopt_long(argc, argv, "vhp:T:dc:o:fs:t:B:rQAn:P:S:i", long_opt, 0)) != -1) {
     switch (opt) {
@@ -1138,6 +1226,8 @@ static bool parse_options(int argc, char **argv, Options &o) {
       case 1012: o.keep_plus = true; break;
       case 1013: o.bare_plus = true; break;
       case 1014: o.lossless = true; break;
+      case 1015: o.digest = true; break;
+      case 1016: o.test = true; break;
       default: fputs(HELP_TEXT, stdout); return false;
     }
   }
@@ -1150,7 +1240,15 @@ static bool parse_options(int argc, char **argv, Options &o) {
 // check_arguments, main.cpp:120-164, and what this build refuses; all of it before anything touches a device
 static void check_arguments(const Options &o, const std::vector<std::string> &files) {
   if (o.interleave && o.paired) FAIL("Interleaved option (-i) cannot be used with paired-end option (-r).\n");
-  if (o.out.empty()) FAIL("No output file specified.\n");
+  if (o.digest && o.decompress) FAIL("--digest is an option of compression: -d checks the text by itself when the archive has a .scalced\n");
+  if (o.digest && !o.lossless) FAIL("--digest needs --lossless: only then is the text -d writes the input's\n");
+  if (o.test) {  // (-o is not needed and is ignored)
+    if (!o.decompress) FAIL("--test can be only used with decompression (-d).\n");
+    const char *other = o.archive_order ? "--archive-order" : o.no_comments ? "--no-comments" : o.stored_bases ? "--stored-bases" : o.bare_plus ? "--bare-plus" :
+                        !o.use_names ? "-n" : o.no_qual ? "-Q" : o.has_range ? "--records" : nullptr;
+    if (other) FAIL("--test checks that the archive gives the input's text back: %s asks for another text\n", other);
+  }
+  if (o.out.empty() && !o.test) FAIL("No output file specified.\n");
   if (!o.use_names && o.library.empty()) FAIL("No library name specified.\n");
   if (o.has_range && !o.decompress) FAIL("--records can be only used with decompression (-d).\n");
   if (o.lossless) {  // (in front of the single options' refusals: each of these says why the promise cannot be kept)
@@ -1177,7 +1275,7 @@ static void check_arguments(const Options &o, const std::vector<std::string> &fi
   if (o.keep_bases && o.gpus > 1) FAIL("--keep-bases runs on one GPU: with --gpus %d the exceptions lie spread over the ranks\n", o.gpus);
   if (o.decompress && files.size() > 1) FAIL("Too many files specified (decompression only supports one file).\n");
   if (o.lossy < 0 || o.lossy > 100) FAIL("Percentage must be in range [0,100].\n");
-  if (o.out == "-" && (o.split || o.paired)) FAIL("stdout can be only used with single-end file decompression. It cannot be used with --split-reads option!\n");
+  if (o.out == "-" && !o.test && (o.split || o.paired)) FAIL("stdout can be only used with single-end file decompression. It cannot be used with --split-reads option!\n");
   if (files.empty()) FAIL("No input file specified.\n");
   for (auto &f : files)
     for (int m = 0; m < (o.paired ? 2 : 1); m++) {

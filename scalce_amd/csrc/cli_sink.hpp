@@ -42,6 +42,7 @@ struct TextSink {
   std::string out;          // -o
   int split = 0;            // -S
   bool interleave = false;  // -i: a part counts pairs
+  bool discard = false;     // --test: the text is dropped, no file is made
   struct PerMate {
     OutFile f;
     bool open = false;
@@ -69,6 +70,7 @@ struct TextSink {
   }
   static int write(void *user, int m, uint64_t, uint64_t nrec, const void *text, uint64_t nbytes, const uint64_t *roff) {
     TextSink *t = static_cast<TextSink *>(user);
+    if (t->discard) return 0;
     PerMate &x = t->pm[m];
     const uint8_t *b = static_cast<const uint8_t *>(text);
     if (!t->split) {
@@ -89,6 +91,7 @@ struct TextSink {
     return 0;
   }
   void finish(int m) {  // (an archive without records still gives its one empty file)
+    if (discard) return;
     if (!pm[m].open && !pm[m].files) open_next(m);
     if (pm[m].open) close_part(m);
   }

@@ -22,6 +22,7 @@
 #include "kernels_comments.hpp"
 #include "kernels_plus.hpp"
 #include "kernels_exceptions.hpp"
+#include "kernels_crc.hpp"
 
 using namespace scalce;
 
@@ -33,5 +34,6 @@ using namespace scalce;
 #include "host_order_emit.inc"
 #include "host_entropy.inc"
 #include "host_api.inc"
+#include "host_crc.inc"
 #include "host_decode.inc"
 #include "kernels_restore.hpp"

@@ -104,6 +104,9 @@ struct Slot {
   // archives with an exception stream: the window's entries per mate (they grow with the windows), the verdict, the pairs' scratch
   HBuf h_exc[2], h_xbad;
   DBuf d_exc[2], d_xbad, d_xws;
+  // params.digest: the CRC-32 of the text that comes down from this slot (a window's, or a stripe's), and the launch's scratch
+  HBuf h_crc;
+  DBuf d_crc, d_crcws;
   Event ev_up, ev_rec, ev_done, t_rec0, t_rec1;
   bool busy = false;
 };
@@ -352,6 +355,12 @@ struct Session {
         SD_TRY(dmalloc(s.d_cbad, 64));
       }
       if (X) SD_TRY(X->setup_slot(*this, i, roff_bytes));
+      if (P.digest) {
+        SD_TRY(hmalloc(s.h_crc, 64));
+        memset(s.h_crc.p, 0, 64);
+        SD_TRY(dmalloc(s.d_crc, 64));
+        SD_TRY(dmalloc(s.d_crcws, scalce_crc32_ws_bytes(cap_text)));
+      }
       if (strip) {
         SD_TRY(hmalloc(s.h_len, len_bytes));
         SD_TRY(dmalloc(s.d_len, len_bytes));
@@ -367,7 +376,7 @@ struct Session {
   void free_slots() {
     for (Slot &s : slot) {
       for (DBuf *b : {&s.d_len, &s.d_text2, &s.d_roff2, &s.d_scan, &s.d_com, &s.d_textc, &s.d_roffc, &s.d_cws, &s.d_cbad, &s.d_exc[0], &s.d_exc[1], &s.d_xbad, &s.d_xws,
-                      &s.d_plus, &s.d_textp, &s.d_roffp, &s.d_pws, &s.d_pbad,
+                      &s.d_plus, &s.d_textp, &s.d_roffp, &s.d_pws, &s.d_pbad, &s.d_crc, &s.d_crcws,
                       &s.d_in, &s.d_text, &s.d_roff})
         drop(*b);
       s = Slot();
@@ -515,6 +524,10 @@ struct Session {
   void hand_over(const Job &j) {
     Slot &s = slot[j.slot];
     const double t0 = now_s();
+    if (P.digest) {  // (jobs reach wr in order: so do their words)
+      S.crc[j.mate] = scalce_crc32_combine(S.crc[j.mate], s.h_crc.as<u32>()[0], j.nbytes);
+      S.text_bytes[j.mate] += j.nbytes;
+    }
     if (wr(wr_user, j.mate, j.first, j.n, s.h_text.as<u8>(), j.nbytes, P.split ? s.h_roff.as<u64>() : nullptr)) fail(SCALCE_ERR_FORMAT, j.mate, -1, 0, "the write callback failed");
     S.write_s += now_s() - t0;
   }
@@ -645,6 +658,10 @@ struct Session {
       SD_TRY(lib(scalce_order_place(ctx, q.d_ord.as<u32>(), m, base, expect, q.d_sidx.as<u32>(), q.d_bad.as<u32>(), s_main)));
       SD_TRY(lib(scalce_records_permute(ctx, sl.d_text.as<u8>(), sl.d_roff.as<u64>(), m, bytes, q.d_sidx.as<u32>(), q.d_gtext.as<u8>(), cap_text,
                                         q.d_groff.as<u64>(), q.d_ws.p, s_main)));
+      if (P.digest) {  // the stripe's text where the download reads it
+        SD_TRY(lib(scalce_crc32_device(ctx, q.d_gtext.as<u8>(), bytes, sl.d_crc.as<u32>(), sl.d_crcws.p, s_main)));
+        SD_HIP(hipMemcpyAsync(sl.h_crc.p, sl.d_crc.p, 4, hipMemcpyDeviceToHost, s_main));
+      }
       SD_HIP(hipMemcpyAsync(sl.h_text.p, q.d_gtext.p, bytes, hipMemcpyDeviceToHost, s_main));
       if (P.split) SD_HIP(hipMemcpyAsync(sl.h_roff.p, q.d_groff.p, 8 * (m + 1), hipMemcpyDeviceToHost, s_main));
       SD_HIP(hipMemcpyAsync(q.h_bad.p, q.d_bad.p, 4, hipMemcpyDeviceToHost, s_main));
@@ -920,6 +937,10 @@ struct Session {
     if (X) {
       SD_TRY(X->download(*this, w));
     } else {
+      if (P.digest) {  // the window's final text where the download reads it
+        SD_TRY(lib(scalce_crc32_device(ctx, window_text(w).as<u8>(), w.nbytes, s.d_crc.as<u32>(), s.d_crcws.p, s_down)));
+        SD_HIP(hipMemcpyAsync(s.h_crc.p, s.d_crc.p, 4, hipMemcpyDeviceToHost, s_down));
+      }
       SD_HIP(hipMemcpyAsync(s.h_text.p, window_text(w).p, w.nbytes, hipMemcpyDeviceToHost, s_down));
       if (P.split) SD_HIP(hipMemcpyAsync(s.h_roff.p, window_roff(w).p, 8 * (w.n + 1), hipMemcpyDeviceToHost, s_down));
     }

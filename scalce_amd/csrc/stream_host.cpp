@@ -112,6 +112,15 @@ struct Mate {
   uint64_t head = 0, tail = 0;    // queue of chunks in d_raw: [head, tail)
   bool eof = false;               // the stream's last chunk has been taken from the ring
   bool all_landed() const { return eof && head == tail; }
+  // SCALCE_STREAM_DIGEST: a ring of CRC words, one per chunk, each with the event behind its way down; `open` = chunks whose word
+  // has not been joined yet (slot, bytes), oldest first
+  static constexpr int CRC_SLOTS = 64;
+  DBuf d_crc, d_crc_ws;
+  HBuf h_crc;
+  std::vector<Event> crc_ev;
+  std::deque<std::pair<int, uint64_t>> crc_open;
+  uint64_t crc_chunks = 0;
+  uint32_t crc = 0;
   uint8_t *text() const { return d_text[cur].as<uint8_t>(); }
 };
 
@@ -156,6 +165,34 @@ int stream_run(scalce_ctx *ctx, const scalce_params *p, scalce_read_fn rd[2], vo
     if ((flags & SCALCE_STREAM_KEEP_COMMENTS) && (rc = scalce_batch_set_keep_comments(b, 1))) { err = scalce_last_error(ctx); return rc; }
     if ((flags & SCALCE_STREAM_KEEP_BASES) && (rc = scalce_batch_set_keep_bases(b, 1))) { err = scalce_last_error(ctx); return rc; }
   }
+  const bool digest = (flags & SCALCE_STREAM_DIGEST) != 0;
+  if (digest)
+    for (int m = 0; m < nm; m++) {
+      ST_HIP(dbuf_alloc(M[m].d_crc, sizeof(uint32_t) * Mate::CRC_SLOTS));
+      ST_HIP(dbuf_alloc(M[m].d_crc_ws, scalce_crc32_ws_bytes(piece)));
+      ST_HIP(M[m].h_crc.alloc(sizeof(uint32_t) * Mate::CRC_SLOTS));
+      M[m].crc_ev.resize(Mate::CRC_SLOTS);
+      for (Event &e : M[m].crc_ev) ST_HIP(e.create());
+    }
+  // the oldest open word of a mate joins its text's CRC; its event has long passed unless the ring is full or the run ends
+  auto crc_join_oldest = [&](Mate &x) -> int {
+    const std::pair<int, uint64_t> o = x.crc_open.front();
+    if (hipEventSynchronize(x.crc_ev[o.first]) != hipSuccess) { err = "the digest of a chunk failed"; return SCALCE_ERR_HIP; }
+    x.crc = scalce_crc32_combine(x.crc, x.h_crc.as<uint32_t>()[o.first], o.second);
+    x.crc_open.pop_front();
+    return SCALCE_OK;
+  };
+  // one launch over the chunk where it arrived, on the stream that takes it into the piece; the word follows it down
+  auto crc_chunk = [&](Mate &x, int sl) -> int {
+    int rc2;
+    if ((int)x.crc_open.size() == Mate::CRC_SLOTS && (rc2 = crc_join_oldest(x))) return rc2;
+    const int k = (int)(x.crc_chunks++ % Mate::CRC_SLOTS);
+    if ((rc2 = scalce_crc32_device(ctx, x.d_raw[sl].as<uint8_t>(), x.raw_n[sl], x.d_crc.as<uint32_t>() + k, x.d_crc_ws.p, s_main))) { err = scalce_last_error(ctx); return rc2; }
+    if (hipMemcpyAsync(x.h_crc.as<uint32_t>() + k, x.d_crc.as<uint32_t>() + k, sizeof(uint32_t), hipMemcpyDeviceToHost, s_main) != hipSuccess ||
+        hipEventRecord(x.crc_ev[k], s_main) != hipSuccess) { err = "hipMemcpyAsync (chunk digest) failed"; return SCALCE_ERR_HIP; }
+    x.crc_open.emplace_back(k, x.raw_n[sl]);
+    return SCALCE_OK;
+  };
   for (int m = 0; m < nm; m++) M[m].reader = std::thread(reader_main, &M[m].ring, rd[m], user[m], piece);
 
   // one more chunk of every mate that has input left and a free slot starts its way up
@@ -192,6 +229,7 @@ int stream_run(scalce_ctx *ctx, const scalce_params *p, scalce_read_fn rd[2], vo
         const double t0 = now_s();
         if (hipEventSynchronize(x.up_ev[sl]) != hipSuccess) { err = "chunk upload failed"; return SCALCE_ERR_HIP; }
         S.h2d_wait_s += now_s() - t0;
+        if (digest && x.raw_n[sl]) { const int rc2 = crc_chunk(x, sl); if (rc2) return rc2; }
         if (x.raw_n[sl] && hipMemcpyAsync(x.text() + x.have, x.d_raw[sl].p, x.raw_n[sl], hipMemcpyDeviceToDevice, s_main) != hipSuccess) {
           err = "hipMemcpyAsync (piece assembly) failed";
           return SCALCE_ERR_HIP;
@@ -242,6 +280,11 @@ int stream_run(scalce_ctx *ctx, const scalce_params *p, scalce_read_fn rd[2], vo
   double t0 = now_s();
   if ((rc = scalce_batch_order(b, s_main)) || (rc = scalce_batch_finish(b, s_main))) { err = scalce_last_error(ctx); return rc; }
   S.order_s = now_s() - t0;
+  for (int m = 0; m < nm && digest; m++) {  // (the stream has just been waited for: every word is down)
+    while (!M[m].crc_open.empty())
+      if ((rc = crc_join_oldest(M[m]))) return rc;
+    S.crc[m] = M[m].crc;
+  }
   // the staging buffers are dead: give them back before the emit stage allocates the streams
   for (int m = 0; m < nm; m++)
     for (int i = 0; i < 2; i++) { M[m].d_text[i].release(); M[m].d_raw[i].release(); }

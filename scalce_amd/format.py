@@ -13,6 +13,10 @@ A run that keeps the '+' lines (--keep-plus) has a .scalcep per mate, ours alone
 longest stored entry in bytes), int64 N, then N entries in archive order, each followed by a newline.  An entry is empty (a
 bare '+'), b"=" (the line repeats the header line behind its '@') or b"'" followed by the line's bytes behind the '+'.
 P = 0: no entries follow, every line was bare.
+
+A run that records what it read (--lossless --digest) has ONE .scalced, ours alone: magic, int32 16 (entry width), int32 kind
+(0 one text, 1 paired files, 2 interleaved; + 4 for two-line records), int64 T (texts: 1 or 2), then T entries of {u64 bytes,
+u32 crc32, u32 0}: zlib's CRC-32 of each mate stream's text as the run read it.
 """
 import gzip
 import struct
@@ -123,6 +127,38 @@ def unpack_plus(data):
     if any(e and e != b"=" and not (e[:1] == b"'" and len(e) > 1) for e in entries):
         raise ValueError("plus-line stream: malformed entry")
     return entries
+
+
+DIGEST_HEADER_BYTES = 24
+DIGEST_ENTRY_WIDTH = 16
+
+
+def pack_digest(kind, texts):
+    """The bytes of a .scalced stream: texts = [(bytes, crc32)] of one or two texts."""
+    if len(texts) not in (1, 2) or not 0 <= kind <= 6 or kind & 3 == 3:
+        raise ValueError("a digest stream holds one or two texts of kind 0, 1, 2 (+ 4)")
+    return MAGIC + struct.pack("<iiq", DIGEST_ENTRY_WIDTH, kind, len(texts)) + b"".join(struct.pack("<QII", n, crc, 0) for n, crc in texts)
+
+
+def unpack_digest(data):
+    """(kind, [(bytes, crc32)]) of the bytes of a .scalced stream (out of its container); ValueError with the library's message."""
+    data = bytes(data)
+    if len(data) < DIGEST_HEADER_BYTES:
+        raise ValueError("truncated digest stream")
+    width, kind, t = struct.unpack("<iiq", data[8:24])
+    if data[:7] != MAGIC[:7] or width != DIGEST_ENTRY_WIDTH or not 0 <= kind <= 6 or kind & 3 == 3 or t not in (1, 2):
+        raise ValueError("is not a scalce digest stream")
+    if len(data) < DIGEST_HEADER_BYTES + DIGEST_ENTRY_WIDTH * t:
+        raise ValueError("truncated digest stream")
+    if len(data) > DIGEST_HEADER_BYTES + DIGEST_ENTRY_WIDTH * t:
+        raise ValueError("is not a scalce digest stream")
+    out = []
+    for i in range(t):
+        n, crc, zero = struct.unpack_from("<QII", data, DIGEST_HEADER_BYTES + DIGEST_ENTRY_WIDTH * i)
+        if zero:
+            raise ValueError("is not a scalce digest stream")
+        out.append((n, crc))
+    return kind, out
 
 
 def sample_qmap(fastq_bytes, sample=100000, lossy=0):

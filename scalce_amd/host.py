@@ -498,11 +498,14 @@ def entropy_begin_group(batches, prep_stream=0, stream=0, last=False):
 class StreamStats(C.Structure):
     _fields_ = [("total_s", C.c_double), ("read_wait_s", C.c_double), ("h2d_wait_s", C.c_double), ("front_s", C.c_double),
                 ("order_s", C.c_double), ("emit_s", C.c_double), ("entropy_s", C.c_double), ("rounds", C.c_uint64),
-                ("reads", C.c_uint64), ("bytes", C.c_uint64 * 2)]
+                ("reads", C.c_uint64), ("bytes", C.c_uint64 * 2),
+                # STREAM_DIGEST: zlib's CRC-32 of each mate stream's text as the run read it (bytes[] says how long it was)
+                ("crc", C.c_uint32 * 2)]
 
 
 READ_FN = C.CFUNCTYPE(C.c_int64, C.c_void_p, C.c_void_p, C.c_uint64)
 STREAM_LEAN, STREAM_DEFER_ENTROPY = 1, 2
+STREAM_DIGEST = 64  # SCALCE_STREAM_DIGEST
 
 
 def stream_compress(ctx, params, read1, read2=None, piece_bytes=0, reads_hint=0, flags=0):
@@ -544,12 +547,18 @@ class UnpackParams(C.Structure):
                 ("len_rd", READ_FN * 2), ("len_user", C.c_void_p * 2), ("len_skip", SKIP_FN * 2)]
 
 
+class UnpackParamsDigest(UnpackParams):
+    """scalce_unpack_params whole, as the library reads it: UnpackParams and, appended, `digest` -- != 0: the CRC-32 of the text
+    handed to wr is taken on the device (UnpackStats.crc / .text_bytes).  What _unpack_params makes; it passes for an UnpackParams."""
+    _fields_ = [("digest", C.c_int32)]
+
+
 class UnpackStats(C.Structure):
     _fields_ = [("windows", C.c_uint64), ("window_text_bytes", C.c_uint64), ("peak_device_bytes", C.c_uint64),
                 ("pinned_host_bytes", C.c_uint64), ("records", C.c_uint64 * 2), ("total_s", C.c_double), ("setup_s", C.c_double),
                 ("read_wait_s", C.c_double), ("decode_s", C.c_double), ("records_s", C.c_double), ("write_wait_s", C.c_double),
                 ("write_s", C.c_double), ("error_mate", C.c_int32), ("error_stream", C.c_int32), ("error_wants_file", C.c_int32),
-                ("decode_batches", C.c_uint64 * 2)]
+                ("decode_batches", C.c_uint64 * 2), ("crc", C.c_uint32 * 2), ("text_bytes", C.c_uint64 * 2)]
 
 
 WRITE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64))
@@ -648,7 +657,7 @@ def _unpack_write_fn(write):
 
 
 def _unpack_params(mates, interleave, no_qualities, mate_digit, library, split, window_text_bytes):
-    return UnpackParams(mates, int(interleave), int(no_qualities), int(mates == 2 if mate_digit is None else mate_digit),
+    return UnpackParamsDigest(mates, int(interleave), int(no_qualities), int(mates == 2 if mate_digit is None else mate_digit),
                         int(library is not None), int(split), library.encode() if library is not None else None, int(window_text_bytes))
 
 
@@ -738,8 +747,9 @@ def _decompress_streams(ctx, p, cm, rg, rp, rd, user, wfn, st, rst, ost, msg, ex
 
 def stream_decompress(ctx, readers, write, mates=1, interleave=False, no_qualities=False, mate_digit=None, library=None,
                       split=0, window_text_bytes=0, first_record=0, nrecords=None, skippers=None, length_readers=None,
-                      length_skippers=None, comment_readers=None, exception_readers=None, plus_readers=None):
-    """scalce_stream_decompress_range: an archive, or a range of its records, back to text in windows of whole records.
+                      length_skippers=None, comment_readers=None, exception_readers=None, plus_readers=None, digest=False):
+    """digest: the CRC-32 of the text handed to `write` is taken on the device: the stats' crc / text_bytes, per mate.
+    scalce_stream_decompress_range: an archive, or a range of its records, back to text in windows of whole records.
     readers[m] = the three callables (cap) -> bytes of mate m's .scalcer, .scalcen and .scalceq streams (b"" at the end; raise
     for a read error); write(mate, first_record, nrecords, text_bytes, record_offsets or None) receives every window in
     order, from the library's writer thread (raise to end the session).  library: print names as <library>.<index> whatever
@@ -762,6 +772,7 @@ def stream_decompress(ctx, readers, write, mates=1, interleave=False, no_qualiti
             if skippers is not None and skippers[m] is not None and skippers[m][k] is not None:
                 rg.skip[m][k] = _unpack_skip_fn(keep, skippers[m][k])
     p = _unpack_params(mates, interleave, no_qualities, mate_digit, library, split, window_text_bytes)
+    p.digest = int(bool(digest))
     for m in range(mates):
         if length_readers is not None and length_readers[m] is not None:
             p.len_rd[m] = _unpack_read_fn(keep, length_readers[m])
@@ -878,6 +889,43 @@ def order_gather(ctx, d_in, d_source, n, d_out, stream=0):
     L.scalce_order_gather.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
     L.scalce_order_gather.restype = C.c_int
     ctx._check(L.scalce_order_gather(ctx.h, d_in, d_source, int(n), d_out, stream))
+
+
+# ---- zlib's CRC-32 of device memory (--digest; kernels_crc.hpp) ---------------------------------------------------------------
+def crc32_plan(nbytes):
+    """scalce_crc32_plan (no device): (G, T, S, workgroups) -- bytes per lane per step, per workgroup step (tile), per workgroup
+    (span) and the workgroups launched for a range of nbytes that begins on a 16-byte boundary."""
+    L = lib()
+    L.scalce_crc32_plan.argtypes = [C.c_uint64, C.POINTER(C.c_uint32)]
+    L.scalce_crc32_plan.restype = C.c_int
+    out = (C.c_uint32 * 4)()
+    rc = L.scalce_crc32_plan(int(nbytes), out)
+    if rc:
+        raise ScalceError(f"[{rc}] scalce_crc32_plan")
+    return tuple(int(v) for v in out)
+
+
+def crc32_ws_bytes(nbytes):
+    L = lib()
+    L.scalce_crc32_ws_bytes.argtypes = [C.c_uint64]
+    L.scalce_crc32_ws_bytes.restype = C.c_uint64
+    return int(L.scalce_crc32_ws_bytes(int(nbytes)))
+
+
+def crc32_combine(crc_a, crc_b, len_b):
+    """scalce_crc32_combine (no device): crc32(A || B) from crc32(A), crc32(B) and len(B)."""
+    L = lib()
+    L.scalce_crc32_combine.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64]
+    L.scalce_crc32_combine.restype = C.c_uint32
+    return int(L.scalce_crc32_combine(int(crc_a), int(crc_b), int(len_b)))
+
+
+def crc32_device(ctx, d_data, nbytes, d_crc, d_ws, stream=0):
+    """scalce_crc32_device: enqueues zlib's crc32 of nbytes at d_data (any byte address) into the u32 at d_crc (device pointers)."""
+    L = ctx.L
+    L.scalce_crc32_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.scalce_crc32_device.restype = C.c_int
+    ctx._check(L.scalce_crc32_device(ctx.h, d_data, int(nbytes), d_crc, d_ws, stream))
 
 
 # ---- what follows the names (archives made with --keep-comments) ------------------------------------------------------------
@@ -1073,8 +1121,9 @@ class RestoreStats(C.Structure):
 
 def stream_decompress_restore(ctx, readers, order_readers, write, spill_dir, mates=1, interleave=False, no_qualities=False,
                               mate_digit=None, library=None, split=0, window_text_bytes=0, length_readers=None, comment_readers=None,
-                              exception_readers=None, plus_readers=None):
-    """scalce_stream_decompress_restore: stream_decompress with the input order restored.  order_readers[m]: the callable
+                              exception_readers=None, plus_readers=None, digest=False):
+    """digest: as for stream_decompress.
+    scalce_stream_decompress_restore: stream_decompress with the input order restored.  order_readers[m]: the callable
     (cap) -> bytes of the .scalceo stream, read from its start once per mate pass (interleaved: only [0]); write receives
     the text in input order, one stripe per call, first_record = the input index of its first record.  Returns
     UnpackStats; its attribute `restore` holds the RestoreStats."""
@@ -1087,6 +1136,7 @@ def stream_decompress_restore(ctx, readers, order_readers, write, spill_dir, mat
             if readers[m][k] is not None:
                 rd[m][k] = _unpack_read_fn(keep, readers[m][k])
     p = _unpack_params(mates, interleave, no_qualities, mate_digit, library, split, window_text_bytes)
+    p.digest = int(bool(digest))
     rp = RestoreParams()
     rp.spill_dir = os.fsencode(spill_dir)
     for m in range(1 if interleave else mates):
