@@ -34,10 +34,14 @@ __attribute__((format(printf, 6, 7))) inline int failure(Failure &f, int rc, int
   f.rc = rc; f.msg = b; f.mate = mate; f.stream = stream; f.wants_file = wants_file;
   return rc;
 }
-// a stream that ends, or fails, before what is asked of it (stream: 0 r, 1 n, 2 q, 3 l, 4 o, 5 c, 6 x, 7 p)
+// the streams the walk names in a failure: r, n, q, l, o, c, x, p by the letter that ends their files' names.  The values reach
+// the library's callers through Failure::stream (scalce_unpack_stats.error_stream): they stay as they are.
+enum StreamId { ST_READ = 0, ST_NAME = 1, ST_QUALITY = 2, ST_LENGTH = 3, ST_ORDER = 4, ST_COMMENT = 5, ST_EXCEPTION = 6, ST_PLUS = 7 };
 inline const char *stream_name(int stream) {
-  return stream == 0 ? "read" : stream == 1 ? "name" : stream == 2 ? "quality" : stream == 3 ? "length" : stream == 5 ? "comment" : stream == 6 ? "exception" : stream == 7 ? "plus-line" : "order";
+  static const char *const NAME[8] = {"read", "name", "quality", "length", "order", "comment", "exception", "plus-line"};
+  return NAME[stream >= 0 && stream < 8 ? stream : ST_ORDER];
 }
+// a stream that ends, or fails, before what is asked of it
 inline int read_error(Failure &f, int m, int stream) { return failure(f, SCALCE_ERR_FORMAT, m, stream, 0, "read error on the %s stream", stream_name(stream)); }
 inline int truncated(Failure &f, int m, int stream) { return failure(f, SCALCE_ERR_FORMAT, m, stream, 0, "(ERROR) truncated %s stream", stream_name(stream)); }
 inline int short_stream(Failure &f, int m, int stream, const Src &s) { return s.bad ? read_error(f, m, stream) : truncated(f, m, stream); }
@@ -59,6 +63,33 @@ struct Buckets {
   u8 header[12];
 };
 
+// What the two streams of text entries -- one newline-terminated entry per record -- differ in on the walk: their id and the
+// text of their failures, and what the plus-line stream alone has: a header whose longest entry is 0 says that no entries
+// follow (every record's is the empty one), and an entry has to be of a class (plusstream.hpp).
+struct TextKind {
+  StreamId stream;
+  const char *(*header_read)(const uint8_t *h, size_t have, uint32_t *longest, uint64_t *n);
+  const char *(*entry_too_long)();
+  int (*count_message)(char *out, size_t cap, uint64_t entries, uint64_t records);
+  bool header_alone;                              // longest == 0: the file is its header
+  const char *(*wrong)(const u8 *e, size_t len);  // what is wrong with an entry of len bytes, or nullptr
+};
+inline const char *any_entry(const u8 *, size_t) { return nullptr; }
+inline const char *plus_entry_wrong(const u8 *e, size_t len) { return plus_class(e, len) == PLUS_MALFORMED ? plus_malformed() : nullptr; }
+inline constexpr TextKind COMMENT_KIND = {ST_COMMENT, comment_header_read, comment_entry_too_long, comment_count_message, false, any_entry};
+inline constexpr TextKind PLUS_KIND = {ST_PLUS, plus_header_read, plus_entry_too_long, plus_count_message, true, plus_entry_wrong};
+static_assert(COMMENT_HEADER_BYTES == PLUS_HEADER_BYTES, "the text streams share a header");
+// ... and such a stream of a mate, and where the walk stands in it
+struct TextStream {
+  const TextKind *kind;
+  Src src;
+  bool open = false;
+  u32 longest = 0;          // its header's C or P: the longest entry, without the newline
+  u64 total = 0, taken = 0;  // its header's N; entries taken or passed over so far
+  u64 delivered = 0, skipped = 0;
+  bool no_entries() const { return kind->header_alone && !longest; }
+};
+
 // what a mate's streams are and where the walk stands in them
 struct ArcMate {
   Src r, n, q;
@@ -66,16 +97,8 @@ struct ArcMate {
   bool has_len = false;
   int l_width = 0;           // bytes per entry
   u64 l_delivered = 0, l_skipped = 0;
-  Src c;                     // the comment stream of an archive made with --keep-comments (scalce_unpack_comments), or not open
-  bool has_com = false;
-  u32 c_longest = 0;         // its header's C: the longest entry, without the newline
-  u64 c_total = 0, c_taken = 0;  // its header's N; entries taken or passed over so far
-  u64 c_delivered = 0, c_skipped = 0;
-  Src p;                     // the plus-line stream of an archive made with --keep-plus (scalce_unpack_plus), or not open
-  bool has_plus = false;
-  u32 p_longest = 0;         // its header's P: the longest stored entry, without the newline (0: no entries follow)
-  u64 p_total = 0, p_taken = 0;  // its header's N; entries taken or passed over so far
-  u64 p_delivered = 0, p_skipped = 0;
+  TextStream com{&COMMENT_KIND};  // the comment stream of an archive made with --keep-comments (scalce_unpack_comments), or not open
+  TextStream plus{&PLUS_KIND};    // the plus-line stream of an archive made with --keep-plus (scalce_unpack_plus), or not open
   int L = 0, no_ac = 0;
   int64_t phred = 0;
   bool q_empty = false;
@@ -134,33 +157,33 @@ struct Walk {
       x.r.open(rd[m][0], RG.skip[m][0], user[m][0], wait, &RS.bytes_delivered[m][0], &RS.bytes_skipped[m][0]);
       x.n.open(rd[m][1], RG.skip[m][1], user[m][1], wait, &RS.bytes_delivered[m][1], &RS.bytes_skipped[m][1]);
       x.q.open(qual ? rd[m][2] : nullptr, RG.skip[m][2], qual ? user[m][2] : nullptr, wait, &RS.bytes_delivered[m][2], &RS.bytes_skipped[m][2]);
-      if (!x.r.need(8) || memcmp(x.r.ptr(), "scalce2", 7)) return failure(f, SCALCE_ERR_FORMAT, m, 0, 1, "is not a scalce archive");
+      if (!x.r.need(8) || memcmp(x.r.ptr(), "scalce2", 7)) return failure(f, SCALCE_ERR_FORMAT, m, ST_READ, 1, "is not a scalce archive");
       const bool has_no_ac = x.r.ptr()[6] == '2' && x.r.ptr()[7] >= '2';
       x.r.skip(8);
       int32_t v = 0;
       if (has_no_ac) {
-        if (!x.r.get(v)) return truncated(f, m, 0);
+        if (!x.r.get(v)) return truncated(f, m, ST_READ);
         x.no_ac = v;
       }
-      if (!x.r.get(v)) return truncated(f, m, 0);
+      if (!x.r.get(v)) return truncated(f, m, ST_READ);
       x.L = v;
-      if (x.L <= 0) return failure(f, SCALCE_ERR_FORMAT, m, 0, 0, "(ERROR) read length %d in the read stream's header", x.L);
-      if (x.r.bad) return read_error(f, m, 0);
+      if (x.L <= 0) return failure(f, SCALCE_ERR_FORMAT, m, ST_READ, 0, "(ERROR) read length %d in the read stream's header", x.L);
+      if (x.r.bad) return read_error(f, m, ST_READ);
       if (qual) {
         if (x.q.need(16)) { x.q.skip(8); x.q.get(x.phred); } else x.q.skip(x.q.avail());
         x.q_empty = !x.q.need(1);
-        if (x.q.bad) return read_error(f, m, 2);
+        if (x.q.bad) return read_error(f, m, ST_QUALITY);
       }
       if (x.n.need(8)) x.n.skip(8);
       if (P.len_rd[m]) {  // the fourth stream: header, then one entry per record
         x.l.open(P.len_rd[m], P.len_skip[m], P.len_user[m], wait, &x.l_delivered, &x.l_skipped);
         int hl = 0;
         const bool whole = x.l.need(LEN_HEADER_BYTES);
-        if (x.l.bad) return read_error(f, m, 3);
-        if (const char *why = len_header_read(x.l.ptr(), whole ? LEN_HEADER_BYTES : 0, &x.l_width, &hl)) return failure(f, SCALCE_ERR_FORMAT, m, 3, 0, "(ERROR) %s", why);
+        if (x.l.bad) return read_error(f, m, ST_LENGTH);
+        if (const char *why = len_header_read(x.l.ptr(), whole ? LEN_HEADER_BYTES : 0, &x.l_width, &hl)) return failure(f, SCALCE_ERR_FORMAT, m, ST_LENGTH, 0, "(ERROR) %s", why);
         x.l.skip(LEN_HEADER_BYTES);
         if (hl != x.L)
-          return failure(f, SCALCE_ERR_FORMAT, m, 3, 0, "(ERROR) the length stream was written for reads of up to %d bases, the read stream holds reads of %d", hl, x.L);
+          return failure(f, SCALCE_ERR_FORMAT, m, ST_LENGTH, 0, "(ERROR) the length stream was written for reads of up to %d bases, the read stream holds reads of %d", hl, x.L);
         x.has_len = true;
       }
     }
@@ -178,7 +201,7 @@ struct Walk {
           while (n.need(1)) { library.append((const char *)n.ptr(), n.avail()); n.skip(n.avail()); if (library.size() > 4096) break; }
         }
     }
-    if (!names && library.size() > 255) return failure(f, SCALCE_ERR_ARG, -1, 1, 0, "library name longer than 255 characters");
+    if (!names && library.size() > 255) return failure(f, SCALCE_ERR_ARG, -1, ST_NAME, 0, "library name longer than 255 characters");
     if (P.interleave && M[0]->no_ac != M[1]->no_ac) return failure(f, SCALCE_ERR_FORMAT, -1, -1, 0, "(ERROR) the mates were not archived together");
     return SCALCE_OK;
   }
@@ -189,7 +212,7 @@ struct Walk {
     ArcMate &x = *M[m];
     while (!x.bk.left) {
       if (!x.r.need(12, look)) {
-        if (x.r.bad) { read_error(f, m, 0); return -1; }
+        if (x.r.bad) { read_error(f, m, ST_READ); return -1; }
         return 1;
       }
       int32_t core = 0;
@@ -203,10 +226,10 @@ struct Walk {
         const int cl = has ? cores.length(cores.user, core) : -1;
         const char *cs = has ? cores.string(cores.user, core) : nullptr;
         if (cl < 0 || !cs) {
-          failure(f, SCALCE_ERR_FORMAT, m, 0, 0, "(ERROR) archive refers to core %d which the core table does not have", core);
+          failure(f, SCALCE_ERR_FORMAT, m, ST_READ, 0, "(ERROR) archive refers to core %d which the core table does not have", core);
           return -1;
         }
-        if (cl > (int)sizeof x.bk.core || cl > x.L) { failure(f, SCALCE_ERR_FORMAT, m, 0, 0, "(ERROR) core %d does not fit the reads", core); return -1; }
+        if (cl > (int)sizeof x.bk.core || cl > x.L) { failure(f, SCALCE_ERR_FORMAT, m, ST_READ, 0, "(ERROR) core %d does not fit the reads", core); return -1; }
         x.bk.core_len = (u32)cl;
         memcpy(x.bk.core, cs, (size_t)cl);
       }
@@ -219,11 +242,11 @@ struct Walk {
   // ---- which stream says how many records there are ---------------------------------------------------------------------
   // Where no symbol count says how many records the archive holds (`known`), the streams that end it for a whole run -- the
   // names, else the raw quality rows, else the read stream, of the pass's first mate -- end it in front of a range too: a
-  // range that begins behind them is empty.  A short read on the stream that decides (0 r, 1 n, 2 q) ends the archive and is
-  // no error; any other stream (3 l never decides) that ends in front of the range, or inside a window, is truncated.
+  // range that begins behind them is empty.  A short read on the stream that decides (r, n or q) ends the archive and is
+  // no error; any other stream (l never decides) that ends in front of the range, or inside a window, is truncated.
   bool decides_count(int m, int stream) const {
-    if (known || m != m0 || stream > 2) return false;
-    return stream == 1 || (!names && (stream == 2 || !(qual && M[m]->no_ac)));
+    if (known || m != m0 || stream > ST_QUALITY) return false;
+    return stream == ST_NAME || (!names && (stream == ST_QUALITY || !(qual && M[m]->no_ac)));
   }
   // ... applied: a stream gave `got` whole records of the n asked for -- n shrinks, or the stream is truncated
   int ended_at(int m, int stream, u64 got, u64 &n, Failure &f) const {
@@ -256,9 +279,9 @@ struct Walk {
     if (m != 0) {  // bare records in mate 1's order
       const u64 rb = (u64)(x.L + 3) / 4;
       const u64 bytes = to ? x.r.read_into(to->slice, n * rb) : x.r.pass(n * rb);
-      if (x.r.bad) return read_error(f, m, 0);
+      if (x.r.bad) return read_error(f, m, ST_READ);
       got = bytes / rb;
-      if (bytes % rb) return truncated(f, m, 0);
+      if (bytes % rb) return truncated(f, m, ST_READ);
       if (to) {
         memset(&to->dir[0], 0, sizeof to->dir[0]);
         to->dir[0].rec_bytes = (u32)rb;
@@ -275,11 +298,11 @@ struct Walk {
       }
       const u64 t = std::min(x.bk.left, n - got), bytes = t * x.bk.rec_bytes;
       if (!to) {
-        if (x.r.pass(bytes) != bytes) return short_stream(f, m, 0, x.r);
+        if (x.r.pass(bytes) != bytes) return short_stream(f, m, ST_READ, x.r);
       } else {
         if (to->ndir == to->cap_dir || to->bytes + bytes > to->cap_slice)
-          return failure(f, SCALCE_ERR_FORMAT, m, 0, 0, "(ERROR) the read stream opens more buckets than the core table has cores");
-        if (x.r.read_into(to->slice + to->bytes, bytes) != bytes) return short_stream(f, m, 0, x.r);
+          return failure(f, SCALCE_ERR_FORMAT, m, ST_READ, 0, "(ERROR) the read stream opens more buckets than the core table has cores");
+        if (x.r.read_into(to->slice + to->bytes, bytes) != bytes) return short_stream(f, m, ST_READ, x.r);
         scalce_fq_bucket &b = to->dir[to->ndir++];
         memset(&b, 0, sizeof b);
         b.first = got; b.off = to->bytes; b.core_len = x.bk.core_len; b.rec_bytes = x.bk.rec_bytes;
@@ -297,98 +320,44 @@ struct Walk {
     got = bytes / width;
     return bytes % width ? truncated(f, m, stream) : SCALCE_OK;
   }
-  int quality_rows(int m, u64 n, u8 *to, u64 &got, Failure &f) { return rows(m, 2, M[m]->q, (u64)M[m]->L, n, to, got, f); }
-  int lengths(int m, u64 n, u8 *to, u64 &got, Failure &f) { return rows(m, 3, M[m]->l, (u64)M[m]->l_width, n, to, got, f); }
+  int quality_rows(int m, u64 n, u8 *to, u64 &got, Failure &f) { return rows(m, ST_QUALITY, M[m]->q, (u64)M[m]->L, n, to, got, f); }
+  int lengths(int m, u64 n, u8 *to, u64 &got, Failure &f) { return rows(m, ST_LENGTH, M[m]->l, (u64)M[m]->l_width, n, to, got, f); }
   // names in front of a range: a length byte per name has to be read, so they go through the look-ahead buffer, not through skip
   int pass_names(int m, u64 n, u64 &got, Failure &f) {
     Src &src = M[m]->n;
     for (got = 0; got < n && src.need(1); got++) {
       const size_t len = src.ptr()[0];
-      if (!src.need(1 + len)) return short_stream(f, m, 1, src);
+      if (!src.need(1 + len)) return short_stream(f, m, ST_NAME, src);
       src.skip(1 + len);
     }
-    return src.bad ? read_error(f, m, 1) : SCALCE_OK;
+    return src.bad ? read_error(f, m, ST_NAME) : SCALCE_OK;
   }
-  // ---- the comment stream (commentstream.hpp): a fifth cursor of the mate ----------------------------------------------------
-  int comments_open(int m, scalce_read_fn rd, void *user, double *wait, Failure &f) {
-    ArcMate &x = *M[m];
-    x.c.open(rd, nullptr, user, wait, &x.c_delivered, &x.c_skipped);
-    const bool whole = x.c.need(COMMENT_HEADER_BYTES);
-    if (x.c.bad) return read_error(f, m, 5);
-    if (const char *why = comment_header_read(x.c.ptr(), whole ? COMMENT_HEADER_BYTES : 0, &x.c_longest, &x.c_total))
-      return failure(f, SCALCE_ERR_FORMAT, m, 5, 0, "(ERROR) %s", why);
-    x.c.skip(COMMENT_HEADER_BYTES);
-    x.has_com = true;
-    x.c_taken = 0;
+  // ---- the text-entry streams (commentstream.hpp, plusstream.hpp): a fifth and a sixth cursor of the mate, walked alike ----
+  int text_open(int m, TextStream &t, scalce_read_fn rd, void *user, double *wait, Failure &f) {
+    const int id = t.kind->stream;
+    t.src.open(rd, nullptr, user, wait, &t.delivered, &t.skipped);
+    const bool whole = t.src.need(COMMENT_HEADER_BYTES);
+    if (t.src.bad) return read_error(f, m, id);
+    if (const char *why = t.kind->header_read(t.src.ptr(), whole ? COMMENT_HEADER_BYTES : 0, &t.longest, &t.total))
+      return failure(f, SCALCE_ERR_FORMAT, m, id, 0, "(ERROR) %s", why);
+    t.src.skip(COMMENT_HEADER_BYTES);
+    t.open = true;
+    t.taken = 0;
     return SCALCE_OK;
   }
-  // the next entry where it lies in the look-ahead buffer: len = its bytes with the newline.  0: there it is; 1: the stream
-  // ends here, between two entries; else the failure -- it ends inside an entry, an entry outgrows the header's C, a read failed
-  int next_comment(int m, size_t &len, Failure &f) {
-    ArcMate &x = *M[m];
-    Src &c = x.c;
-    size_t seen = 0;
-    for (;;) {
-      const size_t have = c.avail();
-      if (have > seen) {
-        const void *nl = memchr(c.ptr() + seen, '\n', have - seen);
-        if (nl) {
-          len = (size_t)((const u8 *)nl - c.ptr()) + 1;
-          if (len - 1 > x.c_longest) return failure(f, SCALCE_ERR_FORMAT, m, 5, 0, "(ERROR) %s", comment_entry_too_long());
-          return 0;
-        }
-        seen = have;
-      }
-      if (seen > x.c_longest) return failure(f, SCALCE_ERR_FORMAT, m, 5, 0, "(ERROR) %s", comment_entry_too_long());
-      if (!c.need(seen + 1)) {
-        if (c.bad) return read_error(f, m, 5);
-        return seen ? truncated(f, m, 5) : 1;
-      }
-    }
-  }
-  // entries in front of a range: passed over on the host by their newlines (the stream is always read, as the names are)
-  int pass_comments(int m, u64 n, u64 &got, Failure &f) {
-    for (got = 0; got < n; got++) {
-      size_t len = 0;
-      const int e = next_comment(m, len, f);
-      if (e == 1) break;
-      if (e) return e;
-      M[m]->c.skip(len);
-      M[m]->c_taken++;
-    }
-    return SCALCE_OK;
-  }
-  int comment_count(int m, u64 entries, u64 records, Failure &f) const {
-    char b[200];
-    comment_count_message(b, sizeof b, entries, records);
-    return failure(f, SCALCE_ERR_FORMAT, m, 5, 0, "(ERROR) %s", b);
-  }
-
-  // ---- the plus-line stream (plusstream.hpp): a sixth cursor of the mate, walked like the comment stream ---------------------
-  int plus_open(int m, scalce_read_fn rd, void *user, double *wait, Failure &f) {
-    ArcMate &x = *M[m];
-    x.p.open(rd, nullptr, user, wait, &x.p_delivered, &x.p_skipped);
-    const bool whole = x.p.need(PLUS_HEADER_BYTES);
-    if (x.p.bad) return read_error(f, m, 7);
-    if (const char *why = plus_header_read(x.p.ptr(), whole ? PLUS_HEADER_BYTES : 0, &x.p_longest, &x.p_total))
-      return failure(f, SCALCE_ERR_FORMAT, m, 7, 0, "(ERROR) %s", why);
-    x.p.skip(PLUS_HEADER_BYTES);
-    x.has_plus = true;
-    x.p_taken = 0;
-    return SCALCE_OK;
-  }
-  // the next entry where it lies in the look-ahead buffer: at = its bytes, len = how many with the newline, cls = what it is.
-  // 0: there it is; 1: the stream ends here, between two entries; else the failure.  A stream with P = 0 holds no entries:
-  // every record's is the empty one.
-  int next_plus(int m, const u8 *&at, size_t &len, PlusClass &cls, Failure &f) {
+  // the next entry where it lies in the look-ahead buffer: at = its bytes, len = how many with the newline.  0: there it is; 1:
+  // the stream ends here, between two entries; else the failure -- it ends inside an entry, an entry outgrows the header's
+  // longest or is none of its kind, a read failed.  A stream that is its header alone holds no entries: every record's is the
+  // empty one.
+  int next_text(int m, TextStream &t, const u8 *&at, size_t &len, Failure &f) {
     static const u8 bare[1] = {'\n'};
-    ArcMate &x = *M[m];
-    if (!x.p_longest) {
-      if (x.p_taken >= x.p_total) return 1;
-      at = bare; len = 1; cls = PLUS_BARE;
+    const int id = t.kind->stream;
+    if (t.no_entries()) {
+      if (t.taken >= t.total) return 1;
+      at = bare; len = 1;
       return 0;
     }
-    Src &c = x.p;
+    Src &c = t.src;
     size_t seen = 0;
     for (;;) {
       const size_t have = c.avail();
@@ -396,43 +365,47 @@ struct Walk {
         const void *nl = memchr(c.ptr() + seen, '\n', have - seen);
         if (nl) {
           len = (size_t)((const u8 *)nl - c.ptr()) + 1;
-          if (len - 1 > x.p_longest) return failure(f, SCALCE_ERR_FORMAT, m, 7, 0, "(ERROR) %s", plus_entry_too_long());
+          if (len - 1 > t.longest) return failure(f, SCALCE_ERR_FORMAT, m, id, 0, "(ERROR) %s", t.kind->entry_too_long());
           at = c.ptr();
-          cls = plus_class(at, len - 1);
-          if (cls == PLUS_MALFORMED) return failure(f, SCALCE_ERR_FORMAT, m, 7, 0, "(ERROR) %s", plus_malformed());
+          if (const char *why = t.kind->wrong(at, len - 1)) return failure(f, SCALCE_ERR_FORMAT, m, id, 0, "(ERROR) %s", why);
           return 0;
         }
         seen = have;
       }
-      if (seen > x.p_longest) return failure(f, SCALCE_ERR_FORMAT, m, 7, 0, "(ERROR) %s", plus_entry_too_long());
+      if (seen > t.longest) return failure(f, SCALCE_ERR_FORMAT, m, id, 0, "(ERROR) %s", t.kind->entry_too_long());
       if (!c.need(seen + 1)) {
-        if (c.bad) return read_error(f, m, 7);
-        return seen ? truncated(f, m, 7) : 1;
+        if (c.bad) return read_error(f, m, id);
+        return seen ? truncated(f, m, id) : 1;
       }
     }
   }
-  void plus_taken(int m, size_t len) {
-    ArcMate &x = *M[m];
-    if (x.p_longest) x.p.skip(len);
-    x.p_taken++;
+  void text_taken(TextStream &t, size_t len) {
+    if (!t.no_entries()) t.src.skip(len);
+    t.taken++;
   }
-  // entries in front of a range: passed over on the host by their newlines; none behind the range is read
-  int pass_plus(int m, u64 n, u64 &got, Failure &f) {
+  // entries in front of a range: passed over on the host by their newlines (a stream that holds entries is always read, as
+  // the names are); none behind the range is read
+  int pass_text(int m, TextStream &t, u64 n, u64 &got, Failure &f) {
     for (got = 0; got < n; got++) {
       const u8 *at;
       size_t len = 0;
-      PlusClass cls;
-      const int e = next_plus(m, at, len, cls, f);
+      const int e = next_text(m, t, at, len, f);
       if (e == 1) break;
       if (e) return e;
-      plus_taken(m, len);
+      text_taken(t, len);
     }
     return SCALCE_OK;
   }
-  int plus_count(int m, u64 entries, u64 records, Failure &f) const {
+  int text_count(int m, const TextStream &t, u64 entries, u64 records, Failure &f) const {
     char b[200];
-    plus_count_message(b, sizeof b, entries, records);
-    return failure(f, SCALCE_ERR_FORMAT, m, 7, 0, "(ERROR) %s", b);
+    t.kind->count_message(b, sizeof b, entries, records);
+    return failure(f, SCALCE_ERR_FORMAT, m, t.kind->stream, 0, "(ERROR) %s", b);
+  }
+  // the plus-line stream's next entry with its class
+  int next_plus(int m, const u8 *&at, size_t &len, PlusClass &cls, Failure &f) {
+    const int e = next_text(m, M[m]->plus, at, len, f);
+    if (!e) cls = plus_class(at, len - 1);
+    return e;
   }
   // One record's (pair's) entries into `to`, if they and what they add fit: header[i] = the bytes of mate i's header line behind
   // its '@' as this run writes it, which is what a repeat adds.  grow = what the entries add to the text.  0: peeked (nothing is
@@ -442,7 +415,7 @@ struct Walk {
     k.grow = 0;
     for (int i = 0; i <= m1 - m0; i++) {
       const int e = next_plus(m0 + i, k.at[i], k.len[i], k.cls[i], f);
-      if (e == 1 && i) return truncated(f, m0 + i, 7);
+      if (e == 1 && i) return truncated(f, m0 + i, ST_PLUS);
       if (e) return e;
       k.grow += plus_growth(k.cls[i], k.len[i] - 1, header[i]);
     }
@@ -453,7 +426,7 @@ struct Walk {
     for (int i = 0; i <= m1 - m0; i++) {
       memcpy(to.bytes + to.nbytes, k.at[i], k.len[i]);
       to.nbytes += k.len[i];
-      plus_taken(m0 + i, k.len[i]);
+      text_taken(M[m0 + i]->plus, k.len[i]);
     }
     to.grow += k.grow;
   }
@@ -475,25 +448,26 @@ struct Walk {
         Src &src = M[m0 + i]->n;
         if (!src.need(1)) { ended++; continue; }
         len[i] = src.ptr()[0];
-        if (!src.need(1 + (size_t)len[i])) return truncated(f, m0 + i, 1);
+        if (!src.need(1 + (size_t)len[i])) return truncated(f, m0 + i, ST_NAME);
         rec += len[i] + rec_budget(m0 + i);
       }
+      const u8 *cat[2] = {nullptr, nullptr};
       size_t clen[2] = {0, 0};  // the records' entries with their newlines
       for (int i = 0; i < nmates && com && !ended; i++) {
-        const int e = next_comment(m0 + i, clen[i], f);
-        if (e == 1) return truncated(f, m0 + i, 5);
+        const int e = next_text(m0 + i, M[m0 + i]->com, cat[i], clen[i], f);
+        if (e == 1) return truncated(f, m0 + i, ST_COMMENT);
         if (e) return e;
         rec += clen[i] - 1;
       }
       PlusPeek pk;
       if (plus && !ended) {
         const u64 header[2] = {len[0] + (clen[0] ? clen[0] - 1 : 0), len[1] + (clen[1] ? clen[1] - 1 : 0)};
-        if (const int e = plus_peek(header, pk, f)) return e == 1 ? truncated(f, m0, 7) : e;
+        if (const int e = plus_peek(header, pk, f)) return e == 1 ? truncated(f, m0, ST_PLUS) : e;
         rec += pk.grow;
       }
       if (ended) {
-        for (int i = 0; i < nmates; i++) if (M[m0 + i]->n.bad) return read_error(f, m0 + i, 1);
-        if (!decides_count(m0, 1) || ended != nmates) return truncated(f, m0, 1);
+        for (int i = 0; i < nmates; i++) if (M[m0 + i]->n.bad) return read_error(f, m0 + i, ST_NAME);
+        if (!decides_count(m0, ST_NAME) || ended != nmates) return truncated(f, m0, ST_NAME);
         break;
       }
       if (n && text + rec > W) break;
@@ -504,9 +478,8 @@ struct Walk {
       if (!fits) break;
       if (plus) plus_commit(*plus, pk);
       for (int i = 0; i < nmates && com; i++) {
-        memcpy(com->bytes + com->nbytes, M[m0 + i]->c.ptr(), clen[i]);
-        M[m0 + i]->c.skip(clen[i]);
-        M[m0 + i]->c_taken++;
+        memcpy(com->bytes + com->nbytes, cat[i], clen[i]);
+        text_taken(M[m0 + i]->com, clen[i]);
         com->nbytes += clen[i];
       }
       for (int i = 0; i < nmates; i++) {
@@ -527,7 +500,7 @@ struct Walk {
     Src &q = M[m]->q;
     for (u64 k = 0; k < frames; k++) {
       u32 sz = 0;
-      if (!q.get(sz, q.skp ? 0 : ~(size_t)0) || q.pass(sz) != sz) return short_stream(f, m, 2, q);
+      if (!q.get(sz, q.skp ? 0 : ~(size_t)0) || q.pass(sz) != sz) return short_stream(f, m, ST_QUALITY, q);
     }
     return SCALCE_OK;
   }
@@ -545,7 +518,7 @@ struct Walk {
     return SCALCE_OK;
   }
   int holds_more(int m, Failure &f) const {
-    return failure(f, SCALCE_ERR_FORMAT, m, 0, 0, "(ERROR) the read stream holds more than the %llu records of the %s stream",
+    return failure(f, SCALCE_ERR_FORMAT, m, ST_READ, 0, "(ERROR) the read stream holds more than the %llu records of the %s stream",
                    (unsigned long long)M[m]->first, names ? "name" : "quality");
   }
 };

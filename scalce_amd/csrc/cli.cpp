@@ -25,16 +25,12 @@
 
 #include "../../include/scalce_hip.h"
 #include "hip_own.hpp"
-#include "lenstream.hpp"
-#include "orderstream.hpp"
 #include "digeststream.hpp"
 #include "cli_io.hpp"
 #include "cli_input.hpp"
 #include "cli_shares.hpp"
 #include "cli_sink.hpp"
-#include "cli_comments.hpp"
-#include "cli_plus.hpp"
-#include "cli_exceptions.hpp"
+#include "cli_sidefiles.hpp"
 
 #ifndef SCALCE_VERSION
 #define SCALCE_VERSION "2.8-mi355x"
@@ -163,7 +159,6 @@ static const char *HELP_TEXT =
 //                       two-line records), int64 T, then T x {u64 bytes, u32 crc32, u32 0}: each input text's size and zlib CRC-32
 //   PREFIX_<m>.scalceq  magic, int64 Phred offset (mate 1's for both mates, compress.cpp:294,816-817); arithmetic coded:
 //                       the scaled table (QTABLE_WORDS x u32), the int64 symbol count and the coded blocks; -A: the q' rows
-static const uint8_t MAGIC[8] = {'s', 'c', 'a', 'l', 'c', 'e', '2', '2'};
 static constexpr size_t QTABLE_WORDS = 512000;
 static std::string archive_path(const std::string &out, int m, char ext) { return out + "_" + std::to_string(m + 1) + ".scalce" + ext; }
 // fn(extension, path) on every mate's files with the extensions `exts` ("rnq": .scalcer, .scalcen, .scalceq)
@@ -174,7 +169,7 @@ template <class Fn> static void for_each_archive_file(const Options &o, const ch
 // -c gz holds every file in a gzip container but an arithmetic-coded .scalceq (compress.cpp:249)
 static bool gz_container(const Options &o, char ext) { return o.container == 1 && (ext != 'q' || o.no_ac); }
 static std::vector<uint8_t> with_magic(const void *fields, size_t n) {
-  std::vector<uint8_t> h(MAGIC, MAGIC + 8);
+  std::vector<uint8_t> h(scalce_host::ARCHIVE_MAGIC, scalce_host::ARCHIVE_MAGIC + 8);
   h.insert(h.end(), static_cast<const uint8_t *>(fields), static_cast<const uint8_t *>(fields) + n);
   return h;
 }
@@ -369,9 +364,7 @@ struct MateFiles {
   void write_lengths(int m) const {  // --variable-length: how long each record really was, in archive order
     OutFile fL;
     fL.open(archive_path(o.out, m, 'l'), gz_container(o, 'l'));
-    uint8_t head[scalce_host::LEN_HEADER_BYTES];
-    scalce_host::len_header_write(head, p.read_len[m]);
-    fL.write(head, sizeof head);
+    side_file_header<scalce_host::LEN_HEADER_BYTES>(fL, scalce_host::len_header_write, p.read_len[m]);
     const std::vector<uint8_t> pad = fetch(ctx, b, SCALCE_OUT_LENGTHS, m);
     const int width = scalce_host::len_entry_width(p.read_len[m]);
     std::vector<uint8_t> entries(pad.size() / 2 * (size_t)width);
@@ -383,9 +376,7 @@ struct MateFiles {
     OutFile fO;
     fO.open(archive_path(o.out, 0, 'o'), gz_container(o, 'o'));
     const std::vector<uint8_t> perm = fetch(ctx, b, SCALCE_OUT_PERM, 0);
-    uint8_t head[scalce_host::ORDER_HEADER_BYTES];
-    scalce_host::order_header_write(head, perm.size() / 4);
-    fO.write(head, sizeof head);
+    side_file_header<scalce_host::ORDER_HEADER_BYTES>(fO, scalce_host::order_header_write, perm.size() / 4);
     fO.write(perm);
     fO.close();
   }
@@ -395,7 +386,7 @@ struct MateFiles {
     uint64_t nbytes = 0;
     uint32_t longest = 0;
     SCOK(ctx, scalce_batch_comments_info(b, m, &nbytes, &longest));
-    comment_file_header(fC, longest, N);
+    side_file_header<scalce_host::COMMENT_HEADER_BYTES>(fC, scalce_host::comment_header_write, longest, N);
     down.to_file(ctx, b, SCALCE_OUT_COMMENTS, m, fC);
     fC.close();
   }
@@ -404,7 +395,7 @@ struct MateFiles {
     fP.open(archive_path(o.out, m, 'p'), gz_container(o, 'p'));
     uint32_t longest = 0;
     SCOK(ctx, scalce_batch_plus_info(b, m, nullptr, &longest, nullptr, nullptr));
-    plus_file_header(fP, longest, N);
+    side_file_header<scalce_host::PLUS_HEADER_BYTES>(fP, scalce_host::plus_header_write, longest, N);
     if (longest) down.to_file(ctx, b, SCALCE_OUT_PLUS, m, fP);  // (P = 0: every line was bare, the file is its header)
     fP.close();
   }
@@ -413,7 +404,7 @@ struct MateFiles {
     fX.open(archive_path(o.out, m, 'x'), gz_container(o, 'x'));
     uint64_t entries = 0;
     SCOK(ctx, scalce_batch_exceptions_info(b, m, &entries, nullptr));
-    exception_file_header(fX, (uint32_t)p.read_len[m], N, entries);
+    side_file_header<scalce_host::EXCEPTION_HEADER_BYTES>(fX, scalce_host::exception_header_write, (uint32_t)p.read_len[m], N, entries);
     down.to_file(ctx, b, SCALCE_OUT_EXCEPTIONS, m, fX);
     fX.close();
   }
@@ -983,15 +974,15 @@ struct Archive {
     for (int m = 0; m < (o.interleave ? 1 : nm) && has_order; m++) order[m].open(scalce_name(base[0], 'o'));
     // what follows the names: put back when every mate has its stream, names are printed and nothing sets the streams aside
     has_comments = !o.no_comments && o.use_names;
-    for (int m = 0; m < nm && has_comments; m++) has_comments = comment_file_present(scalce_name(base[m], 'c'));
+    for (int m = 0; m < nm && has_comments; m++) has_comments = side_file_present(scalce_name(base[m], 'c'));
     for (int m = 0; m < nm && has_comments; m++) comments[m].open(scalce_name(base[m], 'c'));
     // what the archive does not keep of the bases: put back when every mate has its stream
     has_exceptions = !o.stored_bases;
-    for (int m = 0; m < nm && has_exceptions; m++) has_exceptions = exception_file_present(scalce_name(base[m], 'x'));
+    for (int m = 0; m < nm && has_exceptions; m++) has_exceptions = side_file_present(scalce_name(base[m], 'x'));
     for (int m = 0; m < nm && has_exceptions; m++) exceptions[m].open(scalce_name(base[m], 'x'));
     // the '+' lines: put back when every mate has its stream and the records that go out have such a line
     has_plus = !o.bare_plus && !o.no_qual && !o.fasta;
-    for (int m = 0; m < nm && has_plus; m++) has_plus = plus_file_present(scalce_name(base[m], 'p'));
+    for (int m = 0; m < nm && has_plus; m++) has_plus = side_file_present(scalce_name(base[m], 'p'));
     for (int m = 0; m < nm && has_plus; m++) plus[m].open(scalce_name(base[m], 'p'));
   }
 };

@@ -1,5 +1,5 @@
 // digeststream.hpp -- the digest stream of an archive made with --lossless --digest (PREFIX_1.scalced), host side only: no
-// device call, no HIP header.  Layout: the 8 magic bytes, int32 16 (entry width), int32 kind, int64 T (texts: 1 or 2), then T
+// device call, no HIP header.  Layout (sidestream.hpp): the 8 magic bytes, int32 16 (entry width), int32 kind, int64 T (texts: 1 or 2), then T
 // entries of {u64 bytes, u32 crc32, u32 0}, little-endian.  kind: 0 one text, 1 paired files (-r), 2 interleaved (-i); + 4 for
 // two-line records (-f).  The CRC-32 is zlib's (polynomial 0xEDB88320 reflected, initial value and final xor 0xFFFFFFFF) of the
 // text of one mate stream as the run read it.  The writer and the reader (cli.cpp) share it, and with the device kernel
@@ -9,6 +9,8 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+
+#include "sidestream.hpp"
 
 #ifdef __HIPCC__
 #define SCALCE_CRC_HD __host__ __device__
@@ -60,10 +62,9 @@ inline uint32_t crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b) {
 }
 
 // ---- the stream
-constexpr size_t DIGEST_HEADER_BYTES = 24;
+constexpr size_t DIGEST_HEADER_BYTES = side_header_bytes(1);
 constexpr int DIGEST_ENTRY_WIDTH = 16;
 constexpr int DIGEST_KIND_SINGLE = 0, DIGEST_KIND_PAIRED = 1, DIGEST_KIND_INTERLEAVED = 2, DIGEST_KIND_FASTA = 4;
-static const uint8_t DIGEST_MAGIC[8] = {'s', 'c', 'a', 'l', 'c', 'e', '2', '2'};
 
 struct DigestText { uint64_t bytes = 0; uint32_t crc = 0; };
 struct Digest {
@@ -75,11 +76,7 @@ constexpr size_t DIGEST_MAX_BYTES = DIGEST_HEADER_BYTES + 2 * DIGEST_ENTRY_WIDTH
 
 // the whole stream into out (DIGEST_MAX_BYTES of room); returns its size
 inline size_t digest_write(uint8_t *out, const Digest &d) {
-  const int32_t f[2] = {DIGEST_ENTRY_WIDTH, (int32_t)d.kind};
-  const int64_t t = d.texts;
-  memcpy(out, DIGEST_MAGIC, 8);
-  memcpy(out + 8, f, 8);
-  memcpy(out + 16, &t, 8);
+  side_header_write(out, 1, SideHeader{DIGEST_ENTRY_WIDTH, (int32_t)d.kind, {d.texts}});
   for (int i = 0; i < d.texts; i++) {
     uint8_t *e = out + DIGEST_HEADER_BYTES + (size_t)i * DIGEST_ENTRY_WIDTH;
     const uint32_t w[2] = {d.text[i].crc, 0};
@@ -90,17 +87,15 @@ inline size_t digest_write(uint8_t *out, const Digest &d) {
 }
 // nullptr: a stream this build reads (*d filled in); else what is wrong with it.  `have` = every byte of the stream.
 inline const char *digest_read(const uint8_t *h, size_t have, Digest *d) {
-  if (have < DIGEST_HEADER_BYTES) return "truncated digest stream";
-  if (memcmp(h, DIGEST_MAGIC, 7)) return "is not a scalce digest stream";
-  int32_t f[2];
-  memcpy(f, h + 8, 8);
-  if (f[0] != DIGEST_ENTRY_WIDTH || f[1] < 0 || f[1] > 7 || (f[1] & 3) == 3) return "is not a scalce digest stream";
-  int64_t t;
-  memcpy(&t, h + 16, 8);
-  if (t != 1 && t != 2) return "is not a scalce digest stream";
+  SideHeader f;
+  const SideHeaderState st = side_header_read(h, have, 1, &f);
+  if (st == SIDE_SHORT) return "truncated digest stream";
+  const int64_t t = f.count[0];
+  if (st == SIDE_NOT_OURS || f.width != DIGEST_ENTRY_WIDTH || f.param < 0 || f.param > 7 || (f.param & 3) == 3 || (t != 1 && t != 2))
+    return "is not a scalce digest stream";
   if (have < DIGEST_HEADER_BYTES + (size_t)t * DIGEST_ENTRY_WIDTH) return "truncated digest stream";
   if (have > DIGEST_HEADER_BYTES + (size_t)t * DIGEST_ENTRY_WIDTH) return "is not a scalce digest stream";
-  d->kind = f[1];
+  d->kind = f.param;
   d->texts = (int)t;
   for (int i = 0; i < d->texts; i++) {
     const uint8_t *e = h + DIGEST_HEADER_BYTES + (size_t)i * DIGEST_ENTRY_WIDTH;

@@ -1,5 +1,5 @@
 // exceptionstream.hpp -- the exception stream of an archive made with --keep-bases (PREFIX_<m>.scalcex), host side only: no
-// device call, no HIP header.  Layout: the 8 magic bytes, int32 8 (entry width), int32 L, int64 N (records), int64 X (entries),
+// device call, no HIP header.  Layout (sidestream.hpp): the 8 magic bytes, int32 8 (entry width), int32 L, int64 N (records), int64 X (entries),
 // then X little-endian u64, strictly ascending by record and position (one entry per place): bits 0-7 the letter, 8-15 the quality character, 16-27 the position,
 // 28-63 the record's index in archive order.  Header write and read with the text of every failure, and a cursor that hands
 // out the entries of records [r0, r1) over a read callback: it passes over the entries in front of r0 and takes none behind
@@ -11,13 +11,14 @@
 #include <cstring>
 #include <vector>
 
+#include "sidestream.hpp"
+
 namespace scalce_host {
 
-constexpr size_t EXCEPTION_HEADER_BYTES = 32;
+constexpr size_t EXCEPTION_HEADER_BYTES = side_header_bytes(2);
 constexpr int EXCEPTION_ENTRY_WIDTH = 8;
 constexpr int EXCEPTION_POS_BITS = 12, EXCEPTION_REC_SHIFT = 28;
 constexpr uint64_t EXCEPTION_MAX_RECORDS = 1ull << 36;
-static const uint8_t EXCEPTION_MAGIC[8] = {'s', 'c', 'a', 'l', 'c', 'e', '2', '2'};
 
 inline uint64_t exception_entry(uint64_t record, uint32_t pos, uint8_t letter, uint8_t quality) {
   return (uint64_t)letter | (uint64_t)quality << 8 | (uint64_t)pos << 16 | record << EXCEPTION_REC_SHIFT;
@@ -26,11 +27,7 @@ inline uint64_t exception_record(uint64_t e) { return e >> EXCEPTION_REC_SHIFT; 
 inline uint32_t exception_pos(uint64_t e) { return (uint32_t)(e >> 16) & ((1u << EXCEPTION_POS_BITS) - 1u); }
 
 inline void exception_header_write(uint8_t out[EXCEPTION_HEADER_BYTES], uint32_t read_len, uint64_t records, uint64_t entries) {
-  const int32_t f[2] = {EXCEPTION_ENTRY_WIDTH, (int32_t)read_len};
-  memcpy(out, EXCEPTION_MAGIC, 8);
-  memcpy(out + 8, f, 8);
-  memcpy(out + 16, &records, 8);
-  memcpy(out + 24, &entries, 8);
+  side_header_write(out, 2, SideHeader{EXCEPTION_ENTRY_WIDTH, (int32_t)read_len, {(int64_t)records, (int64_t)entries}});
 }
 inline const char *exception_truncated() { return "truncated exception stream"; }
 inline const char *exception_not_a_stream() { return "is not a scalce exception stream"; }
@@ -45,16 +42,13 @@ inline int exception_length_message(char *out, size_t cap, uint32_t read_len, ui
 }
 // nullptr: a header this build reads (*read_len, *records, *entries filled in); else what is wrong with it
 inline const char *exception_header_read(const uint8_t *h, size_t have, uint32_t *read_len, uint64_t *records, uint64_t *entries) {
-  if (have < EXCEPTION_HEADER_BYTES) return exception_truncated();
-  if (memcmp(h, EXCEPTION_MAGIC, 7)) return exception_not_a_stream();
-  int32_t f[2];
-  memcpy(f, h + 8, 8);
-  if (f[0] != EXCEPTION_ENTRY_WIDTH || f[1] <= 0 || f[1] >= (1 << EXCEPTION_POS_BITS)) return exception_not_a_stream();
-  int64_t n, x;
-  memcpy(&n, h + 16, 8);
-  memcpy(&x, h + 24, 8);
+  SideHeader f;
+  const SideHeaderState st = side_header_read(h, have, 2, &f);
+  if (st == SIDE_SHORT) return exception_truncated();
+  if (st == SIDE_NOT_OURS || f.width != EXCEPTION_ENTRY_WIDTH || f.param <= 0 || f.param >= (1 << EXCEPTION_POS_BITS)) return exception_not_a_stream();
+  const int64_t n = f.count[0], x = f.count[1];
   if (n < 0 || (uint64_t)n >= EXCEPTION_MAX_RECORDS || x < 0) return exception_not_a_stream();
-  *read_len = (uint32_t)f[1];
+  *read_len = (uint32_t)f.param;
   *records = (uint64_t)n;
   *entries = (uint64_t)x;
   return nullptr;

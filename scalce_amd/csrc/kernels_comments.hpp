@@ -13,6 +13,24 @@ constexpr u32 COM_MAX = 65535;            // the longest entry kept (its length 
 constexpr u32 COM_CHUNKS = 16;            // destination bytes per thread of comment_copy_k
 constexpr u32 COM_SPAN = 256u * COM_CHUNKS;
 
+// where the first byte of text[i, end) that equals `four`'s (one byte, four times over) lies, searched four bytes at a time;
+// at or behind `end`: there is none.  Bytes behind `nbytes` read as 0.
+__device__ __forceinline__ u64 find_byte(const u8 *text, u64 i, u64 end, u64 nbytes, u32 four) {
+  for (; i < end; i += 4) {
+    const u32 z = zero_bytes(load_u32_unaligned(text, i, nbytes) ^ four);
+    if (z) { i += (u32)(__ffs((int)z) - 1) >> 3; break; }
+  }
+  return i;
+}
+// where entry r of a window's newline-terminated entries begins and how long it is, from where each entry's newline lies; an
+// index that does not fit the entries (the caller's *d_bad says so) gives an empty one
+__device__ __forceinline__ void window_entry(const u64 *ent_end, u64 entry_bytes, u64 r, u64 *es, u64 *E) {
+  const u64 s = r ? ent_end[r - 1] + 1 : 0, e = ent_end[r];
+  const bool ok = s <= e && e < entry_bytes;
+  *es = ok ? s : 0;
+  *E = ok ? e - s : 0;
+}
+
 struct CommentArgs {
   const u8 *text;       // the piece
   u64 nbytes;
@@ -49,11 +67,7 @@ __global__ __launch_bounds__(256) void comment_plan_k(CommentArgs a) {
       if (a.namelen) {
         len = body >= a.namelen[r] ? body - a.namelen[r] : 0;
       } else {
-        u64 i = ns + 1;
-        for (; i < p0; i += 4) {
-          const u32 z = zero_bytes(load_u32_unaligned(a.text, i, a.nbytes) ^ 0x20202020u);
-          if (z) { i += (u32)(__ffs((int)z) - 1) >> 3; break; }
-        }
+        const u64 i = find_byte(a.text, ns + 1, p0, a.nbytes, 0x20202020u);
         len = i < p0 ? p0 - i : 0;
       }
     }
@@ -109,18 +123,11 @@ struct InsertArgs {
   u64 *dst_off;          // nrec + 1: the same for the text with the entries put in
   u8 *dst;
 };
-// where entry r begins and how long it is; an index that does not fit the entries (the caller's *d_bad says so) gives an empty one
-__device__ __forceinline__ void insert_entry(const InsertArgs &a, u64 r, u64 *es, u64 *E) {
-  const u64 s = r ? a.ent_end[r - 1] + 1 : 0, e = a.ent_end[r];
-  const bool ok = s <= e && e < a.entry_bytes;
-  *es = ok ? s : 0;
-  *E = ok ? e - s : 0;
-}
 struct InsertedSize {
   InsertArgs a;
   __device__ u64 operator()(u64 r) const {
     u64 es, E;
-    insert_entry(a, r, &es, &E);
+    window_entry(a.ent_end, a.entry_bytes, r, &es, &E);
     return a.rec_off[r + 1] - a.rec_off[r] + E;
   }
 };
@@ -151,7 +158,7 @@ __global__ __launch_bounds__(256) void insert_copy_k(InsertArgs a) {
       const u64 T = e - s0 < tail ? e - s0 : tail;  // (a record shorter than its tail: never reached in front of it)
       nl = e - T;                // the header line's newline
       A = nl - s0;               // '@' and the name
-      insert_entry(a, rr, &es, &E);  // the entry, without its newline
+      window_entry(a.ent_end, a.entry_bytes, rr, &es, &E);  // the entry, without its newline
       size = A + E + T;
     };
     view(r);

@@ -115,12 +115,6 @@ struct PlusArgs {
   u64 dst_cap;           // room in dst: a text that would outgrow it is not written (*bad)
   u32 *bad;
 };
-__device__ __forceinline__ void plus_entry(const PlusArgs &a, u64 r, u64 *es, u64 *E) {
-  const u64 s = r ? a.ent_end[r - 1] + 1 : 0, e = a.ent_end[r];
-  const bool ok = s <= e && e < a.entry_bytes;
-  *es = ok ? s : 0;
-  *E = ok ? e - s : 0;
-}
 // One thread per record.  The header line's newline is searched forward from the record's start, four bytes at a time; with
 // H bytes of header line the record is H + 2 l + 5 bytes, which says where the '+' lies.  A repeat grows the record by H - 1,
 // a literal by its bytes behind the class byte.  A malformed entry (or a record that is no such text) sets *bad and adds nothing.
@@ -129,14 +123,10 @@ __global__ __launch_bounds__(256) void plus_insert_plan_k(PlusArgs a) {
   if (r >= a.nrec) return;
   const u64 s0 = a.rec_off[r], e = a.rec_off[r + 1], nsrc = a.rec_off[a.nrec];
   const u64 size = e >= s0 ? e - s0 : 0;
-  u64 i = s0;
-  for (; i < e; i += 4) {
-    const u32 z = zero_bytes(load_u32_unaligned(a.text, i, nsrc) ^ 0x0A0A0A0Au);
-    if (z) { i += (u32)(__ffs((int)z) - 1) >> 3; break; }
-  }
+  const u64 i = find_byte(a.text, s0, e, nsrc, 0x0A0A0A0Au);
   const u64 H = i < e ? i - s0 : size;
   u64 es, E;
-  plus_entry(a, r, &es, &E);
+  window_entry(a.ent_end, a.entry_bytes, r, &es, &E);
   u64 grow = 0, at = s0;
   bool bad = false;
   if (H < 1 || size < H + 5 || ((size - H - 5) & 1)) {
@@ -190,7 +180,7 @@ __global__ __launch_bounds__(256) void plus_insert_copy_k(PlusArgs a) {
       ins = a.text; ins_at = s0 + 1; ins_n = nsrc;
       if (G) {
         u64 es, E;
-        plus_entry(a, rr, &es, &E);
+        window_entry(a.ent_end, a.entry_bytes, rr, &es, &E);
         if (a.entries[es] == PLUS_LITERAL) { ins = a.entries; ins_at = es + 1; ins_n = a.entry_bytes; }
       }
     };
@@ -219,11 +209,7 @@ __global__ __launch_bounds__(256) void plus_pair_split_k(u64 npairs, const u8 *t
   rec_off[2 * k] = pair_off[k];
   if (k == npairs) return;
   const u64 s0 = pair_off[k], e = pair_off[k + 1], nsrc = pair_off[npairs];
-  u64 i = s0;
-  for (; i < e; i += 4) {
-    const u32 z = zero_bytes(load_u32_unaligned(text, i, nsrc) ^ 0x0A0A0A0Au);
-    if (z) { i += (u32)(__ffs((int)z) - 1) >> 3; break; }
-  }
+  const u64 i = find_byte(text, s0, e, nsrc, 0x0A0A0A0Au);
   const u64 size1 = (i < e ? i - s0 : 0) + 2 * l1 + 5;
   rec_off[2 * k + 1] = e - s0 < size1 ? s0 : s0 + size1;
 }

@@ -1,5 +1,5 @@
 // orderstream.hpp -- the order stream of an archive made with --keep-order (PREFIX_1.scalceo), host side only: no device call,
-// no HIP header.  Layout: the 8 magic bytes, int32 entry width (4), int32 0, int64 N, then N little-endian u32: entry k is the
+// no HIP header.  Layout (sidestream.hpp): the 8 magic bytes, int32 entry width (4), int32 0, int64 N, then N little-endian u32: entry k is the
 // input index of the k-th record (pair) of the archive.  The writer (cli.cpp) and the reader (stream_decode.cpp) share it, and
 // the table that says where each window's share of each stripe lies in the spill of the restore, with the spill's record word
 // and the spill file itself.
@@ -16,30 +16,25 @@
 #include <string>
 #include <vector>
 
+#include "sidestream.hpp"
+
 namespace scalce_host {
 
-constexpr size_t ORDER_HEADER_BYTES = 24;
+constexpr size_t ORDER_HEADER_BYTES = side_header_bytes(1);
 constexpr int ORDER_ENTRY_WIDTH = 4;
 constexpr uint64_t ORDER_MAX_STRIPES = 65536;
-static const uint8_t ORDER_MAGIC[8] = {'s', 'c', 'a', 'l', 'c', 'e', '2', '2'};
 
 inline void order_header_write(uint8_t out[ORDER_HEADER_BYTES], uint64_t n) {
-  const int32_t f[2] = {ORDER_ENTRY_WIDTH, 0};
-  memcpy(out, ORDER_MAGIC, 8);
-  memcpy(out + 8, f, 8);
-  memcpy(out + 16, &n, 8);
+  side_header_write(out, 1, SideHeader{ORDER_ENTRY_WIDTH, 0, {(int64_t)n}});
 }
 // nullptr: a header this build reads (*n filled in); else what is wrong with it
 inline const char *order_header_read(const uint8_t *h, size_t have, uint64_t *n) {
-  if (have < ORDER_HEADER_BYTES) return "truncated order stream";
-  if (memcmp(h, ORDER_MAGIC, 7)) return "is not a scalce order stream";
-  int32_t f[2];
-  memcpy(f, h + 8, 8);
-  if (f[0] != ORDER_ENTRY_WIDTH || f[1] != 0) return "is not a scalce order stream";
-  int64_t v;
-  memcpy(&v, h + 16, 8);
-  if (v < 0 || v > 0xFFFFFFFFll) return "is not a scalce order stream";
-  *n = (uint64_t)v;
+  SideHeader f;
+  const SideHeaderState st = side_header_read(h, have, 1, &f);
+  if (st == SIDE_SHORT) return "truncated order stream";
+  if (st == SIDE_NOT_OURS || f.width != ORDER_ENTRY_WIDTH || f.param != 0 || f.count[0] < 0 || f.count[0] > 0xFFFFFFFFll)
+    return "is not a scalce order stream";
+  *n = (uint64_t)f.count[0];
   return nullptr;
 }
 // the other messages of the stream; `entries` against the `records` the archive holds

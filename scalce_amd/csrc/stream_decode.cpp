@@ -274,18 +274,18 @@ struct Session {
     S.window_text_bytes = W;
     u64 rec_min = 0, rec_max = 0;
     // (comment streams: the bound of a record's text grows by the mate's longest entry)
-    const bool com = M[A.m0].has_com;
+    const bool com = M[A.m0].com.open;
     const u64 nmates = (u64)(A.m1 - A.m0 + 1);
     u64 C = 0;
-    for (int m = A.m0; m <= A.m1 && com; m++) C = std::max<u64>(C, M[m].c_longest);
+    for (int m = A.m0; m <= A.m1 && com; m++) C = std::max<u64>(C, M[m].com.longest);
     // (plus-line streams: ... and by the longest a '+' line can become: a literal of P - 1 bytes, or the header line's own bound)
     const bool plus = wants_plus();
     u64 PE = 0;
-    for (int m = A.m0; m <= A.m1 && plus; m++) PE = std::max<u64>(PE, M[m].p_longest);
+    for (int m = A.m0; m <= A.m1 && plus; m++) PE = std::max<u64>(PE, M[m].plus.longest);
     for (int m = A.m0; m <= A.m1; m++) {
-      const u64 header = 255 + 32 + (com ? M[m].c_longest : 0);
+      const u64 header = 255 + 32 + (com ? M[m].com.longest : 0);
       rec_min += A.rec_budget(m);
-      rec_max += rec_fixed(m) + header + (plus ? std::max<u64>(M[m].p_longest ? M[m].p_longest - 1 : 0, header) : 0);
+      rec_max += rec_fixed(m) + header + (plus ? std::max<u64>(M[m].plus.longest ? M[m].plus.longest - 1 : 0, header) : 0);
     }
     R = std::max<u64>(1, W / rec_min);
     D = std::min<u64>(R, (u64)scalce_patterns_count(ctx) + 2);
@@ -390,8 +390,8 @@ struct Session {
     Decoder &d = x.d;
     if (!A.qual || x.no_ac || x.q_empty) return SCALCE_OK;
     std::vector<u32> table(TABLE_BYTES / 4);
-    if (x.q.read_into(reinterpret_cast<u8 *>(table.data()), TABLE_BYTES) != TABLE_BYTES) return fail(SCALCE_ERR_FORMAT, m, 2, 0, "(ERROR) truncated quality table");
-    if (!x.q.get(x.total_syms)) return walk(truncated(WF, m, 2));
+    if (x.q.read_into(reinterpret_cast<u8 *>(table.data()), TABLE_BYTES) != TABLE_BYTES) return fail(SCALCE_ERR_FORMAT, m, ST_QUALITY, 0, "(ERROR) truncated quality table");
+    if (!x.q.get(x.total_syms)) return walk(truncated(WF, m, ST_QUALITY));
     x.records_left = x.total_syms / (u64)x.L;
     x.syms_left = x.total_syms;
     x.frames_left = (x.total_syms + FRAME - 1) / FRAME;
@@ -442,20 +442,20 @@ struct Session {
     u64 at = 0;
     u32 k = 0;
     while (k < d.G && k < x.frames_left) {
-      if (!x.q.need(4)) return walk(truncated(WF, m, 2));
+      if (!x.q.need(4)) return walk(truncated(WF, m, ST_QUALITY));
       u32 sz;  // (looked at, not taken: a frame that does not fit the staging any more opens the next batch)
       memcpy(&sz, x.q.ptr(), 4);
       if (at + 4 + (u64)sz > d.coded_cap - 64) {
         if (k) break;
-        return fail(SCALCE_ERR_FORMAT, m, 2, 0, "(ERROR) a coded block of %u bytes: not a quality stream of this coder", sz);
+        return fail(SCALCE_ERR_FORMAT, m, ST_QUALITY, 0, "(ERROR) a coded block of %u bytes: not a quality stream of this coder", sz);
       }
       memcpy(h_coded + at, &sz, 4);
       x.q.skip(4);
-      if (x.q.read_into(h_coded + at + 4, sz) != sz) return walk(truncated(WF, m, 2));
+      if (x.q.read_into(h_coded + at + 4, sz) != sz) return walk(truncated(WF, m, ST_QUALITY));
       at += 4 + (u64)sz;
       k++;
     }
-    if (x.q.bad) return walk(read_error(WF, m, 2));
+    if (x.q.bad) return walk(read_error(WF, m, ST_QUALITY));
     const u64 nsym = std::min<u64>((u64)k * FRAME, x.syms_left);
     // (the first batch of a range begins with x.drop symbols of the records in front of it: they are left where they are
     // decoded and the windows begin behind them, so the carry counts from there)
@@ -496,7 +496,7 @@ struct Session {
       float ms = 0;
       SD_HIP(hipEventElapsedTime(&ms, d.t_dec0[par], d.t_dec1[par]));
       S.decode_s += 1e-3 * ms;
-      if (d.h_bad.as<u32>()[par]) return walk(truncated(WF, m, 2));
+      if (d.h_bad.as<u32>()[par]) return walk(truncated(WF, m, ST_QUALITY));
     }
   }
 
@@ -508,13 +508,13 @@ struct Session {
     if (e != hipSuccess) hip(e, "a window's text did not come down");
     if (j.kind == Job::STRIPE) X->S.place_wait_s += now_s() - t0;
     if (!failed && j.kind != Job::WINDOW && X->rs[j.slot].h_bad.as<u32>()[0])
-      fail(SCALCE_ERR_FORMAT, A.m0, 4, 0, "(ERROR) %s", order_not_permutation());
+      fail(SCALCE_ERR_FORMAT, A.m0, ST_ORDER, 0, "(ERROR) %s", order_not_permutation());
     if (!failed && j.kind != Job::STRIPE && slot[j.slot].h_cbad.p && slot[j.slot].h_cbad.as<u32>()[0])
-      fail(SCALCE_ERR_FORMAT, A.m0, 5, 0, "internal: a window's entries of the comment stream do not fit its records");
+      fail(SCALCE_ERR_FORMAT, A.m0, ST_COMMENT, 0, "internal: a window's entries of the comment stream do not fit its records");
     if (!failed && j.kind != Job::STRIPE && slot[j.slot].h_pbad.p && slot[j.slot].h_pbad.as<u32>()[0])
-      fail(SCALCE_ERR_FORMAT, A.m0, 7, 0, "(ERROR) %s", plus_malformed());
+      fail(SCALCE_ERR_FORMAT, A.m0, ST_PLUS, 0, "(ERROR) %s", plus_malformed());
     if (!failed && j.kind != Job::STRIPE && slot[j.slot].h_xbad.p && slot[j.slot].h_xbad.as<u32>()[0])
-      fail(SCALCE_ERR_FORMAT, A.m0, 6, 0, "(ERROR) %s", exception_outside());
+      fail(SCALCE_ERR_FORMAT, A.m0, ST_EXCEPTION, 0, "(ERROR) %s", exception_outside());
     return !failed;
   }
   void records_time(const Slot &s) {
@@ -577,7 +577,7 @@ struct Session {
   int order_count(u64 records) {
     char b[200];
     order_count_message(b, sizeof b, X->N, records);
-    return fail(SCALCE_ERR_FORMAT, A.m0, 4, 0, "(ERROR) %s", b);
+    return fail(SCALCE_ERR_FORMAT, A.m0, ST_ORDER, 0, "(ERROR) %s", b);
   }
   int spill_error(const char *what) {
     return fail(SCALCE_ERR_FORMAT, -1, -1, 0, "(ERROR) cannot %s a spill file in %s: %s", what, X->dir.c_str(), strerror(errno));
@@ -588,9 +588,9 @@ struct Session {
     x.o = Src();
     x.o.open(x.P.order_rd[m], nullptr, x.P.order_user[m], &S.read_wait_s, &x.delivered, &x.skipped);
     const bool whole = x.o.need(ORDER_HEADER_BYTES);
-    if (x.o.bad) return walk(read_error(WF, m, 4));
+    if (x.o.bad) return walk(read_error(WF, m, ST_ORDER));
     if (const char *why = order_header_read(x.o.ptr(), whole ? ORDER_HEADER_BYTES : 0, &x.N))
-      return fail(SCALCE_ERR_FORMAT, m, 4, 0, "(ERROR) %s", why);
+      return fail(SCALCE_ERR_FORMAT, m, ST_ORDER, 0, "(ERROR) %s", why);
     x.o.skip(ORDER_HEADER_BYTES);
     x.taken = 0;
     for (SpillFile *f : {&x.f_text, &x.f_rec}) {
@@ -613,7 +613,7 @@ struct Session {
     const u32 *idx = q.h_gidx.as<u32>();
     const u64 text_at = x.table.text_bytes, rec_at = x.table.records;
     if (off[j.n] - off[0] != j.nbytes || !x.table.add_window(q.h_counts.as<u32>(), off, j.n)) {
-      fail(SCALCE_ERR_FORMAT, A.m0, 4, 0, "internal: a window's stripes do not add up");
+      fail(SCALCE_ERR_FORMAT, A.m0, ST_ORDER, 0, "internal: a window's stripes do not add up");
       return;
     }
     x.words.resize(j.n);
@@ -634,7 +634,7 @@ struct Session {
       const u64 base = s * x.R, expect = std::min(x.R, x.N - base);
       u64 bytes = 0;
       const u64 m = x.table.take_stripe(pieces, &bytes);
-      if (m != expect) return fail(SCALCE_ERR_FORMAT, A.m0, 4, 0, "(ERROR) %s", order_not_permutation());
+      if (m != expect) return fail(SCALCE_ERR_FORMAT, A.m0, ST_ORDER, 0, "(ERROR) %s", order_not_permutation());
       if (bytes + 64 > cap_text || m > x.rcap) return fail(SCALCE_ERR_CAPACITY, -1, -1, 0, "internal: a stripe of %llu bytes of text", (unsigned long long)bytes);
       const int si = (int)(s & 1);
       if (!wait_slot(si)) return F.rc;
@@ -651,7 +651,7 @@ struct Session {
       u32 *idx = q.h_ord.as<u32>();
       off[0] = 0;
       for (u64 k = 0; k < m; k++) { idx[k] = record_entry(x.words[k]); off[k + 1] = off[k] + record_size(x.words[k]); }
-      if (off[m] != bytes) return fail(SCALCE_ERR_FORMAT, A.m0, 4, 0, "internal: a stripe's record sizes do not add up");
+      if (off[m] != bytes) return fail(SCALCE_ERR_FORMAT, A.m0, ST_ORDER, 0, "internal: a stripe's record sizes do not add up");
       SD_HIP(hipMemcpyAsync(sl.d_text.p, sl.h_text.p, bytes, hipMemcpyHostToDevice, s_main));
       SD_HIP(hipMemcpyAsync(sl.d_roff.p, off, 8 * (m + 1), hipMemcpyHostToDevice, s_main));
       SD_HIP(hipMemcpyAsync(q.d_ord.p, idx, 4 * m, hipMemcpyHostToDevice, s_main));
@@ -680,15 +680,15 @@ struct Session {
     const int m0 = A.m0, m1 = A.m1;
     u64 first = RG.first_record, got = 0;
     if (A.known) { RS.total_records = M[m0].records_left; first = std::min(first, M[m0].records_left); }
-    for (int m = m0; m <= m1 && A.names; m++) SD_TRY(took(A.pass_names(m, first, got, WF), m, 1, got, first));
+    for (int m = m0; m <= m1 && A.names; m++) SD_TRY(took(A.pass_names(m, first, got, WF), m, ST_NAME, got, first));
     for (int m = m0; m <= m1; m++)  // -A: rows of L bytes
-      if (A.qual && M[m].no_ac) SD_TRY(took(A.quality_rows(m, first, nullptr, got, WF), m, 2, got, first));
-    for (int m = m0; m <= m1; m++) SD_TRY(took(A.reads(m, first, nullptr, got, WF), m, 0, got, first));
+      if (A.qual && M[m].no_ac) SD_TRY(took(A.quality_rows(m, first, nullptr, got, WF), m, ST_QUALITY, got, first));
+    for (int m = m0; m <= m1; m++) SD_TRY(took(A.reads(m, first, nullptr, got, WF), m, ST_READ, got, first));
     for (int m = m0; m <= m1; m++) {  // coded qualities: whole frames by their size words, then the symbols in front of the record
       Mate &x = M[m];
       if (!x.d.dec) continue;
       u64 pl[4];
-      if (range_plan_quality(x.L, first, RG.nrecords, x.total_syms, pl)) return fail(SCALCE_ERR_ARG, m, 2, 0, "internal: the range's plan");
+      if (range_plan_quality(x.L, first, RG.nrecords, x.total_syms, pl)) return fail(SCALCE_ERR_ARG, m, ST_QUALITY, 0, "internal: the range's plan");
       SD_TRY(walk(A.pass_frames(m, pl[0], WF)));
       RS.frames_passed[m] = pl[0];
       x.frames_left = pl[1];
@@ -696,11 +696,11 @@ struct Session {
       x.syms_left = pl[2] + pl[3];
     }
     for (int m = m0; m <= m1; m++)  // the length stream: entries of one width
-      if (M[m].has_len) SD_TRY(took(A.lengths(m, first, nullptr, got, WF), m, 3, got, first));
+      if (M[m].has_len) SD_TRY(took(A.lengths(m, first, nullptr, got, WF), m, ST_LENGTH, got, first));
     for (int m = m0; m <= m1; m++)  // the comment stream: entries by their newlines
-      if (M[m].has_com) SD_TRY(took(A.pass_comments(m, first, got, WF), m, 5, got, first));
+      if (M[m].com.open) SD_TRY(took(A.pass_text(m, M[m].com, first, got, WF), m, ST_COMMENT, got, first));
     for (int m = m0; m <= m1; m++)  // the plus-line stream: the same
-      if (M[m].has_plus) SD_TRY(took(A.pass_plus(m, first, got, WF), m, 7, got, first));
+      if (M[m].plus.open) SD_TRY(took(A.pass_text(m, M[m].plus, first, got, WF), m, ST_PLUS, got, first));
     for (int m = m0; m <= m1; m++) {
       Mate &x = M[m];
       x.first = first;
@@ -730,7 +730,7 @@ struct Session {
       NamesDst to[2] = {{h_in + M[m0].o_names, reinterpret_cast<u64 *>(h_in + M[m0].o_noff), M[m0].cap_names},
                                      {h_in + M[m1].o_names, reinterpret_cast<u64 *>(h_in + M[m1].o_noff), M[m1].cap_names}};
       CommentsDst cd{slot[w.si].h_com.as<u8>(), cap_com};
-      w.com = M[m0].has_com;
+      w.com = M[m0].com.open;
       PlusDst pd{slot[w.si].h_plus.as<u8>(), cap_plus};
       w.plus = wants_plus();
       const int rc = A.take_names(to, ncap, W, w.n, w.nb, WF, w.com ? &cd : nullptr, w.plus ? &pd : nullptr);
@@ -758,7 +758,7 @@ struct Session {
         Walk::PlusPeek pk;
         const int e = A.plus_peek(header, pk, WF);
         if (e == 1 && !A.known) break;  // (the stream ends with the archive, whose other streams say where that is)
-        if (e) return walk(e == 1 ? truncated(WF, m0, 7) : e);
+        if (e) return walk(e == 1 ? truncated(WF, m0, ST_PLUS) : e);
         if (n && (t + rec + pk.grow > W || !A.plus_fits(pd, pk))) break;
         A.plus_commit(pd, pk);
         t += rec + pk.grow;
@@ -776,10 +776,10 @@ struct Session {
     u8 *h_in = s.h_in.as<u8>();
     u64 got = 0;
     for (int m = m0; m <= m1 && w.n; m++)  // -A: the q - offset rows as they are
-      if (A.qual && M[m].no_ac) SD_TRY(took(A.quality_rows(m, w.n, h_in + M[m].o_qual, got, WF), m, 2, got, w.n));
+      if (A.qual && M[m].no_ac) SD_TRY(took(A.quality_rows(m, w.n, h_in + M[m].o_qual, got, WF), m, ST_QUALITY, got, w.n));
     for (int m = m0; m <= m1 && w.n; m++) {
       ReadsDst to{h_in + M[m].o_reads, reinterpret_cast<scalce_fq_bucket *>(h_in + M[m].o_dir), M[m].cap_slice, (u32)D};
-      SD_TRY(took(A.reads(m, w.n, &to, got, WF), m, 0, got, w.n));
+      SD_TRY(took(A.reads(m, w.n, &to, got, WF), m, ST_READ, got, w.n));
       w.ndir[m - m0] = to.ndir;
       w.slice[m - m0] = to.bytes;
     }
@@ -788,21 +788,21 @@ struct Session {
     w.strip = M[m0].has_len;
     if (w.strip) {
       Mate &x = M[m0];
-      SD_TRY(took(A.lengths(m0, w.n, s.h_len.as<u8>(), got, WF), m0, 3, got, w.n));
+      SD_TRY(took(A.lengths(m0, w.n, s.h_len.as<u8>(), got, WF), m0, ST_LENGTH, got, w.n));
       const u64 sum = len_entries_sum(s.h_len.as<u8>(), w.n, x.l_width, x.L);
-      if (sum == ~0ull) return fail(SCALCE_ERR_FORMAT, m0, 3, 0, "(ERROR) the length stream holds an entry above the read length %d", x.L);
+      if (sum == ~0ull) return fail(SCALCE_ERR_FORMAT, m0, ST_LENGTH, 0, "(ERROR) the length stream holds an entry above the read length %d", x.L);
       w.cut = 2 * sum;
     }
     if (X) {  // the window's entries of the order stream
       const u64 want = 4 * w.n;
-      if (X->o.read_into(X->rs[w.si].h_ord.as<u8>(), want) != want) return walk(short_stream(WF, m0, 4, X->o));
+      if (X->o.read_into(X->rs[w.si].h_ord.as<u8>(), want) != want) return walk(short_stream(WF, m0, ST_ORDER, X->o));
       X->taken += w.n;
     }
     // the exception stream: the entries of the window's records, per mate (the cursor passes over what lies in front of them)
     w.exc = has_exc[m0];
     for (int m = m0; m <= m1 && w.exc; m++) {
       xents.clear();
-      if (const char *why = xc[m].take(w.first, w.first + w.n, &xents)) return fail(SCALCE_ERR_FORMAT, m, 6, 0, "(ERROR) %s", why);
+      if (const char *why = xc[m].take(w.first, w.first + w.n, &xents)) return fail(SCALCE_ERR_FORMAT, m, ST_EXCEPTION, 0, "(ERROR) %s", why);
       const int i = m - m0;
       w.nexc[i] = xents.size();
       if (8 * w.nexc[i] + 64 > s.h_exc[i].cap) {  // (the slot is idle: its last window is written)
@@ -850,7 +850,7 @@ struct Session {
   // the plus-line streams are put back: there are some, the records that go out have a third line, and not every line was bare
   bool wants_plus() const {
     bool any = false;
-    for (int m = A.m0; m <= A.m1; m++) any = any || (M[m].has_plus && M[m].p_longest);
+    for (int m = A.m0; m <= A.m1; m++) any = any || (M[m].plus.open && M[m].plus.longest);
     return A.qual && any;
   }
   // records -> text, mate by mate, behind the upload; then the entries come back (comments) and the pad goes (variable-length)
@@ -966,7 +966,7 @@ struct Session {
     SD_TRY(walk(A.reads_at_end(more, WF)));
     if (more < 0) return SCALCE_OK;
     if (X && X->taken == X->N)
-      return fail(SCALCE_ERR_FORMAT, A.m0, 4, 0, "(ERROR) order stream holds %llu entries, the archive more records", (unsigned long long)X->N);
+      return fail(SCALCE_ERR_FORMAT, A.m0, ST_ORDER, 0, "(ERROR) order stream holds %llu entries, the archive more records", (unsigned long long)X->N);
     return walk(A.holds_more(more, WF));
   }
 
@@ -981,19 +981,19 @@ struct Session {
     A.known = M[m0].records_left != UNKNOWN;
     if (X && A.known && X->N != M[m0].records_left) return order_count(M[m0].records_left);
     for (int m = m0; m <= m1; m++)
-      if (M[m].has_com && A.known && M[m].c_total != M[m0].records_left) return walk(A.comment_count(m, M[m].c_total, M[m0].records_left, WF));
+      if (M[m].com.open && A.known && M[m].com.total != M[m0].records_left) return walk(A.text_count(m, M[m].com, M[m].com.total, M[m0].records_left, WF));
     for (int m = m0; m <= m1; m++)
-      if (M[m].has_plus && A.known && M[m].p_total != M[m0].records_left) return walk(A.plus_count(m, M[m].p_total, M[m0].records_left, WF));
+      if (M[m].plus.open && A.known && M[m].plus.total != M[m0].records_left) return walk(A.text_count(m, M[m].plus, M[m].plus.total, M[m0].records_left, WF));
     for (int m = m0; m <= m1; m++) {
       if (!has_exc[m]) continue;
       char b[200];
       if (A.known && xc[m].records != M[m0].records_left) {
         exception_count_message(b, sizeof b, xc[m].records, M[m0].records_left);
-        return fail(SCALCE_ERR_FORMAT, m, 6, 0, "(ERROR) %s", b);
+        return fail(SCALCE_ERR_FORMAT, m, ST_EXCEPTION, 0, "(ERROR) %s", b);
       }
       if (xc[m].read_len != (uint32_t)M[m].L) {
         exception_length_message(b, sizeof b, xc[m].read_len, (uint32_t)M[m].L);
-        return fail(SCALCE_ERR_FORMAT, m, 6, 0, "(ERROR) %s", b);
+        return fail(SCALCE_ERR_FORMAT, m, ST_EXCEPTION, 0, "(ERROR) %s", b);
       }
     }
     SD_TRY(pass_over());
@@ -1012,9 +1012,9 @@ struct Session {
     SD_TRY(check_end());
     // (an archive that does not say how many records it holds, read to its end: the stream must have ended with it)
     for (int m = m0; m <= m1; m++)
-      if (M[m].has_com && M[m0].range_left == UNKNOWN && M[m].c_taken != M[m].c_total) return walk(A.comment_count(m, M[m].c_total, M[m].c_taken, WF));
+      if (M[m].com.open && M[m0].range_left == UNKNOWN && M[m].com.taken != M[m].com.total) return walk(A.text_count(m, M[m].com, M[m].com.total, M[m].com.taken, WF));
     for (int m = m0; m <= m1; m++)
-      if (M[m].has_plus && M[m].p_longest && M[m0].range_left == UNKNOWN && M[m].p_taken != M[m].p_total) return walk(A.plus_count(m, M[m].p_total, M[m].p_taken, WF));
+      if (M[m].plus.open && M[m].plus.longest && M[m0].range_left == UNKNOWN && M[m].plus.taken != M[m].plus.total) return walk(A.text_count(m, M[m].plus, M[m].plus.total, M[m].plus.taken, WF));
     drain();
     if (failed) return F.rc;
     for (int m = m0; m <= m1; m++) free_decoder(m);
@@ -1038,23 +1038,23 @@ struct Session {
       if (M[m].q_empty) {
         bool has = false;
         SD_TRY(walk(A.more_reads(m, 1, has, WF)));
-        if (has) return fail(SCALCE_ERR_FORMAT, m, 2, 1, "holds no qualities: the archive was made with -Q or -f; decompress it with -Q");
+        if (has) return fail(SCALCE_ERR_FORMAT, m, ST_QUALITY, 1, "holds no qualities: the archive was made with -Q or -f; decompress it with -Q");
         M[m].records_left = 0;
       }
     for (int m = 0; m < P.mates; m++) {  // the comment streams: header, then one entry per record
       if (!CM.com_rd[m]) continue;
-      if (!A.names) return fail(SCALCE_ERR_ARG, m, 5, 0, "(ERROR) a comment stream goes with stored names: the archive holds none (or -n sets them aside)");
-      SD_TRY(walk(A.comments_open(m, CM.com_rd[m], CM.com_user[m], &S.read_wait_s, WF)));
+      if (!A.names) return fail(SCALCE_ERR_ARG, m, ST_COMMENT, 0, "(ERROR) a comment stream goes with stored names: the archive holds none (or -n sets them aside)");
+      SD_TRY(walk(A.text_open(m, M[m].com, CM.com_rd[m], CM.com_user[m], &S.read_wait_s, WF)));
     }
     for (int m = 0; m < P.mates; m++) {  // the plus-line streams: header, then one entry per record (none when P = 0)
       if (!PL.plus_rd[m]) continue;
-      if (!A.qual) return fail(SCALCE_ERR_ARG, m, 7, 0, "(ERROR) a plus-line stream goes with four-line records: -Q writes two");
-      SD_TRY(walk(A.plus_open(m, PL.plus_rd[m], PL.plus_user[m], &S.read_wait_s, WF)));
+      if (!A.qual) return fail(SCALCE_ERR_ARG, m, ST_PLUS, 0, "(ERROR) a plus-line stream goes with four-line records: -Q writes two");
+      SD_TRY(walk(A.text_open(m, M[m].plus, PL.plus_rd[m], PL.plus_user[m], &S.read_wait_s, WF)));
     }
     for (int m = 0; m < P.mates; m++) {  // the exception streams: header, then the entries in ascending order
       if (!EX.exc_rd[m]) continue;
       xc[m].start(EX.exc_rd[m], EX.exc_user[m]);
-      if (const char *why = xc[m].read_header()) return fail(SCALCE_ERR_FORMAT, m, 6, 0, "(ERROR) %s", why);
+      if (const char *why = xc[m].read_header()) return fail(SCALCE_ERR_FORMAT, m, ST_EXCEPTION, 0, "(ERROR) %s", why);
       has_exc[m] = true;
     }
     for (Stream *s : {&s_up, &s_main, &s_dec, &s_down}) SD_HIP(s->create());

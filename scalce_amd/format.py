@@ -58,6 +58,21 @@ def write_archive(prefix, batch, phred_offset, library=None, gz=False):
                 f.write(pack_lengths(L, batch.output(host.OUT_LENGTHS, m, np.uint16)))
 
 
+def _side_header(width, param, *counts):
+    """The header our side files share: magic, int32 entry width, int32 a parameter of the stream's own, then its int64 counts."""
+    return MAGIC + struct.pack("<ii%dq" % len(counts), width, param, *counts)
+
+
+def _side_fields(data, counts, truncated, not_ours):
+    """(width, param, *counts) of a side stream's header; ValueError with `truncated` or `not_ours`, the stream's own words."""
+    size = 16 + 8 * counts
+    if len(data) < size:
+        raise ValueError(truncated)
+    if data[:7] != MAGIC[:7]:
+        raise ValueError(not_ours)
+    return struct.unpack("<ii%dq" % counts, data[8:size])
+
+
 def length_entry_width(read_len):
     """Bytes per entry of a .scalcel stream for reads of up to read_len bases."""
     return 1 if read_len <= 255 else 2
@@ -69,16 +84,12 @@ def pack_lengths(read_len, pad):
     if pad.size and (pad.min() < 0 or pad.max() > read_len):
         raise ValueError("an entry of a length stream lies in 0 .. read length")
     width = length_entry_width(read_len)
-    return MAGIC + struct.pack("<ii", width, read_len) + pad.astype("<u1" if width == 1 else "<u2").tobytes()
+    return _side_header(width, read_len) + pad.astype("<u1" if width == 1 else "<u2").tobytes()
 
 
 def unpack_lengths(data):
     """(read_len, read_len - length per record) of the bytes of a .scalcel stream (out of its container)."""
-    if len(data) < 16:
-        raise ValueError("truncated length stream")
-    if data[:7] != MAGIC[:7]:
-        raise ValueError("not a scalce length stream")
-    width, read_len = struct.unpack("<ii", data[8:16])
+    width, read_len = _side_fields(data, 0, "truncated length stream", "not a scalce length stream")
     if read_len <= 0 or read_len > 65535 or width != length_entry_width(read_len):
         raise ValueError("length stream: entry width does not fit its read length")
     if (len(data) - 16) % width:
@@ -104,16 +115,14 @@ def pack_plus(entries):
         if e and e != b"=" and not (e[:1] == b"'" and len(e) > 1):
             raise ValueError("plus-line stream: malformed entry")
     longest = max((len(e) for e in entries), default=0)
-    return MAGIC + struct.pack("<iiq", 0, longest, len(entries)) + (b"".join(e + b"\n" for e in entries) if longest else b"")
+    return _side_header(0, longest, len(entries)) + (b"".join(e + b"\n" for e in entries) if longest else b"")
 
 
 def unpack_plus(data):
     """The entries of the bytes of a .scalcep stream (out of its container); ValueError with the library's message."""
     data = bytes(data)
-    if len(data) < PLUS_HEADER_BYTES:
-        raise ValueError("truncated plus-line stream")
-    width, longest, n = struct.unpack("<iiq", data[8:24])
-    if data[:7] != MAGIC[:7] or width != 0 or longest < 0 or longest > PLUS_MAX_ENTRY or n < 0 or n > 0xFFFFFFFF:
+    width, longest, n = _side_fields(data, 1, "truncated plus-line stream", "is not a scalce plus-line stream")
+    if width != 0 or longest < 0 or longest > PLUS_MAX_ENTRY or n < 0 or n > 0xFFFFFFFF:
         raise ValueError("is not a scalce plus-line stream")
     if longest == 0:
         return [b""] * n
@@ -137,16 +146,14 @@ def pack_digest(kind, texts):
     """The bytes of a .scalced stream: texts = [(bytes, crc32)] of one or two texts."""
     if len(texts) not in (1, 2) or not 0 <= kind <= 6 or kind & 3 == 3:
         raise ValueError("a digest stream holds one or two texts of kind 0, 1, 2 (+ 4)")
-    return MAGIC + struct.pack("<iiq", DIGEST_ENTRY_WIDTH, kind, len(texts)) + b"".join(struct.pack("<QII", n, crc, 0) for n, crc in texts)
+    return _side_header(DIGEST_ENTRY_WIDTH, kind, len(texts)) + b"".join(struct.pack("<QII", n, crc, 0) for n, crc in texts)
 
 
 def unpack_digest(data):
     """(kind, [(bytes, crc32)]) of the bytes of a .scalced stream (out of its container); ValueError with the library's message."""
     data = bytes(data)
-    if len(data) < DIGEST_HEADER_BYTES:
-        raise ValueError("truncated digest stream")
-    width, kind, t = struct.unpack("<iiq", data[8:24])
-    if data[:7] != MAGIC[:7] or width != DIGEST_ENTRY_WIDTH or not 0 <= kind <= 6 or kind & 3 == 3 or t not in (1, 2):
+    width, kind, t = _side_fields(data, 1, "truncated digest stream", "is not a scalce digest stream")
+    if width != DIGEST_ENTRY_WIDTH or not 0 <= kind <= 6 or kind & 3 == 3 or t not in (1, 2):
         raise ValueError("is not a scalce digest stream")
     if len(data) < DIGEST_HEADER_BYTES + DIGEST_ENTRY_WIDTH * t:
         raise ValueError("truncated digest stream")

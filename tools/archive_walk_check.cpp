@@ -1,6 +1,6 @@
 // archive_walk_check.cpp -- the walk over an archive's streams (scalce_amd/csrc/archive_walk.hpp: headers, mate 1's buckets,
-// one function per stream that moves it on by n records into a destination or to nowhere, names, the hop over coded frames)
-// on its own: a program for AddressSanitizer, no device, no HIP.
+// one function per stream that moves it on by n records into a destination or to nowhere, names, the entries of the comment
+// and plus-line streams that go with them, the hop over coded frames) on its own: a program for AddressSanitizer, no device, no HIP.
 //   g++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all tools/archive_walk_check.cpp -o /tmp/awc && /tmp/awc
 // The streams are built in memory and come through callbacks that hand out one byte, or odd-sized pieces; what the walk must
 // make of them is written out here by hand (bytes, directory entries, and the literal text of every failure), and every
@@ -20,7 +20,7 @@ typedef std::vector<u8> Bytes;
 #define CHECK(x) do { if (!(x)) { fprintf(stderr, "FAILED %s:%d: %s\n", __FILE__, __LINE__, #x); exit(1); } } while (0)
 
 // ---- the streams behind their callbacks ----------------------------------------------------------------------------------------
-enum Read { ONE_BYTE, ODD_PIECES };
+enum Read { ONE_BYTE, ODD_PIECES, SEVEN_BYTES, EVERYTHING };
 enum Skip { NO_SKIP, EXACT, SHORT };
 struct Feed {
   Bytes bytes;
@@ -33,10 +33,10 @@ struct Feed {
     static const size_t odd[5] = {3, 7, 1, 13, 5};
     CHECK(cap > 0);
     if (f.calls++ == f.error_call) return -1;
-    size_t k = f.rd == ONE_BYTE ? 1 : odd[f.calls % 5];
+    size_t k = f.rd == ONE_BYTE ? 1 : f.rd == SEVEN_BYTES ? 7 : f.rd == EVERYTHING ? (size_t)cap : odd[f.calls % 5];
     k = std::min<size_t>(std::min<size_t>(k, cap), f.bytes.size() - f.at);
     std::unique_ptr<u8[]> piece(new u8[k ? k : 1]);  // (what the callback writes is all it may write)
-    memcpy(piece.get(), f.bytes.data() + f.at, k);
+    if (k) memcpy(piece.get(), f.bytes.data() + f.at, k);  // (a stream cut to nothing has no bytes to point at)
     memcpy(dst, piece.get(), k);
     f.at += k;
     return (int64_t)k;
@@ -69,8 +69,8 @@ static Bytes length_header(int32_t width, int32_t L) { Bytes b; put(b, "scalce22
 
 // an archive: its streams, and the walk opened on them
 struct Arc {
-  Feed r[2], n[2], q[2], l[2];
-  bool has_l = false;
+  Feed r[2], n[2], q[2], l[2], c[2], p[2];
+  bool has_l = false, has_c = false, has_p = false;  // the length, comment and plus-line streams
   int mates = 1, interleave = 0;
   ArcMate am[2];
   Walk w;
@@ -81,7 +81,7 @@ struct Arc {
     for (int m = 0; m < 2; m++) { r[m].bytes = reads_header(L, no_ac); n[m].bytes = names_of_library(); q[m].bytes = quality_header(); }
   }
   void feed(Read rd, Skip sk) {
-    for (Feed *s : {r, n, q, l})
+    for (Feed *s : {r, n, q, l, c, p})
       for (int m = 0; m < 2; m++) { s[m].rd = rd; s[m].sk = sk; }
   }
   int open() {
@@ -102,8 +102,14 @@ struct Arc {
     }
     w.cores.count = 2; w.cores.length = core_length; w.cores.string = core_string;
     w.m0 = 0; w.m1 = interleave ? 1 : 0;
-    return w.headers(P, RG, rd, user, &wait, RS, f);
+    int rc = w.headers(P, RG, rd, user, &wait, RS, f);
+    for (int m = 0; m < mates && !rc && has_c; m++) rc = w.text_open(m, am[m].com, Feed::read_cb, &c[m], &wait, f);
+    for (int m = 0; m < mates && !rc && has_p; m++) rc = w.text_open(m, am[m].plus, Feed::read_cb, &p[m], &wait, f);
+    return rc;
   }
+  // the text-entry stream of a kind, and its feed
+  TextStream &text(bool plus, int m = 0) { return plus ? am[m].plus : am[m].com; }
+  Feed &text_feed(bool plus, int m = 0) { return plus ? p[m] : c[m]; }
 };
 
 static void failed_with(int rc, const Failure &f, int mate, int stream, int wants_file, const char *msg, int line) {
@@ -362,6 +368,330 @@ static void names() {
   }
 }
 
+// ---- the text-entry streams: comments (stream 5) and plus lines (stream 7), through the functions `scalce -d` walks them with ----
+typedef std::vector<std::string> Entries;
+static const Read STEPS[3] = {ONE_BYTE, SEVEN_BYTES, EVERYTHING};
+struct Noun { int stream; const char *truncated, *too_long, *read_error; };
+static const Noun NOUN[2] = {
+    {5, "(ERROR) truncated comment stream", "(ERROR) comment stream: an entry is longer than its header says", "read error on the comment stream"},
+    {7, "(ERROR) truncated plus-line stream", "(ERROR) plus-line stream: an entry is longer than its header says", "read error on the plus-line stream"}};
+// the stream of `entries` (longest: what its header says instead of the truth); a plus-line stream of empty entries is its header
+static Bytes text_stream(bool plus, const Entries &entries, int64_t longest = -1) {
+  uint32_t c = 0;
+  for (const std::string &e : entries) c = std::max<uint32_t>(c, (uint32_t)e.size());
+  Bytes out(COMMENT_HEADER_BYTES);
+  (plus ? plus_header_write : comment_header_write)(out.data(), longest < 0 ? c : (uint32_t)longest, entries.size());
+  if (plus && !c && longest <= 0) return out;
+  for (const std::string &e : entries) { put(out, e.c_str()); out.push_back('\n'); }
+  return out;
+}
+static std::string body_of(const Entries &entries, size_t first, size_t n) {
+  std::string s;
+  for (size_t i = first; i < first + n; i++) s += entries[i] + "\n";
+  return s;
+}
+static Bytes names_of(size_t n) {  // n names of two characters: 3 bytes each, 2 + 16 bytes of a window of reads of 5 bases
+  Bytes b = names_header();
+  for (size_t i = 0; i < n; i++) put(b, name(2, (char)('a' + i % 26)));
+  return b;
+}
+// an archive of one mate (or an interleaved pair) with a stream of the kind per mate, opened
+struct TextArc : Arc {
+  bool plus;
+  TextArc(bool plus_, Read rd, size_t names, const Bytes &m1, const Bytes *m2 = nullptr) : Arc(5), plus(plus_) {
+    (plus ? has_p : has_c) = true;
+    if (m2) { mates = 2; interleave = 1; text_feed(plus, 1).bytes = *m2; }
+    for (int m = 0; m < mates; m++) n[m].bytes = names_of(names);
+    text_feed(plus).bytes = m1;
+    feed(rd, NO_SKIP);
+  }
+  // up to ncap records' (pairs') names and entries, as a window takes them: the entries into a block of exactly `cap` bytes
+  std::unique_ptr<u8[]> got;
+  u64 nbytes = 0, grow = 0;
+  int take(u64 ncap, u64 cap, u64 &cnt, u64 W = (u64)1 << 40) {
+    got.reset(new u8[cap ? cap : 1]);
+    NamesTo t(3 * ncap, ncap);
+    CommentsDst cd{got.get(), cap};
+    PlusDst pd{got.get(), cap};
+    u64 nb[2];
+    const int rc = w.take_names(t.to, ncap, W, cnt, nb, f, plus ? nullptr : &cd, plus ? &pd : nullptr);
+    nbytes = plus ? pd.nbytes : cd.nbytes;
+    grow = pd.grow;
+    return rc;
+  }
+  std::string taken() const { return std::string(got.get(), got.get() + nbytes); }
+};
+
+// every entry of a stream in groups of 1, 2 and all, alternately taken with the records' names and passed over, at every
+// delivery step.  (The cursors this walk replaced were also run with buffers of 1, 5 and 64 bytes, to break entries across
+// refills.  Src has one look-ahead buffer of 1 MiB that grows, so that dimension has no counterpart here: an entry spans
+// refills when it arrives in steps of 1 and 7 bytes, and the entries of 65535 bytes are the longest a stream may hold.)
+static void text_walks(bool plus, const Entries &entries) {
+  const Noun &noun = NOUN[plus];
+  const Bytes data = text_stream(plus, entries);
+  const size_t N = entries.size();
+  uint32_t longest = 0;
+  for (const std::string &e : entries) longest = std::max<uint32_t>(longest, (uint32_t)e.size());
+  for (Read rd : STEPS)
+    for (size_t group : {(size_t)1, (size_t)2, N ? N : (size_t)1}) {
+      TextArc a(plus, rd, N + 1, data);
+      CHECK(a.open() == SCALCE_OK);
+      TextStream &t = a.text(plus);
+      CHECK(t.open && t.total == N && t.longest == longest && t.taken == 0 && t.kind->stream == noun.stream);
+      std::string want;
+      bool skipping = false;
+      for (size_t k = 0; k < N; skipping = !skipping) {
+        const size_t n = std::min(group, N - k);
+        u64 got = ~0ull;
+        if (skipping) {
+          CHECK(a.w.pass_text(0, t, n, got, a.f) == SCALCE_OK && got == n);
+          CHECK(a.w.pass_names(0, n, got, a.f) == SCALCE_OK && got == n);
+        } else {
+          want = body_of(entries, k, n);
+          CHECK(a.take(n, want.size(), got) == SCALCE_OK && got == n && a.taken() == want);  // the entries with their newlines
+        }
+        k += n;
+        CHECK(t.taken == k);
+      }
+      u64 got = ~0ull;
+      CHECK(a.w.pass_text(0, t, 1, got, a.f) == SCALCE_OK && got == 0);  // it ends here, between two entries ...
+      FAILED_WITH(a.take(1, 1, got), a.f, 0, noun.stream, 0, noun.truncated);  // ... where a record that has a name wants one more
+      CHECK(t.taken == N && t.delivered == data.size() && t.skipped == 0);
+      // what the session says when the archive holds another count: up front from the header's, at the end from what was taken
+      const std::string held = std::string(plus ? "(ERROR) plus-line" : "(ERROR) comment") + " stream holds " + std::to_string(N) + " entries, the archive ";
+      FAILED_WITH(a.w.text_count(0, t, t.total, N + 1, a.f), a.f, 0, noun.stream, 0, (held + std::to_string(N + 1) + " records").c_str());
+      FAILED_WITH(a.w.text_count(0, t, t.total, t.taken, a.f), a.f, 0, noun.stream, 0, (held + std::to_string(N) + " records").c_str());
+    }
+}
+
+// a stream of three entries cut at every byte: inside the header the open fails; behind it exactly the entries whose newline
+// survived are given, then the stream is truncated (the cut lies inside an entry) or ends there (between two)
+static void text_cuts(bool plus, const Entries &entries) {
+  const Noun &noun = NOUN[plus];
+  const Bytes whole = text_stream(plus, entries);
+  std::vector<size_t> ends;  // where each entry's newline lies
+  for (size_t i = COMMENT_HEADER_BYTES; i < whole.size(); i++)
+    if (whole[i] == '\n') ends.push_back(i);
+  CHECK(ends.size() == 3 && entries.size() == 3);
+  for (size_t at = 0; at < whole.size(); at++)
+    for (Read rd : STEPS) {
+      TextArc a(plus, rd, 3, cut(whole, at));
+      const int rc = a.open();
+      if (at < COMMENT_HEADER_BYTES) { FAILED_WITH(rc, a.f, 0, noun.stream, 0, noun.truncated); continue; }
+      TextStream &t = a.text(plus);
+      CHECK(rc == SCALCE_OK && t.total == 3 && t.longest == (plus ? 3u : 13u));
+      size_t complete = 0;
+      for (size_t e : ends) complete += e < at ? 1 : 0;
+      for (size_t k = 0; k < complete; k++) {
+        u64 got = ~0ull;
+        const std::string want = entries[k] + "\n";
+        if (k & 1) CHECK(a.w.pass_text(0, t, 1, got, a.f) == SCALCE_OK && got == 1 && a.w.pass_names(0, 1, got, a.f) == SCALCE_OK);
+        else CHECK(a.take(1, want.size(), got) == SCALCE_OK && got == 1 && a.taken() == want);
+      }
+      const size_t begins = complete ? ends[complete - 1] + 1 : COMMENT_HEADER_BYTES;  // the first entry that is not whole
+      const u8 *p = nullptr;
+      size_t len = 0;
+      u64 got = ~0ull;
+      if (at > begins) {
+        FAILED_WITH(a.w.next_text(0, t, p, len, a.f), a.f, 0, noun.stream, 0, noun.truncated);
+        FAILED_WITH(a.w.pass_text(0, t, 3, got, a.f), a.f, 0, noun.stream, 0, noun.truncated);
+      } else {
+        CHECK(a.w.next_text(0, t, p, len, a.f) == 1);
+        CHECK(a.w.pass_text(0, t, 3, got, a.f) == SCALCE_OK && got == 0);
+      }
+      CHECK(t.taken == complete);
+    }
+}
+
+// an entry longer than the header says fails whether its newline is in the buffer or not yet; one of exactly that length passes
+static void text_length_edges(bool plus, const Entries &entries, uint32_t too_short) {
+  const Noun &noun = NOUN[plus];
+  for (Read rd : STEPS) {
+    TextArc a(plus, rd, 3, text_stream(plus, entries, too_short));  // the second entry holds one byte more
+    CHECK(a.open() == SCALCE_OK && a.text(plus).longest == too_short && entries[1].size() == too_short + 1);
+    u64 got = ~0ull;
+    const std::string first = entries[0] + "\n";
+    CHECK(a.take(1, first.size(), got) == SCALCE_OK && got == 1 && a.taken() == first);
+    Failure passed;
+    FAILED_WITH(a.w.pass_text(0, a.text(plus), 2, got, passed), passed, 0, noun.stream, 0, noun.too_long);
+    FAILED_WITH(a.take(2, 64, got), a.f, 0, noun.stream, 0, noun.too_long);
+    TextArc b(plus, rd, 3, text_stream(plus, entries, too_short + 1));
+    CHECK(b.open() == SCALCE_OK && b.w.pass_text(0, b.text(plus), 3, got, b.f) == SCALCE_OK && got == 3 && b.text(plus).taken == 3);
+  }
+}
+
+// a read callback that fails at its first, its second and a later call (one byte per call): in the header twice, then inside
+// the first entry -- what `scalce -d` says of a file it cannot read
+static void text_failed_read(bool plus, const Entries &entries) {
+  const Noun &noun = NOUN[plus];
+  for (int call : {0, 1, (int)COMMENT_HEADER_BYTES + 1})
+    for (int taking = 0; taking < 2; taking++) {
+      TextArc a(plus, ONE_BYTE, 2, text_stream(plus, entries));
+      a.text_feed(plus).error_call = call;
+      const int rc = a.open();
+      if (call < (int)COMMENT_HEADER_BYTES) { FAILED_WITH(rc, a.f, 0, noun.stream, 0, noun.read_error); continue; }
+      u64 got = ~0ull;
+      CHECK(rc == SCALCE_OK);
+      FAILED_WITH(taking ? a.take(2, 64, got) : a.w.pass_text(0, a.text(plus), 2, got, a.f), a.f, 0, noun.stream, 0, noun.read_error);
+    }
+  const Bytes good = text_stream(plus, entries);  // ... and on mate 2's stream, inside its second entry
+  TextArc p(plus, ONE_BYTE, 2, good, &good);
+  p.text_feed(plus, 1).error_call = (int)(COMMENT_HEADER_BYTES + entries[0].size() + 2);
+  u64 got = ~0ull;
+  CHECK(p.open() == SCALCE_OK);
+  FAILED_WITH(p.take(2, 64, got), p.f, 1, noun.stream, 0, noun.read_error);
+}
+
+// what only take_names does with the entries: two mates in one window, a budget and a destination that an entry fills, and
+// mate 2's stream ending before mate 1's
+static void text_windows(bool plus) {
+  const Noun &noun = NOUN[plus];
+  u64 got = ~0ull;
+  {  // a pair's entries land as mate 1's then mate 2's, pair by pair
+    const Entries m1 = plus ? Entries{"=", "", "'x"} : Entries{" a1", "", " a3"}, m2 = plus ? Entries{"", "'yz", "="} : Entries{" b1", " b22", ""};
+    const Bytes s2 = text_stream(plus, m2);
+    std::string want;
+    for (size_t k = 0; k < 3; k++) want += m1[k] + "\n" + m2[k] + "\n";
+    for (Read rd : STEPS) {
+      TextArc a(plus, rd, 3, text_stream(plus, m1), &s2);
+      CHECK(a.open() == SCALCE_OK && a.w.m1 == 1);
+      CHECK(a.take(3, want.size(), got) == SCALCE_OK && got == 3 && a.taken() == want && a.text(plus, 0).taken == 3 && a.text(plus, 1).taken == 3);
+      if (plus) CHECK(a.grow == 2 + 0 + 0 + 2 + 1 + 2);  // (a repeat adds the name's 2 bytes, a literal its bytes behind the class byte)
+    }
+  }
+  {  // a record is its name and 2 L + 6 = 18 bytes of text, and what its entry adds: 7 bytes in the second record here
+    const Entries e = plus ? Entries{"", "'bcdefgh", ""} : Entries{"", " bcdefg", ""};
+    for (u64 W : {(u64)18 + 25 - 1, (u64)18 + 25}) {  // the second record's 25 bytes push the window over W, or just fit
+      TextArc a(plus, ODD_PIECES, 3, text_stream(plus, e)), bare(plus, ODD_PIECES, 3, text_stream(plus, e));
+      CHECK(a.open() == SCALCE_OK && bare.open() == SCALCE_OK);
+      const u64 fits = W == 42 ? 1 : 2;
+      CHECK(a.take(2, 64, got, W) == SCALCE_OK && got == fits && a.taken() == body_of(e, 0, fits) && a.text(plus).taken == fits);
+      NamesTo t(6, 2);  // (the names alone: two records of 18 bytes fit either window -- the entry ends it one record sooner)
+      u64 nb[2];
+      CHECK(bare.w.take_names(t.to, 2, W, got, nb, bare.f) == SCALCE_OK && got == 2);
+    }
+  }
+  {  // a destination whose cap the second record's entry reaches: the window ends in front of it, and nothing of it is taken
+    const Entries e = plus ? Entries{"=", "=", "="} : Entries{" ", " ", " "};
+    for (u64 cap : {(u64)3, (u64)4}) {
+      TextArc a(plus, ODD_PIECES, 3, text_stream(plus, e));
+      CHECK(a.open() == SCALCE_OK);
+      const u64 fits = cap / 2;
+      CHECK(a.take(3, cap, got) == SCALCE_OK && got == fits && a.nbytes == 2 * fits && a.taken() == body_of(e, 0, fits) && a.text(plus).taken == fits);
+    }
+  }
+  {  // mate 2's stream ends between two entries while mate 1's goes on: truncated, on mate 2
+    const Entries m1 = plus ? Entries{"=", "'x"} : Entries{" a", " b"}, m2 = plus ? Entries{"="} : Entries{" c"};
+    const Bytes s2 = text_stream(plus, m2);
+    TextArc a(plus, ODD_PIECES, 2, text_stream(plus, m1), &s2);
+    CHECK(a.open() == SCALCE_OK);
+    FAILED_WITH(a.take(2, 64, got), a.f, 1, noun.stream, 0, noun.truncated);
+  }
+}
+
+// what the plus-line stream alone has
+static void plus_lines() {
+  {  // P = 0: the file is its header.  Nothing is read behind it; N bare entries, then the stream ends
+    const Bytes data = text_stream(true, {"", "", "", ""});
+    CHECK(data.size() == PLUS_HEADER_BYTES);
+    TextArc a(true, EVERYTHING, 4, data);
+    CHECK(a.open() == SCALCE_OK && a.am[0].plus.longest == 0 && a.am[0].plus.total == 4 && a.am[0].plus.no_entries());
+    const int calls = a.p[0].calls;
+    u64 got = ~0ull;
+    CHECK(a.w.pass_text(0, a.am[0].plus, 1, got, a.f) == SCALCE_OK && got == 1);
+    for (int k = 1; k < 4; k++) {
+      const u8 *at = nullptr;
+      size_t len = 0;
+      PlusClass cls = PLUS_MALFORMED;
+      CHECK(a.w.next_plus(0, at, len, cls, a.f) == 0 && len == 1 && at[0] == '\n' && cls == PLUS_BARE);
+      a.w.text_taken(a.am[0].plus, len);
+    }
+    const u8 *at = nullptr;
+    size_t len = 0;
+    PlusClass cls = PLUS_MALFORMED;
+    CHECK(a.w.next_plus(0, at, len, cls, a.f) == 1 && a.am[0].plus.taken == 4);
+    CHECK(a.w.pass_text(0, a.am[0].plus, 2, got, a.f) == SCALCE_OK && got == 0);
+    CHECK(a.p[0].calls == calls && a.am[0].plus.delivered == PLUS_HEADER_BYTES);
+  }
+  {  // every class, as next_plus names it
+    const Entries e = {"", "=", "'a", "'=", "''", "'= x"};
+    const PlusClass want[6] = {PLUS_BARE, PLUS_REPEAT, PLUS_LITERAL, PLUS_LITERAL, PLUS_LITERAL, PLUS_LITERAL};
+    for (Read rd : STEPS) {
+      TextArc a(true, rd, 6, text_stream(true, e));
+      CHECK(a.open() == SCALCE_OK);
+      for (size_t k = 0; k < 6; k++) {
+        const u8 *at = nullptr;
+        size_t len = 0;
+        PlusClass cls = PLUS_MALFORMED;
+        CHECK(a.w.next_plus(0, at, len, cls, a.f) == 0 && cls == want[k] && std::string(at, at + len) == e[k] + "\n");
+        a.w.text_taken(a.am[0].plus, len);
+      }
+    }
+  }
+  // ... and the entries that are of none: '=' with more behind it, a literal of nothing (it would be the bare line), another first byte
+  for (const char *bad : {"=x", "=a", "==", "'", "x", "a", "+r1", "+a", " "})
+    for (Read rd : STEPS) {
+      TextArc a(true, rd, 3, text_stream(true, {"=", bad, ""}, 8));
+      CHECK(a.open() == SCALCE_OK);
+      const u8 *at = nullptr;
+      size_t len = 0;
+      PlusClass cls = PLUS_MALFORMED;
+      u64 got = ~0ull;
+      CHECK(a.w.next_plus(0, at, len, cls, a.f) == 0 && cls == PLUS_REPEAT);
+      a.w.text_taken(a.am[0].plus, len);
+      Failure peeked;
+      FAILED_WITH(a.w.next_plus(0, at, len, cls, peeked), peeked, 0, 7, 0, "(ERROR) plus-line stream: malformed entry");
+      FAILED_WITH(a.w.pass_text(0, a.am[0].plus, 2, got, a.f), a.f, 0, 7, 0, "(ERROR) plus-line stream: malformed entry");
+    }
+  {  // what an entry adds to its record, through plus_peek: header = the header line behind '@', here a name of 10 bytes and a
+     // comment of 7.  A repeat grows the record by both, a literal by its bytes behind the class byte, a bare line by nothing
+    TextArc a(true, SEVEN_BYTES, 3, text_stream(true, {"=", "'abcd", ""}));
+    CHECK(a.open() == SCALCE_OK);
+    const u64 header[2] = {10 + 7, 0}, grows[3] = {17, 4, 0};
+    std::unique_ptr<u8[]> to(new u8[9]);
+    PlusDst pd{to.get(), 9}, small{to.get(), 1};
+    for (int k = 0; k < 3; k++) {
+      Walk::PlusPeek pk;
+      CHECK(a.w.plus_peek(header, pk, a.f) == SCALCE_OK && pk.grow == grows[k] && a.am[0].plus.taken == (u64)k);  // (nothing is consumed yet)
+      CHECK(a.w.plus_fits(pd, pk) && a.w.plus_fits(small, pk) == (k == 2));
+      a.w.plus_commit(pd, pk);
+    }
+    Walk::PlusPeek pk;
+    CHECK(a.w.plus_peek(header, pk, a.f) == 1);
+    CHECK(pd.nbytes == 9 && !memcmp(to.get(), "=\n'abcd\n\n", 9) && pd.grow == 21);
+  }
+  {  // ... and as a window counts it: the comment that take_names puts behind the name is part of what a repeat repeats
+    Arc a(5);
+    a.has_c = a.has_p = true;
+    a.n[0].bytes = names_of(1);
+    a.c[0].bytes = text_stream(false, {" xyz"});
+    a.p[0].bytes = text_stream(true, {"="});
+    CHECK(a.open() == SCALCE_OK);
+    NamesTo t(3, 1);
+    std::unique_ptr<u8[]> cb(new u8[5]), pb(new u8[2]);
+    CommentsDst cd{cb.get(), 5};
+    PlusDst pd{pb.get(), 2};
+    u64 n = ~0ull, nb[2];
+    CHECK(a.w.take_names(t.to, 1, 1 << 20, n, nb, a.f, &cd, &pd) == SCALCE_OK && n == 1);
+    CHECK(cd.nbytes == 5 && !memcmp(cb.get(), " xyz\n", 5) && pd.nbytes == 2 && !memcmp(pb.get(), "=\n", 2) && pd.grow == 2 + 4);
+  }
+}
+
+static void text_streams() {
+  for (int plus = 0; plus < 2; plus++) {
+    const std::vector<Entries> sets = plus ? std::vector<Entries>{{}, {""}, {"="}, {"=", "", "'SRR001666.1 length=36", "'=", "", "=", "''x"},
+                                                                  {"'" + std::string(65534, 'q'), "", "=", "'" + std::string(65534, ' ')}}
+                                           : std::vector<Entries>{{}, {""}, {" "}, {"", " ", " 1:N:0:ATCACG", "", " length=100"},
+                                                                  {std::string(65535, 'q'), "", "x", std::string(65535, ' ')}};
+    for (const Entries &e : sets) text_walks(plus, e);
+    text_cuts(plus, plus ? Entries{"'ab", "", "="} : Entries{" 1:N:0:ATCACG", "", " "});
+    text_length_edges(plus, plus ? Entries{"=", "'abc", ""} : Entries{" ab", " abcd", " a"}, plus ? 3 : 4);
+    text_failed_read(plus, plus ? Entries{"=", "'a"} : Entries{" x", " y"});
+    text_windows(plus);
+  }
+  plus_lines();
+}
+
 // ---- the hop over coded frames ---------------------------------------------------------------------------------------------------
 static void frames() {
   Bytes all = quality_header();  // (behind the header the session takes the table and the symbol count; the hop begins at a size word)
@@ -552,6 +882,7 @@ int main() {
     }
   mate2_and_rows();
   names();
+  text_streams();
   frames();
   malformed();
   puts("archive_walk_check: ok");

@@ -1,5 +1,5 @@
 // cli_host_check.cpp -- the host pieces of the `scalce` tool (scalce_amd/csrc/cli_io.hpp, cli_input.hpp, cli_shares.hpp,
-// cli_sink.hpp) on their own: a program for AddressSanitizer and UBSan, no device, no HIP.
+// cli_sink.hpp, cli_sidefiles.hpp) on their own: a program for AddressSanitizer and UBSan, no device, no HIP.
 //   g++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all tools/cli_host_check.cpp -lz -lpthread -o /tmp/chk && /tmp/chk
 // It works on small files it writes itself, in the directory given as its argument (or one it makes under /tmp), and
 // prints "cli_host_check: ok".
@@ -8,6 +8,7 @@
 #include "../scalce_amd/csrc/cli_input.hpp"
 #include "../scalce_amd/csrc/cli_io.hpp"
 #include "../scalce_amd/csrc/cli_shares.hpp"
+#include "../scalce_amd/csrc/cli_sidefiles.hpp"
 #include "../scalce_amd/csrc/cli_sink.hpp"
 
 #define CHECK(x) do { if (!(x)) { fprintf(stderr, "FAILED %s:%d: %s\n", __FILE__, __LINE__, #x); exit(1); } } while (0)
@@ -374,6 +375,34 @@ static void check_out_file() {
   }
 }
 
+// ---- the side files' headers ----------------------------------------------------------------------------------
+static void check_side_files() {
+  using namespace scalce_host;
+  const std::string path = in_dir("side");
+  CHECK(!side_file_present(path));
+  OutFile f;
+  f.open(path, false);
+  side_file_header<LEN_HEADER_BYTES>(f, len_header_write, 300);
+  side_file_header<ORDER_HEADER_BYTES>(f, order_header_write, (uint64_t)7);
+  side_file_header<COMMENT_HEADER_BYTES>(f, comment_header_write, (uint32_t)13, (uint64_t)4);
+  side_file_header<PLUS_HEADER_BYTES>(f, plus_header_write, (uint32_t)0, (uint64_t)5);
+  side_file_header<EXCEPTION_HEADER_BYTES>(f, exception_header_write, (uint32_t)100, (uint64_t)3, (uint64_t)2);
+  f.close();
+  CHECK(side_file_present(path));
+  Bytes want;  // the five headers, field by field: magic, int32 width, int32 parameter, the int64 counts
+  auto header = [&](int32_t width, int32_t param, std::initializer_list<int64_t> counts) {
+    want.insert(want.end(), {'s', 'c', 'a', 'l', 'c', 'e', '2', '2'});
+    for (int32_t v : {width, param}) want.insert(want.end(), reinterpret_cast<uint8_t *>(&v), reinterpret_cast<uint8_t *>(&v) + 4);
+    for (int64_t v : counts) want.insert(want.end(), reinterpret_cast<uint8_t *>(&v), reinterpret_cast<uint8_t *>(&v) + 8);
+  };
+  header(2, 300, {});
+  header(4, 0, {7});
+  header(0, 13, {4});
+  header(0, 0, {5});
+  header(8, 100, {3, 2});
+  CHECK(want.size() == 16 + 24 + 24 + 24 + 32 && get(path) == want);
+}
+
 // ---- TextSink ----------------------------------------------------------------------------------------------
 static void feed(TextSink &sink, const Fastq &f, int first, int n) {  // records first .. first + n as one window
   std::vector<uint64_t> roff(n + 1);
@@ -422,6 +451,7 @@ int main(int argc, char **argv) {
   check_fd();
   check_place_share();
   check_out_file();
+  check_side_files();
   check_text_sink();
   CHECK(open_descriptors() == before);
   printf("cli_host_check: ok\n");
